@@ -2,6 +2,7 @@
 """bench.py -- scan registrations/sec of the MI355X NDT core (BASELINE.json metric).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload auto|single|mapbuild|batch|large|pyramid]
+                  [--dump-outputs DIR] [--full]
 
 N = 1 (default workload "single" = BASELINE configs[1], the configuration the metric is quoted on):
   a "step" is ONE registration (pcl::Registration::align) of one synthetic 100k-point source scan against
@@ -13,8 +14,8 @@ N > 1 (default workload "mapbuild" = BASELINE configs[3]): 512 source scans of 1
   shared 1M-point target, the scans split over the ranks by toyslam_amd.dist.shard_range, the target grid
   replicated per GPU; a "step" is one lock-step batch registration (ndt_align_batch_device) of every rank's
   share, i.e. 512 registrations.  Registrations of different scans are independent, so there is no collective
-  in the data path; total work is fixed as N grows ("scaling": "strong").  After the timed region the same
-  batch is run once more in the literal north_star form -- every rank steps all 512 Newton / More-Thuente
+  in the data path; total work is fixed as N grows ("scaling": "strong").  With --full, after the timed region the
+  same batch is run once more in the literal north_star form -- every rank steps all 512 Newton / More-Thuente
   state machines, ONE RCCL all-reduce of the zero-padded [512][32] f64 rows per lock-step, issued from C++
   on the library's stream (ndt_comm_*) -- and reported as "lockstep_allreduce".
 
@@ -23,7 +24,11 @@ Launch: the driver starts N > 1 as `python -m torch.distributed.run --nproc-per-
 WORLD_SIZE, this file spawns the N ranks itself (child processes, before anything touches the GPU -- never an
 exec) and relays rank 0's JSON line.
 
-Rank 0 prints ONE JSON line.  Extra legs on rank 0 (outside the timed region):
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line;
+--dump-outputs DIR writes what the timed path returned in its last step (transforms, convergence flags, iteration counts,
+transformation probabilities) as DIR/<name>.npy, float32 or float64 (DIR/<name>_rank<r>.npy at N > 1); the inputs are
+seeded, so two builds can be compared output for output.  Everything else is measured only with --full: the target-build
+and source-upload timings, the registrations_ending_at_T_gt checks, and these legs on rank 0 (outside the timed region):
   roofline     -- average duration of the dominant kernel from HIP events on the library's own stream over a
                   second pass of the same steps; algorithmic bytes = SURVEY 8(d)'s per-evaluation figure x the
                   evaluations the launch served.
@@ -76,13 +81,18 @@ def parse_args(argv=None):
     ap.add_argument("--near-guess", action="store_true",
                     help="--workload large: register from a guess 4 cm / 0.03 deg off T_gt with epsilon 1e-3, 35 iterations -- the "
                          "align(output, guess) path of ndt_rosbag_mapping_node.cpp:130 (tests/golden/large_golden.json: cfgB_near)")
-    ap.add_argument("--lockstep-steps", type=int, default=3, help="N > 1 mapbuild: timed steps of the RCCL lock-step leg")
+    ap.add_argument("--lockstep-steps", type=int, default=3, help="N > 1 mapbuild, --full: timed steps of the RCCL lock-step leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline: target-build timings, roofline / PMC / per-kernel "
+                         "legs, adapter path, node rows, the map-build leg, the CPU baselines, the lock-step leg, recovery of T_gt")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="N = 1 single: do not run the two rocprofv3 --pmc child passes that fill roofline.traffic")
+    ap.add_argument("--no-pmc", action="store_true", help="N = 1 single, --full: do not run the two rocprofv3 --pmc child passes that fill roofline.traffic")
     ap.add_argument("--pmc-child", action="store_true", help="(internal) the short run a --pmc pass wraps: timed steps only, no legs")
     ap.add_argument("--no-bind", action="store_true", help="leave the CPU affinity of the rank alone (default: the cores of the GPU's NUMA node)")
-    ap.add_argument("--no-mapbuild-leg", action="store_true", help="N = 1 single: skip the 512-scan map-build leg")
-    ap.add_argument("--no-lockstep-leg", action="store_true", help="N > 1 mapbuild: skip the RCCL lock-step leg")
+    ap.add_argument("--no-mapbuild-leg", action="store_true", help="N = 1 single, --full: skip the 512-scan map-build leg")
+    ap.add_argument("--no-lockstep-leg", action="store_true", help="N > 1 mapbuild, --full: skip the RCCL lock-step leg")
     ap.add_argument("--backend", default=None, help="torch.distributed backend (default nccl = RCCL; gloo for the selftest)")
     ap.add_argument("--dry-run", action="store_true", help="self-launch only: print the per-rank environment plan and exit")
     ap.add_argument("--selftest-die-rank", type=int, default=-1,
@@ -91,7 +101,12 @@ def parse_args(argv=None):
     ap.add_argument("--rehearse-one-gpu", action="store_true",
                     help="N > 1 ranks that all use GPU 0 and rendezvous over gloo: exercises the sharded workload, the launcher and the "
                          "JSON line on a one-GPU box (RCCL refuses two ranks on one device, so the lock-step leg reports an error)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 # =====================================================================================================
@@ -350,6 +365,18 @@ def near_T_gt(T, T_gt, rot=2e-3, trans=2e-2):
     return bool(np.abs(T[:3, :3] - T_gt[:3, :3]).max() < rot and np.abs(T[:3, 3] - T_gt[:3, 3]).max() < trans)
 
 
+def dump_outputs(directory, arrays, rank=0, world=1):
+    """--dump-outputs: one .npy per array; floating arrays keep their precision (f32 / f64), flags and counts become f64."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    suffix = "_rank%d" % rank if world > 1 else ""
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        np.save(os.path.join(directory, name + suffix + ".npy"), a)
+
+
 def mapbuild_scans(clouds, tgt, lo, hi, n_source):
     """Scans lo..hi-1 of the configs[3] workload (clouds.mapbuild_scan: seeds depend on the scan number only)."""
     scans, T_gts = [], []
@@ -379,7 +406,7 @@ def main():
 
     # N = 1 headline: the counter passes run first, in child processes, while this process has not touched the GPU yet
     pmc = None
-    if world == 1 and workload == "single" and not args.pmc_child and not args.no_pmc:
+    if args.full and world == 1 and workload == "single" and not args.pmc_child and not args.no_pmc:
         try:
             pmc = pmc_traffic_of_headline_kernel(args.set)
         except Exception as e:  # never lose the headline line to an auxiliary leg
@@ -485,29 +512,33 @@ def main():
     t_build_first = time.perf_counter() - t0
     t_build = t_build_dev = t_build_ref = t_build_cloud = t_build_first
     if not args.pmc_child:
-      t_build = median_time(lambda: reg.setInputTarget(tgt))                 # host buffer: H2D over PCIe + grid build
+      if args.full:
+        t_build = median_time(lambda: reg.setInputTarget(tgt))                 # host buffer: H2D over PCIe + grid build
       tgt_dev = torch.from_numpy(np.c_[tgt, np.ones(len(tgt), np.float32)]).cuda()
       torch.cuda.synchronize()
-      t_build_dev = median_time(lambda: reg.setInputTargetDevice(tgt_dev.data_ptr(), len(tgt), 16))  # cloud already in HBM, copied
-      # ... and used where it lies (ndt_set_input_target_device_ref: pcl::Registration keeps a shared pointer, it never copies either)
-      t_build_ref = median_time(lambda: reg.setInputTargetDeviceRef(tgt_dev.data_ptr(), len(tgt)))
-      # ... and from an ndt_cloud (a cloud the library made or uploaded itself keeps its bounding boxes: no box pass, no host round trip)
-      tgt_cloud = reg.uploadCloud(tgt)
-      # (nothing in this call waits for the device -- no box to poll for -- so it is timed as eight builds back to back and one
-      # synchronisation, the way the by-reference builds above pace themselves through their polled boxes)
-      def cloud_builds():
-          for _ in range(8):
-              reg.setInputTargetCloud(tgt_cloud)
-          torch.cuda.synchronize()
-      t_build_cloud = median_time(cloud_builds) / 8
+      tgt_cloud = None
+      if args.full:
+        t_build_dev = median_time(lambda: reg.setInputTargetDevice(tgt_dev.data_ptr(), len(tgt), 16))  # cloud already in HBM, copied
+        # ... and used where it lies (ndt_set_input_target_device_ref: pcl::Registration keeps a shared pointer, it never copies either)
+        t_build_ref = median_time(lambda: reg.setInputTargetDeviceRef(tgt_dev.data_ptr(), len(tgt)))
+        # ... and from an ndt_cloud (a cloud the library made or uploaded itself keeps its bounding boxes: no box pass, no host round trip)
+        tgt_cloud = reg.uploadCloud(tgt)
+        # (nothing in this call waits for the device -- no box to poll for -- so it is timed as eight builds back to back and one
+        # synchronisation, the way the by-reference builds above pace themselves through their polled boxes)
+        def cloud_builds():
+            for _ in range(8):
+                reg.setInputTargetCloud(tgt_cloud)
+            torch.cuda.synchronize()
+        t_build_cloud = median_time(cloud_builds) / 8
       reg.setInputTargetDeviceRef(tgt_dev.data_ptr(), len(tgt))  # (the timed region runs against the by-reference grid, as in round 3)
-      tgt_cloud.release()
+      if tgt_cloud is not None:
+        tgt_cloud.release()
 
     T_gts = None
     if workload in ("single", "large"):
         src = clouds.source_from_target(tgt, N_SOURCE, seed=clouds.SEED + 1 + 7 * rank)
         reg.setInputSource(src)
-        t_source = median_time(lambda: reg.setInputSource(src))           # H2D + spatial ordering of the scan
+        t_source = median_time(lambda: reg.setInputSource(src)) if args.full else None  # H2D + spatial ordering of the scan
 
         def step():
             reg.align(guess)
@@ -554,10 +585,17 @@ def main():
     if args.pmc_child:  # the profiler around this process has what it came for
         print(json.dumps({"pmc_child": True, "steps": steps, "ms_per_step": dt / steps * 1e3}), flush=True)
         return
+    if args.dump_outputs:
+        if T_gts is None:  # pcl::Registration: the final transformation, hasConverged, getFinalNumIteration, getTransformationProbability
+            dump_outputs(args.dump_outputs, {"final_transformation": reg.getFinalTransformation(), "converged": reg.hasConverged(),
+                                             "final_num_iteration": reg.getFinalNumIteration(),
+                                             "transformation_probability": reg.getTransformationProbability()}, rank, world)
+        elif "res" in last:
+            dump_outputs(args.dump_outputs, last["res"], rank, world)
 
     # every rank: did its registrations end at the known T_gt?  (summed over ranks; outside the timed region)
     recovered = None
-    if T_gts is not None:
+    if args.full and T_gts is not None:
         ok = 0
         if T_gts:
             Ts = last["res"]["T"]
@@ -592,7 +630,11 @@ def main():
             "world_size": world, "collective_backend": (dist.get_backend() if dist is not None else None),
             "per_rank_registrations_per_s": per_rank_regs,
             "cgroup_nr_throttled_in_timed_region_rank0": (cg1[0] - cg0[0]) if (cg0 and cg1) else None,
-            "host_binding": binding, "target_build_ms": t_build * 1e3,
+            "host_binding": binding,
+        }
+    if rank == 0 and args.full:
+        out.update({
+            "target_build_ms": t_build * 1e3,
             # (key definitions as in rounds 1-2: device_resident = ndt_set_input_target_device, the library copies the cloud;
             #  the by-reference build and the build from an ndt_cloud have keys of their own)
             "target_build_roofline": None, "target_build_device_resident_ms": t_build_dev * 1e3,
@@ -600,7 +642,7 @@ def main():
             "target_build_device_ref_ms": t_build_ref * 1e3,
             "target_build_resident_cloud_ms": t_build_cloud * 1e3,
             "target_build_first_call_ms": t_build_first * 1e3,
-        }
+        })
         if recovered is not None:
             out["registrations_ending_at_T_gt"] = recovered
             out["registrations_per_step"] = regs_per_step_global
@@ -618,7 +660,7 @@ def main():
         except Exception:
             pass
 
-    if workload in ("single", "large"):
+    if args.full and workload in ("single", "large"):
         if rank == 0:
             single_legs(out, args, reg, ndt, clouds, tgt, src, workload, world, steps, dt, t_build, t_source, N_SOURCE, RESOLUTION, value, guess)
             if pmc is not None and "roofline" in out:
@@ -626,7 +668,7 @@ def main():
                 out["roofline"]["traffic_measured"] = pmc[1]
                 if pmc[0]:
                     out["roofline"]["traffic_over_algorithmic"] = pmc[0] / out["roofline"]["algorithmic_bytes_per_launch"]
-    else:
+    elif args.full:
         batch_legs(out, args, reg, nd, ndt, dist, rank, world, workload, step, steps, dt, N_SOURCE, dev if n_local else None, offsets, lo, hi,
                    T_gts, torch)
     if rank == 0:
@@ -1113,8 +1155,9 @@ def run_pyramid(args, ndt, clouds, tgt, device, steps, warmup, binding, world=1,
     barrier()
     dt = max_over_ranks(time.perf_counter() - t0)
     shutil.rmtree(tmp, ignore_errors=True)
-    ok = sum(int(np.abs(T[:3, :3] - Tg[:3, :3]).max() < 5e-4 and np.abs(T[:3, 3] - Tg[:3, 3]).max() < 2e-2) for T, Tg in zip(r["T"], T_gts))
-    return {"metric": "scans/sec (2M-pt scans, 2.0->1.0->0.5 m pyramid vs 10M-pt target, streamed PCD sequence)",
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"T": np.stack(r["T"]), "file_numbers": r["file_numbers"]}, rank, world)
+    out = {"metric": "scans/sec (2M-pt scans, 2.0->1.0->0.5 m pyramid vs 10M-pt target, streamed PCD sequence)",
             "value": world * steps * n_scans / dt, "unit": "scans/s", "n_gpus": world, "steps": steps, "warmup": max(1, warmup),
             "ms_per_step": dt / steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
             "data": "synthetic",
@@ -1122,8 +1165,11 @@ def run_pyramid(args, ndt, clouds, tgt, device, steps, warmup, binding, world=1,
                                    "buffers), three resident grids 2.0 / 1.0 / 0.5 m over one 10M-pt target (%g m scene), each level's result "
                                    "the next level's guess; one independent sequence per rank" % (n_scans, args.extent)},
             "world_size": world, "pass_ms_rank0": pass_ms, "per_level_ms": r["per_level_ms"], "upload_ms_per_scan": r["upload_ms"], "wait_for_file_ms_per_scan": r["wait_ms"],
-            "grids_build_ms": t_build * 1e3, "scans_ending_at_T_gt_rank0": ok, "evaluations_per_scan": r["evals_per_scan"],
-            "host_binding": binding}
+            "grids_build_ms": t_build * 1e3, "evaluations_per_scan": r["evals_per_scan"], "host_binding": binding}
+    if args.full:
+        out["scans_ending_at_T_gt_rank0"] = sum(int(np.abs(T[:3, :3] - Tg[:3, :3]).max() < 5e-4 and np.abs(T[:3, 3] - Tg[:3, 3]).max() < 2e-2)
+                                                for T, Tg in zip(r["T"], T_gts))
+    return out
 
 
 if __name__ == "__main__":

@@ -32,6 +32,20 @@ def pair():
 
 
 @pytest.fixture(scope="session")
+def reference_pcd(tmp_path_factory):
+    """The reference's bundled scan pair as its raw PCD files (ndt_omp/data/251370668.pcd = target, 251371071.pcd =
+    source; stored xz-compressed, byte for byte) -> (target path, source path)."""
+    import lzma
+    d = tmp_path_factory.mktemp("reference_pcd")
+    paths = []
+    for name in ("251370668", "251371071"):
+        p = d / (name + ".pcd")
+        p.write_bytes(lzma.open(os.path.join(GOLDEN, name + ".pcd.xz")).read())
+        paths.append(str(p))
+    return tuple(paths)
+
+
+@pytest.fixture(scope="session")
 def golden():
     with open(os.path.join(GOLDEN, "oracle_golden.json")) as f:
         return json.load(f)

@@ -1,12 +1,10 @@
 """Row N3: PCD v0.7 reader / writer of the C-ABI (host only, no GPU) against independent Python
-encoders / decoders of the same format and, when the reference tree is mounted, its own fixtures."""
+encoders / decoders of the same format and against the reference's own scans (tests/golden/*.pcd.xz)."""
 import os
 import struct
 
 import numpy as np
 import pytest
-
-REF_PCD = "/root/reference/ndt_omp/data/251370668.pcd"
 
 
 @pytest.fixture(scope="module")
@@ -183,21 +181,16 @@ def test_errors(ndt, tmp_path):
         ndt.pcd_read_xyz(p)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_PCD), reason="reference tree not mounted")
-def test_reference_fixture(ndt):
+def test_reference_fixture(ndt, reference_pcd):
     """The reference's own scan (FIELDS x y z intensity, binary, 69 088 points)."""
     from toyslam_amd import clouds
-    got, dense = ndt.pcd_read_xyz(REF_PCD)
-    py, names = clouds.read_pcd(REF_PCD)
+    got, dense = ndt.pcd_read_xyz(reference_pcd[0])
+    py, names = clouds.read_pcd(reference_pcd[0])
     assert names[:3] == ["x", "y", "z"] and got.shape == (69088, 3) and dense
     assert np.array_equal(got, py[:, :3])
 
 
-REF_PCD2 = "/root/reference/ndt_omp/data/251371071.pcd"
-
-
-@pytest.mark.skipif(not (os.path.exists(REF_PCD) and os.path.exists(REF_PCD2)), reason="reference tree not mounted")
-def test_committed_pair_is_the_reference_pair_after_align_cpp_downsample(ndt, pair):
+def test_committed_pair_is_the_reference_pair_after_align_cpp_downsample(ndt, pair, reference_pcd):
     """tests/golden/pair_0p1.npz (what every parity test registers) is the reference's bundled PCD pair
     after apps/align.cpp's 0.1 m VoxelGrid (align.cpp:36-69: argv[1] = target = 251370668, argv[2] =
     source = 251371071): rebuilt here from the raw files through the library's PCD reader and the
@@ -205,7 +198,7 @@ def test_committed_pair_is_the_reference_pair_after_align_cpp_downsample(ndt, pa
     from oracle import pyoracle as po
     from toyslam_amd import clouds
     t, s = pair
-    for path, fixture in ((REF_PCD, t), (REF_PCD2, s)):
+    for path, fixture in zip(reference_pcd, (t, s)):
         raw, dense = ndt.pcd_read_xyz(path)
         assert dense
         # the generator (oracle/gen_golden.py) used the numpy down-sample: f64 centroid sums

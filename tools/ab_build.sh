@@ -7,6 +7,6 @@ cd $R
 for i in 1 2 3; do
   for v in A B; do
     cp toyslam_amd/libndt_$v.so toyslam_amd/libndt_mi355.so
-    python3 bench.py "$@" --no-cpu-baseline --no-mapbuild-leg 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('$v', round(d['value'],1), round(d['ms_per_step'],4), d.get('protocol_us_per_evaluation'), d.get('body_us_per_evaluation'))"
+    python3 bench.py "$@" --full --no-cpu-baseline --no-mapbuild-leg 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('$v', round(d['value'],1), round(d['ms_per_step'],4), d.get('protocol_us_per_evaluation'), d.get('body_us_per_evaluation'))"
   done
 done

@@ -8,8 +8,8 @@ while [ $# -gt 0 ] && [ "$1" != "--" ]; do vals+=("$1"); shift; done
 [ "$1" = "--" ] && shift
 show='import json,sys; d=json.loads(sys.stdin.read()); print(sys.argv[1], round(d["value"],1), round(d["ms_per_step"],4), d.get("protocol_us_per_evaluation"), d.get("body_us_per_evaluation"))'
 for i in 1 2 3; do
-  python3 bench.py "$@" --no-cpu-baseline --no-mapbuild-leg 2>/dev/null | python3 -c "$show" "default"
+  python3 bench.py "$@" --full --no-cpu-baseline --no-mapbuild-leg 2>/dev/null | python3 -c "$show" "default"
   for v in "${vals[@]}"; do
-    env $var=$v python3 bench.py "$@" --no-cpu-baseline --no-mapbuild-leg 2>/dev/null | python3 -c "$show" "$var=$v"
+    env $var=$v python3 bench.py "$@" --full --no-cpu-baseline --no-mapbuild-leg 2>/dev/null | python3 -c "$show" "$var=$v"
   done
 done

@@ -15,7 +15,7 @@ import sys
 tag = sys.argv[1] if len(sys.argv) > 1 else "r02"
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 O = os.path.join(R, "gpurun_out", "prof_batch")
-out = {"command": "python bench.py --workload batch --batch 64 (stats: --steps 3 --warmup 1; each --pmc pass on its own: --steps 1 --warmup 1)",
+out = {"command": "python bench.py --full --workload batch --batch 64 (stats: --steps 3 --warmup 1; each --pmc pass on its own: --steps 1 --warmup 1)",
        "note": "the timed batch runs as independent lock-step groups (2 at 64 scans); bench.py's roofline leg runs one more pass as ONE "
                "lock-step loop with an event pair around the derivative kernels of every lock-step", "kernel_stats": {}, "pmc": {}}
 rows = list(csv.DictReader(open(os.path.join(O, "kernel_stats.csv"))))
