@@ -1,0 +1,113 @@
+// apps/pair_sequence.cpp -- the loop of the reference's scan-to-scan node (lidar_subscriber/src/ndt_omp_node.cpp) written
+// against the C-ABI alone (no ROS, no PCL): every numbered cloud_N.pcd of a directory is read in order and voxel-filtered
+// at 0.5 m into an ndt_cloud, then ALL consecutive pairs (k-1, k) are registered in one ndt_align_pairs_clouds call with
+// the node's settings (resolution 1.0, step 0.1, epsilon 0.01, 64 iterations, DIRECT7) -- the registrations do not depend
+// on each other once the clouds are known.  A pair that did not converge counts as identity (:120-123); the poses are
+// chained with ndt_host_chain_pose.  Printed per pair: "Transform k-1 to k" and "TransformSum", then one timing line.
+//
+//   pair_sequence <pcd_directory>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#include "ndt_mi355.h"
+
+#define CHECK(call)                                                     \
+  do {                                                                  \
+    if ((call) != NDT_OK) {                                             \
+      std::fprintf(stderr, "%s failed: %s\n", #call, ndt_last_error()); \
+      return 1;                                                         \
+    }                                                                   \
+  } while (0)
+
+static void print_matrix(const char* title, const float* T) {
+  std::printf("%s\n", title);
+  for (int r = 0; r < 4; r++) std::printf("  %.9g %.9g %.9g %.9g\n", T[r], T[4 + r], T[8 + r], T[12 + r]);
+}
+
+using clock_type = std::chrono::steady_clock;
+static double since(clock_type::time_point a) { return std::chrono::duration<double, std::milli>(clock_type::now() - a).count(); }
+
+int main(int argc, char** argv) {
+  if (argc < 2) {
+    std::printf("usage: pair_sequence <pcd_directory>\n");
+    return 0;
+  }
+  const float kLeaf = 0.5f;
+  ndt_handle h = nullptr;
+  CHECK(ndt_create(0, &h));
+  CHECK(ndt_set_resolution(h, 1.0f));
+  CHECK(ndt_set_step_size(h, 0.1));
+  CHECK(ndt_set_transformation_epsilon(h, 0.01));
+  CHECK(ndt_set_maximum_iterations(h, 64));
+  CHECK(ndt_set_neighborhood_search_method(h, NDT_DIRECT7));
+  CHECK(ndt_warm_up(h, 65536));
+
+  // ---- every cloud of the directory, filtered, resident in HBM
+  ndt_pcd_sequence_handle seq = nullptr;
+  CHECK(ndt_pcd_sequence_open(argv[1], &seq));
+  size_t fresh = 0;
+  CHECK(ndt_pcd_sequence_poll(seq, 0, &fresh));
+  std::vector<ndt_cloud> clouds;
+  const auto t_load = clock_type::now();
+  for (;;) {
+    const void* raw = nullptr;
+    size_t n = 0;
+    int dense = 1, number = -1;
+    if (ndt_pcd_sequence_next(seq, &raw, &n, &dense, &number) != NDT_OK) {  // unreadable file: skipped, as the node does
+      std::fprintf(stderr, "skipped: %s\n", ndt_last_error());
+      continue;
+    }
+    if (!raw) break;
+    ndt_cloud c = nullptr;
+    int overflowed = 0;
+    CHECK(ndt_cloud_voxel_filter(h, raw, n, 16, dense, kLeaf, 0, &c, &overflowed));
+    size_t m = 0;
+    CHECK(ndt_cloud_size(c, &m));
+    if (m == 0) {  // empty clouds are not kept
+      ndt_cloud_release(c);
+      continue;
+    }
+    std::printf("Loaded cloud_%d.pcd (%zu points)\n", number, m);
+    clouds.push_back(c);
+  }
+  ndt_pcd_sequence_close(seq);
+  const double load_ms = since(t_load);
+
+  // ---- all consecutive pairs in one call
+  const size_t n_pairs = clouds.size() > 1 ? clouds.size() - 1 : 0;
+  std::vector<int> pairs(2 * n_pairs);
+  for (size_t k = 0; k < n_pairs; k++) {
+    pairs[2 * k] = static_cast<int>(k);
+    pairs[2 * k + 1] = static_cast<int>(k + 1);
+  }
+  std::vector<float> T(16 * n_pairs);
+  std::vector<int> conv(n_pairs), iters(n_pairs);
+  const auto t_align = clock_type::now();
+  CHECK(ndt_align_pairs_clouds(h, clouds.data(), clouds.size(), 1, pairs.data(), n_pairs, nullptr, T.data(), conv.data(), iters.data(), nullptr));
+  const double align_ms = since(t_align);
+
+  // ---- pose chain
+  static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  std::vector<float> sum(kIdentity, kIdentity + 16);
+  size_t not_converged = 0;
+  for (size_t k = 0; k < n_pairs; k++) {
+    float* Tk = T.data() + 16 * k;
+    if (!conv[k]) {
+      not_converged++;
+      for (int i = 0; i < 16; i++) Tk[i] = kIdentity[i];
+    }
+    ndt_host_chain_pose(sum.data(), Tk, sum.data());
+    char title[96];
+    std::snprintf(title, sizeof(title), "Transform %zu to %zu: (%d iterations%s)", k, k + 1, iters[k], conv[k] ? "" : ", not converged");
+    print_matrix(title, Tk);
+    print_matrix("TransformSum:", sum.data());
+  }
+  std::printf("\nclouds %zu  pairs %zu (not converged %zu)\n", clouds.size(), n_pairs, not_converged);
+  std::printf("time: read + prefilter %.2f ms, pairs call %.2f ms (%.1f pairs/s)\n", load_ms, align_ms,
+              align_ms > 0 ? 1e3 * static_cast<double>(n_pairs) / align_ms : 0.0);
+  for (ndt_cloud c : clouds) ndt_cloud_release(c);
+  ndt_destroy(h);
+  return 0;
+}

@@ -301,6 +301,34 @@ ndt_status ndt_align_batch_device(ndt_handle h, const void* d_pts, const size_t*
  * always run as one loop. */
 ndt_status ndt_set_batch_groups(ndt_handle h, int n_groups);
 
+/* ---- pairs (scan-to-scan: every pair against the voxel grid of its own target) -----------------------------------
+ * Registers n_pairs (target, source) pairs of clouds in lock-step.  Cloud c is points [offsets[c], offsets[c+1]) of
+ * `pts`; pairs[2*k] = target cloud, pairs[2*k+1] = source cloud of pair k.  A cloud named as target by several pairs is
+ * gridded once; a cloud may be the target and the source of one pair.  Parameters (resolution, step, epsilon, iterations,
+ * search method, min points per voxel ...) come from the handle; is_dense is the targets' NaN rule.  guesses == NULL ->
+ * Identity.  Per-pair outputs have n_pairs entries; any output may be NULL.
+ * Every pair gets the registration a handle with that target and source would get from ndt_align (a target without a valid
+ * voxel included), and the same bits in any call: whatever the other pairs, their order or the grouping
+ * (ndt_set_batch_groups).  The handle's own target, source, grid and last result are left as they were; ndt_get_stats
+ * reports the pairs call.  The grids stay on the handle until the next pairs call (ndt_pairs_grid_*) or ndt_destroy.
+ * NDT_ERR_INVALID before any device work: NULL offsets / pairs / clouds with a non-zero count, offsets that decrease, a
+ * pair index >= n_clouds, more than 65535 pairs (one call's limit: split larger sets into several calls), a handle with a
+ * communicator or an all-reduce hook (pairs are not sharded). */
+ndt_status ndt_align_pairs(ndt_handle h, const void* pts, const size_t* offsets /* n_clouds+1 */, size_t n_clouds,
+                           size_t stride_bytes, int is_dense, const int* pairs /* 2*n_pairs */, size_t n_pairs,
+                           const float* guesses /* n_pairs*16 or NULL */, float* final_transformations /* n_pairs*16 */,
+                           int* has_converged, int* final_num_iteration, double* transformation_probability);
+/* the same over clouds already resident in HBM (e.g. from ndt_cloud_voxel_filter) */
+ndt_status ndt_align_pairs_clouds(ndt_handle h, const ndt_cloud* clouds, size_t n_clouds, int is_dense, const int* pairs,
+                                  size_t n_pairs, const float* guesses, float* final_transformations, int* has_converged,
+                                  int* final_num_iteration, double* transformation_probability);
+/* the grid the last pairs call built for cloud c (NDT_ERR_NO_INPUT if c was no target of it): as ndt_grid_size /
+ * ndt_grid_info / ndt_grid_dump */
+ndt_status ndt_pairs_grid_size(ndt_handle h, size_t cloud, size_t* n_leaves, size_t* n_valid);
+ndt_status ndt_pairs_grid_info(ndt_handle h, size_t cloud, int* min_b /*3*/, int* max_b /*3*/, int* div_b /*3*/);
+ndt_status ndt_pairs_grid_dump(ndt_handle h, size_t cloud, int64_t* idx, int* nr_points, double* mean, double* cov,
+                               double* icov, double* evals);
+
 /* ---- multi-GPU (one process per GPU, RCCL over xGMI) ---------------------------
  * The reference is a single process (ndt_omp_impl.hpp:206 is its only parallel construct); this is the exchange step
  * north_star adds.  Registrations of different scans are independent, so ndt_align_batch* on every rank over its own

@@ -103,6 +103,11 @@ SIGNATURES = {
     "ndt_align_batch_device": (C.c_int, [vp, vp, szp, C.c_size_t, C.c_size_t, fp, fp, ip, ip, dp]),
     "ndt_set_allreduce": (C.c_int, [vp, ALLREDUCE_FN, vp, C.c_int]),
     "ndt_set_batch_groups": (C.c_int, [vp, C.c_int]),
+    "ndt_align_pairs": (C.c_int, [vp, vp, szp, C.c_size_t, C.c_size_t, C.c_int, ip, C.c_size_t, fp, fp, ip, ip, dp]),
+    "ndt_align_pairs_clouds": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, C.c_int, ip, C.c_size_t, fp, fp, ip, ip, dp]),
+    "ndt_pairs_grid_size": (C.c_int, [vp, C.c_size_t, szp, szp]),
+    "ndt_pairs_grid_info": (C.c_int, [vp, C.c_size_t, ip, ip, ip]),
+    "ndt_pairs_grid_dump": (C.c_int, [vp, C.c_size_t, C.POINTER(C.c_int64), ip, dp, dp, dp, dp]),
     "ndt_align_batch_sharded": (C.c_int, [vp, vp, szp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, fp, fp, ip, ip, dp]),
     "ndt_align_batch_sharded_device": (C.c_int, [vp, vp, szp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, fp, fp, ip, ip, dp]),
     "ndt_comm_get_unique_id": (C.c_int, [vp]),

@@ -278,8 +278,33 @@ static ndt_status align_batch_impl(ndt_handle h, const void* pts, const size_t* 
     if (s) return s;
   }
   const bool use_sorted = cloud->n_sorted > 0 && !cloud->scan_counts.empty();
-  const float4* batch_pts = use_sorted ? cloud->sorted.p : cloud->pts.p;
-  s = ensure_host_rows(h, total);
+  LockStepMembers m;
+  m.pts = use_sorted ? cloud->sorted.p : cloud->pts.p;
+  m.offset.resize(n_local);
+  m.count.resize(n_local);
+  m.n_raw.resize(n_local);
+  for (size_t k = 0; k < n_local; k++) {
+    m.n_raw[k] = offsets[k + 1] - offsets[k];
+    m.offset[k] = static_cast<int>(use_sorted ? cloud->scan_starts[k] : offsets[k] - offsets[0]);
+    m.count[k] = static_cast<int>(use_sorted ? cloud->scan_counts[k] : m.n_raw[k]);
+  }
+  return lock_step(h, m, n_local, guesses, final_T, conv, iters, tprob, first, sharded ? total : 0);
+}
+
+}  // extern "C"
+
+namespace ndtc {
+
+// The lock-step loop itself: one Newton / More-Thuente state machine per member, every step's evaluations of all members
+// in one or a few launches, the rows polled from pinned memory (or exchanged between ranks).  total == 0: not sharded.
+ndt_status lock_step(ndt_context* h, const LockStepMembers& m, size_t n_local, const float* guesses, float* final_T, int* conv,
+                     int* iters, double* tprob, size_t first, size_t total) {
+  const bool sharded = total != 0;
+  if (!sharded) total = n_local;
+  const bool exchange = h->comm != nullptr || h->allreduce != nullptr;
+  if (m.views && (sharded || exchange)) return fail(NDT_ERR_INVALID, "per-member grids are not sharded");
+  const float4* batch_pts = m.pts;
+  ndt_status s = ensure_host_rows(h, total);
   if (s) return s;
   HIP_TRY(h->batch_out.reserve(total * ndt::kEvalStride));
   const ndt::Gauss gs = ndt::gauss_constants(h->resolution, h->outlier_ratio);
@@ -310,7 +335,7 @@ static ndt_status align_batch_impl(ndt_handle h, const void* pts, const size_t* 
 
   // every rank needs every scan's point count (transformation_probability = score / N): one exchange up front
   std::vector<size_t> counts(total, 0);
-  for (size_t k = 0; k < n_local; k++) counts[first + k] = offsets[k + 1] - offsets[k];
+  for (size_t k = 0; k < n_local; k++) counts[first + k] = m.n_raw[k];
   if (sharded && exchange) {
     std::vector<double> rows(total * ndt::kEvalStride, 0.0);
     for (size_t k = 0; k < n_local; k++) rows[(first + k) * ndt::kEvalStride] = static_cast<double>(counts[first + k]);
@@ -343,8 +368,8 @@ static ndt_status align_batch_impl(ndt_handle h, const void* pts, const size_t* 
     descs[g].kind = ndt::EVAL_NONE;
     if (is_local(g)) {
       const size_t k = g - first;
-      descs[g].offset = static_cast<int>(use_sorted ? cloud->scan_starts[k] : offsets[k] - offsets[0]);
-      descs[g].count = static_cast<int>(use_sorted ? cloud->scan_counts[k] : counts[g]);
+      descs[g].offset = m.offset[k];
+      descs[g].count = m.count[k];
       max_n = std::max(max_n, counts[g]);
     }
   }
@@ -353,8 +378,12 @@ static ndt_status align_batch_impl(ndt_handle h, const void* pts, const size_t* 
   const int max_blocks = ndt::batch_blocks(static_cast<int>(max_n));
   HIP_TRY(h->partials.reserve(total * max_blocks * ndt::kEvalStride));
   HIP_TRY(h->descs.reserve((pinned_need + sizeof(ndt::ScanDesc) - 1) / sizeof(ndt::ScanDesc)));  // descriptors + the 3 active lists
-  const ndt::GridView gv = h->grid->view();
-  const bool degenerate = h->grid->empty;
+  const ndt::GridView gv = m.views ? ndt::GridView{} : h->grid->view();
+  const bool degenerate = m.views ? false : h->grid->empty;  // (per-member grids: members without a voxel, m.empty)
+  if (m.views) {  // (m.views outlives the loop: the pageable copy needs no wait)
+    HIP_TRY(h->pair_views.reserve(total));
+    HIP_TRY(hipMemcpyAsync(h->pair_views.p, m.views, total * sizeof(ndt::GridView), hipMemcpyHostToDevice, h->stream));
+  }
   static const int n_host_threads = [] {
     const char* v = getenv("NDT_HOST_THREADS");
     if (v) return std::max(1, atoi(v));
@@ -386,6 +415,7 @@ static ndt_status align_batch_impl(ndt_handle h, const void* pts, const size_t* 
       live_kind[g] = kind;
       n_live_all++;
       if (!is_local(g)) continue;  // somebody else's scan: its row arrives with the exchange
+      if (m.empty && m.empty[g - first]) continue;  // its grid has no voxel: a zero row (below), nothing to launch
       descs[g].kind = kind;
       active[kind * total + n_act[kind]++] = static_cast<int>(g);
     }
@@ -395,9 +425,9 @@ static ndt_status align_batch_impl(ndt_handle h, const void* pts, const size_t* 
     const bool mixed = (n_act[0] != n_live && n_act[1] != n_live && n_act[2] != n_live);
     if (mixed) {
       int* all = active + 3 * total;
-      int m = 0;
+      int n_all = 0;
       for (int c = 0; c < 3; c++)
-        for (int i = 0; i < n_act[c]; i++) all[m++] = active[c * total + i];
+        for (int i = 0; i < n_act[c]; i++) all[n_all++] = active[c * total + i];
     }
     pool.run(total, [&](size_t g) {  // per-scan parameter tables (sin/cos, pose -> matrix)
       if (descs[g].kind == ndt::EVAL_NONE) return;
@@ -407,7 +437,8 @@ static ndt_status align_batch_impl(ndt_handle h, const void* pts, const size_t* 
       else fill_eval_params(rq, gs, kd_radius2(h->resolution), descs[g].P);
     });
     const auto tb1 = now();
-    if (degenerate && !exchange) {
+    const bool nothing_to_launch = degenerate || (m.views && n_live == 0);  // (pairs: every live member's target without a voxel)
+    if (nothing_to_launch && !exchange) {
       std::memset(h->host_result, 0, total * ndt::kEvalStride * sizeof(double));
     } else if (degenerate) {
       // this rank's target has no voxel: its rows are zero, but it still joins the exchange -- the other ranks' grids
@@ -426,7 +457,15 @@ static ndt_status align_batch_impl(ndt_handle h, const void* pts, const size_t* 
       ndt::Hess64Params dummy64 = {};
       if (exchange) HIP_TRY(hipMemsetAsync(h->batch_out.p, 0, total * ndt::kEvalStride * sizeof(double), h->stream));
       if (h->profiling) HIP_TRY(hipEventRecord(h->ev_a, h->stream));
-      if (mixed) {
+      if (m.views) {  // every member against its own grid (ndt_pairs_kernels.hip): the same launches, the same rows
+        const ndt::GridView* d_views = h->pair_views.p;
+        if (mixed) {
+          HIP_TRY(ndt::launch_pairs_step(batch_pts, d_views, h->search, -1, h->descs.p, d_active + 3 * total, n_live, max_blocks, max_blocks, h->partials.p, h->stream));
+        } else {
+          for (int c = 0; c < 3; c++)
+            if (n_act[c]) HIP_TRY(ndt::launch_pairs_step(batch_pts, d_views, h->search, c, h->descs.p, d_active + c * total, n_act[c], max_blocks, max_blocks, h->partials.p, h->stream));
+        }
+      } else if (mixed) {
         HIP_TRY(ndt::launch_batch_step(batch_pts, gv, h->search, h->descs.p, d_active + 3 * total, n_live, max_blocks, max_blocks, h->partials.p, h->stream));
       } else {
         if (n_act[0]) HIP_TRY(ndt::launch_derivatives(batch_pts, 0, gv, dummy, h->search, true, h->descs.p, d_active, n_act[0], max_blocks, max_blocks, h->partials.p, h->stream));
@@ -444,12 +483,15 @@ static ndt_status align_batch_impl(ndt_handle h, const void* pts, const size_t* 
         // straight into pinned host memory; poll those instead of a D2H copy + stream synchronise
         const unsigned long long seq = ++h->eval_seq;
         HIP_TRY(ndt::launch_reduce(h->partials.p, max_blocks, static_cast<int>(total), h->descs.p, h->host_result, h->stream, seq));
-        s = poll_rows(h, total, seq, [&](size_t g) { return live_kind[g] != ndt::EVAL_NONE; });
+        s = poll_rows(h, total, seq, [&](size_t g) { return descs[g].kind != ndt::EVAL_NONE; });
         if (s) return s;
+        if (m.empty)
+          for (size_t g = 0; g < total; g++)
+            if (live_kind[g] != ndt::EVAL_NONE && descs[g].kind == ndt::EVAL_NONE) std::memset(h->host_result + g * ndt::kEvalStride, 0, ndt::kEvalStride * sizeof(double));
       }
     }
     const auto tb2 = now();
-    if (h->profiling && !degenerate) {  // ndt_profile_enable(h, 1): the derivative kernels of this lock-step (slot 0)
+    if (h->profiling && !nothing_to_launch) {  // ndt_profile_enable(h, 1): the derivative kernels of this lock-step (slot 0)
       float ms = 0;
       HIP_TRY(hipEventSynchronize(h->ev_b));
       HIP_TRY(hipEventElapsedTime(&ms, h->ev_a, h->ev_b));
@@ -514,6 +556,10 @@ static ndt_status align_batch_impl(ndt_handle h, const void* pts, const size_t* 
   return NDT_OK;
 }
 
+}  // namespace ndtc
+
+extern "C" {
+
 // A batch without an exchange step is run as several INDEPENDENT lock-step groups, each on a worker handle of its own
 // (own stream, own staging buffers, the target grid shared) driven by a host thread of its own: while one group's
 // kernels run, the other groups' hosts step their Newton / More-Thuente state machines, upload descriptors and queue
@@ -524,8 +570,30 @@ static ndt_status align_batch_impl(ndt_handle h, const void* pts, const size_t* 
 static ndt_status align_batch_grouped(ndt_handle h, const void* pts, const size_t* offsets, size_t n_scans, size_t stride,
                                       bool on_device, const float* guesses, float* final_T, int* conv, int* iters,
                                       double* tprob) {
-  static const int forced = [] { const char* v = getenv("NDT_BATCH_GROUPS"); return v ? std::max(1, atoi(v)) : 0; }();
   const bool exchange = h && (h->comm != nullptr || h->allreduce != nullptr);
+  const size_t groups = batch_group_count(h, n_scans);
+  // (event pairs around the kernels of a lock-step -- ndt_profile_enable(1) -- only mean something without overlap)
+  if (!h || !offsets || exchange || groups <= 1 || !h->grid || !h->target || h->profiling)
+    return align_batch_impl(h, pts, offsets, n_scans, stride, on_device, guesses, final_T, conv, iters, tprob);
+  ndt_status s0 = ensure_device(h);
+  if (s0) return s0;
+  s0 = maybe_compact_records(h, true);  // before the groups' worker handles share the grid
+  if (s0) return s0;
+  return run_groups(
+      h, n_scans, groups, [&](size_t lo, size_t hi) { return static_cast<double>(offsets[hi] - offsets[lo]); },
+      [&](ndt_context* w, size_t lo, size_t hi) {
+        return align_batch_impl(w, pts, offsets + lo, hi - lo, stride, on_device, guesses ? guesses + 16 * lo : nullptr,
+                                final_T ? final_T + 16 * lo : nullptr, conv ? conv + lo : nullptr, iters ? iters + lo : nullptr,
+                                tprob ? tprob + lo : nullptr);
+      });
+}
+
+}  // extern "C"
+
+namespace ndtc {
+
+size_t batch_group_count(const ndt_context* h, size_t n_scans) {
+  static const int forced = [] { const char* v = getenv("NDT_BATCH_GROUPS"); return v ? std::max(1, atoi(v)) : 0; }();
   size_t groups = (h && h->batch_groups_wanted > 0) ? static_cast<size_t>(h->batch_groups_wanted)
                   : forced                           ? static_cast<size_t>(forced)
                                                      : (n_scans >= 192 ? 4 : n_scans >= 16 ? 2 : 1);  // (same-box A/B, two / four groups: 64 scans 5.9k / 5.6k reg/s, 96 6.25k / 6.1k, 128 equal, 512 6.4k / 6.6k; one loop: 32 scans 3.8k against 5.4k as two)
@@ -538,13 +606,11 @@ static ndt_status align_batch_grouped(ndt_handle h, const void* pts, const size_
     return mg;
   }();
   if (!(h && h->batch_groups_wanted > 0) && !forced) groups = std::min(groups, static_cast<size_t>(max_groups));  // a host thread per group
-  // (event pairs around the kernels of a lock-step -- ndt_profile_enable(1) -- only mean something without overlap)
-  if (!h || !offsets || exchange || groups <= 1 || !h->grid || !h->target || h->profiling)
-    return align_batch_impl(h, pts, offsets, n_scans, stride, on_device, guesses, final_T, conv, iters, tprob);
-  ndt_status s0 = ensure_device(h);
-  if (s0) return s0;
-  s0 = maybe_compact_records(h, true);  // before the groups' worker handles share the grid
-  if (s0) return s0;
+  return groups;
+}
+
+ndt_status run_groups(ndt_context* h, size_t n_scans, size_t groups, const std::function<double(size_t, size_t)>& pts_of,
+                      const std::function<ndt_status(ndt_context*, size_t, size_t)>& run) {
   HIP_TRY(hipStreamSynchronize(h->stream));  // the shared grid may still be under construction on h's stream
   while (h->batch_workers.size() < groups) {
     ndt_context* w = new ndt_context();
@@ -569,10 +635,8 @@ static ndt_status align_batch_grouped(ndt_handle h, const void* pts, const size_
     w->target_dense = h->target_dense;
     w->grid = h->grid;
     const size_t lo = n_scans * g / groups, hi = n_scans * (g + 1) / groups;
-    threads.emplace_back([=, &st, &msg] {
-      ndt_status s = align_batch_impl(w, pts, offsets + lo, hi - lo, stride, on_device, guesses ? guesses + 16 * lo : nullptr,
-                             final_T ? final_T + 16 * lo : nullptr, conv ? conv + lo : nullptr, iters ? iters + lo : nullptr,
-                             tprob ? tprob + lo : nullptr);
+    threads.emplace_back([=, &st, &msg, &run] {
+      ndt_status s = run(w, lo, hi);
       st[g] = s;
       if (s) msg[g] = ndt_last_error();
     });
@@ -593,7 +657,7 @@ static ndt_status align_batch_grouped(ndt_handle h, const void* pts, const size_
     ndt_context* w = h->batch_workers[g];
     if (st[g]) return fail(st[g], msg[g]);
     const size_t lo = n_scans * g / groups, hi = n_scans * (g + 1) / groups;
-    const double evals_pts = static_cast<double>(w->n_evals) * (hi > lo ? static_cast<double>(offsets[hi] - offsets[lo]) / static_cast<double>(hi - lo) : 0.0);
+    const double evals_pts = static_cast<double>(w->n_evals) * (hi > lo ? pts_of(lo, hi) / static_cast<double>(hi - lo) : 0.0);
     ne += w->n_evals;
     nh += w->n_hess;
     nn_w += w->mean_neighbors * evals_pts;
@@ -607,6 +671,10 @@ static ndt_status align_batch_grouped(ndt_handle h, const void* pts, const size_
   h->batch_groups = static_cast<int>(groups);
   return NDT_OK;
 }
+
+}  // namespace ndtc
+
+extern "C" {
 
 ndt_status ndt_align_batch(ndt_handle h, const void* pts, const size_t* offsets, size_t n_scans, size_t stride,
                            const float* guesses, float* final_T, int* conv, int* iters, double* tprob) {

@@ -507,10 +507,13 @@ ndt_status order_cloud(ndt_context* h, DeviceCloud* c, const size_t* offsets, si
 
 static ndt_status compact_records_now(ndt_context* h, DeviceGrid* g);
 
-// VoxelGridCovariance::filter(true) on the GPU.
-ndt_status build_grid(ndt_context* h) {
+// The first half of build_grid: the geometry of h->target's grid and the form that builds it.  hd.done: nothing to build
+// (no point, no finite point, or the reference's overflow) -- h->grid already holds the finished grid.
+ndt_status grid_head(ndt_context* h, GridHead& hd) {
+  hd.done = true;
   if (!h->target) return fail(NDT_ERR_NO_INPUT, "no target");
   auto g = std::make_shared<DeviceGrid>();
+  hd.g = g;
   g->target = h->target;
   g->resolution = h->resolution;
   g->min_pts = h->min_pts;
@@ -525,7 +528,6 @@ ndt_status build_grid(ndt_context* h) {
     h->grid = g;
     return NDT_OK;
   }
-  hipStream_t st = h->stream;
   // ---- bbox
   const BBox bb = bbox_of(*h->target, h->target_dense);  // computed during the upload: no kernel, no wait
   const float* min_p = bb.mn;
@@ -560,6 +562,25 @@ ndt_status build_grid(ndt_context* h) {
   // cell count stays within reach of the point count; sparse (sort-based build, hash look-up: ndt_sparse.hip) when the box
   // is mostly empty -- the regime the reference's std::map handles for free.  ndt_set_voxel_index overrides.
   const bool sparse = !h->index_only && (h->voxel_index == 2 || (h->voxel_index == 0 && (geo.n_cells > (1ll << 25) || geo.n_cells > 64ll * n + (1ll << 22))));
+  hd.n = n;
+  hd.max_leaves = max_leaves;
+  hd.max_cand = max_cand;
+  hd.sparse = sparse;
+  hd.done = false;
+  return NDT_OK;
+}
+
+// VoxelGridCovariance::filter(true) on the GPU.
+ndt_status build_grid(ndt_context* h) {
+  GridHead hd;
+  ndt_status hs = grid_head(h, hd);
+  if (hs || hd.done) return hs;
+  const std::shared_ptr<DeviceGrid> g = hd.g;
+  const int n = hd.n;
+  ndt::GridGeom& geo = g->geom;
+  const size_t max_leaves = hd.max_leaves, max_cand = hd.max_cand;
+  const bool sparse = hd.sparse;
+  hipStream_t st = h->stream;
   HIP_TRY(g->counts.reserve(8));  // [points binned, occupied voxels, candidate voxels (>= min_pts), valid voxels, points in crowded cells]
   HIP_TRY(g->leaf_cell.reserve(max_leaves));
   HIP_TRY(g->leaf_start.reserve(max_leaves));
@@ -736,6 +757,92 @@ ndt_status build_grid(ndt_context* h) {
   g->counts_known = false;
   g->empty = false;
   h->grid = g;
+  return NDT_OK;
+}
+
+ndt_status build_grids(ndt_context* h, const std::vector<std::shared_ptr<DeviceCloud>>& targets, int is_dense,
+                       std::vector<std::shared_ptr<DeviceGrid>>& out, size_t* n_small) {
+  // the forms build_grid would choose: the small one only where build_grid takes it (same switches)
+  static const bool chain_only = [] { const char* v = getenv("NDT_K1"); return v && std::strcmp(v, "old") == 0; }();
+  static const bool small_on = [] { const char* v = getenv("NDT_K1_SMALL"); return !v || atoi(v) != 0; }();
+  static const bool want_stamps = [] { const char* v = getenv("NDT_K1_STAMPS"); return v && atoi(v) != 0; }();
+  const std::shared_ptr<DeviceCloud> keep_target = h->target;
+  const std::shared_ptr<DeviceGrid> keep_grid = h->grid;
+  const int keep_dense = h->target_dense;
+  out.assign(targets.size(), nullptr);
+  std::vector<ndt::SmallBuildDesc> descs;
+  std::vector<std::unique_ptr<DevBuf<unsigned>>> scratch;  // per small target: [5 n] (back to the pool behind the launch)
+  int max_K = 0;
+  size_t lds = 0;
+  ndt_status s = NDT_OK;
+  for (size_t i = 0; i < targets.size() && !s; i++) {
+    h->target = targets[i];
+    h->target_dense = is_dense ? 1 : 0;
+    GridHead hd;
+    s = grid_head(h, hd);
+    if (s) break;
+    if (hd.done) {
+      out[i] = h->grid;
+      continue;
+    }
+    DeviceGrid* g = hd.g.get();
+    ndt::GridBuildPlan plan{};
+    ndt::SmallBuildDesc D{};
+    size_t lds_i = 0;
+    const bool small_form = !hd.sparse && !chain_only && !h->index_only && !want_stamps && small_on &&
+                            ndt::grid_build_plan(g->geom.n_cells, hd.n, plan) && ndt::grid_build_small_applies(hd.n, plan) &&
+                            ndt::small_build_desc(hd.n, plan, D, &lds_i);
+    if (!small_form) {
+      s = build_grid(h);
+      out[i] = h->grid;
+      continue;
+    }
+    // the small form's buffers, as build_grid reserves them
+    const size_t n = static_cast<size_t>(hd.n), K = static_cast<size_t>(plan.n_buckets);
+    const size_t rec_slots = n / static_cast<size_t>(std::max(1, h->min_pts)) + 1;
+    auto& sc = *scratch.emplace_back(new DevBuf<unsigned>());
+    if (g->counts.reserve(8) || g->leaf_cell.reserve(hd.max_leaves) || g->leaf_start.reserve(hd.max_leaves) || g->leaf_count.reserve(hd.max_leaves) ||
+        g->leaf_rec.reserve(hd.max_leaves) || g->sorted_idx.reserve(n) || g->lut.reserve(static_cast<size_t>(g->geom.lut_cells)) ||
+        g->recs.reserve(rec_slots) || g->centroids.reserve(rec_slots) || g->bucket_base.reserve(2 * K + 1) || g->bpts.reserve(n) ||
+        sc.reserve(5 * n)) {
+      s = fail(NDT_ERR_HIP, "out of device memory for the pairs grids");
+      break;
+    }
+    D.pts = h->target->pts.p;
+    D.dense = h->target_dense;
+    D.g = g->geom;
+    D.min_pts = h->min_pts;
+    D.eig_ratio = h->eig_ratio;
+    D.bucket_base = g->bucket_base.p;
+    D.bpts = g->bpts.p;
+    D.sorted_idx = g->sorted_idx.p;
+    D.recs = g->recs.p;
+    D.centroids = g->centroids.p;
+    D.lut = g->lut.p;
+    D.scratch = sc.p;
+    D.counts = g->counts.p;
+    descs.push_back(D);
+    max_K = std::max(max_K, plan.n_buckets);
+    lds = std::max(lds, lds_i);
+    g->index_form = false;
+    g->compact_pending = false;  // (a small cloud: build_grid compacts from 65536 points on)
+    g->plan = plan;
+    g->leaves_pending = true;
+    g->counts_known = false;
+    g->empty = false;
+    out[i] = hd.g;
+  }
+  h->target = keep_target;
+  h->grid = keep_grid;
+  h->target_dense = keep_dense;
+  if (s) return s;
+  *n_small = descs.size();
+  if (descs.empty()) return NDT_OK;
+  DevBuf<ndt::SmallBuildDesc> d_descs;
+  HIP_TRY(d_descs.reserve(descs.size()));
+  HIP_TRY(hipMemcpyAsync(d_descs.p, descs.data(), descs.size() * sizeof(ndt::SmallBuildDesc), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(ndt::launch_grid_build_small_multi(d_descs.p, static_cast<int>(descs.size()), max_K, lds, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));  // (`descs` is pageable: the copy has read it)
   return NDT_OK;
 }
 
@@ -1365,7 +1472,10 @@ ndt_status ndt_map_clear(ndt_handle h) {
 // ---- ndt_cloud: clouds that stay in HBM between the steps of a node's loop ----------------------------------------------
 // the cloud is about to be read by work on h's stream: order that stream behind the cloud's making, remember it for the
 // cloud's release
-static ndt_status cloud_use_on(ndt_handle h, DeviceCloud* c) {
+}  // extern "C"
+
+namespace ndtc {
+ndt_status cloud_use_on(ndt_handle h, DeviceCloud* c) {
   if (c->made_on && c->made_on != h->stream) {
     if (c->device != h->device) return fail(NDT_ERR_INVALID, "the cloud lives on another device");
     HIP_TRY(hipStreamSynchronize(c->made_on));
@@ -1373,6 +1483,9 @@ static ndt_status cloud_use_on(ndt_handle h, DeviceCloud* c) {
   }
   return NDT_OK;
 }
+}  // namespace ndtc
+
+extern "C" {
 
 ndt_status ndt_cloud_voxel_filter(ndt_handle h, const void* pts, size_t n, size_t stride, int is_dense, float leaf, int on_device,
                                   ndt_cloud* out, int* overflowed) {

@@ -2095,6 +2095,201 @@ __global__ __launch_bounds__(kSmallThreads) void k1_small(const float4* __restri
 }
 
 // ---------------------------------------------------------------------------
+// k1_small for MANY targets in one launch (ndt_align_pairs: every small target of a call).  blockIdx.y = target, blockIdx.x =
+// bucket; a target's descriptor holds what k1_small takes as arguments.  The records, table, bucketed points and counts are
+// k1_small's for that cloud, bit for bit: a bucket's points are listed in point order whatever the number of scanning
+// waves (every wave takes a contiguous run of chunks, the lists are concatenated in wave order), and the finish is the same
+// code on the same list.  Two differences from k1_small, both deliberate:
+//  - the block is kBlock threads, the size the finish is written for, so that EVERY wave that scans also runs the finish
+//    and meets each of its barriers (k1_small ends its extra scanning waves before the finish's barriers);
+//  - every point's cell index is range-tested per axis before it is used (as k_count tests its cell).
+// ---------------------------------------------------------------------------
+constexpr int kMultiWaves = kBlock / kWave;
+static_assert(kMultiWaves <= kSmallWaves, "K1ListSrc walks kSmallWaves segments");
+
+template <bool DENSE, bool POW2>
+__device__ __forceinline__ int multi_bucket(const GridGeom& g, const K1Deal& deal, float x, float y, float z) {
+#pragma clang fp contract(off)
+  const float fx = x * g.inv_leaf[0], fy = y * g.inv_leaf[1], fz = z * g.inv_leaf[2];
+  const int i0 = static_cast<int>(floorf(fx) - static_cast<float>(g.min_b[0]));
+  const int i1 = static_cast<int>(floorf(fy) - static_cast<float>(g.min_b[1]));
+  const int i2 = static_cast<int>(floorf(fz) - static_cast<float>(g.min_b[2]));
+  if (i0 < 0 || i0 >= g.div_b[0] || i1 < 0 || i1 >= g.div_b[1] || i2 < 0 || i2 >= g.div_b[2]) return -1;
+  const unsigned cell = __umul24(static_cast<unsigned>(i2), static_cast<unsigned>(g.mul[2])) +
+                        (__umul24(static_cast<unsigned>(i1), static_cast<unsigned>(g.mul[1])) + static_cast<unsigned>(i0));
+  const unsigned run = cell >> deal.rb;
+  int b;
+  if (POW2) {
+    b = static_cast<int>(run & (deal.K - 1u));
+  } else {
+    unsigned q, r;
+    deal.divmod(run, q, r);
+    b = static_cast<int>(r);
+  }
+  if (!DENSE) {
+    const float t = (fx + fy) + fz;  // not finite as soon as one coordinate is not
+    if (!(fabsf(t) < INFINITY)) b = -1;
+  }
+  return b;
+}
+
+// one scan of this wave's chunks [c_lo, c_hi): PASS 0 counts the points of the buckets below k and lists bucket k's points;
+// PASS 1 writes bucket k's points to out[] (their final places) -- small_scan's passes and loop, with multi_bucket's range test
+template <bool DENSE, bool POW2, int PASS>
+__device__ __forceinline__ void multi_scan(const float4* __restrict__ pts, int n, const GridGeom& g, const K1Deal& deal, int k, int c_lo, int c_hi,
+                                           float4* mylist, int list_cap, float4* __restrict__ out, unsigned& own_out, unsigned& below_out) {
+  const int lane = threadIdx.x & (kWave - 1);
+  unsigned own = 0, below = 0;  // wave-uniform
+  auto visit = [&](const float4& p, int i, bool in_range) {
+    int b = multi_bucket<DENSE, POW2>(g, deal, p.x, p.y, p.z);
+    if (!in_range) b = -1;
+    if (PASS == 0) below += static_cast<unsigned>(__popcll(__ballot(static_cast<unsigned>(b) < static_cast<unsigned>(k))));
+    const unsigned long long mine = __ballot(b == k);
+    if (mine) {  // (uniform)
+      const unsigned pos = own + __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(mine >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(mine), 0u));
+      if (b == k) {
+        const float4 q = make_float4(p.x, p.y, p.z, __int_as_float(i));
+        if (PASS == 0) {
+          if (pos < static_cast<unsigned>(list_cap)) mylist[pos] = q;
+        } else {
+          out[pos] = q;
+        }
+      }
+      own += static_cast<unsigned>(__popcll(mine));
+    }
+  };
+  const int full_hi = min(c_hi, n / kWave);  // chunks below this one are whole
+  int c0 = c_lo;
+  if (c0 + kSmallBatch <= full_hi) {  // whole batches, two register sets (small_scan's loop: loads of the next batch in flight)
+    const int nbat = (full_hi - c_lo) / kSmallBatch;
+    float4 pa[kSmallBatch], pb[kSmallBatch];
+    auto fetch = [&](float4* dst, int t) {
+      const int cb = c_lo + t * kSmallBatch;
+#pragma unroll
+      for (int u = 0; u < kSmallBatch; u++) dst[u] = pts[(cb + u) * kWave + lane];
+    };
+    auto look = [&](const float4* src, int t) {
+      const int cb = c_lo + t * kSmallBatch;
+#pragma unroll
+      for (int u = 0; u < kSmallBatch; u++) visit(src[u], (cb + u) * kWave + lane, true);
+    };
+    fetch(pa, 0);
+    for (int t = 0; t < nbat; t += 2) {
+      fetch(pb, min(t + 1, nbat - 1));
+      look(pa, t);
+      fetch(pa, min(t + 2, nbat - 1));
+      if (t + 1 < nbat) look(pb, t + 1);  // (uniform)
+    }
+    c0 = c_lo + nbat * kSmallBatch;
+  }
+  for (; c0 < c_hi; c0++) {  // the rest, chunk by chunk
+    const int i = c0 * kWave + lane;
+    visit(pts[min(i, n - 1)], i, i < n);
+  }
+  own_out = own;
+  below_out = below;
+}
+
+__global__ __launch_bounds__(kBlock) void k1_small_multi(const SmallBuildDesc* __restrict__ descs) {
+  extern __shared__ unsigned k1_lds[];
+  const SmallBuildDesc& D = descs[blockIdx.y];
+  const int k = blockIdx.x;
+  if (k >= D.K) return;  // (the whole block, before any barrier: grid.x is the largest K of the launch)
+  const GridGeom g = D.g;
+  const int n = D.n, K = D.K, C = D.C, list_cap = D.list_cap;
+  const K1Deal deal(D.map & 255, D.map >> 8);
+  __shared__ unsigned s_own[kMultiWaves], s_below[kMultiWaves], s_seg[kSmallWaves + 1];
+  float4* list = reinterpret_cast<float4*>(k1_lds + D.fin_words);
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  const int chunks = (n + kWave - 1) / kWave, per = (chunks + kMultiWaves - 1) / kMultiWaves;
+  const int c_lo = min(chunks, wave * per), c_hi = min(chunks, c_lo + per);
+  float4* mylist = list + wave * list_cap;
+  const bool pow2 = (K & (K - 1)) == 0;
+  unsigned own = 0, below = 0;
+  if (D.dense) {
+    if (pow2) multi_scan<true, true, 0>(D.pts, n, g, deal, k, c_lo, c_hi, mylist, list_cap, nullptr, own, below);
+    else multi_scan<true, false, 0>(D.pts, n, g, deal, k, c_lo, c_hi, mylist, list_cap, nullptr, own, below);
+  } else {
+    if (pow2) multi_scan<false, true, 0>(D.pts, n, g, deal, k, c_lo, c_hi, mylist, list_cap, nullptr, own, below);
+    else multi_scan<false, false, 0>(D.pts, n, g, deal, k, c_lo, c_hi, mylist, list_cap, nullptr, own, below);
+  }
+  if (lane == 0) {
+    s_own[wave] = own;
+    s_below[wave] = below;
+  }
+  __syncthreads();
+  unsigned base_w = 0, bb = 0, nb = 0;
+  bool overflow = false;
+  for (int w = 0; w < kMultiWaves; w++) {
+    bb += s_below[w];
+    if (w < wave) base_w += s_own[w];
+    nb += s_own[w];
+    overflow = overflow || s_own[w] > static_cast<unsigned>(list_cap);
+  }
+  if (overflow) {  // (uniform) a list was too short: a second scan, the points straight to their final places
+    unsigned own2 = 0, dummy = 0;
+    if (D.dense) multi_scan<true, false, 1>(D.pts, n, g, deal, k, c_lo, c_hi, nullptr, 0, D.bpts + bb + base_w, own2, dummy);
+    else multi_scan<false, false, 1>(D.pts, n, g, deal, k, c_lo, c_hi, nullptr, 0, D.bpts + bb + base_w, own2, dummy);
+  }
+  if (threadIdx.x == 0) {
+    unsigned run = 0;
+    for (int w = 0; w <= kSmallWaves; w++) {  // (segments past the last wave: empty, at nb)
+      s_seg[w] = run;
+      if (w < kMultiWaves) run += s_own[w];
+    }
+    D.bucket_base[k] = bb;
+    if (k == K - 1) {
+      D.bucket_base[K] = bb + nb;
+      D.counts[0] = bb + nb;  // points binned
+    }
+  }
+  __syncthreads();  // s_seg (every wave, overflow or not)
+  const K1ListSrc lsrc{list, s_seg, list_cap, overflow ? D.bpts + bb : nullptr};
+  if (!overflow)  // (uniform)
+    for (unsigned j = threadIdx.x; j < nb; j += kBlock) D.bpts[bb + j] = lsrc(j);
+  int* lut = D.lut;
+  {  // the look-up table: border slots of my slice, and every cell of my bucket starts out empty (k1_small's pass)
+    const long long per_blk = (g.lut_cells + K - 1) / K;
+    const long long lo = static_cast<long long>(k) * per_blk, hi = min(g.lut_cells, lo + per_blk);
+    const int ex = g.div_b[0] + kLutBorder, ey = g.div_b[1] + kLutBorder, ez = g.div_b[2] + kLutBorder;
+    // (a small grid's padded table has fewer than 2^31 slots: 32-bit quotients through the f32 reciprocal, as k1_small)
+    auto divq = [](unsigned a, unsigned b, float rb) {
+      unsigned q = static_cast<unsigned>(__uint2float_rz(a) * rb);
+      int r = static_cast<int>(a - q * b);
+      if (r < 0) { q--; r += static_cast<int>(b); }
+      if (r >= static_cast<int>(b)) q++;
+      return q;
+    };
+    const float rp2 = 1.0f / static_cast<float>(g.pmul[2]), rp1 = 1.0f / static_cast<float>(g.pmul[1]);
+    const float rm2 = 1.0f / static_cast<float>(g.mul[2]), rm1 = 1.0f / static_cast<float>(g.mul[1]);
+    for (long long sl = lo + threadIdx.x; sl < hi; sl += kBlock) {
+      const unsigned u = static_cast<unsigned>(sl);
+      const int pz = static_cast<int>(divq(u, static_cast<unsigned>(g.pmul[2]), rp2));
+      const unsigned rem = u - static_cast<unsigned>(pz) * static_cast<unsigned>(g.pmul[2]);
+      const int py = static_cast<int>(divq(rem, static_cast<unsigned>(g.pmul[1]), rp1)), px = static_cast<int>(rem) - py * g.pmul[1];
+      if (px < kLutBorder || px >= ex || py < kLutBorder || py >= ey || pz < kLutBorder || pz >= ez) lut[sl] = kLutEmpty;
+    }
+    for (int lc = threadIdx.x; lc < C; lc += kBlock) {
+      const long long cell = static_cast<unsigned>(k1_cell(k, lc, deal));
+      if (cell < g.n_cells) {
+        const unsigned c = static_cast<unsigned>(cell);
+        const int cz = static_cast<int>(divq(c, static_cast<unsigned>(g.mul[2]), rm2));
+        const unsigned rem = c - static_cast<unsigned>(cz) * static_cast<unsigned>(g.mul[2]);
+        const int cy = static_cast<int>(divq(rem, static_cast<unsigned>(g.mul[1]), rm1)), cx = static_cast<int>(rem) - cy * g.mul[1];
+        lut[static_cast<long long>(cx + kLutBorder) + static_cast<long long>(cy + kLutBorder) * g.pmul[1] + static_cast<long long>(cz + kLutBorder) * g.pmul[2]] = kLutEmpty;
+      }
+    }
+  }
+  __syncthreads();  // the bucketed points and the empty slots are out before the finish reads / overwrites them
+  if (nb <= static_cast<unsigned>(D.small_finish))  // (uniform)
+    k1_finish_small(lsrc, k, bb, nb, k1_lds, g, deal, D.min_pts, D.eig_ratio, D.sorted_idx, D.recs, D.centroids, lut, D.bucket_base + K + 1);
+  else
+    k1_finalize_bucket(lsrc, k, bb, nb, k1_lds, g, deal, C, D.min_pts, D.lds_cap, D.wmax, D.sorted_idx,
+                       K1RecordFin{D.min_pts, D.eig_ratio, D.recs, D.centroids, lut, &g}, D.bucket_base + K + 1, D.scratch, static_cast<unsigned>(n),
+                       nullptr);
+}
+
+// ---------------------------------------------------------------------------
 // Record compaction of a bucket-form build.  k1_finalize numbers a voxel's record by where its points sit in the bucket
 // order (unique without a scan over voxels) -- slots with gaps, bucket by bucket.  The evaluation kernels gather records
 // through the look-up table for points that arrive in lattice order, and they run measurably faster (+5 % on the headline
@@ -2474,6 +2669,45 @@ hipError_t launch_grid_build_small(const float4* pts, int n, int dense, const Gr
   hipLaunchKernelGGL(k1_small, dim3(K), dim3(kSmallThreads), fin_lds(lds_cap) + list_bytes, stream, pts, n, dense, g, P.shift, K, C, min_pts, eig_ratio,
                      lds_cap, wmax, list_cap, static_cast<unsigned>(fin_lds(lds_cap) / sizeof(unsigned)), small_finish, S.bucket_base, S.bpts, sorted_idx, recs,
                      centroids, lut, S.bucket_base + K + 1, S.order, counts, S.stamps);
+  return hipGetLastError();
+}
+
+// k1_small's launch parameters for one cloud (launch_grid_build_small's, and each target's of k1_small_multi); false: the
+// finish's LDS does not fit.  lists: kMultiWaves lists holding as many points in all as k1_small's kSmallWaves lists.
+bool small_build_desc(int n, const GridBuildPlan& P, SmallBuildDesc& D, size_t* lds_bytes) {
+  const int K = P.n_buckets, C = P.cells_per_bucket;
+  const int wmax = std::min(C, 1024);
+  static const int list_env = [] { const char* v = getenv("NDT_K1_SMALL_LIST"); return v ? std::max(1, atoi(v)) : 0; }();
+  const int list_cap = (list_env > 0 ? list_env : 384) * kSmallWaves / kMultiWaves;
+  const size_t list_bytes = static_cast<size_t>(kMultiWaves) * list_cap * sizeof(float4);
+  auto fin_lds = [&](int cap) { return ((static_cast<size_t>(3) * C + 3 * static_cast<size_t>(cap)) * sizeof(unsigned) + 5 * static_cast<size_t>(wmax) * 2 + 15) / 16 * 16; };
+  int lds_cap = kK1LdsCap;
+  while (lds_cap > 256 && fin_lds(lds_cap) + list_bytes > kK1MaxDynamicLds) lds_cap -= 256;
+  static const int cap_env = [] { const char* v = getenv("NDT_K1_LDS_CAP"); return v ? std::max(256, atoi(v)) / 256 * 256 : 0; }();
+  if (cap_env > 0) lds_cap = std::min(lds_cap, cap_env);
+  if (fin_lds(lds_cap) + list_bytes > kK1MaxDynamicLds) return false;
+  static const int small_finish = [] { const char* v = getenv("NDT_K1_SMALL_FINISH"); return v ? std::max(0, std::min(kSmallFinish, atoi(v))) : kSmallFinish; }();
+  D.n = n;
+  D.map = P.shift;
+  D.K = K;
+  D.C = C;
+  D.lds_cap = lds_cap;
+  D.wmax = wmax;
+  D.list_cap = list_cap;
+  D.fin_words = static_cast<unsigned>(fin_lds(lds_cap) / sizeof(unsigned));
+  D.small_finish = small_finish;
+  *lds_bytes = fin_lds(lds_cap) + list_bytes;
+  return true;
+}
+hipError_t launch_grid_build_small_multi(const SmallBuildDesc* d_descs, int n_targets, int max_K, size_t lds_bytes, hipStream_t stream) {
+  if (n_targets <= 0) return hipSuccess;
+  if (lds_bytes > kK1MaxDynamicLds || max_K <= 0 || n_targets > 65535) return hipErrorInvalidValue;
+  static bool once = [] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k1_small_multi), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kK1MaxDynamicLds));
+    return true;
+  }();
+  (void)once;
+  hipLaunchKernelGGL(k1_small_multi, dim3(max_K, n_targets), dim3(kBlock), lds_bytes, stream, d_descs);
   return hipGetLastError();
 }
 

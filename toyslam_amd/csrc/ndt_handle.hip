@@ -8,6 +8,8 @@ void ndt_context::release_buffers() {
   source.reset();
   map_scan.reset();
   grid.reset();
+  pairs_grids.clear();
+  pair_views.release();
   partials.release();
   ticket.release();
   batch_out.release();

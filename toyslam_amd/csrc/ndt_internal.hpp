@@ -418,6 +418,10 @@ struct ndt_context {
   bool is_batch_worker = false;
   int batch_groups_wanted = 0;  // ndt_set_batch_groups: 0 = automatic
   std::vector<ndt_context*> batch_workers;  // worker handles of those groups (own stream and staging each; grid shared)
+  // ndt_align_pairs*: the grid of every cloud the last pairs call used as a target (null for the others), and the per-member
+  // GridView table its lock-step kernels read (ndt_pairs.hip)
+  std::vector<std::shared_ptr<DeviceGrid>> pairs_grids;
+  DevBuf<ndt::GridView> pair_views;
 
   ~ndt_context() {
     for (ndt_context* w : batch_workers) delete w;
@@ -498,7 +502,18 @@ ndt_status order_range(ndt_context* h, const float4* d_pts, size_t n, float pitc
                        const BBox* known_bbox = nullptr);
 ndt_status order_batch(ndt_context* h, DeviceCloud* c, const size_t* offsets, size_t n_scans);
 ndt_status order_cloud(ndt_context* h, DeviceCloud* c, const size_t* offsets, size_t n_scans);
+struct GridHead {
+  std::shared_ptr<DeviceGrid> g;  // geometry set
+  int n = 0;
+  size_t max_leaves = 0, max_cand = 0;
+  bool sparse = false, done = true;
+};
+ndt_status grid_head(ndt_context* h, GridHead& hd);
 ndt_status build_grid(ndt_context* h);
+// grids of many targets (ndt_align_pairs): every one the small form takes from ONE k1_small_multi launch, the others through
+// build_grid; out[i] = the grid of targets[i], bit for bit what build_grid makes of it.  *n_small: how many took the launch
+ndt_status build_grids(ndt_context* h, const std::vector<std::shared_ptr<DeviceCloud>>& targets, int is_dense,
+                       std::vector<std::shared_ptr<DeviceGrid>>& out, size_t* n_small);
 ndt_status maybe_compact_records(ndt_context* h, bool eager);
 ndt_status grid_counts(ndt_context* h, DeviceGrid* g);
 ndt_status ensure_cell2leaf(ndt_context* h, DeviceGrid* g);
@@ -510,6 +525,7 @@ ndt_status filter_slots(ndt_handle h, int which, FilterPending& P);
 ndt_status voxel_filter_enqueue(ndt_handle h, hipStream_t st, const float4* d_in, size_t n, int is_dense, float leaf, float4* d_out,
                                 const BBox& bb, FilterPending& P);
 void voxel_filter_finish(const FilterPending& P, size_t* n_out, DeviceCloud* boxes);
+ndt_status cloud_use_on(ndt_handle h, DeviceCloud* c);  // an ndt_cloud made on another stream: wait for it, remember the reader
 // out_boxes: the result's bounding boxes as DeviceCloud keeps them ([2][3] min, [2][3] max), or null
 ndt_status voxel_filter_device(ndt_handle h, const float4* d_in, size_t n, int is_dense, float leaf, float4* d_out,
                                size_t* n_out, bool* overflow, const BBox* known_bbox = nullptr, DeviceCloud* out_boxes = nullptr);
@@ -528,6 +544,22 @@ ndt_status server_evaluate(ndt_context* h, const ndt::EvalRequest& rq, const ndt
                            double* nn_total, bool* served);
 bool server_enabled();
 // ---- ndt_batch.hip
+// The members of one lock-step loop: where each local member's source points lie and, for ndt_align_pairs*, which grid it is
+// evaluated against (views == null: the handle's grid for every member, the map-build batch)
+struct LockStepMembers {
+  const float4* pts = nullptr;     // the ordered (or raw) concatenated sources
+  std::vector<int> offset, count;  // per local member: its segment of pts
+  std::vector<size_t> n_raw;       // per local member: its points as the caller gave them (transformation_probability's N)
+  const ndt::GridView* views = nullptr;  // per local member (host copy; uploaded by lock_step)
+  const char* empty = nullptr;           // per local member: its grid has no voxel (its rows are zero, nothing is launched)
+};
+ndt_status lock_step(ndt_context* h, const LockStepMembers& m, size_t n_local, const float* guesses, float* final_T, int* conv,
+                     int* iters, double* tprob, size_t first = 0, size_t total = 0);
+size_t batch_group_count(const ndt_context* h, size_t n_members);
+// runs run(worker, lo, hi) for member ranges [lo, hi) of n_members, one worker handle and host thread per group (grid and
+// parameters of h copied), and gathers the workers' statistics into h; pts_of(lo, hi): the points of those members
+ndt_status run_groups(ndt_context* h, size_t n_members, size_t groups, const std::function<double(size_t, size_t)>& pts_of,
+                      const std::function<ndt_status(ndt_context*, size_t, size_t)>& run);
 ndt_status comm_allreduce(ndt_context* h, double* d_buf, size_t n_doubles);
 void server_mark(ndt_context* h, bool running);
 

@@ -169,6 +169,29 @@ bool grid_build_small_applies(int n_points, const GridBuildPlan& plan);
 hipError_t launch_grid_build_small(const float4* pts, int n, int dense, const GridGeom& g, const GridBuildPlan& plan, int min_pts,
                                    double eig_ratio, const GridBuildScratch& scratch, int* sorted_idx, VoxelRec* recs, VoxelSide* centroids,
                                    int* lut, unsigned* counts, hipStream_t stream);
+// k1_small over many clouds in one launch (ndt_align_pairs): one descriptor per cloud, blockIdx.y = cloud.  The same records,
+// table, bucketed points and counts as launch_grid_build_small gives that cloud.  small_build_desc fills the launch
+// parameters of a cloud (n, map .. small_finish) and its dynamic LDS; the caller fills the rest.
+struct SmallBuildDesc {
+  const float4* pts;
+  int n, dense;
+  GridGeom g;
+  int map, K, C, min_pts;
+  double eig_ratio;
+  int lds_cap, wmax, list_cap;
+  unsigned fin_words;
+  int small_finish;
+  unsigned* bucket_base;  // [K + 1] bases + [K] valid voxels per bucket
+  float4* bpts;
+  int* sorted_idx;
+  VoxelRec* recs;
+  VoxelSide* centroids;
+  int* lut;
+  unsigned* scratch;      // [5 n]
+  unsigned* counts;
+};
+bool small_build_desc(int n_points, const GridBuildPlan& plan, SmallBuildDesc& desc, size_t* lds_bytes);
+hipError_t launch_grid_build_small_multi(const SmallBuildDesc* d_descs, int n_targets, int max_K, size_t lds_bytes, hipStream_t stream);
 hipError_t launch_grid_build_buckets(const float4* pts, int n, int dense, const GridGeom& g, const GridBuildPlan& plan, int min_pts,
                                      double eig_ratio, const GridBuildScratch& scratch, int* sorted_idx, VoxelRec* recs, VoxelSide* centroids,
                                      int* lut, unsigned* counts, hipStream_t stream);
@@ -286,6 +309,10 @@ hipError_t launch_publish_rows(const double* d_rows, int n_rows, double* host_ro
 // all live scans of a lock-step batch step in one launch, kinds mixed (descs[scan].kind, .pad = rows written)
 hipError_t launch_batch_step(const float4* src, const GridView& gv, int search, const ScanDesc* descs, const int* active,
                              int n_active, int max_blocks, int n_blocks, double* partials, hipStream_t stream);
+// a lock-step step of ndt_align_pairs* (ndt_pairs_kernels.hip): member m is evaluated against views[m] (its own target's
+// grid); kind 0 / 1 / 2 = every member in `active` wants that kind, -1 = kinds mixed (descs[m].kind).  Rows as launch_batch_step
+hipError_t launch_pairs_step(const float4* src, const GridView* views, int search, int kind, const ScanDesc* descs,
+                             const int* active, int n_active, int max_blocks, int n_blocks, double* partials, hipStream_t stream);
 // cell_range (pre-set to 0) and row_any (pre-set to 0, div_y * div_z entries) of a built grid
 hipError_t launch_cell_ranges(const int* leaf_cell, const unsigned* leaf_start, const int* leaf_count, int n_leaves, uint2* cell_range,
                               int div_x, int* row_any, hipStream_t stream);

@@ -77,6 +77,14 @@ class DeviceCloud:
             pass
 
 
+def pairs_array(n_clouds, pairs=None):
+    """(P, 2) int32 C-contiguous (target, source) cloud indices; None = the consecutive pairs (k-1, k) of n_clouds clouds."""
+    if pairs is None:
+        return np.ascontiguousarray(np.stack([np.arange(0, max(n_clouds - 1, 0)), np.arange(1, max(n_clouds, 1))], axis=1),
+                                    dtype=np.int32).reshape(-1, 2)
+    return np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+
+
 class NormalDistributionsTransform:
     """Drop-in shaped like pclomp::NormalDistributionsTransform<PointT, PointT>."""
 
@@ -341,6 +349,60 @@ class NormalDistributionsTransform:
                  _f(g) if g is not None else None, _f(T), _i(conv), _i(it), _d(tp)))
         return dict(T=np.stack([_from_colmajor(T[k]) for k in range(B)]), converged=conv.astype(bool),
                     iterations=it, trans_probability=tp)
+
+    def alignPairs(self, clouds, pairs=None, guesses=None, is_dense=True):
+        """Register (target, source) pairs of clouds in lock-step, every pair against the grid of its own target
+        (ndt_align_pairs*).  clouds: list of (N_k, >=3) host arrays, or of DeviceCloud (ndt_cloud); pairs: (P, 2) cloud
+        indices (target, source), None = the consecutive pairs (k-1, k); at most 65535 pairs per call.  Returns alignBatch's
+        dict, one entry per pair."""
+        resident = [isinstance(c, DeviceCloud) for c in clouds]
+        if any(resident) and not all(resident):
+            raise ValueError("clouds must be all DeviceCloud or all host arrays, not a mix")
+        P = pairs_array(len(clouds), pairs)
+        n = P.shape[0]
+        g = None
+        if guesses is not None:
+            g = np.ascontiguousarray(np.stack([_colmajor(x) for x in guesses]))
+            if g.shape[0] != n:
+                raise ValueError("one guess per pair")
+        T = np.zeros((n, 16), dtype=np.float32)
+        conv = np.zeros(n, dtype=np.int32)
+        it = np.zeros(n, dtype=np.int32)
+        tp = np.zeros(n, dtype=np.float64)
+        out = (_f(g) if g is not None else None, _f(T), _i(conv), _i(it), _d(tp))
+        if clouds and all(isinstance(c, DeviceCloud) for c in clouds):
+            arr = (C.c_void_p * len(clouds))(*[c._c for c in clouds])
+            check(self._L.ndt_align_pairs_clouds(self._h, arr, len(clouds), int(is_dense), _i(P), n, *out))
+        else:
+            cols = {np.asarray(c).shape[1] for c in clouds}
+            if len(cols) > 1:
+                raise ValueError("all clouds must have the same column count")
+            cat = _cloud(np.concatenate(clouds, axis=0)) if clouds else np.zeros((0, 4), np.float32)
+            offsets = np.zeros(len(clouds) + 1, dtype=np.uintp)
+            offsets[1:] = np.cumsum([len(c) for c in clouds])
+            check(self._L.ndt_align_pairs(self._h, cat.ctypes.data, offsets.ctypes.data_as(C.POINTER(C.c_size_t)), len(clouds),
+                                          cat.shape[1] * 4, int(is_dense), _i(P), n, *out))
+        return dict(T=np.stack([_from_colmajor(T[k]) for k in range(n)]) if n else np.zeros((0, 4, 4), np.float32),
+                    converged=conv.astype(bool), iterations=it, trans_probability=tp)
+
+    def pairsGrid(self, c):
+        """The grid the last alignPairs built for target cloud c, in the layout of grid()."""
+        nl, nv = C.c_size_t(0), C.c_size_t(0)
+        check(self._L.ndt_pairs_grid_size(self._h, int(c), C.byref(nl), C.byref(nv)))
+        n = nl.value
+        idx = np.zeros(n, dtype=np.int64)
+        npts = np.zeros(n, dtype=np.int32)
+        mean = np.zeros((n, 3))
+        cov = np.zeros((n, 3, 3))
+        icov = np.zeros((n, 3, 3))
+        evals = np.zeros((n, 3))
+        if n:
+            check(self._L.ndt_pairs_grid_dump(self._h, int(c), idx.ctypes.data_as(C.POINTER(C.c_int64)), _i(npts), _d(mean),
+                                              _d(cov), _d(icov), _d(evals)))
+        mb, xb, db = (np.zeros(3, dtype=np.int32) for _ in range(3))
+        check(self._L.ndt_pairs_grid_info(self._h, int(c), _i(mb), _i(xb), _i(db)))
+        return dict(idx=idx, n=npts, mean=mean, cov=cov, icov=icov, evals=evals, min_b=mb, max_b=xb, div_b=db,
+                    n_valid=nv.value)
 
     def alignBatchSharded(self, clouds=None, first_scan=0, total_scans=None, guesses=None, device_ptr=None, offsets=None,
                           stride_bytes=16):
