@@ -4,11 +4,15 @@
 // the node's settings (resolution 1.0, step 0.1, epsilon 0.01, 64 iterations, DIRECT7) -- the registrations do not depend
 // on each other once the clouds are known.  A pair that did not converge counts as identity (:120-123); the poses are
 // chained with ndt_host_chain_pose.  Printed per pair: "Transform k-1 to k" and "TransformSum", then one timing line.
+// --fitness: also the getFitnessScore of every pair at its final transformation, all from one ndt_pairs_fitness_scores
+// call right after the pairs call ("fitness k-1 to k: <value>", 17 significant digits), and that call's time.
 //
-//   pair_sequence <pcd_directory>
+//   pair_sequence <pcd_directory> [--fitness]
+#include <cfloat>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "ndt_mi355.h"
@@ -31,9 +35,10 @@ static double since(clock_type::time_point a) { return std::chrono::duration<dou
 
 int main(int argc, char** argv) {
   if (argc < 2) {
-    std::printf("usage: pair_sequence <pcd_directory>\n");
+    std::printf("usage: pair_sequence <pcd_directory> [--fitness]\n");
     return 0;
   }
+  const bool want_fitness = argc > 2 && std::strcmp(argv[2], "--fitness") == 0;
   const float kLeaf = 0.5f;
   ndt_handle h = nullptr;
   CHECK(ndt_create(0, &h));
@@ -87,6 +92,13 @@ int main(int argc, char** argv) {
   const auto t_align = clock_type::now();
   CHECK(ndt_align_pairs_clouds(h, clouds.data(), clouds.size(), 1, pairs.data(), n_pairs, nullptr, T.data(), conv.data(), iters.data(), nullptr));
   const double align_ms = since(t_align);
+  std::vector<double> fitness(n_pairs);
+  double fitness_ms = 0;
+  if (want_fitness && n_pairs) {
+    const auto t_fit = clock_type::now();
+    CHECK(ndt_pairs_fitness_scores(h, nullptr, DBL_MAX /* PCL's default */, fitness.data()));
+    fitness_ms = since(t_fit);
+  }
 
   // ---- pose chain
   static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
@@ -104,9 +116,12 @@ int main(int argc, char** argv) {
     print_matrix(title, Tk);
     print_matrix("TransformSum:", sum.data());
   }
+  if (want_fitness)
+    for (size_t k = 0; k < n_pairs; k++) std::printf("fitness %zu to %zu: %.17g\n", k, k + 1, fitness[k]);
   std::printf("\nclouds %zu  pairs %zu (not converged %zu)\n", clouds.size(), n_pairs, not_converged);
   std::printf("time: read + prefilter %.2f ms, pairs call %.2f ms (%.1f pairs/s)\n", load_ms, align_ms,
               align_ms > 0 ? 1e3 * static_cast<double>(n_pairs) / align_ms : 0.0);
+  if (want_fitness) std::printf("time: fitness call %.3f ms\n", fitness_ms);
   for (ndt_cloud c : clouds) ndt_cloud_release(c);
   ndt_destroy(h);
   return 0;

@@ -328,6 +328,28 @@ ndt_status ndt_pairs_grid_size(ndt_handle h, size_t cloud, size_t* n_leaves, siz
 ndt_status ndt_pairs_grid_info(ndt_handle h, size_t cloud, int* min_b /*3*/, int* max_b /*3*/, int* div_b /*3*/);
 ndt_status ndt_pairs_grid_dump(ndt_handle h, size_t cloud, int64_t* idx, int* nr_points, double* mean, double* cov,
                                double* icov, double* evals);
+/* getFitnessScore of every pair of the last ndt_align_pairs* call: pair k's source moved by transforms[16k..] (column-major,
+ * NULL = that call's final transformations) against pair k's target, as ndt_get_fitness_score would compute it on a handle
+ * holding that target and source after an align ending at that transform -- the same bits.  All pairs in one launch.
+ * NDT_ERR_NO_INPUT when the last pairs call failed or had no pair (the sources, grids and transformations a successful
+ * call keeps are dropped when the next one begins, or by ndt_destroy); NDT_ERR_INVALID for a NULL handle or fitness. */
+ndt_status ndt_pairs_fitness_scores(ndt_handle h, const float* transforms /* n_pairs*16 or NULL */, double max_range,
+                                    double* fitness /* n_pairs */);
+/* the number of pairs ndt_pairs_fitness_scores would score (those of the last pairs call; 0 after a failed or empty one):
+ * how many transforms it reads and fitness values it writes */
+ndt_status ndt_pairs_count(ndt_handle h, size_t* n_pairs);
+/* the same for n_scans clouds against the handle's target (ndt_align_batch's layout; transforms required).  Keeps nothing
+ * and runs no collective, even on a handle with a communicator.  NDT_ERR_INVALID before any device work: NULL handle,
+ * offsets or (with scans) transforms / fitness, offsets that decrease, a bad stride, more than 65535 scans;
+ * NDT_ERR_NO_INPUT without a target. */
+ndt_status ndt_batch_fitness_scores(ndt_handle h, const void* pts, const size_t* offsets /* n_scans+1 */, size_t n_scans,
+                                    size_t stride_bytes, const float* transforms /* n_scans*16 */, double max_range,
+                                    double* fitness /* n_scans */);
+ndt_status ndt_batch_fitness_scores_device(ndt_handle h, const void* d_pts, const size_t* offsets, size_t n_scans,
+                                           size_t stride_bytes, const float* transforms, double max_range, double* fitness);
+/* diagnostics: the k_fitness_multi launches of the handle's last ndt_pairs_fitness_scores / ndt_batch_fitness_scores* call
+ * and the blocks of the largest (its partial rows, kEvalStride doubles each, are all that call held at once) */
+ndt_status ndt_diag_fitness_launches(ndt_handle h, size_t* launches, size_t* max_blocks);
 
 /* ---- multi-GPU (one process per GPU, RCCL over xGMI) ---------------------------
  * The reference is a single process (ndt_omp_impl.hpp:206 is its only parallel construct); this is the exchange step

@@ -108,6 +108,11 @@ SIGNATURES = {
     "ndt_pairs_grid_size": (C.c_int, [vp, C.c_size_t, szp, szp]),
     "ndt_pairs_grid_info": (C.c_int, [vp, C.c_size_t, ip, ip, ip]),
     "ndt_pairs_grid_dump": (C.c_int, [vp, C.c_size_t, C.POINTER(C.c_int64), ip, dp, dp, dp, dp]),
+    "ndt_pairs_fitness_scores": (C.c_int, [vp, fp, C.c_double, dp]),
+    "ndt_pairs_count": (C.c_int, [vp, szp]),
+    "ndt_diag_fitness_launches": (C.c_int, [vp, szp, szp]),
+    "ndt_batch_fitness_scores": (C.c_int, [vp, vp, szp, C.c_size_t, C.c_size_t, fp, C.c_double, dp]),
+    "ndt_batch_fitness_scores_device": (C.c_int, [vp, vp, szp, C.c_size_t, C.c_size_t, fp, C.c_double, dp]),
     "ndt_align_batch_sharded": (C.c_int, [vp, vp, szp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, fp, fp, ip, ip, dp]),
     "ndt_align_batch_sharded_device": (C.c_int, [vp, vp, szp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, fp, fp, ip, ip, dp]),
     "ndt_comm_get_unique_id": (C.c_int, [vp]),

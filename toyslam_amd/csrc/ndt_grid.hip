@@ -921,6 +921,78 @@ ndt_status ensure_cell2leaf(ndt_context* h, DeviceGrid* g) {
   }
   return NDT_OK;
 }
+// grid_counts + ensure_cell2leaf of many grids (getFitnessScore of many members): every counts read-back (with the leaf
+// numbering of a bucket-form build) queued, one wait; then every missing index queued, one wait -- two synchronisations
+// in all instead of up to two per grid.  The tables and flags are those of the single-grid calls, which find the work done.
+// The grids are locked in address order (fit_mu), so two callers that share grids cannot deadlock.
+ndt_status ensure_indices(ndt_context* h, const std::vector<DeviceGrid*>& grids) {
+  std::vector<DeviceGrid*> gs;
+  for (DeviceGrid* g : grids)
+    if (g && !g->empty) gs.push_back(g);
+  std::sort(gs.begin(), gs.end());
+  gs.erase(std::unique(gs.begin(), gs.end()), gs.end());
+  std::vector<std::unique_lock<std::mutex>> locks;
+  locks.reserve(gs.size());
+  for (DeviceGrid* g : gs) locks.emplace_back(g->fit_mu);
+  std::vector<DeviceGrid*> need;
+  for (DeviceGrid* g : gs)
+    if (!g->counts_known) need.push_back(g);
+  if (!need.empty()) {
+    ndt_status s = ensure_host_rows(h, (4 * need.size() * sizeof(unsigned) + sizeof(double) * ndt::kEvalStride - 1) /
+                                           (sizeof(double) * ndt::kEvalStride));
+    if (s) return s;
+    unsigned* c = reinterpret_cast<unsigned*>(h->host_result);
+    std::vector<std::unique_ptr<DevBuf<unsigned>>> scratch;  // (kept until the wait)
+    for (size_t i = 0; i < need.size(); i++) {
+      DeviceGrid* g = need[i];
+      if (g->leaves_pending) {
+        const size_t K = static_cast<size_t>(g->plan.n_buckets);
+        scratch.emplace_back(new DevBuf<unsigned>());
+        HIP_TRY(scratch.back()->reserve(4 * K + 4));
+        HIP_TRY(ndt::launch_grid_leaves(g->geom, g->plan, g->min_pts, g->bpts.p, g->bucket_base.p, scratch.back()->p, g->leaf_cell.p,
+                                        g->leaf_start.p, g->leaf_count.p, g->leaf_rec.p, g->counts.p, g->lut.p, h->stream,
+                                        g->index_form ? g->target->pts.p : nullptr));
+      }
+      HIP_TRY(hipMemcpyAsync(c + 4 * i, g->counts.p, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (size_t i = 0; i < need.size(); i++) {
+      DeviceGrid* g = need[i];
+      if (g->leaves_pending) {
+        g->leaves_pending = false;
+        g->bpts.release();
+        g->bucket_base.release();
+      }
+      g->n_sorted = c[4 * i];
+      g->n_leaves = c[4 * i + 1];
+      g->n_cand = c[4 * i + 2];
+      g->n_valid = c[4 * i + 3];
+      g->counts_known = true;
+    }
+  }
+  bool queued = false;
+  for (DeviceGrid* g : gs) {
+    if (g->have_cell2leaf || g->n_sorted == 0) continue;  // (nothing to search: fitness_impl builds no index either)
+    HIP_TRY(g->cell_range.reserve(static_cast<size_t>(g->geom.n_cells)));
+    HIP_TRY(hipMemsetAsync(g->cell_range.p, 0, static_cast<size_t>(g->geom.n_cells) * sizeof(uint2), h->stream));
+    const size_t n_rows = static_cast<size_t>(g->geom.div_b[1]) * static_cast<size_t>(g->geom.div_b[2]);
+    HIP_TRY(g->row_any.reserve(n_rows));
+    HIP_TRY(hipMemsetAsync(g->row_any.p, 0, n_rows * sizeof(int), h->stream));
+    HIP_TRY(ndt::launch_cell_ranges(g->leaf_cell.p, g->leaf_start.p, g->leaf_count.p, static_cast<int>(g->n_leaves), g->cell_range.p,
+                                    g->geom.div_b[0], g->row_any.p, h->stream));
+    HIP_TRY(g->cell_pts.reserve(g->target->n));
+    HIP_TRY(ndt::launch_gather_points(g->target->pts.p, g->sorted_idx.p, g->counts.p, static_cast<int>(g->target->n), g->cell_pts.p,
+                                      h->stream));
+    queued = true;
+  }
+  if (queued) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (DeviceGrid* g : gs)
+      if (g->n_sorted) g->have_cell2leaf = true;
+  }
+  return NDT_OK;
+}
+
 // slack of the shell bound: the build-time and search-time cell indices of a coordinate can differ
 // at cell borders by rounding (SURVEY 8a trap 2) -- a few ulps of the largest coordinate
 float index_slack(const DeviceGrid* g) {

@@ -421,6 +421,14 @@ struct ndt_context {
   // ndt_align_pairs*: the grid of every cloud the last pairs call used as a target (null for the others), and the per-member
   // GridView table its lock-step kernels read (ndt_pairs.hip)
   std::vector<std::shared_ptr<DeviceGrid>> pairs_grids;
+  // ... and, for ndt_pairs_fitness_scores, every pair's source (caller's point order), its target's grid and its final
+  // transformation (column-major, 16 per pair); empty after a failed or empty pairs call
+  std::vector<std::shared_ptr<DeviceCloud>> pairs_sources;
+  std::vector<std::shared_ptr<DeviceGrid>> pairs_targets;
+  std::vector<float> pairs_T;
+  // the last many-member getFitnessScore (fitness_many): its launches and the blocks of the largest one (partial rows
+  // held at once), for ndt_diag_fitness_launches
+  size_t fit_launches = 0, fit_max_blocks = 0;
   DevBuf<ndt::GridView> pair_views;
 
   ~ndt_context() {
@@ -517,10 +525,20 @@ ndt_status build_grids(ndt_context* h, const std::vector<std::shared_ptr<DeviceC
 ndt_status maybe_compact_records(ndt_context* h, bool eager);
 ndt_status grid_counts(ndt_context* h, DeviceGrid* g);
 ndt_status ensure_cell2leaf(ndt_context* h, DeviceGrid* g);
+ndt_status ensure_indices(ndt_context* h, const std::vector<DeviceGrid*>& grids);  // both of the above for many grids, two waits in all
 float index_slack(const DeviceGrid* g);
 ndt_status download_records(ndt_context* h, const float4* d_src, size_t n, void* out, size_t out_stride);
 void fill_point_index(const DeviceGrid* g, ndt::PointIndex& ix);
 ndt_status fitness_impl(ndt_context* h, const float4* d_src, int n, const float* T_colmajor, double max_range, double* fitness);
+// getFitnessScore of many (source, target grid, transform) members: the source's n points at src, moved by the column-major T,
+// against g's point index.  out[k] is what fitness_impl returns for member k on a handle holding that grid (ndt_fitness.hip)
+struct FitnessJob {
+  const DeviceGrid* g = nullptr;
+  const float4* src = nullptr;
+  size_t n = 0;
+  const float* T = nullptr;  // column-major 4x4
+};
+ndt_status fitness_many(ndt_context* h, const std::vector<FitnessJob>& jobs, double max_range, double* out);
 ndt_status filter_slots(ndt_handle h, int which, FilterPending& P);
 ndt_status voxel_filter_enqueue(ndt_handle h, hipStream_t st, const float4* d_in, size_t n, int is_dense, float leaf, float4* d_out,
                                 const BBox& bb, FilterPending& P);

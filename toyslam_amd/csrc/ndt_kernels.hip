@@ -5,8 +5,8 @@
 //  K2  per-evaluation score / gradient / Hessian (computeDerivatives, ndt_omp_impl.hpp:179-285 with updateDerivatives
 //      :484-537 fused with the f32 point transform): k_derivatives (one launch per evaluation, also over a whole lock-step
 //      batch), k_batch_step (mixed-kind batch steps), the all-f64 Hessian k_hessian64 (computeHessian :540-645), k_reduce
-//      (fixed-order sum of the per-block rows), calculateScore (:935-983), getFitnessScore (k_fitness) and the search index
-//      it walks (k_cell_ranges, k_gather_points).
+//      (fixed-order sum of the per-block rows), calculateScore (:935-983), getFitnessScore (k_fitness; k_fitness_multi +
+//      k_fitness_reduce for many members in one launch) and the search index it walks (k_cell_ranges, k_gather_points).
 //
 // Gather work: no MFMA (there is no dense contraction).  Loads are 16 B per lane (float4 points, 3 x dwordx4 per 64-B
 // voxel record), the LUT probe + record gather is served from L2 / Infinity Cache for the target sizes of interest, and the
@@ -234,6 +234,38 @@ __global__ __launch_bounds__(kReduceThreads) void k_reduce(const double* __restr
   }
 }
 
+// k_fitness_multi's rows -> out[m] = {sum of d^2, count} of member m: k_reduce's order (32 strided parts, 4 loads in
+// flight, then the parts in order) over the member's rows, for the two slots getFitnessScore reads
+__global__ __launch_bounds__(kReduceThreads) void k_fitness_reduce(const double* __restrict__ partials, const int* __restrict__ starts,
+                                                                   double* __restrict__ out) {
+  const int m = blockIdx.x;
+  const int rows = starts[m + 1] - starts[m];
+  constexpr int kParts = kReduceThreads / kEvalStride;  // 32
+  const int k = threadIdx.x % kEvalStride, part = threadIdx.x / kEvalStride;
+  const double* base = partials + static_cast<size_t>(starts[m]) * kEvalStride;
+  double v = 0.0;
+  if (k < 2) {
+    int b = part;
+    for (; b + 3 * kParts < rows; b += 4 * kParts) {
+      const double a0 = base[static_cast<size_t>(b) * kEvalStride + k];
+      const double a1 = base[static_cast<size_t>(b + kParts) * kEvalStride + k];
+      const double a2 = base[static_cast<size_t>(b + 2 * kParts) * kEvalStride + k];
+      const double a3 = base[static_cast<size_t>(b + 3 * kParts) * kEvalStride + k];
+      v += a0; v += a1; v += a2; v += a3;
+    }
+    for (; b < rows; b += kParts) v += base[static_cast<size_t>(b) * kEvalStride + k];
+  }
+  __shared__ double s[kParts][2];
+  if (k < 2) s[part][k] = v;
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    double t = 0.0;
+#pragma unroll
+    for (int p = 0; p < kParts; p++) t += s[p][threadIdx.x];
+    out[2 * static_cast<size_t>(m) + threadIdx.x] = t;
+  }
+}
+
 // Rows of the exchange buffer (after the all-reduce of a sharded lock-step) -> the pinned host block the host polls:
 // every row, then its sequence word in slot 31 (publish_row).
 __global__ __launch_bounds__(kWave) void k_publish_rows(const double* __restrict__ rows, double* __restrict__ out,
@@ -286,10 +318,11 @@ __global__ __launch_bounds__(kBlock) void k_gather_points(const float4* __restri
 }
 
 
-__global__ __launch_bounds__(kBlock) void k_fitness(const float4* __restrict__ src, int n, EvalParams P, PointIndex ix,
-                                                    double max_range, double* __restrict__ partials) {
+// getFitnessScore of one source against one index, block `blk` of the `nblk` that serve it (k_fitness: the launch's own
+// block and grid size; k_fitness_multi: the block within its member and the member's block count): its row -> out
+__device__ __forceinline__ void fitness_body(const float4* __restrict__ src, int n, const float (&T)[12], const PointIndex& ix,
+                                             double max_range, int blk, int nblk, double* __restrict__ out, double* lds) {
   constexpr int kTeams = kBlock / kTeam;
-  __shared__ double lds[(kBlock / kWave) * 32];
   double acc[kNumAcc];
 #pragma unroll
   for (int k = 0; k < kNumAcc; k++) acc[k] = 0.0;
@@ -304,7 +337,7 @@ __global__ __launch_bounds__(kBlock) void k_fitness(const float4* __restrict__ s
   // The far queries of a scan come in runs (a wall the target does not cover), and a wave that held eight of them was the
   // kernel's whole duration while the rest of the chip sat idle.
   const int log_slots = 32 - __clz(max(n, 2) - 1), n_slots = 1 << log_slots;
-  for (int base = (blockIdx.x * (kBlock / kWave) + wave_in_block) * kTeamsPerWave; base < n_slots; base += gridDim.x * kTeams) {
+  for (int base = (blk * (kBlock / kWave) + wave_in_block) * kTeamsPerWave; base < n_slots; base += nblk * kTeams) {
     const int i = static_cast<int>(__brev(static_cast<unsigned>(base + team_in_wave)) >> (32 - log_slots));
     float tx = 0.f, ty = 0.f, tz = 0.f;
     bool live = i < n;  // uniform within a team
@@ -312,7 +345,7 @@ __global__ __launch_bounds__(kBlock) void k_fitness(const float4* __restrict__ s
       const float4 pt = src[i];
       live = finite3(pt.x, pt.y, pt.z);  // transformPointCloud leaves it non-finite; no neighbour to report
       if (live) {
-        xform_point(P.T, pt.x, pt.y, pt.z, tx, ty, tz);
+        xform_point(T, pt.x, pt.y, pt.z, tx, ty, tz);
         live = finite3(tx, ty, tz);
       }
     }
@@ -379,7 +412,45 @@ __global__ __launch_bounds__(kBlock) void k_fitness(const float4* __restrict__ s
       acc[1] += 1.0;
     }
   }
-  block_reduce_store<kNumAcc>(acc, partials + static_cast<size_t>(blockIdx.x) * kEvalStride, lds);
+  block_reduce_store<kNumAcc>(acc, out, lds);
+}
+
+__global__ __launch_bounds__(kBlock) void k_fitness(const float4* __restrict__ src, int n, EvalParams P, PointIndex ix,
+                                                    double max_range, double* __restrict__ partials) {
+  __shared__ double lds[(kBlock / kWave) * 32];
+  fitness_body(src, n, P.T, ix, max_range, blockIdx.x, gridDim.x, partials + static_cast<size_t>(blockIdx.x) * kEvalStride, lds);
+}
+
+// A device pointer stored in memory, read as a pointer into the global address space: the compiler can then tell where
+// it points, and the loads through it are global loads (as k_fitness's through its kernel arguments), not flat loads.
+template <class T>
+__device__ __forceinline__ const T* from_global(const T* const* slot) {
+  typedef const __attribute__((address_space(1))) T* GlobalPtr;
+  return (const T*)(GlobalPtr)(*reinterpret_cast<const uintptr_t*>(slot));
+}
+
+// Many members (source, index, transform) in one launch: member m owns blocks [starts[m], starts[m + 1]) and block b's row
+// is partials[b].  A block serves one member, found by a binary search of `starts` (block-uniform: scalar loads), so the
+// wave-wide far-query fallback of fitness_body stays uniform and every row is the one k_fitness would write.
+__global__ __launch_bounds__(kBlock) void k_fitness_multi(const FitnessMember* __restrict__ members, const int* __restrict__ starts,
+                                                          int n_members, double max_range, double* __restrict__ partials) {
+  __shared__ double lds[(kBlock / kWave) * 32];
+  const int b = blockIdx.x;
+  int lo = 0, hi = n_members - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (starts[mid] <= b) lo = mid;
+    else hi = mid - 1;
+  }
+  const int first = starts[lo], nblk = starts[lo + 1] - first;
+  const FitnessMember& M = members[lo];
+  PointIndex ix = M.ix;
+  ix.pts = from_global(&M.ix.pts);
+  ix.cell_range = from_global(&M.ix.cell_range);
+  ix.row_any = from_global(&M.ix.row_any);
+  ix.sorted_idx = from_global(&M.ix.sorted_idx);
+  ix.sorted_pts = from_global(&M.ix.sorted_pts);
+  fitness_body(from_global(&M.src), M.n, M.T, ix, max_range, b - first, nblk, partials + static_cast<size_t>(b) * kEvalStride, lds);
 }
 
 // calculateScore (ndt_omp_impl.hpp:935-983): cloud used as given, f64 throughout
@@ -564,6 +635,14 @@ hipError_t launch_fitness(const float4* src, int n, const float* T12, const Poin
   EvalParams P{};
   for (int i = 0; i < 12; i++) P.T[i] = T12[i];
   hipLaunchKernelGGL(k_fitness, dim3(n_blocks), dim3(kBlock), 0, stream, src, n, P, tgt, max_range, partials);
+  return hipGetLastError();
+}
+
+hipError_t launch_fitness_multi(const FitnessMember* members, const int* starts, int n_members, int n_blocks, double max_range,
+                                double* partials, double* sums, hipStream_t stream) {
+  if (n_members <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_fitness_multi, dim3(n_blocks), dim3(kBlock), 0, stream, members, starts, n_members, max_range, partials);
+  hipLaunchKernelGGL(k_fitness_reduce, dim3(n_members), dim3(kReduceThreads), 0, stream, partials, starts, sums);
   return hipGetLastError();
 }
 

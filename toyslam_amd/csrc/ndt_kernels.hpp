@@ -100,6 +100,14 @@ struct PointIndex {
   float slack = 0.f;  // build-time vs search-time cell index rounding (SURVEY 8a trap 2)
 };
 
+// One member of a many-member getFitnessScore launch (k_fitness_multi): its source, the index of its target, its transform.
+struct FitnessMember {
+  PointIndex ix;
+  const float4* src = nullptr;  // caller's order
+  int n = 0;
+  float T[12];  // row-major 3x4 f32
+};
+
 // Per-evaluation constants of computeDerivatives (ndt_omp_impl.hpp:179-285).
 struct EvalParams {
   float T[12];      // row-major 3x4 f32 transform applied to the source
@@ -319,6 +327,10 @@ hipError_t launch_cell_ranges(const int* leaf_cell, const unsigned* leaf_start, 
 // [PCL] getFitnessScore: team search over the target's point index (ndt_search.hpp); partials [n_blocks][kEvalStride]
 hipError_t launch_fitness(const float4* src, int n, const float* T12, const PointIndex& tgt, double max_range, int n_blocks,
                           double* partials, hipStream_t stream);
+// getFitnessScore of many members in one launch: member m (of n_members) takes blocks [starts[m], starts[m + 1]) of the
+// n_blocks = starts[n_members]; partials [n_blocks][kEvalStride]; sums[m] = {sum of d^2, count} (k_reduce's order over its rows)
+hipError_t launch_fitness_multi(const FitnessMember* members, const int* starts, int n_members, int n_blocks, double max_range,
+                                double* partials, double* sums, hipStream_t stream);
 // pts in the cell order of an index: out[q] = pts[sorted_idx[q]] for q < *d_n_sorted
 hipError_t launch_gather_points(const float4* pts, const int* sorted_idx, const unsigned* d_n_sorted, int n_max, float4* out,
                                 hipStream_t stream);

@@ -8,6 +8,8 @@
 //            grid a handle of its own would hold -- kept in h->pairs_grids until the next pairs call
 //   loop   : ndt_batch.hip's lock_step / run_groups with a per-member GridView table (k_pairs_step,
 //            ndt_pairs_kernels.hip); a pair whose target has no voxel gets zero rows, as a single registration does
+//   kept   : every pair's source (the caller's point order), its target's grid and its final transformation, until the next
+//            pairs call: ndt_pairs_fitness_scores (ndt_fitness.hip) scores the pairs from them
 // The handle's own target, source, grid and last result are not touched.
 #include "ndt_internal.hpp"
 
@@ -89,9 +91,11 @@ static ndt_status align_pairs_impl(ndt_handle h, const std::vector<std::shared_p
   m.views = views.data();
   m.empty = empty.data();
   // ---- lock-step: one loop, or independent groups on worker handles (ndt_set_batch_groups / NDT_BATCH_GROUPS, as a batch)
+  // (the final transformations land in a buffer of our own as well: ndt_pairs_fitness_scores wants them, the caller may not)
+  std::vector<float> T_all(16 * n_pairs);
   const size_t groups = batch_group_count(h, n_pairs);
-  if (groups <= 1 || h->profiling) return lock_step(h, m, n_pairs, guesses, final_T, conv, iters, tprob);
-  return run_groups(
+  if (groups <= 1 || h->profiling) s = lock_step(h, m, n_pairs, guesses, T_all.data(), conv, iters, tprob);
+  else s = run_groups(
       h, n_pairs, groups,
       [&](size_t lo, size_t hi) {
         double n = 0;
@@ -106,9 +110,28 @@ static ndt_status align_pairs_impl(ndt_handle h, const std::vector<std::shared_p
         part.n_raw.assign(m.n_raw.begin() + lo, m.n_raw.begin() + hi);
         part.views = m.views + lo;
         part.empty = m.empty + lo;
-        return lock_step(w, part, hi - lo, guesses ? guesses + 16 * lo : nullptr, final_T ? final_T + 16 * lo : nullptr,
+        return lock_step(w, part, hi - lo, guesses ? guesses + 16 * lo : nullptr, T_all.data() + 16 * lo,
                          conv ? conv + lo : nullptr, iters ? iters + lo : nullptr, tprob ? tprob + lo : nullptr);
       });
+  if (s) return s;
+  if (final_T) std::memcpy(final_T, T_all.data(), T_all.size() * sizeof(float));
+  // what ndt_pairs_fitness_scores needs: each pair's source as the caller gave it, its target's grid, its result
+  h->pairs_sources.resize(n_pairs);
+  h->pairs_targets.resize(n_pairs);
+  for (size_t k = 0; k < n_pairs; k++) {
+    h->pairs_sources[k] = clouds[pairs[2 * k + 1]];
+    h->pairs_targets[k] = grids[pairs[2 * k]];
+  }
+  h->pairs_T.swap(T_all);
+  return NDT_OK;
+}
+
+// the retained state of the last pairs call (ndt_pairs_fitness_scores), dropped when a new call begins
+static void pairs_forget(ndt_handle h) {
+  if (!h) return;
+  h->pairs_sources.clear();
+  h->pairs_targets.clear();
+  h->pairs_T.clear();
 }
 
 // runs fn with the pairs grid of cloud c standing in as the handle's grid (the inspection entries of a single grid)
@@ -130,6 +153,7 @@ extern "C" {
 ndt_status ndt_align_pairs(ndt_handle h, const void* pts, const size_t* offsets, size_t n_clouds, size_t stride_bytes,
                            int is_dense, const int* pairs, size_t n_pairs, const float* guesses, float* final_T, int* conv,
                            int* iters, double* tprob) {
+  pairs_forget(h);
   ndt_status s = pairs_checks(h, n_clouds, pairs, n_pairs);
   if (s) return s;
   if (n_clouds && !offsets) return fail(NDT_ERR_INVALID, "null offsets");
@@ -161,6 +185,7 @@ ndt_status ndt_align_pairs(ndt_handle h, const void* pts, const size_t* offsets,
 
 ndt_status ndt_align_pairs_clouds(ndt_handle h, const ndt_cloud* cl, size_t n_clouds, int is_dense, const int* pairs,
                                   size_t n_pairs, const float* guesses, float* final_T, int* conv, int* iters, double* tprob) {
+  pairs_forget(h);
   ndt_status s = pairs_checks(h, n_clouds, pairs, n_pairs);
   if (s) return s;
   if (n_clouds && !cl) return fail(NDT_ERR_INVALID, "null clouds");

@@ -385,6 +385,50 @@ class NormalDistributionsTransform:
         return dict(T=np.stack([_from_colmajor(T[k]) for k in range(n)]) if n else np.zeros((0, 4, 4), np.float32),
                     converged=conv.astype(bool), iterations=it, trans_probability=tp)
 
+    def pairsFitness(self, transforms=None, max_range=np.finfo(np.float64).max):
+        """getFitnessScore of every pair of the last alignPairs (ndt_pairs_fitness_scores), all in one launch: pair k's source
+        moved by transforms[k] (None = that call's final transformations) against pair k's target.  Returns (P,) float64."""
+        T = None
+        if transforms is not None:
+            T = np.ascontiguousarray(np.stack([_colmajor(x) for x in transforms]), dtype=np.float32)
+        n = C.c_size_t(0)  # the pairs the library holds (those of the last alignPairs): what it reads and writes
+        check(self._L.ndt_pairs_count(self._h, C.byref(n)))
+        P = n.value
+        if T is not None and T.shape[0] != P:
+            raise ValueError("one transform per pair of the last alignPairs")
+        out = np.zeros(max(P, 1), dtype=np.float64)
+        check(self._L.ndt_pairs_fitness_scores(self._h, _f(T) if T is not None else None, float(max_range), _d(out)))
+        return out[:P].copy()
+
+    def fitnessLaunches(self):
+        """(launches, blocks of the largest) of the last pairsFitness / batchFitness (ndt_diag_fitness_launches)."""
+        a, b = C.c_size_t(0), C.c_size_t(0)
+        check(self._L.ndt_diag_fitness_launches(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def batchFitness(self, clouds=None, transforms=None, max_range=np.finfo(np.float64).max, device_ptr=None, offsets=None,
+                     stride_bytes=16):
+        """getFitnessScore of many scans against this handle's target (ndt_batch_fitness_scores*), scan k moved by
+        transforms[k]; clouds / device_ptr + offsets as alignBatch takes them.  Returns (B,) float64."""
+        if clouds is not None:
+            cat = _cloud(np.concatenate(clouds, axis=0)) if len(clouds) else np.zeros((0, 4), np.float32)
+            offsets = np.zeros(len(clouds) + 1, dtype=np.uintp)
+            offsets[1:] = np.cumsum([len(c) for c in clouds])
+            ptr, stride, fn = cat.ctypes.data, cat.shape[1] * 4, self._L.ndt_batch_fitness_scores
+        else:
+            offsets = np.ascontiguousarray(offsets, dtype=np.uintp)
+            ptr, stride, fn = C.c_void_p(device_ptr), stride_bytes, self._L.ndt_batch_fitness_scores_device
+        B = len(offsets) - 1
+        if transforms is None:
+            raise ValueError("batchFitness needs one transform per scan")
+        T = np.ascontiguousarray(np.stack([_colmajor(x) for x in transforms]), dtype=np.float32) if B else np.zeros((0, 16), np.float32)
+        if T.shape[0] != B:
+            raise ValueError("one transform per scan")
+        out = np.zeros(max(B, 1), dtype=np.float64)
+        check(fn(self._h, ptr, offsets.ctypes.data_as(C.POINTER(C.c_size_t)), B, stride, _f(T) if B else None, float(max_range),
+                 _d(out)))
+        return out[:B].copy()
+
     def pairsGrid(self, c):
         """The grid the last alignPairs built for target cloud c, in the layout of grid()."""
         nl, nv = C.c_size_t(0), C.c_size_t(0)
