@@ -6,8 +6,10 @@
 // chained with ndt_host_chain_pose.  Printed per pair: "Transform k-1 to k" and "TransformSum", then one timing line.
 // --fitness: also the getFitnessScore of every pair at its final transformation, all from one ndt_pairs_fitness_scores
 // call right after the pairs call ("fitness k-1 to k: <value>", 17 significant digits), and that call's time.
+// --batch-filter: every scan is read first, then all of them are prefiltered in ONE ndt_cloud_voxel_filter_batch call; the
+// output is the plain run's, timing lines aside.
 //
-//   pair_sequence <pcd_directory> [--fitness]
+//   pair_sequence <pcd_directory> [--fitness] [--batch-filter]
 #include <cfloat>
 #include <chrono>
 #include <cstdio>
@@ -35,10 +37,14 @@ static double since(clock_type::time_point a) { return std::chrono::duration<dou
 
 int main(int argc, char** argv) {
   if (argc < 2) {
-    std::printf("usage: pair_sequence <pcd_directory> [--fitness]\n");
+    std::printf("usage: pair_sequence <pcd_directory> [--fitness] [--batch-filter]\n");
     return 0;
   }
-  const bool want_fitness = argc > 2 && std::strcmp(argv[2], "--fitness") == 0;
+  bool want_fitness = false, batch_filter = false;
+  for (int a = 2; a < argc; a++) {
+    if (std::strcmp(argv[a], "--fitness") == 0) want_fitness = true;
+    if (std::strcmp(argv[a], "--batch-filter") == 0) batch_filter = true;
+  }
   const float kLeaf = 0.5f;
   ndt_handle h = nullptr;
   CHECK(ndt_create(0, &h));
@@ -56,7 +62,41 @@ int main(int argc, char** argv) {
   CHECK(ndt_pcd_sequence_poll(seq, 0, &fresh));
   std::vector<ndt_cloud> clouds;
   const auto t_load = clock_type::now();
-  for (;;) {
+  if (batch_filter) {
+    // every scan's records (16 bytes each) one after the other, then one prefilter call over all of them
+    std::vector<float> raw_all;
+    std::vector<size_t> offsets(1, 0);
+    std::vector<int> dense_all, numbers;
+    for (;;) {
+      const void* raw = nullptr;
+      size_t n = 0;
+      int dense = 1, number = -1;
+      if (ndt_pcd_sequence_next(seq, &raw, &n, &dense, &number) != NDT_OK) {  // unreadable file: skipped, as the node does
+        std::fprintf(stderr, "skipped: %s\n", ndt_last_error());
+        continue;
+      }
+      if (!raw) break;
+      const float* p = static_cast<const float*>(raw);
+      raw_all.insert(raw_all.end(), p, p + 4 * n);
+      offsets.push_back(offsets.back() + n);
+      dense_all.push_back(dense);
+      numbers.push_back(number);
+    }
+    std::vector<ndt_cloud> filtered(numbers.size());
+    CHECK(ndt_cloud_voxel_filter_batch(h, raw_all.data(), offsets.data(), numbers.size(), 16, dense_all.data(), kLeaf, 0, filtered.data(),
+                                       nullptr));
+    for (size_t k = 0; k < filtered.size(); k++) {
+      size_t m = 0;
+      CHECK(ndt_cloud_size(filtered[k], &m));
+      if (m == 0) {  // empty clouds are not kept
+        ndt_cloud_release(filtered[k]);
+        continue;
+      }
+      std::printf("Loaded cloud_%d.pcd (%zu points)\n", numbers[k], m);
+      clouds.push_back(filtered[k]);
+    }
+  }
+  while (!batch_filter) {  // (the plain run: read and prefilter scan by scan)
     const void* raw = nullptr;
     size_t n = 0;
     int dense = 1, number = -1;

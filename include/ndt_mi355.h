@@ -221,6 +221,25 @@ ndt_status ndt_cloud_voxel_filter(ndt_handle h, const void* pts, size_t n, size_
  * k + 1 runs beside the registration of scan k).  One prefilter at a time per handle.  Same result as ndt_cloud_voxel_filter. */
 ndt_status ndt_cloud_voxel_filter_begin(ndt_handle h, ndt_cloud in, int is_dense, float leaf_size);
 ndt_status ndt_cloud_voxel_filter_end(ndt_handle h, ndt_cloud* out, int* overflowed);
+/* N1 of many clouds in one call: pcl::VoxelGrid::filter of n_clouds clouds at one leaf size.  out[k] receives cloud k's
+ * centroids as a new ndt_cloud and overflowed[k] (may be NULL) PCL's "leaf size too small" flag -- what
+ * ndt_cloud_voxel_filter returns for that cloud alone, the same bits, whatever the other clouds and their order.
+ * Buffer form: cloud k is points [offsets[k], offsets[k+1]) of pts (host memory, or device memory when on_device != 0).
+ * is_dense: n_clouds NaN rules, NULL = 0 for every cloud.  Every out[k] is a cloud of its own (ndt_cloud_release; releasing
+ * one leaves the others valid; an empty input gives an empty cloud, never NULL).  Synchronises the handle's stream; the
+ * handle's target, source, grid, results and a begun ndt_cloud_voxel_filter_begin are left as they were.
+ * NDT_ERR_INVALID before any device work: NULL handle or out, !(leaf_size > 0), NULL offsets / in with clouds,
+ * decreasing offsets, a bad stride, NULL pts with points, a NULL entry of in, more than 65535 clouds.
+ * On any error every out[k] is NULL and nothing is kept. */
+ndt_status ndt_cloud_voxel_filter_batch(ndt_handle h, const void* pts, const size_t* offsets /* n_clouds+1 */, size_t n_clouds,
+                                        size_t stride_bytes, const int* is_dense, float leaf_size, int on_device,
+                                        ndt_cloud* out /* n_clouds */, int* overflowed /* n_clouds or NULL */);
+/* the same over clouds already resident in HBM (ndt_cloud_upload, ndt_pcd_sequence_next_cloud views, earlier outputs) */
+ndt_status ndt_cloud_voxel_filter_clouds(ndt_handle h, const ndt_cloud* in, size_t n_clouds, const int* is_dense,
+                                         float leaf_size, ndt_cloud* out, int* overflowed);
+/* diagnostics of the handle's last batched filter: composite passes, clouds that took the single-cloud route, and the
+ * launches, fills and copies the call queued outside that route */
+ndt_status ndt_diag_filter_batch(ndt_handle h, size_t* passes, size_t* single_route, size_t* launches);
 ndt_status ndt_cloud_upload(ndt_handle h, const void* pts, size_t n, size_t stride_bytes, ndt_cloud* out);
 ndt_status ndt_cloud_size(ndt_cloud c, size_t* n);
 ndt_status ndt_cloud_data(ndt_cloud c, const void** d_pts_float4, size_t* n);               /* the records in HBM */

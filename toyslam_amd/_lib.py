@@ -150,6 +150,9 @@ SIGNATURES = {
     "ndt_pcd_sequence_next_cloud": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_void_p), szp, ip, ip]),
     "ndt_cloud_voxel_filter_begin": (C.c_int, [vp, vp, C.c_int, C.c_float]),
     "ndt_cloud_voxel_filter_end": (C.c_int, [vp, C.POINTER(vp), ip]),
+    "ndt_cloud_voxel_filter_batch": (C.c_int, [vp, vp, szp, C.c_size_t, C.c_size_t, ip, C.c_float, C.c_int, C.POINTER(vp), ip]),
+    "ndt_cloud_voxel_filter_clouds": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, ip, C.c_float, C.POINTER(vp), ip]),
+    "ndt_diag_filter_batch": (C.c_int, [vp, szp, szp, szp]),
     "ndt_pcd_sequence_next_device": (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), szp, ip, ip]),
     "ndt_host_extract_file_number": (C.c_int, [C.c_char_p]),
     "ndt_host_repack_fields": (C.c_int, [vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, vp, ip]),

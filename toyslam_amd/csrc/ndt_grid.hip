@@ -1043,30 +1043,18 @@ ndt_status fitness_impl(ndt_context* h, const float4* d_src, int n, const float*
 // count and the per-block rows of the result's bounding boxes travel to page-locked memory behind the last kernel --
 // voxel_filter_finish reads them once that stream has been waited for.  voxel_filter_device is the two with a
 // synchronisation in between (N1); the map update (N2) leaves the wait to whoever next needs the map.
-static constexpr int kOutBoxBlocks = 64;
 struct PoolStreamGuard {  // temporaries allocated (and given back) inside the scope belong to `s`'s pool
   hipStream_t keep;
   explicit PoolStreamGuard(hipStream_t s) : keep(tls_pool_stream) { tls_pool_stream = s; }
   ~PoolStreamGuard() { tls_pool_stream = keep; }
 };
 
-ndt_status voxel_filter_enqueue(ndt_handle h, hipStream_t st, const float4* d_in, size_t n, int is_dense, float leaf, float4* d_out,
-                                const BBox& bb, FilterPending& P) {
-  P.n_max = n;
-  P.fixed_n = 0;
-  P.from_device = false;
-  P.overflow = false;
-  if (n == 0) return NDT_OK;
-  const PoolStreamGuard guard(st);
-  const int ni = static_cast<int>(n);
+FilterRoute filter_route(const ndt_context* h, size_t n, const BBox& bb, float leaf) {
+  FilterRoute r;
   const float* min_p = bb.mn;
   const float* max_p = bb.mx;
-  if (!(min_p[0] <= max_p[0])) {  // no finite point: empty output
-    for (int i = 0; i < kOutBoxBlocks * 12; i++) P.rows[i] = (i % 6) < 3 ? FLT_MAX : -FLT_MAX;
-    return NDT_OK;
-  }
-  const int nb_rows = static_cast<int>(std::min<size_t>(kOutBoxBlocks, (n + 255) / 256));
-  ndt::GridGeom geo{};
+  if (n == 0 || !(min_p[0] <= max_p[0])) return r;  // no finite point: empty output
+  ndt::GridGeom& geo = r.geo;
   long long d[3];
   for (int k = 0; k < 3; k++) {
     geo.leaf[k] = leaf;
@@ -1074,11 +1062,8 @@ ndt_status voxel_filter_enqueue(ndt_handle h, hipStream_t st, const float4* d_in
     d[k] = static_cast<long long>((max_p[k] - min_p[k]) * geo.inv_leaf[k]) + 1;
   }
   if (d[0] * d[1] * d[2] > static_cast<long long>(std::numeric_limits<int32_t>::max())) {
-    HIP_TRY(hipMemcpyAsync(d_out, d_in, n * sizeof(float4), hipMemcpyDeviceToDevice, st));  // output = *input_
-    HIP_TRY(ndt::launch_repack_bbox(d_out, n, sizeof(float4), nullptr, P.rows, nb_rows, st, 0, nullptr));
-    P.fixed_n = n;
-    P.overflow = true;
-    return NDT_OK;
+    r.kind = FilterRoute::kOverflow;
+    return r;
   }
   for (int k = 0; k < 3; k++) {
     geo.min_b[k] = static_cast<int>(std::floor(min_p[k] * geo.inv_leaf[k]));
@@ -1089,10 +1074,39 @@ ndt_status voxel_filter_enqueue(ndt_handle h, hipStream_t st, const float4* d_in
   geo.mul[1] = geo.div_b[0];
   geo.mul[2] = geo.div_b[0] * geo.div_b[1];
   geo.n_cells = static_cast<long long>(geo.div_b[0]) * geo.div_b[1] * geo.div_b[2];
+  // a fine leaf over a wide box (apps/align.cpp: 0.1 m over a whole scan): per-point work only (ndt_sparse.hip)
+  const bool sparse = h->voxel_index == 2 || (h->voxel_index == 0 && geo.n_cells > 16ll * static_cast<long long>(n) + (1ll << 22));
+  r.kind = sparse ? FilterRoute::kSparse : FilterRoute::kDense;
+  return r;
+}
+
+ndt_status voxel_filter_enqueue(ndt_handle h, hipStream_t st, const float4* d_in, size_t n, int is_dense, float leaf, float4* d_out,
+                                const BBox& bb, FilterPending& P) {
+  P.n_max = n;
+  P.fixed_n = 0;
+  P.from_device = false;
+  P.overflow = false;
+  if (n == 0) return NDT_OK;
+  const PoolStreamGuard guard(st);
+  const int ni = static_cast<int>(n);
+  const FilterRoute route = filter_route(h, n, bb, leaf);
+  if (route.kind == FilterRoute::kEmpty) {  // no finite point: empty output
+    for (int i = 0; i < kOutBoxBlocks * 12; i++) P.rows[i] = (i % 6) < 3 ? FLT_MAX : -FLT_MAX;
+    return NDT_OK;
+  }
+  const int nb_rows = static_cast<int>(std::min<size_t>(kOutBoxBlocks, (n + 255) / 256));
+  if (route.kind == FilterRoute::kOverflow) {
+    HIP_TRY(hipMemcpyAsync(d_out, d_in, n * sizeof(float4), hipMemcpyDeviceToDevice, st));  // output = *input_
+    HIP_TRY(ndt::launch_repack_bbox(d_out, n, sizeof(float4), nullptr, P.rows, nb_rows, st, 0, nullptr));
+    P.fixed_n = n;
+    P.overflow = true;
+    return NDT_OK;
+  }
+  const ndt::GridGeom geo = route.geo;
   DevBuf<unsigned> cell_count, block_sums, totals, leaf_start, rank;
   DevBuf<int> key, leaf_cell, leaf_count, leaf_rec, sorted_idx;
   P.from_device = true;
-  if (h->voxel_index == 2 || (h->voxel_index == 0 && geo.n_cells > 16ll * static_cast<long long>(n) + (1ll << 22))) {
+  if (route.kind == FilterRoute::kSparse) {
     // a fine leaf over a wide box (apps/align.cpp: 0.1 m over a whole scan): per-point work only (ndt_sparse.hip)
     const size_t max_l = std::min<size_t>(n, static_cast<size_t>(geo.n_cells));
     const size_t tb = ndt::sparse_index_temp_bytes(ni);
@@ -1550,7 +1564,7 @@ namespace ndtc {
 ndt_status cloud_use_on(ndt_handle h, DeviceCloud* c) {
   if (c->made_on && c->made_on != h->stream) {
     if (c->device != h->device) return fail(NDT_ERR_INVALID, "the cloud lives on another device");
-    HIP_TRY(hipStreamSynchronize(c->made_on));
+    if (!DevPool::instance().retired(c->made_on)) HIP_TRY(hipStreamSynchronize(c->made_on));  // (a destroyed stream's work is over)
     if (std::find(c->used_on.begin(), c->used_on.end(), h->stream) == c->used_on.end()) c->used_on.push_back(h->stream);
   }
   return NDT_OK;

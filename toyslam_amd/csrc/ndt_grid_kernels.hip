@@ -241,6 +241,96 @@ __global__ __launch_bounds__(kBlock) void k_count_batch(const float4* __restrict
   }
 }
 
+// ---------------------------------------------------------------------------
+// N1 of many clouds (ndt_filter_batch.hip): blockIdx.y = the cloud / segment
+// ---------------------------------------------------------------------------
+// order-preserving unsigned form of a non-NaN float (ascending floats -> ascending words, never 0 or ~0)
+__device__ __forceinline__ unsigned box_key(float v) { return static_cast<unsigned>(enc_f32(v)) ^ 0x80000000u; }
+
+// k_repack_bbox over many segments at once; the rows of a segment meet in its 12 words (one atomic max per block and word:
+// a min is stored as the complement of its key)
+__global__ __launch_bounds__(kBlock) void k_repack_bbox_multi(const SegDesc* __restrict__ segs, unsigned* __restrict__ boxes) {
+  const SegDesc d = segs[blockIdx.y];
+  size_t lo = 0, hi = d.n;
+  if (d.range) { lo = d.range[0]; hi = d.range[1]; }
+  const bool rec16 = d.stride == 16 && (reinterpret_cast<uintptr_t>(d.src) & 15) == 0;
+  float mn[6] = {FLT_MAX, FLT_MAX, FLT_MAX, FLT_MAX, FLT_MAX, FLT_MAX};
+  float mx[6] = {-FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX};
+  for (size_t i = lo + blockIdx.x * (size_t)kBlock + threadIdx.x; i < hi; i += (size_t)gridDim.x * kBlock) {
+    float x, y, z;
+    if (rec16) {
+      const float4 p = reinterpret_cast<const float4*>(d.src)[i];
+      x = p.x; y = p.y; z = p.z;
+    } else {
+      const float* p = reinterpret_cast<const float*>(d.src + i * d.stride);
+      x = p[0]; y = p[1]; z = p[2];
+    }
+    if (d.dst) d.dst[i - lo] = make_float4(x, y, z, 1.0f);
+    mn[0] = fminf(mn[0], x); mx[0] = fmaxf(mx[0], x);  // fminf / fmaxf drop NaN operands
+    mn[1] = fminf(mn[1], y); mx[1] = fmaxf(mx[1], y);
+    mn[2] = fminf(mn[2], z); mx[2] = fmaxf(mx[2], z);
+    if (finite3(x, y, z)) {
+      mn[3] = fminf(mn[3], x); mx[3] = fmaxf(mx[3], x);
+      mn[4] = fminf(mn[4], y); mx[4] = fmaxf(mx[4], y);
+      mn[5] = fminf(mn[5], z); mx[5] = fmaxf(mx[5], z);
+    }
+  }
+  if (!boxes) return;
+  __shared__ float s[kBlock / kWave][12];
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+#pragma unroll
+  for (int k = 0; k < 6; k++) {
+    const float a = wave_min(mn[k]), b = wave_max(mx[k]);
+    const int base = (k < 3) ? 0 : 6, c = k % 3;
+    if (lane == 0) { s[wave][base + c] = a; s[wave][base + 3 + c] = b; }
+  }
+  __syncthreads();
+  if (threadIdx.x < 12) {
+    const bool is_min = (threadIdx.x % 6) < 3;
+    float v = s[0][threadIdx.x];
+    for (int w = 1; w < kBlock / kWave; w++) v = is_min ? fminf(v, s[w][threadIdx.x]) : fmaxf(v, s[w][threadIdx.x]);
+    atomicMax(boxes + 12 * blockIdx.y + threadIdx.x, is_min ? ~box_key(v) : box_key(v));
+  }
+}
+
+// k_count over the clouds of a composite pass: cloud k's cell is build_cell on ITS lattice, range-tested against ITS cell
+// count (so that a NaN of a dense cloud is dropped as k_count drops it), then moved to the cloud's own counters
+__global__ __launch_bounds__(kBlock) void k_count_multi(const float4* __restrict__ pts, const FilterBatchCloud* __restrict__ clouds,
+                                                        int* __restrict__ key, unsigned* __restrict__ rank,
+                                                        unsigned* __restrict__ cell_count) {
+  const FilterBatchCloud& C = clouds[blockIdx.y];
+  const int lo = C.first, hi = C.first + C.n, base = C.base, dense = C.dense;
+  const GridGeom g = C.g;
+  for (int i = lo + blockIdx.x * kBlock + threadIdx.x; i < hi; i += gridDim.x * kBlock) {
+    int c = -1;
+    if (g.n_cells > 0) {
+      const float4 p = pts[i];
+      if (dense || finite3(p.x, p.y, p.z)) {
+        c = build_cell(g, p.x, p.y, p.z);
+        if (c < 0 || static_cast<long long>(c) >= g.n_cells) c = -1;
+        else c += base;
+      }
+    }
+    key[i] = c;
+    if (c >= 0) rank[i] = atomicAdd(&cell_count[c], 1u);
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_leaf_ranges(const int* __restrict__ leaf_cell, const unsigned* __restrict__ totals,
+                                                        const FilterBatchCloud* __restrict__ clouds, int n, unsigned* __restrict__ out) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= 2 * n) return;
+  const FilterBatchCloud& C = clouds[i >> 1];
+  const long long bound = C.base + ((i & 1) ? C.g.n_cells : 0);
+  unsigned a = 0, b = totals[1];
+  while (a < b) {  // first leaf whose cell is >= bound
+    const unsigned m = (a + b) >> 1;
+    if (leaf_cell[m] < bound) a = m + 1;
+    else b = m;
+  }
+  out[i] = a;
+}
+
 __global__ __launch_bounds__(kBlock) void k_pick(const unsigned* __restrict__ cell_count, const long long* __restrict__ bases,
                                                  unsigned* __restrict__ out, int n) {
   const int i = blockIdx.x * kBlock + threadIdx.x;
@@ -2918,6 +3008,33 @@ hipError_t launch_count_batch(const float4* pts, const int* d_scan_off, int n_sc
 
 hipError_t launch_pick(const unsigned* cell_count, const long long* d_bases, unsigned* d_out, int n, hipStream_t stream) {
   hipLaunchKernelGGL(k_pick, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, cell_count, d_bases, d_out, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_repack_bbox_multi(const SegDesc* d_segs, int n_segs, size_t max_seg_points, unsigned* d_boxes, hipStream_t stream) {
+  if (n_segs <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_repack_bbox_multi, dim3(grid_for(max_seg_points, 64), n_segs), dim3(kBlock), 0, stream, d_segs, d_boxes);
+  return hipGetLastError();
+}
+
+float box_word_decode(unsigned w, bool is_min) {
+  if (w == 0) return is_min ? FLT_MAX : -FLT_MAX;  // (no block wrote the word)
+  return scan_bbox_decode(static_cast<int>((is_min ? ~w : w) ^ 0x80000000u));
+}
+
+hipError_t launch_count_multi(const float4* pts, const FilterBatchCloud* d_clouds, int n_clouds, int max_cloud_points, int* d_key,
+                              unsigned* d_rank, unsigned* d_cell_count, hipStream_t stream) {
+  if (n_clouds <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_count_multi, dim3(grid_for(max_cloud_points, 256), n_clouds), dim3(kBlock), 0, stream, pts, d_clouds, d_key, d_rank,
+                     d_cell_count);
+  return hipGetLastError();
+}
+
+hipError_t launch_leaf_ranges(const int* leaf_cell, const unsigned* d_totals, const FilterBatchCloud* d_clouds, int n_clouds,
+                              unsigned* d_out, hipStream_t stream) {
+  if (n_clouds <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_leaf_ranges, dim3((2 * n_clouds + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, leaf_cell, d_totals, d_clouds,
+                     n_clouds, d_out);
   return hipGetLastError();
 }
 

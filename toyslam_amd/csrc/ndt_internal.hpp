@@ -220,6 +220,10 @@ struct DeviceCloud {
   hipStream_t made_on = nullptr;
   std::vector<hipStream_t> used_on;
   std::shared_ptr<DeviceCloud> parent;  // a view of another cloud's points (pts borrowed) with an ordered copy of its own
+  // A slice of a batched filter's output block (ndt_filter_batch.hip; pts borrowed): keeps the block alive.  Not `parent`:
+  // the slice is a cloud of its own (ndt_promote_source_to_target promotes it, not the block).  The streams that read a
+  // slice are waited for when the slice goes, so the block's memory goes back only after every reader of every slice.
+  std::shared_ptr<DeviceCloud> owner;
   ~DeviceCloud() {
     if (!made_on) return;
     (void)hipSetDevice(device);
@@ -241,6 +245,7 @@ struct DeviceCloud {
 
 
 // An enqueued voxel filter: where its count and the rows of its result's boxes arrive (page-locked), what the host decided
+static constexpr int kOutBoxBlocks = 64;
 struct FilterPending {
   float* rows = nullptr;     // [64][12] per-block rows of the result's bounding boxes
   unsigned* tot = nullptr;   // [3]: points binned, voxels, -
@@ -430,6 +435,13 @@ struct ndt_context {
   // held at once), for ndt_diag_fitness_launches
   size_t fit_launches = 0, fit_max_blocks = 0;
   DevBuf<ndt::GridView> pair_views;
+  // ndt_cloud_voxel_filter_batch / _clouds (ndt_filter_batch.hip): page-locked descriptors and read-backs, the result rows
+  // of the clouds that take the single-cloud route, and what the last call did (ndt_diag_filter_batch)
+  void* fb_pinned = nullptr;
+  size_t fb_pinned_bytes = 0;
+  void* fb_rows = nullptr;
+  size_t fb_rows_bytes = 0;
+  size_t fb_passes = 0, fb_single = 0, fb_launches = 0;
 
   ~ndt_context() {
     for (ndt_context* w : batch_workers) delete w;
@@ -459,6 +471,8 @@ struct ndt_context {
       (void)hipStreamDestroy(filter_stream);
     }
     if (filter_slots) (void)hipHostFree(filter_slots);
+    if (fb_pinned) (void)hipHostFree(fb_pinned);
+    if (fb_rows) (void)hipHostFree(fb_rows);
     release_buffers();
     if (host_result) (void)hipHostFree(host_result);
     if (host_pub) (void)hipHostFree(host_pub);
@@ -540,6 +554,14 @@ struct FitnessJob {
 };
 ndt_status fitness_many(ndt_context* h, const std::vector<FitnessJob>& jobs, double max_range, double* out);
 ndt_status filter_slots(ndt_handle h, int which, FilterPending& P);
+// The geometry and route of one N1 filter, from the cloud's box alone -- the one decision voxel_filter_enqueue and the
+// batched filter (ndt_filter_batch.hip) both take: no finite point, PCL's index overflow (copy-through), the sparse index
+// (ndt_set_voxel_index, or a box far larger than the points), or a dense cell space over the box (geo)
+struct FilterRoute {
+  enum Kind { kEmpty, kOverflow, kSparse, kDense } kind = kEmpty;
+  ndt::GridGeom geo{};
+};
+FilterRoute filter_route(const ndt_context* h, size_t n, const BBox& bb, float leaf);
 ndt_status voxel_filter_enqueue(ndt_handle h, hipStream_t st, const float4* d_in, size_t n, int is_dense, float leaf, float4* d_out,
                                 const BBox& bb, FilterPending& P);
 void voxel_filter_finish(const FilterPending& P, size_t* n_out, DeviceCloud* boxes);

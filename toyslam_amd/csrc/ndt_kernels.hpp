@@ -246,6 +246,38 @@ hipError_t launch_scan_apply(unsigned* d_cell_count_to_cursor, long long n_cells
 hipError_t launch_scatter(const int* d_key, const unsigned* d_rank, int n, const unsigned* d_cell_start, int* d_sorted_idx,
                           hipStream_t stream);
 
+// N1 of many clouds in one pass (ndt_filter_batch.hip).
+// One segment of the multi-segment repack + box kernel: records of `stride` bytes (x y z first) at src, repacked to dense
+// (x, y, z, 1) at dst (null: boxes only).  range != null: the segment is records [range[0], range[1]) of src, a count
+// that is still on the device (n is then only the bound the grid is sized by).
+struct SegDesc {
+  const unsigned char* src;
+  float4* dst;
+  const unsigned* range;
+  unsigned long long n;
+  int stride;
+  int pad;
+};
+// boxes (null: none) receives 12 words per segment, zero before the launch: the segment's two bounding boxes as
+// k_repack_bbox's rows give them ([0..5] non-NaN min / max xyz, [6..11] finite-only), each value order-encoded so that
+// one atomic max per block and word reduces them.  box_word_decode turns a word back into the float (0: no point).
+hipError_t launch_repack_bbox_multi(const SegDesc* d_segs, int n_segs, size_t max_seg_points, unsigned* d_boxes, hipStream_t stream);
+float box_word_decode(unsigned w, bool is_min);
+// One cloud of a composite count: its own lattice (the single filter's GridGeom), its points [first, first + n) of the
+// pass's block and its first counter.  g.n_cells == 0: the cloud is in the pass's span but not in the pass (keys -1).
+struct FilterBatchCloud {
+  GridGeom g;
+  int first, n;
+  int base;
+  int dense;
+};
+hipError_t launch_count_multi(const float4* pts, const FilterBatchCloud* d_clouds, int n_clouds, int max_cloud_points, int* d_key,
+                              unsigned* d_rank, unsigned* d_cell_count, hipStream_t stream);
+// out[2k], out[2k + 1] = the first leaf of cloud k's cells and the first one past them (leaf_cell is ascending; d_totals[1]
+// leaves)
+hipError_t launch_leaf_ranges(const int* leaf_cell, const unsigned* d_totals, const FilterBatchCloud* d_clouds, int n_clouds,
+                              unsigned* d_out, hipStream_t stream);
+
 // Sparse voxel index (ndt_sparse.hip): leaf arrays in ascending voxel order from a stable sort of (voxel, point) pairs.
 // counts: device [5] = {points binned, occupied voxels, candidates, -, -} (zeroed here; the finalize pass adds [3], [4]).
 // keys_a / keys_b / vals_a / flags / ord: n words of scratch each; temp: sparse_index_temp_bytes(n).

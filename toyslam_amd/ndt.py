@@ -77,6 +77,16 @@ class DeviceCloud:
             pass
 
 
+def _dense_flags(is_dense, n):
+    """(n,) int32 NaN rules of a batched filter: one bool for every cloud, or one per cloud."""
+    if np.ndim(is_dense) == 0:
+        return np.full(max(n, 1), int(bool(is_dense)), dtype=np.int32)
+    f = np.asarray(is_dense).astype(bool).reshape(-1)
+    if f.shape[0] != n:
+        raise ValueError("one is_dense flag per cloud")
+    return np.ascontiguousarray(f, dtype=np.int32) if n else np.zeros(1, dtype=np.int32)
+
+
 def pairs_array(n_clouds, pairs=None):
     """(P, 2) int32 C-contiguous (target, source) cloud indices; None = the consecutive pairs (k-1, k) of n_clouds clouds."""
     if pairs is None:
@@ -295,6 +305,50 @@ class NormalDistributionsTransform:
         c, ov = C.c_void_p(None), C.c_int(0)
         check(self._L.ndt_cloud_voxel_filter_end(self._h, C.byref(c), C.byref(ov)))
         return DeviceCloud(self, c), bool(ov.value)
+
+    def voxelGridFilterClouds(self, clouds, leaf_size, is_dense=True):
+        """N1 of many clouds in one call (ndt_cloud_voxel_filter_batch / _clouds).  clouds: a list of (N_k, >=3) host arrays
+        (concatenated once: the buffer form) or of DeviceCloud (the clouds form), not a mix; is_dense: one bool, or one per
+        cloud.  Cloud k's result is what voxelGridFilterCloud returns for it alone, the same bits.
+        -> (list of DeviceCloud, (n,) bool overflow flags)."""
+        clouds = list(clouds)
+        resident = [isinstance(c, DeviceCloud) for c in clouds]
+        if any(resident) and not all(resident):
+            raise ValueError("clouds must be all DeviceCloud or all host arrays, not a mix")
+        n = len(clouds)
+        dense = _dense_flags(is_dense, n)
+        out = (C.c_void_p * max(n, 1))()
+        ov = np.zeros(max(n, 1), dtype=np.int32)
+        if n and all(resident):
+            arr = (C.c_void_p * n)(*[c._c for c in clouds])
+            check(self._L.ndt_cloud_voxel_filter_clouds(self._h, arr, n, _i(dense), float(leaf_size), out, _i(ov)))
+        else:
+            cols = {np.asarray(c).shape[1] if np.asarray(c).ndim == 2 else -1 for c in clouds}
+            if len(cols) > 1:
+                raise ValueError("all clouds must have the same column count")
+            cat = _cloud(np.concatenate(clouds, axis=0)) if clouds else np.zeros((0, 4), np.float32)
+            offsets = np.zeros(n + 1, dtype=np.uintp)
+            offsets[1:] = np.cumsum([len(c) for c in clouds])
+            check(self._L.ndt_cloud_voxel_filter_batch(self._h, cat.ctypes.data, offsets.ctypes.data_as(C.POINTER(C.c_size_t)), n,
+                                                       cat.shape[1] * 4, _i(dense), float(leaf_size), 0, out, _i(ov)))
+        return [DeviceCloud(self, C.c_void_p(out[k])) for k in range(n)], ov[:n].astype(bool)
+
+    def voxelGridFilterBatchDevice(self, dev_ptr, offsets, stride_bytes, leaf_size, is_dense=True):
+        """The buffer form over records already in HBM: cloud k = records [offsets[k], offsets[k+1]) at dev_ptr."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uintp)
+        n = len(offsets) - 1
+        dense = _dense_flags(is_dense, n)
+        out = (C.c_void_p * max(n, 1))()
+        ov = np.zeros(max(n, 1), dtype=np.int32)
+        check(self._L.ndt_cloud_voxel_filter_batch(self._h, C.c_void_p(dev_ptr), offsets.ctypes.data_as(C.POINTER(C.c_size_t)), n,
+                                                   int(stride_bytes), _i(dense), float(leaf_size), 1, out, _i(ov)))
+        return [DeviceCloud(self, C.c_void_p(out[k])) for k in range(n)], ov[:n].astype(bool)
+
+    def filterBatchDiag(self):
+        """What the last voxelGridFilterClouds / voxelGridFilterBatchDevice did (ndt_diag_filter_batch)."""
+        p, s, l = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        check(self._L.ndt_diag_filter_batch(self._h, C.byref(p), C.byref(s), C.byref(l)))
+        return dict(passes=p.value, single_route=s.value, launches=l.value)
 
     def warmUp(self, expected_scan_points=0):
         check(self._L.ndt_warm_up(self._h, int(expected_scan_points)))
