@@ -98,6 +98,26 @@ def test_pairs_grids_equal_single_handle_grids(mods, pair):
     grids_equal(g.pairsGrid(0), ref.grid())
 
 
+@pytest.mark.parametrize("env", [{}, {"NDT_K1_SMALL_LIST": "8"}, {"NDT_K1_LDS_CAP": "512"}, {"NDT_K1_SMALL_FINISH": "0"}],
+                         ids=["default", "lists_overflow_second_scan", "small_passes", "general_finish_only"])
+def test_pairs_grids_equal_single_handle_grids_in_every_small_form_regime(mods, env, tmp_path):
+    """The one-launch build of many small targets and the one-launch build of a single one, forced through each path of the
+    small form (wave lists that overflow, LDS passes of 512 points, the general finish only): the same grids, bit for bit,
+    for clouds of 6 to 49 152 points, crowded ones included, dense and with NaN / inf (tools/probes/pairs_grids_check.py:
+    the switches are read once per process)."""
+    import sys
+    out = str(tmp_path / "grids.npz")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "probes", "pairs_grids_check.py"), out], env=dict(os.environ, **env),
+                       capture_output=True, text=True, timeout=280)
+    assert r.returncode == 0, r.stderr[-1500:]
+    z = np.load(out)
+    for form in ("dense", "nonfinite"):
+        for c in range(int(z["n_clouds"])):
+            a, b = ({k: z["%s%d_%s_%s" % (form, c, who, k)] for k in ("idx", "n", "mean", "cov", "icov", "evals", "min_b", "max_b", "div_b", "n_valid")}
+                    for who in ("pairs", "single"))
+            grids_equal(a, b)
+
+
 @pytest.mark.parametrize("method", ["DIRECT1", "DIRECT7", "DIRECT26", "KDTREE"])
 def test_each_pair_matches_a_single_registration(mods, pair, method):
     ndt, po, clouds = mods

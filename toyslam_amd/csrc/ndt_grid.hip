@@ -570,6 +570,108 @@ ndt_status grid_head(ndt_context* h, GridHead& hd) {
   return NDT_OK;
 }
 
+// The form build_grid builds hd's dense table in (plan: the bucket plan).  The bucket form, its cells dealt to the buckets in
+// short runs (k1_bucket), is the faster one for every cloud shape measured, uniform to heavily clustered (tools/time_k1_forms.py);
+// NDT_K1=old: the general chain, kept for index-only builds -- GICP's search index -- and as the cross-check of tools/fuzz_grid.py.
+enum K1Form { K1_CHAIN, K1_BUCKETS, K1_SMALL };
+static K1Form k1_form(const ndt_context* h, const GridHead& hd, ndt::GridBuildPlan& plan) {
+  static const bool chain_only = [] { const char* v = getenv("NDT_K1"); return v && std::strcmp(v, "old") == 0; }();
+  static const bool small_on = [] { const char* v = getenv("NDT_K1_SMALL"); return !v || atoi(v) != 0; }();
+  if (hd.sparse || chain_only || h->index_only || !ndt::grid_build_plan(hd.g->geom.n_cells, hd.n, plan)) return K1_CHAIN;
+  return small_on && ndt::grid_build_small_applies(hd.n, plan) ? K1_SMALL : K1_BUCKETS;
+}
+// NDT_K1_STAMPS=1: the bucket form's phase clocks on stderr (development aid)
+static bool k1_stamps_on() { static const bool on = [] { const char* v = getenv("NDT_K1_STAMPS"); return v && atoi(v) != 0; }(); return on; }
+
+// A bucket-form build of hd's target with the bucket plan `plan`: the grid's buffers (scratch: the finish's [5 n] words) and
+// state as the build leaves it, and for the one-launch form (k1_small; many targets: k1_small_multi) the launch in *D (*lds: its
+// dynamic LDS; multi: k1_small_multi's lists).
+static ndt_status setup_bucket_form(ndt_context* h, const GridHead& hd, const ndt::GridBuildPlan& plan, DevBuf<unsigned>& scratch,
+                                    ndt::SmallBuildDesc* D, size_t* lds, bool multi) {
+  DeviceGrid* g = hd.g.get();
+  const size_t n = static_cast<size_t>(hd.n), K = static_cast<size_t>(plan.n_buckets);
+  const size_t rec_slots = n / static_cast<size_t>(std::max(1, h->min_pts)) + 1;  // slot = segment start / min_pts
+  HIP_TRY(g->counts.reserve(8));  // (build_grid has reserved these and the table before it chooses the form)
+  HIP_TRY(g->leaf_cell.reserve(hd.max_leaves));
+  HIP_TRY(g->leaf_start.reserve(hd.max_leaves));
+  HIP_TRY(g->leaf_count.reserve(hd.max_leaves));
+  HIP_TRY(g->leaf_rec.reserve(hd.max_leaves));
+  HIP_TRY(g->sorted_idx.reserve(n));
+  HIP_TRY(g->lut.reserve(static_cast<size_t>(g->geom.lut_cells)));
+  HIP_TRY(g->recs.reserve(rec_slots));
+  HIP_TRY(g->centroids.reserve(rec_slots));
+  HIP_TRY(g->bucket_base.reserve(2 * K + 1));  // [K + 1] bucket bases, [K] valid voxels per bucket
+  HIP_TRY(g->bpts.reserve(n));
+  HIP_TRY(scratch.reserve(5 * n));
+  g->plan = plan;
+  g->leaves_pending = true;  // leaf arrays and the occupied / candidate counts: on demand (grid_counts)
+  g->counts_known = false;
+  g->empty = false;
+  if (!D) return NDT_OK;
+  if (!ndt::small_build_desc(hd.n, plan, multi, *D, lds)) return fail(NDT_ERR_HIP, "one-launch grid build: the finish's LDS does not fit");
+  D->pts = h->target->pts.p;
+  D->dense = h->target_dense;
+  D->g = g->geom;
+  D->min_pts = h->min_pts;
+  D->eig_ratio = h->eig_ratio;
+  D->bucket_base = g->bucket_base.p;
+  D->bpts = g->bpts.p;
+  D->sorted_idx = g->sorted_idx.p;
+  D->recs = g->recs.p;
+  D->centroids = g->centroids.p;
+  D->lut = g->lut.p;
+  D->scratch = scratch.p;
+  D->counts = g->counts.p;
+  return NDT_OK;
+}
+
+// NDT_K1_STAMPS: the bucket form's phase clocks, per phase the median and the maximum over the buckets / blocks (shader cycles)
+static ndt_status print_k1_stamps(ndt_context* h, const unsigned long long* stamps, const ndt::GridBuildPlan& plan, bool small_form) {
+  const size_t K = static_cast<size_t>(plan.n_buckets);
+  std::vector<unsigned long long> hst(8 * K);
+  HIP_TRY(hipMemcpyAsync(hst.data(), stamps, 8 * K * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  static const char* names[8] = {"load+rank", "scans+select", "place", "teams", "sums+finish", "passes", "points", "total"};
+  std::fprintf(stderr, "[k1_finalize clocks, %zu buckets] ", K);
+  for (int q = 0; q < 8; q++) {
+    std::vector<unsigned long long> d;
+    for (size_t b = 0; b < K; b++)
+      if (hst[8 * b + 7]) d.push_back(hst[8 * b + q]);
+    if (d.empty()) continue;
+    std::sort(d.begin(), d.end());
+    std::fprintf(stderr, "%s %llu/%llu  ", names[q], d[d.size() / 2], d.back());
+  }
+  std::fprintf(stderr, "\n");
+  if (small_form) {  // k1_small: cycles from the block's start to the end of the scan / the publication / the end
+    std::vector<unsigned long long> hk(4 * K);
+    HIP_TRY(hipMemcpy(hk.data(), stamps + 8 * K, 4 * K * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    std::fprintf(stderr, "[k1_small clocks, %zu blocks, cycles since the block's start: scan / published / end] ", K);
+    for (int q = 1; q < 4; q++) {
+      std::vector<unsigned long long> d;
+      for (size_t b = 0; b < K; b++) d.push_back(hk[4 * b + q] - hk[4 * b]);
+      std::sort(d.begin(), d.end());
+      std::fprintf(stderr, "%llu/%llu  ", d[d.size() / 2], d.back());
+    }
+    unsigned long long t_lo = ~0ull, t_hi = 0;
+    for (size_t b = 0; b < K; b++) { t_lo = std::min(t_lo, hk[4 * b]); t_hi = std::max(t_hi, hk[4 * b + 3]); }
+    std::fprintf(stderr, " first start -> last end %llu\n", t_hi - t_lo);
+  }
+  const size_t B = small_form ? 0 : static_cast<size_t>(plan.n_blocks);
+  std::vector<unsigned long long> hs(8 * B + 1);
+  HIP_TRY(hipMemcpy(hs.data(), stamps + 8 * K, 8 * B * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  if (B) std::fprintf(stderr, "[k1_scatter clocks, %zu blocks, cycles since the block's start: tables / ranks / column scan / stores] ", B);
+  for (int q = 1; q < 5; q++) {
+    std::vector<unsigned long long> d;
+    for (size_t bq = 0; bq < B; bq++)
+      if (hs[8 * bq] && hs[8 * bq + q]) d.push_back(hs[8 * bq + q] - hs[8 * bq]);
+    if (d.empty()) continue;
+    std::sort(d.begin(), d.end());
+    std::fprintf(stderr, "%llu/%llu  ", d[d.size() / 2], d.back());
+  }
+  std::fprintf(stderr, "\n");
+  return NDT_OK;
+}
+
 // VoxelGridCovariance::filter(true) on the GPU.
 ndt_status build_grid(ndt_context* h) {
   GridHead hd;
@@ -579,7 +681,6 @@ ndt_status build_grid(ndt_context* h) {
   const int n = hd.n;
   ndt::GridGeom& geo = g->geom;
   const size_t max_leaves = hd.max_leaves, max_cand = hd.max_cand;
-  const bool sparse = hd.sparse;
   hipStream_t st = h->stream;
   HIP_TRY(g->counts.reserve(8));  // [points binned, occupied voxels, candidate voxels (>= min_pts), valid voxels, points in crowded cells]
   HIP_TRY(g->leaf_cell.reserve(max_leaves));
@@ -587,7 +688,7 @@ ndt_status build_grid(ndt_context* h) {
   HIP_TRY(g->leaf_count.reserve(max_leaves));
   HIP_TRY(g->leaf_rec.reserve(max_leaves));
   HIP_TRY(g->sorted_idx.reserve(n));
-  if (sparse) {
+  if (hd.sparse) {
     const size_t rec_slots = static_cast<size_t>(n) / static_cast<size_t>(std::max(1, h->min_pts)) + 1;  // slot = segment start / min_pts
     HIP_TRY(g->recs.reserve(rec_slots));
     HIP_TRY(g->centroids.reserve(rec_slots));
@@ -618,36 +719,30 @@ ndt_status build_grid(ndt_context* h) {
     return NDT_OK;
   }
   HIP_TRY(g->lut.reserve(static_cast<size_t>(geo.lut_cells)));
-  static const int k1_mode = [] { const char* v = getenv("NDT_K1"); return !v ? 0 : std::strcmp(v, "old") == 0 ? 1 : std::strcmp(v, "new") == 0 ? 2 : 0; }();
-  // The bucket form builds every dense grid (NDT_K1=old: the general chain, kept for index-only builds -- GICP's search
-  // index -- and as the cross-check of tools/fuzz_grid.py).  With its cells dealt to the buckets in short runs (k1_bucket)
-  // it is the faster form for every cloud shape measured, uniform to heavily clustered (tools/time_k1_forms.py).
-  const bool buckets_on = k1_mode != 1;
   ndt::GridBuildPlan plan{};
-  if (buckets_on && !h->index_only && ndt::grid_build_plan(geo.n_cells, n, plan)) {
+  const K1Form form = k1_form(h, hd, plan);
+  if (form != K1_CHAIN) {
     // ---- bucket form (ndt_kernels.hip "K1, bucket form"): no per-point global atomic, per-voxel work staged through LDS
     const size_t K = static_cast<size_t>(plan.n_buckets);
-    const size_t rec_slots = static_cast<size_t>(n) / static_cast<size_t>(std::max(1, h->min_pts)) + 1;  // slot = segment start / min_pts
-    HIP_TRY(g->recs.reserve(rec_slots));
-    HIP_TRY(g->centroids.reserve(rec_slots));
     DevBuf<unsigned> cntmat, order;
-    HIP_TRY(g->bucket_base.reserve(2 * K + 1));  // [K + 1] bucket bases, [K] valid voxels per bucket (k1_finalize -> k1_count)
-    HIP_TRY(cntmat.reserve((static_cast<size_t>(plan.n_blocks) + 1) * K));
-    HIP_TRY(order.reserve(5 * static_cast<size_t>(n)));
-    HIP_TRY(g->bpts.reserve(n));
-    ndt::GridBuildScratch S{};
-    S.cntmat = cntmat.p;
-    S.bucket_base = g->bucket_base.p;
-    S.bpts = g->bpts.p;
-    static const bool index_form_env = [] { const char* v = getenv("NDT_K1_INDEX"); return v && atoi(v) != 0; }();
-    S.index_form = index_form_env;
-    S.order = order.p;
-    static const bool want_stamps = [] { const char* v = getenv("NDT_K1_STAMPS"); return v && atoi(v) != 0; }();
     DevBuf<unsigned long long> stamps;
-    if (want_stamps) {
+    if (k1_stamps_on()) {
       HIP_TRY(stamps.reserve(8 * (K + std::max(K, static_cast<size_t>(plan.n_blocks)))));
       HIP_TRY(hipMemsetAsync(stamps.p, 0, 8 * (K + std::max(K, static_cast<size_t>(plan.n_blocks))) * sizeof(unsigned long long), st));
-      S.stamps = stamps.p;
+    }
+    ndt::SmallBuildDesc D{};
+    size_t lds = 0;
+    hs = setup_bucket_form(h, hd, plan, order, form == K1_SMALL ? &D : nullptr, &lds, false);
+    if (hs) return hs;
+    if (form == K1_SMALL) {
+      HIP_TRY(ndt::launch_grid_build_small(D, lds, stamps.p, st));
+    } else {
+      HIP_TRY(cntmat.reserve((static_cast<size_t>(plan.n_blocks) + 1) * K));
+      static const bool index_form_env = [] { const char* v = getenv("NDT_K1_INDEX"); return v && atoi(v) != 0; }();
+      const ndt::GridBuildScratch S{cntmat.p, g->bucket_base.p, g->bpts.p, order.p, stamps.p, index_form_env};
+      HIP_TRY(ndt::launch_grid_build_buckets(h->target->pts.p, n, h->target_dense, geo, plan, h->min_pts, h->eig_ratio, S, g->sorted_idx.p,
+                                             g->recs.p, g->centroids.p, g->lut.p, g->counts.p, st));
+      g->index_form = S.index_form;
     }
     // Records dense and in ascending cell order (maybe_compact_records: two small launches, ~13 us) pay for themselves as
     // soon as a few scans are registered against the grid: +8 % on lock-step batches, +1-5 % on a single 100k-point scan.
@@ -656,62 +751,8 @@ ndt_status build_grid(ndt_context* h) {
     // registration against it, or before the first lock-step batch (NDT_K1_COMPACT=eager: at once, as round 2 did; off: never).
     // The mapping nodes' 16 k-point clouds (records that fit L2 many times over) never compact.
     static const int compact_mode = [] { const char* v = getenv("NDT_K1_COMPACT"); return !v ? 1 : std::strcmp(v, "eager") == 0 ? 2 : std::strcmp(v, "off") == 0 ? 0 : 1; }();
-    static const bool small_on = [] { const char* v = getenv("NDT_K1_SMALL"); return !v || atoi(v) != 0; }();
-    const bool small_form = small_on && ndt::grid_build_small_applies(n, plan);
-    if (small_form) S.index_form = false;
-    g->index_form = S.index_form;
-    if (small_form)
-      HIP_TRY(ndt::launch_grid_build_small(h->target->pts.p, n, h->target_dense, geo, plan, h->min_pts, h->eig_ratio, S, g->sorted_idx.p,
-                                           g->recs.p, g->centroids.p, g->lut.p, g->counts.p, st));
-    else
-    HIP_TRY(ndt::launch_grid_build_buckets(h->target->pts.p, n, h->target_dense, geo, plan, h->min_pts, h->eig_ratio, S, g->sorted_idx.p,
-                                           g->recs.p, g->centroids.p, g->lut.p, g->counts.p, st));
     g->compact_pending = n > 65536 && compact_mode != 0;
-    if (want_stamps) {  // k1_finalize's phase clocks: per phase the median and the maximum over the buckets (shader cycles)
-      std::vector<unsigned long long> hst(8 * K);
-      HIP_TRY(hipMemcpyAsync(hst.data(), stamps.p, 8 * K * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      static const char* names[8] = {"load+rank", "scans+select", "place", "teams", "sums+finish", "passes", "points", "total"};
-      std::fprintf(stderr, "[k1_finalize clocks, %zu buckets] ", K);
-      for (int q = 0; q < 8; q++) {
-        std::vector<unsigned long long> d;
-        for (size_t b = 0; b < K; b++)
-          if (hst[8 * b + 7]) d.push_back(hst[8 * b + q]);
-        if (d.empty()) continue;
-        std::sort(d.begin(), d.end());
-        std::fprintf(stderr, "%s %llu/%llu  ", names[q], d[d.size() / 2], d.back());
-      }
-      std::fprintf(stderr, "\n");
-      if (small_form) {  // k1_small: cycles from the block's start to the end of the scan / the publication / the end
-        std::vector<unsigned long long> hk(4 * K);
-        HIP_TRY(hipMemcpy(hk.data(), stamps.p + 8 * K, 4 * K * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        std::fprintf(stderr, "[k1_small clocks, %zu blocks, cycles since the block's start: scan / published / end] ", K);
-        for (int q = 1; q < 4; q++) {
-          std::vector<unsigned long long> d;
-          for (size_t b = 0; b < K; b++) d.push_back(hk[4 * b + q] - hk[4 * b]);
-          std::sort(d.begin(), d.end());
-          std::fprintf(stderr, "%llu/%llu  ", d[d.size() / 2], d.back());
-        }
-        unsigned long long t_lo = ~0ull, t_hi = 0;
-        for (size_t b = 0; b < K; b++) { t_lo = std::min(t_lo, hk[4 * b]); t_hi = std::max(t_hi, hk[4 * b + 3]); }
-        std::fprintf(stderr, " first start -> last end %llu\n", t_hi - t_lo);
-      }
-      const size_t B = small_form ? 0 : static_cast<size_t>(plan.n_blocks);
-      std::vector<unsigned long long> hs(8 * B + 1);
-      HIP_TRY(hipMemcpy(hs.data(), stamps.p + 8 * K, 8 * B * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-      if (B) std::fprintf(stderr, "[k1_scatter clocks, %zu blocks, cycles since the block's start: tables / ranks / column scan / stores] ", B);
-      for (int q = 1; q < 5; q++) {
-        std::vector<unsigned long long> d;
-        for (size_t bq = 0; bq < B; bq++)
-          if (hs[8 * bq] && hs[8 * bq + q]) d.push_back(hs[8 * bq + q] - hs[8 * bq]);
-        if (d.empty()) continue;
-        std::sort(d.begin(), d.end());
-        std::fprintf(stderr, "%llu/%llu  ", d[d.size() / 2], d.back());
-      }
-      std::fprintf(stderr, "\n");
-    }
-    g->plan = plan;
-    g->leaves_pending = true;  // leaf arrays and the occupied / candidate counts: on demand (grid_counts)
+    if (k1_stamps_on() && (hs = print_k1_stamps(h, stamps.p, plan, form == K1_SMALL))) return hs;
     if (compact_mode == 2 && g->compact_pending) {
       ndt_status cs = compact_records_now(h, g.get());
       if (cs) return cs;
@@ -762,10 +803,6 @@ ndt_status build_grid(ndt_context* h) {
 
 ndt_status build_grids(ndt_context* h, const std::vector<std::shared_ptr<DeviceCloud>>& targets, int is_dense,
                        std::vector<std::shared_ptr<DeviceGrid>>& out, size_t* n_small) {
-  // the forms build_grid would choose: the small one only where build_grid takes it (same switches)
-  static const bool chain_only = [] { const char* v = getenv("NDT_K1"); return v && std::strcmp(v, "old") == 0; }();
-  static const bool small_on = [] { const char* v = getenv("NDT_K1_SMALL"); return !v || atoi(v) != 0; }();
-  static const bool want_stamps = [] { const char* v = getenv("NDT_K1_STAMPS"); return v && atoi(v) != 0; }();
   const std::shared_ptr<DeviceCloud> keep_target = h->target;
   const std::shared_ptr<DeviceGrid> keep_grid = h->grid;
   const int keep_dense = h->target_dense;
@@ -785,51 +822,18 @@ ndt_status build_grids(ndt_context* h, const std::vector<std::shared_ptr<DeviceC
       out[i] = h->grid;
       continue;
     }
-    DeviceGrid* g = hd.g.get();
+    // the one-launch form where build_grid takes it; stamped builds (development aid) through build_grid
     ndt::GridBuildPlan plan{};
-    ndt::SmallBuildDesc D{};
-    size_t lds_i = 0;
-    const bool small_form = !hd.sparse && !chain_only && !h->index_only && !want_stamps && small_on &&
-                            ndt::grid_build_plan(g->geom.n_cells, hd.n, plan) && ndt::grid_build_small_applies(hd.n, plan) &&
-                            ndt::small_build_desc(hd.n, plan, D, &lds_i);
-    if (!small_form) {
+    if (k1_stamps_on() || k1_form(h, hd, plan) != K1_SMALL) {
       s = build_grid(h);
       out[i] = h->grid;
       continue;
     }
-    // the small form's buffers, as build_grid reserves them
-    const size_t n = static_cast<size_t>(hd.n), K = static_cast<size_t>(plan.n_buckets);
-    const size_t rec_slots = n / static_cast<size_t>(std::max(1, h->min_pts)) + 1;
-    auto& sc = *scratch.emplace_back(new DevBuf<unsigned>());
-    if (g->counts.reserve(8) || g->leaf_cell.reserve(hd.max_leaves) || g->leaf_start.reserve(hd.max_leaves) || g->leaf_count.reserve(hd.max_leaves) ||
-        g->leaf_rec.reserve(hd.max_leaves) || g->sorted_idx.reserve(n) || g->lut.reserve(static_cast<size_t>(g->geom.lut_cells)) ||
-        g->recs.reserve(rec_slots) || g->centroids.reserve(rec_slots) || g->bucket_base.reserve(2 * K + 1) || g->bpts.reserve(n) ||
-        sc.reserve(5 * n)) {
-      s = fail(NDT_ERR_HIP, "out of device memory for the pairs grids");
-      break;
-    }
-    D.pts = h->target->pts.p;
-    D.dense = h->target_dense;
-    D.g = g->geom;
-    D.min_pts = h->min_pts;
-    D.eig_ratio = h->eig_ratio;
-    D.bucket_base = g->bucket_base.p;
-    D.bpts = g->bpts.p;
-    D.sorted_idx = g->sorted_idx.p;
-    D.recs = g->recs.p;
-    D.centroids = g->centroids.p;
-    D.lut = g->lut.p;
-    D.scratch = sc.p;
-    D.counts = g->counts.p;
-    descs.push_back(D);
+    size_t lds_i = 0;
+    s = setup_bucket_form(h, hd, plan, *scratch.emplace_back(new DevBuf<unsigned>()), &descs.emplace_back(), &lds_i, true);
+    if (s) break;
     max_K = std::max(max_K, plan.n_buckets);
     lds = std::max(lds, lds_i);
-    g->index_form = false;
-    g->compact_pending = false;  // (a small cloud: build_grid compacts from 65536 points on)
-    g->plan = plan;
-    g->leaves_pending = true;
-    g->counts_known = false;
-    g->empty = false;
     out[i] = hd.g;
   }
   h->target = keep_target;

@@ -5,7 +5,8 @@
 //                    ordinals, LUT init) -> counting-sort scatter of point indices -> k_presort_large (crowded voxels) ->
 //                    k_finalize
 //    bucket form:    k1_hist -> k1_colscan -> k1_scatter -> k1_finalize (order-preserving: no global atomics, no sort by
-//                    point index; crowded cells summed by lane teams), k1_count / k1_leaves on demand
+//                    point index; crowded cells summed by lane teams), k1_count / k1_leaves on demand; small clouds in
+//                    ONE launch: k1_small (one cloud) / k1_small_multi (many), the same block body k1_small_block
 //    (the sort-based sparse form is ndt_sparse.hip; all three end in finish_voxel: index-ordered f64 sums -- bit-identical
 //    to the reference's sequential accumulation --, mean, covariance with the reference's quirks, 3x3 symmetric
 //    eigen-solve, eigenvalue inflation, inverse, validity -> 64-B VoxelRec)
@@ -1941,27 +1942,34 @@ __device__ __forceinline__ void k1_finish_small(const Src& src, const int k, con
 // ---------------------------------------------------------------------------
 // K1 for small clouds (the mapping nodes' 16 k points): ONE launch.  The four-kernel chain above is, at that size, four launch
 // boundaries around ~3 us of work each.  Here every block reads the WHOLE cloud (256 KB out of L2), keeps the points of its
-// own bucket and only counts the others, and then finishes its bucket exactly as k1_finalize does:
-//   scan     eight waves (two per SIMD: one wave alone issues a dependent instruction every ~8 cycles, two share the SIMD
-//            without slowing each other); wave w walks the w-th eighth of the cloud in 64-point chunks: cell, bucket; ballot of "bucket below mine" ->
-//            running count (the bucket's base in the bucket order, without any histogram, scan or exchange between blocks),
-//            ballot of "mine" -> the point goes to the wave's list in LDS (x, y, z, index).  The lists of waves 0..7 one
-//            after the other hold the bucket's points in ascending point index -- the order k1_scatter produces.
+// own bucket and only counts the others, and then finishes its bucket exactly as k1_finalize does.  One block body,
+// k1_small_block<WAVES, RANGE>, serves two kernels: k1_small (one cloud; kSmallWaves scanning waves) and k1_small_multi
+// (many clouds, blockIdx.y = cloud; kMultiWaves scanning waves, every point's cell index range-tested per axis):
+//   scan     WAVES waves (k1_small: two per SIMD -- one wave alone issues a dependent instruction every ~8 cycles, two share
+//            the SIMD without slowing each other); wave w walks the w-th part of the cloud in 64-point chunks: cell, bucket;
+//            ballot of "bucket below mine" -> running count (the bucket's base in the bucket order, without any histogram,
+//            scan or exchange between blocks), ballot of "mine" -> the point goes to the wave's list in LDS (x, y, z,
+//            index).  The lists of the waves one after the other hold the bucket's points in ascending point index -- the
+//            order k1_scatter produces, whatever the number of waves: the two kernels give the same grid, bit for bit.
 //   publish  bucket_base[k], the bucketed points (the leaf pass and grid_counts read both later on)
 //   table    the block owns the look-up table slots of its bucket's cells (all written: record or empty) and the border
 //            slots of the k-th slice of the padded table -- every slot has one writer, nothing is cleared beforehand
-//   finish   by the first four waves (the others have ended): k1_finish_small / k1_finalize_bucket on the lists
+//   finish   by the first kBlock / kWave waves (k1_small's others end before the finish's barriers):
+//            k1_finish_small / k1_finalize_bucket on the lists
 // No block waits for another one: no grid barrier, no co-residency requirement, fine on a CU-masked stream or beside a
 // resident evaluation server.  The price is the redundant scan, n x K cell computations (~5 us per 16 k points on every
 // CU: issue-bound, not memory-bound -- the same loop over one L1-resident kilobyte is 8 % faster) -- hence small clouds
-// only.  A wave whose list overflows (a bucket with more than list_cap points from one eighth of the cloud) is detected by the whole block; the block then scans a second time and writes its points straight to their
-// final places in the bucketed cloud, and finishes from there.
+// only.  A wave whose list overflows (a bucket with more than list_cap points from one wave's part of the cloud) is
+// detected by the whole block; the block then scans a second time and writes its points straight to their final places
+// in the bucketed cloud, and finishes from there.
 // ---------------------------------------------------------------------------
-constexpr int kSmallWaves = 8;                      // waves of the scan (two per SIMD); the first kBlock / kWave of them finish the bucket
+constexpr int kSmallWaves = 8;                      // k1_small's scanning waves (two per SIMD)
 constexpr int kSmallThreads = kSmallWaves * kWave;  // 512
+constexpr int kMultiWaves = kBlock / kWave;         // k1_small_multi's: the finish's block, so every wave meets its barriers
+static_assert(kMultiWaves <= kSmallWaves, "K1ListSrc walks kSmallWaves segments");
 struct K1ListSrc {
-  const float4* list;    // [kSmallWaves][cap]
-  const unsigned* seg;   // LDS [kSmallWaves + 1]: first bucket position of every wave's list, then nb
+  const float4* list;    // [WAVES][cap]
+  const unsigned* seg;   // LDS [kSmallWaves + 1]: first bucket position of every wave's list, then nb (past the last wave: nb)
   int cap;
   const float4* spilled;  // after an overflow: the bucket's slice of the bucketed cloud instead (else null)
   __device__ __forceinline__ float4 operator()(unsigned j) const {
@@ -1978,7 +1986,7 @@ constexpr int kSmallBatch = 8;               // 64-point chunks a wave has in fl
 // multiply-adds below are exact and the cell needs no further range test: a small grid has fewer than 2^24 cells), the run's
 // bucket by a mask when K is a power of two.  -1: not a point of the grid (non-finite, or outside the box: garbage in a
 // cloud declared dense) -- such a point is dropped here, so the finish never sees it.
-template <bool DENSE, bool POW2>
+template <bool DENSE, bool POW2, bool RANGE>
 __device__ __forceinline__ int small_bucket(const GridGeom& g, const K1Deal& deal, float x, float y, float z) {
 #pragma clang fp contract(off)
   const float fx = x * g.inv_leaf[0], fy = y * g.inv_leaf[1], fz = z * g.inv_leaf[2];
@@ -1986,9 +1994,11 @@ __device__ __forceinline__ int small_bucket(const GridGeom& g, const K1Deal& dea
   const int i1 = static_cast<int>(floorf(fy) - static_cast<float>(g.min_b[1]));
   const int i2 = static_cast<int>(floorf(fz) - static_cast<float>(g.min_b[2]));
   // The box is the box of these very points, so a finite point is inside it -- 0 <= i < div_b < 2^24 on every axis, the
-  // 24-bit multiply-adds are exact and equal build_cell's -- and needs no range test.  What is not finite: in a cloud
-  // declared dense nothing that gets here (an infinity makes the box overflow, the host stops before any kernel; a NaN
-  // converts to index 0 on every axis here as in build_cell); otherwise the point is dropped.
+  // 24-bit multiply-adds are exact and equal build_cell's -- and needs no range test (RANGE: tested all the same, as k_count
+  // tests its cell).  What is not finite: in a cloud declared dense nothing that gets here (an infinity makes the box
+  // overflow, the host stops before any kernel; a NaN converts to index 0 on every axis here as in build_cell); otherwise
+  // the point is dropped.
+  if (RANGE && (i0 < 0 || i0 >= g.div_b[0] || i1 < 0 || i1 >= g.div_b[1] || i2 < 0 || i2 >= g.div_b[2])) return -1;
   const unsigned cell = __umul24(static_cast<unsigned>(i2), static_cast<unsigned>(g.mul[2])) +
                         (__umul24(static_cast<unsigned>(i1), static_cast<unsigned>(g.mul[1])) + static_cast<unsigned>(i0));
   const unsigned run = cell >> deal.rb;
@@ -2010,14 +2020,14 @@ __device__ __forceinline__ int small_bucket(const GridGeom& g, const K1Deal& dea
 // One scan of this wave's chunks [c_lo, c_hi).  PASS 0: count the points of the buckets below k (-> below), collect the
 // points of bucket k in the wave's list (own = how many there are, also beyond the list's capacity).  PASS 1: the points of
 // bucket k go to out[own++] (their final places in the bucketed cloud).
-template <bool DENSE, bool POW2, int PASS>
+template <bool DENSE, bool POW2, bool RANGE, int PASS>
 __device__ __forceinline__ void small_scan(const float4* __restrict__ pts, int n, const GridGeom& g, const K1Deal& deal, int k, int c_lo, int c_hi,
                                            float4* mylist, int list_cap, float4* __restrict__ out, unsigned& own_out, unsigned& below_out) {
   const int lane = threadIdx.x & (kWave - 1);
   unsigned own = 0, below = 0;  // wave-uniform
   const int full_hi = min(c_hi, n / kWave);  // chunks below this one are whole: no bounds test per point
   auto visit = [&](const float4& p, int i, bool in_range) {
-    int b = small_bucket<DENSE, POW2>(g, deal, p.x, p.y, p.z);
+    int b = small_bucket<DENSE, POW2, RANGE>(g, deal, p.x, p.y, p.z);
     if (!in_range) b = -1;
     if (PASS == 0) below += static_cast<unsigned>(__popcll(__ballot(static_cast<unsigned>(b) < static_cast<unsigned>(k))));
     const unsigned long long mine = __ballot(b == k);
@@ -2070,35 +2080,34 @@ __device__ __forceinline__ void small_scan(const float4* __restrict__ pts, int n
   below_out = below;
 }
 
-__global__ __launch_bounds__(kSmallThreads) void k1_small(const float4* __restrict__ pts, int n, int dense, GridGeom g, int map, int K, int C, int min_pts,
-                                                   double eig_ratio, int lds_cap, int wmax, int list_cap, unsigned fin_words /* LDS words of the finish */,
-                                                   int small_finish /* buckets up to this size: k1_finish_small (0: never) */,
-                                                   unsigned* __restrict__ bucket_base, float4* __restrict__ bpts, int* __restrict__ sorted_idx,
-                                                   VoxelRec* __restrict__ recs, VoxelSide* __restrict__ centroids, int* __restrict__ lut,
-                                                   unsigned* __restrict__ bucket_valid, unsigned* __restrict__ scratch, unsigned* __restrict__ counts,
-                                                   unsigned long long* __restrict__ st /* development aid (NDT_K1_STAMPS), or null */) {
+// The block of bucket k of the cloud D describes: WAVES waves scan, the first kBlock / kWave of them finish the bucket.
+// st: the phase clocks of NDT_K1_STAMPS (development aid), or null.  (D is a pointer: a reference parameter, and k1_small
+// taking a SmallBuildDesc argument, each changed the kernels' code generation.)
+template <int WAVES, bool RANGE>
+__device__ __forceinline__ void k1_small_block(const SmallBuildDesc* D, const int k, unsigned long long* st) {
   extern __shared__ unsigned k1_lds[];
   auto mark = [&](int q) {  // thread 0's clock: 0 start, 1 scan done, 2 published + table slots cleared, 3 end
-    if (st && threadIdx.x == 0) st[8 * static_cast<size_t>(K) + 4 * blockIdx.x + q] = stamp();
+    if (st && threadIdx.x == 0) st[8 * static_cast<size_t>(D->K) + 4 * blockIdx.x + q] = stamp();
   };
   mark(0);
-  const K1Deal deal(map & 255, map >> 8);
-  __shared__ unsigned s_own[kSmallWaves], s_below[kSmallWaves], s_seg[kSmallWaves + 1];
-  float4* list = reinterpret_cast<float4*>(k1_lds + fin_words);  // (fin_words is a multiple of 4)
-  const int k = blockIdx.x;
+  const GridGeom g = D->g;
+  const int n = D->n, K = D->K, C = D->C, list_cap = D->list_cap;
+  const K1Deal deal(D->map & 255, D->map >> 8);
+  __shared__ unsigned s_own[WAVES], s_below[WAVES], s_seg[kSmallWaves + 1];
+  float4* list = reinterpret_cast<float4*>(k1_lds + D->fin_words);  // (fin_words is a multiple of 4)
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  const int chunks = (n + kWave - 1) / kWave, per = (chunks + kSmallWaves - 1) / kSmallWaves;  // chunks per wave
+  const int chunks = (n + kWave - 1) / kWave, per = (chunks + WAVES - 1) / WAVES;  // chunks per wave
   const int c_lo = min(chunks, wave * per), c_hi = min(chunks, c_lo + per);
   float4* mylist = list + wave * list_cap;
   const bool pow2 = (K & (K - 1)) == 0;
   // ---- scan ----
   unsigned own = 0, below = 0;
-  if (dense) {
-    if (pow2) small_scan<true, true, 0>(pts, n, g, deal, k, c_lo, c_hi, mylist, list_cap, nullptr, own, below);
-    else small_scan<true, false, 0>(pts, n, g, deal, k, c_lo, c_hi, mylist, list_cap, nullptr, own, below);
+  if (D->dense) {
+    if (pow2) small_scan<true, true, RANGE, 0>(D->pts, n, g, deal, k, c_lo, c_hi, mylist, list_cap, nullptr, own, below);
+    else small_scan<true, false, RANGE, 0>(D->pts, n, g, deal, k, c_lo, c_hi, mylist, list_cap, nullptr, own, below);
   } else {
-    if (pow2) small_scan<false, true, 0>(pts, n, g, deal, k, c_lo, c_hi, mylist, list_cap, nullptr, own, below);
-    else small_scan<false, false, 0>(pts, n, g, deal, k, c_lo, c_hi, mylist, list_cap, nullptr, own, below);
+    if (pow2) small_scan<false, true, RANGE, 0>(D->pts, n, g, deal, k, c_lo, c_hi, mylist, list_cap, nullptr, own, below);
+    else small_scan<false, false, RANGE, 0>(D->pts, n, g, deal, k, c_lo, c_hi, mylist, list_cap, nullptr, own, below);
   }
   if (lane == 0) {
     s_own[wave] = own;
@@ -2108,7 +2117,7 @@ __global__ __launch_bounds__(kSmallThreads) void k1_small(const float4* __restri
   mark(1);
   unsigned base_w = 0, bb = 0, nb = 0;
   bool overflow = false;
-  for (int w = 0; w < kSmallWaves; w++) {
+  for (int w = 0; w < WAVES; w++) {
     bb += s_below[w];
     if (w < wave) base_w += s_own[w];
     nb += s_own[w];
@@ -2116,28 +2125,27 @@ __global__ __launch_bounds__(kSmallThreads) void k1_small(const float4* __restri
   }
   if (overflow) {  // (uniform, rare) a list was too short: a second scan, the points straight to their final places
     unsigned own2 = 0, dummy = 0;
-    if (dense) small_scan<true, false, 1>(pts, n, g, deal, k, c_lo, c_hi, nullptr, 0, bpts + bb + base_w, own2, dummy);
-    else small_scan<false, false, 1>(pts, n, g, deal, k, c_lo, c_hi, nullptr, 0, bpts + bb + base_w, own2, dummy);
+    if (D->dense) small_scan<true, false, RANGE, 1>(D->pts, n, g, deal, k, c_lo, c_hi, nullptr, 0, D->bpts + bb + base_w, own2, dummy);
+    else small_scan<false, false, RANGE, 1>(D->pts, n, g, deal, k, c_lo, c_hi, nullptr, 0, D->bpts + bb + base_w, own2, dummy);
   }
   if (threadIdx.x == 0) {
     unsigned run = 0;
-    for (int w = 0; w < kSmallWaves; w++) {
+    for (int w = 0; w <= kSmallWaves; w++) {
       s_seg[w] = run;
-      run += s_own[w];
+      if (w < WAVES) run += s_own[w];
     }
-    s_seg[kSmallWaves] = run;
-    bucket_base[k] = bb;
+    D->bucket_base[k] = bb;
     if (k == K - 1) {
-      bucket_base[K] = bb + nb;
-      counts[0] = bb + nb;  // points binned
+      D->bucket_base[K] = bb + nb;
+      D->counts[0] = bb + nb;  // points binned
     }
   }
-  const K1ListSrc lsrc{list, s_seg, list_cap, overflow ? bpts + bb : nullptr};
-  if (!overflow) {  // (uniform)
-    __syncthreads();  // s_seg
-    for (unsigned j = threadIdx.x; j < nb; j += kSmallThreads) bpts[bb + j] = lsrc(j);
-  }
+  __syncthreads();  // s_seg
+  const K1ListSrc lsrc{list, s_seg, list_cap, overflow ? D->bpts + bb : nullptr};
+  if (!overflow)  // (uniform)
+    for (unsigned j = threadIdx.x; j < nb; j += WAVES * kWave) D->bpts[bb + j] = lsrc(j);
   // ---- the look-up table: border slots of my slice, and every cell of my bucket starts out empty ----
+  int* lut = D->lut;
   {
     const long long per_blk = (g.lut_cells + K - 1) / K;
     const long long lo = static_cast<long long>(k) * per_blk, hi = min(g.lut_cells, lo + per_blk);
@@ -2153,14 +2161,14 @@ __global__ __launch_bounds__(kSmallThreads) void k1_small(const float4* __restri
     };
     const float rp2 = 1.0f / static_cast<float>(g.pmul[2]), rp1 = 1.0f / static_cast<float>(g.pmul[1]);
     const float rm2 = 1.0f / static_cast<float>(g.mul[2]), rm1 = 1.0f / static_cast<float>(g.mul[1]);
-    for (long long sl = lo + threadIdx.x; sl < hi; sl += kSmallThreads) {
+    for (long long sl = lo + threadIdx.x; sl < hi; sl += WAVES * kWave) {
       const unsigned u = static_cast<unsigned>(sl);  // (a small grid's padded table has fewer than 2^31 slots)
       const int pz = static_cast<int>(divq(u, static_cast<unsigned>(g.pmul[2]), rp2));
       const unsigned rem = u - static_cast<unsigned>(pz) * static_cast<unsigned>(g.pmul[2]);
       const int py = static_cast<int>(divq(rem, static_cast<unsigned>(g.pmul[1]), rp1)), px = static_cast<int>(rem) - py * g.pmul[1];
       if (px < kLutBorder || px >= ex || py < kLutBorder || py >= ey || pz < kLutBorder || pz >= ez) lut[sl] = kLutEmpty;
     }
-    for (int lc = threadIdx.x; lc < C; lc += kSmallThreads) {
+    for (int lc = threadIdx.x; lc < C; lc += WAVES * kWave) {
       const long long cell = static_cast<unsigned>(k1_cell(k, lc, deal));
       if (cell < g.n_cells) {
         const unsigned c = static_cast<unsigned>(cell);
@@ -2173,210 +2181,33 @@ __global__ __launch_bounds__(kSmallThreads) void k1_small(const float4* __restri
   }
   __syncthreads();  // the bucketed points and the empty slots are out before anything of the finish reads / overwrites them
   mark(2);
-  // The finish is written for kBlock threads: the scan's other waves end here.  (A barrier waits for the waves of the
-  // workgroup that have not terminated -- s_barrier, CDNA3 ISA 4.4 -- so the barriers of the finish are the four waves' own.)
-  if (threadIdx.x >= kBlock) return;
-  if (nb <= static_cast<unsigned>(small_finish))  // (uniform)
-    k1_finish_small(lsrc, k, bb, nb, k1_lds, g, deal, min_pts, eig_ratio, sorted_idx, recs, centroids, lut, bucket_valid);
+  // The finish is written for kBlock threads: k1_small's other scanning waves end here.  (A barrier waits for the waves of
+  // the workgroup that have not terminated -- s_barrier, CDNA3 ISA 4.4 -- so the barriers of the finish are the four waves' own.)
+  if (WAVES * kWave > kBlock && threadIdx.x >= kBlock) return;
+  unsigned* bucket_valid = D->bucket_base + K + 1;
+  if (nb <= static_cast<unsigned>(D->small_finish))  // (uniform)
+    k1_finish_small(lsrc, k, bb, nb, k1_lds, g, deal, D->min_pts, D->eig_ratio, D->sorted_idx, D->recs, D->centroids, lut, bucket_valid);
   else
-    k1_finalize_bucket(lsrc, k, bb, nb, k1_lds, g, deal, C, min_pts, lds_cap, wmax, sorted_idx, K1RecordFin{min_pts, eig_ratio, recs, centroids, lut, &g},
-                       bucket_valid, scratch, static_cast<unsigned>(n), st);
+    k1_finalize_bucket(lsrc, k, bb, nb, k1_lds, g, deal, C, D->min_pts, D->lds_cap, D->wmax, D->sorted_idx,
+                       K1RecordFin{D->min_pts, D->eig_ratio, D->recs, D->centroids, lut, &g}, bucket_valid, D->scratch, static_cast<unsigned>(n), st);
   mark(3);
 }
 
-// ---------------------------------------------------------------------------
-// k1_small for MANY targets in one launch (ndt_align_pairs: every small target of a call).  blockIdx.y = target, blockIdx.x =
-// bucket; a target's descriptor holds what k1_small takes as arguments.  The records, table, bucketed points and counts are
-// k1_small's for that cloud, bit for bit: a bucket's points are listed in point order whatever the number of scanning
-// waves (every wave takes a contiguous run of chunks, the lists are concatenated in wave order), and the finish is the same
-// code on the same list.  Two differences from k1_small, both deliberate:
-//  - the block is kBlock threads, the size the finish is written for, so that EVERY wave that scans also runs the finish
-//    and meets each of its barriers (k1_small ends its extra scanning waves before the finish's barriers);
-//  - every point's cell index is range-tested per axis before it is used (as k_count tests its cell).
-// ---------------------------------------------------------------------------
-constexpr int kMultiWaves = kBlock / kWave;
-static_assert(kMultiWaves <= kSmallWaves, "K1ListSrc walks kSmallWaves segments");
-
-template <bool DENSE, bool POW2>
-__device__ __forceinline__ int multi_bucket(const GridGeom& g, const K1Deal& deal, float x, float y, float z) {
-#pragma clang fp contract(off)
-  const float fx = x * g.inv_leaf[0], fy = y * g.inv_leaf[1], fz = z * g.inv_leaf[2];
-  const int i0 = static_cast<int>(floorf(fx) - static_cast<float>(g.min_b[0]));
-  const int i1 = static_cast<int>(floorf(fy) - static_cast<float>(g.min_b[1]));
-  const int i2 = static_cast<int>(floorf(fz) - static_cast<float>(g.min_b[2]));
-  if (i0 < 0 || i0 >= g.div_b[0] || i1 < 0 || i1 >= g.div_b[1] || i2 < 0 || i2 >= g.div_b[2]) return -1;
-  const unsigned cell = __umul24(static_cast<unsigned>(i2), static_cast<unsigned>(g.mul[2])) +
-                        (__umul24(static_cast<unsigned>(i1), static_cast<unsigned>(g.mul[1])) + static_cast<unsigned>(i0));
-  const unsigned run = cell >> deal.rb;
-  int b;
-  if (POW2) {
-    b = static_cast<int>(run & (deal.K - 1u));
-  } else {
-    unsigned q, r;
-    deal.divmod(run, q, r);
-    b = static_cast<int>(r);
-  }
-  if (!DENSE) {
-    const float t = (fx + fy) + fz;  // not finite as soon as one coordinate is not
-    if (!(fabsf(t) < INFINITY)) b = -1;
-  }
-  return b;
+__global__ __launch_bounds__(kSmallThreads) void k1_small(const float4* __restrict__ pts, int n, int dense, GridGeom g, int map, int K, int C, int min_pts,
+                                                   double eig_ratio, int lds_cap, int wmax, int list_cap, unsigned fin_words, int small_finish,
+                                                   unsigned* __restrict__ bucket_base, float4* __restrict__ bpts, int* __restrict__ sorted_idx,
+                                                   VoxelRec* __restrict__ recs, VoxelSide* __restrict__ centroids, int* __restrict__ lut,
+                                                   unsigned* __restrict__ scratch, unsigned* __restrict__ counts, unsigned long long* __restrict__ st) {
+  const SmallBuildDesc D{pts, n, dense, g, map, K, C, min_pts, eig_ratio, lds_cap, wmax, list_cap, fin_words, small_finish,
+                         bucket_base, bpts, sorted_idx, recs, centroids, lut, scratch, counts};
+  k1_small_block<kSmallWaves, false>(&D, blockIdx.x, st);
 }
 
-// one scan of this wave's chunks [c_lo, c_hi): PASS 0 counts the points of the buckets below k and lists bucket k's points;
-// PASS 1 writes bucket k's points to out[] (their final places) -- small_scan's passes and loop, with multi_bucket's range test
-template <bool DENSE, bool POW2, int PASS>
-__device__ __forceinline__ void multi_scan(const float4* __restrict__ pts, int n, const GridGeom& g, const K1Deal& deal, int k, int c_lo, int c_hi,
-                                           float4* mylist, int list_cap, float4* __restrict__ out, unsigned& own_out, unsigned& below_out) {
-  const int lane = threadIdx.x & (kWave - 1);
-  unsigned own = 0, below = 0;  // wave-uniform
-  auto visit = [&](const float4& p, int i, bool in_range) {
-    int b = multi_bucket<DENSE, POW2>(g, deal, p.x, p.y, p.z);
-    if (!in_range) b = -1;
-    if (PASS == 0) below += static_cast<unsigned>(__popcll(__ballot(static_cast<unsigned>(b) < static_cast<unsigned>(k))));
-    const unsigned long long mine = __ballot(b == k);
-    if (mine) {  // (uniform)
-      const unsigned pos = own + __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(mine >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(mine), 0u));
-      if (b == k) {
-        const float4 q = make_float4(p.x, p.y, p.z, __int_as_float(i));
-        if (PASS == 0) {
-          if (pos < static_cast<unsigned>(list_cap)) mylist[pos] = q;
-        } else {
-          out[pos] = q;
-        }
-      }
-      own += static_cast<unsigned>(__popcll(mine));
-    }
-  };
-  const int full_hi = min(c_hi, n / kWave);  // chunks below this one are whole
-  int c0 = c_lo;
-  if (c0 + kSmallBatch <= full_hi) {  // whole batches, two register sets (small_scan's loop: loads of the next batch in flight)
-    const int nbat = (full_hi - c_lo) / kSmallBatch;
-    float4 pa[kSmallBatch], pb[kSmallBatch];
-    auto fetch = [&](float4* dst, int t) {
-      const int cb = c_lo + t * kSmallBatch;
-#pragma unroll
-      for (int u = 0; u < kSmallBatch; u++) dst[u] = pts[(cb + u) * kWave + lane];
-    };
-    auto look = [&](const float4* src, int t) {
-      const int cb = c_lo + t * kSmallBatch;
-#pragma unroll
-      for (int u = 0; u < kSmallBatch; u++) visit(src[u], (cb + u) * kWave + lane, true);
-    };
-    fetch(pa, 0);
-    for (int t = 0; t < nbat; t += 2) {
-      fetch(pb, min(t + 1, nbat - 1));
-      look(pa, t);
-      fetch(pa, min(t + 2, nbat - 1));
-      if (t + 1 < nbat) look(pb, t + 1);  // (uniform)
-    }
-    c0 = c_lo + nbat * kSmallBatch;
-  }
-  for (; c0 < c_hi; c0++) {  // the rest, chunk by chunk
-    const int i = c0 * kWave + lane;
-    visit(pts[min(i, n - 1)], i, i < n);
-  }
-  own_out = own;
-  below_out = below;
-}
-
+// blockIdx.y = cloud, blockIdx.x = bucket
 __global__ __launch_bounds__(kBlock) void k1_small_multi(const SmallBuildDesc* __restrict__ descs) {
-  extern __shared__ unsigned k1_lds[];
   const SmallBuildDesc& D = descs[blockIdx.y];
-  const int k = blockIdx.x;
-  if (k >= D.K) return;  // (the whole block, before any barrier: grid.x is the largest K of the launch)
-  const GridGeom g = D.g;
-  const int n = D.n, K = D.K, C = D.C, list_cap = D.list_cap;
-  const K1Deal deal(D.map & 255, D.map >> 8);
-  __shared__ unsigned s_own[kMultiWaves], s_below[kMultiWaves], s_seg[kSmallWaves + 1];
-  float4* list = reinterpret_cast<float4*>(k1_lds + D.fin_words);
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  const int chunks = (n + kWave - 1) / kWave, per = (chunks + kMultiWaves - 1) / kMultiWaves;
-  const int c_lo = min(chunks, wave * per), c_hi = min(chunks, c_lo + per);
-  float4* mylist = list + wave * list_cap;
-  const bool pow2 = (K & (K - 1)) == 0;
-  unsigned own = 0, below = 0;
-  if (D.dense) {
-    if (pow2) multi_scan<true, true, 0>(D.pts, n, g, deal, k, c_lo, c_hi, mylist, list_cap, nullptr, own, below);
-    else multi_scan<true, false, 0>(D.pts, n, g, deal, k, c_lo, c_hi, mylist, list_cap, nullptr, own, below);
-  } else {
-    if (pow2) multi_scan<false, true, 0>(D.pts, n, g, deal, k, c_lo, c_hi, mylist, list_cap, nullptr, own, below);
-    else multi_scan<false, false, 0>(D.pts, n, g, deal, k, c_lo, c_hi, mylist, list_cap, nullptr, own, below);
-  }
-  if (lane == 0) {
-    s_own[wave] = own;
-    s_below[wave] = below;
-  }
-  __syncthreads();
-  unsigned base_w = 0, bb = 0, nb = 0;
-  bool overflow = false;
-  for (int w = 0; w < kMultiWaves; w++) {
-    bb += s_below[w];
-    if (w < wave) base_w += s_own[w];
-    nb += s_own[w];
-    overflow = overflow || s_own[w] > static_cast<unsigned>(list_cap);
-  }
-  if (overflow) {  // (uniform) a list was too short: a second scan, the points straight to their final places
-    unsigned own2 = 0, dummy = 0;
-    if (D.dense) multi_scan<true, false, 1>(D.pts, n, g, deal, k, c_lo, c_hi, nullptr, 0, D.bpts + bb + base_w, own2, dummy);
-    else multi_scan<false, false, 1>(D.pts, n, g, deal, k, c_lo, c_hi, nullptr, 0, D.bpts + bb + base_w, own2, dummy);
-  }
-  if (threadIdx.x == 0) {
-    unsigned run = 0;
-    for (int w = 0; w <= kSmallWaves; w++) {  // (segments past the last wave: empty, at nb)
-      s_seg[w] = run;
-      if (w < kMultiWaves) run += s_own[w];
-    }
-    D.bucket_base[k] = bb;
-    if (k == K - 1) {
-      D.bucket_base[K] = bb + nb;
-      D.counts[0] = bb + nb;  // points binned
-    }
-  }
-  __syncthreads();  // s_seg (every wave, overflow or not)
-  const K1ListSrc lsrc{list, s_seg, list_cap, overflow ? D.bpts + bb : nullptr};
-  if (!overflow)  // (uniform)
-    for (unsigned j = threadIdx.x; j < nb; j += kBlock) D.bpts[bb + j] = lsrc(j);
-  int* lut = D.lut;
-  {  // the look-up table: border slots of my slice, and every cell of my bucket starts out empty (k1_small's pass)
-    const long long per_blk = (g.lut_cells + K - 1) / K;
-    const long long lo = static_cast<long long>(k) * per_blk, hi = min(g.lut_cells, lo + per_blk);
-    const int ex = g.div_b[0] + kLutBorder, ey = g.div_b[1] + kLutBorder, ez = g.div_b[2] + kLutBorder;
-    // (a small grid's padded table has fewer than 2^31 slots: 32-bit quotients through the f32 reciprocal, as k1_small)
-    auto divq = [](unsigned a, unsigned b, float rb) {
-      unsigned q = static_cast<unsigned>(__uint2float_rz(a) * rb);
-      int r = static_cast<int>(a - q * b);
-      if (r < 0) { q--; r += static_cast<int>(b); }
-      if (r >= static_cast<int>(b)) q++;
-      return q;
-    };
-    const float rp2 = 1.0f / static_cast<float>(g.pmul[2]), rp1 = 1.0f / static_cast<float>(g.pmul[1]);
-    const float rm2 = 1.0f / static_cast<float>(g.mul[2]), rm1 = 1.0f / static_cast<float>(g.mul[1]);
-    for (long long sl = lo + threadIdx.x; sl < hi; sl += kBlock) {
-      const unsigned u = static_cast<unsigned>(sl);
-      const int pz = static_cast<int>(divq(u, static_cast<unsigned>(g.pmul[2]), rp2));
-      const unsigned rem = u - static_cast<unsigned>(pz) * static_cast<unsigned>(g.pmul[2]);
-      const int py = static_cast<int>(divq(rem, static_cast<unsigned>(g.pmul[1]), rp1)), px = static_cast<int>(rem) - py * g.pmul[1];
-      if (px < kLutBorder || px >= ex || py < kLutBorder || py >= ey || pz < kLutBorder || pz >= ez) lut[sl] = kLutEmpty;
-    }
-    for (int lc = threadIdx.x; lc < C; lc += kBlock) {
-      const long long cell = static_cast<unsigned>(k1_cell(k, lc, deal));
-      if (cell < g.n_cells) {
-        const unsigned c = static_cast<unsigned>(cell);
-        const int cz = static_cast<int>(divq(c, static_cast<unsigned>(g.mul[2]), rm2));
-        const unsigned rem = c - static_cast<unsigned>(cz) * static_cast<unsigned>(g.mul[2]);
-        const int cy = static_cast<int>(divq(rem, static_cast<unsigned>(g.mul[1]), rm1)), cx = static_cast<int>(rem) - cy * g.mul[1];
-        lut[static_cast<long long>(cx + kLutBorder) + static_cast<long long>(cy + kLutBorder) * g.pmul[1] + static_cast<long long>(cz + kLutBorder) * g.pmul[2]] = kLutEmpty;
-      }
-    }
-  }
-  __syncthreads();  // the bucketed points and the empty slots are out before the finish reads / overwrites them
-  if (nb <= static_cast<unsigned>(D.small_finish))  // (uniform)
-    k1_finish_small(lsrc, k, bb, nb, k1_lds, g, deal, D.min_pts, D.eig_ratio, D.sorted_idx, D.recs, D.centroids, lut, D.bucket_base + K + 1);
-  else
-    k1_finalize_bucket(lsrc, k, bb, nb, k1_lds, g, deal, C, D.min_pts, D.lds_cap, D.wmax, D.sorted_idx,
-                       K1RecordFin{D.min_pts, D.eig_ratio, D.recs, D.centroids, lut, &g}, D.bucket_base + K + 1, D.scratch, static_cast<unsigned>(n),
-                       nullptr);
+  if (static_cast<int>(blockIdx.x) >= D.K) return;  // (the whole block, before any barrier: grid.x is the largest K of the launch)
+  k1_small_block<kMultiWaves, true>(&D, blockIdx.x, nullptr);
 }
 
 // ---------------------------------------------------------------------------
@@ -2734,48 +2565,24 @@ bool grid_build_small_applies(int n, const GridBuildPlan& P) {
   static const int small_max = [] { const char* v = getenv("NDT_K1_SMALL_MAX"); return v ? atoi(v) : 49152; }();
   return n > 0 && n <= small_max && P.n_buckets <= 512;
 }
-hipError_t launch_grid_build_small(const float4* pts, int n, int dense, const GridGeom& g, const GridBuildPlan& P, int min_pts,
-                                   double eig_ratio, const GridBuildScratch& S, int* sorted_idx, VoxelRec* recs, VoxelSide* centroids,
-                                   int* lut, unsigned* counts, hipStream_t stream) {
+// The launch parameters of a small-form build of one cloud, k1_small's or (multi) k1_small_multi's; false: the finish's LDS
+// does not fit.  k1_small_multi's kMultiWaves lists hold as many points in all as k1_small's kSmallWaves lists.
+bool small_build_desc(int n, const GridBuildPlan& P, bool multi, SmallBuildDesc& D, size_t* lds_bytes) {
   const int K = P.n_buckets, C = P.cells_per_bucket;
   const int wmax = std::min(C, 1024);
-  // lists: eight waves x list_cap points of 16 bytes (NDT_K1_SMALL_LIST: tests force the overflow path with a tiny capacity)
+  const int waves = multi ? kMultiWaves : kSmallWaves;
+  // lists: list_cap points of 16 bytes per wave (NDT_K1_SMALL_LIST, per k1_small wave: tests force the overflow path with a
+  // tiny capacity)
   static const int list_env = [] { const char* v = getenv("NDT_K1_SMALL_LIST"); return v ? std::max(1, atoi(v)) : 0; }();
-  const int list_cap = list_env > 0 ? list_env : 384;
-  const size_t list_bytes = static_cast<size_t>(kSmallWaves) * list_cap * sizeof(float4);
-  auto fin_lds = [&](int cap) { return ((static_cast<size_t>(3) * C + 3 * static_cast<size_t>(cap)) * sizeof(unsigned) + 5 * static_cast<size_t>(wmax) * 2 + 15) / 16 * 16; };
-  int lds_cap = kK1LdsCap;
-  while (lds_cap > 256 && fin_lds(lds_cap) + list_bytes > kK1MaxDynamicLds) lds_cap -= 256;
-  static const int cap_env = [] { const char* v = getenv("NDT_K1_LDS_CAP"); return v ? std::max(256, atoi(v)) / 256 * 256 : 0; }();
-  if (cap_env > 0) lds_cap = std::min(lds_cap, cap_env);
-  if (fin_lds(lds_cap) + list_bytes > kK1MaxDynamicLds) return hipErrorInvalidValue;
-  // (NDT_K1_SMALL_FINISH=0: every bucket through k1_finalize_bucket -- the cross-check of the two finishes)
-  static const int small_finish = [] { const char* v = getenv("NDT_K1_SMALL_FINISH"); return v ? std::max(0, std::min(kSmallFinish, atoi(v))) : kSmallFinish; }();
-  static bool once = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k1_small), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kK1MaxDynamicLds));
-    return true;
-  }();
-  (void)once;
-  hipLaunchKernelGGL(k1_small, dim3(K), dim3(kSmallThreads), fin_lds(lds_cap) + list_bytes, stream, pts, n, dense, g, P.shift, K, C, min_pts, eig_ratio,
-                     lds_cap, wmax, list_cap, static_cast<unsigned>(fin_lds(lds_cap) / sizeof(unsigned)), small_finish, S.bucket_base, S.bpts, sorted_idx, recs,
-                     centroids, lut, S.bucket_base + K + 1, S.order, counts, S.stamps);
-  return hipGetLastError();
-}
-
-// k1_small's launch parameters for one cloud (launch_grid_build_small's, and each target's of k1_small_multi); false: the
-// finish's LDS does not fit.  lists: kMultiWaves lists holding as many points in all as k1_small's kSmallWaves lists.
-bool small_build_desc(int n, const GridBuildPlan& P, SmallBuildDesc& D, size_t* lds_bytes) {
-  const int K = P.n_buckets, C = P.cells_per_bucket;
-  const int wmax = std::min(C, 1024);
-  static const int list_env = [] { const char* v = getenv("NDT_K1_SMALL_LIST"); return v ? std::max(1, atoi(v)) : 0; }();
-  const int list_cap = (list_env > 0 ? list_env : 384) * kSmallWaves / kMultiWaves;
-  const size_t list_bytes = static_cast<size_t>(kMultiWaves) * list_cap * sizeof(float4);
+  const int list_cap = (list_env > 0 ? list_env : 384) * kSmallWaves / waves;
+  const size_t list_bytes = static_cast<size_t>(waves) * list_cap * sizeof(float4);
   auto fin_lds = [&](int cap) { return ((static_cast<size_t>(3) * C + 3 * static_cast<size_t>(cap)) * sizeof(unsigned) + 5 * static_cast<size_t>(wmax) * 2 + 15) / 16 * 16; };
   int lds_cap = kK1LdsCap;
   while (lds_cap > 256 && fin_lds(lds_cap) + list_bytes > kK1MaxDynamicLds) lds_cap -= 256;
   static const int cap_env = [] { const char* v = getenv("NDT_K1_LDS_CAP"); return v ? std::max(256, atoi(v)) / 256 * 256 : 0; }();
   if (cap_env > 0) lds_cap = std::min(lds_cap, cap_env);
   if (fin_lds(lds_cap) + list_bytes > kK1MaxDynamicLds) return false;
+  // (NDT_K1_SMALL_FINISH=0: every bucket through k1_finalize_bucket -- the cross-check of the two finishes)
   static const int small_finish = [] { const char* v = getenv("NDT_K1_SMALL_FINISH"); return v ? std::max(0, std::min(kSmallFinish, atoi(v))) : kSmallFinish; }();
   D.n = n;
   D.map = P.shift;
@@ -2788,6 +2595,18 @@ bool small_build_desc(int n, const GridBuildPlan& P, SmallBuildDesc& D, size_t* 
   D.small_finish = small_finish;
   *lds_bytes = fin_lds(lds_cap) + list_bytes;
   return true;
+}
+hipError_t launch_grid_build_small(const SmallBuildDesc& D, size_t lds_bytes, unsigned long long* stamps, hipStream_t stream) {
+  if (lds_bytes > kK1MaxDynamicLds || D.K <= 0) return hipErrorInvalidValue;
+  static bool once = [] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k1_small), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kK1MaxDynamicLds));
+    return true;
+  }();
+  (void)once;
+  hipLaunchKernelGGL(k1_small, dim3(D.K), dim3(kSmallThreads), lds_bytes, stream, D.pts, D.n, D.dense, D.g, D.map, D.K, D.C, D.min_pts, D.eig_ratio,
+                     D.lds_cap, D.wmax, D.list_cap, D.fin_words, D.small_finish, D.bucket_base, D.bpts, D.sorted_idx, D.recs, D.centroids, D.lut,
+                     D.scratch, D.counts, stamps);
+  return hipGetLastError();
 }
 hipError_t launch_grid_build_small_multi(const SmallBuildDesc* d_descs, int n_targets, int max_K, size_t lds_bytes, hipStream_t stream) {
   if (n_targets <= 0) return hipSuccess;

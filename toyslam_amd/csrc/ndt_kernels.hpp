@@ -172,14 +172,10 @@ size_t filter_buckets_bitmap_words(long long n_cells);
 hipError_t launch_filter_buckets(const float4* pts, int n, int dense, const GridGeom& g, const GridBuildPlan& plan, const GridBuildScratch& scratch,
                                  int* st_cell, float4* st_cent, unsigned* bitmap_words, unsigned* wprefix, unsigned* counts, float4* out,
                                  hipStream_t stream);
-// the same grid from ONE launch, for small clouds (every block scans the whole cloud and finishes its own bucket); scratch.cntmat unused
+// the same grid from ONE launch, for small clouds (every block scans the whole cloud and finishes its own bucket; no cntmat):
+// k1_small for one cloud, k1_small_multi for many (ndt_align_pairs: one descriptor per cloud, blockIdx.y = cloud).  The two
+// kernels are one block body with 8 and 4 scanning waves, and give a cloud the same records, table, bucketed points and counts.
 bool grid_build_small_applies(int n_points, const GridBuildPlan& plan);
-hipError_t launch_grid_build_small(const float4* pts, int n, int dense, const GridGeom& g, const GridBuildPlan& plan, int min_pts,
-                                   double eig_ratio, const GridBuildScratch& scratch, int* sorted_idx, VoxelRec* recs, VoxelSide* centroids,
-                                   int* lut, unsigned* counts, hipStream_t stream);
-// k1_small over many clouds in one launch (ndt_align_pairs): one descriptor per cloud, blockIdx.y = cloud.  The same records,
-// table, bucketed points and counts as launch_grid_build_small gives that cloud.  small_build_desc fills the launch
-// parameters of a cloud (n, map .. small_finish) and its dynamic LDS; the caller fills the rest.
 struct SmallBuildDesc {
   const float4* pts;
   int n, dense;
@@ -198,7 +194,11 @@ struct SmallBuildDesc {
   unsigned* scratch;      // [5 n]
   unsigned* counts;
 };
-bool small_build_desc(int n_points, const GridBuildPlan& plan, SmallBuildDesc& desc, size_t* lds_bytes);
+// fills the launch parameters of a cloud (n, map .. small_finish) for k1_small, or for k1_small_multi (multi), and its dynamic
+// LDS; the caller fills the rest.  false: the finish's LDS does not fit.
+bool small_build_desc(int n_points, const GridBuildPlan& plan, bool multi, SmallBuildDesc& desc, size_t* lds_bytes);
+hipError_t launch_grid_build_small(const SmallBuildDesc& desc, size_t lds_bytes, unsigned long long* stamps /* NDT_K1_STAMPS, or null */,
+                                   hipStream_t stream);
 hipError_t launch_grid_build_small_multi(const SmallBuildDesc* d_descs, int n_targets, int max_K, size_t lds_bytes, hipStream_t stream);
 hipError_t launch_grid_build_buckets(const float4* pts, int n, int dense, const GridGeom& g, const GridBuildPlan& plan, int min_pts,
                                      double eig_ratio, const GridBuildScratch& scratch, int* sorted_idx, VoxelRec* recs, VoxelSide* centroids,
