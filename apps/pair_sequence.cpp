@@ -8,8 +8,10 @@
 // call right after the pairs call ("fitness k-1 to k: <value>", 17 significant digits), and that call's time.
 // --batch-filter: every scan is read first, then all of them are prefiltered in ONE ndt_cloud_voxel_filter_batch call; the
 // output is the plain run's, timing lines aside.
+// --map <out.pcd>: after the pose chain, all filtered scans at their chained poses (scan 0 at the identity) go into the map
+// in ONE ndt_map_update_clouds call at the node's 0.5 m; "map: <n> points", and the map written as a binary PCD.
 //
-//   pair_sequence <pcd_directory> [--fitness] [--batch-filter]
+//   pair_sequence <pcd_directory> [--fitness] [--batch-filter] [--map <out.pcd>]
 #include <cfloat>
 #include <chrono>
 #include <cstdio>
@@ -37,13 +39,21 @@ static double since(clock_type::time_point a) { return std::chrono::duration<dou
 
 int main(int argc, char** argv) {
   if (argc < 2) {
-    std::printf("usage: pair_sequence <pcd_directory> [--fitness] [--batch-filter]\n");
+    std::printf("usage: pair_sequence <pcd_directory> [--fitness] [--batch-filter] [--map <out.pcd>]\n");
     return 0;
   }
   bool want_fitness = false, batch_filter = false;
+  const char* map_path = nullptr;
   for (int a = 2; a < argc; a++) {
     if (std::strcmp(argv[a], "--fitness") == 0) want_fitness = true;
     if (std::strcmp(argv[a], "--batch-filter") == 0) batch_filter = true;
+    if (std::strcmp(argv[a], "--map") == 0) {
+      if (a + 1 >= argc) {
+        std::fprintf(stderr, "--map needs a file name\nusage: pair_sequence <pcd_directory> [--fitness] [--batch-filter] [--map <out.pcd>]\n");
+        return 2;
+      }
+      map_path = argv[++a];
+    }
   }
   const float kLeaf = 0.5f;
   ndt_handle h = nullptr;
@@ -143,6 +153,7 @@ int main(int argc, char** argv) {
   // ---- pose chain
   static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   std::vector<float> sum(kIdentity, kIdentity + 16);
+  std::vector<float> poses(kIdentity, kIdentity + 16);  // scan k's pose in the frame of scan 0 (--map)
   size_t not_converged = 0;
   for (size_t k = 0; k < n_pairs; k++) {
     float* Tk = T.data() + 16 * k;
@@ -155,6 +166,7 @@ int main(int argc, char** argv) {
     std::snprintf(title, sizeof(title), "Transform %zu to %zu: (%d iterations%s)", k, k + 1, iters[k], conv[k] ? "" : ", not converged");
     print_matrix(title, Tk);
     print_matrix("TransformSum:", sum.data());
+    poses.insert(poses.end(), sum.begin(), sum.end());
   }
   if (want_fitness)
     for (size_t k = 0; k < n_pairs; k++) std::printf("fitness %zu to %zu: %.17g\n", k, k + 1, fitness[k]);
@@ -162,6 +174,20 @@ int main(int argc, char** argv) {
   std::printf("time: read + prefilter %.2f ms, pairs call %.2f ms (%.1f pairs/s)\n", load_ms, align_ms,
               align_ms > 0 ? 1e3 * static_cast<double>(n_pairs) / align_ms : 0.0);
   if (want_fitness) std::printf("time: fitness call %.3f ms\n", fitness_ms);
+  if (map_path) {  // ---- every scan at its pose into the map: one call
+    const auto t_map = clock_type::now();
+    std::vector<int> dense(clouds.size(), 1);
+    int overflowed = 0;
+    size_t n_map = 0;
+    CHECK(ndt_map_update_clouds(h, clouds.data(), clouds.size(), dense.data(), poses.data(), kLeaf, &overflowed));
+    CHECK(ndt_map_size(h, &n_map));
+    const double map_ms = since(t_map);
+    std::vector<float> map(4 * (n_map ? n_map : 1));
+    CHECK(ndt_map_get(h, map.data(), 16));
+    CHECK(ndt_pcd_write_xyz(map_path, map.data(), n_map, 16, 1));
+    std::printf("map: %zu points\n", n_map);
+    std::printf("time: map call %.3f ms%s\n", map_ms, overflowed ? " (leaf size too small: unfiltered)" : "");
+  }
   for (ndt_cloud c : clouds) ndt_cloud_release(c);
   ndt_destroy(h);
   return 0;

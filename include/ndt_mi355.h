@@ -248,6 +248,40 @@ void ndt_cloud_release(ndt_cloud c);
 ndt_status ndt_set_input_source_cloud(ndt_handle h, ndt_cloud c);
 ndt_status ndt_set_input_target_cloud(ndt_handle h, ndt_cloud c, int is_dense);
 ndt_status ndt_map_update_cloud(ndt_handle h, ndt_cloud scan, int is_dense, const float* pose, float leaf_size, int* overflowed);
+/* N2 of many scans in one call.  PCL: for k in order { transformPointCloud(scan k, poses[16k..]); map += it; } then ONE
+ * VoxelGrid::filter(leaf) of the concatenation [map | scan 0 | scan 1 | ...] -- one transform launch for all scans and one
+ * filter, where a loop of ndt_map_update_cloud re-filters the growing map once per scan.
+ * NOT the loop's map: a voxel of this map is the centroid of ALL points that fell into it (the map's and every scan's); the
+ * loop keeps centroids of centroids.  Both occupy the same voxels, the coordinates differ (by up to a good part of the leaf
+ * size).  The mapping nodes' map, bit for bit, is what the per-scan calls give.
+ * - The map after the call is, bit for bit, pcl::VoxelGrid::filter of that concatenation, scan k moved as transformPointCloud
+ *   moves it (a non-finite point of a scan with is_dense[k] == 0 is left as it is by the transform and dropped by the filter).
+ *   The concatenation is dense only if the map was and every scan is.  is_dense: one flag per scan, NULL = 0 for all;
+ *   poses: 16 column-major floats per scan, NULL = the identity for all.
+ * - n_scans == 1 is ndt_map_update_cloud / ndt_map_update / ndt_map_update_device of that scan: same map, same *overflowed,
+ *   same bits.  Overflow ("leaf size too small"): the unfiltered concatenation is kept and *overflowed = 1.
+ * - n_scans == 0 is NDT_OK, touches nothing and needs no device.  Scans of zero points are allowed; if all are empty the map
+ *   is filtered again, as the single call does with an empty scan.
+ * - Completion as ndt_map_update_cloud: queued on the map's stream; size and boxes are settled by the next call that needs
+ *   them (ndt_map_size, ndt_map_get*, the next update).  The handle keeps a reference to every scan until then: releasing
+ *   the caller's references right after the call is safe.  The buffer form copies: its buffer is free on return.
+ * - The handle's target, source, grid, last result, a begun ndt_cloud_voxel_filter_begin and the pairs state stay as they
+ *   were; ndt_map_update* continues on the same map afterwards.
+ * - NDT_ERR_INVALID before any device work, map untouched: NULL handle, !(leaf_size > 0), NULL scans / offsets with
+ *   n_scans > 0, a NULL entry of scans, decreasing offsets, a stride below 12 or not a multiple of 4, NULL pts with points,
+ *   more than 65 535 scans, a total (map + scans) above INT_MAX points (with an update still queued, the map's size is
+ *   known only once that update has been waited for: the refusal then comes behind that wait, and still before anything of
+ *   this call is copied or queued).  After any later error the map is what it was. */
+ndt_status ndt_map_update_clouds(ndt_handle h, const ndt_cloud* scans, size_t n_scans, const int* is_dense /* n_scans or NULL = 0 */,
+                                 const float* poses /* n_scans*16 column-major, NULL = identity for all */, float leaf_size,
+                                 int* overflowed);
+/* buffer form: scan k is points [offsets[k], offsets[k+1]) of pts (host memory, or device memory when on_device != 0) */
+ndt_status ndt_map_update_batch(ndt_handle h, const void* pts, const size_t* offsets /* n_scans+1 */, size_t n_scans,
+                                size_t stride_bytes, const int* is_dense, const float* poses, float leaf_size, int on_device,
+                                int* overflowed);
+/* diagnostics of the handle's last ndt_map_update_clouds / _batch call: transform launches (1 whatever the number of scans),
+ * filters of the concatenation (1), exact bounding-box passes (0, or 1 when the scans' boxes under their poses did not do) */
+ndt_status ndt_diag_map_batch(ndt_handle h, size_t* transform_launches, size_t* filters, size_t* box_passes);
 ndt_status ndt_promote_source_to_target(ndt_handle h, int is_dense);
 
 /* ---- PCD files (row N3 of the scope table) -----------------------------------

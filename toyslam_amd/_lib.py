@@ -94,6 +94,9 @@ SIGNATURES = {
     "ndt_set_input_source_cloud": (C.c_int, [vp, vp]),
     "ndt_set_input_target_cloud": (C.c_int, [vp, vp, C.c_int]),
     "ndt_map_update_cloud": (C.c_int, [vp, vp, C.c_int, fp, C.c_float, ip]),
+    "ndt_map_update_clouds": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, ip, fp, C.c_float, ip]),
+    "ndt_map_update_batch": (C.c_int, [vp, vp, szp, C.c_size_t, C.c_size_t, ip, fp, C.c_float, C.c_int, ip]),
+    "ndt_diag_map_batch": (C.c_int, [vp, szp, szp, szp]),
     "ndt_promote_source_to_target": (C.c_int, [vp, C.c_int]),
     "ndt_host_chain_pose": (None, [fp, fp, fp]),
     "ndt_pcd_read_header": (C.c_int, [C.c_char_p, szp, ip, ip]),

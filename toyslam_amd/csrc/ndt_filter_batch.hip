@@ -31,17 +31,6 @@ struct BatchIn {
   BBox bb{};                // the box of its NaN rule
 };
 
-// page-locked scratch of the handle, grown on demand (only while nothing queued reads it)
-ndt_status pinned_at_least(void*& p, size_t& have, size_t bytes) {
-  if (have >= bytes) return NDT_OK;
-  if (p) (void)hipHostFree(p);
-  p = nullptr;
-  have = 0;
-  HIP_TRY(hipHostMalloc(&p, bytes + bytes / 4, hipHostMallocDefault));
-  have = bytes + bytes / 4;
-  return NDT_OK;
-}
-
 void decode_boxes(const unsigned* w, DeviceCloud* c) {
   for (int v = 0; v < 2; v++)
     for (int k = 0; k < 3; k++) {
@@ -95,7 +84,7 @@ ndt_status composite_pass(ndt_handle h, const float4* block, const std::vector<B
   DevBuf<unsigned char> d_desc;
   HIP_TRY(d_desc.reserve(desc_bytes + seg_bytes));
   HIP_TRY(work.reserve(n_words));
-  ndt_status s = pinned_at_least(h->fb_pinned, h->fb_pinned_bytes, std::max(desc_bytes + seg_bytes, back_bytes));
+  ndt_status s = pinned_at_least(h->fb_pinned, h->fb_pinned_bytes, std::max(desc_bytes + seg_bytes, back_bytes), st);
   if (s) return s;
   std::memcpy(h->fb_pinned, cl.data(), desc_bytes);
   // the result's boxes: segment j = the leaves [lo, hi) of the block that k_leaf_ranges finds (a device-side range)
@@ -170,7 +159,7 @@ ndt_status filter_batch_run(ndt_handle h, const float4* block, const std::vector
   std::vector<FilterPending> pend(single.size());
   if (!single.empty()) {
     const size_t per = kOutBoxBlocks * 12 + 4;
-    ndt_status s = pinned_at_least(h->fb_rows, h->fb_rows_bytes, single.size() * per * sizeof(float));
+    ndt_status s = pinned_at_least(h->fb_rows, h->fb_rows_bytes, single.size() * per * sizeof(float), h->stream);
     if (s) return s;
     for (size_t i = 0; i < single.size(); i++) {
       const size_t k = single[i];
@@ -250,7 +239,7 @@ ndt_status filter_batch_buffer(ndt_handle h, const void* pts, const size_t* offs
       block = staged.p;
     }
     const size_t seg_bytes = N * sizeof(ndt::SegDesc), box_bytes = 12 * N * sizeof(unsigned);
-    ndt_status s = pinned_at_least(h->fb_pinned, h->fb_pinned_bytes, seg_bytes + box_bytes);
+    ndt_status s = pinned_at_least(h->fb_pinned, h->fb_pinned_bytes, seg_bytes + box_bytes, st);
     if (s) return s;
     ndt::SegDesc* segs = static_cast<ndt::SegDesc*>(h->fb_pinned);
     for (size_t k = 0; k < N; k++) {
@@ -301,7 +290,7 @@ ndt_status filter_batch_clouds(ndt_handle h, const ndt_cloud* cl, size_t N, cons
   if (total) {
     HIP_TRY(staged.reserve(total));
     const size_t seg_bytes = N * sizeof(ndt::SegDesc);
-    ndt_status s = pinned_at_least(h->fb_pinned, h->fb_pinned_bytes, seg_bytes);
+    ndt_status s = pinned_at_least(h->fb_pinned, h->fb_pinned_bytes, seg_bytes, st);
     if (s) return s;
     ndt::SegDesc* segs = static_cast<ndt::SegDesc*>(h->fb_pinned);
     for (size_t k = 0; k < N; k++) {

@@ -6,7 +6,7 @@
 void ndt_context::release_buffers() {
   target.reset();
   source.reset();
-  map_scan.reset();
+  map_scans.clear();
   grid.reset();
   pairs_grids.clear();
   pair_views.release();
@@ -27,6 +27,22 @@ namespace ndtc {
 
 thread_local std::string g_last_error;
 thread_local hipStream_t tls_pool_stream = nullptr;
+
+// Page-locked scratch of a handle, grown on demand.  The block may only be rewritten while nothing queued still reads it --
+// the caller's business: it writes behind a wait of its own -- and growing frees the old block, so the stream whose queued
+// copies may still read it (`reader`) is waited for first.
+ndt_status pinned_at_least(void*& p, size_t& have, size_t bytes, hipStream_t reader) {
+  if (have >= bytes) return NDT_OK;
+  if (p) {
+    if (reader) HIP_TRY(hipStreamSynchronize(reader));
+    (void)hipHostFree(p);
+  }
+  p = nullptr;
+  have = 0;
+  HIP_TRY(hipHostMalloc(&p, bytes + bytes / 4, hipHostMallocDefault));
+  have = bytes + bytes / 4;
+  return NDT_OK;
+}
 
 int usable_devices() {
   int n = 0;

@@ -377,7 +377,7 @@ struct ndt_context {
   hipEvent_t map_ready = nullptr;       // recorded on the handle's stream: the scan the update reads is complete
   bool map_pending = false;
   FilterPending map_filter;
-  std::shared_ptr<DeviceCloud> map_scan;  // the scan a queued update reads (kept until the update has been waited for)
+  std::vector<std::shared_ptr<DeviceCloud>> map_scans;  // the scans a queued update reads (kept until the update has been waited for)
   float* filter_slots = nullptr;        // page-locked: [3] x (64 x 12 rows + count words): slot 0 N1, slot 1 the map, slot 2 a begun N1
   // ndt_cloud_voxel_filter_begin / _end: one prefilter queued on a stream of its own (beside a registration on the handle's)
   hipStream_t filter_stream = nullptr;
@@ -442,6 +442,11 @@ struct ndt_context {
   void* fb_rows = nullptr;
   size_t fb_rows_bytes = 0;
   size_t fb_passes = 0, fb_single = 0, fb_launches = 0;
+  // ndt_map_update_clouds / _batch (ndt_map_batch.hip): the page-locked scan descriptors of the one transform launch, and what
+  // the last call did (ndt_diag_map_batch)
+  void* mb_pinned = nullptr;
+  size_t mb_pinned_bytes = 0;
+  size_t mb_transform_launches = 0, mb_filters = 0, mb_box_passes = 0;
 
   ~ndt_context() {
     for (ndt_context* w : batch_workers) delete w;
@@ -473,6 +478,7 @@ struct ndt_context {
     if (filter_slots) (void)hipHostFree(filter_slots);
     if (fb_pinned) (void)hipHostFree(fb_pinned);
     if (fb_rows) (void)hipHostFree(fb_rows);
+    if (mb_pinned) (void)hipHostFree(mb_pinned);
     release_buffers();
     if (host_result) (void)hipHostFree(host_result);
     if (host_pub) (void)hipHostFree(host_pub);
@@ -512,6 +518,9 @@ int side_cus();
 ndt_status ensure_device(ndt_context* h);
 ndt_status ensure_host_rows(ndt_context* h, size_t rows);
 ndt::SolverParams solver_params(const ndt_context* h);
+// page-locked scratch of a handle, grown on demand; `reader`: the stream whose queued copies may still read the old block
+// (waited for before it is freed).  Rewriting the block is the caller's to order: only behind a wait for what reads it
+ndt_status pinned_at_least(void*& p, size_t& have, size_t bytes, hipStream_t reader);
 // ---- ndt_grid.hip
 ndt_status upload_cloud(ndt_context* h, const void* pts, size_t n, size_t stride, bool on_device,
                         std::shared_ptr<DeviceCloud>& out, bool by_reference = false);
@@ -565,6 +574,19 @@ FilterRoute filter_route(const ndt_context* h, size_t n, const BBox& bb, float l
 ndt_status voxel_filter_enqueue(ndt_handle h, hipStream_t st, const float4* d_in, size_t n, int is_dense, float leaf, float4* d_out,
                                 const BBox& bb, FilterPending& P);
 void voxel_filter_finish(const FilterPending& P, size_t* n_out, DeviceCloud* boxes);
+// N2 of a list of resident scans in one pass (the single ndt_map_update* are the list of one): scan k moved by its pose
+// (16 column-major floats, null = identity) behind the map, in the list's order, then one filter of the concatenation
+struct MapScan {
+  std::shared_ptr<DeviceCloud> c;
+  int dense = 1;
+  const float* pose = nullptr;
+};
+struct MapBatchDiag {
+  size_t transform_launches = 0, filters = 0, box_passes = 0;
+};
+ndt_status map_update_scans(ndt_handle h, const std::vector<MapScan>& scans, float leaf, int* overflowed, MapBatchDiag* diag);
+// the map's stream exists and a queued update has been waited for: map_n, the boxes and h->mb_pinned are the handle's again
+ndt_status map_settle(ndt_handle h);
 ndt_status cloud_use_on(ndt_handle h, DeviceCloud* c);  // an ndt_cloud made on another stream: wait for it, remember the reader
 // out_boxes: the result's bounding boxes as DeviceCloud keeps them ([2][3] min, [2][3] max), or null
 ndt_status voxel_filter_device(ndt_handle h, const float4* d_in, size_t n, int is_dense, float leaf, float4* d_out,

@@ -453,6 +453,37 @@ __global__ __launch_bounds__(kBlock) void k_fitness_multi(const FitnessMember* _
   fitness_body(from_global(&M.src), M.n, M.T, ix, max_range, b - first, nblk, partials + static_cast<size_t>(b) * kEvalStride, lds);
 }
 
+// transformPointCloud of many scans in one launch (N2 of many scans, ndt_map_update_clouds): scan s owns blocks
+// [starts[s], starts[s + 1]) and writes its records to dst + first.  A block finds its scan as k_fitness_multi's blocks find
+// their member (block-uniform binary search: scalar loads) and reads the scan's records through a global-address-space
+// pointer; per point it is k_transform's body, so every record is the one launch_transform writes.
+__global__ __launch_bounds__(kBlock) void k_transform_multi(const TransformScan* __restrict__ scans, const int* __restrict__ starts,
+                                                            int n_scans, float4* __restrict__ dst) {
+  const int b = blockIdx.x;
+  int lo = 0, hi = n_scans - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (starts[mid] <= b) lo = mid;
+    else hi = mid - 1;
+  }
+  const int first = starts[lo];
+  const unsigned step = static_cast<unsigned>(starts[lo + 1] - first) * kBlock;
+  const TransformScan& S = scans[lo];
+  const float4* __restrict__ src = from_global(&S.src);
+  float4* __restrict__ out = dst + S.first;
+  const unsigned n = static_cast<unsigned>(S.n);
+  const int dense = S.dense;
+  float T[12];
+#pragma unroll
+  for (int k = 0; k < 12; k++) T[k] = S.T[k];
+  for (unsigned i = static_cast<unsigned>(b - first) * kBlock + threadIdx.x; i < n; i += step) {  // (n <= INT_MAX, step <= 2^19)
+    const float4 pt = src[i];
+    float tx = pt.x, ty = pt.y, tz = pt.z;
+    if (dense || finite3(pt.x, pt.y, pt.z)) xform_point(T, pt.x, pt.y, pt.z, tx, ty, tz);
+    out[i] = make_float4(tx, ty, tz, 1.0f);
+  }
+}
+
 // calculateScore (ndt_omp_impl.hpp:935-983): cloud used as given, f64 throughout
 template <int NNB>
 __global__ __launch_bounds__(kBlock) void k_calc_score(const float4* __restrict__ cloud, int n, GridView gv, double d1,
@@ -607,6 +638,15 @@ hipError_t launch_transform(const float4* src, int n, const float* T12, float4* 
   EvalParams P = {};
   for (int i = 0; i < 12; i++) P.T[i] = T12[i];
   hipLaunchKernelGGL(k_transform, dim3(grid_for(n, 2048)), dim3(kBlock), 0, stream, src, n, P, dst, dense);
+  return hipGetLastError();
+}
+
+int transform_multi_blocks(size_t n) { return n ? grid_for(n, 2048) : 0; }
+
+hipError_t launch_transform_multi(const TransformScan* d_scans, const int* d_starts, int n_scans, int n_blocks, float4* dst,
+                                  hipStream_t stream) {
+  if (n_scans <= 0 || n_blocks <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_transform_multi, dim3(n_blocks), dim3(kBlock), 0, stream, d_scans, d_starts, n_scans, dst);
   return hipGetLastError();
 }
 

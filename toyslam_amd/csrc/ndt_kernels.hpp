@@ -367,6 +367,20 @@ hipError_t launch_fitness_multi(const FitnessMember* members, const int* starts,
 hipError_t launch_gather_points(const float4* pts, const int* sorted_idx, const unsigned* d_n_sorted, int n_max, float4* out,
                                 hipStream_t stream);
 hipError_t launch_transform(const float4* src, int n, const float* T12, float4* dst, hipStream_t stream, int dense = 1);
+// transformPointCloud of many scans in one launch (k_transform_multi): scan s (of n_scans, every one with n > 0) is moved by
+// its T and written to dst + first .. + n; it takes blocks [starts[s], starts[s + 1]) of the n_blocks = starts[n_scans],
+// transform_multi_blocks(n) of them.  dense = 0: non-finite points are left as they are (launch_transform's rule).
+struct TransformScan {
+  const float4* src = nullptr;
+  int n = 0;
+  int first = 0;  // where its records go, in records from dst
+  int dense = 1;
+  int pad = 0;
+  float T[12];    // row-major 3x4 f32
+};
+int transform_multi_blocks(size_t n);
+hipError_t launch_transform_multi(const TransformScan* d_scans, const int* d_starts, int n_scans, int n_blocks, float4* dst,
+                                  hipStream_t stream);
 hipError_t launch_calc_score(const float4* cloud, int n, const GridView& gv, double d1, double d2, double d3,
                              int search, float r2, int n_blocks, double* partials, hipStream_t stream);
 

@@ -375,6 +375,70 @@ class NormalDistributionsTransform:
         check(self._L.ndt_map_update_cloud(self._h, dc._c, int(is_dense), _f(T) if T is not None else None, float(leaf_size), C.byref(ov)))
         return self.mapSize(), bool(ov.value)
 
+    # ---- many posed scans into the map in one call (ndt_map_update_clouds / _batch) -----------
+    @staticmethod
+    def _poses(poses, n):
+        """(n, 16) float32 column-major poses of a batched map update, or None (the identity for every scan)."""
+        if poses is None:
+            return None
+        poses = list(poses)
+        if len(poses) != n:
+            raise ValueError("one pose per scan")
+        if n == 0:
+            return None
+        return np.ascontiguousarray(np.stack([_colmajor(T) for T in poses]))
+
+    def mapUpdateClouds(self, clouds, poses=None, leaf_size=0.5, is_dense=True):
+        """N2 of many scans in one call: every DeviceCloud moved by its pose, all appended to the map in the list's order, ONE
+        voxel filter of the concatenation (not the per-scan loop's map: see ndt_map_update_clouds).  poses: one 4x4 per scan,
+        None = the identity for all; is_dense: one bool, or one per scan.  Returns (map size, overflowed)."""
+        clouds = list(clouds)
+        if not all(isinstance(c, DeviceCloud) for c in clouds):
+            raise ValueError("clouds must be DeviceCloud objects (host arrays: mapUpdateBatch)")
+        n = len(clouds)
+        P = self._poses(poses, n)
+        dense = _dense_flags(is_dense, n)
+        arr = (C.c_void_p * max(n, 1))(*[c._c for c in clouds])
+        ov = C.c_int(0)
+        check(self._L.ndt_map_update_clouds(self._h, arr, n, _i(dense), _f(P) if P is not None else None, float(leaf_size), C.byref(ov)))
+        return self.mapSize(), bool(ov.value)
+
+    def mapUpdateBatch(self, scans, poses=None, leaf_size=0.5, is_dense=True):
+        """The same from a list of (N_k, >=3) host arrays, concatenated once and sent up with one copy (ndt_map_update_batch)."""
+        scans = [np.asarray(c) for c in scans]
+        n = len(scans)
+        cols = {c.shape[1] if c.ndim == 2 else -1 for c in scans}
+        if len(cols) > 1:
+            raise ValueError("all scans must have the same column count")
+        P = self._poses(poses, n)
+        dense = _dense_flags(is_dense, n)
+        cat = _cloud(np.concatenate(scans, axis=0)) if scans else np.zeros((0, 4), np.float32)
+        offsets = np.zeros(n + 1, dtype=np.uintp)
+        offsets[1:] = np.cumsum([len(c) for c in scans])
+        ov = C.c_int(0)
+        check(self._L.ndt_map_update_batch(self._h, cat.ctypes.data, offsets.ctypes.data_as(C.POINTER(C.c_size_t)), n, cat.shape[1] * 4,
+                                           _i(dense), _f(P) if P is not None else None, float(leaf_size), 0, C.byref(ov)))
+        return self.mapSize(), bool(ov.value)
+
+    def mapUpdateBatchDevice(self, dev_ptr, offsets, stride_bytes, poses=None, leaf_size=0.5, is_dense=True):
+        """The buffer form over records already in HBM: scan k = records [offsets[k], offsets[k+1]) at dev_ptr."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uintp)
+        n = len(offsets) - 1
+        if n < 0:
+            raise ValueError("offsets must hold n_scans + 1 entries")
+        P = self._poses(poses, n)
+        dense = _dense_flags(is_dense, n)
+        ov = C.c_int(0)
+        check(self._L.ndt_map_update_batch(self._h, C.c_void_p(dev_ptr), offsets.ctypes.data_as(C.POINTER(C.c_size_t)), n, int(stride_bytes),
+                                           _i(dense), _f(P) if P is not None else None, float(leaf_size), 1, C.byref(ov)))
+        return self.mapSize(), bool(ov.value)
+
+    def mapBatchDiag(self):
+        """What the last mapUpdateClouds / mapUpdateBatch / mapUpdateBatchDevice did (ndt_diag_map_batch)."""
+        t, f, b = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        check(self._L.ndt_diag_map_batch(self._h, C.byref(t), C.byref(f), C.byref(b)))
+        return dict(transform_launches=t.value, filters=f.value, box_passes=b.value)
+
     # ---- batch (map-build) ---------------------------------------------------------
     def alignBatch(self, clouds=None, guesses=None, device_ptr=None, offsets=None, stride_bytes=16):
         """Register many sources against the one target in lock-step.
