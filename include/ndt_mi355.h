@@ -506,6 +506,15 @@ ndt_status ndt_selftest_server_idle(ndt_handle h, const double* p, int stall_ms,
  * *n_waves in: capacity, out: waves written. */
 ndt_status ndt_diag_stamps(ndt_handle h, const double* p, unsigned long long* stamps, size_t* n_waves);
 
+/* Diagnostic: how this handle (its CU count and partition, ndt_get_cu_partition) cuts an evaluation of n source points, form by
+ * form: *ppb points per 512-thread block of the one-launch kernel and of the evaluation server, *fused_blocks the one-launch
+ * kernel's grid, *launch_blocks the grid of the separate derivative / f64-Hessian kernels (256 points per block and pass),
+ * *server_blocks the evaluation server's grid, *batch_blocks the blocks of an n-point member of a lock-step batch or of a
+ * pair.  A grid that covers fewer than n points in one pass is walked grid-strided.  The values come from the functions the
+ * launchers call; no device work beyond opening the device.  For tests that place a scan on a boundary of a plan. */
+ndt_status ndt_diag_eval_plan(ndt_handle h, size_t n, int* ppb, int* fused_blocks, int* launch_blocks, int* server_blocks,
+                              int* batch_blocks);
+
 /* Diagnostic: round-trip latency of the persistent evaluation server, averaged over n_iter commands:
  * us[0] = no-op round (protocol only), us[1] = derivatives without Hessian, us[2] = with Hessian. */
 ndt_status ndt_diag_server_roundtrip(ndt_handle h, const double* p, int n_iter, double* us);

@@ -256,7 +256,7 @@ ndt_status server_start(ndt_context* h) {
   unsigned* const counter_next = h->server_counter.p + (h->server_counter_set ^ 1) * ndt::kServerCounterWords;
   // one 512-thread block per CU at most: every block must be resident for the round to complete
   const int ppb = ndt::points_per_block(n, h->cu_count);
-  int nblk = std::max(1, std::min(h->cu_count > 0 ? h->cu_count : 64, (n + ppb - 1) / ppb));
+  const int nblk = ndt::server_blocks(n, h->cu_count);
   h->server_blocks = nblk;
   HIP_TRY(h->partials.reserve(static_cast<size_t>(nblk) * ndt::kEvalStride));
   HIP_TRY(ensure_host_rows(h, 1) == NDT_OK ? hipSuccess : hipErrorOutOfMemory);
@@ -589,7 +589,7 @@ ndt_status ndt_diag_selfdrive(ndt_handle h, const double* p, int rounds, double*
   std::lock_guard<std::mutex> turn(server_device_mutex(h->device));
   const int n = h->source->k2_n();
   const int ppb = ndt::points_per_block(n, h->cu_count);
-  const int nblk = std::max(1, std::min(h->cu_count > 0 ? h->cu_count : 64, (n + ppb - 1) / ppb));
+  const int nblk = ndt::server_blocks(n, h->cu_count);
   const size_t mb_bytes = ndt::server_mailbox_bytes();
   DevBuf<unsigned char> mb;
   DevBuf<double> parts;
@@ -639,6 +639,23 @@ ndt_status ndt_diag_selfdrive(ndt_handle h, const double* p, int rounds, double*
   return NDT_OK;
 }
 
+// Diagnostic: how an evaluation of n source points would be cut on this handle (its CU count and partition), form by form --
+// the functions the launchers themselves call, no device work
+ndt_status ndt_diag_eval_plan(ndt_handle h, size_t n, int* ppb, int* fused_blocks, int* launch_blocks, int* server_blocks,
+                              int* batch_blocks) {
+  if (!h || !ppb || !fused_blocks || !launch_blocks || !server_blocks || !batch_blocks) return fail(NDT_ERR_INVALID, "bad arguments");
+  if (n > static_cast<size_t>(0x7fffffff)) return fail(NDT_ERR_INVALID, "more points than a scan may have");
+  ndt_status s = ensure_device(h);  // the handle's CU count is the device's (or its partition's)
+  if (s) return s;
+  const int ni = static_cast<int>(n);
+  *ppb = ndt::points_per_block(ni, h->cu_count);
+  *fused_blocks = ndt::fused_blocks(ni, h->cu_count, h->cu_partition != 0);
+  *launch_blocks = ndt::derivative_blocks(ni, h->search);
+  *server_blocks = ndt::server_blocks(ni, h->cu_count);
+  *batch_blocks = ndt::batch_blocks(ni);
+  return NDT_OK;
+}
+
 ndt_status ndt_diag_server_roundtrip(ndt_handle h, const double* p, int n_iter, double* us) {
   if (!h || !p || !us || n_iter <= 0) return fail(NDT_ERR_INVALID, "bad arguments");
   ndt_status s = check_ready(h);
@@ -680,8 +697,7 @@ ndt_status ndt_diag_server_roundtrip(ndt_handle h, const double* p, int n_iter, 
   {  // device-side stamps of the LAST round (with Hessian), s_memrealtime ticks of 10 ns
     std::vector<unsigned long long> d(8 + 10 * 1024);
     HIP_TRY(hipMemcpy(d.data(), h->server_dbg.p, d.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    const int ppb_diag = ndt::points_per_block(h->source->k2_n(), h->cu_count);
-    const int nblk = std::max(1, std::min(h->cu_count > 0 ? h->cu_count : 64, (h->source->k2_n() + ppb_diag - 1) / ppb_diag));
+    const int nblk = ndt::server_blocks(h->source->k2_n(), h->cu_count);
     unsigned long long got_min = ~0ull, got_max = 0, tk_min = ~0ull, tk_max = 0;
     for (int b = 0; b < nblk; b++) {
       got_min = std::min(got_min, d[8 + 2 * b]); got_max = std::max(got_max, d[8 + 2 * b]);

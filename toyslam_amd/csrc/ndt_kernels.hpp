@@ -314,6 +314,9 @@ hipError_t launch_derivatives(const float4* src, int n, const GridView& gv, cons
 // on a CU partition)
 int points_per_block(int n, int cus);
 int fused_blocks(int n, int cus, bool partition);
+// blocks of the persistent evaluation server: one 512-thread block per CU at most (every block must be resident for a round
+// to complete); above cus * points_per_block points a thread walks several points
+int server_blocks(int n, int cus);
 hipError_t launch_derivatives_fused(const float4* src, int n, const GridView& gv, const EvalParams& P, int search,
                                     bool want_hessian, int n_blocks, int ppb, double* partials, unsigned* counter, double* out_row,
                                     unsigned long long seq, hipStream_t stream);

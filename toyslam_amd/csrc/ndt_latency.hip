@@ -632,6 +632,10 @@ int fused_blocks(int n, int cus, bool partition) {
   if (partition && cus > 0 && b > static_cast<size_t>(2 * cus)) b = 2 * cus;  // a handle on a CU partition: still all blocks resident at once
   return static_cast<int>(b);
 }
+int server_blocks(int n, int cus) {
+  const int ppb = points_per_block(n, cus);
+  return std::max(1, std::min(cus > 0 ? cus : 64, (n + ppb - 1) / ppb));
+}
 
 hipError_t launch_derivatives_fused(const float4* src, int n, const GridView& gv, const EvalParams& P, int search,
                                     bool want_hessian, int n_blocks, int ppb, double* partials, unsigned* counter, double* out_row,

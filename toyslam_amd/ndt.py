@@ -95,6 +95,9 @@ def pairs_array(n_clouds, pairs=None):
     return np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
 
 
+EVAL_PLAN_FIELDS = ("ppb", "fused_blocks", "launch_blocks", "server_blocks", "batch_blocks")
+
+
 class NormalDistributionsTransform:
     """Drop-in shaped like pclomp::NormalDistributionsTransform<PointT, PointT>."""
 
@@ -660,6 +663,13 @@ class NormalDistributionsTransform:
         n = C.c_size_t(max_waves)
         check(self._L.ndt_diag_stamps(self._h, _d(p), st.ctypes.data_as(C.POINTER(C.c_ulonglong)), C.byref(n)))
         return st[:n.value]
+
+    def evalPlan(self, n):
+        """How this handle cuts an evaluation of n source points (ndt_diag_eval_plan): dict of ppb, fused_blocks,
+        launch_blocks, server_blocks, batch_blocks."""
+        v = [C.c_int(0) for _ in range(5)]
+        check(self._L.ndt_diag_eval_plan(self._h, int(n), *[C.byref(x) for x in v]))
+        return dict(zip(EVAL_PLAN_FIELDS, (x.value for x in v)))
 
     def diag_server_roundtrip(self, p, n_iter=200):
         p = np.ascontiguousarray(p, dtype=np.float64)
