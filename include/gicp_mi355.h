@@ -69,6 +69,10 @@ ndt_status gicp_step_correspond(gicp_handle h, const float* guess, const float* 
 /* OptimizationFunctorWithIndices (:241-368) at x over the correspondences of the last step:
  * mode 0 operator() -> *f; 1 df -> g[6]; 2 fdf -> *f, g[6]. */
 ndt_status gicp_step_functor(gicp_handle h, int mode, const double* x, double* f, double* g);
+/* How the launchers cut n points into blocks: out = grids of the kNN / covariance pass (n = points of the cloud), the
+ * correspondence step, the functor kernel and the objective server (n = source points) -- the very values the launches
+ * use, NDT_GICP_MAX_BLOCKS included. */
+ndt_status gicp_diag_plan(gicp_handle h, size_t n, int out[4]);
 /* applyState on the identity (:519-532): column-major 4x4 */
 void gicp_host_apply_state(const double* x, float* T);
 

@@ -203,6 +203,6 @@ def test_gicp_symbols_exported(built_lib):
     import re
     hdr = open(os.path.join(ROOT, "include", "gicp_mi355.h")).read()
     names = set(re.findall(r"\b(gicp_[a-z_0-9]+)\s*\(", hdr))
-    assert len(names) >= 18
+    assert len(names) >= 19 and "gicp_diag_plan" in names
     for n in names:
         assert hasattr(built_lib, n), n

@@ -180,6 +180,7 @@ SIGNATURES = {
     "gicp_covariances": (C.c_int, [vp, C.c_int, dp, ip, fp]),
     "gicp_step_correspond": (C.c_int, [vp, fp, fp, ip, fp, ip]),
     "gicp_step_functor": (C.c_int, [vp, C.c_int, dp, dp, dp]),
+    "gicp_diag_plan": (C.c_int, [vp, C.c_size_t, ip]),
     "gicp_host_apply_state": (None, [dp, fp]),
 }
 

@@ -72,6 +72,9 @@ namespace {
 // what the index leaf size aims for (points per occupied cell; NDT_GICP_PPC overrides it for tuning runs): with the
 // margin bound most queries finish inside their own cell, so fuller cells cost little and far queries need fewer shells
 static const double kGicpPointsPerCell = std::getenv("NDT_GICP_PPC") ? std::atof(std::getenv("NDT_GICP_PPC")) : 12.0;
+// development switch: caps the grids of all four GICP kernels (0 = each kernel's own limit), so that their grid-strided
+// regime is reached at a few thousand points -- as NDT_K2_MAX_BLOCKS does for the NDT kernels
+static const int kGicpMaxBlocks = std::getenv("NDT_GICP_MAX_BLOCKS") ? std::max(0, std::atoi(std::getenv("NDT_GICP_MAX_BLOCKS"))) : 0;
 constexpr long long kGicpMaxCells = 1ll << 26;       // dense cell table budget (256 MB of int)
 
 // Builds the voxel index of a host cloud on `c`: finite check, upload, leaf size from the cloud's own
@@ -189,8 +192,8 @@ ndt_status gicp_cloud_covariances(gicp_context* h, int which, bool want_neighbor
   // the source's pass runs on the source index's own stream, next to the target's (two independent kernels of a few
   // thousand waves each); everything that follows on the main stream waits for it through an event
   hipStream_t st = (which == 1) ? h->src.stream : h->tgt.stream;
-  HIP_TRY(gicp::launch_knn_covariances(gicp_index_of(c), k, h->prm.gicp_epsilon, cov.p, want_neighbors ? h->nn_idx.p : nullptr,
-                                       want_neighbors ? h->nn_d2.p : nullptr, st));
+  HIP_TRY(gicp::launch_knn_covariances(gicp_index_of(c), k, h->prm.gicp_epsilon, gicp::knn_blocks(static_cast<int>(n), kGicpMaxBlocks),
+                                       cov.p, want_neighbors ? h->nn_idx.p : nullptr, want_neighbors ? h->nn_d2.p : nullptr, st));
   if (which == 1) {
     if (!h->ev_src) HIP_TRY(hipEventCreateWithFlags(&h->ev_src, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(h->ev_src, h->src.stream));
@@ -248,9 +251,10 @@ struct GicpDevice : gicp::Backend {
     have_grad = false;
     server_stop();  // the correspondences change: the next BFGS run gets a fresh server behind this kernel
     const double thr = h->prm.corr_dist_threshold * h->prm.corr_dist_threshold;  // :401
-    const hipError_t e = gicp::launch_correspond(h->output.p, static_cast<int>(h->src.target->n), transformation, rot,
-                                                 gicp_index_of(&h->tgt), h->cov_src.p, h->cov_tgt.p, thr, h->corr.p, h->maha.p,
-                                                 h->tgt.stream);
+    const int n = static_cast<int>(h->src.target->n);
+    const hipError_t e = gicp::launch_correspond(h->output.p, n, transformation, rot, gicp_index_of(&h->tgt), h->cov_src.p,
+                                                 h->cov_tgt.p, thr, gicp::correspond_blocks(n, kGicpMaxBlocks), h->corr.p,
+                                                 h->maha.p, h->tgt.stream);
     if (e != hipSuccess) {
       error = std::string("correspondence kernel: ") + hipGetErrorString(e);
       return false;
@@ -289,7 +293,7 @@ struct GicpDevice : gicp::Backend {
     h->srv_flip ^= 1;
     ndt::server_reset_mailbox(mailbox());
     const int n = static_cast<int>(h->src.target->n);
-    h->srv_blocks = gicp::server_blocks(n);
+    h->srv_blocks = gicp::server_blocks(n, kGicpMaxBlocks);
     hipError_t e = hipMemsetAsync(h->srv_counter.p, 0, 32 * gicp::kGicpServerParts * sizeof(unsigned), h->tgt.stream);
     if (e == hipSuccess) e = h->partials.reserve(static_cast<size_t>(std::max(h->srv_blocks, gicp::kFunctorMaxBlocks)) * ndt::kEvalStride);
     if (e == hipSuccess)
@@ -354,7 +358,7 @@ struct GicpDevice : gicp::Backend {
     if (!have_row) {
       const unsigned long long seq = ++h->seq;
       const hipError_t e = gicp::launch_functor(launch_mode, h->output.p, n, h->tgt.target->pts.p, h->corr.p, h->maha.p, T,
-                                                gicp::functor_blocks(n), h->partials.p, h->counter.p, h->host_pub, seq, h->tgt.stream);
+                                                gicp::functor_blocks(n, kGicpMaxBlocks), h->partials.p, h->counter.p, h->host_pub, seq, h->tgt.stream);
       if (e != hipSuccess) {
         error = std::string("functor kernel: ") + hipGetErrorString(e);
         return false;
@@ -657,6 +661,16 @@ ndt_status gicp_step_functor(gicp_handle h, int mode, const double* x, double* f
     for (int i = 0; i < 9; i++) R[i] = sums.R[i] * (2.0 / m);
     gicp::rotation_gradient(x, R, g);
   }
+  return NDT_OK;
+}
+
+ndt_status gicp_diag_plan(gicp_handle h, size_t n, int out[4]) {
+  if (!h || !out || n > static_cast<size_t>(std::numeric_limits<int>::max())) return fail(NDT_ERR_INVALID, "bad arguments");
+  const int ni = static_cast<int>(n);
+  out[0] = gicp::knn_blocks(ni, kGicpMaxBlocks);
+  out[1] = gicp::correspond_blocks(ni, kGicpMaxBlocks);
+  out[2] = gicp::functor_blocks(ni, kGicpMaxBlocks);
+  out[3] = gicp::server_blocks(ni, kGicpMaxBlocks);
   return NDT_OK;
 }
 

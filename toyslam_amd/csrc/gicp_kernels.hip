@@ -594,29 +594,36 @@ __global__ __launch_bounds__(kBlock) void k_gicp_server(const float4* __restrict
 
 }  // namespace
 
-hipError_t launch_knn_covariances(const PointIndex& ix, int k, double gicp_epsilon, double* cov6, int* nn_idx, float* nn_d2,
-                                  hipStream_t stream) {
-  if (k < 1 || k > kMaxK) return hipErrorInvalidValue;
+// The four grids.  max_blocks > 0 caps a grid below its own limit (NDT_GICP_MAX_BLOCKS, a development switch: every kernel
+// strides over what its grid does not cover, so the results do not depend on it).
+static int grid_of(int n, int per_block, int limit, int max_blocks) {
+  if (max_blocks > 0) limit = min(limit, max_blocks);
+  return max(1, min(limit, (n + per_block - 1) / per_block));
+}
+int knn_blocks(int n, int max_blocks) { return grid_of(n, kKnnBlock / kTeam, 65536, max_blocks); }
+int correspond_blocks(int n, int max_blocks) { return grid_of(n, kBlock / kTeam, 32768, max_blocks); }
+int functor_blocks(int n, int max_blocks) { return grid_of(n, kBlock, kFunctorMaxBlocks, max_blocks); }
+int server_blocks(int n, int max_blocks) { return grid_of(n, kBlock, 512, max_blocks); }
+
+hipError_t launch_knn_covariances(const PointIndex& ix, int k, double gicp_epsilon, int blocks, double* cov6, int* nn_idx,
+                                  float* nn_d2, hipStream_t stream) {
+  if (k < 1 || k > kMaxK || blocks < 1) return hipErrorInvalidValue;
   constexpr int kQueriesPerBlock = kKnnBlock / kTeam;
-  const int blocks = max(1, min(65536, (ix.n + kQueriesPerBlock - 1) / kQueriesPerBlock));
   const size_t lds = static_cast<size_t>(k) * kQueriesPerBlock * 12;  // per team: k distances, k positions, k ordered indices
   hipLaunchKernelGGL(k_knn_covariances, dim3(blocks), dim3(kKnnBlock), lds, stream, ix, k, gicp_epsilon, cov6, nn_idx, nn_d2);
   return hipGetLastError();
 }
 
 hipError_t launch_correspond(const float4* output, int n, const float* T12, const Rot3d& R, const PointIndex& tgt,
-                             const double* cov_src6, const double* cov_tgt6, double dist_threshold, int* corr, float* maha9,
-                             hipStream_t stream) {
+                             const double* cov_src6, const double* cov_tgt6, double dist_threshold, int blocks, int* corr,
+                             float* maha9, hipStream_t stream) {
+  if (blocks < 1) return hipErrorInvalidValue;
   EvalParams P{};
   for (int i = 0; i < 12; i++) P.T[i] = T12[i];
-  constexpr int kQueriesPerBlock = kBlock / kTeam;
-  const int blocks = max(1, min(32768, (n + kQueriesPerBlock - 1) / kQueriesPerBlock));
   hipLaunchKernelGGL(k_correspond, dim3(blocks), dim3(kBlock), 0, stream, output, n, P, R, tgt, cov_src6, cov_tgt6,
                      dist_threshold, corr, maha9);
   return hipGetLastError();
 }
-
-int functor_blocks(int n) { return max(1, min(kFunctorMaxBlocks, (n + kBlock - 1) / kBlock)); }
 
 hipError_t launch_functor(int mode, const float4* output, int n, const float4* tgt, const int* corr, const float* maha9,
                           const float* T12, int n_blocks, double* partials, unsigned* counter, double* out_row,
@@ -634,8 +641,6 @@ hipError_t launch_functor(int mode, const float4* output, int n, const float4* t
                        out_row, seq);
   return hipGetLastError();
 }
-
-int server_blocks(int n) { return max(1, min(512, (n + kBlock - 1) / kBlock)); }
 
 hipError_t launch_server(const float4* output, int n, const float4* tgt, const int* corr, const float* maha9, void* mailbox,
                          int n_blocks, double* partials, unsigned* counter, double* out_rows, unsigned long long first_seq,

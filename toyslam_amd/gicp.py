@@ -115,6 +115,15 @@ class GeneralizedIterativeClosestPoint:
         check(self._L.gicp_covariances(self._h, which, _d(cov), None, None))
         return cov
 
+    PLAN_FIELDS = ("knn_blocks", "correspond_blocks", "functor_blocks", "server_blocks")
+
+    def plan(self, n):
+        """How the launchers cut n points into blocks (gicp_diag_plan): dict of knn_blocks, correspond_blocks,
+        functor_blocks, server_blocks."""
+        v = np.zeros(4, dtype=np.int32)
+        check(self._L.gicp_diag_plan(self._h, int(n), _i(v)))
+        return dict(zip(self.PLAN_FIELDS, (int(x) for x in v)))
+
     def step_correspond(self, guess=None, transformation=None):
         g = None if guess is None else _colmajor(guess)
         t = None if transformation is None else _colmajor(transformation)
