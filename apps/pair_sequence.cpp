@@ -8,10 +8,13 @@
 // call right after the pairs call ("fitness k-1 to k: <value>", 17 significant digits), and that call's time.
 // --batch-filter: every scan is read first, then all of them are prefiltered in ONE ndt_cloud_voxel_filter_batch call; the
 // output is the plain run's, timing lines aside.
+// --gicp: the same consecutive pairs through gicp_align_pairs_clouds (pclomp::GeneralizedIterativeClosestPoint with its
+// constructor's settings, as apps/align.cpp runs it) in place of the NDT pairs call: every filtered scan indexed once, the
+// k-NN covariances of all scans from one launch; poses chained as for NDT.  With --fitness the scores come from the same call.
 // --map <out.pcd>: after the pose chain, all filtered scans at their chained poses (scan 0 at the identity) go into the map
 // in ONE ndt_map_update_clouds call at the node's 0.5 m; "map: <n> points", and the map written as a binary PCD.
 //
-//   pair_sequence <pcd_directory> [--fitness] [--batch-filter] [--map <out.pcd>]
+//   pair_sequence <pcd_directory> [--fitness] [--batch-filter] [--gicp] [--map <out.pcd>]
 #include <cfloat>
 #include <chrono>
 #include <cstdio>
@@ -19,6 +22,7 @@
 #include <cstring>
 #include <vector>
 
+#include "gicp_mi355.h"
 #include "ndt_mi355.h"
 
 #define CHECK(call)                                                     \
@@ -39,17 +43,18 @@ static double since(clock_type::time_point a) { return std::chrono::duration<dou
 
 int main(int argc, char** argv) {
   if (argc < 2) {
-    std::printf("usage: pair_sequence <pcd_directory> [--fitness] [--batch-filter] [--map <out.pcd>]\n");
+    std::printf("usage: pair_sequence <pcd_directory> [--fitness] [--batch-filter] [--gicp] [--map <out.pcd>]\n");
     return 0;
   }
-  bool want_fitness = false, batch_filter = false;
+  bool want_fitness = false, batch_filter = false, use_gicp = false;
   const char* map_path = nullptr;
   for (int a = 2; a < argc; a++) {
     if (std::strcmp(argv[a], "--fitness") == 0) want_fitness = true;
     if (std::strcmp(argv[a], "--batch-filter") == 0) batch_filter = true;
+    if (std::strcmp(argv[a], "--gicp") == 0) use_gicp = true;
     if (std::strcmp(argv[a], "--map") == 0) {
       if (a + 1 >= argc) {
-        std::fprintf(stderr, "--map needs a file name\nusage: pair_sequence <pcd_directory> [--fitness] [--batch-filter] [--map <out.pcd>]\n");
+        std::fprintf(stderr, "--map needs a file name\nusage: pair_sequence <pcd_directory> [--fitness] [--batch-filter] [--gicp] [--map <out.pcd>]\n");
         return 2;
       }
       map_path = argv[++a];
@@ -139,12 +144,18 @@ int main(int argc, char** argv) {
   }
   std::vector<float> T(16 * n_pairs);
   std::vector<int> conv(n_pairs), iters(n_pairs);
-  const auto t_align = clock_type::now();
-  CHECK(ndt_align_pairs_clouds(h, clouds.data(), clouds.size(), 1, pairs.data(), n_pairs, nullptr, T.data(), conv.data(), iters.data(), nullptr));
-  const double align_ms = since(t_align);
   std::vector<double> fitness(n_pairs);
+  gicp_handle gh = nullptr;
+  if (use_gicp) CHECK(gicp_create(0, &gh));
+  const auto t_align = clock_type::now();
+  if (use_gicp)
+    CHECK(gicp_align_pairs_clouds(gh, clouds.data(), clouds.size(), pairs.data(), n_pairs, nullptr, DBL_MAX /* PCL's default */, T.data(),
+                                  conv.data(), iters.data(), nullptr, want_fitness ? fitness.data() : nullptr));
+  else
+    CHECK(ndt_align_pairs_clouds(h, clouds.data(), clouds.size(), 1, pairs.data(), n_pairs, nullptr, T.data(), conv.data(), iters.data(), nullptr));
+  const double align_ms = since(t_align);
   double fitness_ms = 0;
-  if (want_fitness && n_pairs) {
+  if (want_fitness && n_pairs && !use_gicp) {
     const auto t_fit = clock_type::now();
     CHECK(ndt_pairs_fitness_scores(h, nullptr, DBL_MAX /* PCL's default */, fitness.data()));
     fitness_ms = since(t_fit);
@@ -173,7 +184,7 @@ int main(int argc, char** argv) {
   std::printf("\nclouds %zu  pairs %zu (not converged %zu)\n", clouds.size(), n_pairs, not_converged);
   std::printf("time: read + prefilter %.2f ms, pairs call %.2f ms (%.1f pairs/s)\n", load_ms, align_ms,
               align_ms > 0 ? 1e3 * static_cast<double>(n_pairs) / align_ms : 0.0);
-  if (want_fitness) std::printf("time: fitness call %.3f ms\n", fitness_ms);
+  if (want_fitness && !use_gicp) std::printf("time: fitness call %.3f ms\n", fitness_ms);
   if (map_path) {  // ---- every scan at its pose into the map: one call
     const auto t_map = clock_type::now();
     std::vector<int> dense(clouds.size(), 1);
@@ -189,6 +200,7 @@ int main(int argc, char** argv) {
     std::printf("time: map call %.3f ms%s\n", map_ms, overflowed ? " (leaf size too small: unfiltered)" : "");
   }
   for (ndt_cloud c : clouds) ndt_cloud_release(c);
+  gicp_destroy(gh);
   ndt_destroy(h);
   return 0;
 }

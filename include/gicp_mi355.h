@@ -46,6 +46,48 @@ ndt_status gicp_set_input_source(gicp_handle h, const void* pts, size_t n, size_
 ndt_status gicp_set_source_covariances(gicp_handle h, const double* cov, size_t n);
 ndt_status gicp_set_target_covariances(gicp_handle h, const double* cov, size_t n);
 
+/* setInputTarget / setInputSource BY REFERENCE from a cloud resident in HBM (ndt_cloud_upload, ndt_cloud_voxel_filter*,
+ * batched filter outputs, sequence views): no download, no host pass over the points.  Same index, covariances,
+ * correspondences and registration -- the same bits -- as gicp_set_input_target / _source on the same points.
+ * The handle holds a reference of its own (the caller may release the cloud).  A cloud with a non-finite point:
+ * NDT_ERR_INVALID (found on the device: one counting pass, one word read back), as is a NULL or empty cloud; the handle then
+ * has no such input, as after a refused host call.  Resets the covariances like the host setters. */
+ndt_status gicp_set_input_target_cloud(gicp_handle h, ndt_cloud c);
+ndt_status gicp_set_input_source_cloud(gicp_handle h, ndt_cloud c);
+
+/* GICP of n_pairs (target, source) pairs of resident clouds: pairs[2k] = target, pairs[2k+1] = source of pair k.
+ * Every cloud NAMED by a pair is indexed once and gets its k-NN covariances once, whatever the number of pairs that
+ * name it and in whichever role -- the covariances of ALL named clouds from one launch (k_knn_covariances_multi; a further
+ * launch per 2^20 blocks = 8.4 M points) -- then the pairs are registered one after the other by the existing outer loop
+ * (k_correspond, the objective server, host BFGS).
+ * Pair k gets what a fresh gicp_handle with the same parameters gets from gicp_set_input_target(points of the target),
+ * gicp_set_input_source(points of the source), gicp_align(guess k) and gicp_get_fitness_score(max_range): the same
+ * bits, whatever the other pairs, their order and the order of the clouds.  Parameters (k, epsilons, iteration limits,
+ * gate) are the handle's.  Caller-supplied covariances (gicp_set_*_covariances) are not used by this call.
+ * guesses: n_pairs*16 column-major or NULL = identity.  Outputs have n_pairs entries, any may be NULL; fitness NULL =
+ * not computed.  The handle's own target, source, covariances, last result and stats are left as they were (only the
+ * scratch of gicp_step_correspond is reused: gicp_step_functor wants a new step afterwards).
+ * The handle keeps a reference to every named cloud, with its index and covariances, until the next pairs call or
+ * gicp_destroy (gicp_pairs_covariances reads them).
+ * NDT_ERR_INVALID before any device work, nothing written: NULL handle; NULL clouds / pairs with a non-zero count; a
+ * NULL entry of clouds; a pair index < 0 or >= n_clouds; more than 65535 pairs; a NAMED cloud with fewer points than
+ * k_correspondences (the message names the cloud; an unnamed one may be any size, empty included).
+ * NDT_ERR_INVALID after the device's finite check (one launch over all named clouds, one count per cloud read back): a
+ * named cloud with a non-finite point.  On any error no output is written and nothing is kept.  n_pairs == 0: NDT_OK, no
+ * device needed. */
+ndt_status gicp_align_pairs_clouds(gicp_handle h, const ndt_cloud* clouds, size_t n_clouds, const int* pairs, size_t n_pairs,
+                                   const float* guesses, double max_range, float* final_T, int* converged,
+                                   int* n_iterations, int* correspondences, double* fitness);
+
+/* inspection of the last successful pairs call (dropped by the next one or gicp_destroy; NDT_ERR_NO_INPUT otherwise
+ * or when `cloud` was not named): the covariances it computed for cloud `cloud`, [n][9] row-major as gicp_covariances */
+ndt_status gicp_pairs_covariances(gicp_handle h, size_t cloud, double* cov);
+/* index builds (== named clouds), k_knn_covariances_multi launches, and the blocks of those launches together */
+ndt_status gicp_diag_pairs(gicp_handle h, size_t* index_builds, size_t* knn_launches, size_t* knn_blocks);
+/* host wall clock of the last successful pairs call's two halves, in ms: the preparation (finite check, index builds, the
+ * covariance launch, waited for) and the registrations with their fitness scores (tools/time_gicp_pairs.py) */
+ndt_status gicp_diag_pairs_time(gicp_handle h, double* prepare_ms, double* register_ms);
+
 /* pcl::Registration::align(output, guess) -> computeTransformation (gicp_omp_impl.hpp:372-517).
  * guess / final_T: column-major 4x4 f32 (Eigen::Matrix4f::data()), guess may be NULL (identity).
  * out_cloud: NULL or n_source records of stride 16 bytes (x, y, z, 1). */

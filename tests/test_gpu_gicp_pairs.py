@@ -1,0 +1,389 @@
+"""GPU: GICP over clouds that stay in HBM -- gicp_set_input_*_cloud and gicp_align_pairs_clouds (every named cloud indexed
+once, the k-NN covariances of all of them from ONE k_knn_covariances_multi launch, then one registration per pair).
+
+What is EXPECTED never comes from the pairs call: it is the CPU oracle's answer (oracle.pyoracle) or what a fresh
+single-cloud handle fed the host arrays gives (gicp_set_input_target / _source, gicp_align, gicp_get_fitness_score) -- and
+against the latter every comparison is bit for bit (np.array_equal)."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import ROOT, rot_err, trans_err
+from oracle import pyoracle as po
+from test_gicp_gpu import ROT_TOL, TRANS_TOL, gmod  # noqa: F401  (gmod: the fixture)
+from test_gicp_pairs_host import Outputs, call
+from toyslam_amd import clouds
+
+pytestmark = pytest.mark.gpu
+
+CAP = int(os.environ.get("NDT_GICP_MAX_BLOCKS", "0") or 0)   # the development switch that caps every member's blocks
+LIMIT = int(os.environ.get("NDT_GICP_MULTI_MAX_BLOCKS", "0") or 0) or 1 << 20   # blocks one covariance launch carries
+SIZES = {20: (20, 21, 27, 28, 29, 64, 65, 1023, 1024, 1025, 2500), 5: (5, 6, 12, 13, 14, 300), 64: (64, 65, 71, 72, 73, 600)}
+GUESS = clouds.make_T([0.2, -0.1, 0.05], np.radians([0.3, -0.2, 0.6])).astype(np.float32)   # test_align_matches_oracle's
+
+
+@pytest.fixture(scope="module")
+def up(gmod):
+    """An NDT handle: the owner of the resident clouds (ndt_cloud_upload)."""
+    from toyslam_amd import ndt
+    return ndt.NormalDistributionsTransform()
+
+
+@pytest.fixture(scope="module")
+def scene():
+    tgt = clouds.target_surfaces(20000)[:, :3].astype(np.float32)
+    src = clouds.source_from_target(tgt, 8000)[:, :3].astype(np.float32)
+    return tgt, src
+
+
+def noisy_subsets(sizes, seed=7):
+    """Random subsets of a 3 000-point scene of 20 m, each under a small pose of its own (+-0.1 m, +-0.01 rad) plus 1 cm
+    noise."""
+    base = clouds.target_surfaces(3000, extent=20.0, n_boxes=12)[:, :3]
+    rng = np.random.default_rng(seed)
+    out = []
+    for n in sizes:
+        sub = base[rng.choice(len(base), n, replace=False)]
+        T = clouds.make_T(rng.uniform(-0.1, 0.1, 3), rng.uniform(-0.01, 0.01, 3))
+        out.append((clouds.apply_T(T, sub) + rng.normal(0, 0.01, (n, 3))).astype(np.float32))
+    return out
+
+
+@pytest.fixture(scope="module")
+def subsets():
+    return {k: noisy_subsets(s) for k, s in SIZES.items()}
+
+
+def launches_of(blocks):
+    """Launches of the covariance pass: members in order while their blocks stay within LIMIT, a member never split."""
+    n, acc = 1, 0
+    for b in blocks:
+        if acc > 0 and acc + b > LIMIT:
+            n, acc = n + 1, 0
+        acc += b
+    return n
+
+
+def fresh(gmod, tgt, src, guess, max_range, params=()):
+    """What a fresh handle fed the host arrays gives for one pair: (T, converged, iterations, correspondences, fitness)."""
+    g = gmod.GeneralizedIterativeClosestPoint()
+    for name, v in params:
+        getattr(g, name)(v)
+    g.setInputTarget(tgt)
+    g.setInputSource(src)
+    g.align(guess)
+    return (g.getFinalTransformation(), g.hasConverged(), g.getFinalNumIteration(), g.stats()["correspondences"],
+            g.getFitnessScore(max_range))
+
+
+def same_as_fresh(r, k, want, ctx):
+    T, conv, it, corr, fit = want
+    assert np.array_equal(r["T"][k], T), ctx
+    assert (bool(r["converged"][k]), int(r["iterations"][k]), int(r["correspondences"][k])) == (conv, it, corr), ctx
+    assert r["fitness"][k] == fit, ctx
+
+
+# ------------------------------------------------------------------ 1. cloud inputs equal host inputs
+def test_cloud_inputs_equal_host_inputs(gmod, up, scene):
+    tgt, src = scene
+    a, b = gmod.GeneralizedIterativeClosestPoint(), gmod.GeneralizedIterativeClosestPoint()
+    dt, ds = up.uploadCloud(tgt), up.uploadCloud(src)
+    a.setInputTargetCloud(dt)
+    a.setInputSourceCloud(ds)
+    dt.release()    # the handle holds a reference of its own
+    b.setInputTarget(tgt)
+    b.setInputSource(src)
+    for which in (0, 1):
+        ca, cb = a.covariances(which), b.covariances(which)
+        assert ca.shape == cb.shape == (len(tgt if which == 0 else src), 3, 3) and np.array_equal(ca, cb)
+    (ma, ia, ha), (mb, ib, hb) = a.step_correspond(GUESS), b.step_correspond(GUESS)
+    assert ma == mb > 0 and np.array_equal(ia, ib) and np.array_equal(ha, hb)
+    for guess in (None, GUESS):
+        a.align(guess)
+        b.align(guess)
+        assert np.array_equal(a.getFinalTransformation(), b.getFinalTransformation())
+        assert a.getFinalNumIteration() == b.getFinalNumIteration() > 0 and a.stats() == b.stats()
+        assert a.getFitnessScore() == b.getFitnessScore() and a.getFitnessScore(1.0) == b.getFitnessScore(1.0)
+
+
+# ------------------------------------------------------------------ 2. the multi kernel at member and block boundaries
+REF = {}   # (k, cloud) -> (oracle covariances or None, single-handle covariances): computed once, never written again
+
+
+def reference(gmod, k, cl, i):
+    if (k, i) not in REF:
+        g = gmod.GeneralizedIterativeClosestPoint()
+        g.setCorrespondenceRandomness(k)
+        g.setInputTarget(cl[i])
+        # k = 5 on a few dozen points: degenerate shapes are compared with the single handle only (test_gicp_gpu_plans)
+        oracle = po.gicp_covariances(cl[i], k, 1e-3) if (k >= 20 or len(cl[i]) >= 30) else None
+        REF[(k, i)] = (oracle, g.covariances(0))
+        for a in REF[(k, i)]:
+            if a is not None:
+                a.setflags(write=False)
+    return REF[(k, i)]
+
+
+@pytest.mark.parametrize("k", [20, 5, 64])
+def test_multi_kernel_at_member_and_block_boundaries(gmod, up, subsets, k):
+    """One pairs call over the consecutive pairs of clouds whose sizes sit on the cuts of the member table: n = k, k + 1, a
+    partly filled / full / one-over last block of 8 queries, members of 1, 3, 4, 8, 9, 128, 129 and 313 blocks."""
+    cl = subsets[k]
+    g = gmod.GeneralizedIterativeClosestPoint()
+    g.setCorrespondenceRandomness(k)
+    g.setMaximumIterations(1)
+    blocks = [-(-len(c) // 8) for c in cl]
+    if CAP:
+        blocks = [min(CAP, b) for b in blocks]
+    assert [g.plan(len(c))["knn_blocks"] for c in cl] == blocks
+    if not CAP and k == 20:
+        assert sorted(set(blocks)) == [3, 4, 8, 9, 128, 129, 313]
+    for order in (list(range(len(cl))), list(range(len(cl)))[::-1]):
+        dcs = [up.uploadCloud(cl[i]) for i in order]
+        g.alignPairsClouds(dcs)
+        d = g.diagPairs()
+        bl = [blocks[i] for i in order]
+        assert d == dict(index_builds=len(cl), knn_launches=launches_of(bl), knn_blocks=sum(blocks)), d
+        assert launches_of(bl) == (1 if LIMIT == 1 << 20 else {20: 5, 5: 1, 64: 1}[k]), (k, bl)
+        for pos, i in enumerate(order):
+            oracle, single = reference(gmod, k, cl, i)
+            cov = g.pairsCovariances(pos)
+            ctx = "k=%d n=%d (cloud %d at %d)" % (k, len(cl[i]), i, pos)
+            assert cov.shape == single.shape and np.array_equal(cov, single), ctx
+            if oracle is not None:
+                dev = float(np.abs(cov - oracle).max())
+                print("%s: covariances max abs deviation from the oracle %.3g" % (ctx, dev))
+                assert np.all(np.isfinite(oracle)) and dev < 1e-12, ctx
+
+
+def rerun_boundaries(env):
+    """The test above once more, in a process of its own under `env` (the switches are read once per process)."""
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_gicp_pairs.py"), "-q", "-s", "-m", "gpu",
+                        "-p", "no:cacheprovider", "-k", "test_multi_kernel_at_member_and_block_boundaries"],
+                       env=dict(os.environ, **env), capture_output=True, text=True, timeout=280, cwd=ROOT)
+    tail = r.stdout[-4000:] + r.stderr[-1500:]
+    assert r.returncode == 0, tail
+    last = r.stdout.strip().splitlines()[-1]
+    assert "3 passed" in last and "skipped" not in last and "failed" not in last, tail
+
+
+def test_multi_kernel_with_every_member_capped_at_three_blocks():
+    """NDT_GICP_MAX_BLOCKS=3: every member of more than 24 points is strided by its own three blocks, knn_blocks is the sum
+    of min(3, ...)."""
+    if CAP:
+        pytest.skip("this process already runs under NDT_GICP_MAX_BLOCKS; the rerun is for a process without it")
+    rerun_boundaries({"NDT_GICP_MAX_BLOCKS": "3"})
+
+
+def test_multi_kernel_split_into_several_launches():
+    """NDT_GICP_MULTI_MAX_BLOCKS=140 (the real limit, 2^20 blocks, is 8.4 M points away): the k = 20 members go out in five
+    launches -- the seven small ones together, then the members of 128, 128, 129 and 313 blocks each on its own, the last
+    one larger than the limit -- in either order of the clouds, with every cloud's bits unchanged."""
+    if LIMIT != 1 << 20 or CAP:
+        pytest.skip("this process already runs under NDT_GICP_MAX_BLOCKS or NDT_GICP_MULTI_MAX_BLOCKS; the rerun is for a process without them")
+    rerun_boundaries({"NDT_GICP_MULTI_MAX_BLOCKS": "140"})
+
+
+# ------------------------------------------------------------------ 3. pairs equal fresh handles
+PAIRS = [(0, 1), (1, 2), (2, 3), (3, 4), (0, 4), (2, 2), (1, 3)]
+GUESSES = [None, clouds.make_T([0.05, -0.03, 0.02], [0.004, -0.003, 0.01]).astype(np.float32), None,
+           clouds.make_T([-0.04, 0.06, 0.0], [0.0, 0.005, -0.008]).astype(np.float32), None, None,
+           clouds.make_T([0.02, 0.02, -0.03], [-0.006, 0.0, 0.004]).astype(np.float32)]
+EYE = np.eye(4, dtype=np.float32)
+PARAM_SETS = {"defaults": (),
+              "k10_gate1_iter5": (("setCorrespondenceRandomness", 10), ("setMaxCorrespondenceDistance", 1.0), ("setMaximumIterations", 5))}
+FRESH = {}
+
+
+@pytest.fixture(scope="module")
+def five(subsets, scene):
+    return list(subsets[20][7:11]) + [scene[0][:3000]]
+
+
+def fresh_pairs(gmod, five, name):
+    """The seven pairs through a fresh handle each, once per parameter set."""
+    if name not in FRESH:
+        FRESH[name] = [fresh(gmod, five[t], five[s], GUESSES[p], 1.0, PARAM_SETS[name]) for p, (t, s) in enumerate(PAIRS)]
+    return FRESH[name]
+
+
+def run_pairs(gmod, dcs, name, order):
+    g = gmod.GeneralizedIterativeClosestPoint()
+    for meth, v in PARAM_SETS[name]:
+        getattr(g, meth)(v)
+    r = g.alignPairsClouds(dcs, [PAIRS[p] for p in order], [EYE if GUESSES[p] is None else GUESSES[p] for p in order], 1.0)
+    return g, r
+
+
+@pytest.mark.parametrize("name", list(PARAM_SETS))
+def test_pairs_equal_fresh_handles(gmod, up, five, name):
+    """Consecutive pairs, a loop closure, one cloud as target and source of the same pair, one cloud a target twice; three
+    pairs with a guess; max_range 1 m^2 -- in the given order and shuffled."""
+    assert [len(c) for c in five] == [1023, 1024, 1025, 2500, 3000]
+    want = fresh_pairs(gmod, five, name)
+    dcs = [up.uploadCloud(c) for c in five]
+    shuffled = [int(x) for x in np.random.default_rng(3).permutation(len(PAIRS))]
+    assert shuffled != list(range(len(PAIRS)))
+    for order in (list(range(len(PAIRS))), shuffled):
+        g, r = run_pairs(gmod, dcs, name, order)
+        for pos, p in enumerate(order):
+            same_as_fresh(r, pos, want[p], "%s pair %s at %d" % (name, PAIRS[p], pos))
+        assert g.diagPairs()["index_builds"] == 5 and g.diagPairs()["knn_launches"] == 1
+    assert any(w[2] > 1 for w in want) and all(np.all(np.isfinite(w[0])) for w in want)   # they do iterate
+
+
+# ------------------------------------------------------------------ 4. against the oracle
+@pytest.fixture(scope="module")
+def oracle(scene):
+    o = po.OracleGICP()
+    o.setInputTarget(scene[0])
+    o.setInputSource(scene[1])
+    return o
+
+
+@pytest.mark.parametrize("case", ["identity", "guess"])
+def test_pairs_call_matches_the_oracle(gmod, up, scene, oracle, case):
+    guess = GUESS if case == "guess" else None
+    ro = oracle.align(guess)
+    g = gmod.GeneralizedIterativeClosestPoint()
+    r = g.alignPairsClouds([up.uploadCloud(scene[0]), up.uploadCloud(scene[1])], [(0, 1)], None if guess is None else [guess])
+    rot, tr = rot_err(r["T"][0], ro["T"]), trans_err(r["T"][0], ro["T"])
+    print("%s: rot %.3g trans %.3g iterations %d" % (case, rot, tr, ro["iterations"]))
+    assert rot < ROT_TOL and tr < TRANS_TOL
+    assert bool(r["converged"][0]) == ro["converged"] and int(r["iterations"][0]) == ro["iterations"]
+    assert int(r["correspondences"][0]) == ro["correspondences"]
+
+
+# ------------------------------------------------------------------ 5. handle state
+def test_pairs_call_leaves_the_handle_as_it_was(gmod, up, scene, five):
+    tgt, src = scene[0][:6000], scene[1][:2500]
+    rng = np.random.default_rng(5)
+
+    def spd(n):
+        a = rng.normal(0, 1, (n, 3, 3))
+        return (a @ a.transpose(0, 2, 1)) * 0.01 + 1e-3 * np.eye(3)
+
+    g = gmod.GeneralizedIterativeClosestPoint()
+    g.setInputTarget(tgt)
+    g.setInputSource(src)
+    ct, cs = spd(len(tgt)), spd(len(src))
+    g.setTargetCovariances(ct)
+    g.setSourceCovariances(cs)
+    g.align(GUESS)
+    before = (g.getFinalTransformation(), g.hasConverged(), g.getFinalNumIteration(), g.stats(), g.covariances(0), g.covariances(1))
+    r = g.alignPairsClouds([up.uploadCloud(c) for c in five], PAIRS[:3], max_range=1.0)
+    assert r["T"].shape == (3, 4, 4) and not np.array_equal(r["T"][0], before[0])
+    after = (g.getFinalTransformation(), g.hasConverged(), g.getFinalNumIteration(), g.stats(), g.covariances(0), g.covariances(1))
+    for x, y in zip(before, after):
+        assert np.array_equal(x, y) if isinstance(x, np.ndarray) else x == y
+    g.align(GUESS)
+    assert np.array_equal(g.getFinalTransformation(), before[0]) and g.stats() == before[3]
+    # ... and the pairs call did not use the handle's supplied covariances: pair 0 is a fresh handle's
+    assert GUESSES[0] is None
+    same_as_fresh(r, 0, fresh_pairs(gmod, five, "defaults")[0], "pair 0 after a used handle")
+
+
+# ------------------------------------------------------------------ 6. refusals on the device
+def test_refusals_on_the_device(gmod, up, five):
+    from toyslam_amd import _lib
+    L = _lib.lib()
+    want = fresh_pairs(gmod, five, "defaults")
+    g = gmod.GeneralizedIterativeClosestPoint()
+    dcs = [up.uploadCloud(c) for c in five]
+    tiny = up.uploadCloud(five[0][:19])
+    nan, inf = five[1].copy(), five[2].copy()
+    nan[1000, 1] = np.nan
+    inf[3, 2] = -np.inf
+    d_nan, d_inf = up.uploadCloud(nan), up.uploadCloud(inf)
+
+    def good(extra=()):
+        r = g.alignPairsClouds(dcs + list(extra), PAIRS[:2], [EYE, GUESSES[1]], 1.0)
+        for p in (0, 1):
+            same_as_fresh(r, p, want[p], "good call, pair %d" % p)
+        assert g.diagPairs()["index_builds"] == 3
+
+    def refused(cl, pairs, what):
+        arr = (C.c_void_p * len(cl))(*[None if c is None else c._c for c in cl])
+        out = Outputs(len(pairs))
+        assert call(L, g._h, arr, len(cl), np.asarray(pairs, np.int32).reshape(-1), len(pairs), out) == _lib.NDT_ERR_INVALID, what
+        assert out.untouched(), what
+        with pytest.raises(_lib.NdtError) as e:   # nothing is kept
+            g.pairsCovariances(0)
+        assert e.value.status == _lib.NDT_ERR_NO_INPUT, what
+
+    good()
+    refused(dcs, [(0, 1), (1, 5)], "index of n_clouds")
+    good()
+    refused(dcs, [(0, 1), (-1, 2)], "negative index")
+    good()
+    refused(dcs[:2] + [None] + dcs[3:], [(0, 1)], "a NULL entry")
+    good()
+    arr = (C.c_void_p * 6)(*[c._c for c in dcs + [tiny]])
+    out = Outputs(1)
+    assert call(L, g._h, arr, 6, [0, 5], 1, out) == _lib.NDT_ERR_INVALID and out.untouched()
+    assert b"cloud 5" in L.ndt_last_error() and b"19" in L.ndt_last_error()
+    good()
+    good(extra=[tiny])   # the 19-point cloud unnamed is accepted
+    refused([dcs[0], d_nan], [(0, 1)], "a NaN")
+    good()
+    refused([d_inf, dcs[1]], [(0, 1)], "an infinity")
+    good()
+    # the cloud setters refuse such clouds too, and the handle then has no such input
+    h = gmod.GeneralizedIterativeClosestPoint()
+    h.setInputSourceCloud(dcs[1])
+    for bad in (d_nan, d_inf):
+        with pytest.raises(_lib.NdtError) as e:
+            h.setInputTargetCloud(bad)
+        assert e.value.status == _lib.NDT_ERR_INVALID
+        with pytest.raises(_lib.NdtError) as e:
+            h.align()
+        assert e.value.status == _lib.NDT_ERR_NO_INPUT
+    with pytest.raises(_lib.NdtError):
+        h.setInputSourceCloud(d_nan)
+    h.setInputTargetCloud(dcs[0])
+    h.setInputSourceCloud(dcs[1])
+    h.align()
+    assert np.array_equal(h.getFinalTransformation(), want[0][0])
+
+
+# ------------------------------------------------------------------ 7. a sequence
+def test_a_sequence_of_forty_clouds(gmod, up):
+    cl = noisy_subsets([2000] * 40, seed=11)
+    params = (("setMaximumIterations", 3),)
+    g = gmod.GeneralizedIterativeClosestPoint()
+    g.setMaximumIterations(3)
+    r = g.alignPairsClouds([up.uploadCloud(c) for c in cl], max_range=1.0)
+    assert g.diagPairs() == dict(index_builds=40, knn_launches=1, knn_blocks=40 * (min(CAP, 250) if CAP else 250))
+    assert r["T"].shape == (39, 4, 4) and np.all(np.isfinite(r["T"])) and np.all(np.isfinite(r["fitness"]))
+    assert np.all(r["converged"] | (r["iterations"] == 3)) and np.all(r["correspondences"] > 0)
+    for p in (0, 38):
+        same_as_fresh(r, p, fresh(gmod, cl[p], cl[p + 1], None, 1.0, params), "sequence pair %d" % p)
+
+
+# ------------------------------------------------------------------ 8. apps/pair_sequence --gicp
+def test_pair_sequence_app_registers_the_pairs_by_gicp(gmod, up, tmp_path):
+    """pair_sequence --gicp --fitness on six scans written as PCD files: the printed transformations, pose chain and fitness
+    scores are those of alignPairsClouds over the same scans filtered at the node's 0.5 m (%.9g / %.17g print f32 / f64
+    exactly)."""
+    from test_gpu_pairs import build_app, matrices, sequence
+    from toyslam_amd import ndt
+    scans, d = sequence(clouds, ndt, tmp_path)
+    out = subprocess.run([build_app(tmp_path, "pair_sequence"), str(d), "--gicp", "--fitness"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr[-2000:]
+    step, chain = matrices(out.stdout, "Transform "), matrices(out.stdout, "TransformSum")
+    fit = [float(ln.split(":")[1]) for ln in out.stdout.splitlines() if ln.startswith("fitness ")]
+    assert len(step) == len(chain) == len(fit) == 5
+    g = gmod.GeneralizedIterativeClosestPoint()
+    r = g.alignPairsClouds([up.voxelGridFilterCloud(sc, 0.5)[0] for sc in scans])
+    assert "pairs 5 (not converged %d)" % int((~r["converged"]).sum()) in out.stdout
+    total = np.eye(4, dtype=np.float32)
+    for k in range(5):
+        T = r["T"][k] if r["converged"][k] else np.eye(4, dtype=np.float32)   # (the node counts such a pair as identity)
+        total = ndt.host_chain_pose(total, T)
+        assert np.array_equal(step[k].astype(np.float32), T) and np.array_equal(chain[k].astype(np.float32), total), k
+        assert fit[k] == r["fitness"][k], k
+    assert r["converged"].any() and np.all(r["iterations"] > 0)

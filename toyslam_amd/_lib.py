@@ -173,6 +173,12 @@ SIGNATURES = {
     "gicp_set_input_source": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t]),
     "gicp_set_source_covariances": (C.c_int, [vp, dp, C.c_size_t]),
     "gicp_set_target_covariances": (C.c_int, [vp, dp, C.c_size_t]),
+    "gicp_set_input_target_cloud": (C.c_int, [vp, vp]),
+    "gicp_set_input_source_cloud": (C.c_int, [vp, vp]),
+    "gicp_align_pairs_clouds": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, ip, C.c_size_t, fp, C.c_double, fp, ip, ip, ip, dp]),
+    "gicp_pairs_covariances": (C.c_int, [vp, C.c_size_t, dp]),
+    "gicp_diag_pairs": (C.c_int, [vp, szp, szp, szp]),
+    "gicp_diag_pairs_time": (C.c_int, [vp, dp, dp]),
     "gicp_align": (C.c_int, [vp, fp, fp, ip, ip, vp]),
     "gicp_get_result": (C.c_int, [vp, fp, ip, ip]),
     "gicp_get_fitness_score": (C.c_int, [vp, C.c_double, dp]),

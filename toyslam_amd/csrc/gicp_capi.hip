@@ -46,6 +46,19 @@ struct gicp_context {
   unsigned long long seq = 0;
   float guess_rm[16];          // guess of the current align / step, row-major
   bool step_ready = false;
+  // gicp_align_pairs_clouds: what the last successful call prepared for every cloud a pair named (null for the others) --
+  // the cloud, its search index, its k-NN covariances [n][6] -- and what it launched (gicp_pairs_covariances, gicp_diag_pairs)
+  struct Prepared {
+    std::shared_ptr<DeviceCloud> cloud;
+    std::shared_ptr<DeviceGrid> grid;
+    DevBuf<double> cov;
+  };
+  std::vector<std::unique_ptr<Prepared>> pairs_prepared;
+  bool pairs_valid = false;
+  size_t pairs_index_builds = 0, pairs_knn_launches = 0, pairs_knn_blocks = 0;
+  double pairs_prepare_ms = 0, pairs_register_ms = 0;  // host wall clock of the call's two halves (tools/time_gicp_pairs.py)
+  DevBuf<unsigned char> member_table;  // the member tables of the finite check and of k_knn_covariances_multi
+  DevBuf<unsigned> finite_counts;
   // results
   float final_T[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // column-major
   int converged = 0, nr_iterations = 0, n_f = 0, n_df = 0, n_fdf = 0, correspondences = 0;
@@ -56,6 +69,7 @@ struct gicp_context {
       (void)hipStreamSynchronize(tgt.stream);
       tls_pool_stream = tgt.stream;
     }
+    pairs_prepared.clear(); member_table.release(); finite_counts.release();
     cov_tgt.release(); cov_src.release(); output.release(); corr.release(); maha.release(); partials.release();
     counter.release(); out_cloud.release(); nn_idx.release(); nn_d2.release();
     if (host_pub) (void)hipHostFree(host_pub);
@@ -75,33 +89,21 @@ static const double kGicpPointsPerCell = std::getenv("NDT_GICP_PPC") ? std::atof
 // development switch: caps the grids of all four GICP kernels (0 = each kernel's own limit), so that their grid-strided
 // regime is reached at a few thousand points -- as NDT_K2_MAX_BLOCKS does for the NDT kernels
 static const int kGicpMaxBlocks = std::getenv("NDT_GICP_MAX_BLOCKS") ? std::max(0, std::atoi(std::getenv("NDT_GICP_MAX_BLOCKS"))) : 0;
+// development switch: the blocks one k_knn_covariances_multi launch carries (default gicp::kKnnMultiMaxBlocks), so that the
+// split of a pairs call's covariance pass into several launches is reached with a few thousand points
+static const int kGicpMultiMaxBlocks = std::getenv("NDT_GICP_MULTI_MAX_BLOCKS") ? std::max(1, std::atoi(std::getenv("NDT_GICP_MULTI_MAX_BLOCKS")))
+                                                                                : gicp::kKnnMultiMaxBlocks;
 constexpr long long kGicpMaxCells = 1ll << 26;       // dense cell table budget (256 MB of int)
 
-// Builds the voxel index of a host cloud on `c`: finite check, upload, leaf size from the cloud's own
-// density (volume guess first, then corrected once from the measured points per occupied cell --
+// Builds the voxel index of the cloud c->target (on the device, every point finite, inside the box mn .. mx) on `c`: leaf
+// size from the cloud's own density (volume guess first, then corrected once from the measured points per occupied cell --
 // scans are surfaces, so occupancy grows with the square of the leaf).
-ndt_status gicp_build_index(ndt_context* c, const void* pts, size_t n, size_t stride, float* hint_leaf, size_t* hint_n) {
-  if (!pts || n == 0) return fail(NDT_ERR_INVALID, "invalid or empty point cloud dataset given");
-  if (stride < 12 || stride % 4) return fail(NDT_ERR_INVALID, "stride_bytes must be a multiple of 4 and >= 12");
-  double mn[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, mx[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
-  const unsigned char* base = static_cast<const unsigned char*>(pts);
-  for (size_t i = 0; i < n; i++) {
-    float p[3];
-    std::memcpy(p, base + i * stride, sizeof(p));
-    if (!(std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2])))
-      return fail(NDT_ERR_INVALID, "GICP needs finite points (point " + std::to_string(i) + " is not)");
-    for (int k = 0; k < 3; k++) {
-      mn[k] = std::min(mn[k], static_cast<double>(p[k]));
-      mx[k] = std::max(mx[k], static_cast<double>(p[k]));
-    }
-  }
-  ndt_status s = ensure_device(c);
-  if (s) return s;
+ndt_status gicp_index_cloud(ndt_context* c, const double mn[3], const double mx[3], float* hint_leaf, size_t* hint_n) {
   c->target_dense = 1;
   c->min_pts = 1;
   c->index_only = true;
-  s = upload_cloud(c, pts, n, stride, false, c->target);
-  if (s) return s;
+  const size_t n = c->target->n;
+  ndt_status s = NDT_OK;
   double ext[3], vol = 1.0, ext_max = 0.0;
   for (int k = 0; k < 3; k++) {
     ext[k] = std::max(mx[k] - mn[k], 1e-3);
@@ -140,6 +142,79 @@ ndt_status gicp_build_index(ndt_context* c, const void* pts, size_t n, size_t st
   *hint_leaf = leaf;
   *hint_n = n;
   return ensure_cell2leaf(c, c->grid.get());
+}
+
+// The index of a host cloud on `c`: finite check and bounding box on the host, upload, gicp_index_cloud.
+ndt_status gicp_build_index(ndt_context* c, const void* pts, size_t n, size_t stride, float* hint_leaf, size_t* hint_n) {
+  if (!pts || n == 0) return fail(NDT_ERR_INVALID, "invalid or empty point cloud dataset given");
+  if (stride < 12 || stride % 4) return fail(NDT_ERR_INVALID, "stride_bytes must be a multiple of 4 and >= 12");
+  double mn[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, mx[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
+  const unsigned char* base = static_cast<const unsigned char*>(pts);
+  for (size_t i = 0; i < n; i++) {
+    float p[3];
+    std::memcpy(p, base + i * stride, sizeof(p));
+    if (!(std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2])))
+      return fail(NDT_ERR_INVALID, "GICP needs finite points (point " + std::to_string(i) + " is not)");
+    for (int k = 0; k < 3; k++) {
+      mn[k] = std::min(mn[k], static_cast<double>(p[k]));
+      mx[k] = std::max(mx[k], static_cast<double>(p[k]));
+    }
+  }
+  ndt_status s = ensure_device(c);
+  if (s) return s;
+  s = upload_cloud(c, pts, n, stride, false, c->target);
+  if (s) return s;
+  return gicp_index_cloud(c, mn, mx, hint_leaf, hint_n);
+}
+
+// The index of a cloud resident in HBM (an ndt_cloud whose points passed gicp_finite_check) on `c`: the box the cloud
+// carries (computed when it was made) takes the place of the host loop, nothing is copied.
+ndt_status gicp_index_resident(ndt_context* c, const std::shared_ptr<DeviceCloud>& cloud, float* hint_leaf, size_t* hint_n) {
+  double mn[3], mx[3];
+  for (int k = 0; k < 3; k++) {  // (every point finite: the box of the non-NaN points and that of the finite ones are one)
+    mn[k] = static_cast<double>(cloud->bb_min[1][k]);
+    mx[k] = static_cast<double>(cloud->bb_max[1][k]);
+  }
+  c->target = cloud;
+  return gicp_index_cloud(c, mn, mx, hint_leaf, hint_n);
+}
+
+// An asynchronous copy from pageable host memory is queued on `s`: unless the success path has synchronised already
+// (done), leaving the scope waits for the stream, so an error return between the copy and that synchronise cannot free
+// the host memory under a copy still queued.
+struct StreamDrain {
+  hipStream_t s;
+  bool done = false;
+  ~StreamDrain() { if (!done) (void)hipStreamSynchronize(s); }
+};
+
+// One device pass, one launch, over all of `clouds` (on h->tgt's stream): bad[m] = points of clouds[m] that are not finite.
+// One small read-back; the points stay where they are.
+ndt_status gicp_finite_check(gicp_context* h, const std::vector<const DeviceCloud*>& clouds, std::vector<unsigned>& bad) {
+  const size_t m = clouds.size();
+  bad.assign(m, 0);
+  if (m == 0) return NDT_OK;
+  std::vector<gicp::FiniteMember> tab(m);
+  long long blocks = 0;
+  for (size_t i = 0; i < m; i++) {
+    tab[i].pts = clouds[i]->pts.p;
+    tab[i].n = static_cast<int>(clouds[i]->n);
+    tab[i].first_block = static_cast<int>(blocks);
+    blocks += gicp::finite_blocks(tab[i].n);
+  }
+  if (blocks > static_cast<long long>(std::numeric_limits<int>::max())) return fail(NDT_ERR_INVALID, "too many points in the named clouds");
+  hipStream_t st = h->tgt.stream;
+  HIP_TRY(h->member_table.reserve(m * sizeof(gicp::FiniteMember)));
+  HIP_TRY(h->finite_counts.reserve(m));
+  StreamDrain drain{st};  // `tab` is pageable: whatever path leaves, its copy has run before it dies
+  HIP_TRY(hipMemcpyAsync(h->member_table.p, tab.data(), m * sizeof(gicp::FiniteMember), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(h->finite_counts.p, 0, m * sizeof(unsigned), st));
+  HIP_TRY(gicp::launch_count_nonfinite_multi(reinterpret_cast<const gicp::FiniteMember*>(h->member_table.p), static_cast<int>(m),
+                                             static_cast<int>(blocks), h->finite_counts.p, st));
+  HIP_TRY(hipMemcpyAsync(bad.data(), h->finite_counts.p, m * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  drain.done = true;
+  return NDT_OK;
 }
 
 gicp::PointIndex gicp_index_of(const ndt_context* c) {
@@ -479,6 +554,269 @@ ndt_status gicp_set_input_source(gicp_handle h, const void* pts, size_t n, size_
   if (s) return s;
   HIP_TRY(hipStreamSynchronize(h->src.stream));  // the index is read from tgt's stream from here on
   h->have_src = true;
+  return NDT_OK;
+}
+
+// setInputTarget (which = 0) / setInputSource (1) from a resident cloud: finite check on the device, the index built over
+// the cloud where it lies
+static ndt_status gicp_set_input_cloud(gicp_handle h, int which, ndt_cloud cl) {
+  if (!h) return fail(NDT_ERR_INVALID, "null");
+  (which == 0 ? h->have_tgt : h->have_src) = false;
+  (which == 0 ? h->have_cov_tgt : h->have_cov_src) = false;
+  (which == 0 ? h->user_cov_tgt : h->user_cov_src) = false;
+  h->step_ready = false;
+  if (!cl || !cl->c || cl->c->n == 0) return fail(NDT_ERR_INVALID, "invalid or empty point cloud dataset given");
+  ndt_status s = ensure_device(&h->tgt);
+  if (s) return s;
+  HIP_TRY(hipStreamSynchronize(h->tgt.stream));  // kernels of an earlier align may still read the old index
+  s = cloud_use_on(&h->tgt, cl->c.get());  // (the source's points are read on the main stream too)
+  if (s) return s;
+  std::vector<unsigned> bad;
+  s = gicp_finite_check(h, {cl->c.get()}, bad);
+  if (s) return s;
+  if (bad[0]) return fail(NDT_ERR_INVALID, "GICP needs finite points (" + std::to_string(bad[0]) + " of the cloud's are not)");
+  ndt_context* c = which == 0 ? &h->tgt : &h->src;
+  if (which == 1) {
+    s = ensure_device(c);
+    if (!s) s = cloud_use_on(c, cl->c.get());
+    if (s) return s;
+  }
+  s = gicp_index_resident(c, cl->c, &h->hint_leaf[which], &h->hint_n[which]);
+  if (s) return s;
+  if (which == 1) HIP_TRY(hipStreamSynchronize(h->src.stream));  // the index is read from tgt's stream from here on
+  (which == 0 ? h->have_tgt : h->have_src) = true;
+  return NDT_OK;
+}
+ndt_status gicp_set_input_target_cloud(gicp_handle h, ndt_cloud c) { return gicp_set_input_cloud(h, 0, c); }
+ndt_status gicp_set_input_source_cloud(gicp_handle h, ndt_cloud c) { return gicp_set_input_cloud(h, 1, c); }
+
+// drops what the last pairs call kept (the buffers go back to the main stream's pool)
+static void gicp_pairs_drop(gicp_handle h) {
+  h->pairs_valid = false;
+  h->pairs_index_builds = h->pairs_knn_launches = h->pairs_knn_blocks = 0;
+  h->pairs_prepare_ms = h->pairs_register_ms = 0;
+  if (h->pairs_prepared.empty()) return;
+  if (h->tgt.device_ready) (void)ensure_device(&h->tgt);
+  h->pairs_prepared.clear();
+}
+
+ndt_status gicp_align_pairs_clouds(gicp_handle h, const ndt_cloud* clouds, size_t n_clouds, const int* pairs, size_t n_pairs,
+                                   const float* guesses, double max_range, float* final_T, int* converged, int* n_iterations,
+                                   int* correspondences, double* fitness) {
+  if (!h) return fail(NDT_ERR_INVALID, "null handle");
+  gicp_pairs_drop(h);
+  if (n_clouds && !clouds) return fail(NDT_ERR_INVALID, "null clouds");
+  if (n_pairs && !pairs) return fail(NDT_ERR_INVALID, "null pairs");
+  if (n_pairs > 65535) return fail(NDT_ERR_INVALID, "at most 65535 pairs per call");
+  for (size_t c = 0; c < n_clouds; c++)
+    if (!clouds[c] || !clouds[c]->c) return fail(NDT_ERR_INVALID, "null cloud (entry " + std::to_string(c) + ")");
+  for (size_t i = 0; i < 2 * n_pairs; i++)
+    if (pairs[i] < 0 || static_cast<size_t>(pairs[i]) >= n_clouds) return fail(NDT_ERR_INVALID, "pair names a cloud that does not exist");
+  const int k = h->prm.k_correspondences;
+  std::vector<int> named;  // in order of first use
+  {
+    std::vector<char> seen(n_clouds, 0);
+    for (size_t i = 0; i < 2 * n_pairs; i++)
+      if (!seen[pairs[i]]) {
+        seen[pairs[i]] = 1;
+        named.push_back(pairs[i]);
+      }
+  }
+  for (int c : named)
+    if (clouds[c]->c->n < static_cast<size_t>(k))  // gicp_omp_impl.hpp:53-57
+      return fail(NDT_ERR_INVALID, "number of points in cloud " + std::to_string(c) + " (" + std::to_string(clouds[c]->c->n) +
+                                       ") is less than k_correspondences_ (" + std::to_string(k) + ")");
+  if (n_pairs == 0) {
+    h->pairs_valid = true;
+    return NDT_OK;
+  }
+  ndt_status s = ensure_device(&h->tgt);
+  if (s) return s;
+  hipStream_t st = h->tgt.stream;
+  HIP_TRY(hipStreamSynchronize(st));
+  const auto t_begin = std::chrono::steady_clock::now();
+  auto t_prepared = t_begin;
+  // ---- every named cloud: stream order, then the finite check of all of them in one launch
+  std::vector<const DeviceCloud*> nc;
+  for (int c : named) {
+    s = cloud_use_on(&h->tgt, clouds[c]->c.get());
+    if (s) return s;
+    nc.push_back(clouds[c]->c.get());
+  }
+  std::vector<unsigned> bad;
+  s = gicp_finite_check(h, nc, bad);
+  if (s) return s;
+  for (size_t j = 0; j < named.size(); j++)
+    if (bad[j]) return fail(NDT_ERR_INVALID, "GICP needs finite points (" + std::to_string(bad[j]) + " of cloud " + std::to_string(named[j]) + " are not)");
+
+  // ---- from here on the handle's inputs are swapped for the prepared clouds; `keep` puts everything back
+  struct Keep {
+    gicp_context* h;
+    std::shared_ptr<DeviceCloud> tt, st;
+    std::shared_ptr<DeviceGrid> tg, sg;
+    float t_res, s_res;
+    bool have_tgt, have_src, have_cov_tgt, have_cov_src, user_cov_tgt, user_cov_src;
+    DevBuf<double> cov_tgt, cov_src;
+    float final_T[16], guess_rm[16];
+    int converged, nr_iterations, n_f, n_df, n_fdf, correspondences;
+    explicit Keep(gicp_context* c) : h(c), tt(c->tgt.target), st(c->src.target), tg(c->tgt.grid), sg(c->src.grid),
+                                     t_res(c->tgt.resolution), s_res(c->src.resolution), have_tgt(c->have_tgt), have_src(c->have_src),
+                                     have_cov_tgt(c->have_cov_tgt), have_cov_src(c->have_cov_src), user_cov_tgt(c->user_cov_tgt),
+                                     user_cov_src(c->user_cov_src), converged(c->converged), nr_iterations(c->nr_iterations),
+                                     n_f(c->n_f), n_df(c->n_df), n_fdf(c->n_fdf), correspondences(c->correspondences) {
+      cov_tgt.swap(c->cov_tgt);
+      cov_src.swap(c->cov_src);
+      std::memcpy(final_T, c->final_T, sizeof(final_T));
+      std::memcpy(guess_rm, c->guess_rm, sizeof(guess_rm));
+    }
+    ~Keep() {
+      h->tgt.target = tt; h->src.target = st; h->tgt.grid = tg; h->src.grid = sg;
+      h->tgt.resolution = t_res; h->src.resolution = s_res;
+      h->have_tgt = have_tgt; h->have_src = have_src; h->have_cov_tgt = have_cov_tgt; h->have_cov_src = have_cov_src;
+      h->user_cov_tgt = user_cov_tgt; h->user_cov_src = user_cov_src;
+      h->cov_tgt.borrow(nullptr, 0);  // (what the pairs borrowed is the prepared clouds')
+      h->cov_src.borrow(nullptr, 0);
+      h->cov_tgt.swap(cov_tgt);
+      h->cov_src.swap(cov_src);
+      std::memcpy(h->final_T, final_T, sizeof(final_T));
+      std::memcpy(h->guess_rm, guess_rm, sizeof(guess_rm));
+      h->converged = converged; h->nr_iterations = nr_iterations;
+      h->n_f = n_f; h->n_df = n_df; h->n_fdf = n_fdf; h->correspondences = correspondences;
+      h->step_ready = false;  // (the scratch of gicp_step_correspond has been used by the pairs)
+    }
+  };
+  std::vector<std::unique_ptr<gicp_context::Prepared>> prep(n_clouds);
+  std::vector<float> T_all(16 * n_pairs);
+  std::vector<int> conv_all(n_pairs), it_all(n_pairs), corr_all(n_pairs);
+  std::vector<double> fit_all(n_pairs);
+  size_t knn_launches = 0, knn_blocks = 0;
+  {
+    Keep keep(h);
+    // ---- one index per named cloud, the leaf of the previous one as the hint for the next (the builds are the handle's own
+    // path, one after the other, on the main stream)
+    float hint_leaf = 0.f;
+    size_t hint_n = 0;
+    for (int c : named) {
+      prep[c].reset(new gicp_context::Prepared());
+      prep[c]->cloud = clouds[c]->c;
+      s = gicp_index_resident(&h->tgt, clouds[c]->c, &hint_leaf, &hint_n);
+      if (s) return s;
+      prep[c]->grid = h->tgt.grid;
+      HIP_TRY(prep[c]->cov.reserve(clouds[c]->c->n * 6));
+    }
+    // ---- the covariances of all of them: one launch (members in order while their blocks stay within kGicpMultiMaxBlocks,
+    // then a further launch)
+    std::vector<gicp::KnnMember> tab(named.size());
+    std::vector<std::pair<size_t, size_t>> launches;  // [first member, end member)
+    {
+      size_t first = 0;
+      long long blocks = 0;
+      for (size_t j = 0; j < named.size(); j++) {
+        const gicp_context::Prepared& P = *prep[named[j]];
+        const int nb = gicp::knn_blocks(static_cast<int>(P.cloud->n), kGicpMaxBlocks);
+        if (blocks > 0 && blocks + nb > kGicpMultiMaxBlocks) {  // (a member is never split: alone it may exceed the limit)
+          launches.emplace_back(first, j);
+          first = j;
+          blocks = 0;
+        }
+        fill_point_index(P.grid.get(), tab[j].ix);
+        tab[j].cov6 = P.cov.p;
+        tab[j].first_block = static_cast<int>(blocks);
+        tab[j].n_blocks = nb;
+        blocks += nb;
+        knn_blocks += static_cast<size_t>(nb);
+      }
+      launches.emplace_back(first, named.size());
+    }
+    HIP_TRY(h->member_table.reserve(tab.size() * sizeof(gicp::KnnMember)));
+    StreamDrain drain{st};  // (a launch that fails returns with the table's copy waited for)
+    HIP_TRY(hipMemcpyAsync(h->member_table.p, tab.data(), tab.size() * sizeof(gicp::KnnMember), hipMemcpyHostToDevice, st));
+    for (const auto& l : launches) {
+      const gicp::KnnMember* d = reinterpret_cast<const gicp::KnnMember*>(h->member_table.p) + l.first;
+      const int nb = tab[l.second - 1].first_block + tab[l.second - 1].n_blocks;
+      HIP_TRY(gicp::launch_knn_covariances_multi(d, static_cast<int>(l.second - l.first), nb, k, h->prm.gicp_epsilon, st));
+      knn_launches++;
+    }
+    HIP_TRY(hipStreamSynchronize(st));  // (the table's host copy may go; a failed launch shows here, not in the first pair)
+    drain.done = true;
+    t_prepared = std::chrono::steady_clock::now();
+    // ---- the pairs, one after the other, through the handle's own outer loop
+    for (size_t p = 0; p < n_pairs; p++) {
+      gicp_context::Prepared& Pt = *prep[pairs[2 * p]];
+      gicp_context::Prepared& Ps = *prep[pairs[2 * p + 1]];
+      h->tgt.target = Pt.cloud; h->tgt.grid = Pt.grid; h->tgt.resolution = Pt.grid->resolution;
+      h->src.target = Ps.cloud; h->src.grid = Ps.grid; h->src.resolution = Ps.grid->resolution;
+      h->cov_tgt.borrow(Pt.cov.p, Pt.cloud->n * 6);
+      h->cov_src.borrow(Ps.cov.p, Ps.cloud->n * 6);
+      h->have_tgt = h->have_src = h->have_cov_tgt = h->have_cov_src = true;
+      h->user_cov_tgt = h->user_cov_src = false;
+      s = gicp_prepare(h, guesses ? guesses + 16 * p : nullptr);
+      if (s) return s;
+      GicpDevice dev(h);
+      const gicp::Result r = gicp::run(h->prm, h->guess_rm, dev);
+      dev.server_stop();
+      if (r.backend_failed || !dev.error.empty()) return fail(NDT_ERR_HIP, dev.error.empty() ? "device failure" : dev.error);
+      colmajor_from_rowmajor(r.final_T, &T_all[16 * p]);
+      conv_all[p] = r.converged ? 1 : 0;
+      it_all[p] = r.nr_iterations;
+      corr_all[p] = r.correspondences;
+      if (fitness) {
+        s = fitness_impl(&h->tgt, Ps.cloud->pts.p, static_cast<int>(Ps.cloud->n), &T_all[16 * p], max_range, &fit_all[p]);
+        if (s) return s;
+      }
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  if (final_T) std::memcpy(final_T, T_all.data(), T_all.size() * sizeof(float));
+  if (converged) std::memcpy(converged, conv_all.data(), n_pairs * sizeof(int));
+  if (n_iterations) std::memcpy(n_iterations, it_all.data(), n_pairs * sizeof(int));
+  if (correspondences) std::memcpy(correspondences, corr_all.data(), n_pairs * sizeof(int));
+  if (fitness) std::memcpy(fitness, fit_all.data(), n_pairs * sizeof(double));
+  h->pairs_prepared.swap(prep);
+  h->pairs_index_builds = named.size();
+  h->pairs_knn_launches = knn_launches;
+  h->pairs_knn_blocks = knn_blocks;
+  h->pairs_prepare_ms = std::chrono::duration<double, std::milli>(t_prepared - t_begin).count();
+  h->pairs_register_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_prepared).count();
+  h->pairs_valid = true;
+  return NDT_OK;
+}
+
+ndt_status gicp_pairs_covariances(gicp_handle h, size_t cloud, double* cov) {
+  if (!h || !cov) return fail(NDT_ERR_INVALID, "bad arguments");
+  if (!h->pairs_valid || cloud >= h->pairs_prepared.size() || !h->pairs_prepared[cloud])
+    return fail(NDT_ERR_NO_INPUT, "the last pairs call computed no covariances for this cloud");
+  ndt_status s = ensure_device(&h->tgt);
+  if (s) return s;
+  const gicp_context::Prepared& P = *h->pairs_prepared[cloud];
+  const size_t n = P.cloud->n;
+  std::vector<double> c6(n * 6);
+  HIP_TRY(hipMemcpyAsync(c6.data(), P.cov.p, n * 6 * sizeof(double), hipMemcpyDeviceToHost, h->tgt.stream));
+  HIP_TRY(hipStreamSynchronize(h->tgt.stream));
+  for (size_t i = 0; i < n; i++) {
+    const double* s6 = &c6[i * 6];
+    double* o = cov + i * 9;
+    o[0] = s6[0]; o[1] = s6[1]; o[2] = s6[2];
+    o[3] = s6[1]; o[4] = s6[3]; o[5] = s6[4];
+    o[6] = s6[2]; o[7] = s6[4]; o[8] = s6[5];
+  }
+  return NDT_OK;
+}
+
+ndt_status gicp_diag_pairs(gicp_handle h, size_t* index_builds, size_t* knn_launches, size_t* knn_blocks) {
+  if (!h) return fail(NDT_ERR_INVALID, "null");
+  if (!h->pairs_valid) return fail(NDT_ERR_NO_INPUT, "no successful pairs call on this handle");
+  if (index_builds) *index_builds = h->pairs_index_builds;
+  if (knn_launches) *knn_launches = h->pairs_knn_launches;
+  if (knn_blocks) *knn_blocks = h->pairs_knn_blocks;
+  return NDT_OK;
+}
+
+ndt_status gicp_diag_pairs_time(gicp_handle h, double* prepare_ms, double* register_ms) {
+  if (!h) return fail(NDT_ERR_INVALID, "null");
+  if (!h->pairs_valid) return fail(NDT_ERR_NO_INPUT, "no successful pairs call on this handle");
+  if (prepare_ms) *prepare_ms = h->pairs_prepare_ms;
+  if (register_ms) *register_ms = h->pairs_register_ms;
   return NDT_OK;
 }
 

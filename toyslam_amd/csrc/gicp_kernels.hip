@@ -3,6 +3,9 @@
 //   k_knn_covariances  computeCovariances (gicp_omp_impl.hpp:48-116): exact k nearest neighbours of
 //                      every point of a cloud among the cloud itself, the f64 covariance of those k
 //                      points, its eigenvectors, and the regularised covariance (1, 1, epsilon).
+//   k_knn_covariances_multi  the same for many clouds in one launch (gicp_align_pairs_clouds): a table of members, each
+//                      with blocks of its own; one per-block body shared with k_knn_covariances.
+//   k_count_nonfinite_multi  the finite check of many resident clouds in one launch.
 //   k_correspond       per outer iteration (:419-456): nearest target point of every transformed
 //                      source point, distance gate, Mahalanobis matrix (R C1 R^T + C2)^-1.
 //   k_functor          the BFGS objective / gradient sums (:241-368), one fused launch per evaluation.
@@ -33,9 +36,13 @@ __device__ __forceinline__ void matvec_eigen(const float* T12, float x, float y,
   oz = ((T12[8] * x + T12[9] * y) + T12[10] * z) + T12[11] * 1.0f;
 }
 
-__global__ __launch_bounds__(kKnnBlock) void k_knn_covariances(PointIndex ix, int k, double gicp_epsilon,
-                                                               double* __restrict__ cov6, int* __restrict__ nn_idx,
-                                                               float* __restrict__ nn_d2) {
+// The work of ONE block of a kNN / covariance grid, shared by k_knn_covariances (one cloud per launch) and
+// k_knn_covariances_multi (many clouds per launch): block `block` of the `n_blocks` that cut cloud `ix`, eight queries per
+// pass, strided by n_blocks.  Both kernels hand it the cloud and the block's place among the cloud's own blocks and nothing
+// else, so a cloud's covariances are the same bits whichever kernel computed them.
+__device__ __forceinline__ void knn_covariances_block(const PointIndex& ix, int k, double gicp_epsilon, int block, int n_blocks,
+                                                      double* __restrict__ cov6, int* __restrict__ nn_idx,
+                                                      float* __restrict__ nn_d2) {
 #pragma clang fp contract(off)
   // One candidate list PER TEAM (k entries, unordered, its worst entry tracked), not one per lane: an eighth of the
   // LDS (the per-lane lists capped the kernel at 3.5 waves per SIMD) and a bound every lane prunes with.  A candidate
@@ -53,7 +60,7 @@ __global__ __launch_bounds__(kKnnBlock) void k_knn_covariances(PointIndex ix, in
   const int r_max = max_shells(ix, r_lim);
   auto lds_fence = [] { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); };  // one wave per block: program order is enough
   // The loop is uniform across the wave (a team without a query idles): the scan of the isolated queries is wave-wide.
-  for (int base = blockIdx.x * kTeams; base < ix.n; base += gridDim.x * kTeams) {
+  for (int base = block * kTeams; base < ix.n; base += n_blocks * kTeams) {
     const int i = base + team;  // uniform within a team
     const bool live = i < ix.n;
     const float4 q = live ? ix.pts[i] : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -279,6 +286,61 @@ __global__ __launch_bounds__(kKnnBlock) void k_knn_covariances(PointIndex ix, in
       }
     for (int t = 0; t < 6; t++) cov6[static_cast<size_t>(i) * 6 + t] = out[t];
   }
+}
+
+__global__ __launch_bounds__(kKnnBlock) void k_knn_covariances(PointIndex ix, int k, double gicp_epsilon,
+                                                               double* __restrict__ cov6, int* __restrict__ nn_idx,
+                                                               float* __restrict__ nn_d2) {
+  knn_covariances_block(ix, k, gicp_epsilon, static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x), cov6, nn_idx, nn_d2);
+}
+
+// The covariances of MANY clouds from one launch (gicp_align_pairs_clouds).  members[m] owns the n_blocks consecutive blocks
+// from first_block on (ascending, no gaps: member m + 1 starts where m ends, the grid is their sum); a block finds its
+// member by bisection over first_block.  blockIdx.x and the table are the same for the whole wave, so the search and the
+// copy of the member's PointIndex are scalar loads and scalar compares: no lane searches, nothing diverges.  From there on
+// the block does what a block of k_knn_covariances does for that cloud alone (knn_covariances_block).
+__global__ __launch_bounds__(kKnnBlock) void k_knn_covariances_multi(const KnnMember* __restrict__ members, int n_members, int k,
+                                                                     double gicp_epsilon) {
+  const int b = static_cast<int>(blockIdx.x);
+  int lo = 0, hi = n_members - 1;  // the last member whose first_block <= b
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (members[mid].first_block <= b) lo = mid;
+    else hi = mid - 1;
+  }
+  const PointIndex ix = members[lo].ix;
+  const int local = b - members[lo].first_block, n_blocks = members[lo].n_blocks;
+  if (local >= n_blocks) return;  // (a grid larger than the table's blocks: nothing to do)
+  knn_covariances_block(ix, k, gicp_epsilon, local, n_blocks, members[lo].cov6, nullptr, nullptr);
+}
+
+// The finite check of many clouds in one launch: counts[m] += the points of member m with a NaN or an infinity among x, y, z.
+// Member m owns the blocks from first_block on, kFinitePointsPerBlock points each; found as above.  counts zeroed before.
+constexpr int kFiniteBlock = 256;
+__global__ __launch_bounds__(kFiniteBlock) void k_count_nonfinite_multi(const FiniteMember* __restrict__ members, int n_members,
+                                                                        unsigned* __restrict__ counts) {
+  const int b = static_cast<int>(blockIdx.x);
+  int lo = 0, hi = n_members - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (members[mid].first_block <= b) lo = mid;
+    else hi = mid - 1;
+  }
+  const float4* __restrict__ pts = members[lo].pts;
+  const int n = members[lo].n;
+  const long long first = static_cast<long long>(b - members[lo].first_block) * kFinitePointsPerBlock;
+  unsigned bad = 0;
+  for (int j = threadIdx.x; j < kFinitePointsPerBlock; j += kFiniteBlock) {
+    const long long i = first + j;
+    if (i >= n) break;
+    const float4 p = pts[i];
+    bad += (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) ? 0u : 1u;
+  }
+  const unsigned long long any = __ballot(bad != 0);
+  if (any == 0) return;
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) bad += __shfl_xor(bad, off, kWave);
+  if ((threadIdx.x & (kWave - 1)) == 0) atomicAdd(&counts[lo], bad);
 }
 
 __device__ __forceinline__ void load_sym(const double* __restrict__ c6, double C[3][3]) {
@@ -611,6 +673,24 @@ hipError_t launch_knn_covariances(const PointIndex& ix, int k, double gicp_epsil
   constexpr int kQueriesPerBlock = kKnnBlock / kTeam;
   const size_t lds = static_cast<size_t>(k) * kQueriesPerBlock * 12;  // per team: k distances, k positions, k ordered indices
   hipLaunchKernelGGL(k_knn_covariances, dim3(blocks), dim3(kKnnBlock), lds, stream, ix, k, gicp_epsilon, cov6, nn_idx, nn_d2);
+  return hipGetLastError();
+}
+
+hipError_t launch_knn_covariances_multi(const KnnMember* d_members, int n_members, int n_blocks, int k, double gicp_epsilon,
+                                        hipStream_t stream) {
+  if (k < 1 || k > kMaxK || n_members < 1 || n_blocks < 1 || !d_members) return hipErrorInvalidValue;
+  constexpr int kQueriesPerBlock = kKnnBlock / kTeam;
+  const size_t lds = static_cast<size_t>(k) * kQueriesPerBlock * 12;  // as launch_knn_covariances: the same k for every member
+  hipLaunchKernelGGL(k_knn_covariances_multi, dim3(n_blocks), dim3(kKnnBlock), lds, stream, d_members, n_members, k, gicp_epsilon);
+  return hipGetLastError();
+}
+
+int finite_blocks(int n) { return max(1, (n + kFinitePointsPerBlock - 1) / kFinitePointsPerBlock); }
+
+hipError_t launch_count_nonfinite_multi(const FiniteMember* d_members, int n_members, int n_blocks, unsigned* counts,
+                                        hipStream_t stream) {
+  if (n_members < 1 || n_blocks < 1 || !d_members || !counts) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_count_nonfinite_multi, dim3(n_blocks), dim3(kFiniteBlock), 0, stream, d_members, n_members, counts);
   return hipGetLastError();
 }
 

@@ -29,6 +29,36 @@ int server_blocks(int n, int max_blocks);
 hipError_t launch_knn_covariances(const PointIndex& ix, int k, double gicp_epsilon, int blocks, double* cov6, int* nn_idx,
                                   float* nn_d2, hipStream_t stream);
 
+// The same for many clouds in one launch (k_knn_covariances_multi): member m is cloud ix, gets knn_blocks(ix.n, cap) blocks
+// of its own -- n_blocks, the grid launch_knn_covariances would be given for it -- from first_block on, and writes cov6.
+// d_members: the table in device memory, first_block ascending from 0 without gaps; n_blocks of the launch = their sum.
+// Every member's cov6 is bit for bit what launch_knn_covariances(ix, k, eps, n_blocks, cov6, ...) writes.
+struct KnnMember {
+  PointIndex ix;
+  double* cov6 = nullptr;
+  int first_block = 0;
+  int n_blocks = 0;
+};
+// Blocks one k_knn_covariances_multi launch carries at most; the members beyond go to a further launch (a member is never
+// split: its blocks stride by its own count).  2^20 blocks of 8 queries are 8.4 M points per pass -- every sequence the
+// callers hold today is one launch -- and 16 members of knn_blocks' own limit (65536); the grid's x dimension would allow
+// 2^31, the bound is there so that one launch stays a bounded piece of work on a shared device.
+constexpr int kKnnMultiMaxBlocks = 1 << 20;
+hipError_t launch_knn_covariances_multi(const KnnMember* d_members, int n_members, int n_blocks, int k, double gicp_epsilon,
+                                        hipStream_t stream);
+
+// The finite check of many clouds in one launch (k_count_nonfinite_multi): counts[m] (zeroed by the caller) += the number of
+// points of member m with a NaN or an infinity in x, y or z.  Member m owns finite_blocks(n) blocks from first_block on.
+struct FiniteMember {
+  const float4* pts = nullptr;
+  int n = 0;
+  int first_block = 0;
+};
+constexpr int kFinitePointsPerBlock = 2048;
+int finite_blocks(int n);
+hipError_t launch_count_nonfinite_multi(const FiniteMember* d_members, int n_members, int n_blocks, unsigned* counts,
+                                        hipStream_t stream);
+
 // One outer iteration's correspondence step (:405-456): query = T * output[i]; corr[i] = nearest target
 // index if its squared distance < dist_threshold else -1; maha9[i] = (R C1 R^T + C2)^-1 as f32 (row-major).
 struct Rot3d {

@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
-from .ndt import _cloud, _colmajor, _d, _f, _from_colmajor, _i
+from .ndt import _cloud, _colmajor, _d, _f, _from_colmajor, _i, pairs_array
 
 
 class GeneralizedIterativeClosestPoint:
@@ -58,6 +58,63 @@ class GeneralizedIterativeClosestPoint:
         c = _cloud(cloud)
         check(self._L.gicp_set_input_source(self._h, c.ctypes.data, c.shape[0], c.strides[0]))
         self._n[1] = c.shape[0]
+
+    def setInputTargetCloud(self, dc):
+        """setInputTarget from a cloud resident in HBM (ndt.DeviceCloud: uploadCloud, voxelGridFilterCloud*, ...): by
+        reference, no download (gicp_set_input_target_cloud)."""
+        self._n[0] = 0
+        check(self._L.gicp_set_input_target_cloud(self._h, dc._c))
+        self._n[0] = len(dc)
+
+    def setInputSourceCloud(self, dc):
+        self._n[1] = 0
+        check(self._L.gicp_set_input_source_cloud(self._h, dc._c))
+        self._n[1] = len(dc)
+
+    def alignPairsClouds(self, clouds, pairs=None, guesses=None, max_range=None):
+        """GICP of (target, source) pairs of resident clouds (gicp_align_pairs_clouds): every named cloud indexed once, the
+        k-NN covariances of all of them from one launch, then one registration per pair with this handle's parameters.
+        clouds: list of ndt.DeviceCloud; pairs: (P, 2) cloud indices (target, source), None = the consecutive pairs (k-1, k);
+        guesses: one 4x4 per pair or None; max_range: getFitnessScore's, None = no limit.  Returns a dict with one entry per
+        pair: T (P, 4, 4), converged, iterations, correspondences, fitness."""
+        P = pairs_array(len(clouds), pairs)
+        n = P.shape[0]
+        g = None
+        if guesses is not None:
+            g = np.ascontiguousarray(np.stack([_colmajor(x) for x in guesses])) if n else np.zeros((1, 16), np.float32)
+            if n and g.shape[0] != n:
+                raise ValueError("one guess per pair")
+        m = max(n, 1)
+        T = np.zeros((m, 16), dtype=np.float32)
+        conv, it, corr = (np.zeros(m, dtype=np.int32) for _ in range(3))
+        fit = np.zeros(m, dtype=np.float64)
+        arr = (C.c_void_p * max(len(clouds), 1))(*[c._c for c in clouds])
+        check(self._L.gicp_align_pairs_clouds(self._h, arr, len(clouds), _i(P) if n else None, n, _f(g) if g is not None else None,
+                                              float(np.finfo(np.float64).max if max_range is None else max_range), _f(T),
+                                              _i(conv), _i(it), _i(corr), _d(fit)))
+        self._pairs_n = {i: len(clouds[i]) for i in set(P.reshape(-1).tolist())}
+        return dict(T=np.stack([_from_colmajor(T[k]) for k in range(n)]) if n else np.zeros((0, 4, 4), np.float32),
+                    converged=conv[:n].astype(bool), iterations=it[:n].copy(), correspondences=corr[:n].copy(),
+                    fitness=fit[:n].copy())
+
+    def pairsCovariances(self, c):
+        """The k-NN covariances the last alignPairsClouds computed for cloud c: (n, 3, 3) (gicp_pairs_covariances)."""
+        n = getattr(self, "_pairs_n", {}).get(int(c), 0)
+        cov = np.zeros((max(n, 1), 3, 3))
+        check(self._L.gicp_pairs_covariances(self._h, int(c), _d(cov)))
+        return cov[:n]
+
+    def diagPairs(self):
+        """What the last alignPairsClouds did: dict of index_builds, knn_launches, knn_blocks (gicp_diag_pairs)."""
+        a = [C.c_size_t(0) for _ in range(3)]
+        check(self._L.gicp_diag_pairs(self._h, *[C.byref(x) for x in a]))
+        return dict(index_builds=a[0].value, knn_launches=a[1].value, knn_blocks=a[2].value)
+
+    def pairsTime(self):
+        """Host wall clock of the last alignPairsClouds' two halves: dict of prepare_ms, register_ms (gicp_diag_pairs_time)."""
+        a, b = C.c_double(0.0), C.c_double(0.0)
+        check(self._L.gicp_diag_pairs_time(self._h, C.byref(a), C.byref(b)))
+        return dict(prepare_ms=a.value, register_ms=b.value)
 
     def setSourceCovariances(self, cov):
         """gicp_omp.h:165-168.  cov: (n, 3, 3) symmetric matrices, one per source point; None clears them."""
