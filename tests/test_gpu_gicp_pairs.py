@@ -260,6 +260,7 @@ def test_pairs_call_matches_the_oracle(gmod, up, scene, oracle, case):
 
 # ------------------------------------------------------------------ 5. handle state
 def test_pairs_call_leaves_the_handle_as_it_was(gmod, up, scene, five):
+    from toyslam_amd import _lib
     tgt, src = scene[0][:6000], scene[1][:2500]
     rng = np.random.default_rng(5)
 
@@ -274,10 +275,17 @@ def test_pairs_call_leaves_the_handle_as_it_was(gmod, up, scene, five):
     g.setTargetCovariances(ct)
     g.setSourceCovariances(cs)
     g.align(GUESS)
-    before = (g.getFinalTransformation(), g.hasConverged(), g.getFinalNumIteration(), g.stats(), g.covariances(0), g.covariances(1))
-    r = g.alignPairsClouds([up.uploadCloud(c) for c in five], PAIRS[:3], max_range=1.0)
+
+    def state():   # (the fitness score reads the handle's own target index and source cloud)
+        return (g.getFinalTransformation(), g.hasConverged(), g.getFinalNumIteration(), g.stats(), g.covariances(0), g.covariances(1),
+                g.getFitnessScore(1.0))
+
+    before = state()
+    dcs = [up.uploadCloud(c) for c in five]
+    r = g.alignPairsClouds(dcs, PAIRS[:3], max_range=1.0)
     assert r["T"].shape == (3, 4, 4) and not np.array_equal(r["T"][0], before[0])
-    after = (g.getFinalTransformation(), g.hasConverged(), g.getFinalNumIteration(), g.stats(), g.covariances(0), g.covariances(1))
+    after = state()
+    assert np.isfinite(before[6]) and before[6] > 0
     for x, y in zip(before, after):
         assert np.array_equal(x, y) if isinstance(x, np.ndarray) else x == y
     g.align(GUESS)
@@ -285,6 +293,49 @@ def test_pairs_call_leaves_the_handle_as_it_was(gmod, up, scene, five):
     # ... and the pairs call did not use the handle's supplied covariances: pair 0 is a fresh handle's
     assert GUESSES[0] is None
     same_as_fresh(r, 0, fresh_pairs(gmod, five, "defaults")[0], "pair 0 after a used handle")
+    # the one thing a pairs call may invalidate is the scratch of step_correspond: step_functor wants a new step
+    x = np.array([0.1, -0.2, 0.05, 0.01, -0.02, 0.03])
+    g.step_correspond(GUESS)
+    f0, g0 = g.step_functor(2, x)
+    g.alignPairsClouds(dcs, PAIRS[:3], max_range=1.0)
+    with pytest.raises(_lib.NdtError) as e:
+        g.step_functor(2, x)
+    assert e.value.status == _lib.NDT_ERR_NO_INPUT
+    g.step_correspond(GUESS)
+    f1, g1 = g.step_functor(2, x)
+    assert np.isfinite(f0) and f1 == f0 and np.array_equal(g1, g0)
+    # a handle whose covariances are its own k-NN ones: the source's, with their neighbour lists, around a pairs call
+    h = gmod.GeneralizedIterativeClosestPoint()
+    h.setInputTarget(tgt)
+    h.setInputSource(src)
+    nb_before = h.covariances(1, neighbors=True)
+    h.alignPairsClouds(dcs, PAIRS[:3], max_range=1.0)
+    nb_after = h.covariances(1, neighbors=True)
+    assert len(nb_before) == len(nb_after) == 3 and nb_before[0].shape == (len(src), 3, 3)
+    for x, y in zip(nb_before, nb_after):
+        assert np.array_equal(x, y)
+
+
+def test_inputs_set_around_a_pairs_call(gmod, up, five):
+    """One handle: the target set from host memory, a pairs call over all five clouds, the source set from a resident cloud,
+    align -- what a fresh handle given the two inputs and no pairs call gives; and a further pairs call computes the
+    covariances the first one did."""
+    dcs = [up.uploadCloud(c) for c in five]
+    g = gmod.GeneralizedIterativeClosestPoint()
+    g.setInputTarget(five[3])
+    g.alignPairsClouds(dcs, PAIRS, max_range=1.0)
+    cov0 = g.pairsCovariances(0)
+    g.setInputSourceCloud(dcs[4])
+    g.align()
+    f = gmod.GeneralizedIterativeClosestPoint()
+    f.setInputTarget(five[3])
+    f.setInputSource(five[4])
+    f.align()
+    assert np.array_equal(g.getFinalTransformation(), f.getFinalTransformation())
+    assert g.getFinalNumIteration() == f.getFinalNumIteration() > 0 and g.hasConverged() == f.hasConverged()
+    assert g.stats() == f.stats() and g.getFitnessScore(1.0) == f.getFitnessScore(1.0)
+    g.alignPairsClouds(dcs, PAIRS, max_range=1.0)
+    assert cov0.shape == (len(five[0]), 3, 3) and np.array_equal(g.pairsCovariances(0), cov0)
 
 
 # ------------------------------------------------------------------ 6. refusals on the device

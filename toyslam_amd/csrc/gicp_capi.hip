@@ -2,24 +2,35 @@
 // cloud upload and K1 grid build (ndt_internal.hpp) -- the
 // voxel index K1 produces over a cloud is the search structure of GICP's nearest-neighbour queries.
 //
-// A gicp_context owns two ndt_contexts used purely as index holders: `tgt` (the GICP target as its
-// target cloud + grid) and `src` (the GICP *source* as ITS target cloud + grid, for the source's own
-// k-NN covariances).  All GICP kernels run on tgt's stream.
+// One input of a registration is a GicpInput: a cloud's search index (which holds the cloud), its packed covariances and
+// where they came from.  The handle's own target and source are two of them (in[0], in[1]), the clouds a pairs call
+// prepares are more of them, and a registration (gicp_register, gicp_prepare, GicpDevice) is a function of two of them --
+// its parameters, streams and scratch are the handle's.  The two ndt_contexts a gicp_context owns are tools, not state:
+// `tgt` is the main stream (all GICP kernels run on it) and the builder of every index but the handle's source's, `src`
+// builds that one and runs its k-NN covariances next to the target's.  Neither keeps a cloud or a grid between calls.
 #include "ndt_internal.hpp"
 
-namespace {
+struct LeafHint {  // consecutive clouds have about the same density: the index leaf the previous one ended up with, and its size
+  float leaf = 0.f;
+  size_t n = 0;
+};
 
-struct GicpDevice;
-
-}  // namespace
+struct GicpInput {
+  std::shared_ptr<DeviceGrid> grid;  // the search index; grid->target is the cloud
+  DevBuf<double> cov;                // [n][6]
+  bool have_cov = false;
+  bool user_cov = false;  // supplied through gicp_set_*_covariances
+  // the setters' side: the input has been set (a pairs call's record: the cloud was named), the leaf chain of this slot
+  bool set = false;
+  LeafHint hint;
+  const DeviceCloud& cloud() const { return *grid->target; }
+  size_t n() const { return grid->target->n; }
+};
 
 struct gicp_context {
-  ndt_context tgt, src;
+  ndt_context tgt, src;  // first: every device buffer below goes back to the pool before these two destroy their streams
   gicp::Params prm;
-  bool have_tgt = false, have_src = false;
-  bool have_cov_tgt = false, have_cov_src = false;
-  bool user_cov_tgt = false, user_cov_src = false;  // supplied through gicp_set_*_covariances
-  DevBuf<double> cov_tgt, cov_src;  // [n][6]
+  GicpInput in[2];                  // target, source
   DevBuf<float4> output;            // the source moved by the guess
   DevBuf<int> corr;
   DevBuf<float> maha;
@@ -39,45 +50,39 @@ struct gicp_context {
   DevBuf<unsigned> srv_counter;
   int srv_blocks = 0;
   bool src_cov_pending = false;
-  float hint_leaf[2] = {0.f, 0.f};  // index leaf the previous target / source ended up with, and its size
-  size_t hint_n[2] = {0, 0};
-  hipEvent_t ev_src = nullptr;  // the source's covariance pass (on the source index's stream) -> the main stream
+  hipEvent_t ev_src = nullptr;  // the source's covariance pass (on src's stream) -> the main stream
   size_t out_pinned_bytes = 0;
   unsigned long long seq = 0;
-  float guess_rm[16];          // guess of the current align / step, row-major
   bool step_ready = false;
-  // gicp_align_pairs_clouds: what the last successful call prepared for every cloud a pair named (null for the others) --
-  // the cloud, its search index, its k-NN covariances [n][6] -- and what it launched (gicp_pairs_covariances, gicp_diag_pairs)
-  struct Prepared {
-    std::shared_ptr<DeviceCloud> cloud;
-    std::shared_ptr<DeviceGrid> grid;
-    DevBuf<double> cov;
-  };
-  std::vector<std::unique_ptr<Prepared>> pairs_prepared;
+  // gicp_align_pairs_clouds: what the last successful call prepared for every cloud (`set`: a pair named it), and what it
+  // launched (gicp_pairs_covariances, gicp_diag_pairs)
+  std::vector<GicpInput> pairs_prepared;
   bool pairs_valid = false;
   size_t pairs_index_builds = 0, pairs_knn_launches = 0, pairs_knn_blocks = 0;
   double pairs_prepare_ms = 0, pairs_register_ms = 0;  // host wall clock of the call's two halves (tools/time_gicp_pairs.py)
   DevBuf<unsigned char> member_table;  // the member tables of the finite check and of k_knn_covariances_multi
   DevBuf<unsigned> finite_counts;
-  // results
+  // the last gicp_align's result
+  gicp::Result result;
   float final_T[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // column-major
-  int converged = 0, nr_iterations = 0, n_f = 0, n_df = 0, n_fdf = 0, correspondences = 0;
 
+  ndt_context* builder(int which) { return which == 0 ? &tgt : &src; }
+
+  // Nothing may still run when the buffers go: both streams are waited for.  The inputs, the pairs records and the scratch
+  // are members, released after this body in reverse order of declaration -- into the main stream's pool, which tgt's
+  // destructor then empties -- so nothing is listed here but what is not a DevBuf.
   ~gicp_context() {
-    if (tgt.device_ready) {
-      (void)hipSetDevice(tgt.device);
-      (void)hipStreamSynchronize(tgt.stream);
-      tls_pool_stream = tgt.stream;
-    }
-    pairs_prepared.clear(); member_table.release(); finite_counts.release();
-    cov_tgt.release(); cov_src.release(); output.release(); corr.release(); maha.release(); partials.release();
-    counter.release(); out_cloud.release(); nn_idx.release(); nn_d2.release();
+    for (ndt_context* c : {&src, &tgt})
+      if (c->device_ready) {
+        (void)hipSetDevice(c->device);
+        (void)hipStreamSynchronize(c->stream);
+        tls_pool_stream = c->stream;
+      }
     if (host_pub) (void)hipHostFree(host_pub);
     if (out_pinned) (void)hipHostFree(out_pinned);
     if (ev_src) (void)hipEventDestroy(ev_src);
     if (srv_mbs) (void)hipFree(srv_mbs);
     if (srv_rows) (void)hipHostFree(srv_rows);
-    srv_counter.release();
   }
 };
 
@@ -95,20 +100,27 @@ static const int kGicpMultiMaxBlocks = std::getenv("NDT_GICP_MULTI_MAX_BLOCKS") 
                                                                                 : gicp::kKnnMultiMaxBlocks;
 constexpr long long kGicpMaxCells = 1ll << 26;       // dense cell table budget (256 MB of int)
 
-// Builds the voxel index of the cloud c->target (on the device, every point finite, inside the box mn .. mx) on `c`: leaf
-// size from the cloud's own density (volume guess first, then corrected once from the measured points per occupied cell --
-// scans are surfaces, so occupancy grows with the square of the leaf).
-ndt_status gicp_index_cloud(ndt_context* c, const double mn[3], const double mx[3], float* hint_leaf, size_t* hint_n) {
+// The voxel index of `cloud` (on the device, every point finite -- so the box the cloud carries over its finite points is
+// the box of all of them) into in.grid: leaf size from the cloud's own density (volume guess first, then corrected once
+// from the measured points per occupied cell -- scans are surfaces, so occupancy grows with the square of the leaf).
+// Built with `c`: its stream, its scratch, its pool (the caller has made `c` current).  `c` is handed the cloud for the
+// build alone and keeps neither it nor the grid.
+ndt_status gicp_index_cloud(ndt_context* c, const std::shared_ptr<DeviceCloud>& cloud, LeafHint& hint, GicpInput& in) {
+  struct Lend {
+    ndt_context* c;
+    ~Lend() { c->grid.reset(); c->target.reset(); }
+  } lend{c};
+  in.grid.reset();  // (before the new one is allocated: an input never holds two)
+  c->target = cloud;
   c->target_dense = 1;
   c->min_pts = 1;
   c->index_only = true;
-  const size_t n = c->target->n;
+  const size_t n = cloud->n;
   ndt_status s = NDT_OK;
-  double ext[3], vol = 1.0, ext_max = 0.0;
+  double ext[3], vol = 1.0;
   for (int k = 0; k < 3; k++) {
-    ext[k] = std::max(mx[k] - mn[k], 1e-3);
+    ext[k] = std::max(static_cast<double>(cloud->bb_max[1][k]) - static_cast<double>(cloud->bb_min[1][k]), 1e-3);
     vol *= ext[k];
-    ext_max = std::max(ext_max, ext[k]);
   }
   auto clamp_leaf = [&](double leaf) {
     leaf = std::max(leaf, 1e-4);
@@ -120,9 +132,9 @@ ndt_status gicp_index_cloud(ndt_context* c, const double mn[3], const double mx[
     return static_cast<float>(leaf);
   };
   float leaf = clamp_leaf(std::cbrt(vol * kGicpPointsPerCell / static_cast<double>(n)));
-  // consecutive scans of a sequence have about the same density: start from the leaf the previous cloud of about this size
-  // ended up with (usually right at once; the search results do not depend on the leaf, only the time does)
-  if (*hint_leaf > 0 && n >= *hint_n - *hint_n / 4 && n <= *hint_n + *hint_n / 4) leaf = clamp_leaf(*hint_leaf);
+  // start from the leaf the previous cloud of about this size ended up with (usually right at once; the search results do
+  // not depend on the leaf, only the time does)
+  if (hint.leaf > 0 && n >= hint.n - hint.n / 4 && n <= hint.n + hint.n / 4) leaf = clamp_leaf(hint.leaf);
   for (int pass = 0; pass < 4; pass++) {
     c->resolution = leaf;
     s = build_grid(c);
@@ -139,44 +151,30 @@ ndt_status gicp_index_cloud(ndt_context* c, const double mn[3], const double mx[
   if (std::getenv("NDT_GICP_DEBUG"))
     std::fprintf(stderr, "[gicp index] n=%zu leaf=%.4f cells=%lld (%d x %d x %d) occupied=%zu\n", n, static_cast<double>(leaf),
                  c->grid->geom.n_cells, c->grid->geom.div_b[0], c->grid->geom.div_b[1], c->grid->geom.div_b[2], c->grid->n_leaves);
-  *hint_leaf = leaf;
-  *hint_n = n;
-  return ensure_cell2leaf(c, c->grid.get());
+  hint.leaf = leaf;
+  hint.n = n;
+  s = ensure_cell2leaf(c, c->grid.get());
+  if (!s) in.grid = std::move(c->grid);
+  return s;
 }
 
-// The index of a host cloud on `c`: finite check and bounding box on the host, upload, gicp_index_cloud.
-ndt_status gicp_build_index(ndt_context* c, const void* pts, size_t n, size_t stride, float* hint_leaf, size_t* hint_n) {
+// The index of a host cloud: finite check on the host, upload (which computes the box), gicp_index_cloud.
+ndt_status gicp_build_index(ndt_context* c, const void* pts, size_t n, size_t stride, LeafHint& hint, GicpInput& in) {
   if (!pts || n == 0) return fail(NDT_ERR_INVALID, "invalid or empty point cloud dataset given");
   if (stride < 12 || stride % 4) return fail(NDT_ERR_INVALID, "stride_bytes must be a multiple of 4 and >= 12");
-  double mn[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, mx[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
   const unsigned char* base = static_cast<const unsigned char*>(pts);
   for (size_t i = 0; i < n; i++) {
     float p[3];
     std::memcpy(p, base + i * stride, sizeof(p));
     if (!(std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2])))
       return fail(NDT_ERR_INVALID, "GICP needs finite points (point " + std::to_string(i) + " is not)");
-    for (int k = 0; k < 3; k++) {
-      mn[k] = std::min(mn[k], static_cast<double>(p[k]));
-      mx[k] = std::max(mx[k], static_cast<double>(p[k]));
-    }
   }
   ndt_status s = ensure_device(c);
   if (s) return s;
-  s = upload_cloud(c, pts, n, stride, false, c->target);
+  std::shared_ptr<DeviceCloud> cloud;
+  s = upload_cloud(c, pts, n, stride, false, cloud);
   if (s) return s;
-  return gicp_index_cloud(c, mn, mx, hint_leaf, hint_n);
-}
-
-// The index of a cloud resident in HBM (an ndt_cloud whose points passed gicp_finite_check) on `c`: the box the cloud
-// carries (computed when it was made) takes the place of the host loop, nothing is copied.
-ndt_status gicp_index_resident(ndt_context* c, const std::shared_ptr<DeviceCloud>& cloud, float* hint_leaf, size_t* hint_n) {
-  double mn[3], mx[3];
-  for (int k = 0; k < 3; k++) {  // (every point finite: the box of the non-NaN points and that of the finite ones are one)
-    mn[k] = static_cast<double>(cloud->bb_min[1][k]);
-    mx[k] = static_cast<double>(cloud->bb_max[1][k]);
-  }
-  c->target = cloud;
-  return gicp_index_cloud(c, mn, mx, hint_leaf, hint_n);
+  return gicp_index_cloud(c, cloud, hint, in);
 }
 
 // An asynchronous copy from pageable host memory is queued on `s`: unless the success path has synchronised already
@@ -217,9 +215,9 @@ ndt_status gicp_finite_check(gicp_context* h, const std::vector<const DeviceClou
   return NDT_OK;
 }
 
-gicp::PointIndex gicp_index_of(const ndt_context* c) {
+gicp::PointIndex gicp_index_of(const GicpInput& in) {
   gicp::PointIndex ix;
-  fill_point_index(c->grid.get(), ix);
+  fill_point_index(in.grid.get(), ix);
   return ix;
 }
 
@@ -232,10 +230,42 @@ void colmajor_from_rowmajor(const float* rm, float* cm) {
     for (int c = 0; c < 4; c++) cm[c * 4 + r] = rm[r * 4 + c];
 }
 
-ndt_status gicp_ready(gicp_context* h) {
-  if (!h->have_tgt) return fail(NDT_ERR_NO_INPUT, "no target cloud set");
-  if (!h->have_src) return fail(NDT_ERR_NO_INPUT, "no source cloud set");
-  ndt_status s = ensure_device(&h->tgt);  // current device + this thread's pool stream
+// packed covariances [n][6] (the upper triangle, row by row) <-> [n][9] row-major 3x3
+void cov9_from_cov6(const double* c6, size_t n, double* c9) {
+  for (size_t i = 0; i < n; i++) {
+    const double* s6 = c6 + i * 6;
+    double* o = c9 + i * 9;
+    o[0] = s6[0]; o[1] = s6[1]; o[2] = s6[2];
+    o[3] = s6[1]; o[4] = s6[3]; o[5] = s6[4];
+    o[6] = s6[2]; o[7] = s6[4]; o[8] = s6[5];
+  }
+}
+void cov6_from_cov9(const double* c9, size_t n, double* c6) {
+  for (size_t i = 0; i < n; i++) {
+    const double* m = c9 + i * 9;
+    double* o = c6 + i * 6;
+    o[0] = m[0]; o[1] = m[1]; o[2] = m[2]; o[3] = m[4]; o[4] = m[5]; o[5] = m[8];
+  }
+}
+
+// what every input setter starts with: the input is not set (and stays so if the setter fails), its covariances are gone
+// (target_covariances_.reset() / input_covariances_.reset())
+GicpInput& gicp_unset(gicp_context* h, int which) {
+  GicpInput& in = h->in[which];
+  in.set = in.have_cov = in.user_cov = false;
+  h->step_ready = false;
+  return in;
+}
+
+ndt_status gicp_inputs_set(const gicp_context* h) {
+  if (!h->in[0].set) return fail(NDT_ERR_NO_INPUT, "no target cloud set");
+  if (!h->in[1].set) return fail(NDT_ERR_NO_INPUT, "no source cloud set");
+  return NDT_OK;
+}
+
+// the main stream current (device, this thread's pool stream) and the scratch every evaluation needs
+ndt_status gicp_scratch(gicp_context* h) {
+  ndt_status s = ensure_device(&h->tgt);
   if (s) return s;
   if (!h->host_pub) {
     HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->host_pub), ndt::kPublishSlots * sizeof(double), hipHostMallocDefault));
@@ -248,33 +278,30 @@ ndt_status gicp_ready(gicp_context* h) {
   return NDT_OK;
 }
 
-// computeCovariances of one cloud (lazily, gicp_omp_impl.hpp:385-397)
-ndt_status gicp_cloud_covariances(gicp_context* h, int which, bool want_neighbors) {
-  ndt_context* c = which == 0 ? &h->tgt : &h->src;
-  DevBuf<double>& cov = which == 0 ? h->cov_tgt : h->cov_src;
-  bool& have = which == 0 ? h->have_cov_tgt : h->have_cov_src;
-  if (have && !want_neighbors) return NDT_OK;
-  const size_t n = c->target->n;
+// computeCovariances of one cloud (lazily, gicp_omp_impl.hpp:385-397).  on_src_stream: the handle's source, whose pass runs
+// on the stream its index was built on, next to the target's (two independent kernels of a few thousand waves each);
+// everything that follows on the main stream waits for it through an event (gicp_join_source)
+ndt_status gicp_cloud_covariances(gicp_context* h, GicpInput& in, bool on_src_stream, bool want_neighbors) {
+  if (in.have_cov && !want_neighbors) return NDT_OK;
+  const size_t n = in.n();
   const int k = h->prm.k_correspondences;
   if (k > static_cast<int>(n))  // :53-57: PCL_ERROR and return, the covariances stay empty
     return fail(NDT_ERR_INVALID, "number of points in cloud (" + std::to_string(n) + ") is less than k_correspondences_ (" +
                                      std::to_string(k) + ")");
-  HIP_TRY(cov.reserve(n * 6));
+  HIP_TRY(in.cov.reserve(n * 6));
   if (want_neighbors) {
     HIP_TRY(h->nn_idx.reserve(n * static_cast<size_t>(k)));
     HIP_TRY(h->nn_d2.reserve(n * static_cast<size_t>(k)));
   }
-  // the source's pass runs on the source index's own stream, next to the target's (two independent kernels of a few
-  // thousand waves each); everything that follows on the main stream waits for it through an event
-  hipStream_t st = (which == 1) ? h->src.stream : h->tgt.stream;
-  HIP_TRY(gicp::launch_knn_covariances(gicp_index_of(c), k, h->prm.gicp_epsilon, gicp::knn_blocks(static_cast<int>(n), kGicpMaxBlocks),
-                                       cov.p, want_neighbors ? h->nn_idx.p : nullptr, want_neighbors ? h->nn_d2.p : nullptr, st));
-  if (which == 1) {
+  hipStream_t st = on_src_stream ? h->src.stream : h->tgt.stream;
+  HIP_TRY(gicp::launch_knn_covariances(gicp_index_of(in), k, h->prm.gicp_epsilon, gicp::knn_blocks(static_cast<int>(n), kGicpMaxBlocks),
+                                       in.cov.p, want_neighbors ? h->nn_idx.p : nullptr, want_neighbors ? h->nn_d2.p : nullptr, st));
+  if (on_src_stream) {
     if (!h->ev_src) HIP_TRY(hipEventCreateWithFlags(&h->ev_src, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(h->ev_src, h->src.stream));
     h->src_cov_pending = true;  // gicp_join_source makes the main stream wait -- after the target's pass has been queued
   }
-  have = true;
+  in.have_cov = true;
   return NDT_OK;
 }
 
@@ -286,29 +313,43 @@ ndt_status gicp_join_source(gicp_context* h) {
   return NDT_OK;
 }
 
-// covariances of both clouds + the guess-moved source (:385-403)
-ndt_status gicp_prepare(gicp_context* h, const float* guess_cm) {
-  ndt_status s = gicp_ready(h);
+// the covariances of `in` to the host as [n][9], behind everything queued on the main stream, which is waited for
+ndt_status gicp_read_covariances(gicp_context* h, const GicpInput& in, double* cov9) {
+  const size_t n = in.n();
+  std::vector<double> c6(n * 6);
+  HIP_TRY(hipMemcpyAsync(c6.data(), in.cov.p, n * 6 * sizeof(double), hipMemcpyDeviceToHost, h->tgt.stream));
+  HIP_TRY(hipStreamSynchronize(h->tgt.stream));
+  cov9_from_cov6(c6.data(), n, cov9);
+  return NDT_OK;
+}
+
+// covariances of both clouds + the guess-moved source (:385-403); guess_rm: the guess, row-major.  An input that has its
+// covariances (every record of a pairs call) launches nothing here: only the handle's own source ever uses src's stream.
+ndt_status gicp_prepare(gicp_context* h, GicpInput& tgt, GicpInput& src, const float* guess_cm, float guess_rm[16]) {
+  ndt_status s = gicp_scratch(h);
   if (s) return s;
-  s = gicp_cloud_covariances(h, 1, false);  // (source first: it runs on its own stream while the target's is queued here)
+  s = gicp_cloud_covariances(h, src, true, false);  // (source first: it runs on its own stream while the target's is queued here)
   if (s) return s;
-  s = gicp_cloud_covariances(h, 0, false);
+  s = gicp_cloud_covariances(h, tgt, false, false);
   if (s) return s;
   s = gicp_join_source(h);
   if (s) return s;
-  const size_t n = h->src.target->n;
-  rowmajor_from_colmajor(guess_cm, h->guess_rm);
+  const size_t n = src.n();
+  rowmajor_from_colmajor(guess_cm, guess_rm);
   HIP_TRY(h->output.reserve(n));
   HIP_TRY(h->corr.reserve(n));
   HIP_TRY(h->maha.reserve(n * 9));
   HIP_TRY(h->partials.reserve(static_cast<size_t>(gicp::kFunctorMaxBlocks) * ndt::kEvalStride));
   // pcl::transformPointCloud(output, output, guess), :403
-  HIP_TRY(ndt::launch_transform(h->src.target->pts.p, static_cast<int>(n), h->guess_rm, h->output.p, h->tgt.stream));
+  HIP_TRY(ndt::launch_transform(src.cloud().pts.p, static_cast<int>(n), guess_rm, h->output.p, h->tgt.stream));
   return NDT_OK;
 }
 
+// The device side of one registration of `src` onto `tgt`, with h's parameters, main stream and scratch.
 struct GicpDevice : gicp::Backend {
   gicp_context* h;
+  const GicpInput& tgt;
+  const GicpInput& src;
   std::string error;
   // The line search evaluates operator() and then, if the step passes Fletcher's rho test, df at the very same
   // point (gicp_driver.cpp line_search): the operator() launch also accumulates df's sums, and the df request that
@@ -318,7 +359,7 @@ struct GicpDevice : gicp::Backend {
   bool have_grad = false;
   float grad_T[16];
   gicp::FunctorSums grad_sums;
-  explicit GicpDevice(gicp_context* ctx) : h(ctx) {}
+  GicpDevice(gicp_context* ctx, const GicpInput& target, const GicpInput& source) : h(ctx), tgt(target), src(source) {}
 
   bool correspond(const float transformation[16], const double R[9]) override {
     gicp::Rot3d rot;
@@ -326,10 +367,9 @@ struct GicpDevice : gicp::Backend {
     have_grad = false;
     server_stop();  // the correspondences change: the next BFGS run gets a fresh server behind this kernel
     const double thr = h->prm.corr_dist_threshold * h->prm.corr_dist_threshold;  // :401
-    const int n = static_cast<int>(h->src.target->n);
-    const hipError_t e = gicp::launch_correspond(h->output.p, n, transformation, rot, gicp_index_of(&h->tgt), h->cov_src.p,
-                                                 h->cov_tgt.p, thr, gicp::correspond_blocks(n, kGicpMaxBlocks), h->corr.p,
-                                                 h->maha.p, h->tgt.stream);
+    const int n = static_cast<int>(src.n());
+    const hipError_t e = gicp::launch_correspond(h->output.p, n, transformation, rot, gicp_index_of(tgt), src.cov.p, tgt.cov.p, thr,
+                                                 gicp::correspond_blocks(n, kGicpMaxBlocks), h->corr.p, h->maha.p, h->tgt.stream);
     if (e != hipSuccess) {
       error = std::string("correspondence kernel: ") + hipGetErrorString(e);
       return false;
@@ -367,12 +407,12 @@ struct GicpDevice : gicp::Backend {
     server_mark(&h->tgt, true);  // this device's turn among the persistent kernels of the process
     h->srv_flip ^= 1;
     ndt::server_reset_mailbox(mailbox());
-    const int n = static_cast<int>(h->src.target->n);
+    const int n = static_cast<int>(src.n());
     h->srv_blocks = gicp::server_blocks(n, kGicpMaxBlocks);
     hipError_t e = hipMemsetAsync(h->srv_counter.p, 0, 32 * gicp::kGicpServerParts * sizeof(unsigned), h->tgt.stream);
     if (e == hipSuccess) e = h->partials.reserve(static_cast<size_t>(std::max(h->srv_blocks, gicp::kFunctorMaxBlocks)) * ndt::kEvalStride);
     if (e == hipSuccess)
-      e = gicp::launch_server(h->output.p, n, h->tgt.target->pts.p, h->corr.p, h->maha.p, mailbox(), h->srv_blocks, h->partials.p,
+      e = gicp::launch_server(h->output.p, n, tgt.cloud().pts.p, h->corr.p, h->maha.p, mailbox(), h->srv_blocks, h->partials.p,
                               h->srv_counter.p, h->srv_rows, h->seq + 1, 2000000ull /* 20 ms */, h->tgt.stream);
     if (e != hipSuccess) {
       server_mark(&h->tgt, false);
@@ -419,7 +459,7 @@ struct GicpDevice : gicp::Backend {
       out = grad_sums;
       return true;
     }
-    const int n = static_cast<int>(h->src.target->n);
+    const int n = static_cast<int>(src.n());
     const int launch_mode = (mode == 0 && fuse) ? 3 : mode;
     double row[ndt::kEvalStride];
     bool have_row = false;
@@ -432,7 +472,7 @@ struct GicpDevice : gicp::Backend {
     }
     if (!have_row) {
       const unsigned long long seq = ++h->seq;
-      const hipError_t e = gicp::launch_functor(launch_mode, h->output.p, n, h->tgt.target->pts.p, h->corr.p, h->maha.p, T,
+      const hipError_t e = gicp::launch_functor(launch_mode, h->output.p, n, tgt.cloud().pts.p, h->corr.p, h->maha.p, T,
                                                 gicp::functor_blocks(n, kGicpMaxBlocks), h->partials.p, h->counter.p, h->host_pub, seq, h->tgt.stream);
       if (e != hipSuccess) {
         error = std::string("functor kernel: ") + hipGetErrorString(e);
@@ -470,6 +510,21 @@ struct GicpDevice : gicp::Backend {
   ~GicpDevice() override { server_stop(); }
 };
 
+// One registration of `src` onto `tgt` from the guess (column-major, NULL = identity): what gicp_align and every pair of
+// gicp_align_pairs_clouds run.  *status != NDT_OK: the result means nothing.
+gicp::Result gicp_register(gicp_context* h, GicpInput& tgt, GicpInput& src, const float* guess_cm, ndt_status* status) {
+  gicp::Result r{};
+  float guess_rm[16];
+  *status = gicp_prepare(h, tgt, src, guess_cm, guess_rm);
+  if (*status) return r;
+  h->step_ready = false;  // the scratch of gicp_step_correspond is overwritten from here on
+  GicpDevice dev(h, tgt, src);
+  r = gicp::run(h->prm, guess_rm, dev);
+  dev.server_stop();  // before anything else is queued on the stream or waited for: the server would sit out its patience
+  if (r.backend_failed || !dev.error.empty()) *status = fail(NDT_ERR_HIP, dev.error.empty() ? "device failure" : dev.error);
+  return r;
+}
+
 }  // namespace
 
 extern "C" {
@@ -483,15 +538,7 @@ ndt_status gicp_create(int device, gicp_handle* out) {
   return NDT_OK;
 }
 
-void gicp_destroy(gicp_handle h) {
-  if (!h) return;
-  for (ndt_context* c : {&h->tgt, &h->src})
-    if (c->device_ready) {
-      (void)hipSetDevice(c->device);
-      (void)hipStreamSynchronize(c->stream);
-    }
-  delete h;
-}
+void gicp_destroy(gicp_handle h) { delete h; }
 
 ndt_status gicp_set_correspondence_randomness(gicp_handle h, int k) {
   if (!h || k < 1 || k > gicp::kMaxK) return fail(NDT_ERR_INVALID, "k_correspondences must be in [1, 64]");
@@ -526,45 +573,28 @@ ndt_status gicp_set_max_correspondence_distance(gicp_handle h, double d) {
   return NDT_OK;
 }
 
-ndt_status gicp_set_input_target(gicp_handle h, const void* pts, size_t n, size_t stride_bytes) {
+// setInputTarget (which = 0) / setInputSource (1) from host memory
+static ndt_status gicp_set_input(gicp_handle h, int which, const void* pts, size_t n, size_t stride_bytes) {
   if (!h) return fail(NDT_ERR_INVALID, "null");
-  h->have_tgt = false;
-  h->have_cov_tgt = h->user_cov_tgt = false;  // target_covariances_.reset()
-  h->step_ready = false;
+  GicpInput& in = gicp_unset(h, which);
   if (h->tgt.device_ready) {  // kernels of an earlier align may still read the old index
     HIP_TRY(hipSetDevice(h->tgt.device));
     HIP_TRY(hipStreamSynchronize(h->tgt.stream));
   }
-  const ndt_status s = gicp_build_index(&h->tgt, pts, n, stride_bytes, &h->hint_leaf[0], &h->hint_n[0]);
+  ndt_context* c = h->builder(which);
+  const ndt_status s = gicp_build_index(c, pts, n, stride_bytes, in.hint, in);
   if (s) return s;
-  h->have_tgt = true;
+  if (which == 1) HIP_TRY(hipStreamSynchronize(c->stream));  // the index is read from the main stream from here on
+  in.set = true;
   return NDT_OK;
 }
+ndt_status gicp_set_input_target(gicp_handle h, const void* pts, size_t n, size_t stride_bytes) { return gicp_set_input(h, 0, pts, n, stride_bytes); }
+ndt_status gicp_set_input_source(gicp_handle h, const void* pts, size_t n, size_t stride_bytes) { return gicp_set_input(h, 1, pts, n, stride_bytes); }
 
-ndt_status gicp_set_input_source(gicp_handle h, const void* pts, size_t n, size_t stride_bytes) {
-  if (!h) return fail(NDT_ERR_INVALID, "null");
-  h->have_src = false;
-  h->have_cov_src = h->user_cov_src = false;  // input_covariances_.reset()
-  h->step_ready = false;
-  if (h->tgt.device_ready) {
-    HIP_TRY(hipSetDevice(h->tgt.device));
-    HIP_TRY(hipStreamSynchronize(h->tgt.stream));
-  }
-  const ndt_status s = gicp_build_index(&h->src, pts, n, stride_bytes, &h->hint_leaf[1], &h->hint_n[1]);
-  if (s) return s;
-  HIP_TRY(hipStreamSynchronize(h->src.stream));  // the index is read from tgt's stream from here on
-  h->have_src = true;
-  return NDT_OK;
-}
-
-// setInputTarget (which = 0) / setInputSource (1) from a resident cloud: finite check on the device, the index built over
-// the cloud where it lies
+// the same from a resident cloud: finite check on the device, the index built over the cloud where it lies
 static ndt_status gicp_set_input_cloud(gicp_handle h, int which, ndt_cloud cl) {
   if (!h) return fail(NDT_ERR_INVALID, "null");
-  (which == 0 ? h->have_tgt : h->have_src) = false;
-  (which == 0 ? h->have_cov_tgt : h->have_cov_src) = false;
-  (which == 0 ? h->user_cov_tgt : h->user_cov_src) = false;
-  h->step_ready = false;
+  GicpInput& in = gicp_unset(h, which);
   if (!cl || !cl->c || cl->c->n == 0) return fail(NDT_ERR_INVALID, "invalid or empty point cloud dataset given");
   ndt_status s = ensure_device(&h->tgt);
   if (s) return s;
@@ -575,16 +605,16 @@ static ndt_status gicp_set_input_cloud(gicp_handle h, int which, ndt_cloud cl) {
   s = gicp_finite_check(h, {cl->c.get()}, bad);
   if (s) return s;
   if (bad[0]) return fail(NDT_ERR_INVALID, "GICP needs finite points (" + std::to_string(bad[0]) + " of the cloud's are not)");
-  ndt_context* c = which == 0 ? &h->tgt : &h->src;
+  ndt_context* c = h->builder(which);
   if (which == 1) {
     s = ensure_device(c);
     if (!s) s = cloud_use_on(c, cl->c.get());
     if (s) return s;
   }
-  s = gicp_index_resident(c, cl->c, &h->hint_leaf[which], &h->hint_n[which]);
+  s = gicp_index_cloud(c, cl->c, in.hint, in);
   if (s) return s;
-  if (which == 1) HIP_TRY(hipStreamSynchronize(h->src.stream));  // the index is read from tgt's stream from here on
-  (which == 0 ? h->have_tgt : h->have_src) = true;
+  if (which == 1) HIP_TRY(hipStreamSynchronize(c->stream));  // the index is read from the main stream from here on
+  in.set = true;
   return NDT_OK;
 }
 ndt_status gicp_set_input_target_cloud(gicp_handle h, ndt_cloud c) { return gicp_set_input_cloud(h, 0, c); }
@@ -649,124 +679,74 @@ ndt_status gicp_align_pairs_clouds(gicp_handle h, const ndt_cloud* clouds, size_
   for (size_t j = 0; j < named.size(); j++)
     if (bad[j]) return fail(NDT_ERR_INVALID, "GICP needs finite points (" + std::to_string(bad[j]) + " of cloud " + std::to_string(named[j]) + " are not)");
 
-  // ---- from here on the handle's inputs are swapped for the prepared clouds; `keep` puts everything back
-  struct Keep {
-    gicp_context* h;
-    std::shared_ptr<DeviceCloud> tt, st;
-    std::shared_ptr<DeviceGrid> tg, sg;
-    float t_res, s_res;
-    bool have_tgt, have_src, have_cov_tgt, have_cov_src, user_cov_tgt, user_cov_src;
-    DevBuf<double> cov_tgt, cov_src;
-    float final_T[16], guess_rm[16];
-    int converged, nr_iterations, n_f, n_df, n_fdf, correspondences;
-    explicit Keep(gicp_context* c) : h(c), tt(c->tgt.target), st(c->src.target), tg(c->tgt.grid), sg(c->src.grid),
-                                     t_res(c->tgt.resolution), s_res(c->src.resolution), have_tgt(c->have_tgt), have_src(c->have_src),
-                                     have_cov_tgt(c->have_cov_tgt), have_cov_src(c->have_cov_src), user_cov_tgt(c->user_cov_tgt),
-                                     user_cov_src(c->user_cov_src), converged(c->converged), nr_iterations(c->nr_iterations),
-                                     n_f(c->n_f), n_df(c->n_df), n_fdf(c->n_fdf), correspondences(c->correspondences) {
-      cov_tgt.swap(c->cov_tgt);
-      cov_src.swap(c->cov_src);
-      std::memcpy(final_T, c->final_T, sizeof(final_T));
-      std::memcpy(guess_rm, c->guess_rm, sizeof(guess_rm));
+  // ---- one record per named cloud: its index, the leaf of the previous one as the hint for the next (a chain of this
+  // call's own; the builds are the handle's own path, one after the other, on the main stream)
+  std::vector<GicpInput> prep(n_clouds);
+  LeafHint hint;
+  for (int c : named) {
+    GicpInput& P = prep[c];
+    s = gicp_index_cloud(&h->tgt, clouds[c]->c, hint, P);
+    if (s) return s;
+    HIP_TRY(P.cov.reserve(P.n() * 6));
+    P.set = P.have_cov = true;  // (the covariances: the launch below, waited for before the first pair)
+  }
+  // ---- the covariances of all of them: one launch (members in order while their blocks stay within kGicpMultiMaxBlocks,
+  // then a further launch)
+  std::vector<gicp::KnnMember> tab(named.size());
+  std::vector<std::pair<size_t, size_t>> launches;  // [first member, end member)
+  size_t knn_launches = 0, knn_blocks = 0;
+  {
+    size_t first = 0;
+    long long blocks = 0;
+    for (size_t j = 0; j < named.size(); j++) {
+      const GicpInput& P = prep[named[j]];
+      const int nb = gicp::knn_blocks(static_cast<int>(P.n()), kGicpMaxBlocks);
+      if (blocks > 0 && blocks + nb > kGicpMultiMaxBlocks) {  // (a member is never split: alone it may exceed the limit)
+        launches.emplace_back(first, j);
+        first = j;
+        blocks = 0;
+      }
+      tab[j].ix = gicp_index_of(P);
+      tab[j].cov6 = P.cov.p;
+      tab[j].first_block = static_cast<int>(blocks);
+      tab[j].n_blocks = nb;
+      blocks += nb;
+      knn_blocks += static_cast<size_t>(nb);
     }
-    ~Keep() {
-      h->tgt.target = tt; h->src.target = st; h->tgt.grid = tg; h->src.grid = sg;
-      h->tgt.resolution = t_res; h->src.resolution = s_res;
-      h->have_tgt = have_tgt; h->have_src = have_src; h->have_cov_tgt = have_cov_tgt; h->have_cov_src = have_cov_src;
-      h->user_cov_tgt = user_cov_tgt; h->user_cov_src = user_cov_src;
-      h->cov_tgt.borrow(nullptr, 0);  // (what the pairs borrowed is the prepared clouds')
-      h->cov_src.borrow(nullptr, 0);
-      h->cov_tgt.swap(cov_tgt);
-      h->cov_src.swap(cov_src);
-      std::memcpy(h->final_T, final_T, sizeof(final_T));
-      std::memcpy(h->guess_rm, guess_rm, sizeof(guess_rm));
-      h->converged = converged; h->nr_iterations = nr_iterations;
-      h->n_f = n_f; h->n_df = n_df; h->n_fdf = n_fdf; h->correspondences = correspondences;
-      h->step_ready = false;  // (the scratch of gicp_step_correspond has been used by the pairs)
-    }
-  };
-  std::vector<std::unique_ptr<gicp_context::Prepared>> prep(n_clouds);
+    launches.emplace_back(first, named.size());
+  }
+  HIP_TRY(h->member_table.reserve(tab.size() * sizeof(gicp::KnnMember)));
+  StreamDrain drain{st};  // (a launch that fails returns with the table's copy waited for)
+  HIP_TRY(hipMemcpyAsync(h->member_table.p, tab.data(), tab.size() * sizeof(gicp::KnnMember), hipMemcpyHostToDevice, st));
+  for (const auto& l : launches) {
+    const gicp::KnnMember* d = reinterpret_cast<const gicp::KnnMember*>(h->member_table.p) + l.first;
+    const int nb = tab[l.second - 1].first_block + tab[l.second - 1].n_blocks;
+    HIP_TRY(gicp::launch_knn_covariances_multi(d, static_cast<int>(l.second - l.first), nb, k, h->prm.gicp_epsilon, st));
+    knn_launches++;
+  }
+  HIP_TRY(hipStreamSynchronize(st));  // (the table's host copy may go; a failed launch shows here, not in the first pair)
+  drain.done = true;
+  t_prepared = std::chrono::steady_clock::now();
+  // ---- the pairs, one after the other: gicp_align's registration and gicp_get_fitness_score's score of two records.  The
+  // handle's own inputs, covariances, result and statistics are not touched (its step scratch is: gicp_register)
   std::vector<float> T_all(16 * n_pairs);
   std::vector<int> conv_all(n_pairs), it_all(n_pairs), corr_all(n_pairs);
   std::vector<double> fit_all(n_pairs);
-  size_t knn_launches = 0, knn_blocks = 0;
-  {
-    Keep keep(h);
-    // ---- one index per named cloud, the leaf of the previous one as the hint for the next (the builds are the handle's own
-    // path, one after the other, on the main stream)
-    float hint_leaf = 0.f;
-    size_t hint_n = 0;
-    for (int c : named) {
-      prep[c].reset(new gicp_context::Prepared());
-      prep[c]->cloud = clouds[c]->c;
-      s = gicp_index_resident(&h->tgt, clouds[c]->c, &hint_leaf, &hint_n);
+  for (size_t p = 0; p < n_pairs; p++) {
+    GicpInput& Pt = prep[pairs[2 * p]];
+    GicpInput& Ps = prep[pairs[2 * p + 1]];
+    const gicp::Result r = gicp_register(h, Pt, Ps, guesses ? guesses + 16 * p : nullptr, &s);
+    if (s) return s;
+    colmajor_from_rowmajor(r.final_T, &T_all[16 * p]);
+    conv_all[p] = r.converged ? 1 : 0;
+    it_all[p] = r.nr_iterations;
+    corr_all[p] = r.correspondences;
+    if (fitness) {
+      s = fitness_against(&h->tgt, Pt.grid.get(), Ps.cloud().pts.p, static_cast<int>(Ps.n()), &T_all[16 * p], max_range, &fit_all[p]);
       if (s) return s;
-      prep[c]->grid = h->tgt.grid;
-      HIP_TRY(prep[c]->cov.reserve(clouds[c]->c->n * 6));
     }
-    // ---- the covariances of all of them: one launch (members in order while their blocks stay within kGicpMultiMaxBlocks,
-    // then a further launch)
-    std::vector<gicp::KnnMember> tab(named.size());
-    std::vector<std::pair<size_t, size_t>> launches;  // [first member, end member)
-    {
-      size_t first = 0;
-      long long blocks = 0;
-      for (size_t j = 0; j < named.size(); j++) {
-        const gicp_context::Prepared& P = *prep[named[j]];
-        const int nb = gicp::knn_blocks(static_cast<int>(P.cloud->n), kGicpMaxBlocks);
-        if (blocks > 0 && blocks + nb > kGicpMultiMaxBlocks) {  // (a member is never split: alone it may exceed the limit)
-          launches.emplace_back(first, j);
-          first = j;
-          blocks = 0;
-        }
-        fill_point_index(P.grid.get(), tab[j].ix);
-        tab[j].cov6 = P.cov.p;
-        tab[j].first_block = static_cast<int>(blocks);
-        tab[j].n_blocks = nb;
-        blocks += nb;
-        knn_blocks += static_cast<size_t>(nb);
-      }
-      launches.emplace_back(first, named.size());
-    }
-    HIP_TRY(h->member_table.reserve(tab.size() * sizeof(gicp::KnnMember)));
-    StreamDrain drain{st};  // (a launch that fails returns with the table's copy waited for)
-    HIP_TRY(hipMemcpyAsync(h->member_table.p, tab.data(), tab.size() * sizeof(gicp::KnnMember), hipMemcpyHostToDevice, st));
-    for (const auto& l : launches) {
-      const gicp::KnnMember* d = reinterpret_cast<const gicp::KnnMember*>(h->member_table.p) + l.first;
-      const int nb = tab[l.second - 1].first_block + tab[l.second - 1].n_blocks;
-      HIP_TRY(gicp::launch_knn_covariances_multi(d, static_cast<int>(l.second - l.first), nb, k, h->prm.gicp_epsilon, st));
-      knn_launches++;
-    }
-    HIP_TRY(hipStreamSynchronize(st));  // (the table's host copy may go; a failed launch shows here, not in the first pair)
-    drain.done = true;
-    t_prepared = std::chrono::steady_clock::now();
-    // ---- the pairs, one after the other, through the handle's own outer loop
-    for (size_t p = 0; p < n_pairs; p++) {
-      gicp_context::Prepared& Pt = *prep[pairs[2 * p]];
-      gicp_context::Prepared& Ps = *prep[pairs[2 * p + 1]];
-      h->tgt.target = Pt.cloud; h->tgt.grid = Pt.grid; h->tgt.resolution = Pt.grid->resolution;
-      h->src.target = Ps.cloud; h->src.grid = Ps.grid; h->src.resolution = Ps.grid->resolution;
-      h->cov_tgt.borrow(Pt.cov.p, Pt.cloud->n * 6);
-      h->cov_src.borrow(Ps.cov.p, Ps.cloud->n * 6);
-      h->have_tgt = h->have_src = h->have_cov_tgt = h->have_cov_src = true;
-      h->user_cov_tgt = h->user_cov_src = false;
-      s = gicp_prepare(h, guesses ? guesses + 16 * p : nullptr);
-      if (s) return s;
-      GicpDevice dev(h);
-      const gicp::Result r = gicp::run(h->prm, h->guess_rm, dev);
-      dev.server_stop();
-      if (r.backend_failed || !dev.error.empty()) return fail(NDT_ERR_HIP, dev.error.empty() ? "device failure" : dev.error);
-      colmajor_from_rowmajor(r.final_T, &T_all[16 * p]);
-      conv_all[p] = r.converged ? 1 : 0;
-      it_all[p] = r.nr_iterations;
-      corr_all[p] = r.correspondences;
-      if (fitness) {
-        s = fitness_impl(&h->tgt, Ps.cloud->pts.p, static_cast<int>(Ps.cloud->n), &T_all[16 * p], max_range, &fit_all[p]);
-        if (s) return s;
-      }
-    }
-    HIP_TRY(hipStreamSynchronize(st));
   }
+  HIP_TRY(hipStreamSynchronize(st));
   if (final_T) std::memcpy(final_T, T_all.data(), T_all.size() * sizeof(float));
   if (converged) std::memcpy(converged, conv_all.data(), n_pairs * sizeof(int));
   if (n_iterations) std::memcpy(n_iterations, it_all.data(), n_pairs * sizeof(int));
@@ -784,23 +764,11 @@ ndt_status gicp_align_pairs_clouds(gicp_handle h, const ndt_cloud* clouds, size_
 
 ndt_status gicp_pairs_covariances(gicp_handle h, size_t cloud, double* cov) {
   if (!h || !cov) return fail(NDT_ERR_INVALID, "bad arguments");
-  if (!h->pairs_valid || cloud >= h->pairs_prepared.size() || !h->pairs_prepared[cloud])
+  if (!h->pairs_valid || cloud >= h->pairs_prepared.size() || !h->pairs_prepared[cloud].set)
     return fail(NDT_ERR_NO_INPUT, "the last pairs call computed no covariances for this cloud");
   ndt_status s = ensure_device(&h->tgt);
   if (s) return s;
-  const gicp_context::Prepared& P = *h->pairs_prepared[cloud];
-  const size_t n = P.cloud->n;
-  std::vector<double> c6(n * 6);
-  HIP_TRY(hipMemcpyAsync(c6.data(), P.cov.p, n * 6 * sizeof(double), hipMemcpyDeviceToHost, h->tgt.stream));
-  HIP_TRY(hipStreamSynchronize(h->tgt.stream));
-  for (size_t i = 0; i < n; i++) {
-    const double* s6 = &c6[i * 6];
-    double* o = cov + i * 9;
-    o[0] = s6[0]; o[1] = s6[1]; o[2] = s6[2];
-    o[3] = s6[1]; o[4] = s6[3]; o[5] = s6[4];
-    o[6] = s6[2]; o[7] = s6[4]; o[8] = s6[5];
-  }
-  return NDT_OK;
+  return gicp_read_covariances(h, h->pairs_prepared[cloud], cov);
 }
 
 ndt_status gicp_diag_pairs(gicp_handle h, size_t* index_builds, size_t* knn_launches, size_t* knn_blocks) {
@@ -822,27 +790,18 @@ ndt_status gicp_diag_pairs_time(gicp_handle h, double* prepare_ms, double* regis
 
 ndt_status gicp_align(gicp_handle h, const float* guess, float* final_T, int* converged, int* n_iterations, void* out_cloud) {
   if (!h) return fail(NDT_ERR_INVALID, "null");
-  ndt_status s = gicp_prepare(h, guess);
+  ndt_status s = gicp_inputs_set(h);
   if (s) return s;
-  h->step_ready = false;
-  GicpDevice dev(h);
-  const gicp::Result r = gicp::run(h->prm, h->guess_rm, dev);
-  dev.server_stop();  // before anything else is queued on the stream or waited for: the server would sit out its patience
-  if (r.backend_failed || !dev.error.empty()) return fail(NDT_ERR_HIP, dev.error.empty() ? "device failure" : dev.error);
+  const GicpInput& src = h->in[1];
+  const gicp::Result r = gicp_register(h, h->in[0], h->in[1], guess, &s);
+  if (s) return s;
+  h->result = r;
   colmajor_from_rowmajor(r.final_T, h->final_T);
-  h->converged = r.converged ? 1 : 0;
-  h->nr_iterations = r.nr_iterations;
-  h->n_f = r.n_f;
-  h->n_df = r.n_df;
-  h->n_fdf = r.n_fdf;
-  h->correspondences = r.correspondences;
-  if (final_T) std::memcpy(final_T, h->final_T, sizeof(h->final_T));
-  if (converged) *converged = h->converged;
-  if (n_iterations) *n_iterations = h->nr_iterations;
+  (void)gicp_get_result(h, final_T, converged, n_iterations);
   if (out_cloud) {  // pcl::transformPointCloud(*input_, output, final_transformation_), :513-516
-    const size_t n = h->src.target->n;
+    const size_t n = src.n();
     HIP_TRY(h->out_cloud.reserve(n));
-    HIP_TRY(ndt::launch_transform(h->src.target->pts.p, static_cast<int>(n), r.final_T, h->out_cloud.p, h->tgt.stream));
+    HIP_TRY(ndt::launch_transform(src.cloud().pts.p, static_cast<int>(n), r.final_T, h->out_cloud.p, h->tgt.stream));
     // through page-locked staging: a D2H copy into the caller's pageable buffer is staged by the runtime in small pieces
     const size_t bytes = n * sizeof(float4);
     if (h->out_pinned_bytes < bytes) {
@@ -862,24 +821,26 @@ ndt_status gicp_align(gicp_handle h, const float* guess, float* final_T, int* co
 ndt_status gicp_get_result(gicp_handle h, float* final_T, int* converged, int* n_iterations) {
   if (!h) return fail(NDT_ERR_INVALID, "null");
   if (final_T) std::memcpy(final_T, h->final_T, sizeof(h->final_T));
-  if (converged) *converged = h->converged;
-  if (n_iterations) *n_iterations = h->nr_iterations;
+  if (converged) *converged = h->result.converged ? 1 : 0;
+  if (n_iterations) *n_iterations = h->result.nr_iterations;
   return NDT_OK;
 }
 
 ndt_status gicp_get_fitness_score(gicp_handle h, double max_range, double* fitness) {
   if (!h || !fitness) return fail(NDT_ERR_INVALID, "bad arguments");
-  ndt_status s = gicp_ready(h);
+  ndt_status s = gicp_inputs_set(h);
+  if (!s) s = gicp_scratch(h);
   if (s) return s;
-  return fitness_impl(&h->tgt, h->src.target->pts.p, static_cast<int>(h->src.target->n), h->final_T, max_range, fitness);
+  const GicpInput& src = h->in[1];
+  return fitness_against(&h->tgt, h->in[0].grid.get(), src.cloud().pts.p, static_cast<int>(src.n()), h->final_T, max_range, fitness);
 }
 
 ndt_status gicp_get_stats(gicp_handle h, int* n_f, int* n_df, int* n_fdf, int* correspondences) {
   if (!h) return fail(NDT_ERR_INVALID, "null");
-  if (n_f) *n_f = h->n_f;
-  if (n_df) *n_df = h->n_df;
-  if (n_fdf) *n_fdf = h->n_fdf;
-  if (correspondences) *correspondences = h->correspondences;
+  if (n_f) *n_f = h->result.n_f;
+  if (n_df) *n_df = h->result.n_df;
+  if (n_fdf) *n_fdf = h->result.n_fdf;
+  if (correspondences) *correspondences = h->result.correspondences;
   return NDT_OK;
 }
 
@@ -887,28 +848,21 @@ ndt_status gicp_get_stats(gicp_handle h, int* n_f, int* n_df, int* n_fdf, int* c
 // the k-NN ones until the cloud is set again.  cov: [n][9] row-major 3x3 (symmetric: the upper triangle is kept).
 static ndt_status gicp_set_covariances(gicp_handle h, int which, const double* cov, size_t n) {
   if (!h) return fail(NDT_ERR_INVALID, "null");
-  if (!(which == 0 ? h->have_tgt : h->have_src)) return fail(NDT_ERR_NO_INPUT, "set the cloud before its covariances");
-  bool& have = which == 0 ? h->have_cov_tgt : h->have_cov_src;
-  bool& user = which == 0 ? h->user_cov_tgt : h->user_cov_src;
+  GicpInput& in = h->in[which];
+  if (!in.set) return fail(NDT_ERR_NO_INPUT, "set the cloud before its covariances");
   if (!cov || n == 0) {  // an empty vector: computed again by the next align (:386,392)
-    have = user = false;
+    in.have_cov = in.user_cov = false;
     return NDT_OK;
   }
-  ndt_context* c = which == 0 ? &h->tgt : &h->src;
-  if (n != c->target->n) return fail(NDT_ERR_INVALID, "one covariance per point of the cloud is required");
+  if (n != in.n()) return fail(NDT_ERR_INVALID, "one covariance per point of the cloud is required");
   ndt_status s = ensure_device(&h->tgt);
   if (s) return s;
   std::vector<double> c6(n * 6);
-  for (size_t i = 0; i < n; i++) {
-    const double* m = cov + i * 9;
-    double* o = &c6[i * 6];
-    o[0] = m[0]; o[1] = m[1]; o[2] = m[2]; o[3] = m[4]; o[4] = m[5]; o[5] = m[8];
-  }
-  DevBuf<double>& dst = which == 0 ? h->cov_tgt : h->cov_src;
-  HIP_TRY(dst.reserve(n * 6));
+  cov6_from_cov9(cov, n, c6.data());
+  HIP_TRY(in.cov.reserve(n * 6));
   HIP_TRY(hipStreamSynchronize(h->tgt.stream));  // kernels of an earlier align may still read the old covariances
-  HIP_TRY(hipMemcpy(dst.p, c6.data(), n * 6 * sizeof(double), hipMemcpyHostToDevice));
-  have = user = true;
+  HIP_TRY(hipMemcpy(in.cov.p, c6.data(), n * 6 * sizeof(double), hipMemcpyHostToDevice));
+  in.have_cov = in.user_cov = true;
   h->step_ready = false;
   return NDT_OK;
 }
@@ -917,45 +871,39 @@ ndt_status gicp_set_source_covariances(gicp_handle h, const double* cov, size_t 
 
 ndt_status gicp_covariances(gicp_handle h, int which, double* cov, int* nn_idx, float* nn_d2) {
   if (!h || !cov || which < 0 || which > 1) return fail(NDT_ERR_INVALID, "bad arguments");
-  if (!(which == 0 ? h->have_tgt : h->have_src)) return fail(NDT_ERR_NO_INPUT, "cloud not set");
+  GicpInput& in = h->in[which];
+  if (!in.set) return fail(NDT_ERR_NO_INPUT, "cloud not set");
   ndt_status s = ensure_device(&h->tgt);
   if (s) return s;
   // inspection: the k-NN covariances for the CURRENT k (caller-supplied ones are returned as they are; neighbours cannot
   // be asked for then)
-  if (which == 0 ? h->user_cov_tgt : h->user_cov_src) {
+  if (in.user_cov) {
     if (nn_idx || nn_d2) return fail(NDT_ERR_INVALID, "caller-supplied covariances have no neighbour lists");
   } else {
-    (which == 0 ? h->have_cov_tgt : h->have_cov_src) = false;
+    in.have_cov = false;
   }
   const bool want_nn = nn_idx && nn_d2;
-  s = gicp_cloud_covariances(h, which, want_nn);
+  s = gicp_cloud_covariances(h, in, which == 1, want_nn);
   if (s) return s;
   s = gicp_join_source(h);
   if (s) return s;
-  ndt_context* c = which == 0 ? &h->tgt : &h->src;
-  const size_t n = c->target->n;
-  std::vector<double> c6(n * 6);
-  HIP_TRY(hipMemcpyAsync(c6.data(), (which == 0 ? h->cov_tgt : h->cov_src).p, n * 6 * sizeof(double), hipMemcpyDeviceToHost, h->tgt.stream));
   if (want_nn) {
-    const size_t k = static_cast<size_t>(h->prm.k_correspondences);
-    HIP_TRY(hipMemcpyAsync(nn_idx, h->nn_idx.p, n * k * sizeof(int), hipMemcpyDeviceToHost, h->tgt.stream));
-    HIP_TRY(hipMemcpyAsync(nn_d2, h->nn_d2.p, n * k * sizeof(float), hipMemcpyDeviceToHost, h->tgt.stream));
+    const size_t nk = in.n() * static_cast<size_t>(h->prm.k_correspondences);
+    HIP_TRY(hipMemcpyAsync(nn_idx, h->nn_idx.p, nk * sizeof(int), hipMemcpyDeviceToHost, h->tgt.stream));
+    HIP_TRY(hipMemcpyAsync(nn_d2, h->nn_d2.p, nk * sizeof(float), hipMemcpyDeviceToHost, h->tgt.stream));
   }
-  HIP_TRY(hipStreamSynchronize(h->tgt.stream));
-  for (size_t i = 0; i < n; i++) {
-    const double* s6 = &c6[i * 6];
-    double* o = cov + i * 9;
-    o[0] = s6[0]; o[1] = s6[1]; o[2] = s6[2];
-    o[3] = s6[1]; o[4] = s6[3]; o[5] = s6[4];
-    o[6] = s6[2]; o[7] = s6[4]; o[8] = s6[5];
-  }
-  return NDT_OK;
+  return gicp_read_covariances(h, in, cov);  // (waits for the main stream: the neighbour lists have arrived too)
 }
 
 ndt_status gicp_step_correspond(gicp_handle h, const float* guess, const float* transformation, int* corr, float* maha,
                                 int* n_correspondences) {
   if (!h) return fail(NDT_ERR_INVALID, "null");
-  ndt_status s = gicp_prepare(h, guess);
+  ndt_status s = gicp_inputs_set(h);
+  if (s) return s;
+  GicpInput& tgt = h->in[0];
+  GicpInput& src = h->in[1];
+  float guess_rm[16];
+  s = gicp_prepare(h, tgt, src, guess, guess_rm);
   if (s) return s;
   float T[16];
   rowmajor_from_colmajor(transformation, T);
@@ -963,12 +911,12 @@ ndt_status gicp_step_correspond(gicp_handle h, const float* guess, const float* 
   for (int i = 0; i < 3; i++)
     for (int j = 0; j < 3; j++) {
       double acc = 0.0;
-      for (int k = 0; k < 4; k++) acc += static_cast<double>(T[i * 4 + k]) * static_cast<double>(h->guess_rm[k * 4 + j]);
+      for (int k = 0; k < 4; k++) acc += static_cast<double>(T[i * 4 + k]) * static_cast<double>(guess_rm[k * 4 + j]);
       R[i * 3 + j] = acc;
     }
-  GicpDevice dev(h);
+  GicpDevice dev(h, tgt, src);
   if (!dev.correspond(T, R)) return fail(NDT_ERR_HIP, dev.error);
-  const size_t n = h->src.target->n;
+  const size_t n = src.n();
   std::vector<int> c(n);
   HIP_TRY(hipMemcpyAsync(c.data(), h->corr.p, n * sizeof(int), hipMemcpyDeviceToHost, h->tgt.stream));
   if (maha) HIP_TRY(hipMemcpyAsync(maha, h->maha.p, n * 9 * sizeof(float), hipMemcpyDeviceToHost, h->tgt.stream));
@@ -984,9 +932,10 @@ ndt_status gicp_step_correspond(gicp_handle h, const float* guess, const float* 
 ndt_status gicp_step_functor(gicp_handle h, int mode, const double* x, double* f, double* g) {
   if (!h || !x || mode < 0 || mode > 2) return fail(NDT_ERR_INVALID, "bad arguments");
   if (!h->step_ready) return fail(NDT_ERR_NO_INPUT, "gicp_step_correspond has not run");
-  ndt_status s = gicp_ready(h);
+  ndt_status s = gicp_inputs_set(h);
+  if (!s) s = gicp_scratch(h);
   if (s) return s;
-  GicpDevice dev(h);
+  GicpDevice dev(h, h->in[0], h->in[1]);
   float T[16];
   gicp::apply_state(x, T);
   gicp::FunctorSums sums;

@@ -1017,10 +1017,11 @@ void fill_point_index(const DeviceGrid* g, ndt::PointIndex& ix) {
   ix.n_sorted = static_cast<int>(g->n_sorted);
   ix.slack = index_slack(g);
 }
-// [PCL] Registration::getFitnessScore of the dense device cloud d_src moved by T against h's target
-ndt_status fitness_impl(ndt_context* h, const float4* d_src, int n, const float* T_colmajor, double max_range, double* fitness) {
+// [PCL] Registration::getFitnessScore of the dense device cloud d_src moved by T against the target of the grid g (on h's
+// stream, with h's scratch)
+ndt_status fitness_against(ndt_context* h, DeviceGrid* g, const float4* d_src, int n, const float* T_colmajor, double max_range,
+                           double* fitness) {
   *fitness = std::numeric_limits<double>::max();  // nr == 0 in the reference
-  DeviceGrid* g = h->grid.get();
   ndt_status s = grid_counts(h, g);
   if (s) return s;
   if (n == 0 || g->empty || g->n_sorted == 0) return NDT_OK;
@@ -1039,6 +1040,10 @@ ndt_status fitness_impl(ndt_context* h, const float4* d_src, int n, const float*
   HIP_TRY(hipStreamSynchronize(h->stream));
   if (h->host_result[1] > 0) *fitness = h->host_result[0] / h->host_result[1];
   return NDT_OK;
+}
+// ... against h's own target
+ndt_status fitness_impl(ndt_context* h, const float4* d_src, int n, const float* T_colmajor, double max_range, double* fitness) {
+  return fitness_against(h, h->grid.get(), d_src, n, T_colmajor, max_range, fitness);
 }
 
 // ---- N1: voxel-grid centroid down-sample -----------------------------------

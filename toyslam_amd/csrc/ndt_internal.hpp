@@ -553,6 +553,9 @@ float index_slack(const DeviceGrid* g);
 ndt_status download_records(ndt_context* h, const float4* d_src, size_t n, void* out, size_t out_stride);
 void fill_point_index(const DeviceGrid* g, ndt::PointIndex& ix);
 ndt_status fitness_impl(ndt_context* h, const float4* d_src, int n, const float* T_colmajor, double max_range, double* fitness);
+// the same against a grid the caller names instead of h->grid (GICP: the target input's index)
+ndt_status fitness_against(ndt_context* h, DeviceGrid* g, const float4* d_src, int n, const float* T_colmajor, double max_range,
+                           double* fitness);
 // getFitnessScore of many (source, target grid, transform) members: the source's n points at src, moved by the column-major T,
 // against g's point index.  out[k] is what fitness_impl returns for member k on a handle holding that grid (ndt_fitness.hip)
 struct FitnessJob {
