@@ -44,7 +44,7 @@ ndt_status fitness_many(ndt_context* h, const std::vector<FitnessJob>& jobs, dou
     const FitnessJob& j = jobs[k];
     if (j.n == 0 || !j.g || j.g->empty || j.g->n_sorted == 0) continue;
     const int n = static_cast<int>(j.n);
-    const int nblk = std::max(1, std::min(2048, (n + 31) / 32));  // fitness_impl's grid: 32 query teams per block
+    const int nblk = fitness_blocks(n);  // fitness_impl's grid
     if (cur > 0 && cur + nblk > bound) {  // close the chunk
       starts.push_back(cur);
       chunk_blocks.push_back(cur);

@@ -1031,7 +1031,7 @@ ndt_status fitness_against(ndt_context* h, DeviceGrid* g, const float4* d_src, i
   if (s) return s;
   float T12[12];
   colmajor_to_T12(T_colmajor, T12);
-  const int nblk = std::max(1, std::min(2048, (n + 31) / 32));  // 32 query teams per block
+  const int nblk = fitness_blocks(n);
   HIP_TRY(h->partials.reserve(static_cast<size_t>(nblk) * ndt::kEvalStride));
   ndt::PointIndex ix;
   fill_point_index(g, ix);

@@ -565,6 +565,9 @@ struct FitnessJob {
   const float* T = nullptr;  // column-major 4x4
 };
 ndt_status fitness_many(ndt_context* h, const std::vector<FitnessJob>& jobs, double max_range, double* out);
+// blocks of getFitnessScore over n source points (k_fitness's grid, a member's blocks of k_fitness_multi): 32 query teams per
+// block, at most 2048 blocks (the teams then stride over the queries)
+inline int fitness_blocks(int n) { return std::max(1, std::min(2048, (n + 31) / 32)); }
 ndt_status filter_slots(ndt_handle h, int which, FilterPending& P);
 // The geometry and route of one N1 filter, from the cloud's box alone -- the one decision voxel_filter_enqueue and the
 // batched filter (ndt_filter_batch.hip) both take: no finite point, PCL's index overflow (copy-through), the sparse index
