@@ -404,6 +404,42 @@ ndt_status ndt_batch_fitness_scores_device(ndt_handle h, const void* d_pts, cons
  * and the blocks of the largest (its partial rows, kEvalStride doubles each, are all that call held at once) */
 ndt_status ndt_diag_fitness_launches(ndt_handle h, size_t* launches, size_t* max_blocks);
 
+/* ---- one source, many poses (re-localisation in a map, loop-closure checks, recovery after a dropped scan) ------------
+ * The caller holds candidate poses of the handle's input source and wants the one that registers.
+ *
+ * ndt_score_poses: calculateScore (ndt_omp_impl.hpp:935-983) of the handle's input source moved by each of n_poses transforms
+ * (column-major 4x4 f32, as ndt_align's guess), against the handle's target grid, search method and Gauss constants.
+ * scores[g] is what ndt_calculate_score returns for pcl::transformPointCloud(source, transforms + 16 g) -- the same bits --
+ * without the host transform, the upload and the launches per pose: one launch scores up to NDT_SCORE_POSES_CHUNK poses
+ * (default 4096, 1 .. 65535; fewer while a chunk's partial rows would exceed 256 MiB), one read-back per launch.  The source
+ * is walked in the caller's order; non-finite points count in the divisor and add nothing; an empty grid gives 0.0, a pose
+ * that moves every point out of the grid gives 0.0, a source of no points gives NaN (0 / 0 in the reference).
+ * n_poses == 0: NDT_OK, nothing written, no device needed.  NDT_ERR_INVALID before any device work: NULL handle, NULL
+ * transforms or scores with n_poses > 0, a handle with a communicator or an all-reduce hook.  Then NDT_ERR_NO_DEVICE without
+ * a gfx950 device, NDT_ERR_NO_INPUT without a target or a source. */
+ndt_status ndt_score_poses(ndt_handle h, const float* transforms /* n_poses*16 */, size_t n_poses, double* scores /* n_poses */);
+/* diagnostics: the k_score_poses launches of the handle's last ndt_score_poses call that reached the device, and the blocks
+ * of all of them together (poses x the blocks ndt_calculate_score walks a cloud of the source's size with) */
+ndt_status ndt_diag_score_poses(ndt_handle h, size_t* launches, size_t* blocks);
+/* ndt_align of the handle's source against its target from each of n_guesses guesses, in lock-step (one source in HBM,
+ * every member a view of it).  Outputs as ndt_align_batch's, any may be NULL; *best = index of the largest
+ * transformation_probability (NaN never wins, ties to the lower index, -1 if none -- also for n_guesses == 0, which writes
+ * nothing else).  Member g's outputs are, bit for bit, those of member g of ndt_align_batch over the source repeated
+ * n_guesses times (a source of 65 536 points and more is read from the handle's own ordered copy: the order a batch gives
+ * it while its box has at most 4e6 cells of the resolution).  One lock-step loop (no batch groups); at most 65535 guesses.  Argument and state errors as
+ * ndt_score_poses.  The handle's own last result (ndt_get_result) is left as it was; ndt_get_stats follows ndt_align_batch. */
+ndt_status ndt_align_guesses(ndt_handle h, const float* guesses /* n_guesses*16 */, size_t n_guesses, float* final_transformations,
+                             int* has_converged, int* final_num_iteration, double* transformation_probability, int* best);
+/* indices of the `keep` largest finite scores, best first, ties to the lower index; *n_out <= keep (fewer when fewer are
+ * finite).  Host only. */
+void ndt_host_pick_top(const double* scores, size_t n, size_t keep, int* idx_out /* min(keep, n) */, size_t* n_out);
+/* ndt_score_poses over the candidates, ndt_host_pick_top, ndt_align_guesses from the picked ones.  picked[k] = candidate
+ * index of member k; the per-member outputs have *n_picked entries (room for min(keep, n_candidates)); *best indexes the
+ * candidates (-1 if none: no candidate, keep == 0, or no finite score).  Any output may be NULL. */
+ndt_status ndt_align_multistart(ndt_handle h, const float* candidates /* n_candidates*16 */, size_t n_candidates, size_t keep,
+                                int* picked, size_t* n_picked, float* final_transformations, int* has_converged,
+                                int* final_num_iteration, double* transformation_probability, int* best);
+
 /* ---- multi-GPU (one process per GPU, RCCL over xGMI) ---------------------------
  * The reference is a single process (ndt_omp_impl.hpp:206 is its only parallel construct); this is the exchange step
  * north_star adds.  Registrations of different scans are independent, so ndt_align_batch* on every rank over its own

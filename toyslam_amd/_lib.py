@@ -116,6 +116,11 @@ SIGNATURES = {
     "ndt_diag_fitness_launches": (C.c_int, [vp, szp, szp]),
     "ndt_batch_fitness_scores": (C.c_int, [vp, vp, szp, C.c_size_t, C.c_size_t, fp, C.c_double, dp]),
     "ndt_batch_fitness_scores_device": (C.c_int, [vp, vp, szp, C.c_size_t, C.c_size_t, fp, C.c_double, dp]),
+    "ndt_score_poses": (C.c_int, [vp, fp, C.c_size_t, dp]),
+    "ndt_diag_score_poses": (C.c_int, [vp, szp, szp]),
+    "ndt_align_guesses": (C.c_int, [vp, fp, C.c_size_t, fp, ip, ip, dp, ip]),
+    "ndt_host_pick_top": (None, [dp, C.c_size_t, C.c_size_t, ip, szp]),
+    "ndt_align_multistart": (C.c_int, [vp, fp, C.c_size_t, C.c_size_t, ip, szp, fp, ip, ip, dp, ip]),
     "ndt_align_batch_sharded": (C.c_int, [vp, vp, szp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, fp, fp, ip, ip, dp]),
     "ndt_align_batch_sharded_device": (C.c_int, [vp, vp, szp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, fp, fp, ip, ip, dp]),
     "ndt_comm_get_unique_id": (C.c_int, [vp]),

@@ -1,4 +1,5 @@
-// ndt_batch.hip -- lock-step batches (map-build mode: many sources against the one target) and the multi-GPU exchange step.
+// ndt_batch.hip -- lock-step batches (map-build mode: many sources against the one target; one source from many guesses:
+// ndt_align_guesses, ndt_align_multistart) and the multi-GPU exchange step.
 // (split out of the former single C-ABI unit; shared state in ndt_internal.hpp)
 #include "ndt_internal.hpp"
 
@@ -592,6 +593,14 @@ static ndt_status align_batch_grouped(ndt_handle h, const void* pts, const size_
 
 namespace ndtc {
 
+ndt_status many_poses_checks(const ndt_context* h, const void* table, size_t n, const void* out, const char* what) {
+  if (!h) return fail(NDT_ERR_INVALID, "null handle");
+  if (n && (!table || !out)) return fail(NDT_ERR_INVALID, std::string("null ") + what);
+  if (h->comm || h->allreduce)
+    return fail(NDT_ERR_INVALID, "one source under many poses is not sharded: the handle has a communicator or an all-reduce hook");
+  return NDT_OK;
+}
+
 size_t batch_group_count(const ndt_context* h, size_t n_scans) {
   static const int forced = [] { const char* v = getenv("NDT_BATCH_GROUPS"); return v ? std::max(1, atoi(v)) : 0; }();
   size_t groups = (h && h->batch_groups_wanted > 0) ? static_cast<size_t>(h->batch_groups_wanted)
@@ -695,6 +704,100 @@ ndt_status ndt_align_batch_sharded_device(ndt_handle h, const void* d_pts, const
                                           int* iters, double* tprob) {
   if (total_scans == 0) return fail(NDT_ERR_INVALID, "total_scans must be > 0");
   return align_batch_impl(h, d_pts, offsets, n_local, stride, true, guesses, final_T, conv, iters, tprob, first_scan, total_scans);
+}
+
+// ---- one source, many starting poses ---------------------------------------------------------------------
+// ndt_align of the handle's source from each of n_guesses guesses: a lock-step whose members are all the same segment of
+// one point buffer (the batch kernels read members through (offset, count) descriptors: views that alias need nothing new).
+// The buffer is the source as a batch orders a scan -- the handle's ordered copy where it has one (big scans), otherwise the
+// scan ordered here on its own lattice, as order_cloud orders every member of ndt_align_batch (a few small launches over
+// pool scratch, once per call whatever n_guesses is) -- so member g is, bit for bit, member g of ndt_align_batch over the
+// source repeated n_guesses times, without the n_guesses uploads and orderings.
+ndt_status ndt_align_guesses(ndt_handle h, const float* guesses, size_t n_guesses, float* final_T, int* conv, int* iters,
+                             double* tprob, int* best) {
+  ndt_status s = many_poses_checks(h, guesses, n_guesses, h, "guesses");
+  if (s) return s;
+  if (n_guesses > 65535) return fail(NDT_ERR_INVALID, "at most 65535 guesses per call");
+  if (n_guesses == 0) {
+    if (best) *best = -1;
+    return NDT_OK;
+  }
+  s = ensure_device(h);
+  if (s) return s;
+  if (!h->grid || !h->target) return fail(NDT_ERR_NO_INPUT, "no input target");
+  if (!h->source) return fail(NDT_ERR_NO_INPUT, "no input source");
+  s = maybe_compact_records(h, true);  // many registrations against this grid, as a batch
+  if (s) return s;
+  const DeviceCloud& src = *h->source;
+  DeviceCloud view;  // the source's points, borrowed, with an ordered copy of its own
+  LockStepMembers m;
+  m.pts = src.pts.p;
+  int count = static_cast<int>(src.n);
+  if (src.n_sorted > 0) {
+    m.pts = src.sorted.p;
+    count = static_cast<int>(src.n_sorted);
+  } else if (src.n > 0) {
+    view.pts.borrow(src.pts.p, src.n);
+    view.n = src.n;
+    const size_t offsets[2] = {0, src.n};
+    s = order_cloud(h, &view, offsets, 1);
+    if (s) return s;
+    if (view.n_sorted > 0 && !view.scan_counts.empty()) {
+      m.pts = view.sorted.p + view.scan_starts[0];
+      count = static_cast<int>(view.scan_counts[0]);
+    }
+  }
+  m.offset.assign(n_guesses, 0);
+  m.count.assign(n_guesses, count);
+  m.n_raw.assign(n_guesses, src.n);
+  std::vector<double> tp(n_guesses, 0.0);
+  s = lock_step(h, m, n_guesses, guesses, final_T, conv, iters, tp.data());
+  if (s) return s;
+  if (tprob) std::memcpy(tprob, tp.data(), n_guesses * sizeof(double));
+  if (best) {
+    *best = -1;
+    for (size_t g = 0; g < n_guesses; g++)
+      if (!std::isnan(tp[g]) && (*best < 0 || tp[g] > tp[*best])) *best = static_cast<int>(g);
+  }
+  return NDT_OK;
+}
+
+void ndt_host_pick_top(const double* scores, size_t n, size_t keep, int* idx_out, size_t* n_out) {
+  std::vector<int> idx;
+  for (size_t i = 0; scores && i < n; i++)
+    if (std::isfinite(scores[i])) idx.push_back(static_cast<int>(i));
+  const size_t k = std::min(keep, idx.size());
+  std::partial_sort(idx.begin(), idx.begin() + k, idx.end(),
+                    [&](int a, int b) { return scores[a] > scores[b] || (scores[a] == scores[b] && a < b); });
+  for (size_t i = 0; idx_out && i < k; i++) idx_out[i] = idx[i];
+  if (n_out) *n_out = k;
+}
+
+ndt_status ndt_align_multistart(ndt_handle h, const float* candidates, size_t n_candidates, size_t keep, int* picked,
+                                size_t* n_picked, float* final_T, int* conv, int* iters, double* tprob, int* best) {
+  ndt_status s = many_poses_checks(h, candidates, n_candidates, h, "candidates");
+  if (s) return s;
+  if (n_candidates > static_cast<size_t>(std::numeric_limits<int>::max())) return fail(NDT_ERR_INVALID, "too many candidates");
+  if (std::min(keep, n_candidates) > 65535) return fail(NDT_ERR_INVALID, "at most 65535 guesses are registered per call");
+  if (n_picked) *n_picked = 0;
+  if (best) *best = -1;
+  if (n_candidates == 0 || keep == 0) return NDT_OK;
+  std::vector<double> scores(n_candidates);
+  s = ndt_score_poses(h, candidates, n_candidates, scores.data());
+  if (s) return s;
+  std::vector<int> idx(std::min(keep, n_candidates));
+  size_t np = 0;
+  ndt_host_pick_top(scores.data(), n_candidates, keep, idx.data(), &np);
+  if (np == 0) return NDT_OK;  // no candidate with a finite score
+  std::vector<float> guesses(16 * np);
+  for (size_t k = 0; k < np; k++) std::memcpy(guesses.data() + 16 * k, candidates + 16 * static_cast<size_t>(idx[k]), 16 * sizeof(float));
+  int b = -1;
+  s = ndt_align_guesses(h, guesses.data(), np, final_T, conv, iters, tprob, &b);
+  if (s) return s;
+  if (picked) std::memcpy(picked, idx.data(), np * sizeof(int));
+  if (n_picked) *n_picked = np;
+  if (best) *best = b >= 0 ? idx[b] : -1;
+  return NDT_OK;
 }
 
 void ndt_host_thread_budget(int* affinity_cpus, double* quota_cpus, int* local_world_size) {

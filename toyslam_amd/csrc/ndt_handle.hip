@@ -21,6 +21,7 @@ void ndt_context::release_buffers() {
   server_dev_mb.release();
   server_counter.release();
   server_dbg.release();
+  sp_poses.release();
 }
 
 namespace ndtc {

@@ -3,10 +3,12 @@
 // itself, and the helpers one unit offers the others.  Not installed; nothing here crosses the C-ABI.
 //   ndt_handle.hip : handle lifetime, parameters, results, profiling switches, host-only scalar exports
 //   ndt_grid.hip   : cloud upload, bounding boxes, spatial ordering, K1 target grid build (dense / sparse index),
-//                    N1 voxel filter, N2 map accumulation, getFitnessScore, calculateScore, grid inspection
+//                    N1 voxel filter, N2 map accumulation, getFitnessScore, calculateScore (of a cloud, of the source under
+//                    many poses), grid inspection
 //   ndt_eval.hip   : one evaluation (launch path), the persistent evaluation server's host side (mailbox protocol),
 //                    ndt_align, ndt_eval*, diagnostics and self-tests
-//   ndt_batch.hip  : lock-step batches (ndt_align_batch*), the RCCL communicator (ndt_comm_*), ndt_set_allreduce
+//   ndt_batch.hip  : lock-step batches (ndt_align_batch*, ndt_align_guesses, ndt_align_multistart), the RCCL communicator
+//                    (ndt_comm_*), ndt_set_allreduce
 //   ndt_io.hip     : PCD files, numbered scan sequences, PointCloud2-style repacking (host)
 //   gicp_capi.hip  : the GICP row
 #pragma once
@@ -447,6 +449,12 @@ struct ndt_context {
   void* mb_pinned = nullptr;
   size_t mb_pinned_bytes = 0;
   size_t mb_transform_launches = 0, mb_filters = 0, mb_box_passes = 0;
+  // ndt_score_poses (ndt_grid.hip): the pose table of one chunk (12 row-major floats per pose) in page-locked memory and in
+  // HBM, and what the last call did (ndt_diag_score_poses)
+  void* sp_pinned = nullptr;
+  size_t sp_pinned_bytes = 0;
+  DevBuf<float> sp_poses;
+  size_t sp_launches = 0, sp_blocks = 0;
 
   ~ndt_context() {
     for (ndt_context* w : batch_workers) delete w;
@@ -479,6 +487,7 @@ struct ndt_context {
     if (fb_pinned) (void)hipHostFree(fb_pinned);
     if (fb_rows) (void)hipHostFree(fb_rows);
     if (mb_pinned) (void)hipHostFree(mb_pinned);
+    if (sp_pinned) (void)hipHostFree(sp_pinned);
     release_buffers();
     if (host_result) (void)hipHostFree(host_result);
     if (host_pub) (void)hipHostFree(host_pub);
@@ -623,6 +632,9 @@ struct LockStepMembers {
 };
 ndt_status lock_step(ndt_context* h, const LockStepMembers& m, size_t n_local, const float* guesses, float* final_T, int* conv,
                      int* iters, double* tprob, size_t first = 0, size_t total = 0);
+// what ndt_score_poses, ndt_align_guesses and ndt_align_multistart refuse before any device work: a null handle, a null
+// table with entries, a handle with a communicator or an all-reduce hook
+ndt_status many_poses_checks(const ndt_context* h, const void* table, size_t n, const void* out, const char* what);
 size_t batch_group_count(const ndt_context* h, size_t n_members);
 // runs run(worker, lo, hi) for member ranges [lo, hi) of n_members, one worker handle and host thread per group (grid and
 // parameters of h copied), and gathers the workers' statistics into h; pts_of(lo, hi): the points of those members

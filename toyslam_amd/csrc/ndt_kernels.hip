@@ -5,7 +5,7 @@
 //  K2  per-evaluation score / gradient / Hessian (computeDerivatives, ndt_omp_impl.hpp:179-285 with updateDerivatives
 //      :484-537 fused with the f32 point transform): k_derivatives (one launch per evaluation, also over a whole lock-step
 //      batch), k_batch_step (mixed-kind batch steps), the all-f64 Hessian k_hessian64 (computeHessian :540-645), k_reduce
-//      (fixed-order sum of the per-block rows), calculateScore (:935-983), getFitnessScore (k_fitness; k_fitness_multi +
+//      (fixed-order sum of the per-block rows), calculateScore (:935-983; k_score_poses: of one source under many poses), getFitnessScore (k_fitness; k_fitness_multi +
 //      k_fitness_reduce for many members in one launch) and the search index it walks (k_cell_ranges, k_gather_points).
 //
 // Gather work: no MFMA (there is no dense contraction).  Loads are 16 B per lane (float4 points, 3 x dwordx4 per 64-B
@@ -484,7 +484,39 @@ __global__ __launch_bounds__(kBlock) void k_transform_multi(const TransformScan*
   }
 }
 
-// calculateScore (ndt_omp_impl.hpp:935-983): cloud used as given, f64 throughout
+// calculateScore (ndt_omp_impl.hpp:935-983) of ONE point, used as given, f64 throughout: its score increments are added to
+// `acc`.  The one body of k_calc_score and k_score_poses: a point gets the same terms in the same order from either.
+template <int NNB>
+__device__ __forceinline__ void calc_score_point(const GridView& gv, float px, float py, float pz, double d1, double d2, double d3,
+                                                 float r2, double& acc) {
+  if (!finite3(px, py, pz)) return;  // no neighbourhood in the reference (garbage voxel index): adds nothing
+  int vi, vj, vk;
+  search_ijk(gv.g, px, py, pz, vi, vj, vk);
+  if (!near_grid(gv.g, vi, vj, vk)) return;
+  const unsigned centre = lut_index(gv.g, vi, vj, vk);
+  int rec[NNB];
+  int cnt = 0;
+  for (int k = 0; k < NNB; k++) {
+    int dx, dy, dz;
+    nb_offset<NNB>(k, dx, dy, dz);
+    rec[k] = (NNB == 27) ? probe_kd(gv, vi, vj, vk, centre, dx, dy, dz, px, py, pz, r2) : probe(gv, vi, vj, vk, centre, dx, dy, dz);
+    cnt += (rec[k] >= 0);
+  }
+  for (int k = 0; k < NNB; k++) {
+    if (rec[k] < 0) continue;
+    const double* mu = gv.recs[rec[k]].mean;
+    const double* ic = gv.centroids[rec[k]].icov;  // the leaf's f64 icov_ (:966)
+    const double x0 = static_cast<double>(px) - mu[0], x1 = static_cast<double>(py) - mu[1], x2 = static_cast<double>(pz) - mu[2];
+    const double c00 = ic[0], c01 = ic[1], c02 = ic[2], c11 = ic[3], c12 = ic[4], c22 = ic[5];
+    const double c0 = (c00 * x0 + c01 * x1) + c02 * x2;
+    const double c1 = (c01 * x0 + c11 * x1) + c12 * x2;
+    const double c2 = (c02 * x0 + c12 * x1) + c22 * x2;
+    const double e = exp(-d2 * ((x0 * c0 + x1 * c1) + x2 * c2) / 2);
+    acc += (-d1 * e - d3) / cnt;
+  }
+}
+
+// calculateScore of a cloud used as given
 template <int NNB>
 __global__ __launch_bounds__(kBlock) void k_calc_score(const float4* __restrict__ cloud, int n, GridView gv, double d1,
                                                        double d2, double d3, float r2, double* __restrict__ partials) {
@@ -492,33 +524,32 @@ __global__ __launch_bounds__(kBlock) void k_calc_score(const float4* __restrict_
   double acc[1] = {0.0};
   for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
     const float4 pt = cloud[i];
-    if (!finite3(pt.x, pt.y, pt.z)) continue;  // no neighbourhood in the reference (garbage voxel index): adds nothing
-    int vi, vj, vk;
-    search_ijk(gv.g, pt.x, pt.y, pt.z, vi, vj, vk);
-    if (!near_grid(gv.g, vi, vj, vk)) continue;
-    const unsigned centre = lut_index(gv.g, vi, vj, vk);
-    int rec[NNB];
-    int cnt = 0;
-    for (int k = 0; k < NNB; k++) {
-      int dx, dy, dz;
-      nb_offset<NNB>(k, dx, dy, dz);
-      rec[k] = (NNB == 27) ? probe_kd(gv, vi, vj, vk, centre, dx, dy, dz, pt.x, pt.y, pt.z, r2) : probe(gv, vi, vj, vk, centre, dx, dy, dz);
-      cnt += (rec[k] >= 0);
-    }
-    for (int k = 0; k < NNB; k++) {
-      if (rec[k] < 0) continue;
-      const double* mu = gv.recs[rec[k]].mean;
-      const double* ic = gv.centroids[rec[k]].icov;  // the leaf's f64 icov_ (:966)
-      const double x0 = static_cast<double>(pt.x) - mu[0], x1 = static_cast<double>(pt.y) - mu[1], x2 = static_cast<double>(pt.z) - mu[2];
-      const double c00 = ic[0], c01 = ic[1], c02 = ic[2], c11 = ic[3], c12 = ic[4], c22 = ic[5];
-      const double c0 = (c00 * x0 + c01 * x1) + c02 * x2;
-      const double c1 = (c01 * x0 + c11 * x1) + c12 * x2;
-      const double c2 = (c02 * x0 + c12 * x1) + c22 * x2;
-      const double e = exp(-d2 * ((x0 * c0 + x1 * c1) + x2 * c2) / 2);
-      acc[0] += (-d1 * e - d3) / cnt;
-    }
+    calc_score_point<NNB>(gv, pt.x, pt.y, pt.z, d1, d2, d3, r2, acc[0]);
   }
   block_reduce_store<1>(acc, partials + static_cast<size_t>(blockIdx.x) * kEvalStride, lds);
+}
+
+// calculateScore of ONE resident source moved by MANY transforms (ndt_score_poses): blockIdx.y = pose of the chunk,
+// blockIdx.x = block of the point walk -- k_calc_score's walk (same grid extent, same stride: a thread meets the same points in
+// the same order), every point moved by the pose first.  xform_point is k_transform's arithmetic, so the moved point is the
+// record launch_transform would have written and the row is the one k_calc_score writes for that moved cloud.  The pose
+// (12 row-major floats) is block-uniform: scalar loads.  Rows: partials[pose][block][kEvalStride], for one launch_reduce.
+template <int NNB>
+__global__ __launch_bounds__(kBlock) void k_score_poses(const float4* __restrict__ src, int n, GridView gv, const float* __restrict__ poses,
+                                                        double d1, double d2, double d3, float r2, double* __restrict__ partials) {
+  __shared__ double lds[(kBlock / kWave) * 32];
+  float T[12];
+  const float* __restrict__ Tg = poses + static_cast<size_t>(blockIdx.y) * 12;
+#pragma unroll
+  for (int k = 0; k < 12; k++) T[k] = Tg[k];
+  double acc[1] = {0.0};
+  for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+    const float4 pt = src[i];
+    float tx, ty, tz;
+    xform_point(T, pt.x, pt.y, pt.z, tx, ty, tz);
+    calc_score_point<NNB>(gv, tx, ty, tz, d1, d2, d3, r2, acc[0]);
+  }
+  block_reduce_store<1>(acc, partials + (static_cast<size_t>(blockIdx.y) * gridDim.x + blockIdx.x) * kEvalStride, lds);
 }
 
 inline int grid_for(size_t n, int max_blocks) {
@@ -660,6 +691,17 @@ hipError_t launch_calc_score(const float4* cloud, int n, const GridView& gv, dou
     hipLaunchKernelGGL(k_calc_score<1>, dim3(n_blocks), dim3(kBlock), 0, stream, cloud, n, gv, d1, d2, d3, r2, partials);
   else
     hipLaunchKernelGGL(k_calc_score<7>, dim3(n_blocks), dim3(kBlock), 0, stream, cloud, n, gv, d1, d2, d3, r2, partials);
+  return hipGetLastError();
+}
+
+hipError_t launch_score_poses(const float4* src, int n, const GridView& gv, const float* d_poses, int n_poses, double d1, double d2,
+                              double d3, int search, float r2, int n_blocks, double* partials, hipStream_t stream) {
+  if (n_poses <= 0) return hipSuccess;
+  const dim3 grid(n_blocks, n_poses), block(kBlock);
+  if (search == 0) hipLaunchKernelGGL(k_score_poses<27>, grid, block, 0, stream, src, n, gv, d_poses, d1, d2, d3, r2, partials);
+  else if (search == 1) hipLaunchKernelGGL(k_score_poses<26>, grid, block, 0, stream, src, n, gv, d_poses, d1, d2, d3, r2, partials);
+  else if (search == 3) hipLaunchKernelGGL(k_score_poses<1>, grid, block, 0, stream, src, n, gv, d_poses, d1, d2, d3, r2, partials);
+  else hipLaunchKernelGGL(k_score_poses<7>, grid, block, 0, stream, src, n, gv, d_poses, d1, d2, d3, r2, partials);
   return hipGetLastError();
 }
 

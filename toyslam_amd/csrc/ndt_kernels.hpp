@@ -386,6 +386,11 @@ hipError_t launch_transform_multi(const TransformScan* d_scans, const int* d_sta
                                   hipStream_t stream);
 hipError_t launch_calc_score(const float4* cloud, int n, const GridView& gv, double d1, double d2, double d3,
                              int search, float r2, int n_blocks, double* partials, hipStream_t stream);
+// calculateScore of src moved by each of n_poses (<= 65535) transforms (d_poses: 12 row-major floats per pose, device memory):
+// grid (n_blocks, n_poses), rows partials[pose][n_blocks][kEvalStride] (slot 0 written) for launch_reduce(partials, n_blocks,
+// n_poses).  With n_blocks = launch_calc_score's, pose g's rows are the ones launch_calc_score writes for launch_transform's cloud.
+hipError_t launch_score_poses(const float4* src, int n, const GridView& gv, const float* d_poses, int n_poses, double d1, double d2,
+                              double d3, int search, float r2, int n_blocks, double* partials, hipStream_t stream);
 
 hipError_t launch_voxel_centroids(const float4* pts, const unsigned* leaf_start, const int* leaf_count, int n_leaves,
                                   int* sorted_idx, float4* out, hipStream_t stream, const unsigned* d_totals = nullptr,

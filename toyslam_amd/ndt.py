@@ -550,6 +550,68 @@ class NormalDistributionsTransform:
                  _d(out)))
         return out[:B].copy()
 
+    # ---- one source, many poses (ndt_score_poses / ndt_align_guesses / ndt_align_multistart) -------
+    @staticmethod
+    def _pose_table(poses):
+        """(G, 16) float32 column-major table of G 4x4 transforms (a list, or one (G, 4, 4) array; G may be 0)."""
+        a = np.asarray(poses, dtype=np.float32)
+        if a.size == 0:
+            return np.zeros((0, 16), dtype=np.float32)
+        if a.ndim != 3 or a.shape[1:] != (4, 4):
+            raise ValueError("poses must be G transforms of 4x4")
+        return np.ascontiguousarray(a.transpose(0, 2, 1)).reshape(-1, 16)
+
+    def scorePoses(self, transforms):
+        """calculateScore of the input source moved by each of the 4x4 transforms, all poses in one launch per chunk:
+        (G,) float64, entry g the bits of calculateScore(transformPointCloud(source, transforms[g]))."""
+        T = self._pose_table(transforms)
+        G = T.shape[0]
+        out = np.zeros(max(G, 1), dtype=np.float64)
+        check(self._L.ndt_score_poses(self._h, _f(T) if G else None, G, _d(out)))
+        return out[:G].copy()
+
+    def scorePosesLaunches(self):
+        """(launches, blocks of all of them) of the last scorePoses (ndt_diag_score_poses)."""
+        a, b = C.c_size_t(0), C.c_size_t(0)
+        check(self._L.ndt_diag_score_poses(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def alignGuesses(self, guesses):
+        """Register the input source from each of the 4x4 guesses in lock-step (ndt_align_guesses).  Returns alignBatch's
+        dict, one entry per guess, plus best = index of the largest transformation probability (-1 if none)."""
+        g = self._pose_table(guesses)
+        G = g.shape[0]
+        T = np.zeros((max(G, 1), 16), dtype=np.float32)
+        conv = np.zeros(max(G, 1), dtype=np.int32)
+        it = np.zeros(max(G, 1), dtype=np.int32)
+        tp = np.zeros(max(G, 1), dtype=np.float64)
+        best = C.c_int(-1)
+        check(self._L.ndt_align_guesses(self._h, _f(g) if G else None, G, _f(T), _i(conv), _i(it), _d(tp), C.byref(best)))
+        return dict(T=np.stack([_from_colmajor(T[k]) for k in range(G)]) if G else np.zeros((0, 4, 4), np.float32),
+                    converged=conv[:G].astype(bool), iterations=it[:G].copy(), trans_probability=tp[:G].copy(), best=best.value)
+
+    def alignMultistart(self, candidates, keep):
+        """scorePoses over the candidates, the `keep` best of them (host_pick_top) as the guesses of one alignGuesses
+        (ndt_align_multistart).  Returns alignGuesses' dict over the picked members, plus picked = their candidate indices;
+        best indexes the candidates."""
+        c = self._pose_table(candidates)
+        n, keep = c.shape[0], int(keep)
+        if keep < 0:
+            raise ValueError("keep must be >= 0")
+        room = max(min(keep, n), 1)
+        picked = np.zeros(room, dtype=np.int32)
+        T = np.zeros((room, 16), dtype=np.float32)
+        conv = np.zeros(room, dtype=np.int32)
+        it = np.zeros(room, dtype=np.int32)
+        tp = np.zeros(room, dtype=np.float64)
+        n_picked, best = C.c_size_t(0), C.c_int(-1)
+        check(self._L.ndt_align_multistart(self._h, _f(c) if n else None, n, keep, _i(picked), C.byref(n_picked), _f(T), _i(conv),
+                                           _i(it), _d(tp), C.byref(best)))
+        P = n_picked.value
+        return dict(T=np.stack([_from_colmajor(T[k]) for k in range(P)]) if P else np.zeros((0, 4, 4), np.float32),
+                    converged=conv[:P].astype(bool), iterations=it[:P].copy(), trans_probability=tp[:P].copy(),
+                    picked=picked[:P].copy(), best=best.value)
+
     def pairsGrid(self, c):
         """The grid the last alignPairs built for target cloud c, in the layout of grid()."""
         nl, nv = C.c_size_t(0), C.c_size_t(0)
@@ -818,6 +880,16 @@ def host_angle_derivatives(p):
     hd = np.zeros((15, 3))
     _lib.lib().ndt_host_angle_derivatives(_d(p), _f(j), _f(h), _d(jd), _d(hd))
     return j, h, jd, hd
+
+
+def host_pick_top(scores, keep):
+    """Indices of the `keep` largest finite scores, best first, ties to the lower index (ndt_host_pick_top)."""
+    s = np.ascontiguousarray(scores, dtype=np.float64).reshape(-1)
+    keep = int(keep)
+    idx = np.zeros(max(min(keep, s.shape[0]), 1), dtype=np.int32)
+    n = C.c_size_t(0)
+    _lib.lib().ndt_host_pick_top(_d(s), s.shape[0], keep, _i(idx), C.byref(n))
+    return idx[:n.value].copy()
 
 
 def host_thread_budget():
