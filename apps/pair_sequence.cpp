@@ -11,10 +11,12 @@
 // --gicp: the same consecutive pairs through gicp_align_pairs_clouds (pclomp::GeneralizedIterativeClosestPoint with its
 // constructor's settings, as apps/align.cpp runs it) in place of the NDT pairs call: every filtered scan indexed once, the
 // k-NN covariances of all scans from one launch; poses chained as for NDT.  With --fitness the scores come from the same call.
+// --gicp --lockstep: the same through gicp_align_pairs_lockstep (the registrations advanced together: one correspondence
+// launch and one objective launch per step for all pairs in flight); it prints the lines --gicp prints.
 // --map <out.pcd>: after the pose chain, all filtered scans at their chained poses (scan 0 at the identity) go into the map
 // in ONE ndt_map_update_clouds call at the node's 0.5 m; "map: <n> points", and the map written as a binary PCD.
 //
-//   pair_sequence <pcd_directory> [--fitness] [--batch-filter] [--gicp] [--map <out.pcd>]
+//   pair_sequence <pcd_directory> [--fitness] [--batch-filter] [--gicp [--lockstep]] [--map <out.pcd>]
 #include <cfloat>
 #include <chrono>
 #include <cstdio>
@@ -43,18 +45,19 @@ static double since(clock_type::time_point a) { return std::chrono::duration<dou
 
 int main(int argc, char** argv) {
   if (argc < 2) {
-    std::printf("usage: pair_sequence <pcd_directory> [--fitness] [--batch-filter] [--gicp] [--map <out.pcd>]\n");
+    std::printf("usage: pair_sequence <pcd_directory> [--fitness] [--batch-filter] [--gicp [--lockstep]] [--map <out.pcd>]\n");
     return 0;
   }
-  bool want_fitness = false, batch_filter = false, use_gicp = false;
+  bool want_fitness = false, batch_filter = false, use_gicp = false, lockstep = false;
   const char* map_path = nullptr;
   for (int a = 2; a < argc; a++) {
     if (std::strcmp(argv[a], "--fitness") == 0) want_fitness = true;
     if (std::strcmp(argv[a], "--batch-filter") == 0) batch_filter = true;
     if (std::strcmp(argv[a], "--gicp") == 0) use_gicp = true;
+    if (std::strcmp(argv[a], "--lockstep") == 0) lockstep = true;
     if (std::strcmp(argv[a], "--map") == 0) {
       if (a + 1 >= argc) {
-        std::fprintf(stderr, "--map needs a file name\nusage: pair_sequence <pcd_directory> [--fitness] [--batch-filter] [--gicp] [--map <out.pcd>]\n");
+        std::fprintf(stderr, "--map needs a file name\nusage: pair_sequence <pcd_directory> [--fitness] [--batch-filter] [--gicp [--lockstep]] [--map <out.pcd>]\n");
         return 2;
       }
       map_path = argv[++a];
@@ -148,7 +151,10 @@ int main(int argc, char** argv) {
   gicp_handle gh = nullptr;
   if (use_gicp) CHECK(gicp_create(0, &gh));
   const auto t_align = clock_type::now();
-  if (use_gicp)
+  if (use_gicp && lockstep)
+    CHECK(gicp_align_pairs_lockstep(gh, clouds.data(), clouds.size(), pairs.data(), n_pairs, nullptr, DBL_MAX /* PCL's default */, T.data(),
+                                    conv.data(), iters.data(), nullptr, want_fitness ? fitness.data() : nullptr));
+  else if (use_gicp)
     CHECK(gicp_align_pairs_clouds(gh, clouds.data(), clouds.size(), pairs.data(), n_pairs, nullptr, DBL_MAX /* PCL's default */, T.data(),
                                   conv.data(), iters.data(), nullptr, want_fitness ? fitness.data() : nullptr));
   else

@@ -88,6 +88,32 @@ ndt_status gicp_diag_pairs(gicp_handle h, size_t* index_builds, size_t* knn_laun
  * covariance launch, waited for) and the registrations with their fitness scores (tools/time_gicp_pairs.py) */
 ndt_status gicp_diag_pairs_time(gicp_handle h, double* prepare_ms, double* register_ms);
 
+/* gicp_align_pairs_clouds with the registrations ADVANCED TOGETHER instead of one after the other: the same arguments, the
+ * same checks and messages, the same preparation (one function serves both calls), the same records for
+ * gicp_pairs_covariances / gicp_diag_pairs / gicp_diag_pairs_time, the same "nothing written on error" -- and for pair k
+ * the same bits, whatever the other pairs, their order and the window.  Every pair in flight runs the existing outer
+ * loop and BFGS on a host thread of its own; a step is one k_correspond_multi launch for the members that need new
+ * correspondences and one k_functor_multi launch that evaluates every waiting member's objective at its own pose in its
+ * own mode (no persistent kernel, no waiting on the device).  At most 32 pairs are in flight (NDT_GICP_LOCKSTEP_MEMBERS:
+ * 1 ... 256); when one ends the next pair starts at the following step.  A list that repeats (target, source) with
+ * different guesses is a multi-start: the clouds are prepared once.  The handle's own inputs, covariances, result,
+ * statistics and step scratch are left as they were. */
+ndt_status gicp_align_pairs_lockstep(gicp_handle h, const ndt_cloud* clouds, size_t n_clouds, const int* pairs, size_t n_pairs,
+                                     const float* guesses, double max_range, float* final_T, int* converged,
+                                     int* n_iterations, int* correspondences, double* fitness);
+/* The handle's own source registered onto its own target from each of n_guesses guesses (n*16 column-major), all of them
+ * members of one lock-step.  The covariances are computed once -- the handle's k-NN ones, or the ones the caller set.
+ * Output g (n_guesses entries each, any may be NULL; fitness NULL = not computed) has the bits of gicp_align(guess g)
+ * followed by gicp_get_stats / gicp_get_fitness_score(max_range) on this handle.  gicp_get_result, gicp_get_stats and the
+ * handle's covariances are left as they were.  n_guesses == 0: NDT_OK, no device and no inputs needed.  Otherwise
+ * NDT_ERR_NO_INPUT without both inputs; NDT_ERR_INVALID: more than 65535 guesses, NULL guesses.  Nothing written on error. */
+ndt_status gicp_align_guesses(gicp_handle h, const float* guesses /* n*16 */, size_t n_guesses, double max_range,
+                              float* final_T, int* converged, int* n_iterations, int* correspondences, double* fitness);
+/* the last successful lock-step call of either kind (NDT_ERR_NO_INPUT otherwise): its steps, the steps with a
+ * k_correspond_multi launch, its k_functor_multi launches (one per step), and the most members one step carried */
+ndt_status gicp_diag_lockstep(gicp_handle h, size_t* steps, size_t* correspond_launches, size_t* functor_launches,
+                              size_t* max_members_in_step);
+
 /* pcl::Registration::align(output, guess) -> computeTransformation (gicp_omp_impl.hpp:372-517).
  * guess / final_T: column-major 4x4 f32 (Eigen::Matrix4f::data()), guess may be NULL (identity).
  * out_cloud: NULL or n_source records of stride 16 bytes (x, y, z, 1). */

@@ -181,6 +181,9 @@ SIGNATURES = {
     "gicp_set_input_target_cloud": (C.c_int, [vp, vp]),
     "gicp_set_input_source_cloud": (C.c_int, [vp, vp]),
     "gicp_align_pairs_clouds": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, ip, C.c_size_t, fp, C.c_double, fp, ip, ip, ip, dp]),
+    "gicp_align_pairs_lockstep": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, ip, C.c_size_t, fp, C.c_double, fp, ip, ip, ip, dp]),
+    "gicp_align_guesses": (C.c_int, [vp, fp, C.c_size_t, C.c_double, fp, ip, ip, ip, dp]),
+    "gicp_diag_lockstep": (C.c_int, [vp, szp, szp, szp, szp]),
     "gicp_pairs_covariances": (C.c_int, [vp, C.c_size_t, dp]),
     "gicp_diag_pairs": (C.c_int, [vp, szp, szp, szp]),
     "gicp_diag_pairs_time": (C.c_int, [vp, dp, dp]),

@@ -10,6 +10,8 @@
 // builds that one and runs its k-NN covariances next to the target's.  Neither keeps a cloud or a grid between calls.
 #include "ndt_internal.hpp"
 
+#include "gicp_lockstep.hpp"
+
 struct LeafHint {  // consecutive clouds have about the same density: the index leaf the previous one ended up with, and its size
   float leaf = 0.f;
   size_t n = 0;
@@ -61,6 +63,16 @@ struct gicp_context {
   size_t pairs_index_builds = 0, pairs_knn_launches = 0, pairs_knn_blocks = 0;
   double pairs_prepare_ms = 0, pairs_register_ms = 0;  // host wall clock of the call's two halves (tools/time_gicp_pairs.py)
   DevBuf<unsigned char> member_table;  // the member tables of the finite check and of k_knn_covariances_multi
+  // the lock-step (gicp_align_pairs_lockstep, gicp_align_guesses): the slots' tagged rows and the tables' staging in pinned
+  // host memory, the tables, partial rows and ticket counters on the device (grow-only, sized by the window); what the
+  // last successful call did (gicp_diag_lockstep)
+  void* ls_host = nullptr;
+  int ls_slots = 0;
+  DevBuf<unsigned char> ls_tables;
+  DevBuf<double> ls_partials;
+  DevBuf<unsigned> ls_counters;
+  bool ls_valid = false;
+  gicp::LockstepStats ls_stats;
   DevBuf<unsigned> finite_counts;
   // the last gicp_align's result
   gicp::Result result;
@@ -83,6 +95,7 @@ struct gicp_context {
     if (ev_src) (void)hipEventDestroy(ev_src);
     if (srv_mbs) (void)hipFree(srv_mbs);
     if (srv_rows) (void)hipHostFree(srv_rows);
+    if (ls_host) (void)hipHostFree(ls_host);
   }
 };
 
@@ -325,14 +338,18 @@ ndt_status gicp_read_covariances(gicp_context* h, const GicpInput& in, double* c
 
 // covariances of both clouds + the guess-moved source (:385-403); guess_rm: the guess, row-major.  An input that has its
 // covariances (every record of a pairs call) launches nothing here: only the handle's own source ever uses src's stream.
-ndt_status gicp_prepare(gicp_context* h, GicpInput& tgt, GicpInput& src, const float* guess_cm, float guess_rm[16]) {
+ndt_status gicp_prepare_covariances(gicp_context* h, GicpInput& tgt, GicpInput& src) {
   ndt_status s = gicp_scratch(h);
   if (s) return s;
   s = gicp_cloud_covariances(h, src, true, false);  // (source first: it runs on its own stream while the target's is queued here)
   if (s) return s;
   s = gicp_cloud_covariances(h, tgt, false, false);
   if (s) return s;
-  s = gicp_join_source(h);
+  return gicp_join_source(h);
+}
+
+ndt_status gicp_prepare(gicp_context* h, GicpInput& tgt, GicpInput& src, const float* guess_cm, float guess_rm[16]) {
+  ndt_status s = gicp_prepare_covariances(h, tgt, src);
   if (s) return s;
   const size_t n = src.n();
   rowmajor_from_colmajor(guess_cm, guess_rm);
@@ -354,17 +371,15 @@ struct GicpDevice : gicp::Backend {
   // The line search evaluates operator() and then, if the step passes Fletcher's rho test, df at the very same
   // point (gicp_driver.cpp line_search): the operator() launch also accumulates df's sums, and the df request that
   // follows is answered from here without a launch.
-  bool fuse = std::getenv("NDT_GICP_NO_FUSE") == nullptr;
+  // (gicp::SumsPlan: the mapping the lock-step's members use too)
+  gicp::SumsPlan plan{gicp::fuse_enabled()};
   int evals_served = 0;
-  bool have_grad = false;
-  float grad_T[16];
-  gicp::FunctorSums grad_sums;
   GicpDevice(gicp_context* ctx, const GicpInput& target, const GicpInput& source) : h(ctx), tgt(target), src(source) {}
 
   bool correspond(const float transformation[16], const double R[9]) override {
     gicp::Rot3d rot;
     for (int i = 0; i < 9; i++) rot.m[i] = R[i];
-    have_grad = false;
+    plan.invalidate();
     server_stop();  // the correspondences change: the next BFGS run gets a fresh server behind this kernel
     const double thr = h->prm.corr_dist_threshold * h->prm.corr_dist_threshold;  // :401
     const int n = static_cast<int>(src.n());
@@ -455,12 +470,9 @@ struct GicpDevice : gicp::Backend {
   }
 
   bool sums(int mode, const float T[16], gicp::FunctorSums& out) override {
-    if (mode == 1 && have_grad && std::memcmp(T, grad_T, sizeof(grad_T)) == 0) {
-      out = grad_sums;
-      return true;
-    }
+    if (plan.answered(mode, T, out)) return true;
     const int n = static_cast<int>(src.n());
-    const int launch_mode = (mode == 0 && fuse) ? 3 : mode;
+    const int launch_mode = plan.launch_mode(mode);
     double row[ndt::kEvalStride];
     bool have_row = false;
     if (server_available()) {
@@ -496,15 +508,8 @@ struct GicpDevice : gicp::Backend {
       }
       pub_gather(h->host_pub, row);
     }
-    out.f = row[0];
-    for (int i = 0; i < 3; i++) out.g[i] = row[1 + i];
-    for (int i = 0; i < 9; i++) out.R[i] = row[4 + i];
-    out.m = row[13];
-    if (launch_mode == 3) {  // slot 0 is operator()'s value; keep the gradient sums for the df that follows
-      have_grad = true;
-      std::memcpy(grad_T, T, sizeof(grad_T));
-      grad_sums = out;
-    }
+    gicp::sums_from_row(row, out);
+    plan.keep(launch_mode, T, out);
     return true;
   }
   ~GicpDevice() override { server_stop(); }
@@ -523,6 +528,228 @@ gicp::Result gicp_register(gicp_context* h, GicpInput& tgt, GicpInput& src, cons
   dev.server_stop();  // before anything else is queued on the stream or waited for: the server would sit out its patience
   if (r.backend_failed || !dev.error.empty()) *status = fail(NDT_ERR_HIP, dev.error.empty() ? "device failure" : dev.error);
   return r;
+}
+
+// ---- the lock-step: the device side of gicp::run_lockstep ----------------------------------------------------------
+// One registration of the lock-step: two inputs and a guess.
+struct LockstepJob {
+  const GicpInput* tgt;
+  const GicpInput* src;
+  float guess_rm[16];
+};
+
+size_t ls_align(size_t v) { return (v + 255) & ~static_cast<size_t>(255); }
+
+// The slots' memory for a window of `slots` members (grow-only; the counters are zeroed at every call: a failed step may
+// have left tickets behind).  Pinned: [slots] tagged rows, then the staging of the three tables; device: the three tables.
+struct LockstepLayout {
+  size_t rows = 0, members = 0, corr = 0, functor = 0, host_bytes = 0, dev_members = 0, dev_corr = 0, dev_functor = 0, dev_bytes = 0;
+  explicit LockstepLayout(size_t w) {
+    members = rows + ls_align(w * ndt::kPublishSlots * sizeof(double));
+    corr = members + ls_align(w * sizeof(gicp::LockstepMember));
+    functor = corr + ls_align(w * sizeof(gicp::LockstepCorrespond));
+    host_bytes = functor + ls_align(w * sizeof(gicp::LockstepFunctor));
+    dev_corr = dev_members + ls_align(w * sizeof(gicp::LockstepMember));
+    dev_functor = dev_corr + ls_align(w * sizeof(gicp::LockstepCorrespond));
+    dev_bytes = dev_functor + ls_align(w * sizeof(gicp::LockstepFunctor));
+  }
+};
+
+ndt_status gicp_lockstep_scratch(gicp_context* h, int slots) {
+  const int rows_per_slot = gicp::server_blocks(1 << 30, kGicpMaxBlocks);
+  if (h->ls_slots < slots) {
+    HIP_TRY(hipStreamSynchronize(h->tgt.stream));
+    if (h->ls_host) (void)hipHostFree(h->ls_host);
+    h->ls_host = nullptr;
+    h->ls_slots = 0;
+    const LockstepLayout L(static_cast<size_t>(slots));
+    HIP_TRY(hipHostMalloc(&h->ls_host, L.host_bytes, hipHostMallocDefault));
+    std::memset(h->ls_host, 0, L.host_bytes);
+    HIP_TRY(h->ls_tables.reserve(L.dev_bytes));
+    HIP_TRY(h->ls_partials.reserve(static_cast<size_t>(slots) * rows_per_slot * ndt::kEvalStride));
+    HIP_TRY(h->ls_counters.reserve(static_cast<size_t>(slots)));
+    h->ls_slots = slots;
+  }
+  HIP_TRY(hipMemsetAsync(h->ls_counters.p, 0, static_cast<size_t>(h->ls_slots) * sizeof(unsigned), h->tgt.stream));
+  return NDT_OK;
+}
+
+// gicp::StepExecutor on the device: per step one table upload, one k_correspond_multi launch for the members that asked for
+// correspondences, one k_functor_multi launch for all of them, and the poll of their tagged rows.  Called by the
+// coordinator (the API's calling thread) only.  A member in flight owns a slot: a row of the tables, of the partial rows,
+// a counter and a pinned row; and its own scratch from the main stream's pool -- the guess-moved source, corr, maha9 --
+// which goes back when the member ends (stream order makes the next user safe).
+struct LockstepDevice : gicp::StepExecutor {
+  gicp_context* h;
+  const std::vector<LockstepJob>& jobs;
+  LockstepLayout L;
+  struct Scratch {
+    DevBuf<float4> output;
+    DevBuf<int> corr;
+    DevBuf<float> maha;
+  };
+  std::vector<std::unique_ptr<Scratch>> scratch;  // per slot
+  std::vector<int> slot_of;                       // per member, -1 = not in flight
+  std::vector<int> free_slots;
+  int rows_per_slot;
+  std::string error;
+
+  LockstepDevice(gicp_context* ctx, const std::vector<LockstepJob>& j)
+      : h(ctx), jobs(j), L(static_cast<size_t>(ctx->ls_slots)), scratch(static_cast<size_t>(ctx->ls_slots)), slot_of(j.size(), -1),
+        rows_per_slot(gicp::server_blocks(1 << 30, kGicpMaxBlocks)) {
+    for (int s = h->ls_slots - 1; s >= 0; s--) free_slots.push_back(s);
+  }
+  template <class T>
+  T* host_at(size_t off) const { return reinterpret_cast<T*>(static_cast<unsigned char*>(h->ls_host) + off); }
+  template <class T>
+  T* dev_at(size_t off) const { return reinterpret_cast<T*>(h->ls_tables.p + off); }
+  double* row_of(int slot) const { return host_at<double>(L.rows) + static_cast<size_t>(slot) * ndt::kPublishSlots; }
+  bool hip_ok(hipError_t e, const char* what) {
+    if (e == hipSuccess) return true;
+    error = std::string(what) + ": " + hipGetErrorString(e);
+    return false;
+  }
+
+  bool start(int member) override {
+    if (free_slots.empty()) {
+      error = "lock-step: no free slot";
+      return false;
+    }
+    const LockstepJob& job = jobs[static_cast<size_t>(member)];
+    const size_t n = job.src->n();
+    std::unique_ptr<Scratch> sc(new Scratch());
+    if (!hip_ok(sc->output.reserve(n), "lock-step scratch") || !hip_ok(sc->corr.reserve(n), "lock-step scratch") ||
+        !hip_ok(sc->maha.reserve(n * 9), "lock-step scratch"))
+      return false;
+    hipStream_t st = h->tgt.stream;
+    // pcl::transformPointCloud(output, output, guess), :403
+    if (!hip_ok(ndt::launch_transform(job.src->cloud().pts.p, static_cast<int>(n), job.guess_rm, sc->output.p, st), "transform kernel")) return false;
+    const int slot = free_slots.back();
+    gicp::LockstepMember& m = host_at<gicp::LockstepMember>(L.members)[slot];
+    m = gicp::LockstepMember();
+    m.output = sc->output.p;
+    m.tgt_pts = job.tgt->cloud().pts.p;
+    m.cov_src6 = job.src->cov.p;
+    m.cov_tgt6 = job.tgt->cov.p;
+    m.corr = sc->corr.p;
+    m.maha9 = sc->maha.p;
+    m.partials = h->ls_partials.p + static_cast<size_t>(slot) * rows_per_slot * ndt::kEvalStride;
+    m.counter = h->ls_counters.p + slot;
+    m.out_row = row_of(slot);
+    m.tgt = gicp_index_of(*job.tgt);
+    m.n = static_cast<int>(n);
+    // (the staging row is rewritten only when the slot has a new owner: its last owner's final step, queued behind this
+    // copy's predecessors, has been waited for)
+    if (!hip_ok(hipMemcpyAsync(dev_at<gicp::LockstepMember>(L.dev_members) + slot, &m, sizeof(m), hipMemcpyHostToDevice, st), "lock-step member table"))
+      return false;
+    free_slots.pop_back();
+    scratch[static_cast<size_t>(slot)] = std::move(sc);
+    slot_of[static_cast<size_t>(member)] = slot;
+    return true;
+  }
+
+  void finish(int member) override {
+    const int slot = slot_of[static_cast<size_t>(member)];
+    if (slot < 0) return;
+    scratch[static_cast<size_t>(slot)].reset();
+    slot_of[static_cast<size_t>(member)] = -1;
+    free_slots.push_back(slot);
+  }
+
+  bool step(const std::vector<gicp::StepRequest>& requests, std::vector<gicp::FunctorSums>& out) override {
+    hipStream_t st = h->tgt.stream;
+    gicp::LockstepCorrespond* ct = host_at<gicp::LockstepCorrespond>(L.corr);
+    gicp::LockstepFunctor* ft = host_at<gicp::LockstepFunctor>(L.functor);
+    int n_corr = 0, corr_blocks = 0, n_fun = 0, fun_blocks = 0;
+    for (const gicp::StepRequest& r : requests) {
+      const int slot = slot_of[static_cast<size_t>(r.member)];
+      const int n = static_cast<int>(jobs[static_cast<size_t>(r.member)].src->n());
+      if (r.correspond) {
+        gicp::LockstepCorrespond& c = ct[n_corr++];
+        for (int i = 0; i < 12; i++) c.T[i] = r.corr_T[i];
+        for (int i = 0; i < 9; i++) c.R.m[i] = r.corr_R[i];
+        c.slot = slot;
+        c.first_block = corr_blocks;
+        c.n_blocks = gicp::correspond_blocks(n, kGicpMaxBlocks);
+        c.pad = 0;
+        corr_blocks += c.n_blocks;
+      }
+      gicp::LockstepFunctor& f = ft[n_fun++];
+      for (int i = 0; i < 12; i++) f.T[i] = r.T[i];
+      f.slot = slot;
+      f.mode = r.mode;
+      f.first_block = fun_blocks;
+      f.n_blocks = gicp::server_blocks(n, kGicpMaxBlocks);
+      fun_blocks += f.n_blocks;
+    }
+    const unsigned long long seq = ++h->seq;
+    // (the staging is free: the previous step's kernels, queued behind its copies, have published)
+    if (n_corr) {
+      if (!hip_ok(hipMemcpyAsync(dev_at<gicp::LockstepCorrespond>(L.dev_corr), ct, static_cast<size_t>(n_corr) * sizeof(*ct), hipMemcpyHostToDevice, st),
+                  "lock-step step table"))
+        return false;
+      const double thr = h->prm.corr_dist_threshold * h->prm.corr_dist_threshold;  // :401
+      if (!hip_ok(gicp::launch_correspond_multi(dev_at<gicp::LockstepMember>(L.dev_members), dev_at<gicp::LockstepCorrespond>(L.dev_corr), n_corr,
+                                                corr_blocks, thr, st),
+                  "correspondence kernel"))
+        return false;
+    }
+    if (!hip_ok(hipMemcpyAsync(dev_at<gicp::LockstepFunctor>(L.dev_functor), ft, static_cast<size_t>(n_fun) * sizeof(*ft), hipMemcpyHostToDevice, st),
+                "lock-step step table") ||
+        !hip_ok(gicp::launch_functor_multi(dev_at<gicp::LockstepMember>(L.dev_members), dev_at<gicp::LockstepFunctor>(L.dev_functor), n_fun, fun_blocks,
+                                           seq, st),
+                "functor kernel"))
+      return false;
+    // every member's row arrives as 64 self-validating words; poll them as GicpDevice::sums polls its one, and look at the
+    // stream now and then so that a failed launch cannot hang the caller
+    int arrived = 0;
+    std::vector<char> have(static_cast<size_t>(n_fun), 0);
+    for (unsigned long long spins = 1; arrived < n_fun; spins++) {
+      for (int i = 0; i < n_fun; i++)
+        if (!have[static_cast<size_t>(i)] && pub_ready(row_of(ft[i].slot), seq)) {
+          have[static_cast<size_t>(i)] = 1;
+          arrived++;
+        }
+      if (arrived < n_fun && (spins & 0xffff) == 0) {
+        const hipError_t q = hipStreamQuery(st);
+        if (q == hipSuccess) {
+          bool all = true;
+          for (int i = 0; i < n_fun; i++) all = all && pub_ready(row_of(ft[i].slot), seq);
+          if (all) break;
+          error = "functor kernel finished without publishing its result";
+          return false;
+        }
+        if (q != hipErrorNotReady) return hip_ok(q, "functor kernel");
+      }
+    }
+    double row[ndt::kEvalStride];
+    for (int i = 0; i < n_fun; i++) {
+      pub_gather(row_of(ft[i].slot), row);
+      gicp::sums_from_row(row, out[static_cast<size_t>(i)]);
+    }
+    return true;
+  }
+};
+
+// The registrations of `jobs` advanced together, with h's parameters.  results[j] is gicp_register's for job j.
+ndt_status gicp_register_lockstep(gicp_context* h, const std::vector<LockstepJob>& jobs, std::vector<gicp::Result>& results,
+                                  gicp::LockstepStats& stats) {
+  const int window = std::min<int>(gicp::lockstep_window(), static_cast<int>(std::max<size_t>(jobs.size(), 1)));
+  ndt_status s = gicp_scratch(h);
+  if (!s) s = gicp_lockstep_scratch(h, window);
+  if (s) return s;
+  std::vector<gicp::LockstepInput> in(jobs.size());
+  for (size_t j = 0; j < jobs.size(); j++) {
+    in[j].prm = h->prm;
+    std::memcpy(in[j].guess, jobs[j].guess_rm, sizeof(in[j].guess));
+  }
+  LockstepDevice dev(h, jobs);
+  const bool ok = gicp::run_lockstep(in, window, gicp::fuse_enabled(), dev, results, stats);
+  if (!ok) {
+    (void)hipStreamSynchronize(h->tgt.stream);  // before the members' scratch goes back to the pool
+    return fail(NDT_ERR_HIP, dev.error.empty() ? "device failure" : dev.error);
+  }
+  return NDT_OK;
 }
 
 }  // namespace
@@ -630,9 +857,18 @@ static void gicp_pairs_drop(gicp_handle h) {
   h->pairs_prepared.clear();
 }
 
-ndt_status gicp_align_pairs_clouds(gicp_handle h, const ndt_cloud* clouds, size_t n_clouds, const int* pairs, size_t n_pairs,
-                                   const float* guesses, double max_range, float* final_T, int* converged, int* n_iterations,
-                                   int* correspondences, double* fitness) {
+// What both pairs calls do before the first registration: the argument checks, the named clouds made readable on the main
+// stream, the finite check of all of them in one launch, one index per named cloud (a leaf chain of the call's own) and
+// the covariances of all of them from one k_knn_covariances_multi launch (a further launch per kGicpMultiMaxBlocks),
+// waited for.  empty: n_pairs == 0, nothing was needed.
+struct PairsPrep {
+  std::vector<GicpInput> prep;  // one record per cloud; set: a pair named it
+  size_t index_builds = 0, knn_launches = 0, knn_blocks = 0;
+  std::chrono::steady_clock::time_point t_begin, t_prepared;
+  bool empty = false;
+};
+
+static ndt_status gicp_pairs_prepare(gicp_handle h, const ndt_cloud* clouds, size_t n_clouds, const int* pairs, size_t n_pairs, PairsPrep& out) {
   if (!h) return fail(NDT_ERR_INVALID, "null handle");
   gicp_pairs_drop(h);
   if (n_clouds && !clouds) return fail(NDT_ERR_INVALID, "null clouds");
@@ -658,14 +894,14 @@ ndt_status gicp_align_pairs_clouds(gicp_handle h, const ndt_cloud* clouds, size_
                                        ") is less than k_correspondences_ (" + std::to_string(k) + ")");
   if (n_pairs == 0) {
     h->pairs_valid = true;
+    out.empty = true;
     return NDT_OK;
   }
   ndt_status s = ensure_device(&h->tgt);
   if (s) return s;
   hipStream_t st = h->tgt.stream;
   HIP_TRY(hipStreamSynchronize(st));
-  const auto t_begin = std::chrono::steady_clock::now();
-  auto t_prepared = t_begin;
+  out.t_begin = std::chrono::steady_clock::now();
   // ---- every named cloud: stream order, then the finite check of all of them in one launch
   std::vector<const DeviceCloud*> nc;
   for (int c : named) {
@@ -681,7 +917,8 @@ ndt_status gicp_align_pairs_clouds(gicp_handle h, const ndt_cloud* clouds, size_
 
   // ---- one record per named cloud: its index, the leaf of the previous one as the hint for the next (a chain of this
   // call's own; the builds are the handle's own path, one after the other, on the main stream)
-  std::vector<GicpInput> prep(n_clouds);
+  std::vector<GicpInput>& prep = out.prep;
+  prep = std::vector<GicpInput>(n_clouds);
   LeafHint hint;
   for (int c : named) {
     GicpInput& P = prep[c];
@@ -726,39 +963,167 @@ ndt_status gicp_align_pairs_clouds(gicp_handle h, const ndt_cloud* clouds, size_
   }
   HIP_TRY(hipStreamSynchronize(st));  // (the table's host copy may go; a failed launch shows here, not in the first pair)
   drain.done = true;
-  t_prepared = std::chrono::steady_clock::now();
+  out.t_prepared = std::chrono::steady_clock::now();
+  out.index_builds = named.size();
+  out.knn_launches = knn_launches;
+  out.knn_blocks = knn_blocks;
+  return NDT_OK;
+}
+
+// The pairs' results to the caller and the call's records to the handle (both pairs calls, after the last registration).
+struct PairsResults {
+  std::vector<float> T;
+  std::vector<int> conv, it, corr;
+  std::vector<double> fit;
+  explicit PairsResults(size_t n) : T(16 * n), conv(n), it(n), corr(n), fit(n) {}
+  void set(size_t p, const gicp::Result& r) {
+    colmajor_from_rowmajor(r.final_T, &T[16 * p]);
+    conv[p] = r.converged ? 1 : 0;
+    it[p] = r.nr_iterations;
+    corr[p] = r.correspondences;
+  }
+};
+static void gicp_pairs_finish(gicp_handle h, PairsPrep& pp, const PairsResults& R, size_t n_pairs, float* final_T, int* converged,
+                              int* n_iterations, int* correspondences, double* fitness) {
+  if (final_T) std::memcpy(final_T, R.T.data(), R.T.size() * sizeof(float));
+  if (converged) std::memcpy(converged, R.conv.data(), n_pairs * sizeof(int));
+  if (n_iterations) std::memcpy(n_iterations, R.it.data(), n_pairs * sizeof(int));
+  if (correspondences) std::memcpy(correspondences, R.corr.data(), n_pairs * sizeof(int));
+  if (fitness) std::memcpy(fitness, R.fit.data(), n_pairs * sizeof(double));
+  h->pairs_prepared.swap(pp.prep);
+  h->pairs_index_builds = pp.index_builds;
+  h->pairs_knn_launches = pp.knn_launches;
+  h->pairs_knn_blocks = pp.knn_blocks;
+  h->pairs_prepare_ms = std::chrono::duration<double, std::milli>(pp.t_prepared - pp.t_begin).count();
+  h->pairs_register_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - pp.t_prepared).count();
+  h->pairs_valid = true;
+}
+
+ndt_status gicp_align_pairs_clouds(gicp_handle h, const ndt_cloud* clouds, size_t n_clouds, const int* pairs, size_t n_pairs,
+                                   const float* guesses, double max_range, float* final_T, int* converged, int* n_iterations,
+                                   int* correspondences, double* fitness) {
+  PairsPrep pp;
+  ndt_status s = gicp_pairs_prepare(h, clouds, n_clouds, pairs, n_pairs, pp);
+  if (s || pp.empty) return s;
+  std::vector<GicpInput>& prep = pp.prep;
   // ---- the pairs, one after the other: gicp_align's registration and gicp_get_fitness_score's score of two records.  The
   // handle's own inputs, covariances, result and statistics are not touched (its step scratch is: gicp_register)
-  std::vector<float> T_all(16 * n_pairs);
-  std::vector<int> conv_all(n_pairs), it_all(n_pairs), corr_all(n_pairs);
-  std::vector<double> fit_all(n_pairs);
+  PairsResults R(n_pairs);
   for (size_t p = 0; p < n_pairs; p++) {
     GicpInput& Pt = prep[pairs[2 * p]];
     GicpInput& Ps = prep[pairs[2 * p + 1]];
     const gicp::Result r = gicp_register(h, Pt, Ps, guesses ? guesses + 16 * p : nullptr, &s);
     if (s) return s;
-    colmajor_from_rowmajor(r.final_T, &T_all[16 * p]);
-    conv_all[p] = r.converged ? 1 : 0;
-    it_all[p] = r.nr_iterations;
-    corr_all[p] = r.correspondences;
+    R.set(p, r);
     if (fitness) {
-      s = fitness_against(&h->tgt, Pt.grid.get(), Ps.cloud().pts.p, static_cast<int>(Ps.n()), &T_all[16 * p], max_range, &fit_all[p]);
+      s = fitness_against(&h->tgt, Pt.grid.get(), Ps.cloud().pts.p, static_cast<int>(Ps.n()), &R.T[16 * p], max_range, &R.fit[p]);
       if (s) return s;
     }
   }
-  HIP_TRY(hipStreamSynchronize(st));
-  if (final_T) std::memcpy(final_T, T_all.data(), T_all.size() * sizeof(float));
-  if (converged) std::memcpy(converged, conv_all.data(), n_pairs * sizeof(int));
-  if (n_iterations) std::memcpy(n_iterations, it_all.data(), n_pairs * sizeof(int));
-  if (correspondences) std::memcpy(correspondences, corr_all.data(), n_pairs * sizeof(int));
-  if (fitness) std::memcpy(fitness, fit_all.data(), n_pairs * sizeof(double));
-  h->pairs_prepared.swap(prep);
-  h->pairs_index_builds = named.size();
-  h->pairs_knn_launches = knn_launches;
-  h->pairs_knn_blocks = knn_blocks;
-  h->pairs_prepare_ms = std::chrono::duration<double, std::milli>(t_prepared - t_begin).count();
-  h->pairs_register_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_prepared).count();
-  h->pairs_valid = true;
+  HIP_TRY(hipStreamSynchronize(h->tgt.stream));
+  gicp_pairs_finish(h, pp, R, n_pairs, final_T, converged, n_iterations, correspondences, fitness);
+  return NDT_OK;
+}
+
+ndt_status gicp_align_pairs_lockstep(gicp_handle h, const ndt_cloud* clouds, size_t n_clouds, const int* pairs, size_t n_pairs,
+                                     const float* guesses, double max_range, float* final_T, int* converged, int* n_iterations,
+                                     int* correspondences, double* fitness) {
+  PairsPrep pp;
+  ndt_status s = gicp_pairs_prepare(h, clouds, n_clouds, pairs, n_pairs, pp);
+  if (s) return s;
+  if (pp.empty) {
+    h->ls_stats = gicp::LockstepStats();
+    h->ls_valid = true;
+    return NDT_OK;
+  }
+  // ---- the pairs, advanced together (gicp::run_lockstep over LockstepDevice), then gicp_get_fitness_score's score of
+  // each.  The handle's own inputs, covariances, result, statistics and step scratch are not touched.
+  std::vector<LockstepJob> jobs(n_pairs);
+  for (size_t p = 0; p < n_pairs; p++) {
+    jobs[p].tgt = &pp.prep[pairs[2 * p]];
+    jobs[p].src = &pp.prep[pairs[2 * p + 1]];
+    rowmajor_from_colmajor(guesses ? guesses + 16 * p : nullptr, jobs[p].guess_rm);
+  }
+  std::vector<gicp::Result> res;
+  gicp::LockstepStats stats;
+  s = gicp_register_lockstep(h, jobs, res, stats);
+  if (s) return s;
+  PairsResults R(n_pairs);
+  for (size_t p = 0; p < n_pairs; p++) {
+    R.set(p, res[p]);
+    if (fitness) {
+      s = fitness_against(&h->tgt, jobs[p].tgt->grid.get(), jobs[p].src->cloud().pts.p, static_cast<int>(jobs[p].src->n()), &R.T[16 * p],
+                          max_range, &R.fit[p]);
+      if (s) return s;
+    }
+  }
+  HIP_TRY(hipStreamSynchronize(h->tgt.stream));
+  gicp_pairs_finish(h, pp, R, n_pairs, final_T, converged, n_iterations, correspondences, fitness);
+  h->ls_stats = stats;
+  h->ls_valid = true;
+  return NDT_OK;
+}
+
+ndt_status gicp_align_guesses(gicp_handle h, const float* guesses, size_t n_guesses, double max_range, float* final_T, int* converged,
+                              int* n_iterations, int* correspondences, double* fitness) {
+  if (!h) return fail(NDT_ERR_INVALID, "null handle");
+  if (n_guesses > 65535) return fail(NDT_ERR_INVALID, "at most 65535 guesses per call");
+  if (n_guesses == 0) {  // (nothing to register: no device, and no inputs, needed)
+    h->ls_stats = gicp::LockstepStats();
+    h->ls_valid = true;
+    return NDT_OK;
+  }
+  ndt_status s = gicp_inputs_set(h);
+  if (s) return s;
+  if (!guesses) return fail(NDT_ERR_INVALID, "null guesses");
+  GicpInput& tgt = h->in[0];
+  GicpInput& src = h->in[1];
+  // the covariances gicp_align would use: the caller's, or the k-NN ones, computed once for all guesses -- and, where this
+  // call computed them, not kept: the handle's covariances stay as they were
+  struct Restore {
+    GicpInput &a, &b;
+    bool ha, hb;
+    ~Restore() { a.have_cov = ha; b.have_cov = hb; }
+  } restore{tgt, src, tgt.have_cov, src.have_cov};
+  s = gicp_prepare_covariances(h, tgt, src);
+  if (s) return s;
+  std::vector<LockstepJob> jobs(n_guesses);
+  for (size_t g = 0; g < n_guesses; g++) {
+    jobs[g].tgt = &tgt;
+    jobs[g].src = &src;
+    rowmajor_from_colmajor(guesses + 16 * g, jobs[g].guess_rm);
+  }
+  std::vector<gicp::Result> res;
+  gicp::LockstepStats stats;
+  s = gicp_register_lockstep(h, jobs, res, stats);
+  if (s) return s;
+  PairsResults R(n_guesses);
+  for (size_t g = 0; g < n_guesses; g++) {
+    R.set(g, res[g]);
+    if (fitness) {
+      s = fitness_against(&h->tgt, tgt.grid.get(), src.cloud().pts.p, static_cast<int>(src.n()), &R.T[16 * g], max_range, &R.fit[g]);
+      if (s) return s;
+    }
+  }
+  HIP_TRY(hipStreamSynchronize(h->tgt.stream));
+  if (final_T) std::memcpy(final_T, R.T.data(), R.T.size() * sizeof(float));
+  if (converged) std::memcpy(converged, R.conv.data(), n_guesses * sizeof(int));
+  if (n_iterations) std::memcpy(n_iterations, R.it.data(), n_guesses * sizeof(int));
+  if (correspondences) std::memcpy(correspondences, R.corr.data(), n_guesses * sizeof(int));
+  if (fitness) std::memcpy(fitness, R.fit.data(), n_guesses * sizeof(double));
+  h->ls_stats = stats;
+  h->ls_valid = true;
+  return NDT_OK;
+}
+
+ndt_status gicp_diag_lockstep(gicp_handle h, size_t* steps, size_t* correspond_launches, size_t* functor_launches,
+                              size_t* max_members_in_step) {
+  if (!h) return fail(NDT_ERR_INVALID, "null");
+  if (!h->ls_valid) return fail(NDT_ERR_NO_INPUT, "no successful lock-step call on this handle");
+  if (steps) *steps = h->ls_stats.steps;
+  if (correspond_launches) *correspond_launches = h->ls_stats.correspond_launches;
+  if (functor_launches) *functor_launches = h->ls_stats.functor_launches;
+  if (max_members_in_step) *max_members_in_step = h->ls_stats.max_members_in_step;
   return NDT_OK;
 }
 

@@ -9,6 +9,8 @@
 //   k_correspond       per outer iteration (:419-456): nearest target point of every transformed
 //                      source point, distance gate, Mahalanobis matrix (R C1 R^T + C2)^-1.
 //   k_functor          the BFGS objective / gradient sums (:241-368), one fused launch per evaluation.
+//   k_correspond_multi / k_functor_multi  the same two for the members of a lock-step (gicp_align_pairs_lockstep,
+//                      gicp_align_guesses): a table of members, per-block bodies shared with the single kernels.
 //
 // All three are gather kernels over point sets that sit in L2 at the reference's sizes (tens of
 // thousands of points after the 0.1 m prefilter, apps/align.cpp:60-69); nothing here is
@@ -349,10 +351,14 @@ __device__ __forceinline__ void load_sym(const double* __restrict__ c6, double C
   C[2][0] = c6[2]; C[2][1] = c6[4]; C[2][2] = c6[5];
 }
 
-__global__ __launch_bounds__(kBlock) void k_correspond(const float4* __restrict__ output, int n, EvalParams P, Rot3d R,
-                                                       PointIndex ix, const double* __restrict__ cov_src6,
-                                                       const double* __restrict__ cov_tgt6, double dist_threshold,
-                                                       int* __restrict__ corr, float* __restrict__ maha9) {
+// The work of ONE block of a correspondence grid, shared by k_correspond (one registration per launch) and
+// k_correspond_multi (the members of a lock-step, gicp_align_pairs_lockstep): block `block` of the `n_blocks` that cut the
+// n queries, 32 queries per pass, strided by n_blocks.  Both kernels hand it the member's arrays and the block's place
+// among the member's own blocks and nothing else, so corr and maha9 are the same bits whichever kernel wrote them.
+__device__ __forceinline__ void correspond_block(const float4* __restrict__ output, int n, const float* __restrict__ T12,
+                                                 const Rot3d& R, const PointIndex& ix, const double* __restrict__ cov_src6,
+                                                 const double* __restrict__ cov_tgt6, double dist_threshold, int block,
+                                                 int n_blocks, int* __restrict__ corr, float* __restrict__ maha9) {
 #pragma clang fp contract(off)
   constexpr int kTeams = kBlock / kTeam;
   const int sub = threadIdx.x & (kTeam - 1);
@@ -362,7 +368,7 @@ __global__ __launch_bounds__(kBlock) void k_correspond(const float4* __restrict_
   // The loop is uniform across the WAVE (a team without a query idles): the fallback below is a wave-wide operation.
   constexpr int kTeamsPerWave = kWave / kTeam;
   const int wave_in_block = threadIdx.x / kWave, team_in_wave = (threadIdx.x & (kWave - 1)) / kTeam;
-  for (int base = (blockIdx.x * (kBlock / kWave) + wave_in_block) * kTeamsPerWave; base < n; base += gridDim.x * kTeams) {
+  for (int base = (block * (kBlock / kWave) + wave_in_block) * kTeamsPerWave; base < n; base += n_blocks * kTeams) {
     const int i = base + team_in_wave;
     const bool live = i < n;  // uniform within a team
     float qx = 0.f, qy = 0.f, qz = 0.f;
@@ -371,7 +377,7 @@ __global__ __launch_bounds__(kBlock) void k_correspond(const float4* __restrict_
     int tb_i = 0x7fffffff;
     if (live) {
       const float4 p = output[i];
-      matvec_eigen(P.T, p.x, p.y, p.z, qx, qy, qz);
+      matvec_eigen(T12, p.x, p.y, p.z, qx, qy, qz);
       float best = INFINITY;  // this lane's share: distance and POSITION in the cell order (the index behind it is
       int best_p = -1;        // looked up on ties and at the end of a shell only)
       auto consider = [&](float d, unsigned pos, bool ok) {
@@ -431,30 +437,74 @@ __global__ __launch_bounds__(kBlock) void k_correspond(const float4* __restrict_
   }
 }
 
+__global__ __launch_bounds__(kBlock) void k_correspond(const float4* __restrict__ output, int n, EvalParams P, Rot3d R,
+                                                       PointIndex ix, const double* __restrict__ cov_src6,
+                                                       const double* __restrict__ cov_tgt6, double dist_threshold,
+                                                       int* __restrict__ corr, float* __restrict__ maha9) {
+  correspond_block(output, n, P.T, R, ix, cov_src6, cov_tgt6, dist_threshold, static_cast<int>(blockIdx.x),
+                   static_cast<int>(gridDim.x), corr, maha9);
+}
+
+// The correspondence steps of MANY registrations from one launch (the lock-step of gicp_align_pairs_lockstep and
+// gicp_align_guesses).  steps[s] is one member that asked for new correspondences in this step: its transformation and
+// rotation, its slot in the member table, and the n_blocks consecutive blocks from first_block on it owns (ascending, no
+// gaps) -- correspond_blocks(n, cap) of them, the grid k_correspond gets for it alone.  A block finds its entry by
+// bisection; blockIdx.x and both tables are the same for the whole wave, so the search and the member's pointers are
+// scalar.  From there on the block does what a block of k_correspond does for that member (correspond_block).
+__global__ __launch_bounds__(kBlock) void k_correspond_multi(const LockstepMember* __restrict__ members,
+                                                             const LockstepCorrespond* __restrict__ steps, int n_steps,
+                                                             double dist_threshold) {
+  const int b = static_cast<int>(blockIdx.x);
+  int lo = 0, hi = n_steps - 1;  // the last entry whose first_block <= b
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (steps[mid].first_block <= b) lo = mid;
+    else hi = mid - 1;
+  }
+  const LockstepCorrespond* __restrict__ st = steps + lo;
+  const int local = b - st->first_block, n_blocks = st->n_blocks;
+  if (local >= n_blocks) return;  // (a grid larger than the table's blocks: nothing to do)
+  const LockstepMember* __restrict__ m = members + st->slot;
+  const PointIndex ix = m->tgt;
+  const Rot3d R = st->R;
+  correspond_block(m->output, m->n, st->T, R, ix, m->cov_src6, m->cov_tgt6, dist_threshold, local, n_blocks, m->corr, m->maha9);
+}
+
 // MODE 0: operator() only; 1: df / fdf (f64); 2: operator() in slot 0 AND the f64 gradient sums of df in slots 1..12 --
 // the line search asks for df right after operator() at the same point, and one launch serves both
+//
+// The work of ONE block of a functor grid, shared by k_functor (one evaluation per launch) and k_functor_multi (one
+// evaluation of every waiting member of a lock-step per launch): block `block` of the `n_blocks` that cut the n source
+// points, its row into partials[block], a ticket on `counter`, and the member's last block sums the n_blocks rows in the
+// fixed order and publishes them into out_row.  Both kernels hand it the member's arrays, the block's place among the
+// member's own blocks and their LDS and nothing else, so a member's row is the same bits whichever kernel summed it.
+constexpr int kFunctorWaves = kBlock / kWave, kFunctorParts = kBlock / kEvalStride;
+struct FunctorLds {
+  double lds[kFunctorWaves * 32];
+  double lds2[kFunctorParts * kEvalStride];
+  int last;
+};
 template <int MODE>
-__global__ __launch_bounds__(kBlock) void k_functor(const float4* __restrict__ output, int n, const float4* __restrict__ tgt,
-                                                    const int* __restrict__ corr, const float* __restrict__ maha9,
-                                                    EvalParams P, double* __restrict__ partials,
-                                                    unsigned* __restrict__ counter, double* __restrict__ out_row,
-                                                    unsigned long long seq) {
+__device__ __forceinline__ void functor_block(const float4* __restrict__ output, int n, const float4* __restrict__ tgt,
+                                              const int* __restrict__ corr, const float* __restrict__ maha9,
+                                              const float* __restrict__ T12, int block, int n_blocks,
+                                              double* __restrict__ partials, unsigned* __restrict__ counter,
+                                              double* __restrict__ out_row, unsigned long long seq, FunctorLds& sh) {
 #pragma clang fp contract(off)
-  constexpr int kWaves = kBlock / kWave, kParts = kBlock / kEvalStride;
-  __shared__ double lds[kWaves * 32];
-  __shared__ double lds2[kParts * kEvalStride];
-  __shared__ int s_last;
+  constexpr int kWaves = kFunctorWaves, kParts = kFunctorParts;
+  double* lds = sh.lds;
+  double* lds2 = sh.lds2;
   double acc[kFunctorValues];
 #pragma unroll
   for (int k = 0; k < kFunctorValues; k++) acc[k] = 0.0;
-  for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+  for (int i = block * kBlock + threadIdx.x; i < n; i += n_blocks * kBlock) {
     const int c = corr[i];
     if (c < 0) continue;
     const float4 ps = output[i];
     const float4 pt = tgt[c];
     const float* M = maha9 + static_cast<size_t>(i) * 9;
     float px, py, pz;
-    matvec_eigen(P.T, ps.x, ps.y, ps.z, px, py, pz);
+    matvec_eigen(T12, ps.x, ps.y, ps.z, px, py, pz);
     const float r0 = px - pt.x, r1 = py - pt.y, r2 = pz - pt.z;
     if (MODE != 1) {  // operator(), :241-274
       const float m0 = (M[0] * r0 + M[1] * r1) + M[2] * r2;
@@ -498,19 +548,19 @@ __global__ __launch_bounds__(kBlock) void k_functor(const float4* __restrict__ o
 #pragma unroll
         for (int w = 1; w < kWaves; w++) v += lds[w * 32 + lane];
       }
-      __hip_atomic_store(partials + static_cast<size_t>(blockIdx.x) * kEvalStride + lane, v, __ATOMIC_RELAXED,
+      __hip_atomic_store(partials + static_cast<size_t>(block) * kEvalStride + lane, v, __ATOMIC_RELAXED,
                          __HIP_MEMORY_SCOPE_AGENT);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (lane == 0) {
       const unsigned ticket = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s_last = (ticket == gridDim.x - 1) ? 1 : 0;
+      sh.last = (ticket == static_cast<unsigned>(n_blocks) - 1u) ? 1 : 0;
     }
   }
   __syncthreads();
-  if (!s_last) return;
+  if (!sh.last) return;
   const int k = threadIdx.x % kEvalStride, part = threadIdx.x / kEvalStride;
-  lds2[part * kEvalStride + k] = sum_rows_fixed<kParts>(partials, gridDim.x, threadIdx.x);
+  lds2[part * kEvalStride + k] = sum_rows_fixed<kParts>(partials, n_blocks, threadIdx.x);
   __syncthreads();
   if (threadIdx.x < kEvalStride) {
     double t = 0.0;
@@ -521,6 +571,46 @@ __global__ __launch_bounds__(kBlock) void k_functor(const float4* __restrict__ o
   }
   __syncthreads();
   publish_row_tagged(out_row, lds, threadIdx.x, seq);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(kBlock) void k_functor(const float4* __restrict__ output, int n, const float4* __restrict__ tgt,
+                                                    const int* __restrict__ corr, const float* __restrict__ maha9,
+                                                    EvalParams P, double* __restrict__ partials,
+                                                    unsigned* __restrict__ counter, double* __restrict__ out_row,
+                                                    unsigned long long seq) {
+  __shared__ FunctorLds sh;
+  functor_block<MODE>(output, n, tgt, corr, maha9, P.T, static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x), partials,
+                      counter, out_row, seq, sh);
+}
+
+// One evaluation of EVERY waiting member of a lock-step from one launch.  steps[s] is one member blocked in an objective
+// evaluation: its pose, its mode (0 operator(), 1 / 2 df / fdf, 3 operator() with df's sums -- launch_functor's numbering),
+// its slot in the member table and the n_blocks blocks from first_block on it owns: server_blocks(n, cap) of them, the
+// count the objective server of a single registration sums over, so the row is the server's row.  Found by bisection as in
+// k_correspond_multi; the mode is the same for the whole block, a scalar branch onto k_functor's three bodies.  Every
+// member has its own partial rows, ticket counter and tagged row in pinned host memory; all rows carry the step's seq.
+__global__ __launch_bounds__(kBlock) void k_functor_multi(const LockstepMember* __restrict__ members,
+                                                          const LockstepFunctor* __restrict__ steps, int n_steps,
+                                                          unsigned long long seq) {
+  __shared__ FunctorLds sh;
+  const int b = static_cast<int>(blockIdx.x);
+  int lo = 0, hi = n_steps - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (steps[mid].first_block <= b) lo = mid;
+    else hi = mid - 1;
+  }
+  const LockstepFunctor* __restrict__ st = steps + lo;
+  const int local = b - st->first_block, n_blocks = st->n_blocks, mode = st->mode;
+  if (local >= n_blocks) return;
+  const LockstepMember* __restrict__ m = members + st->slot;
+  if (mode == 0)
+    functor_block<0>(m->output, m->n, m->tgt_pts, m->corr, m->maha9, st->T, local, n_blocks, m->partials, m->counter, m->out_row, seq, sh);
+  else if (mode == 3)
+    functor_block<2>(m->output, m->n, m->tgt_pts, m->corr, m->maha9, st->T, local, n_blocks, m->partials, m->counter, m->out_row, seq, sh);
+  else
+    functor_block<1>(m->output, m->n, m->tgt_pts, m->corr, m->maha9, st->T, local, n_blocks, m->partials, m->counter, m->out_row, seq, sh);
 }
 
 // ---------------------------------------------------------------------------
@@ -719,6 +809,20 @@ hipError_t launch_functor(int mode, const float4* output, int n, const float4* t
   else
     hipLaunchKernelGGL(k_functor<1>, dim3(n_blocks), dim3(kBlock), 0, stream, output, n, tgt, corr, maha9, P, partials, counter,
                        out_row, seq);
+  return hipGetLastError();
+}
+
+hipError_t launch_correspond_multi(const LockstepMember* d_members, const LockstepCorrespond* d_steps, int n_steps, int n_blocks,
+                                   double dist_threshold, hipStream_t stream) {
+  if (n_steps < 1 || n_blocks < 1 || !d_members || !d_steps) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_correspond_multi, dim3(n_blocks), dim3(kBlock), 0, stream, d_members, d_steps, n_steps, dist_threshold);
+  return hipGetLastError();
+}
+
+hipError_t launch_functor_multi(const LockstepMember* d_members, const LockstepFunctor* d_steps, int n_steps, int n_blocks,
+                                unsigned long long seq, hipStream_t stream) {
+  if (n_steps < 1 || n_blocks < 1 || !d_members || !d_steps) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_functor_multi, dim3(n_blocks), dim3(kBlock), 0, stream, d_members, d_steps, n_steps, seq);
   return hipGetLastError();
 }
 

@@ -76,6 +76,46 @@ hipError_t launch_functor(int mode, const float4* output, int n, const float4* t
                           const float* T12, int n_blocks, double* partials, unsigned* counter, double* out_row,
                           unsigned long long seq, hipStream_t stream);
 
+// The lock-step of many registrations (gicp_align_pairs_lockstep, gicp_align_guesses): one k_correspond_multi launch for the
+// members that asked for new correspondences and one k_functor_multi launch for every member waiting for an evaluation.
+// LockstepMember: what a member keeps while it is in flight (slot = its place in the device table), uploaded once when it
+// starts.  LockstepCorrespond / LockstepFunctor: one entry per member that takes part in a step, first_block ascending
+// from 0 without gaps, uploaded every step.  A member's corr / maha9 are bit for bit what launch_correspond(.., n_blocks, ..)
+// writes, and its row what launch_functor(mode, .., n_blocks, ..) publishes (the per-block bodies are shared).
+struct LockstepMember {
+  const float4* output = nullptr;  // the source moved by the guess
+  const float4* tgt_pts = nullptr;
+  const double* cov_src6 = nullptr;
+  const double* cov_tgt6 = nullptr;
+  int* corr = nullptr;
+  float* maha9 = nullptr;
+  double* partials = nullptr;   // its own rows: [n_blocks of the functor][kEvalStride]
+  unsigned* counter = nullptr;  // its own ticket counter (zero between launches)
+  double* out_row = nullptr;    // its own tagged row, pinned host memory
+  PointIndex tgt;
+  int n = 0;
+  int pad = 0;
+};
+struct LockstepCorrespond {
+  float T[12];
+  Rot3d R;
+  int slot = 0;
+  int first_block = 0;
+  int n_blocks = 0;  // correspond_blocks(n, cap)
+  int pad = 0;
+};
+struct LockstepFunctor {
+  float T[12];
+  int slot = 0;
+  int mode = 0;  // launch_functor's
+  int first_block = 0;
+  int n_blocks = 0;  // server_blocks(n, cap)
+};
+hipError_t launch_correspond_multi(const LockstepMember* d_members, const LockstepCorrespond* d_steps, int n_steps, int n_blocks,
+                                   double dist_threshold, hipStream_t stream);
+hipError_t launch_functor_multi(const LockstepMember* d_members, const LockstepFunctor* d_steps, int n_steps, int n_blocks,
+                                unsigned long long seq, hipStream_t stream);
+
 // Persistent objective server (one launch per BFGS run), see gicp_kernels.hip.  mailbox: 256 + 128 bytes of fine-grained
 // device memory laid out like the NDT server's (the host posts with ndt::server_post: kind = functor mode 0 / 1 / 3, or
 // ndt::kServerCmdExit); counter: kGicpServerParts * 32 zeroed u32; out_rows: kGicpServerParts tagged rows of pinned host memory.

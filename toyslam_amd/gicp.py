@@ -77,6 +77,14 @@ class GeneralizedIterativeClosestPoint:
         clouds: list of ndt.DeviceCloud; pairs: (P, 2) cloud indices (target, source), None = the consecutive pairs (k-1, k);
         guesses: one 4x4 per pair or None; max_range: getFitnessScore's, None = no limit.  Returns a dict with one entry per
         pair: T (P, 4, 4), converged, iterations, correspondences, fitness."""
+        return self._align_pairs(self._L.gicp_align_pairs_clouds, clouds, pairs, guesses, max_range)
+
+    def alignPairsLockstep(self, clouds, pairs=None, guesses=None, max_range=None):
+        """alignPairsClouds with the registrations advanced together (gicp_align_pairs_lockstep): per step one correspondence
+        launch and one objective launch for all pairs in flight.  Same arguments, same return dict, same bits per pair."""
+        return self._align_pairs(self._L.gicp_align_pairs_lockstep, clouds, pairs, guesses, max_range)
+
+    def _align_pairs(self, call, clouds, pairs, guesses, max_range):
         P = pairs_array(len(clouds), pairs)
         n = P.shape[0]
         g = None
@@ -89,13 +97,35 @@ class GeneralizedIterativeClosestPoint:
         conv, it, corr = (np.zeros(m, dtype=np.int32) for _ in range(3))
         fit = np.zeros(m, dtype=np.float64)
         arr = (C.c_void_p * max(len(clouds), 1))(*[c._c for c in clouds])
-        check(self._L.gicp_align_pairs_clouds(self._h, arr, len(clouds), _i(P) if n else None, n, _f(g) if g is not None else None,
-                                              float(np.finfo(np.float64).max if max_range is None else max_range), _f(T),
-                                              _i(conv), _i(it), _i(corr), _d(fit)))
+        check(call(self._h, arr, len(clouds), _i(P) if n else None, n, _f(g) if g is not None else None,
+                   float(np.finfo(np.float64).max if max_range is None else max_range), _f(T), _i(conv), _i(it), _i(corr), _d(fit)))
         self._pairs_n = {i: len(clouds[i]) for i in set(P.reshape(-1).tolist())}
         return dict(T=np.stack([_from_colmajor(T[k]) for k in range(n)]) if n else np.zeros((0, 4, 4), np.float32),
                     converged=conv[:n].astype(bool), iterations=it[:n].copy(), correspondences=corr[:n].copy(),
                     fitness=fit[:n].copy())
+
+    def alignGuesses(self, guesses, max_range=None):
+        """This handle's source onto its target from every guess (list of 4x4), all advanced together (gicp_align_guesses).
+        Entry g of the returned dict -- T (G, 4, 4), converged, iterations, correspondences, fitness -- is what align(guess g),
+        stats() and getFitnessScore(max_range) give; getFinalTransformation() and stats() are left as they were."""
+        n = len(guesses)
+        g = np.ascontiguousarray(np.stack([_colmajor(x) for x in guesses])) if n else np.zeros((1, 16), np.float32)
+        m = max(n, 1)
+        T = np.zeros((m, 16), dtype=np.float32)
+        conv, it, corr = (np.zeros(m, dtype=np.int32) for _ in range(3))
+        fit = np.zeros(m, dtype=np.float64)
+        check(self._L.gicp_align_guesses(self._h, _f(g), n, float(np.finfo(np.float64).max if max_range is None else max_range),
+                                         _f(T), _i(conv), _i(it), _i(corr), _d(fit)))
+        return dict(T=np.stack([_from_colmajor(T[k]) for k in range(n)]) if n else np.zeros((0, 4, 4), np.float32),
+                    converged=conv[:n].astype(bool), iterations=it[:n].copy(), correspondences=corr[:n].copy(),
+                    fitness=fit[:n].copy())
+
+    def diagLockstep(self):
+        """What the last alignPairsLockstep / alignGuesses did: dict of steps, correspond_launches, functor_launches,
+        max_members_in_step (gicp_diag_lockstep)."""
+        a = [C.c_size_t(0) for _ in range(4)]
+        check(self._L.gicp_diag_lockstep(self._h, *[C.byref(x) for x in a]))
+        return dict(steps=a[0].value, correspond_launches=a[1].value, functor_launches=a[2].value, max_members_in_step=a[3].value)
 
     def pairsCovariances(self, c):
         """The k-NN covariances the last alignPairsClouds computed for cloud c: (n, 3, 3) (gicp_pairs_covariances)."""
