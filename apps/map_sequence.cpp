@@ -22,8 +22,14 @@
 // after the other, 2.7 ms overlapped, 3.7 ms overlapped on CU partitions -- the steps are short host-paced sequences of
 // pageable copies and small launches, and two threads driving them get in each other's way; hence not the default.
 //
-//   map_sequence <pcd_directory> [voxel_leaf_size (0.5 | 0.3)] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]
+//   map_sequence [--scan-to-map] <pcd_directory> [voxel_leaf_size (0.5 | 0.3)] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]
 // ("host": the serial loop with every cloud passing through host buffers, as in rounds 1-3; the default keeps them in HBM)
+//
+// --scan-to-map (anywhere on the line; the node's loop with clouds resident in HBM): every scan after the first is registered
+// against the ACCUMULATED target -- all scans so far, each merged into the voxel grid at its registered pose
+// (ndt_target_accumulate_cloud) -- instead of against its predecessor alone.  The registration starts from the previous scan's
+// pose (the rosbag node's guess rule) and its result IS the scan's pose in the map: nothing is chained, so the trajectory
+// does not add up the errors of the pairs.  The printed lines keep their form.
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -103,6 +109,7 @@ class Channel {
 // what the two loops share: the state of the node and what happens with a registration's result
 struct Node {
   bool rosbag = false;
+  bool scan_to_map = false;  // --scan-to-map: registrations against the accumulated target; a result is a pose in the map
   std::vector<std::vector<float>> trajectory;                     // trajectory_
   std::vector<float> pose = std::vector<float>(kIdentity, kIdentity + 16);
   std::vector<float> pres_transform = std::vector<float>(kIdentity, kIdentity + 16);  // rosbag node :33,95
@@ -134,7 +141,7 @@ struct Node {
       std::snprintf(title, sizeof(title), "Transform %zu to %zu: (%d iterations)", loaded - 2, loaded - 1, iterations);
       print_matrix(title, T);
       std::vector<float> global(T, T + 16);
-      if (!trajectory.empty()) ndt_host_chain_pose(trajectory.back().data(), T, global.data());  // trajectory_.back() * transform
+      if (!scan_to_map && !trajectory.empty()) ndt_host_chain_pose(trajectory.back().data(), T, global.data());  // trajectory_.back() * transform
       trajectory.push_back(global);
       map_pose = global;
       return true;
@@ -227,16 +234,19 @@ static int run_resident(Node& node, ndt_pcd_sequence_handle seq, float voxel_lea
         t0 = clock_type::now();
         int ov = 0;
         CHECK(ndt_map_update_cloud(h, current, 1, kIdentity, 0.5f, &ov));
+        if (node.scan_to_map) CHECK(ndt_target_accumulate_cloud(h, current, 1, kIdentity));
         node.t_map += since(t0);
         return 0;
       }
       t0 = clock_type::now();  // process_available_clouds, :70-100
-      CHECK(ndt_set_input_target_cloud(h, previous, 1));
+      if (!node.scan_to_map) CHECK(ndt_set_input_target_cloud(h, previous, 1));
       CHECK(ndt_set_input_source_cloud(h, current));
       float T[16];
       int converged = 0, iterations = 0;
       double probability = 0;
-      CHECK(ndt_align(h, node.rosbag ? node.pres_transform.data() : nullptr, T, &converged, &iterations, &probability, nullptr, 0));
+      const float* guess = node.rosbag ? node.pres_transform.data() : nullptr;
+      if (node.scan_to_map) guess = node.trajectory.empty() ? kIdentity : node.trajectory.back().data();  // the previous scan's pose
+      CHECK(ndt_align(h, guess, T, &converged, &iterations, &probability, nullptr, 0));
       node.t_align += since(t0);
       std::vector<float> map_pose;
       std::string err;
@@ -249,6 +259,7 @@ static int run_resident(Node& node, ndt_pcd_sequence_handle seq, float voxel_lea
         t0 = clock_type::now();
         int ov = 0;
         CHECK(ndt_map_update_cloud(h, current, 1, map_pose.data(), 0.5f, &ov));  // :204 / map_voxel :88: leaf fixed at 0.5
+        if (node.scan_to_map) CHECK(ndt_target_accumulate_cloud(h, current, 1, map_pose.data()));
         node.t_map += since(t0);
       }
       return 0;
@@ -513,14 +524,29 @@ static int run_pipelined(Node& node, ndt_pcd_sequence_handle seq, float voxel_le
 }
 
 int main(int argc, char** argv) {
+  bool scan_to_map = false;
+  {  // the switch is taken out of the line before the positional arguments are read
+    int kept = 1;
+    for (int i = 1; i < argc; i++) {
+      if (std::strcmp(argv[i], "--scan-to-map") == 0) scan_to_map = true;
+      else argv[kept++] = argv[i];
+    }
+    argc = kept;
+  }
   if (argc < 2) {
-    std::printf("usage: map_sequence <pcd_directory> [voxel_leaf_size] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]\n");
+    std::printf("usage: map_sequence [--scan-to-map] <pcd_directory> [voxel_leaf_size] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]\n");
     return 0;
   }
   Node node;
   node.rosbag = argc > 4 && std::strcmp(argv[4], "rosbag") == 0;
   const bool serial = !(argc > 5 && std::strcmp(argv[5], "pipeline") == 0);
   const bool host_clouds = argc > 6 && std::strcmp(argv[6], "host") == 0;  // serial only: every cloud through host buffers
+  node.scan_to_map = scan_to_map;
+  if (scan_to_map && (node.rosbag || !serial || host_clouds)) {
+    // (the rosbag loop prints getFitnessScore, which needs the target's points: an accumulated target keeps none)
+    std::fprintf(stderr, "--scan-to-map runs the node's serial loop with resident clouds: not with rosbag, pipeline or host\n");
+    return 2;
+  }
   const float voxel_leaf_size = argc > 2 ? static_cast<float>(std::atof(argv[2])) : (node.rosbag ? 0.3f : 0.5f);  // :44 / rosbag :87
   ndt_handle h = nullptr, map_handle = nullptr;
   CHECK(ndt_create(0, &h));

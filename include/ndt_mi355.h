@@ -284,6 +284,58 @@ ndt_status ndt_map_update_batch(ndt_handle h, const void* pts, const size_t* off
 ndt_status ndt_diag_map_batch(ndt_handle h, size_t* transform_launches, size_t* filters, size_t* box_passes);
 ndt_status ndt_promote_source_to_target(ndt_handle h, int is_dense);
 
+/* ---- accumulating target: posed scans merged into the voxel grid (scan-to-MAP registration) --------------------------
+ * Every other target of this library is built from ONE cloud; a mapping node that wants to register a scan against the map
+ * would have to keep every posed point and rebuild the grid from the growing concatenation before each scan.  Here the
+ * handle's target becomes an ACCUMULATED grid: per voxel the running first-pass sums of applyFilter (count, f64 sum /
+ * outer-product sums seeded Identity, f32 centroid sums, _impl.hpp:209-263) and the finished record.  No points are kept:
+ * memory is O(voxels), an update costs O(points of the update).
+ * - Equivalence.  After any sequence of accumulate calls the handle behaves like a handle with the same parameters whose
+ *   target was set from the concatenation -- in call order, and in cloud order within _clouds -- of the clouds moved by their
+ *   poses: ndt_grid_size / _info / _dump return the same leaves, counts, means, covariances, inverse covariances and
+ *   eigenvalues, and ndt_eval*, ndt_eval_hessian_f64, ndt_calculate_score, ndt_score_poses, ndt_align, ndt_align_guesses,
+ *   ndt_align_multistart and ndt_align_batch* the same bits, for all four search methods (the evaluation kernels see an
+ *   ordinary grid: the padded dense table, or the hash keyed by the reference's linear index; ndt_set_voxel_index chooses
+ *   between the two as for a cloud target, by the points accumulated so far).  `pose` is a column-major 4x4, NULL =
+ *   identity; the transform is N2's pcl::transformPointCloud in f32 (the device code of ndt_map_update*).  A non-finite
+ *   row is left as it is by the transform and lands in no voxel (the is_dense == 0 rule; a cloud passed as dense must not
+ *   hold one, as for ndt_set_input_target).
+ * - _clouds: all clouds go through ONE pass (one transform launch, one key launch, one sort, one merge); the result has
+ *   the bits of the same clouds accumulated one call at a time.  poses: 16 floats per cloud, NULL = identity for all.
+ * - The first accumulate call on a handle REPLACES whatever target it held (it starts empty; a cloud target is not
+ *   continued).  ndt_set_input_target*, ndt_share_input_target into the handle and ndt_promote_source_to_target replace the
+ *   accumulated target; _reset empties it and leaves the handle with no target.  ndt_warm_up leaves it as it was.
+ * - Resolution, min_points_per_voxel and the eigenvalue ratio are captured when a target starts (the first accumulate
+ *   after create, reset or a replaced target); later changes of the last two apply from the next reset, as they apply from
+ *   the next build for a cloud target.  ndt_set_resolution to a different value DROPS the accumulated target: there is no
+ *   cloud to rebuild from.
+ * - What needs the target's points, or shares the immutable grid with another handle, returns an error and changes
+ *   nothing: ndt_get_fitness_score (and ndt_batch_fitness_scores*) NDT_ERR_NO_INPUT; ndt_clone of, and
+ *   ndt_share_input_target from, such a handle NDT_ERR_INVALID.
+ * - Refused before anything of the target changes -- NDT_ERR_INVALID: a NULL handle, NULL points or clouds with a non-zero
+ *   count, a NULL entry of clouds, a bad stride, more than INT_MAX points in one call, a finite point whose cell index
+ *   floor(x / leaf) lies outside [-2^20, 2^20) on any axis (inside that range the reference's f32 index arithmetic,
+ *   _impl.hpp:218-223, is exact and independent of the bounding box; outside it the voxel of a point would depend on the
+ *   box); NDT_ERR_GRID_OVERFLOW: the union of the boxes would have more than INT_MAX cells.
+ * - n == 0, or only empty clouds: NDT_OK, nothing changes, no device needed.
+ * - ndt_target_accumulated: rows accumulated (non-finite ones included), occupied voxels, updates; zeros without an
+ *   accumulated target.  ndt_diag_target_accumulate, of the last accumulate call: voxels it touched, voxels it created,
+ *   whether every table entry was rewritten (the box, or the table's form or size, changed), whether the key table or the
+ *   slot arrays were doubled, and the launches it queued (sort and scans count one each).
+ * Development switches, read when a target starts: NDT_ACC_HASH_BITS (log2 of the initial key table, default 16) and
+ * NDT_ACC_SLOTS (initial voxel slots, default 32768); both double on demand. */
+ndt_status ndt_target_accumulate(ndt_handle h, const void* pts, size_t n, size_t stride_bytes, int is_dense, const float* pose);
+ndt_status ndt_target_accumulate_device(ndt_handle h, const void* d_pts, size_t n, size_t stride_bytes, int is_dense, const float* pose);
+ndt_status ndt_target_accumulate_cloud(ndt_handle h, ndt_cloud c, int is_dense, const float* pose);
+ndt_status ndt_target_accumulate_clouds(ndt_handle h, const ndt_cloud* clouds, size_t n_clouds, int is_dense, const float* poses /* n*16 or NULL */);
+ndt_status ndt_target_accumulate_reset(ndt_handle h);
+ndt_status ndt_target_accumulated(ndt_handle h, size_t* n_points, size_t* n_voxels, size_t* n_updates);
+ndt_status ndt_diag_target_accumulate(ndt_handle h, size_t* touched_voxels, size_t* new_voxels, int* relinked, int* table_grown, size_t* launches);
+/* the key of the accumulated target's voxel table: the absolute cell (i, j, k), 21 bits per axis, k in the high bits so
+ * that keys ascend with the linear voxel index.  Host only.  NDT_ERR_INVALID outside [-2^20, 2^20). */
+ndt_status ndt_host_acc_pack_cell(int i, int j, int k, uint64_t* key);
+void ndt_host_acc_unpack_cell(uint64_t key, int* i, int* j, int* k);
+
 /* ---- PCD files (row N3 of the scope table) -----------------------------------
  * What pcl::io::loadPCDFile<pcl::PointXYZ> hands the callers (ndt_omp/apps/align.cpp:48-55,
  * ndt_omp_mapping_node.cpp:140, ndt_omp_node.cpp:82) and what pcl::io::savePCDFileBinary writes

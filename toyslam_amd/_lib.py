@@ -98,6 +98,15 @@ SIGNATURES = {
     "ndt_map_update_batch": (C.c_int, [vp, vp, szp, C.c_size_t, C.c_size_t, ip, fp, C.c_float, C.c_int, ip]),
     "ndt_diag_map_batch": (C.c_int, [vp, szp, szp, szp]),
     "ndt_promote_source_to_target": (C.c_int, [vp, C.c_int]),
+    "ndt_target_accumulate": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_int, fp]),
+    "ndt_target_accumulate_device": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_int, fp]),
+    "ndt_target_accumulate_cloud": (C.c_int, [vp, vp, C.c_int, fp]),
+    "ndt_target_accumulate_clouds": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, C.c_int, fp]),
+    "ndt_target_accumulate_reset": (C.c_int, [vp]),
+    "ndt_target_accumulated": (C.c_int, [vp, szp, szp, szp]),
+    "ndt_diag_target_accumulate": (C.c_int, [vp, szp, szp, ip, ip, szp]),
+    "ndt_host_acc_pack_cell": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
+    "ndt_host_acc_unpack_cell": (None, [C.c_uint64, ip, ip, ip]),
     "ndt_host_chain_pose": (None, [fp, fp, fp]),
     "ndt_pcd_read_header": (C.c_int, [C.c_char_p, szp, ip, ip]),
     "ndt_pcd_read_xyz": (C.c_int, [C.c_char_p, vp, C.c_size_t, C.c_size_t, szp, ip]),

@@ -103,6 +103,7 @@ static ndt_status batch_fitness_impl(ndt_handle h, const void* pts, const size_t
   const size_t n_pts = offsets[n_scans] - offsets[0];
   if (n_pts && !pts) return fail(NDT_ERR_INVALID, "null point buffer");
   if (!h->grid || !h->target) return fail(NDT_ERR_NO_INPUT, "no input target");
+  if (h->grid->accumulated) return fail(NDT_ERR_NO_INPUT, "getFitnessScore needs the target's points: an accumulated target keeps none");
   if (n_scans == 0) return NDT_OK;
   ndt_status s = ensure_device(h);
   if (s) return s;

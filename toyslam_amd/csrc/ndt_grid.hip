@@ -882,6 +882,7 @@ ndt_status maybe_compact_records(ndt_context* h, bool eager) {
 // occupied / candidate / valid voxel counts of a built grid (fetched from the device on first use)
 ndt_status grid_counts(ndt_context* h, DeviceGrid* g) {
   if (g->counts_known || g->empty) return NDT_OK;
+  if (g->accumulated) return acc_grid_counts(h, g);
   std::lock_guard<std::mutex> lock(g->fit_mu);
   if (g->counts_known) return NDT_OK;
   if (g->leaves_pending) {  // bucket-form build: number the leaves now that somebody wants them
@@ -1021,6 +1022,7 @@ void fill_point_index(const DeviceGrid* g, ndt::PointIndex& ix) {
 // stream, with h's scratch)
 ndt_status fitness_against(ndt_context* h, DeviceGrid* g, const float4* d_src, int n, const float* T_colmajor, double max_range,
                            double* fitness) {
+  if (g->accumulated) return fail(NDT_ERR_NO_INPUT, "getFitnessScore needs the target's points: an accumulated target keeps none");
   *fitness = std::numeric_limits<double>::max();  // nr == 0 in the reference
   ndt_status s = grid_counts(h, g);
   if (s) return s;
@@ -1321,6 +1323,8 @@ ndt_status ndt_share_input_target(ndt_handle dst, ndt_handle src) {
   if (!dst || !src) return fail(NDT_ERR_INVALID, "null handle");
   if (!src->target || !src->grid) return fail(NDT_ERR_NO_INPUT, "the donor handle has no input target");
   if (dst == src) return NDT_OK;
+  if (src->grid->accumulated)
+    return fail(NDT_ERR_INVALID, "an accumulated target cannot be shared: its grid changes in place and belongs to one handle");
   if (dst->device != src->device) return fail(NDT_ERR_INVALID, "handles on different devices");
   HIP_TRY(hipSetDevice(src->device));
   if (src->device_ready) HIP_TRY(hipStreamSynchronize(src->stream));  // the grid may still be under construction there
@@ -2046,6 +2050,7 @@ ndt_status ndt_grid_dump(ndt_handle h, int64_t* idx, int* nr_points, double* mea
                          double* evals) {
   if (!h || !h->grid) return fail(NDT_ERR_NO_INPUT, "no grid");
   DeviceGrid* g = h->grid.get();
+  if (g->accumulated) return acc_grid_dump(h, idx, nr_points, mean, cov, icov, evals);
   if (!g->empty) {
     ndt_status sc = ensure_device(h);
     if (!sc) sc = grid_counts(h, g);

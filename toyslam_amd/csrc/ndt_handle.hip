@@ -148,6 +148,8 @@ ndt_status ndt_create(int device, ndt_handle* out) {
 
 ndt_status ndt_clone(ndt_handle src, ndt_handle* out) {
   if (!src || !out) return fail(NDT_ERR_INVALID, "bad arguments");
+  if (acc_is_live(src))
+    return fail(NDT_ERR_INVALID, "an accumulated target cannot be cloned: its grid changes in place and is not shared between handles");
   if (src->device_ready) {  // the shared grid / clouds may still be under construction on the source's stream
     HIP_TRY(hipSetDevice(src->device));
     HIP_TRY(hipStreamSynchronize(src->stream));
@@ -195,6 +197,14 @@ ndt_status ndt_set_resolution(ndt_handle h, float resolution) {
   // ndt_omp.h:132-142 -- rebuilds only when a SOURCE (input_) is set
   if (h->resolution != resolution) {
     h->resolution = resolution;
+    if (acc_is_live(h)) {  // no cloud to rebuild from: the accumulated target is dropped
+      if (h->device_ready) {
+        HIP_TRY(hipSetDevice(h->device));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+      }
+      acc_drop(h);
+      return NDT_OK;
+    }
     if (h->source && h->target) return build_grid(h);
   }
   return NDT_OK;

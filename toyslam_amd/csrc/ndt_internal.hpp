@@ -9,6 +9,7 @@
 //                    ndt_align, ndt_eval*, diagnostics and self-tests
 //   ndt_batch.hip  : lock-step batches (ndt_align_batch*, ndt_align_guesses, ndt_align_multistart), the RCCL communicator
 //                    (ndt_comm_*), ndt_set_allreduce
+//   ndt_accumulate.hip : the accumulating target (ndt_target_accumulate*): kernels and C-ABI
 //   ndt_io.hip     : PCD files, numbered scan sequences, PointCloud2-style repacking (host)
 //   gicp_capi.hip  : the GICP row
 #pragma once
@@ -288,6 +289,9 @@ struct DeviceGrid {
   ndt::GridBuildPlan plan{};
   DevBuf<float4> bpts;
   bool index_form = false;  // (NDT_K1_INDEX=1: bpts holds point indices)
+  // the grid of an accumulating target (ndt_accumulate.hip): lut / recs / centroids / geom only, mutated in place by its one
+  // handle; no points, no leaf arrays -- what needs either (getFitnessScore, sharing) refuses it
+  bool accumulated = false;
   DevBuf<unsigned> bucket_base;
   ndt::GridView view() const {
     ndt::GridView v;
@@ -311,6 +315,7 @@ struct ndt_cloud_s {
 struct ndt_context;
 namespace ndtc {
 void comm_release(ndt_context* h);  // ndt_batch.hip
+struct AccTarget;                   // ndt_accumulate.hip
 }
 
 struct ndt_context {
@@ -455,6 +460,11 @@ struct ndt_context {
   size_t sp_pinned_bytes = 0;
   DevBuf<float> sp_poses;
   size_t sp_launches = 0, sp_blocks = 0;
+  // ndt_target_accumulate* (ndt_accumulate.hip): the accumulated target -- alive while `grid` is its grid -- and what the last
+  // call did (ndt_diag_target_accumulate)
+  std::shared_ptr<ndtc::AccTarget> acc;
+  size_t acc_touched = 0, acc_new = 0, acc_launches = 0;
+  int acc_relinked = 0, acc_grown = 0;
 
   ~ndt_context() {
     for (ndt_context* w : batch_workers) delete w;
@@ -488,6 +498,7 @@ struct ndt_context {
     if (fb_rows) (void)hipHostFree(fb_rows);
     if (mb_pinned) (void)hipHostFree(mb_pinned);
     if (sp_pinned) (void)hipHostFree(sp_pinned);
+    acc.reset();
     release_buffers();
     if (host_result) (void)hipHostFree(host_result);
     if (host_pub) (void)hipHostFree(host_pub);
@@ -606,6 +617,11 @@ ndt_status cloud_use_on(ndt_handle h, DeviceCloud* c);  // an ndt_cloud made on 
 // out_boxes: the result's bounding boxes as DeviceCloud keeps them ([2][3] min, [2][3] max), or null
 ndt_status voxel_filter_device(ndt_handle h, const float4* d_in, size_t n, int is_dense, float leaf, float4* d_out,
                                size_t* n_out, bool* overflow, const BBox* known_bbox = nullptr, DeviceCloud* out_boxes = nullptr);
+// ---- ndt_accumulate.hip
+bool acc_is_live(const ndt_context* h);  // the handle's target is an accumulated one
+void acc_drop(ndt_context* h);           // forget it (the handle is left without a target if it was live)
+ndt_status acc_grid_counts(ndt_context* h, DeviceGrid* g);
+ndt_status acc_grid_dump(ndt_context* h, int64_t* idx, int* nr_points, double* mean, double* cov, double* icov, double* evals);
 // ---- ndt_eval.hip
 void colmajor_to_T12(const float* m, float* T12);
 float kd_radius2(float resolution);

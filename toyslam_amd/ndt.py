@@ -442,6 +442,56 @@ class NormalDistributionsTransform:
         check(self._L.ndt_diag_map_batch(self._h, C.byref(t), C.byref(f), C.byref(b)))
         return dict(transform_launches=t.value, filters=f.value, box_passes=b.value)
 
+    # ---- accumulating target: posed scans merged into the voxel grid (ndt_target_accumulate*) ----
+    def targetAccumulate(self, scan, pose=None, is_dense=True):
+        """The scan moved by `pose` (4x4, None = identity) is merged into the handle's accumulated target: afterwards the handle
+        behaves as if its target had been set from the concatenation of every accumulated scan.  The first call replaces the
+        target the handle held.  Returns targetAccumulated()."""
+        a = _cloud(scan)
+        T = None if pose is None else _colmajor(pose)
+        check(self._L.ndt_target_accumulate(self._h, a.ctypes.data, a.shape[0], a.shape[1] * 4, int(is_dense),
+                                            _f(T) if T is not None else None))
+        return self.targetAccumulated()
+
+    def targetAccumulateDevice(self, dev_ptr, n, stride_bytes, pose=None, is_dense=True):
+        T = None if pose is None else _colmajor(pose)
+        check(self._L.ndt_target_accumulate_device(self._h, C.c_void_p(dev_ptr), n, stride_bytes, int(is_dense),
+                                                   _f(T) if T is not None else None))
+        return self.targetAccumulated()
+
+    def targetAccumulateCloud(self, dc, pose=None, is_dense=True):
+        T = None if pose is None else _colmajor(pose)
+        check(self._L.ndt_target_accumulate_cloud(self._h, dc._c, int(is_dense), _f(T) if T is not None else None))
+        return self.targetAccumulated()
+
+    def targetAccumulateClouds(self, clouds, poses=None, is_dense=True):
+        """Many DeviceClouds in ONE pass (one sort, one merge), in the list's order; poses: one 4x4 per cloud, None = the
+        identity for all.  The same bits as one targetAccumulateCloud per cloud."""
+        clouds = list(clouds)
+        if not all(isinstance(c, DeviceCloud) for c in clouds):
+            raise ValueError("clouds must be DeviceCloud objects")
+        n = len(clouds)
+        P = self._poses(poses, n)
+        arr = (C.c_void_p * max(n, 1))(*[c._c for c in clouds])
+        check(self._L.ndt_target_accumulate_clouds(self._h, arr, n, int(is_dense), _f(P) if P is not None else None))
+        return self.targetAccumulated()
+
+    def targetAccumulateReset(self):
+        check(self._L.ndt_target_accumulate_reset(self._h))
+
+    def targetAccumulated(self):
+        """-> dict(points, voxels, updates) of the accumulated target (zeros without one)."""
+        p, v, u = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        check(self._L.ndt_target_accumulated(self._h, C.byref(p), C.byref(v), C.byref(u)))
+        return dict(points=p.value, voxels=v.value, updates=u.value)
+
+    def targetAccumulateDiag(self):
+        """What the last targetAccumulate* call did (ndt_diag_target_accumulate)."""
+        t, n, l = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        r, g = C.c_int(0), C.c_int(0)
+        check(self._L.ndt_diag_target_accumulate(self._h, C.byref(t), C.byref(n), C.byref(r), C.byref(g), C.byref(l)))
+        return dict(touched_voxels=t.value, new_voxels=n.value, relinked=bool(r.value), table_grown=bool(g.value), launches=l.value)
+
     # ---- batch (map-build) ---------------------------------------------------------
     def alignBatch(self, clouds=None, guesses=None, device_ptr=None, offsets=None, stride_bytes=16):
         """Register many sources against the one target in lock-step.
@@ -890,6 +940,20 @@ def host_pick_top(scores, keep):
     n = C.c_size_t(0)
     _lib.lib().ndt_host_pick_top(_d(s), s.shape[0], keep, _i(idx), C.byref(n))
     return idx[:n.value].copy()
+
+
+def host_acc_pack_cell(i, j, k):
+    """Key of the absolute voxel (i, j, k) in the accumulated target's table (ndt_host_acc_pack_cell); NdtError outside
+    [-2^20, 2^20)."""
+    key = C.c_uint64(0)
+    check(_lib.lib().ndt_host_acc_pack_cell(int(i), int(j), int(k), C.byref(key)))
+    return key.value
+
+
+def host_acc_unpack_cell(key):
+    i, j, k = C.c_int(0), C.c_int(0), C.c_int(0)
+    _lib.lib().ndt_host_acc_unpack_cell(C.c_uint64(int(key)), C.byref(i), C.byref(j), C.byref(k))
+    return i.value, j.value, k.value
 
 
 def host_thread_budget():
