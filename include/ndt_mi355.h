@@ -188,6 +188,13 @@ ndt_status ndt_map_size(ndt_handle h, size_t* n);
 ndt_status ndt_map_get(ndt_handle h, void* out, size_t out_stride_bytes); /* x,y,z,1.0f per point */
 ndt_status ndt_map_get_device(ndt_handle h, const void** d_pts_float4, size_t* n);
 void ndt_host_chain_pose(const float* pose /*16*/, const float* transform /*16*/, float* out /*16, may alias*/);
+/* The voxel lattice of pitch `leaf` over the box [mn, mx] as every grid build, the accumulating target, the voxel filter and
+ * the source ordering compute it (voxel_grid_covariance_omp_impl.hpp:75-103), and whether a target of n_points points
+ * over it gets the sparse voxel index under ndt_set_voxel_index mode voxel_index.  Host only.  NDT_ERR_GRID_OVERFLOW
+ * (outputs untouched) where the reference's integer indices would overflow, NDT_ERR_INVALID for a leaf that is not
+ * positive or a NULL corner.  Any output may be NULL. */
+ndt_status ndt_host_lattice(float leaf, const float* mn /*3*/, const float* mx /*3*/, int* min_b /*3*/, int* max_b /*3*/,
+                            int* div_b /*3*/, long long* n_cells, int voxel_index, long long n_points, int* sparse);
 
 /* What a node does once, at start-up, instead of inside its first scans: the device context, the library's code object (tens
  * of milliseconds on first use), the handle's page-locked result / staging slots, and one pass through the loop's calls

@@ -202,6 +202,86 @@ def test_pairs_leave_the_handle_state_alone(mods, pair):
     assert np.array_equal(before[0], after[0]) and before[1:] == after[1:]
 
 
+def small_scene(clouds):
+    """four clouds of ~2 000 points (surfaces over 20 m, four boxes each so that a hundred voxels hold six points: the
+    one-launch form's range, so k1_small_multi carries the pairs grids) that share no point, and a source for the first"""
+    A, B, C, D = (clouds.target_surfaces(2000 + 37 * k, seed=400 + k, extent=20.0, n_boxes=4)[:, :3].astype(np.float32) for k in range(4))
+    S = clouds.source_from_target(A, 700, T_gt=clouds.make_T([0.2, -0.1, 0.02], np.deg2rad([0.2, -0.3, 0.8])), seed=411)[:, :3].astype(np.float32)
+    return A, B, C, D, S
+
+
+def own_registration(g):
+    g.align()
+    return (g.getFinalTransformation(), g.getFinalNumIteration(), g.hasConverged(), g.getTransformationProbability(),
+            g.getFitnessScore())
+
+
+def same_registration(a, b):
+    return np.array_equal(a[0], b[0]) and a[1:] == b[1:]
+
+
+GRID_FIELDS = ("idx", "n", "mean", "cov", "icov", "evals", "min_b", "max_b", "div_b", "n_valid")
+
+
+def test_pairs_call_and_its_inspection_leave_the_handles_own_target_alone(mods):
+    """The pairs call grids other clouds and ndt_pairs_grid_* look at those grids, all with the handle's stream and scratch:
+    the handle's own target, its grid and what it registers against it stay what they were, bit for bit."""
+    ndt, po, clouds = mods
+    A, B, C, D, S = small_scene(clouds)
+    g = handle(ndt)
+    g.setInputTarget(A)
+    g.setInputSource(S)
+    grid_before = g.grid()
+    before = own_registration(g)
+    assert before[2] and len(grid_before["idx"]) > 50 and grid_before["n_valid"] > 20
+    cl, pairs = [B, C, D], [(0, 1), (1, 2), (2, 0), (0, 2)]
+    g.alignPairs(cl, pairs)
+    ref = handle(ndt)
+    for c in range(3):  # every cloud is a target: the three inspection entries for each
+        got = g.pairsGrid(c)
+        ref.setInputTarget(cl[c])
+        grids_equal(got, ref.grid())
+        assert len(got["idx"]) > 50
+        now = g.grid()  # ... and the handle's own grid after each of them
+        for k in GRID_FIELDS:
+            assert np.array_equal(now[k], grid_before[k]), (c, k)
+    assert same_registration(own_registration(g), before)
+
+
+def test_pairs_call_that_fails_in_its_grid_builds_leaves_nothing_behind(mods):
+    """Three targets, the second one two points 3 km apart on every axis: 3001^3 = 2.7e10 cells at resolution 1.0, beyond the
+    reference's int indices (voxel_grid_covariance_omp_impl.hpp:75-84) -- an ordinary error return from the middle of the
+    grid builds.  The handle's own target and registration are untouched, and no pairs grid is left: the call clears
+    them before it builds, so every ndt_pairs_grid_size answers NDT_ERR_NO_INPUT (as before this call took the clouds'
+    grids out of the handle's fields)."""
+    from toyslam_amd._lib import NdtError, NDT_ERR_GRID_OVERFLOW, NDT_ERR_NO_INPUT
+    ndt, po, clouds = mods
+    A, B, C, D, S = small_scene(clouds)
+    assert 3001 ** 3 > 2 ** 31 - 1
+    wide = np.array([[-1500.0, -1500.0, -1500.0], [1500.0, 1500.0, 1500.0]], dtype=np.float32)
+    g = handle(ndt)
+    g.setInputTarget(A)
+    g.setInputSource(S)
+    grid_before = g.grid()
+    before = own_registration(g)
+    g.alignPairs([B, C], [(0, 1)])  # (pairs grids of an earlier call: gone after the failed one)
+    assert len(g.pairsGrid(0)["idx"]) > 50
+    cl = [B, wide, D, C]
+    with pytest.raises(NdtError) as e:
+        g.alignPairs(cl, [(0, 3), (1, 3), (2, 3)])
+    assert e.value.status == NDT_ERR_GRID_OVERFLOW and "overflow" in str(e.value)
+    for c in range(len(cl)):
+        nl, nv = ndt.C.c_size_t(0), ndt.C.c_size_t(0)
+        assert g._L.ndt_pairs_grid_size(g._h, c, ndt.C.byref(nl), ndt.C.byref(nv)) == NDT_ERR_NO_INPUT, c
+    now = g.grid()
+    for k in GRID_FIELDS:
+        assert np.array_equal(now[k], grid_before[k]), k
+    assert same_registration(own_registration(g), before)
+    # and the handle goes on: the same call without the wide cloud
+    res = g.alignPairs([B, D, C], [(0, 2), (1, 2)])
+    assert res["T"].shape == (2, 4, 4) and len(g.pairsGrid(1)["idx"]) > 50
+
+
 def sequence(clouds, ndt, tmp_path, n=6):
     rng = np.random.default_rng(19)
     world = clouds.target_surfaces(60000, seed=77, extent=60.0)[:, :3].astype(np.float32)

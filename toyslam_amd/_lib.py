@@ -108,6 +108,7 @@ SIGNATURES = {
     "ndt_host_acc_pack_cell": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
     "ndt_host_acc_unpack_cell": (None, [C.c_uint64, ip, ip, ip]),
     "ndt_host_chain_pose": (None, [fp, fp, fp]),
+    "ndt_host_lattice": (C.c_int, [C.c_float, fp, fp, ip, ip, ip, C.POINTER(C.c_longlong), C.c_int, C.c_longlong, ip]),
     "ndt_pcd_read_header": (C.c_int, [C.c_char_p, szp, ip, ip]),
     "ndt_pcd_read_xyz": (C.c_int, [C.c_char_p, vp, C.c_size_t, C.c_size_t, szp, ip]),
     "ndt_pcd_write_xyz": (C.c_int, [C.c_char_p, vp, C.c_size_t, C.c_size_t, C.c_int]),

@@ -116,18 +116,10 @@ constexpr long long kGicpMaxCells = 1ll << 26;       // dense cell table budget 
 // The voxel index of `cloud` (on the device, every point finite -- so the box the cloud carries over its finite points is
 // the box of all of them) into in.grid: leaf size from the cloud's own density (volume guess first, then corrected once
 // from the measured points per occupied cell -- scans are surfaces, so occupancy grows with the square of the leaf).
-// Built with `c`: its stream, its scratch, its pool (the caller has made `c` current).  `c` is handed the cloud for the
-// build alone and keeps neither it nor the grid.
+// Built with `c`: its stream, its scratch, its pool (the caller has made `c` current); `c` holds neither the cloud nor the grid.
 ndt_status gicp_index_cloud(ndt_context* c, const std::shared_ptr<DeviceCloud>& cloud, LeafHint& hint, GicpInput& in) {
-  struct Lend {
-    ndt_context* c;
-    ~Lend() { c->grid.reset(); c->target.reset(); }
-  } lend{c};
   in.grid.reset();  // (before the new one is allocated: an input never holds two)
-  c->target = cloud;
-  c->target_dense = 1;
-  c->min_pts = 1;
-  c->index_only = true;
+  std::shared_ptr<DeviceGrid> grid;
   const size_t n = cloud->n;
   ndt_status s = NDT_OK;
   double ext[3], vol = 1.0;
@@ -149,13 +141,12 @@ ndt_status gicp_index_cloud(ndt_context* c, const std::shared_ptr<DeviceCloud>& 
   // not depend on the leaf, only the time does)
   if (hint.leaf > 0 && n >= hint.n - hint.n / 4 && n <= hint.n + hint.n / 4) leaf = clamp_leaf(hint.leaf);
   for (int pass = 0; pass < 4; pass++) {
-    c->resolution = leaf;
-    s = build_grid(c);
+    s = build_grid(c, cloud, GridSpec{leaf, 1, c->eig_ratio, 0, true, true}, grid);  // cells and their point lists only
     if (s) return s;
-    s = grid_counts(c, c->grid.get());
+    s = grid_counts(c, grid.get());
     if (s) return s;
-    const double per_cell = static_cast<double>(n) / static_cast<double>(std::max<size_t>(c->grid->n_leaves, 1));
-    if (per_cell <= 2.0 * kGicpPointsPerCell && (per_cell >= 0.4 * kGicpPointsPerCell || c->grid->n_leaves <= 8)) break;
+    const double per_cell = static_cast<double>(n) / static_cast<double>(std::max<size_t>(grid->n_leaves, 1));
+    if (per_cell <= 2.0 * kGicpPointsPerCell && (per_cell >= 0.4 * kGicpPointsPerCell || grid->n_leaves <= 8)) break;
     // too coarse (dense surfaces) or too fine (flat / thin clouds, where the volume guess means little)
     const float next = clamp_leaf(static_cast<double>(leaf) * std::sqrt(kGicpPointsPerCell / per_cell));
     if (next < 0.9f * leaf || next > 1.1f * leaf) leaf = next;
@@ -163,11 +154,11 @@ ndt_status gicp_index_cloud(ndt_context* c, const std::shared_ptr<DeviceCloud>& 
   }
   if (std::getenv("NDT_GICP_DEBUG"))
     std::fprintf(stderr, "[gicp index] n=%zu leaf=%.4f cells=%lld (%d x %d x %d) occupied=%zu\n", n, static_cast<double>(leaf),
-                 c->grid->geom.n_cells, c->grid->geom.div_b[0], c->grid->geom.div_b[1], c->grid->geom.div_b[2], c->grid->n_leaves);
+                 grid->geom.n_cells, grid->geom.div_b[0], grid->geom.div_b[1], grid->geom.div_b[2], grid->n_leaves);
   hint.leaf = leaf;
   hint.n = n;
-  s = ensure_cell2leaf(c, c->grid.get());
-  if (!s) in.grid = std::move(c->grid);
+  s = ensure_cell2leaf(c, grid.get());
+  if (!s) in.grid = std::move(grid);
   return s;
 }
 

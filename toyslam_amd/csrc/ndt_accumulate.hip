@@ -343,27 +343,12 @@ struct AccScan {
   const float* pose = nullptr;
 };
 
-// VoxelGridCovariance geometry of the box (voxel_grid_covariance_omp_impl.hpp:75-103), as grid_head computes it for a cloud
+// the lattice of the accumulated box (lattice_geometry: what a cloud's grid gets) and its padded table
 ndt_status acc_geometry(float resolution, const float* min_p, const float* max_p, ndt::GridGeom& geo) {
-  for (int k = 0; k < 3; k++) {
-    geo.leaf[k] = resolution;
-    geo.inv_leaf[k] = 1.0f / resolution;
-  }
-  long long d[3];
-  for (int k = 0; k < 3; k++) d[k] = static_cast<long long>((max_p[k] - min_p[k]) * geo.inv_leaf[k]) + 1;
-  if (d[0] * d[1] * d[2] > static_cast<long long>(std::numeric_limits<int32_t>::max()))
+  const ndt::LatticeStatus ls = ndt::lattice_geometry(resolution, min_p, max_p, geo);
+  if (ls == ndt::kLatticeIndexOverflow)
     return fail(NDT_ERR_GRID_OVERFLOW, "leaf size is too small for the accumulated target: integer indices would overflow");
-  for (int k = 0; k < 3; k++) {
-    geo.min_b[k] = static_cast<int>(std::floor(min_p[k] * geo.inv_leaf[k]));
-    geo.max_b[k] = static_cast<int>(std::floor(max_p[k] * geo.inv_leaf[k]));
-    geo.div_b[k] = geo.max_b[k] - geo.min_b[k] + 1;
-  }
-  geo.mul[0] = 1;
-  geo.mul[1] = geo.div_b[0];
-  geo.mul[2] = geo.div_b[0] * geo.div_b[1];
-  geo.n_cells = static_cast<long long>(geo.div_b[0]) * geo.div_b[1] * geo.div_b[2];
-  if (geo.n_cells <= 0 || geo.n_cells > static_cast<long long>(std::numeric_limits<int32_t>::max()))
-    return fail(NDT_ERR_GRID_OVERFLOW, "voxel grid too large");
+  if (ls != ndt::kLatticeOk) return fail(NDT_ERR_GRID_OVERFLOW, "voxel grid too large");
   ndt::set_padded_lut(geo);
   return NDT_OK;
 }
@@ -554,9 +539,9 @@ ndt_status acc_update(ndt_context* h, const std::vector<AccScan>& scans, size_t 
   if (have_box) {
     const ndt_status gs = acc_geometry(a->resolution, mn, mx, geo);
     if (gs) return gs;
-    // dense or sparse, by grid_head's rule for a cloud of the points accumulated so far
+    // dense or sparse, by the rule for a cloud of the points accumulated so far
     const long long np = static_cast<long long>(std::min<size_t>(n_points, static_cast<size_t>(std::numeric_limits<int>::max())));
-    sparse = h->voxel_index == 2 || (h->voxel_index == 0 && (geo.n_cells > (1ll << 25) || geo.n_cells > 64ll * np + (1ll << 22)));
+    sparse = ndt::wants_sparse_index(h->voxel_index, geo.n_cells, np);
   }
   if (static_cast<long long>(a->n_slots) + n_new > (1ll << 30)) return fail(NDT_ERR_INVALID, "too many voxels in the accumulated target");
   // ---- from here on the target changes

@@ -280,22 +280,9 @@ ndt_status order_range(ndt_context* h, const float4* d_pts, size_t n, float pitc
   const float* max_p = bb.mx;
   if (!(min_p[0] <= max_p[0])) return NDT_OK;  // no finite point
   ndt::GridGeom geo{};
-  for (;; pitch *= 2.0f) {
-    double cells = 1;
-    for (int k = 0; k < 3; k++) {
-      geo.leaf[k] = pitch;
-      geo.inv_leaf[k] = 1.0f / pitch;
-      geo.min_b[k] = static_cast<int>(std::floor(min_p[k] * geo.inv_leaf[k]));
-      geo.max_b[k] = static_cast<int>(std::floor(max_p[k] * geo.inv_leaf[k]));
-      geo.div_b[k] = geo.max_b[k] - geo.min_b[k] + 1;
-      cells *= geo.div_b[k];
-    }
-    if (cells <= 4.0e6) break;
-  }
-  geo.mul[0] = 1;
-  geo.mul[1] = geo.div_b[0];
-  geo.mul[2] = geo.div_b[0] * geo.div_b[1];
-  geo.n_cells = static_cast<long long>(geo.div_b[0]) * geo.div_b[1] * geo.div_b[2];
+  // the pitch doubled until the lattice has at most 4e6 cells (either overflow status means far more: an extent of d cells
+  // spans at least d / 2 of them, so over INT32_MAX by the reference's test is over 2^28 cells -- the same pitch is chosen)
+  while (ndt::lattice_geometry(pitch, min_p, max_p, geo) != ndt::kLatticeOk || geo.n_cells > 4000000) pitch *= 2.0f;
   // Big clouds: stable radix passes of K1's order-preserving scatter (launch_order_radix) -- the same order, point for point,
   // as the counting sort below (NDT_ORDER=chain: that one always).
   static const bool radix_on = [] { const char* v = getenv("NDT_ORDER"); return !v || std::strcmp(v, "chain") != 0; }();
@@ -507,65 +494,45 @@ ndt_status order_cloud(ndt_context* h, DeviceCloud* c, const size_t* offsets, si
 
 static ndt_status compact_records_now(ndt_context* h, DeviceGrid* g);
 
-// The first half of build_grid: the geometry of h->target's grid and the form that builds it.  hd.done: nothing to build
-// (no point, no finite point, or the reference's overflow) -- h->grid already holds the finished grid.
-ndt_status grid_head(ndt_context* h, GridHead& hd) {
+// The first half of build_grid: the geometry of the cloud's grid hd.g and what its build needs.  hd.done: nothing to build
+// (no point, no finite point, or the reference's overflow) -- hd.g is the finished (empty) grid.  A failure other than that
+// overflow leaves hd.g null.
+struct GridHead {
+  std::shared_ptr<DeviceGrid> g;  // geometry set
+  int n = 0;
+  size_t max_leaves = 0, max_cand = 0;
+  bool sparse = false, done = true;
+};
+static ndt_status grid_head(const std::shared_ptr<DeviceCloud>& cloud, const GridSpec& spec, GridHead& hd) {
   hd.done = true;
-  if (!h->target) return fail(NDT_ERR_NO_INPUT, "no target");
+  if (!cloud) return fail(NDT_ERR_NO_INPUT, "no target");
   auto g = std::make_shared<DeviceGrid>();
   hd.g = g;
-  g->target = h->target;
-  g->resolution = h->resolution;
-  g->min_pts = h->min_pts;
-  g->eig_ratio = h->eig_ratio;
-  const int n = static_cast<int>(h->target->n);
+  g->target = cloud;
+  g->resolution = spec.resolution;
+  g->min_pts = spec.min_pts;
+  g->eig_ratio = spec.eig_ratio;
+  const int n = static_cast<int>(cloud->n);
   ndt::GridGeom& geo = g->geom;
   for (int k = 0; k < 3; k++) {
-    geo.leaf[k] = h->resolution;
-    geo.inv_leaf[k] = 1.0f / h->resolution;  // [PCL] VoxelGrid::setLeafSize
+    geo.leaf[k] = spec.resolution;
+    geo.inv_leaf[k] = 1.0f / spec.resolution;  // [PCL] VoxelGrid::setLeafSize
   }
-  if (n == 0) {
-    h->grid = g;
-    return NDT_OK;
-  }
-  // ---- bbox
-  const BBox bb = bbox_of(*h->target, h->target_dense);  // computed during the upload: no kernel, no wait
-  const float* min_p = bb.mn;
-  const float* max_p = bb.mx;
-  if (!(min_p[0] <= max_p[0])) {  // no finite point at all
-    h->grid = g;
-    return NDT_OK;
-  }
-  // ---- geometry, voxel_grid_covariance_omp_impl.hpp:75-103
-  long long d[3];
-  for (int k = 0; k < 3; k++) d[k] = static_cast<long long>((max_p[k] - min_p[k]) * geo.inv_leaf[k]) + 1;
-  if (d[0] * d[1] * d[2] > static_cast<long long>(std::numeric_limits<int32_t>::max())) {
-    h->grid = g;  // the reference warns and leaves an empty grid (:79-84)
+  if (n == 0) return NDT_OK;
+  const BBox bb = bbox_of(*cloud, spec.dense);  // computed during the upload: no kernel, no wait
+  if (!(bb.mn[0] <= bb.mx[0])) return NDT_OK;  // no finite point at all
+  const ndt::LatticeStatus ls = ndt::lattice_geometry(spec.resolution, bb.mn, bb.mx, geo);
+  if (ls == ndt::kLatticeIndexOverflow)  // the reference warns and leaves an empty grid (:79-84)
     return fail(NDT_ERR_GRID_OVERFLOW, "leaf size is too small for the input dataset: integer indices would overflow");
-  }
-  for (int k = 0; k < 3; k++) {
-    geo.min_b[k] = static_cast<int>(std::floor(min_p[k] * geo.inv_leaf[k]));
-    geo.max_b[k] = static_cast<int>(std::floor(max_p[k] * geo.inv_leaf[k]));
-    geo.div_b[k] = geo.max_b[k] - geo.min_b[k] + 1;
-  }
-  geo.mul[0] = 1;
-  geo.mul[1] = geo.div_b[0];
-  geo.mul[2] = geo.div_b[0] * geo.div_b[1];
-  geo.n_cells = static_cast<long long>(geo.div_b[0]) * geo.div_b[1] * geo.div_b[2];
-  if (geo.n_cells <= 0 || geo.n_cells > static_cast<long long>(std::numeric_limits<int32_t>::max()))
+  if (ls != ndt::kLatticeOk) {
+    hd.g.reset();
     return fail(NDT_ERR_GRID_OVERFLOW, "voxel grid too large");
-
-  const size_t max_leaves = std::min<size_t>(static_cast<size_t>(n), static_cast<size_t>(geo.n_cells));
-  const size_t max_cand = std::min<size_t>(max_leaves, static_cast<size_t>(n) / static_cast<size_t>(std::max(1, h->min_pts)) + 1);
+  }
   ndt::set_padded_lut(geo);
-  // Dense or sparse voxel index?  Dense (a table over the whole bounding box, one dependent load per probe) as long as the
-  // cell count stays within reach of the point count; sparse (sort-based build, hash look-up: ndt_sparse.hip) when the box
-  // is mostly empty -- the regime the reference's std::map handles for free.  ndt_set_voxel_index overrides.
-  const bool sparse = !h->index_only && (h->voxel_index == 2 || (h->voxel_index == 0 && (geo.n_cells > (1ll << 25) || geo.n_cells > 64ll * n + (1ll << 22))));
   hd.n = n;
-  hd.max_leaves = max_leaves;
-  hd.max_cand = max_cand;
-  hd.sparse = sparse;
+  hd.max_leaves = std::min<size_t>(static_cast<size_t>(n), static_cast<size_t>(geo.n_cells));
+  hd.max_cand = std::min<size_t>(hd.max_leaves, static_cast<size_t>(n) / static_cast<size_t>(std::max(1, spec.min_pts)) + 1);
+  hd.sparse = !spec.index_only && ndt::wants_sparse_index(spec.voxel_index, geo.n_cells, n);
   hd.done = false;
   return NDT_OK;
 }
@@ -574,23 +541,23 @@ ndt_status grid_head(ndt_context* h, GridHead& hd) {
 // short runs (k1_bucket), is the faster one for every cloud shape measured, uniform to heavily clustered (tools/time_k1_forms.py);
 // NDT_K1=old: the general chain, kept for index-only builds -- GICP's search index -- and as the cross-check of tools/fuzz_grid.py.
 enum K1Form { K1_CHAIN, K1_BUCKETS, K1_SMALL };
-static K1Form k1_form(const ndt_context* h, const GridHead& hd, ndt::GridBuildPlan& plan) {
+static K1Form k1_form(const GridSpec& spec, const GridHead& hd, ndt::GridBuildPlan& plan) {
   static const bool chain_only = [] { const char* v = getenv("NDT_K1"); return v && std::strcmp(v, "old") == 0; }();
   static const bool small_on = [] { const char* v = getenv("NDT_K1_SMALL"); return !v || atoi(v) != 0; }();
-  if (hd.sparse || chain_only || h->index_only || !ndt::grid_build_plan(hd.g->geom.n_cells, hd.n, plan)) return K1_CHAIN;
+  if (hd.sparse || chain_only || spec.index_only || !ndt::grid_build_plan(hd.g->geom.n_cells, hd.n, plan)) return K1_CHAIN;
   return small_on && ndt::grid_build_small_applies(hd.n, plan) ? K1_SMALL : K1_BUCKETS;
 }
 // NDT_K1_STAMPS=1: the bucket form's phase clocks on stderr (development aid)
 static bool k1_stamps_on() { static const bool on = [] { const char* v = getenv("NDT_K1_STAMPS"); return v && atoi(v) != 0; }(); return on; }
 
-// A bucket-form build of hd's target with the bucket plan `plan`: the grid's buffers (scratch: the finish's [5 n] words) and
+// A bucket-form build of hd's cloud with the bucket plan `plan`: the grid's buffers (scratch: the finish's [5 n] words) and
 // state as the build leaves it, and for the one-launch form (k1_small; many targets: k1_small_multi) the launch in *D (*lds: its
 // dynamic LDS; multi: k1_small_multi's lists).
-static ndt_status setup_bucket_form(ndt_context* h, const GridHead& hd, const ndt::GridBuildPlan& plan, DevBuf<unsigned>& scratch,
+static ndt_status setup_bucket_form(const GridSpec& spec, const GridHead& hd, const ndt::GridBuildPlan& plan, DevBuf<unsigned>& scratch,
                                     ndt::SmallBuildDesc* D, size_t* lds, bool multi) {
   DeviceGrid* g = hd.g.get();
   const size_t n = static_cast<size_t>(hd.n), K = static_cast<size_t>(plan.n_buckets);
-  const size_t rec_slots = n / static_cast<size_t>(std::max(1, h->min_pts)) + 1;  // slot = segment start / min_pts
+  const size_t rec_slots = n / static_cast<size_t>(std::max(1, spec.min_pts)) + 1;  // slot = segment start / min_pts
   HIP_TRY(g->counts.reserve(8));  // (build_grid has reserved these and the table before it chooses the form)
   HIP_TRY(g->leaf_cell.reserve(hd.max_leaves));
   HIP_TRY(g->leaf_start.reserve(hd.max_leaves));
@@ -609,11 +576,11 @@ static ndt_status setup_bucket_form(ndt_context* h, const GridHead& hd, const nd
   g->empty = false;
   if (!D) return NDT_OK;
   if (!ndt::small_build_desc(hd.n, plan, multi, *D, lds)) return fail(NDT_ERR_HIP, "one-launch grid build: the finish's LDS does not fit");
-  D->pts = h->target->pts.p;
-  D->dense = h->target_dense;
+  D->pts = g->target->pts.p;
+  D->dense = spec.dense;
   D->g = g->geom;
-  D->min_pts = h->min_pts;
-  D->eig_ratio = h->eig_ratio;
+  D->min_pts = spec.min_pts;
+  D->eig_ratio = spec.eig_ratio;
   D->bucket_base = g->bucket_base.p;
   D->bpts = g->bpts.p;
   D->sorted_idx = g->sorted_idx.p;
@@ -673,12 +640,16 @@ static ndt_status print_k1_stamps(ndt_context* h, const unsigned long long* stam
 }
 
 // VoxelGridCovariance::filter(true) on the GPU.
-ndt_status build_grid(ndt_context* h) {
+ndt_status build_grid(ndt_context* h, const std::shared_ptr<DeviceCloud>& cloud, const GridSpec& spec, std::shared_ptr<DeviceGrid>& out) {
   GridHead hd;
-  ndt_status hs = grid_head(h, hd);
-  if (hs || hd.done) return hs;
+  ndt_status hs = grid_head(cloud, spec, hd);
+  if (hs || hd.done) {
+    if (hd.g) out = hd.g;  // the empty grid (no point, no finite point, the reference's overflow)
+    return hs;
+  }
   const std::shared_ptr<DeviceGrid> g = hd.g;
   const int n = hd.n;
+  const float4* pts = cloud->pts.p;
   ndt::GridGeom& geo = g->geom;
   const size_t max_leaves = hd.max_leaves, max_cand = hd.max_cand;
   hipStream_t st = h->stream;
@@ -689,7 +660,7 @@ ndt_status build_grid(ndt_context* h) {
   HIP_TRY(g->leaf_rec.reserve(max_leaves));
   HIP_TRY(g->sorted_idx.reserve(n));
   if (hd.sparse) {
-    const size_t rec_slots = static_cast<size_t>(n) / static_cast<size_t>(std::max(1, h->min_pts)) + 1;  // slot = segment start / min_pts
+    const size_t rec_slots = static_cast<size_t>(n) / static_cast<size_t>(std::max(1, spec.min_pts)) + 1;  // slot = segment start / min_pts
     HIP_TRY(g->recs.reserve(rec_slots));
     HIP_TRY(g->centroids.reserve(rec_slots));
     int bits = 10;
@@ -704,23 +675,23 @@ ndt_status build_grid(ndt_context* h) {
     HIP_TRY(temp.reserve(tb));
     HIP_TRY(w.reserve(4 * static_cast<size_t>(n)));
     HIP_TRY(vals.reserve(n));
-    HIP_TRY(ndt::launch_sparse_index(h->target->pts.p, n, h->target_dense, geo, h->min_pts, temp.p, tb, w.p, w.p + n, vals.p, w.p + 2 * static_cast<size_t>(n),
+    HIP_TRY(ndt::launch_sparse_index(pts, n, spec.dense, geo, spec.min_pts, temp.p, tb, w.p, w.p + n, vals.p, w.p + 2 * static_cast<size_t>(n),
                                      w.p + 3 * static_cast<size_t>(n), g->leaf_cell.p, g->leaf_start.p, g->leaf_count.p, g->leaf_rec.p, g->sorted_idx.p,
                                      g->counts.p, st));
     ndt::FinalizeDump nodump{nullptr, nullptr, nullptr, nullptr, nullptr};
     DevBuf<float4> big_pts;
     HIP_TRY(big_pts.reserve(n));
-    HIP_TRY(ndt::launch_finalize(h->target->pts.p, g->leaf_cell.p, g->leaf_start.p, g->leaf_count.p, g->leaf_rec.p, static_cast<int>(max_leaves),
-                                 g->sorted_idx.p, h->min_pts, h->eig_ratio, g->recs.p, g->centroids.p, g->lut.p, geo, g->counts.p + 3, nodump, st,
+    HIP_TRY(ndt::launch_finalize(pts, g->leaf_cell.p, g->leaf_start.p, g->leaf_count.p, g->leaf_rec.p, static_cast<int>(max_leaves),
+                                 g->sorted_idx.p, spec.min_pts, spec.eig_ratio, g->recs.p, g->centroids.p, g->lut.p, geo, g->counts.p + 3, nodump, st,
                                  g->counts.p, big_pts.p));
     g->counts_known = false;
     g->empty = false;
-    h->grid = g;
+    out = g;
     return NDT_OK;
   }
   HIP_TRY(g->lut.reserve(static_cast<size_t>(geo.lut_cells)));
   ndt::GridBuildPlan plan{};
-  const K1Form form = k1_form(h, hd, plan);
+  const K1Form form = k1_form(spec, hd, plan);
   if (form != K1_CHAIN) {
     // ---- bucket form (ndt_kernels.hip "K1, bucket form"): no per-point global atomic, per-voxel work staged through LDS
     const size_t K = static_cast<size_t>(plan.n_buckets);
@@ -732,7 +703,7 @@ ndt_status build_grid(ndt_context* h) {
     }
     ndt::SmallBuildDesc D{};
     size_t lds = 0;
-    hs = setup_bucket_form(h, hd, plan, order, form == K1_SMALL ? &D : nullptr, &lds, false);
+    hs = setup_bucket_form(spec, hd, plan, order, form == K1_SMALL ? &D : nullptr, &lds, false);
     if (hs) return hs;
     if (form == K1_SMALL) {
       HIP_TRY(ndt::launch_grid_build_small(D, lds, stamps.p, st));
@@ -740,7 +711,7 @@ ndt_status build_grid(ndt_context* h) {
       HIP_TRY(cntmat.reserve((static_cast<size_t>(plan.n_blocks) + 1) * K));
       static const bool index_form_env = [] { const char* v = getenv("NDT_K1_INDEX"); return v && atoi(v) != 0; }();
       const ndt::GridBuildScratch S{cntmat.p, g->bucket_base.p, g->bpts.p, order.p, stamps.p, index_form_env};
-      HIP_TRY(ndt::launch_grid_build_buckets(h->target->pts.p, n, h->target_dense, geo, plan, h->min_pts, h->eig_ratio, S, g->sorted_idx.p,
+      HIP_TRY(ndt::launch_grid_build_buckets(pts, n, spec.dense, geo, plan, spec.min_pts, spec.eig_ratio, S, g->sorted_idx.p,
                                              g->recs.p, g->centroids.p, g->lut.p, g->counts.p, st));
       g->index_form = S.index_form;
     }
@@ -770,26 +741,26 @@ ndt_status build_grid(ndt_context* h) {
   HIP_TRY(key.reserve(n));
   HIP_TRY(rank.reserve(n));
   HIP_TRY(hipMemsetAsync(cell_count.p, 0, static_cast<size_t>(geo.n_cells) * sizeof(unsigned), st));
-  HIP_TRY(ndt::launch_count(h->target->pts.p, n, h->target_dense, geo, key.p, rank.p, cell_count.p, st));
+  HIP_TRY(ndt::launch_count(pts, n, spec.dense, geo, key.p, rank.p, cell_count.p, st));
   // ---- scan
   const int n_tiles = ndt::scan_tiles(geo.n_cells);
   HIP_TRY(block_sums.reserve(static_cast<size_t>(n_tiles) * 3));
-  HIP_TRY(ndt::launch_scan_reduce(cell_count.p, geo.n_cells, h->min_pts, block_sums.p, n_tiles, st));
+  HIP_TRY(ndt::launch_scan_reduce(cell_count.p, geo.n_cells, spec.min_pts, block_sums.p, n_tiles, st));
   HIP_TRY(ndt::launch_scan_blocks(block_sums.p, n_tiles, g->counts.p, st));
   // The counts stay on the device: the later kernels read the voxel count there, the arrays are sized
   // for the worst case, and the host fetches the four numbers only if somebody asks (grid_counts()).
   // Two host round trips (~30 us each) less per target; nothing below waits for the GPU.
-  HIP_TRY(ndt::launch_scan_apply(cell_count.p, geo.n_cells, h->min_pts, block_sums.p, n_tiles, g->leaf_cell.p,
+  HIP_TRY(ndt::launch_scan_apply(cell_count.p, geo.n_cells, spec.min_pts, block_sums.p, n_tiles, g->leaf_cell.p,
                                  g->leaf_start.p, g->leaf_count.p, g->leaf_rec.p, st));
   // ---- scatter + finalize
   HIP_TRY(ndt::launch_scatter(key.p, rank.p, n, cell_count.p, g->sorted_idx.p, st));
   HIP_TRY(hipMemsetAsync(g->counts.p + 3, 0, 2 * sizeof(unsigned), st));
   ndt::FinalizeDump nodump{nullptr, nullptr, nullptr, nullptr, nullptr};
   DevBuf<float4> big_pts;  // scratch of the crowded-leaf path (k_presort_large)
-  if (!h->index_only) {
+  if (!spec.index_only) {
     HIP_TRY(big_pts.reserve(n));
-    HIP_TRY(ndt::launch_finalize(h->target->pts.p, g->leaf_cell.p, g->leaf_start.p, g->leaf_count.p, g->leaf_rec.p,
-                                 static_cast<int>(max_leaves), g->sorted_idx.p, h->min_pts, h->eig_ratio, g->recs.p, g->centroids.p,
+    HIP_TRY(ndt::launch_finalize(pts, g->leaf_cell.p, g->leaf_start.p, g->leaf_count.p, g->leaf_rec.p,
+                                 static_cast<int>(max_leaves), g->sorted_idx.p, spec.min_pts, spec.eig_ratio, g->recs.p, g->centroids.p,
                                  g->lut.p, geo, g->counts.p + 3, nodump, st, g->counts.p, big_pts.p));
   }
   }
@@ -797,49 +768,38 @@ ndt_status build_grid(ndt_context* h) {
   // pool hands memory out again only to work queued on the same stream, i.e. after these kernels
   g->counts_known = false;
   g->empty = false;
-  h->grid = g;
+  out = g;
   return NDT_OK;
 }
 
 ndt_status build_grids(ndt_context* h, const std::vector<std::shared_ptr<DeviceCloud>>& targets, int is_dense,
                        std::vector<std::shared_ptr<DeviceGrid>>& out, size_t* n_small) {
-  const std::shared_ptr<DeviceCloud> keep_target = h->target;
-  const std::shared_ptr<DeviceGrid> keep_grid = h->grid;
-  const int keep_dense = h->target_dense;
+  const GridSpec spec = grid_spec_of(h, is_dense);
   out.assign(targets.size(), nullptr);
   std::vector<ndt::SmallBuildDesc> descs;
   std::vector<std::unique_ptr<DevBuf<unsigned>>> scratch;  // per small target: [5 n] (back to the pool behind the launch)
   int max_K = 0;
   size_t lds = 0;
   ndt_status s = NDT_OK;
-  for (size_t i = 0; i < targets.size() && !s; i++) {
-    h->target = targets[i];
-    h->target_dense = is_dense ? 1 : 0;
+  for (size_t i = 0; i < targets.size(); i++) {
     GridHead hd;
-    s = grid_head(h, hd);
-    if (s) break;
-    if (hd.done) {
-      out[i] = h->grid;
-      continue;
-    }
+    s = grid_head(targets[i], spec, hd);
+    if (s) return s;
+    out[i] = hd.g;
+    if (hd.done) continue;
     // the one-launch form where build_grid takes it; stamped builds (development aid) through build_grid
     ndt::GridBuildPlan plan{};
-    if (k1_stamps_on() || k1_form(h, hd, plan) != K1_SMALL) {
-      s = build_grid(h);
-      out[i] = h->grid;
+    if (k1_stamps_on() || k1_form(spec, hd, plan) != K1_SMALL) {
+      s = build_grid(h, targets[i], spec, out[i]);
+      if (s) return s;
       continue;
     }
     size_t lds_i = 0;
-    s = setup_bucket_form(h, hd, plan, *scratch.emplace_back(new DevBuf<unsigned>()), &descs.emplace_back(), &lds_i, true);
-    if (s) break;
+    s = setup_bucket_form(spec, hd, plan, *scratch.emplace_back(new DevBuf<unsigned>()), &descs.emplace_back(), &lds_i, true);
+    if (s) return s;
     max_K = std::max(max_K, plan.n_buckets);
     lds = std::max(lds, lds_i);
-    out[i] = hd.g;
   }
-  h->target = keep_target;
-  h->grid = keep_grid;
-  h->target_dense = keep_dense;
-  if (s) return s;
   *n_small = descs.size();
   if (descs.empty()) return NDT_OK;
   DevBuf<ndt::SmallBuildDesc> d_descs;
@@ -1066,25 +1026,10 @@ FilterRoute filter_route(const ndt_context* h, size_t n, const BBox& bb, float l
   const float* max_p = bb.mx;
   if (n == 0 || !(min_p[0] <= max_p[0])) return r;  // no finite point: empty output
   ndt::GridGeom& geo = r.geo;
-  long long d[3];
-  for (int k = 0; k < 3; k++) {
-    geo.leaf[k] = leaf;
-    geo.inv_leaf[k] = 1.0f / leaf;
-    d[k] = static_cast<long long>((max_p[k] - min_p[k]) * geo.inv_leaf[k]) + 1;
-  }
-  if (d[0] * d[1] * d[2] > static_cast<long long>(std::numeric_limits<int32_t>::max())) {
+  if (ndt::lattice_geometry(leaf, min_p, max_p, geo) == ndt::kLatticeIndexOverflow) {
     r.kind = FilterRoute::kOverflow;
     return r;
   }
-  for (int k = 0; k < 3; k++) {
-    geo.min_b[k] = static_cast<int>(std::floor(min_p[k] * geo.inv_leaf[k]));
-    geo.max_b[k] = static_cast<int>(std::floor(max_p[k] * geo.inv_leaf[k]));
-    geo.div_b[k] = geo.max_b[k] - geo.min_b[k] + 1;
-  }
-  geo.mul[0] = 1;
-  geo.mul[1] = geo.div_b[0];
-  geo.mul[2] = geo.div_b[0] * geo.div_b[1];
-  geo.n_cells = static_cast<long long>(geo.div_b[0]) * geo.div_b[1] * geo.div_b[2];
   // a fine leaf over a wide box (apps/align.cpp: 0.1 m over a whole scan): per-point work only (ndt_sparse.hip)
   const bool sparse = h->voxel_index == 2 || (h->voxel_index == 0 && geo.n_cells > 16ll * static_cast<long long>(n) + (1ll << 22));
   r.kind = sparse ? FilterRoute::kSparse : FilterRoute::kDense;
@@ -1264,7 +1209,7 @@ static ndt_status set_target_impl(ndt_handle h, const void* pts, size_t n, size_
   if (s) return s;
   h->target = c;
   h->target_dense = is_dense ? 1 : 0;
-  return build_grid(h);  // init(), ndt_omp.h:276-283
+  return build_grid(h, c, grid_spec_of(h, is_dense), h->grid);  // init(), ndt_omp.h:276-283
 }
 ndt_status ndt_set_input_target(ndt_handle h, const void* pts, size_t n, size_t stride, int is_dense) {
   return set_target_impl(h, pts, n, stride, is_dense, false);
@@ -1858,7 +1803,7 @@ ndt_status ndt_set_input_target_cloud(ndt_handle h, ndt_cloud c, int is_dense) {
   if (s) return s;
   h->target = c->c;
   h->target_dense = is_dense ? 1 : 0;
-  return build_grid(h);
+  return build_grid(h, h->target, grid_spec_of(h, is_dense), h->grid);
 }
 ndt_status ndt_promote_source_to_target(ndt_handle h, int is_dense) {
   if (!h) return fail(NDT_ERR_INVALID, "null handle");
@@ -1868,7 +1813,7 @@ ndt_status ndt_promote_source_to_target(ndt_handle h, int is_dense) {
   // the resident points and their boxes: no upload, no repack, no bounding-box pass (a view made for ordering: its parent)
   h->target = h->source->parent ? h->source->parent : h->source;
   h->target_dense = is_dense ? 1 : 0;
-  return build_grid(h);
+  return build_grid(h, h->target, grid_spec_of(h, is_dense), h->grid);
 }
 
 ndt_status ndt_map_update_cloud(ndt_handle h, ndt_cloud scan, int is_dense, const float* pose, float leaf, int* overflowed) {
@@ -2021,35 +1966,64 @@ ndt_status ndt_map_get_device(ndt_handle h, const void** d_pts, size_t* n) {
   return NDT_OK;
 }
 void ndt_host_chain_pose(const float* pose, const float* transform, float* out) { ndt::chain_pose(pose, transform, out); }
-
-ndt_status ndt_grid_size(ndt_handle h, size_t* n_leaves, size_t* n_valid) {
-  if (!h || !h->grid) return fail(NDT_ERR_NO_INPUT, "no grid");
-  if (!h->grid->empty) {
-    ndt_status s = ensure_device(h);
-    if (!s) s = grid_counts(h, h->grid.get());
-    if (s) return s;
+ndt_status ndt_host_lattice(float leaf, const float* mn, const float* mx, int* min_b, int* max_b, int* div_b, long long* n_cells,
+                            int voxel_index, long long n_points, int* sparse) {
+  if (!mn || !mx || !(leaf > 0)) return fail(NDT_ERR_INVALID, "bad arguments");
+  ndt::GridGeom geo{};
+  if (ndt::lattice_geometry(leaf, mn, mx, geo) != ndt::kLatticeOk)
+    return fail(NDT_ERR_GRID_OVERFLOW, "leaf size is too small for the box: integer indices would overflow");
+  for (int k = 0; k < 3; k++) {
+    if (min_b) min_b[k] = geo.min_b[k];
+    if (max_b) max_b[k] = geo.max_b[k];
+    if (div_b) div_b[k] = geo.div_b[k];
   }
-  if (n_leaves) *n_leaves = h->grid->n_leaves;
-  if (n_valid) *n_valid = h->grid->n_valid;
+  if (n_cells) *n_cells = geo.n_cells;
+  if (sparse) *sparse = ndt::wants_sparse_index(voxel_index, geo.n_cells, n_points) ? 1 : 0;
   return NDT_OK;
 }
 
+ndt_status ndt_grid_size(ndt_handle h, size_t* n_leaves, size_t* n_valid) {
+  if (!h || !h->grid) return fail(NDT_ERR_NO_INPUT, "no grid");
+  return grid_size(h, h->grid.get(), n_leaves, n_valid);
+}
 ndt_status ndt_grid_info(ndt_handle h, int* min_b, int* max_b, int* div_b) {
   if (!h || !h->grid) return fail(NDT_ERR_NO_INPUT, "no grid");
-  for (int k = 0; k < 3; k++) {
-    if (min_b) min_b[k] = h->grid->geom.min_b[k];
-    if (max_b) max_b[k] = h->grid->geom.max_b[k];
-    if (div_b) div_b[k] = h->grid->geom.div_b[k];
-  }
+  grid_info(h->grid.get(), min_b, max_b, div_b);
   return NDT_OK;
+}
+ndt_status ndt_grid_dump(ndt_handle h, int64_t* idx, int* nr_points, double* mean, double* cov, double* icov,
+                         double* evals) {
+  if (!h || !h->grid) return fail(NDT_ERR_NO_INPUT, "no grid");
+  return grid_dump(h, h->grid.get(), idx, nr_points, mean, cov, icov, evals);
+}
+
+}  // extern "C"
+
+namespace ndtc {
+
+ndt_status grid_size(ndt_context* h, DeviceGrid* g, size_t* n_leaves, size_t* n_valid) {
+  if (!g->empty) {
+    ndt_status s = ensure_device(h);
+    if (!s) s = grid_counts(h, g);
+    if (s) return s;
+  }
+  if (n_leaves) *n_leaves = g->n_leaves;
+  if (n_valid) *n_valid = g->n_valid;
+  return NDT_OK;
+}
+
+void grid_info(const DeviceGrid* g, int* min_b, int* max_b, int* div_b) {
+  for (int k = 0; k < 3; k++) {
+    if (min_b) min_b[k] = g->geom.min_b[k];
+    if (max_b) max_b[k] = g->geom.max_b[k];
+    if (div_b) div_b[k] = g->geom.div_b[k];
+  }
 }
 
 // Re-runs the finalize pass in dump mode (the records and LUT it rewrites are
 // bit-identical, so sharing handles stay valid).
-ndt_status ndt_grid_dump(ndt_handle h, int64_t* idx, int* nr_points, double* mean, double* cov, double* icov,
-                         double* evals) {
-  if (!h || !h->grid) return fail(NDT_ERR_NO_INPUT, "no grid");
-  DeviceGrid* g = h->grid.get();
+ndt_status grid_dump(ndt_context* h, DeviceGrid* g, int64_t* idx, int* nr_points, double* mean, double* cov, double* icov,
+                     double* evals) {
   if (g->accumulated) return acc_grid_dump(h, idx, nr_points, mean, cov, icov, evals);
   if (!g->empty) {
     ndt_status sc = ensure_device(h);
@@ -2109,4 +2083,4 @@ ndt_status ndt_grid_dump(ndt_handle h, int64_t* idx, int* nr_points, double* mea
   return NDT_OK;
 }
 
-}  // extern "C"
+}  // namespace ndtc

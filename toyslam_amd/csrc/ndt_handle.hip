@@ -205,7 +205,7 @@ ndt_status ndt_set_resolution(ndt_handle h, float resolution) {
       acc_drop(h);
       return NDT_OK;
     }
-    if (h->source && h->target) return build_grid(h);
+    if (h->source && h->target) return build_grid(h, h->target, grid_spec_of(h, h->target_dense), h->grid);
   }
   return NDT_OK;
 }

@@ -392,7 +392,6 @@ struct ndt_context {
   FilterPending n1_filter;
   std::shared_ptr<DeviceCloud> n1_in, n1_out;
   int voxel_index = 0;              // ndt_set_voxel_index: 0 automatic, 1 dense table, 2 sparse (sorted build + hash look-up)
-  bool index_only = false;  // GICP's point index: cells and their point lists only, no per-voxel statistics
   int persistent = -1;  // -1 = default (NDT_PERSISTENT / on), 0 = launch per evaluation, 1 = server
   // Two command mailboxes, used by alternate server instances: a server told to finish (transform +
   // exit) is not waited for, and the next instance's first command must not overwrite the line the
@@ -553,18 +552,31 @@ ndt_status order_range(ndt_context* h, const float4* d_pts, size_t n, float pitc
                        const BBox* known_bbox = nullptr);
 ndt_status order_batch(ndt_context* h, DeviceCloud* c, const size_t* offsets, size_t n_scans);
 ndt_status order_cloud(ndt_context* h, DeviceCloud* c, const size_t* offsets, size_t n_scans);
-struct GridHead {
-  std::shared_ptr<DeviceGrid> g;  // geometry set
-  int n = 0;
-  size_t max_leaves = 0, max_cand = 0;
-  bool sparse = false, done = true;
+// What a voxel grid is built with, apart from the cloud: a handle's settings (grid_spec_of) or a caller's own (GICP's point
+// index: index_only -- cells and their point lists, no per-voxel statistics)
+struct GridSpec {
+  float resolution;
+  int min_pts;
+  double eig_ratio;
+  int voxel_index;  // ndt_set_voxel_index
+  bool dense;       // the cloud holds no NaN / inf
+  bool index_only;
 };
-ndt_status grid_head(ndt_context* h, GridHead& hd);
-ndt_status build_grid(ndt_context* h);
+inline GridSpec grid_spec_of(const ndt_context* h, int is_dense) {
+  return GridSpec{h->resolution, h->min_pts, h->eig_ratio, h->voxel_index, is_dense != 0, false};
+}
+// VoxelGridCovariance::filter(true) of `cloud` on the GPU, into `out`; h: the stream, the pool, the scratch.  `out` is
+// assigned when the build has queued its last launch, and with the empty grid of a cloud without a finite point or of the
+// reference's index overflow (NDT_ERR_GRID_OVERFLOW); any other failure leaves it alone.
+ndt_status build_grid(ndt_context* h, const std::shared_ptr<DeviceCloud>& cloud, const GridSpec& spec, std::shared_ptr<DeviceGrid>& out);
 // grids of many targets (ndt_align_pairs): every one the small form takes from ONE k1_small_multi launch, the others through
 // build_grid; out[i] = the grid of targets[i], bit for bit what build_grid makes of it.  *n_small: how many took the launch
 ndt_status build_grids(ndt_context* h, const std::vector<std::shared_ptr<DeviceCloud>>& targets, int is_dense,
                        std::vector<std::shared_ptr<DeviceGrid>>& out, size_t* n_small);
+// the inspection of a built grid g (ndt_grid_size / _info / _dump of the handle's, ndt_pairs_grid_* of a pairs call's)
+ndt_status grid_size(ndt_context* h, DeviceGrid* g, size_t* n_leaves, size_t* n_valid);
+void grid_info(const DeviceGrid* g, int* min_b, int* max_b, int* div_b);
+ndt_status grid_dump(ndt_context* h, DeviceGrid* g, int64_t* idx, int* nr_points, double* mean, double* cov, double* icov, double* evals);
 ndt_status maybe_compact_records(ndt_context* h, bool eager);
 ndt_status grid_counts(ndt_context* h, DeviceGrid* g);
 ndt_status ensure_cell2leaf(ndt_context* h, DeviceGrid* g);

@@ -70,6 +70,38 @@ inline void set_padded_lut(GridGeom& g) {
     if (m != 0.5f) g.pow2 = 0;
   }
 }
+// The lattice of pitch `leaf` over the box [mn, mx] (voxel_grid_covariance_omp_impl.hpp:75-103, in the reference's f32 and
+// integer operations): leaf, inv_leaf, min_b, max_b, div_b, mul and n_cells of geo -- the one place a box becomes cell
+// indices (target grids, the accumulating target, the voxel filter, the ordering of a source).  Index overflow is the
+// reference's own dx * dy * dz test (:75-84; geo then holds leaf and inv_leaf only), too many cells a lattice whose cell
+// count leaves int32 all the same.  The padded table (set_padded_lut) is the caller's.
+enum LatticeStatus { kLatticeOk, kLatticeIndexOverflow, kLatticeTooManyCells };
+inline LatticeStatus lattice_geometry(float leaf, const float min_p[3], const float max_p[3], GridGeom& geo) {
+  long long d[3];
+  for (int k = 0; k < 3; k++) {
+    geo.leaf[k] = leaf;
+    geo.inv_leaf[k] = 1.0f / leaf;  // [PCL] VoxelGrid::setLeafSize
+    d[k] = static_cast<long long>((max_p[k] - min_p[k]) * geo.inv_leaf[k]) + 1;
+  }
+  if (d[0] * d[1] * d[2] > static_cast<long long>(INT32_MAX)) return kLatticeIndexOverflow;
+  for (int k = 0; k < 3; k++) {
+    geo.min_b[k] = static_cast<int>(std::floor(min_p[k] * geo.inv_leaf[k]));
+    geo.max_b[k] = static_cast<int>(std::floor(max_p[k] * geo.inv_leaf[k]));
+    geo.div_b[k] = geo.max_b[k] - geo.min_b[k] + 1;
+  }
+  geo.mul[0] = 1;
+  geo.mul[1] = geo.div_b[0];
+  geo.mul[2] = geo.div_b[0] * geo.div_b[1];
+  geo.n_cells = static_cast<long long>(geo.div_b[0]) * geo.div_b[1] * geo.div_b[2];
+  return geo.n_cells <= 0 || geo.n_cells > static_cast<long long>(INT32_MAX) ? kLatticeTooManyCells : kLatticeOk;
+}
+// Dense or sparse voxel index for n_cells cells over n points?  Dense (a table over the whole bounding box, one dependent
+// load per probe) as long as the cell count stays within reach of the point count; sparse (sort-based build, hash look-up:
+// ndt_sparse.hip) when the box is mostly empty -- the regime the reference's std::map handles for free.  voxel_index:
+// ndt_set_voxel_index (0 automatic, 1 dense, 2 sparse).
+inline bool wants_sparse_index(int voxel_index, long long n_cells, long long n) {
+  return voxel_index == 2 || (voxel_index == 0 && (n_cells > (1ll << 25) || n_cells > 64ll * n + (1ll << 22)));
+}
 
 // LUT entry: record index (>= 0) of a valid voxel; kLutEmpty; or lut_rejected(r) (<= -2) for a voxel that
 // reached min_points_per_voxel but was rejected (nr_points = -1, _impl.hpp:337-341,360-364): the DIRECT

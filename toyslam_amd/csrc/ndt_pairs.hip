@@ -134,16 +134,12 @@ static void pairs_forget(ndt_handle h) {
   h->pairs_T.clear();
 }
 
-// runs fn with the pairs grid of cloud c standing in as the handle's grid (the inspection entries of a single grid)
-template <class F>
-static ndt_status with_pairs_grid(ndt_handle h, size_t c, const F& fn) {
+// the grid the last pairs call built for cloud c
+static ndt_status pairs_grid(ndt_handle h, size_t c, DeviceGrid*& g) {
   if (!h) return fail(NDT_ERR_INVALID, "null handle");
   if (c >= h->pairs_grids.size() || !h->pairs_grids[c]) return fail(NDT_ERR_NO_INPUT, "the last pairs call built no grid for this cloud");
-  std::shared_ptr<DeviceGrid> keep = h->grid;
-  h->grid = h->pairs_grids[c];
-  const ndt_status s = fn();
-  h->grid = keep;
-  return s;
+  g = h->pairs_grids[c].get();
+  return NDT_OK;
 }
 
 }  // namespace ndtc
@@ -207,14 +203,21 @@ ndt_status ndt_align_pairs_clouds(ndt_handle h, const ndt_cloud* cl, size_t n_cl
 }
 
 ndt_status ndt_pairs_grid_size(ndt_handle h, size_t cloud, size_t* n_leaves, size_t* n_valid) {
-  return with_pairs_grid(h, cloud, [&] { return ndt_grid_size(h, n_leaves, n_valid); });
+  DeviceGrid* g = nullptr;
+  const ndt_status s = pairs_grid(h, cloud, g);
+  return s ? s : grid_size(h, g, n_leaves, n_valid);
 }
 ndt_status ndt_pairs_grid_info(ndt_handle h, size_t cloud, int* min_b, int* max_b, int* div_b) {
-  return with_pairs_grid(h, cloud, [&] { return ndt_grid_info(h, min_b, max_b, div_b); });
+  DeviceGrid* g = nullptr;
+  const ndt_status s = pairs_grid(h, cloud, g);
+  if (!s) grid_info(g, min_b, max_b, div_b);
+  return s;
 }
 ndt_status ndt_pairs_grid_dump(ndt_handle h, size_t cloud, int64_t* idx, int* nr_points, double* mean, double* cov, double* icov,
                                double* evals) {
-  return with_pairs_grid(h, cloud, [&] { return ndt_grid_dump(h, idx, nr_points, mean, cov, icov, evals); });
+  DeviceGrid* g = nullptr;
+  const ndt_status s = pairs_grid(h, cloud, g);
+  return s ? s : grid_dump(h, g, idx, nr_points, mean, cov, icov, evals);
 }
 
 }  // extern "C"

@@ -908,6 +908,17 @@ def host_chain_pose(pose, transform):
     return _from_colmajor(out)
 
 
+def host_lattice(leaf, mn, mx, voxel_index=0, n_points=0):
+    """The voxel lattice of pitch leaf over the box [mn, mx] (ndt_host_lattice): status, min_b, max_b, div_b, n_cells, and
+    whether a target of n_points points over it gets the sparse voxel index in mode voxel_index."""
+    mn, mx = (np.ascontiguousarray(v, dtype=np.float32).reshape(3) for v in (mn, mx))
+    mb, xb, db = (np.zeros(3, dtype=np.int32) for _ in range(3))
+    cells, sparse = C.c_longlong(0), C.c_int(0)
+    st = _lib.lib().ndt_host_lattice(float(leaf), _f(mn), _f(mx), _i(mb), _i(xb), _i(db), C.byref(cells), int(voxel_index),
+                                     int(n_points), C.byref(sparse))
+    return dict(status=st, min_b=mb, max_b=xb, div_b=db, n_cells=cells.value, sparse=bool(sparse.value))
+
+
 def host_pose_to_matrix(p):
     p = np.ascontiguousarray(p, dtype=np.float64)
     T = np.zeros(16, dtype=np.float32)
