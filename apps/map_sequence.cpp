@@ -22,7 +22,7 @@
 // after the other, 2.7 ms overlapped, 3.7 ms overlapped on CU partitions -- the steps are short host-paced sequences of
 // pageable copies and small launches, and two threads driving them get in each other's way; hence not the default.
 //
-//   map_sequence [--scan-to-map] <pcd_directory> [voxel_leaf_size (0.5 | 0.3)] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]
+//   map_sequence [--scan-to-map [--window <metres>]] <pcd_directory> [voxel_leaf_size (0.5 | 0.3)] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]
 // ("host": the serial loop with every cloud passing through host buffers, as in rounds 1-3; the default keeps them in HBM)
 //
 // --scan-to-map (anywhere on the line; the node's loop with clouds resident in HBM): every scan after the first is registered
@@ -30,6 +30,10 @@
 // (ndt_target_accumulate_cloud) -- instead of against its predecessor alone.  The registration starts from the previous scan's
 // pose (the rosbag node's guess rule) and its result IS the scan's pose in the map: nothing is chained, so the trajectory
 // does not add up the errors of the pairs.  The printed lines keep their form.
+// --window <metres> (with --scan-to-map): after a scan has been accumulated at its pose the target is cropped to the
+// axis-aligned cube of that half-side around the pose's translation (ndt_target_accumulate_crop): the map the registrations see
+// stays bounded on a trajectory of any length.  The largest voxel count the target reached is printed at the end.
+#include <algorithm>
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -110,11 +114,27 @@ class Channel {
 struct Node {
   bool rosbag = false;
   bool scan_to_map = false;  // --scan-to-map: registrations against the accumulated target; a result is a pose in the map
+  float window = 0;          // --window: half-side of the cube the accumulated target is cropped to after every scan (0: never)
+  size_t max_voxels = 0;     // the largest voxel count the windowed target reached
   std::vector<std::vector<float>> trajectory;                     // trajectory_
   std::vector<float> pose = std::vector<float>(kIdentity, kIdentity + 16);
   std::vector<float> pres_transform = std::vector<float>(kIdentity, kIdentity + 16);  // rosbag node :33,95
   size_t loaded = 0, registered = 0, not_converged = 0;
   double t_filter = 0, t_align = 0, t_map = 0, t_wait = 0;  // t_wait: for the next file (the reader runs ahead in the background)
+
+  // --scan-to-map: the scan into the accumulated target at its pose in the map (column-major), then the window around it
+  int accumulate(ndt_handle h, ndt_cloud scan, const float* map_pose) {
+    CHECK(ndt_target_accumulate_cloud(h, scan, 1, map_pose));
+    if (window > 0) {
+      const float lo[3] = {map_pose[12] - window, map_pose[13] - window, map_pose[14] - window};
+      const float hi[3] = {map_pose[12] + window, map_pose[13] + window, map_pose[14] + window};
+      CHECK(ndt_target_accumulate_crop(h, lo, hi));
+      size_t voxels = 0;
+      CHECK(ndt_target_accumulated(h, nullptr, &voxels, nullptr));
+      max_voxels = std::max(max_voxels, voxels);
+    }
+    return 0;
+  }
 
   // after align: -> whether the scan goes into the global map, and with which pose
   bool after_align(ndt_handle h, float* T, int converged, int iterations, std::vector<float>& map_pose, std::string& err) {
@@ -234,7 +254,7 @@ static int run_resident(Node& node, ndt_pcd_sequence_handle seq, float voxel_lea
         t0 = clock_type::now();
         int ov = 0;
         CHECK(ndt_map_update_cloud(h, current, 1, kIdentity, 0.5f, &ov));
-        if (node.scan_to_map) CHECK(ndt_target_accumulate_cloud(h, current, 1, kIdentity));
+        if (node.scan_to_map && node.accumulate(h, current, kIdentity)) return 1;
         node.t_map += since(t0);
         return 0;
       }
@@ -259,7 +279,7 @@ static int run_resident(Node& node, ndt_pcd_sequence_handle seq, float voxel_lea
         t0 = clock_type::now();
         int ov = 0;
         CHECK(ndt_map_update_cloud(h, current, 1, map_pose.data(), 0.5f, &ov));  // :204 / map_voxel :88: leaf fixed at 0.5
-        if (node.scan_to_map) CHECK(ndt_target_accumulate_cloud(h, current, 1, map_pose.data()));
+        if (node.scan_to_map && node.accumulate(h, current, map_pose.data())) return 1;
         node.t_map += since(t0);
       }
       return 0;
@@ -524,17 +544,28 @@ static int run_pipelined(Node& node, ndt_pcd_sequence_handle seq, float voxel_le
 }
 
 int main(int argc, char** argv) {
-  bool scan_to_map = false;
-  {  // the switch is taken out of the line before the positional arguments are read
+  bool scan_to_map = false, bad_window = false;
+  float window = 0;
+  {  // the switches are taken out of the line before the positional arguments are read
     int kept = 1;
     for (int i = 1; i < argc; i++) {
-      if (std::strcmp(argv[i], "--scan-to-map") == 0) scan_to_map = true;
-      else argv[kept++] = argv[i];
+      if (std::strcmp(argv[i], "--scan-to-map") == 0) {
+        scan_to_map = true;
+      } else if (std::strcmp(argv[i], "--window") == 0) {
+        window = i + 1 < argc ? static_cast<float>(std::atof(argv[++i])) : 0.f;
+        bad_window = !(window > 0);
+      } else {
+        argv[kept++] = argv[i];
+      }
     }
     argc = kept;
   }
+  if (bad_window || (window > 0 && !scan_to_map)) {
+    std::fprintf(stderr, "--window <metres> takes a positive half-side and goes with --scan-to-map\n");
+    return 2;
+  }
   if (argc < 2) {
-    std::printf("usage: map_sequence [--scan-to-map] <pcd_directory> [voxel_leaf_size] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]\n");
+    std::printf("usage: map_sequence [--scan-to-map [--window <metres>]] <pcd_directory> [voxel_leaf_size] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]\n");
     return 0;
   }
   Node node;
@@ -542,6 +573,7 @@ int main(int argc, char** argv) {
   const bool serial = !(argc > 5 && std::strcmp(argv[5], "pipeline") == 0);
   const bool host_clouds = argc > 6 && std::strcmp(argv[6], "host") == 0;  // serial only: every cloud through host buffers
   node.scan_to_map = scan_to_map;
+  node.window = window;
   if (scan_to_map && (node.rosbag || !serial || host_clouds)) {
     // (the rosbag loop prints getFitnessScore, which needs the target's points: an accumulated target keeps none)
     std::fprintf(stderr, "--scan-to-map runs the node's serial loop with resident clouds: not with rosbag, pipeline or host\n");
@@ -584,6 +616,7 @@ int main(int argc, char** argv) {
     std::snprintf(title, sizeof(title), "trajectory[%zu]:", i);
     print_matrix(title, node.trajectory[i].data());
   }
+  if (node.window > 0) std::printf("window %g m: the accumulated target reached %zu voxels at most\n", node.window, node.max_voxels);
   std::printf("start-up (device, code object, page-locked slots; ndt_warm_up): %.1f ms, not in the times below\n", warm_ms);
   std::printf("time: total %.2f ms  (prefilter %.2f, %s %.2f, map update %.2f, waiting for the next file %.2f; %s)\n", since(t_begin), node.t_filter,
               serial ? "set inputs + align" : "take inputs over + align", node.t_align, node.t_map, node.t_wait,

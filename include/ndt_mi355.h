@@ -338,6 +338,41 @@ ndt_status ndt_target_accumulate_clouds(ndt_handle h, const ndt_cloud* clouds, s
 ndt_status ndt_target_accumulate_reset(ndt_handle h);
 ndt_status ndt_target_accumulated(ndt_handle h, size_t* n_points, size_t* n_voxels, size_t* n_updates);
 ndt_status ndt_diag_target_accumulate(ndt_handle h, size_t* touched_voxels, size_t* new_voxels, int* relinked, int* table_grown, size_t* launches);
+/* Crop the accumulated target to an axis-aligned box: a scan-to-map loop keeps a bounded map (a window around the vehicle)
+ * instead of a target that only grows.  A voxel's sums depend only on the points of its own cell and on their order, so
+ * dropping whole voxels leaves every kept voxel bit for bit what it would be had the dropped points never been accumulated.
+ * - Cell range.  Per axis lo = floor(min * inv_leaf) and hi = floor(max * inv_leaf) with inv_leaf = 1.0f / resolution of the
+ *   running target: the f32 product rounded before the floor, the arithmetic that bins a point.  Both are saturated to
+ *   [-2^20, 2^20), so -INFINITY / +INFINITY leave a side open.
+ * - Keep rule.  A voxel is kept exactly when its absolute cell lies in [lo, hi] on all three axes -- the cells a point inside
+ *   the box could fall into.  Every other voxel is removed whatever its state (under min_points_per_voxel, valid, rejected).
+ * - Equivalence.  After a crop, and after any later accumulate calls and further crops, the handle behaves like a handle with
+ *   the same parameters whose target was set from the concatenation, in the original order, of every posed point accumulated
+ *   so far whose cell lies inside every crop range applied AFTER that point was accumulated: the same dump (indices, counts,
+ *   means, covariances, inverse covariances, eigenvalues, min_b / max_b / div_b) and the same bits from every evaluation and
+ *   registration call listed above, for all four search methods.
+ * - Box.  After a crop the box is the tight cell box of the kept voxels (what the concatenation's box gives: floor is
+ *   monotone); a later update unions its own box with it as before.  The points' float extent is unknown after a crop, so
+ *   the target then carries its box as the centres of the corner cells, (cell + 0.5f) * leaf, which floor back to those
+ *   cells for |cell| < 2^20.  The reference's dx*dy*dz overflow refusal (NDT_ERR_GRID_OVERFLOW) is from then on decided from
+ *   these cell extents, not from the points' extent: it can differ from the concatenation's only at the INT32_MAX edge.
+ * - Bookkeeping.  ndt_target_accumulated's n_points becomes the sum of the kept voxels' counts (non-finite rows accumulated
+ *   earlier lie in no voxel and are forgotten), n_voxels the kept voxels; n_updates is unchanged.  The dense-or-sparse rule
+ *   of ndt_set_voxel_index is applied again with the new cell and point counts: a target that went sparse because its box
+ *   grew comes back to the dense table.  Slot arrays and key table shrink to the smallest capacities (power-of-two multiples
+ *   of the initial ones) that hold the kept voxels.
+ * - Nothing removed: NDT_OK; nothing of the target is written, no table rewritten (removed_voxels == 0, relinked == 0).
+ * - Everything removed: NDT_OK; the target is empty as after accumulating only non-finite points -- no box, 0 voxels, the
+ *   captured parameters kept; the next accumulate starts its box afresh.
+ * - A removed cell that receives points again starts from empty sums.
+ * - Refused before anything changes and without a device -- NDT_ERR_INVALID: a NULL handle, NULL bounds, a NaN bound,
+ *   min > max on an axis; NDT_ERR_NO_INPUT: no live accumulated target.
+ * - One crop is mark + scan over the SLOTS, one read-back, and (if anything goes) compaction, key-table and look-up-table
+ *   rebuild: five launches whatever was accumulated, none over points.  ndt_warm_up leaves a cropped target as it was.
+ * ndt_diag_target_crop, of the last crop: voxels kept and removed, points kept, whether the tables were rebuilt, launches
+ * (the scan counts one). */
+ndt_status ndt_target_accumulate_crop(ndt_handle h, const float min_xyz[3], const float max_xyz[3]);
+ndt_status ndt_diag_target_crop(ndt_handle h, size_t* kept_voxels, size_t* removed_voxels, size_t* kept_points, int* relinked, size_t* launches);
 /* the key of the accumulated target's voxel table: the absolute cell (i, j, k), 21 bits per axis, k in the high bits so
  * that keys ascend with the linear voxel index.  Host only.  NDT_ERR_INVALID outside [-2^20, 2^20). */
 ndt_status ndt_host_acc_pack_cell(int i, int j, int k, uint64_t* key);

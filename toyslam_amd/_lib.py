@@ -105,6 +105,8 @@ SIGNATURES = {
     "ndt_target_accumulate_reset": (C.c_int, [vp]),
     "ndt_target_accumulated": (C.c_int, [vp, szp, szp, szp]),
     "ndt_diag_target_accumulate": (C.c_int, [vp, szp, szp, ip, ip, szp]),
+    "ndt_target_accumulate_crop": (C.c_int, [vp, fp, fp]),
+    "ndt_diag_target_crop": (C.c_int, [vp, szp, szp, szp, ip, szp]),
     "ndt_host_acc_pack_cell": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
     "ndt_host_acc_unpack_cell": (None, [C.c_uint64, ip, ip, ip]),
     "ndt_host_chain_pose": (None, [fp, fp, fp]),

@@ -23,6 +23,13 @@
 //                       new, continue its sums over the run in ascending point index
 //   k_acc_finish        a thread per touched voxel: finish_voxel -> record, centroid, table entry
 // The evaluation kernels see an ordinary GridView: the padded dense table or the hash keyed by the reference's linear index.
+//
+// One crop to a box of cells (ndt_target_accumulate_crop) -- over the slots, never over points:
+//   k_acc_crop_mark     a thread per slot: keep flag from its cell; kept slots, their points and their cell box
+//   scan                new slot numbers (kept slots keep their order)
+//   ---- one read-back: kept slots, kept points, cell box; nothing removed -> return; the host derives geometry, form, capacities ----
+//   k_acc_crop_compact  kept slots into FRESH arrays (cell, sums, state, record, side sector: none depends on box or slot)
+//   k_acc_rehash / k_acc_relink   the cleared key table and the cleared look-up table from the kept slots
 #include <hipcub/hipcub.hpp>
 
 #include "ndt_internal.hpp"
@@ -297,6 +304,77 @@ __global__ __launch_bounds__(kBlock) void k_acc_finish(const int* __restrict__ l
   else v.state[slot] = c.w < min_pts ? 0 : valid ? 1 : 2;
 }
 
+// ---- crop to a box of cells (ndt_target_accumulate_crop): over the slots, never over points
+struct AccCropBox {
+  int lo[3], hi[3];  // kept: lo <= cell <= hi on every axis
+};
+// info words of a crop: [0..2] lowest kept cell, [3..5] highest kept cell, [6] kept slots, [8..9] kept points (64 bit)
+constexpr int kAccCropInfoWords = 10;
+
+// a thread per slot: its keep flag; kept slots, their points and their cell box reduced in the wave, then one atomic per
+// wave and word (cells are exact floats: |cell| <= 2^20)
+__global__ __launch_bounds__(kBlock) void k_acc_crop_mark(const int4* __restrict__ cell, int n_slots, AccCropBox box, unsigned* __restrict__ keep,
+                                                          int* __restrict__ info) {
+  const int s = blockIdx.x * kBlock + threadIdx.x;
+  bool kept = false;
+  float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+  double pts = 0.0;
+  if (s < n_slots) {
+    const int4 c = cell[s];
+    kept = c.x >= box.lo[0] && c.x <= box.hi[0] && c.y >= box.lo[1] && c.y <= box.hi[1] && c.z >= box.lo[2] && c.z <= box.hi[2];
+    keep[s] = kept ? 1u : 0u;
+    if (kept) {
+      mn[0] = mx[0] = static_cast<float>(c.x);
+      mn[1] = mx[1] = static_cast<float>(c.y);
+      mn[2] = mx[2] = static_cast<float>(c.z);
+      pts = static_cast<double>(c.w);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    mn[k] = wave_min(mn[k]);
+    mx[k] = wave_max(mx[k]);
+  }
+  pts = wave_sum(pts);  // (at most 64 x INT_MAX: exact)
+  const unsigned long long mask = __ballot(kept);
+  if ((threadIdx.x & (kWave - 1)) == 0 && mask != 0) {
+    for (int k = 0; k < 3; k++) {
+      atomicMin(info + k, static_cast<int>(mn[k]));
+      atomicMax(info + 3 + k, static_cast<int>(mx[k]));
+    }
+    atomicAdd(info + 6, __popcll(mask));
+    atomicAdd(reinterpret_cast<unsigned long long*>(info + 8), static_cast<unsigned long long>(pts));
+  }
+}
+
+// every kept slot to its new number (the exclusive scan of the keep flags: kept slots keep their order) in fresh arrays.
+// A record and its side sector hold the voxel's mean, inverse covariance, count and centroid -- nothing of the box or of
+// the slot number -- so they are copied, not finished again
+__global__ __launch_bounds__(kBlock) void k_acc_crop_compact(AccView from, int n_slots, const unsigned* __restrict__ keep,
+                                                             const unsigned* __restrict__ number, int n_kept, int4* __restrict__ cell,
+                                                             AccSums* __restrict__ sums, int* __restrict__ state, VoxelRec* __restrict__ recs,
+                                                             VoxelSide* __restrict__ cents) {
+  const int s = blockIdx.x * kBlock + threadIdx.x;
+  if (s >= n_slots || !keep[s]) return;
+  const int t = static_cast<int>(number[s]);
+  if (t >= n_kept) return;  // (cannot happen: the scan numbers the kept slots 0 .. n_kept - 1)
+  cell[t] = from.cell[s];
+  sums[t] = from.sums[s];
+  const int st = from.state[s];
+  state[t] = st;
+  if (st != 0) {  // a voxel under min_pts has no record yet
+    const float4* rs = reinterpret_cast<const float4*>(from.recs + s);
+    const float4* cs = reinterpret_cast<const float4*>(from.cents + s);
+    float4* rd = reinterpret_cast<float4*>(recs + t);
+    float4* cd = reinterpret_cast<float4*>(cents + t);
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      rd[q] = rs[q];
+      cd[q] = cs[q];
+    }
+  }
+}
+
 inline int acc_grid_for(size_t n, int cap) {
   const size_t b = (n + kBlock - 1) / kBlock;
   return static_cast<int>(std::max<size_t>(1, std::min<size_t>(b, static_cast<size_t>(cap))));
@@ -316,6 +394,7 @@ struct AccTarget {
   double eig_ratio = 0.01;
   size_t n_points = 0, n_updates = 0;
   int n_slots = 0, slot_cap = 0, bits = 0;
+  int first_bits = 0, first_cap = 0;  // the capacities a target starts with: what a crop shrinks back towards
   DevBuf<unsigned long long> keys;
   DevBuf<int> vals;
   DevBuf<int4> cell;
@@ -421,7 +500,8 @@ ndt_status acc_update(ndt_context* h, const std::vector<AccScan>& scans, size_t 
     a->resolution = h->resolution;
     a->min_pts = h->min_pts;
     a->eig_ratio = h->eig_ratio;
-    a->bits = env_int("NDT_ACC_HASH_BITS", 16, 2, 30);
+    a->bits = a->first_bits = env_int("NDT_ACC_HASH_BITS", 16, 2, 30);
+    a->first_cap = env_int("NDT_ACC_SLOTS", 1 << 15, 1, 1 << 30);
     a->slot_cap = 0;
     a->grid = std::make_shared<DeviceGrid>();
     a->grid->accumulated = true;
@@ -558,9 +638,8 @@ ndt_status acc_update(ndt_context* h, const std::vector<AccScan>& scans, size_t 
   if (!have_box) return NDT_OK;  // no finite point so far: the empty grid
   const int n_slots_before = a->n_slots;
   if (a->slot_cap == 0 && !a->cell.p) {
-    const int first_cap = env_int("NDT_ACC_SLOTS", 1 << 15, 1, 1 << 30);
     bool ignore = false;
-    ndt_status s0 = acc_grow(h, a, first_cap, &ignore);
+    ndt_status s0 = acc_grow(h, a, a->first_cap, &ignore);
     if (s0) return s0;
   }
   bool grown = false;
@@ -633,6 +712,171 @@ ndt_status acc_buffer(ndt_handle h, const void* pts, size_t n, size_t stride, bo
   if (s) return s;
   one[0].pose = pose;
   return acc_update(h, one, n);
+}
+
+// floor(bound * inv_leaf) as k_acc_keys bins a point (the f32 product rounded before the floor), saturated to the lattice
+int acc_crop_cell(float bound, float inv_leaf) {
+  const float p = bound * inv_leaf, lim = static_cast<float>(ndt::kAccCellBias);
+  if (!(p >= -lim)) return -ndt::kAccCellBias;
+  if (p >= lim) return ndt::kAccCellBias - 1;
+  return static_cast<int>(std::floor(p));
+}
+
+// the target as after accumulating only non-finite points: no box, no voxel, no arrays; the captured parameters stay
+void acc_make_empty(AccTarget* a) {
+  DeviceGrid* g = a->grid.get();
+  a->keys.release();  // (to the stream's pool: reused only behind what is queued)
+  a->vals.release();
+  a->cell.release();
+  a->sums.release();
+  a->state.release();
+  g->recs.release();
+  g->centroids.release();
+  g->lut.release();
+  a->n_slots = a->slot_cap = 0;
+  a->bits = a->first_bits;
+  a->have_box = false;
+  a->sparse = false;
+  for (int k = 0; k < 3; k++) a->mn[k] = a->mx[k] = 0;
+  g->geom = ndt::GridGeom{};
+  for (int k = 0; k < 3; k++) {
+    g->geom.leaf[k] = a->resolution;
+    g->geom.inv_leaf[k] = 1.0f / a->resolution;
+  }
+  g->empty = true;
+  g->n_leaves = g->n_cand = g->n_valid = 0;
+  g->counts_known = true;
+}
+
+// ndt_target_accumulate_crop once the bounds are cells: mark + scan, ONE read-back, then (if anything goes) the kept slots
+// compacted into fresh arrays in their order, the key table and the look-up table rebuilt from them
+ndt_status acc_crop(ndt_context* h, AccTarget* a, const ndt::AccCropBox& box) {
+  hipStream_t st = h->stream;
+  DeviceGrid* g = a->grid.get();
+  h->crop_kept = static_cast<size_t>(a->n_slots);
+  h->crop_points = a->n_points;
+  h->crop_removed = h->crop_launches = 0;
+  h->crop_relinked = 0;
+  if (a->n_slots == 0) {  // no voxel: only the non-finite rows are forgotten
+    h->crop_points = a->n_points = 0;
+    h->target->n = 0;
+    return NDT_OK;
+  }
+  const int n_slots = a->n_slots;
+  const size_t S = static_cast<size_t>(n_slots);
+  DevBuf<unsigned> w;  // keep flags, new numbers
+  DevBuf<int> info;
+  DevBuf<unsigned char> temp;
+  HIP_TRY(w.reserve(2 * S));
+  HIP_TRY(info.reserve(ndt::kAccCropInfoWords));
+  unsigned *keep = w.p, *number = w.p + S;
+  size_t tb = 0;
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, keep, number, n_slots, st));
+  tb += 256;
+  HIP_TRY(temp.reserve(tb));
+  const int imax = std::numeric_limits<int>::max(), imin = std::numeric_limits<int>::min();
+  const int info0[ndt::kAccCropInfoWords] = {imax, imax, imax, imin, imin, imin, 0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(info.p, info0, sizeof(info0), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(ndt::k_acc_crop_mark, dim3(ndt::acc_grid_for(S, 1 << 30)), dim3(ndt::kBlock), 0, st, a->cell.p, n_slots, box, keep, info.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(temp.p, tb, keep, number, n_slots, st));
+  h->crop_launches += 2;
+  // ---- the one read-back
+  int hinfo[ndt::kAccCropInfoWords];
+  HIP_TRY(hipMemcpyAsync(hinfo, info.p, sizeof(hinfo), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const int kept = hinfo[6];
+  unsigned long long kept_points = 0;
+  std::memcpy(&kept_points, hinfo + 8, sizeof(kept_points));
+  if (kept < 0 || kept > n_slots) return fail(NDT_ERR_HIP, "crop: the kept count is out of range");
+  if (kept == n_slots) {  // nothing removed: nothing written, no table rewritten (only the non-finite rows are forgotten)
+    h->crop_points = a->n_points = static_cast<size_t>(kept_points);
+    h->target->n = a->n_points;
+    return NDT_OK;
+  }
+  h->crop_kept = static_cast<size_t>(kept);
+  h->crop_removed = S - static_cast<size_t>(kept);
+  h->crop_points = static_cast<size_t>(kept_points);
+  if (kept == 0) {
+    acc_make_empty(a);
+    a->n_points = 0;
+    h->target->n = 0;
+    return NDT_OK;
+  }
+  // ---- the box of the kept cells, carried as the centres of its corner cells: (cell + 0.5f) * leaf floors back to the cell
+  // for |cell| < 2^20 (the two roundings stay under 0.2 of a cell), so a later update unions its points' box with it as ever
+  float mn[3], mx[3];
+  for (int k = 0; k < 3; k++) {
+    mn[k] = (static_cast<float>(hinfo[k]) + 0.5f) * a->resolution;
+    mx[k] = (static_cast<float>(hinfo[3 + k]) + 0.5f) * a->resolution;
+  }
+  ndt::GridGeom geo = g->geom;
+  const ndt_status gs = acc_geometry(a->resolution, mn, mx, geo);
+  if (gs) return gs;
+  for (int k = 0; k < 3; k++)
+    if (geo.min_b[k] != hinfo[k] || geo.max_b[k] != hinfo[3 + k]) return fail(NDT_ERR_HIP, "crop: the kept cells' box does not round-trip");
+  const long long np = static_cast<long long>(std::min<unsigned long long>(kept_points, static_cast<unsigned long long>(std::numeric_limits<int>::max())));
+  const bool sparse = ndt::wants_sparse_index(h->voxel_index, geo.n_cells, np);
+  // ---- capacities: the smallest the kept slots fit (power-of-two multiples of what the target started with)
+  int cap = std::max(a->first_cap, 1);
+  while (cap < kept) cap *= 2;
+  int bits = std::max(a->first_bits, 2);
+  while (2 * static_cast<size_t>(kept) > (static_cast<size_t>(1) << bits)) bits++;
+  int hash_bits = 0;
+  if (sparse) {
+    hash_bits = 10;
+    while ((static_cast<size_t>(1) << hash_bits) < 2 * static_cast<size_t>(cap)) hash_bits++;
+  }
+  geo.hash_bits = hash_bits;
+  const size_t key_cap = static_cast<size_t>(1) << bits;
+  const size_t words = sparse ? (static_cast<size_t>(2) << hash_bits) : static_cast<size_t>(geo.lut_cells);
+  DevBuf<int4> cell;
+  DevBuf<ndt::AccSums> sums;
+  DevBuf<int> state, vals, lut;
+  DevBuf<ndt::VoxelRec> recs;
+  DevBuf<ndt::VoxelSide> cents;
+  DevBuf<unsigned long long> keys;
+  HIP_TRY(cell.reserve(cap));
+  HIP_TRY(sums.reserve(cap));
+  HIP_TRY(state.reserve(cap));
+  HIP_TRY(recs.reserve(cap));
+  HIP_TRY(cents.reserve(cap));
+  HIP_TRY(keys.reserve(key_cap));
+  HIP_TRY(vals.reserve(key_cap));
+  HIP_TRY(lut.reserve(words));
+  // ---- from here on the target changes
+  HIP_TRY(hipMemsetAsync(keys.p, 0xFF, key_cap * sizeof(unsigned long long), st));
+  HIP_TRY(hipMemsetAsync(lut.p, 0xFF, words * sizeof(int), st));  // kLutEmpty / free hash slots
+  hipLaunchKernelGGL(ndt::k_acc_crop_compact, dim3(ndt::acc_grid_for(S, 1 << 30)), dim3(ndt::kBlock), 0, st, a->view(), n_slots, keep, number, kept, cell.p,
+                     sums.p, state.p, recs.p, cents.p);
+  a->cell.swap(cell);  // (the old arrays go back to the pool at scope exit: reused only behind the compaction, stream order)
+  a->sums.swap(sums);
+  a->state.swap(state);
+  g->recs.swap(recs);
+  g->centroids.swap(cents);
+  a->keys.swap(keys);
+  a->vals.swap(vals);
+  g->lut.swap(lut);
+  a->slot_cap = cap;
+  a->bits = bits;
+  a->n_slots = kept;
+  hipLaunchKernelGGL(ndt::k_acc_rehash, dim3(ndt::acc_grid_for(kept, 1 << 30)), dim3(ndt::kBlock), 0, st, a->view(), kept);
+  hipLaunchKernelGGL(ndt::k_acc_relink, dim3(ndt::acc_grid_for(kept, 1 << 30)), dim3(ndt::kBlock), 0, st, a->view(), kept, geo, g->lut.p);
+  h->crop_launches += 3;
+  h->crop_relinked = 1;
+  g->geom = geo;
+  a->sparse = sparse;
+  for (int k = 0; k < 3; k++) {
+    a->mn[k] = mn[k];
+    a->mx[k] = mx[k];
+  }
+  a->n_points = static_cast<size_t>(kept_points);
+  h->target->n = a->n_points;
+  g->empty = false;
+  g->n_leaves = static_cast<size_t>(kept);
+  g->counts_known = false;
+  HIP_TRY(hipGetLastError());
+  return NDT_OK;
 }
 
 }  // namespace
@@ -789,6 +1033,35 @@ ndt_status ndt_diag_target_accumulate(ndt_handle h, size_t* touched_voxels, size
   if (relinked) *relinked = h->acc_relinked;
   if (table_grown) *table_grown = h->acc_grown;
   if (launches) *launches = h->acc_launches;
+  return NDT_OK;
+}
+
+ndt_status ndt_target_accumulate_crop(ndt_handle h, const float* min_xyz, const float* max_xyz) {
+  if (!h) return fail(NDT_ERR_INVALID, "null handle");
+  if (!min_xyz || !max_xyz) return fail(NDT_ERR_INVALID, "null bounds");
+  for (int k = 0; k < 3; k++) {
+    if (std::isnan(min_xyz[k]) || std::isnan(max_xyz[k])) return fail(NDT_ERR_INVALID, "a bound of the crop box is NaN");
+    if (min_xyz[k] > max_xyz[k]) return fail(NDT_ERR_INVALID, "the crop box has min > max on an axis");
+  }
+  AccTarget* a = acc_live(h);
+  if (!a) return fail(NDT_ERR_NO_INPUT, "no accumulated target to crop");
+  ndt::AccCropBox box;
+  const float inv_leaf = 1.0f / a->resolution;
+  for (int k = 0; k < 3; k++) {
+    box.lo[k] = acc_crop_cell(min_xyz[k], inv_leaf);
+    box.hi[k] = acc_crop_cell(max_xyz[k], inv_leaf);
+  }
+  ndt_status s = ensure_device(h);
+  if (s) return s;
+  return acc_crop(h, a, box);
+}
+ndt_status ndt_diag_target_crop(ndt_handle h, size_t* kept_voxels, size_t* removed_voxels, size_t* kept_points, int* relinked, size_t* launches) {
+  if (!h) return fail(NDT_ERR_INVALID, "null handle");
+  if (kept_voxels) *kept_voxels = h->crop_kept;
+  if (removed_voxels) *removed_voxels = h->crop_removed;
+  if (kept_points) *kept_points = h->crop_points;
+  if (relinked) *relinked = h->crop_relinked;
+  if (launches) *launches = h->crop_launches;
   return NDT_OK;
 }
 

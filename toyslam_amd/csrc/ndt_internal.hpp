@@ -464,6 +464,9 @@ struct ndt_context {
   std::shared_ptr<ndtc::AccTarget> acc;
   size_t acc_touched = 0, acc_new = 0, acc_launches = 0;
   int acc_relinked = 0, acc_grown = 0;
+  // ... and the last ndt_target_accumulate_crop (ndt_diag_target_crop)
+  size_t crop_kept = 0, crop_removed = 0, crop_points = 0, crop_launches = 0;
+  int crop_relinked = 0;
 
   ~ndt_context() {
     for (ndt_context* w : batch_workers) delete w;

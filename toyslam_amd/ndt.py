@@ -492,6 +492,21 @@ class NormalDistributionsTransform:
         check(self._L.ndt_diag_target_accumulate(self._h, C.byref(t), C.byref(n), C.byref(r), C.byref(g), C.byref(l)))
         return dict(touched_voxels=t.value, new_voxels=n.value, relinked=bool(r.value), table_grown=bool(g.value), launches=l.value)
 
+    def targetAccumulateCrop(self, min_xyz, max_xyz):
+        """Crop the accumulated target to the box [min_xyz, max_xyz] (ndt_target_accumulate_crop): a voxel stays exactly when
+        its cell lies in crop_cell_range(resolution, min_xyz, max_xyz); afterwards the handle behaves as if the points of
+        the other cells had never been accumulated.  -inf / +inf leave a side open.  Returns targetAccumulated()."""
+        mn, mx = (np.ascontiguousarray(v, dtype=np.float32).reshape(3) for v in (min_xyz, max_xyz))
+        check(self._L.ndt_target_accumulate_crop(self._h, _f(mn), _f(mx)))
+        return self.targetAccumulated()
+
+    def targetCropDiag(self):
+        """What the last targetAccumulateCrop did (ndt_diag_target_crop)."""
+        k, r, p, l = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        w = C.c_int(0)
+        check(self._L.ndt_diag_target_crop(self._h, C.byref(k), C.byref(r), C.byref(p), C.byref(w), C.byref(l)))
+        return dict(kept_voxels=k.value, removed_voxels=r.value, kept_points=p.value, relinked=bool(w.value), launches=l.value)
+
     # ---- batch (map-build) ---------------------------------------------------------
     def alignBatch(self, clouds=None, guesses=None, device_ptr=None, offsets=None, stride_bytes=16):
         """Register many sources against the one target in lock-step.
@@ -965,6 +980,28 @@ def host_acc_unpack_cell(key):
     i, j, k = C.c_int(0), C.c_int(0), C.c_int(0)
     _lib.lib().ndt_host_acc_unpack_cell(C.c_uint64(int(key)), C.byref(i), C.byref(j), C.byref(k))
     return i.value, j.value, k.value
+
+
+ACC_CELL_LIMIT = 1 << 20  # the accumulating target's lattice: cells of [-2^20, 2^20) on every axis
+
+
+def crop_cell_range(resolution, min_xyz, max_xyz):
+    """The cells ndt_target_accumulate_crop keeps, restated in numpy f32: per axis lo = floor(min * inv_leaf) and
+    hi = floor(max * inv_leaf) with inv_leaf = 1.0f / resolution -- the f32 product rounded before the floor, as a point is
+    binned -- saturated to [-2^20, 2^20).  -> (lo, hi), int64 arrays of the bounds' shape."""
+    inv = np.float32(1.0) / np.float32(resolution)
+    out = []
+    with np.errstate(over="ignore", invalid="ignore"):
+        for b in (min_xyz, max_xyz):
+            p = np.asarray(b, dtype=np.float32) * inv
+            out.append(np.clip(np.floor(p), -ACC_CELL_LIMIT, ACC_CELL_LIMIT - 1).astype(np.int64))
+    return out[0], out[1]
+
+
+def crop_cell_centre(resolution, cell):
+    """(cell + 0.5f) * leaf in f32: the float a cropped target carries for a corner cell of its box; it floors back to the
+    cell on the lattice of pitch `resolution` for every cell of [-2^20, 2^20)."""
+    return (np.asarray(cell).astype(np.float32) + np.float32(0.5)) * np.float32(resolution)
 
 
 def host_thread_budget():
