@@ -22,7 +22,7 @@
 // after the other, 2.7 ms overlapped, 3.7 ms overlapped on CU partitions -- the steps are short host-paced sequences of
 // pageable copies and small launches, and two threads driving them get in each other's way; hence not the default.
 //
-//   map_sequence [--scan-to-map [--window <metres>]] <pcd_directory> [voxel_leaf_size (0.5 | 0.3)] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]
+//   map_sequence [--scan-to-map [--window <metres>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> [voxel_leaf_size (0.5 | 0.3)] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]
 // ("host": the serial loop with every cloud passing through host buffers, as in rounds 1-3; the default keeps them in HBM)
 //
 // --scan-to-map (anywhere on the line; the node's loop with clouds resident in HBM): every scan after the first is registered
@@ -33,6 +33,11 @@
 // --window <metres> (with --scan-to-map): after a scan has been accumulated at its pose the target is cropped to the
 // axis-aligned cube of that half-side around the pose's translation (ndt_target_accumulate_crop): the map the registrations see
 // stays bounded on a trajectory of any length.  The largest voxel count the target reached is printed at the end.
+// --save-target <file> (with --scan-to-map): after the run the whole accumulated target is saved (ndt_target_accumulate_save).
+// --load-target <file> (with --scan-to-map): the file is imported before the first scan (ndt_target_accumulate_load), and the
+// first scan is then registered against it from the identity guess -- like every later scan from the previous pose --
+// instead of being placed at the identity.  --localize (with --load-target): scans are registered against the loaded map but
+// neither accumulated into it nor is it cropped.
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
@@ -116,6 +121,8 @@ struct Node {
   bool scan_to_map = false;  // --scan-to-map: registrations against the accumulated target; a result is a pose in the map
   float window = 0;          // --window: half-side of the cube the accumulated target is cropped to after every scan (0: never)
   size_t max_voxels = 0;     // the largest voxel count the windowed target reached
+  bool have_map = false;     // --load-target: the target holds a map before the first scan, which is registered like the others
+  bool localize = false;     // --localize: the loaded map stays as it is
   std::vector<std::vector<float>> trajectory;                     // trajectory_
   std::vector<float> pose = std::vector<float>(kIdentity, kIdentity + 16);
   std::vector<float> pres_transform = std::vector<float>(kIdentity, kIdentity + 16);  // rosbag node :33,95
@@ -124,6 +131,7 @@ struct Node {
 
   // --scan-to-map: the scan into the accumulated target at its pose in the map (column-major), then the window around it
   int accumulate(ndt_handle h, ndt_cloud scan, const float* map_pose) {
+    if (localize) return 0;
     CHECK(ndt_target_accumulate_cloud(h, scan, 1, map_pose));
     if (window > 0) {
       const float lo[3] = {map_pose[12] - window, map_pose[13] - window, map_pose[14] - window};
@@ -158,7 +166,8 @@ struct Node {
     }
     if (converged) {
       char title[96];
-      std::snprintf(title, sizeof(title), "Transform %zu to %zu: (%d iterations)", loaded - 2, loaded - 1, iterations);
+      if (loaded < 2) std::snprintf(title, sizeof(title), "Transform map to %zu: (%d iterations)", loaded - 1, iterations);  // --load-target
+      else std::snprintf(title, sizeof(title), "Transform %zu to %zu: (%d iterations)", loaded - 2, loaded - 1, iterations);
       print_matrix(title, T);
       std::vector<float> global(T, T + 16);
       if (!scan_to_map && !trajectory.empty()) ndt_host_chain_pose(trajectory.back().data(), T, global.data());  // trajectory_.back() * transform
@@ -250,7 +259,7 @@ static int run_resident(Node& node, ndt_pcd_sequence_handle seq, float voxel_lea
     node.loaded++;
     std::printf("Loaded cloud_%d.pcd (%zu points)\n", number, m);
     auto step = [&]() -> int {
-      if (node.loaded == 1) {  // load_initial_clouds, :64-68
+      if (node.loaded == 1 && !node.have_map) {  // load_initial_clouds, :64-68
         t0 = clock_type::now();
         int ov = 0;
         CHECK(ndt_map_update_cloud(h, current, 1, kIdentity, 0.5f, &ov));
@@ -544,8 +553,12 @@ static int run_pipelined(Node& node, ndt_pcd_sequence_handle seq, float voxel_le
 }
 
 int main(int argc, char** argv) {
-  bool scan_to_map = false, bad_window = false;
+  bool scan_to_map = false, bad_window = false, localize = false, bad_file = false;
   float window = 0;
+  const char *save_target = nullptr, *load_target = nullptr;
+  static const char kUsage[] =
+      "usage: map_sequence [--scan-to-map [--window <metres>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> "
+      "[voxel_leaf_size] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]\n";
   {  // the switches are taken out of the line before the positional arguments are read
     int kept = 1;
     for (int i = 1; i < argc; i++) {
@@ -554,6 +567,12 @@ int main(int argc, char** argv) {
       } else if (std::strcmp(argv[i], "--window") == 0) {
         window = i + 1 < argc ? static_cast<float>(std::atof(argv[++i])) : 0.f;
         bad_window = !(window > 0);
+      } else if (std::strcmp(argv[i], "--save-target") == 0 || std::strcmp(argv[i], "--load-target") == 0) {
+        const char*& file = argv[i][2] == 's' ? save_target : load_target;
+        file = i + 1 < argc ? argv[++i] : nullptr;
+        bad_file = bad_file || !file;
+      } else if (std::strcmp(argv[i], "--localize") == 0) {
+        localize = true;
       } else {
         argv[kept++] = argv[i];
       }
@@ -564,8 +583,12 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--window <metres> takes a positive half-side and goes with --scan-to-map\n");
     return 2;
   }
+  if (bad_file || ((save_target || load_target) && !scan_to_map) || (localize && !load_target)) {
+    std::fprintf(stderr, "--save-target <file> and --load-target <file> go with --scan-to-map, --localize goes with --load-target\n%s", kUsage);
+    return 2;
+  }
   if (argc < 2) {
-    std::printf("usage: map_sequence [--scan-to-map [--window <metres>]] <pcd_directory> [voxel_leaf_size] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]\n");
+    std::printf("%s", kUsage);
     return 0;
   }
   Node node;
@@ -574,6 +597,8 @@ int main(int argc, char** argv) {
   const bool host_clouds = argc > 6 && std::strcmp(argv[6], "host") == 0;  // serial only: every cloud through host buffers
   node.scan_to_map = scan_to_map;
   node.window = window;
+  node.have_map = load_target != nullptr;
+  node.localize = localize;
   if (scan_to_map && (node.rosbag || !serial || host_clouds)) {
     // (the rosbag loop prints getFitnessScore, which needs the target's points: an accumulated target keeps none)
     std::fprintf(stderr, "--scan-to-map runs the node's serial loop with resident clouds: not with rosbag, pipeline or host\n");
@@ -601,6 +626,7 @@ int main(int argc, char** argv) {
   }
   CHECK(ndt_warm_up(h, 65536));  // (a node knows its sensor: the reference's scans are lidar sweeps of some ten thousand points)
   if (map_handle) CHECK(ndt_warm_up(map_handle, 65536));
+  if (load_target) CHECK(ndt_target_accumulate_load(h, load_target));  // the map is there before the first scan arrives
   const double warm_ms = since(t_warm);
   const auto t_begin = clock_type::now();
   const int rc = !serial ? run_pipelined(node, seq, voxel_leaf_size, h, map_handle)
@@ -617,6 +643,12 @@ int main(int argc, char** argv) {
     print_matrix(title, node.trajectory[i].data());
   }
   if (node.window > 0) std::printf("window %g m: the accumulated target reached %zu voxels at most\n", node.window, node.max_voxels);
+  if (save_target) {
+    size_t voxels = 0;
+    CHECK(ndt_target_accumulate_save(h, nullptr, nullptr, save_target));
+    CHECK(ndt_diag_target_export(h, &voxels, nullptr, nullptr));
+    std::printf("accumulated target saved: %zu voxels, %zu bytes\n", voxels, 64 + 104 * voxels);
+  }
   std::printf("start-up (device, code object, page-locked slots; ndt_warm_up): %.1f ms, not in the times below\n", warm_ms);
   std::printf("time: total %.2f ms  (prefilter %.2f, %s %.2f, map update %.2f, waiting for the next file %.2f; %s)\n", since(t_begin), node.t_filter,
               serial ? "set inputs + align" : "take inputs over + align", node.t_align, node.t_map, node.t_wait,

@@ -318,7 +318,8 @@ ndt_status ndt_promote_source_to_target(ndt_handle h, int is_dense);
  *   cloud to rebuild from.
  * - What needs the target's points, or shares the immutable grid with another handle, returns an error and changes
  *   nothing: ndt_get_fitness_score (and ndt_batch_fitness_scores*) NDT_ERR_NO_INPUT; ndt_clone of, and
- *   ndt_share_input_target from, such a handle NDT_ERR_INVALID.
+ *   ndt_share_input_target from, such a handle NDT_ERR_INVALID (ndt_target_accumulate_export + _import, below, give another
+ *   handle the same map).
  * - Refused before anything of the target changes -- NDT_ERR_INVALID: a NULL handle, NULL points or clouds with a non-zero
  *   count, a NULL entry of clouds, a bad stride, more than INT_MAX points in one call, a finite point whose cell index
  *   floor(x / leaf) lies outside [-2^20, 2^20) on any axis (inside that range the reference's f32 index arithmetic,
@@ -373,6 +374,62 @@ ndt_status ndt_diag_target_accumulate(ndt_handle h, size_t* touched_voxels, size
  * (the scan counts one). */
 ndt_status ndt_target_accumulate_crop(ndt_handle h, const float min_xyz[3], const float max_xyz[3]);
 ndt_status ndt_diag_target_crop(ndt_handle h, size_t* kept_voxels, size_t* removed_voxels, size_t* kept_points, int* relinked, size_t* launches);
+/* Export and import: voxels leave an accumulated target and enter another one (or the same one later) bit for bit -- a map
+ * saved to a file and loaded by a later run, a second handle with the same map (ndt_clone / ndt_share_input_target keep
+ * refusing accumulated targets: export + import is the way), tiles paged out when a crop window moves on and paged back in
+ * when it returns.  A voxel's state is its absolute cell, its count and the twelve running sums; finishing it reads nothing
+ * else, and it depends only on the points of its own cell and on their order.
+ * - The blob (little-endian).  Header, 64 bytes: char magic[8] = "NDTACC1\0" at 0; u32 version = 1 at 8; u32 row_bytes = 104
+ *   at 12; f32 resolution at 16; u32 0 at 20; u64 n_voxels at 24; i32 lo[3] at 32 and i32 hi[3] at 44, the tight cell box of
+ *   the rows (all zero when n_voxels == 0); u64 checksum at 56.  Then n_voxels rows of 104 bytes: i32 i, j, k, count;
+ *   f64 d[9] = sx sy sz cxx cxy cxz cyy cyz czz (the Identity seed included); f32 f[3], the centroid sums; f32 0.
+ *   Rows are in strictly ascending key (ndt_host_acc_pack_cell: k high, i low), which is ascending linear index: a blob is
+ *   canonical -- two targets that hold the same points per cell in the same order export identical bytes, whatever their
+ *   history or slot order.  Checksum: h = 0xcbf29ce484222325, then per 8-byte word w of bytes [0, 56) followed by the rows
+ *   h = (h ^ w) * 0x100000001b3 mod 2^64.  The blob holds no min_points_per_voxel and no eigenvalue ratio: the sums do not
+ *   depend on them, and the importing target finishes the voxels under its own captured values.
+ * - Export.  Both bounds NULL: every voxel.  Otherwise the cell range of ndt_target_accumulate_crop (same arithmetic, same
+ *   saturation, the same refusals of NaN and min > max; exactly one NULL bound is NDT_ERR_INVALID).  Every voxel whose cell
+ *   lies in the range is exported whatever its state.  The target is not changed: nothing of it is written.  *bytes = the
+ *   size of the blob; buf == NULL: only that.  capacity too small: NDT_ERR_INVALID, nothing written.  No live accumulated
+ *   target: NDT_ERR_NO_INPUT.  A selection of no voxel, or a target without voxels, gives the valid 64-byte blob.
+ *   Device side: mark over the slots (the crop's kernel), hipCUB's stable sort of the (key, slot) pairs, one gather kernel
+ *   that writes the rows in sorted order -- THREE launches whatever the number of voxels (ONE, the mark, for buf == NULL;
+ *   none for a target without voxels) -- one read-back for the count, then the copy of the rows; the host writes the header
+ *   and the checksum.  ndt_diag_target_export, of the last export or save: rows, the sum of their counts, launches.
+ * - Import is an accumulate call in voxel form, with the start rule of ndt_target_accumulate*: a handle without a live
+ *   accumulated target starts one (resolution, min_points_per_voxel and eigenvalue ratio captured; a cloud target is
+ *   replaced, not continued), a live one is continued.  The blob's resolution must have the bits of that target's
+ *   resolution, and every cell of the blob must be ABSENT from the target.  Imports and point updates may follow each other
+ *   in any order.  New voxels take the slots after the existing ones, in blob order.  The box becomes the union of the
+ *   current box with the centres of the blob's corner cells, (cell + 0.5f) * leaf; NDT_ERR_GRID_OVERFLOW and the
+ *   dense-or-sparse rule are decided as in an update.  n_points grows by the sum of the rows' counts, n_voxels by the rows,
+ *   n_updates by one; ndt_diag_target_accumulate reports the import as an update (touched = new = rows).
+ * - Equivalence.  After any sequence of accumulate, crop and import calls the handle behaves like a handle with the same
+ *   parameters whose target was set from one concatenation: every posed point accumulated directly and the points behind
+ *   every imported voxel, each under the crops applied after it came in; within a cell the points in the order they were
+ *   first accumulated, wherever that happened.  The same dump and the same bits from every evaluation and registration
+ *   call listed above, for all four search methods.
+ * - A blob of no rows: NDT_OK, nothing changes, no device needed.
+ * - Import refuses, before anything changes and without a device, each with its own message -- NDT_ERR_INVALID: a NULL
+ *   handle or blob, fewer than 64 bytes, the magic, the version, row_bytes, bytes != 64 + 104 * n_voxels, the checksum, a
+ *   resolution that is not finite and positive, lo > hi or a box outside [-2^20, 2^20), a resolution other than the
+ *   target's, more than 2^30 voxels in the target afterwards.  After ONE check launch over the uploaded rows and the one
+ *   read-back, still before anything changes: a cell outside the header's box or a header box that is not the tight box of
+ *   the rows, count < 1, a non-finite sum, keys not strictly ascending (duplicates included), a cell already in the target.
+ *   Then growth and relink as an update, one placement launch and one finish launch over the new slots: 3 launches, plus one
+ *   when the key table is rebuilt and one when the look-up table is relinked, whatever the number of voxels.
+ * - _save is _export into a host buffer written to `path` through a temporary file in the same directory and a rename;
+ *   _load is the whole file read and imported.  I/O failures: NDT_ERR_INVALID with the path and strerror.
+ * ndt_host_acc_blob_info: the header of a blob that passes the device-free checks.  ndt_host_acc_blob_checksum: the hash
+ * above over `bytes` (a multiple of 8) of data.  Both host only. */
+ndt_status ndt_target_accumulate_export(ndt_handle h, const float min_xyz[3], const float max_xyz[3], void* buf, size_t capacity, size_t* bytes);
+ndt_status ndt_target_accumulate_import(ndt_handle h, const void* blob, size_t bytes);
+ndt_status ndt_target_accumulate_save(ndt_handle h, const float min_xyz[3], const float max_xyz[3], const char* path);
+ndt_status ndt_target_accumulate_load(ndt_handle h, const char* path);
+ndt_status ndt_diag_target_export(ndt_handle h, size_t* voxels, size_t* points, size_t* launches);
+ndt_status ndt_host_acc_blob_info(const void* blob, size_t bytes, float* resolution, size_t* n_voxels, int lo[3], int hi[3]);
+ndt_status ndt_host_acc_blob_checksum(const void* data, size_t bytes, uint64_t* out);
 /* the key of the accumulated target's voxel table: the absolute cell (i, j, k), 21 bits per axis, k in the high bits so
  * that keys ascend with the linear voxel index.  Host only.  NDT_ERR_INVALID outside [-2^20, 2^20). */
 ndt_status ndt_host_acc_pack_cell(int i, int j, int k, uint64_t* key);

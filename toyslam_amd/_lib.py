@@ -107,6 +107,13 @@ SIGNATURES = {
     "ndt_diag_target_accumulate": (C.c_int, [vp, szp, szp, ip, ip, szp]),
     "ndt_target_accumulate_crop": (C.c_int, [vp, fp, fp]),
     "ndt_diag_target_crop": (C.c_int, [vp, szp, szp, szp, ip, szp]),
+    "ndt_target_accumulate_export": (C.c_int, [vp, fp, fp, vp, C.c_size_t, szp]),
+    "ndt_target_accumulate_import": (C.c_int, [vp, vp, C.c_size_t]),
+    "ndt_target_accumulate_save": (C.c_int, [vp, fp, fp, C.c_char_p]),
+    "ndt_target_accumulate_load": (C.c_int, [vp, C.c_char_p]),
+    "ndt_diag_target_export": (C.c_int, [vp, szp, szp, szp]),
+    "ndt_host_acc_blob_info": (C.c_int, [vp, C.c_size_t, fp, szp, ip, ip]),
+    "ndt_host_acc_blob_checksum": (C.c_int, [vp, C.c_size_t, C.POINTER(C.c_uint64)]),
     "ndt_host_acc_pack_cell": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
     "ndt_host_acc_unpack_cell": (None, [C.c_uint64, ip, ip, ip]),
     "ndt_host_chain_pose": (None, [fp, fp, fp]),

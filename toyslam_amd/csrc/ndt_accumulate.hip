@@ -31,7 +31,11 @@
 //   k_acc_crop_compact  kept slots into FRESH arrays (cell, sums, state, record, side sector: none depends on box or slot)
 //   k_acc_rehash / k_acc_relink   the cleared key table and the cleared look-up table from the kept slots
 #include <hipcub/hipcub.hpp>
+#include <unistd.h>
 
+#include <cerrno>
+
+#include "ndt_acc_blob.hpp"
 #include "ndt_internal.hpp"
 #include "ndt_voxel_finish.hpp"
 
@@ -312,9 +316,11 @@ struct AccCropBox {
 constexpr int kAccCropInfoWords = 10;
 
 // a thread per slot: its keep flag; kept slots, their points and their cell box reduced in the wave, then one atomic per
-// wave and word (cells are exact floats: |cell| <= 2^20)
+// wave and word (cells are exact floats: |cell| <= 2^20).  An export also wants the pairs its sort takes (sort_keys != null):
+// the packed cell of a kept slot, kAccEmptyKey (sorts last) of any other, and the slot
 __global__ __launch_bounds__(kBlock) void k_acc_crop_mark(const int4* __restrict__ cell, int n_slots, AccCropBox box, unsigned* __restrict__ keep,
-                                                          int* __restrict__ info) {
+                                                          int* __restrict__ info, unsigned long long* __restrict__ sort_keys,
+                                                          int* __restrict__ sort_vals) {
   const int s = blockIdx.x * kBlock + threadIdx.x;
   bool kept = false;
   float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
@@ -323,6 +329,10 @@ __global__ __launch_bounds__(kBlock) void k_acc_crop_mark(const int4* __restrict
     const int4 c = cell[s];
     kept = c.x >= box.lo[0] && c.x <= box.hi[0] && c.y >= box.lo[1] && c.y <= box.hi[1] && c.z >= box.lo[2] && c.z <= box.hi[2];
     keep[s] = kept ? 1u : 0u;
+    if (sort_keys) {
+      sort_keys[s] = kept ? acc_pack(c.x, c.y, c.z) : kAccEmptyKey;
+      sort_vals[s] = s;
+    }
     if (kept) {
       mn[0] = mx[0] = static_cast<float>(c.x);
       mn[1] = mx[1] = static_cast<float>(c.y);
@@ -373,6 +383,104 @@ __global__ __launch_bounds__(kBlock) void k_acc_crop_compact(AccView from, int n
       cd[q] = cs[q];
     }
   }
+}
+
+// ---- export / import (ndt_target_accumulate_export / _import): a voxel leaves or enters as its cell, count and sums
+struct AccRow {  // a row of the blob (include/ndt_mi355.h)
+  int i, j, k, count;
+  double d[9];
+  float f[3];
+  float pad;
+};
+static_assert(sizeof(AccRow) == ndtc::kAccBlobRowBytes, "a blob row is 104 bytes");
+
+// a thread per row of the export: the slots in ascending key, as the sort left them; info[6] = rows (k_acc_crop_mark)
+__global__ __launch_bounds__(kBlock) void k_acc_export_gather(AccView v, const int* __restrict__ sorted_slot, const int* __restrict__ info, int n_slots,
+                                                              AccRow* __restrict__ rows) {
+  const int o = blockIdx.x * kBlock + threadIdx.x;
+  if (o >= n_slots || o >= info[6]) return;
+  const int s = sorted_slot[o];
+  const int4 c = v.cell[s];
+  const AccSums A = v.sums[s];
+  AccRow r;
+  r.i = c.x; r.j = c.y; r.k = c.z; r.count = c.w;
+#pragma unroll
+  for (int q = 0; q < 9; q++) r.d[q] = A.d[q];
+#pragma unroll
+  for (int q = 0; q < 3; q++) r.f[q] = A.f[q];
+  r.pad = 0.f;
+  rows[o] = r;
+}
+
+// what is wrong with a row (info[6] of an import check)
+constexpr int kAccRowOutside = 1, kAccRowCount = 2, kAccRowNonFinite = 4, kAccRowOrder = 8, kAccRowPresent = 16;
+
+// a thread per row of an import: its flags, the rows' cell box and the sum of their counts, reduced as k_acc_crop_mark does.
+// info words as a crop's: [0..2] lowest cell, [3..5] highest cell, [6] flags (or), [8..9] points (64 bit)
+__global__ __launch_bounds__(kBlock) void k_acc_import_check(const AccRow* __restrict__ rows, int n, AccCropBox box, AccView v, int* __restrict__ info) {
+  const int o = blockIdx.x * kBlock + threadIdx.x;
+  int flags = 0;
+  bool inside = false;
+  float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+  double pts = 0.0;
+  if (o < n) {
+    const AccRow r = rows[o];
+    inside = r.i >= box.lo[0] && r.i <= box.hi[0] && r.j >= box.lo[1] && r.j <= box.hi[1] && r.k >= box.lo[2] && r.k <= box.hi[2];
+    if (!inside) flags |= kAccRowOutside;
+    if (r.count < 1) flags |= kAccRowCount;
+    else pts = static_cast<double>(r.count);
+    bool fin = isfinite(r.f[0]) && isfinite(r.f[1]) && isfinite(r.f[2]);
+#pragma unroll
+    for (int q = 0; q < 9; q++) fin = fin && isfinite(r.d[q]);
+    if (!fin) flags |= kAccRowNonFinite;
+    if (inside) {  // (the header's box lies within the lattice: the cell packs)
+      const unsigned long long key = acc_pack(r.i, r.j, r.k);
+      if (o > 0) {
+        const AccRow p = rows[o - 1];
+        const bool p_inside = p.i >= box.lo[0] && p.i <= box.hi[0] && p.j >= box.lo[1] && p.j <= box.hi[1] && p.k >= box.lo[2] && p.k <= box.hi[2];
+        if (p_inside && acc_pack(p.i, p.j, p.k) >= key) flags |= kAccRowOrder;
+      }
+      if (acc_find(v, key) >= 0) flags |= kAccRowPresent;
+      mn[0] = mx[0] = static_cast<float>(r.i);
+      mn[1] = mx[1] = static_cast<float>(r.j);
+      mn[2] = mx[2] = static_cast<float>(r.k);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    mn[k] = wave_min(mn[k]);
+    mx[k] = wave_max(mx[k]);
+  }
+  pts = wave_sum(pts);  // (at most 64 x INT_MAX: exact)
+  const unsigned long long mask = __ballot(inside);
+  if (mask != 0 && (threadIdx.x & (kWave - 1)) == 0) {
+    for (int k = 0; k < 3; k++) {
+      atomicMin(info + k, static_cast<int>(mn[k]));
+      atomicMax(info + 3 + k, static_cast<int>(mx[k]));
+    }
+  }
+  if ((threadIdx.x & (kWave - 1)) == 0) atomicAdd(reinterpret_cast<unsigned long long*>(info + 8), static_cast<unsigned long long>(pts));
+  if (flags) atomicOr(info + 6, flags);
+}
+
+// a thread per (checked) row: the voxel into slot n_slots_before + row -- cell, sums, "not finished yet", its key
+__global__ __launch_bounds__(kBlock) void k_acc_import_place(const AccRow* __restrict__ rows, int n, int n_slots_before, AccView v,
+                                                             int* __restrict__ touched) {
+  const int o = blockIdx.x * kBlock + threadIdx.x;
+  if (o >= n) return;
+  const AccRow r = rows[o];
+  const int slot = n_slots_before + o;
+  AccSums A;
+#pragma unroll
+  for (int q = 0; q < 9; q++) A.d[q] = r.d[q];
+#pragma unroll
+  for (int q = 0; q < 3; q++) A.f[q] = r.f[q];
+  A.pad = 0.f;
+  v.cell[slot] = make_int4(r.i, r.j, r.k, r.count);
+  v.sums[slot] = A;
+  v.state[slot] = 0;
+  acc_insert(v, acc_pack(r.i, r.j, r.k), slot);
+  touched[o] = slot;
 }
 
 inline int acc_grid_for(size_t n, int cap) {
@@ -486,6 +594,72 @@ ndt_status acc_grow(ndt_context* h, AccTarget* a, int want, bool* grown) {
   return NDT_OK;
 }
 
+// a target starts: the handle's parameters captured, nothing of its previous target continued.  It becomes the handle's
+// (acc_adopt) only once the call that starts it can no longer be refused
+std::shared_ptr<AccTarget> acc_start(ndt_context* h) {
+  auto started = std::make_shared<AccTarget>();
+  AccTarget* a = started.get();
+  a->resolution = h->resolution;
+  a->min_pts = h->min_pts;
+  a->eig_ratio = h->eig_ratio;
+  a->bits = a->first_bits = env_int("NDT_ACC_HASH_BITS", 16, 2, 30);
+  a->first_cap = env_int("NDT_ACC_SLOTS", 1 << 15, 1, 1 << 30);
+  a->slot_cap = 0;
+  a->grid = std::make_shared<DeviceGrid>();
+  a->grid->accumulated = true;
+  a->grid->resolution = a->resolution;
+  a->grid->min_pts = a->min_pts;
+  a->grid->eig_ratio = a->eig_ratio;
+  for (int k = 0; k < 3; k++) {
+    a->grid->geom.leaf[k] = a->resolution;
+    a->grid->geom.inv_leaf[k] = 1.0f / a->resolution;
+  }
+  return started;
+}
+void acc_adopt(ndt_context* h, const std::shared_ptr<AccTarget>& started) {
+  h->acc = started;
+  h->grid = started->grid;
+  auto holder = std::make_shared<DeviceCloud>();  // the handle "has a target"; its points are not kept
+  h->target = holder;
+  h->target_dense = 0;
+}
+
+// the table the evaluation kernels read, under the geometry `geo` of the box [mn, mx]: relinked only when the box, its form
+// or its size changed.  The slots before this call are entered again; the call's own voxels follow through k_acc_finish
+ndt_status acc_settle_table(ndt_context* h, AccTarget* a, ndt::GridGeom& geo, bool sparse, const float* mn, const float* mx, int n_slots_before) {
+  hipStream_t st = h->stream;
+  DeviceGrid* g = a->grid.get();
+  bool relink = !a->have_box || sparse != a->sparse || std::memcmp(geo.min_b, g->geom.min_b, sizeof(geo.min_b)) != 0 ||
+                std::memcmp(geo.max_b, g->geom.max_b, sizeof(geo.max_b)) != 0;
+  int hash_bits = 0;
+  if (sparse) {
+    hash_bits = 10;
+    while ((static_cast<size_t>(1) << hash_bits) < 2 * static_cast<size_t>(a->slot_cap)) hash_bits++;
+    if (hash_bits != g->geom.hash_bits) relink = true;
+  }
+  geo.hash_bits = hash_bits;
+  if (relink) {
+    const size_t words = sparse ? (static_cast<size_t>(2) << hash_bits) : static_cast<size_t>(geo.lut_cells);
+    DevBuf<int> lut;
+    HIP_TRY(lut.reserve(words));
+    HIP_TRY(hipMemsetAsync(lut.p, 0xFF, words * sizeof(int), st));  // kLutEmpty / free hash slots
+    g->lut.swap(lut);
+    if (n_slots_before) {
+      hipLaunchKernelGGL(ndt::k_acc_relink, dim3(ndt::acc_grid_for(n_slots_before, 1 << 30)), dim3(ndt::kBlock), 0, st, a->view(), n_slots_before, geo, g->lut.p);
+      h->acc_launches++;
+      h->acc_relinked = a->have_box ? 1 : 0;
+    }
+  }
+  g->geom = geo;
+  a->sparse = sparse;
+  a->have_box = true;
+  for (int k = 0; k < 3; k++) {
+    a->mn[k] = mn[k];
+    a->mx[k] = mx[k];
+  }
+  return NDT_OK;
+}
+
 ndt_status acc_update(ndt_context* h, const std::vector<AccScan>& scans, size_t total) {
   static const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   hipStream_t st = h->stream;
@@ -495,23 +669,8 @@ ndt_status acc_update(ndt_context* h, const std::vector<AccScan>& scans, size_t 
   AccTarget* a = acc_live(h);
   std::shared_ptr<AccTarget> started;
   if (!a) {  // a target starts: parameters captured, nothing of the handle's previous target is continued
-    started = std::make_shared<AccTarget>();
+    started = acc_start(h);
     a = started.get();
-    a->resolution = h->resolution;
-    a->min_pts = h->min_pts;
-    a->eig_ratio = h->eig_ratio;
-    a->bits = a->first_bits = env_int("NDT_ACC_HASH_BITS", 16, 2, 30);
-    a->first_cap = env_int("NDT_ACC_SLOTS", 1 << 15, 1, 1 << 30);
-    a->slot_cap = 0;
-    a->grid = std::make_shared<DeviceGrid>();
-    a->grid->accumulated = true;
-    a->grid->resolution = a->resolution;
-    a->grid->min_pts = a->min_pts;
-    a->grid->eig_ratio = a->eig_ratio;
-    for (int k = 0; k < 3; k++) {
-      a->grid->geom.leaf[k] = a->resolution;
-      a->grid->geom.inv_leaf[k] = 1.0f / a->resolution;
-    }
   }
   DeviceGrid* g = a->grid.get();
   const float inv_leaf = 1.0f / a->resolution;
@@ -625,13 +784,7 @@ ndt_status acc_update(ndt_context* h, const std::vector<AccScan>& scans, size_t 
   }
   if (static_cast<long long>(a->n_slots) + n_new > (1ll << 30)) return fail(NDT_ERR_INVALID, "too many voxels in the accumulated target");
   // ---- from here on the target changes
-  if (started) {
-    h->acc = started;
-    h->grid = a->grid;
-    auto holder = std::make_shared<DeviceCloud>();  // the handle "has a target"; its points are not kept
-    h->target = holder;
-    h->target_dense = 0;
-  }
+  if (started) acc_adopt(h, started);
   a->n_points = n_points;
   a->n_updates++;
   h->target->n = a->n_points;
@@ -645,35 +798,8 @@ ndt_status acc_update(ndt_context* h, const std::vector<AccScan>& scans, size_t 
   bool grown = false;
   ndt_status s = acc_grow(h, a, n_slots_before + n_new, &grown);
   if (s) return s;
-  // ---- the table the evaluation kernels read: relinked only when the box, its form or its size changed
-  bool relink = !a->have_box || sparse != a->sparse || std::memcmp(geo.min_b, g->geom.min_b, sizeof(geo.min_b)) != 0 ||
-                std::memcmp(geo.max_b, g->geom.max_b, sizeof(geo.max_b)) != 0;
-  int hash_bits = 0;
-  if (sparse) {
-    hash_bits = 10;
-    while ((static_cast<size_t>(1) << hash_bits) < 2 * static_cast<size_t>(a->slot_cap)) hash_bits++;
-    if (hash_bits != g->geom.hash_bits) relink = true;
-  }
-  geo.hash_bits = hash_bits;
-  if (relink) {
-    const size_t words = sparse ? (static_cast<size_t>(2) << hash_bits) : static_cast<size_t>(geo.lut_cells);
-    DevBuf<int> lut;
-    HIP_TRY(lut.reserve(words));
-    HIP_TRY(hipMemsetAsync(lut.p, 0xFF, words * sizeof(int), st));  // kLutEmpty / free hash slots
-    g->lut.swap(lut);
-    if (n_slots_before) {
-      hipLaunchKernelGGL(ndt::k_acc_relink, dim3(ndt::acc_grid_for(n_slots_before, 1 << 30)), dim3(ndt::kBlock), 0, st, a->view(), n_slots_before, geo, g->lut.p);
-      h->acc_launches++;
-      h->acc_relinked = a->have_box ? 1 : 0;
-    }
-  }
-  g->geom = geo;
-  a->sparse = sparse;
-  a->have_box = true;
-  for (int k = 0; k < 3; k++) {
-    a->mn[k] = mn[k];
-    a->mx[k] = mx[k];
-  }
+  s = acc_settle_table(h, a, geo, sparse, mn, mx, n_slots_before);
+  if (s) return s;
   // ---- merge and finish the touched voxels
   if (n_runs > 0) {
     const ndt::FinalizeDump nodump{nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -777,7 +903,8 @@ ndt_status acc_crop(ndt_context* h, AccTarget* a, const ndt::AccCropBox& box) {
   const int imax = std::numeric_limits<int>::max(), imin = std::numeric_limits<int>::min();
   const int info0[ndt::kAccCropInfoWords] = {imax, imax, imax, imin, imin, imin, 0, 0, 0, 0};
   HIP_TRY(hipMemcpyAsync(info.p, info0, sizeof(info0), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(ndt::k_acc_crop_mark, dim3(ndt::acc_grid_for(S, 1 << 30)), dim3(ndt::kBlock), 0, st, a->cell.p, n_slots, box, keep, info.p);
+  hipLaunchKernelGGL(ndt::k_acc_crop_mark, dim3(ndt::acc_grid_for(S, 1 << 30)), dim3(ndt::kBlock), 0, st, a->cell.p, n_slots, box, keep, info.p,
+                     static_cast<unsigned long long*>(nullptr), static_cast<int*>(nullptr));
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipcub::DeviceScan::ExclusiveSum(temp.p, tb, keep, number, n_slots, st));
   h->crop_launches += 2;
@@ -877,6 +1004,234 @@ ndt_status acc_crop(ndt_context* h, AccTarget* a, const ndt::AccCropBox& box) {
   g->counts_known = false;
   HIP_TRY(hipGetLastError());
   return NDT_OK;
+}
+
+// ndt_target_accumulate_export once the bounds are cells.  buf == null: only the size (the mark alone).  Else mark, sort of
+// the (key, slot) pairs, gather -- queued together -- then ONE read-back (rows, their points, their cell box) and the copy of
+// the rows; the host writes the header and the checksum.  Nothing of the target is written
+ndt_status acc_export(ndt_context* h, AccTarget* a, const ndt::AccCropBox& box, void* buf, size_t capacity, size_t* bytes) {
+  hipStream_t st = h->stream;
+  h->exp_voxels = h->exp_points = h->exp_launches = 0;
+  const int zero[3] = {0, 0, 0};
+  if (a->n_slots == 0) {  // no voxel: the header alone
+    if (buf && capacity < ndtc::kAccBlobHeaderBytes) return fail(NDT_ERR_INVALID, "the export buffer is too small for the blob");
+    if (buf) acc_blob_write_header(buf, a->resolution, 0, zero, zero, nullptr);
+    *bytes = ndtc::kAccBlobHeaderBytes;
+    return NDT_OK;
+  }
+  const int n_slots = a->n_slots;
+  const size_t S = static_cast<size_t>(n_slots);
+  DevBuf<unsigned> keep;
+  DevBuf<int> info, vals_a, vals_b;
+  DevBuf<unsigned long long> keys_a, keys_b;
+  DevBuf<ndt::AccRow> rows;
+  DevBuf<unsigned char> temp;
+  HIP_TRY(keep.reserve(S));
+  HIP_TRY(info.reserve(ndt::kAccCropInfoWords));
+  size_t tb = 0;
+  if (buf) {
+    HIP_TRY(keys_a.reserve(S));
+    HIP_TRY(keys_b.reserve(S));
+    HIP_TRY(vals_a.reserve(S));
+    HIP_TRY(vals_b.reserve(S));
+    HIP_TRY(rows.reserve(S));
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys_a.p, keys_b.p, vals_a.p, vals_b.p, n_slots, 0, 64, st));
+    tb += 256;
+    HIP_TRY(temp.reserve(tb));
+  }
+  const int imax = std::numeric_limits<int>::max(), imin = std::numeric_limits<int>::min();
+  const int info0[ndt::kAccCropInfoWords] = {imax, imax, imax, imin, imin, imin, 0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(info.p, info0, sizeof(info0), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(ndt::k_acc_crop_mark, dim3(ndt::acc_grid_for(S, 1 << 30)), dim3(ndt::kBlock), 0, st, a->cell.p, n_slots, box, keep.p, info.p,
+                     buf ? keys_a.p : nullptr, buf ? vals_a.p : nullptr);
+  HIP_TRY(hipGetLastError());
+  h->exp_launches = 1;
+  if (buf) {
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(temp.p, tb, keys_a.p, keys_b.p, vals_a.p, vals_b.p, n_slots, 0, 64, st));
+    hipLaunchKernelGGL(ndt::k_acc_export_gather, dim3(ndt::acc_grid_for(S, 1 << 30)), dim3(ndt::kBlock), 0, st, a->view(), vals_b.p, info.p, n_slots, rows.p);
+    HIP_TRY(hipGetLastError());
+    h->exp_launches = 3;
+  }
+  // ---- the one read-back
+  int hinfo[ndt::kAccCropInfoWords];
+  HIP_TRY(hipMemcpyAsync(hinfo, info.p, sizeof(hinfo), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const int n = hinfo[6];
+  unsigned long long points = 0;
+  std::memcpy(&points, hinfo + 8, sizeof(points));
+  if (n < 0 || n > n_slots) return fail(NDT_ERR_HIP, "export: the row count is out of range");
+  const size_t payload = static_cast<size_t>(n) * ndtc::kAccBlobRowBytes, need = ndtc::kAccBlobHeaderBytes + payload;
+  if (buf) {
+    if (capacity < need) return fail(NDT_ERR_INVALID, "the export buffer is too small for the blob");
+    unsigned char* out = static_cast<unsigned char*>(buf);
+    if (n) {
+      HIP_TRY(hipMemcpyAsync(out + ndtc::kAccBlobHeaderBytes, rows.p, payload, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+    }
+    acc_blob_write_header(out, a->resolution, static_cast<uint64_t>(n), hinfo, hinfo + 3, out + ndtc::kAccBlobHeaderBytes);
+  }
+  *bytes = need;
+  h->exp_voxels = static_cast<size_t>(n);
+  h->exp_points = static_cast<size_t>(points);
+  return NDT_OK;
+}
+
+ndt_status acc_export_entry(ndt_handle h, const float* min_xyz, const float* max_xyz, void* buf, size_t capacity, size_t* bytes) {
+  if (!h) return fail(NDT_ERR_INVALID, "null handle");
+  if (!bytes) return fail(NDT_ERR_INVALID, "null bytes");
+  if ((min_xyz == nullptr) != (max_xyz == nullptr)) return fail(NDT_ERR_INVALID, "one bound of the export box is null: give both, or neither for every voxel");
+  ndt::AccCropBox box;
+  for (int k = 0; k < 3; k++) {
+    box.lo[k] = -ndt::kAccCellBias;
+    box.hi[k] = ndt::kAccCellBias - 1;
+  }
+  if (min_xyz) {
+    for (int k = 0; k < 3; k++) {
+      if (std::isnan(min_xyz[k]) || std::isnan(max_xyz[k])) return fail(NDT_ERR_INVALID, "a bound of the crop box is NaN");
+      if (min_xyz[k] > max_xyz[k]) return fail(NDT_ERR_INVALID, "the crop box has min > max on an axis");
+    }
+  }
+  AccTarget* a = acc_live(h);
+  if (!a) return fail(NDT_ERR_NO_INPUT, "no accumulated target to export");
+  if (min_xyz) {
+    const float inv_leaf = 1.0f / a->resolution;
+    for (int k = 0; k < 3; k++) {
+      box.lo[k] = acc_crop_cell(min_xyz[k], inv_leaf);
+      box.hi[k] = acc_crop_cell(max_xyz[k], inv_leaf);
+    }
+  }
+  if (a->n_slots) {
+    ndt_status s = ensure_device(h);
+    if (s) return s;
+  }
+  return acc_export(h, a, box, buf, capacity, bytes);
+}
+
+// ndt_target_accumulate_import: an accumulate call whose input is voxels.  Upload, ONE check launch over the rows, ONE
+// read-back, the refusals; then growth and relink as an update, the rows placed behind the existing slots and finished
+ndt_status acc_import(ndt_handle h, const void* blob, size_t bytes) {
+  if (!h) return fail(NDT_ERR_INVALID, "null handle");
+  ndtc::AccBlobHeader hd;
+  if (const char* why = acc_blob_parse(blob, bytes, &hd)) return fail(NDT_ERR_INVALID, why);
+  AccTarget* a = acc_live(h);
+  const float resolution = a ? a->resolution : h->resolution;
+  if (std::memcmp(&hd.resolution, &resolution, sizeof(float)) != 0)
+    return fail(NDT_ERR_INVALID, "the blob's resolution is not the resolution of the target it is imported into");
+  if (static_cast<unsigned long long>(a ? a->n_slots : 0) + hd.n_voxels > (1ull << 30)) return fail(NDT_ERR_INVALID, "too many voxels in the accumulated target");
+  if (hd.n_voxels == 0) return NDT_OK;
+  ndt_status s = ensure_device(h);
+  if (s) return s;
+  hipStream_t st = h->stream;
+  h->acc_touched = h->acc_new = h->acc_launches = 0;
+  h->acc_relinked = h->acc_grown = 0;
+  std::shared_ptr<AccTarget> started;
+  if (!a) {
+    started = acc_start(h);
+    a = started.get();
+  }
+  DeviceGrid* g = a->grid.get();
+  const int n = static_cast<int>(hd.n_voxels);
+  const size_t N = static_cast<size_t>(n);
+  DevBuf<ndt::AccRow> rows;
+  DevBuf<int> info, touched;
+  HIP_TRY(rows.reserve(N));
+  HIP_TRY(info.reserve(ndt::kAccCropInfoWords));
+  HIP_TRY(touched.reserve(N));
+  const int imax = std::numeric_limits<int>::max(), imin = std::numeric_limits<int>::min();
+  const int info0[ndt::kAccCropInfoWords] = {imax, imax, imax, imin, imin, imin, 0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(info.p, info0, sizeof(info0), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(rows.p, static_cast<const unsigned char*>(blob) + ndtc::kAccBlobHeaderBytes, N * sizeof(ndt::AccRow), hipMemcpyHostToDevice, st));
+  ndt::AccCropBox box;
+  for (int k = 0; k < 3; k++) {
+    box.lo[k] = hd.lo[k];
+    box.hi[k] = hd.hi[k];
+  }
+  hipLaunchKernelGGL(ndt::k_acc_import_check, dim3(ndt::acc_grid_for(N, 1 << 30)), dim3(ndt::kBlock), 0, st, rows.p, n, box, a->view(), info.p);
+  HIP_TRY(hipGetLastError());
+  h->acc_launches++;
+  // ---- the one read-back (the blob is the caller's pageable memory: the copy has read it by then)
+  int hinfo[ndt::kAccCropInfoWords];
+  HIP_TRY(hipMemcpyAsync(hinfo, info.p, sizeof(hinfo), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  // ---- refusals: nothing of the target has been written so far
+  const int flags = hinfo[6];
+  if (flags & ndt::kAccRowOutside) return fail(NDT_ERR_INVALID, "a row of the blob lies outside the cell box of its header");
+  if (flags & ndt::kAccRowCount) return fail(NDT_ERR_INVALID, "a row of the blob has a count below 1");
+  if (flags & ndt::kAccRowNonFinite) return fail(NDT_ERR_INVALID, "a row of the blob holds a non-finite sum");
+  if (flags & ndt::kAccRowOrder) return fail(NDT_ERR_INVALID, "the rows of the blob are not in strictly ascending key order");
+  for (int k = 0; k < 3; k++)
+    if (hinfo[k] != hd.lo[k] || hinfo[3 + k] != hd.hi[k]) return fail(NDT_ERR_INVALID, "the header's cell box is not the tight box of the blob's rows");
+  if (flags & ndt::kAccRowPresent) return fail(NDT_ERR_INVALID, "cell already in the target: a blob's cells must be absent from the target it is imported into");
+  unsigned long long points = 0;
+  std::memcpy(&points, hinfo + 8, sizeof(points));
+  // ---- the box: the union with the centres of the blob's corner cells, the float a cropped target carries
+  float mn[3], mx[3];
+  for (int k = 0; k < 3; k++) {
+    const float lo = (static_cast<float>(hd.lo[k]) + 0.5f) * a->resolution, hi = (static_cast<float>(hd.hi[k]) + 0.5f) * a->resolution;
+    mn[k] = a->have_box ? std::min(a->mn[k], lo) : lo;
+    mx[k] = a->have_box ? std::max(a->mx[k], hi) : hi;
+  }
+  ndt::GridGeom geo = g->geom;
+  s = acc_geometry(a->resolution, mn, mx, geo);
+  if (s) return s;
+  const size_t n_points = a->n_points + static_cast<size_t>(points);
+  const long long np = static_cast<long long>(std::min<size_t>(n_points, static_cast<size_t>(std::numeric_limits<int>::max())));
+  const bool sparse = ndt::wants_sparse_index(h->voxel_index, geo.n_cells, np);
+  // ---- from here on the target changes
+  if (started) acc_adopt(h, started);
+  a->n_points = n_points;
+  a->n_updates++;
+  h->target->n = a->n_points;
+  const int n_slots_before = a->n_slots;
+  if (a->slot_cap == 0 && !a->cell.p) {
+    bool ignore = false;
+    s = acc_grow(h, a, a->first_cap, &ignore);
+    if (s) return s;
+  }
+  bool grown = false;
+  s = acc_grow(h, a, n_slots_before + n, &grown);
+  if (s) return s;
+  s = acc_settle_table(h, a, geo, sparse, mn, mx, n_slots_before);
+  if (s) return s;
+  const ndt::FinalizeDump nodump{nullptr, nullptr, nullptr, nullptr, nullptr};
+  hipLaunchKernelGGL(ndt::k_acc_import_place, dim3(ndt::acc_grid_for(N, 1 << 30)), dim3(ndt::kBlock), 0, st, rows.p, n, n_slots_before, a->view(), touched.p);
+  hipLaunchKernelGGL(ndt::k_acc_finish, dim3(ndt::acc_grid_for(N, 1 << 30)), dim3(ndt::kBlock), 0, st, touched.p, n, a->view(), a->min_pts, a->eig_ratio,
+                     g->recs.p, g->centroids.p, g->lut.p, geo, nodump, static_cast<int*>(nullptr));
+  HIP_TRY(hipGetLastError());
+  h->acc_launches += 2;
+  a->n_slots = n_slots_before + n;
+  g->empty = false;
+  g->n_leaves = static_cast<size_t>(a->n_slots);
+  g->counts_known = false;
+  h->acc_touched = h->acc_new = N;
+  h->acc_grown = grown ? 1 : 0;
+  return NDT_OK;
+}
+
+// a whole file into memory / a buffer to a file through a temporary one beside it; "" = done, else the failure
+std::string acc_read_file(const char* path, std::vector<unsigned char>& out) {
+  FILE* f = std::fopen(path, "rb");
+  if (!f) return std::string("cannot open ") + path + ": " + std::strerror(errno);
+  unsigned char chunk[1 << 16];
+  size_t got;
+  while ((got = std::fread(chunk, 1, sizeof(chunk), f)) > 0) out.insert(out.end(), chunk, chunk + got);
+  const bool bad = std::ferror(f) != 0;
+  const int err = errno;
+  std::fclose(f);
+  return bad ? std::string("cannot read ") + path + ": " + std::strerror(err) : std::string();
+}
+std::string acc_write_file(const char* path, const unsigned char* data, size_t bytes) {
+  const std::string tmp = std::string(path) + ".tmp" + std::to_string(static_cast<long long>(getpid()));
+  FILE* f = std::fopen(tmp.c_str(), "wb");
+  if (!f) return std::string("cannot write ") + path + ": " + std::strerror(errno);
+  const bool wrote = std::fwrite(data, 1, bytes, f) == bytes;
+  int err = errno;
+  const bool closed = std::fclose(f) == 0;
+  if (wrote && !closed) err = errno;
+  if (wrote && closed && std::rename(tmp.c_str(), path) == 0) return std::string();
+  if (wrote && closed) err = errno;
+  std::remove(tmp.c_str());
+  return std::string("cannot write ") + path + ": " + std::strerror(err);
 }
 
 }  // namespace
@@ -1062,6 +1417,57 @@ ndt_status ndt_diag_target_crop(ndt_handle h, size_t* kept_voxels, size_t* remov
   if (kept_points) *kept_points = h->crop_points;
   if (relinked) *relinked = h->crop_relinked;
   if (launches) *launches = h->crop_launches;
+  return NDT_OK;
+}
+
+ndt_status ndt_target_accumulate_export(ndt_handle h, const float* min_xyz, const float* max_xyz, void* buf, size_t capacity, size_t* bytes) {
+  return acc_export_entry(h, min_xyz, max_xyz, buf, capacity, bytes);
+}
+ndt_status ndt_target_accumulate_import(ndt_handle h, const void* blob, size_t bytes) { return acc_import(h, blob, bytes); }
+ndt_status ndt_target_accumulate_save(ndt_handle h, const float* min_xyz, const float* max_xyz, const char* path) {
+  if (!h) return fail(NDT_ERR_INVALID, "null handle");
+  if (!path) return fail(NDT_ERR_INVALID, "null path");
+  const AccTarget* a = acc_live(h);
+  // room for every voxel: one export, whatever the box selects
+  std::vector<unsigned char> blob(ndtc::kAccBlobHeaderBytes + (a ? static_cast<size_t>(a->n_slots) : 0) * ndtc::kAccBlobRowBytes);
+  size_t bytes = 0;
+  ndt_status s = acc_export_entry(h, min_xyz, max_xyz, blob.data(), blob.size(), &bytes);
+  if (s) return s;
+  const std::string err = acc_write_file(path, blob.data(), bytes);
+  if (!err.empty()) return fail(NDT_ERR_INVALID, err);
+  return NDT_OK;
+}
+ndt_status ndt_target_accumulate_load(ndt_handle h, const char* path) {
+  if (!h) return fail(NDT_ERR_INVALID, "null handle");
+  if (!path) return fail(NDT_ERR_INVALID, "null path");
+  std::vector<unsigned char> blob;
+  const std::string err = acc_read_file(path, blob);
+  if (!err.empty()) return fail(NDT_ERR_INVALID, err);
+  return acc_import(h, blob.data(), blob.size());
+}
+ndt_status ndt_diag_target_export(ndt_handle h, size_t* voxels, size_t* points, size_t* launches) {
+  if (!h) return fail(NDT_ERR_INVALID, "null handle");
+  if (voxels) *voxels = h->exp_voxels;
+  if (points) *points = h->exp_points;
+  if (launches) *launches = h->exp_launches;
+  return NDT_OK;
+}
+ndt_status ndt_host_acc_blob_info(const void* blob, size_t bytes, float* resolution, size_t* n_voxels, int* lo, int* hi) {
+  ndtc::AccBlobHeader hd;
+  if (const char* why = acc_blob_parse(blob, bytes, &hd)) return fail(NDT_ERR_INVALID, why);
+  if (resolution) *resolution = hd.resolution;
+  if (n_voxels) *n_voxels = static_cast<size_t>(hd.n_voxels);
+  for (int k = 0; k < 3; k++) {
+    if (lo) lo[k] = hd.lo[k];
+    if (hi) hi[k] = hd.hi[k];
+  }
+  return NDT_OK;
+}
+ndt_status ndt_host_acc_blob_checksum(const void* data, size_t bytes, uint64_t* out) {
+  if (!out) return fail(NDT_ERR_INVALID, "null out");
+  if (bytes && !data) return fail(NDT_ERR_INVALID, "null data");
+  if (bytes % 8) return fail(NDT_ERR_INVALID, "the checksum runs over 8-byte words: bytes must be a multiple of 8");
+  *out = acc_blob_hash(ndtc::kAccBlobHashSeed, data, bytes);
   return NDT_OK;
 }
 

@@ -467,6 +467,8 @@ struct ndt_context {
   // ... and the last ndt_target_accumulate_crop (ndt_diag_target_crop)
   size_t crop_kept = 0, crop_removed = 0, crop_points = 0, crop_launches = 0;
   int crop_relinked = 0;
+  // ... and the last ndt_target_accumulate_export / _save (ndt_diag_target_export)
+  size_t exp_voxels = 0, exp_points = 0, exp_launches = 0;
 
   ~ndt_context() {
     for (ndt_context* w : batch_workers) delete w;

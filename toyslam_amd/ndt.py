@@ -507,6 +507,52 @@ class NormalDistributionsTransform:
         check(self._L.ndt_diag_target_crop(self._h, C.byref(k), C.byref(r), C.byref(p), C.byref(w), C.byref(l)))
         return dict(kept_voxels=k.value, removed_voxels=r.value, kept_points=p.value, relinked=bool(w.value), launches=l.value)
 
+    @staticmethod
+    def _box(min_xyz, max_xyz):
+        if (min_xyz is None) != (max_xyz is None):
+            raise ValueError("give both bounds, or neither for every voxel")
+        if min_xyz is None:
+            return None, None
+        mn, mx = (np.ascontiguousarray(v, dtype=np.float32).reshape(3) for v in (min_xyz, max_xyz))
+        return mn, mx
+
+    def targetAccumulateExport(self, min_xyz=None, max_xyz=None):
+        """The voxels of the accumulated target whose cells lie in crop_cell_range(resolution, min_xyz, max_xyz) -- all of
+        them without bounds -- as a blob (ndt_target_accumulate_export; layout: ACC_ROW_DTYPE, acc_blob_info).  The target
+        is not changed.  -> bytes."""
+        mn, mx = self._box(min_xyz, max_xyz)
+        cap = 64 + ACC_ROW_DTYPE.itemsize * self.targetAccumulated()["voxels"]   # room for every voxel: one call
+        buf = np.empty(cap, dtype=np.uint8)
+        n = C.c_size_t(0)
+        check(self._L.ndt_target_accumulate_export(self._h, _f(mn) if mn is not None else None, _f(mx) if mx is not None else None,
+                                                   buf.ctypes.data, cap, C.byref(n)))
+        return buf[:n.value].tobytes()
+
+    def targetAccumulateImport(self, blob):
+        """The voxels of a blob into the accumulated target (ndt_target_accumulate_import): an accumulate call whose input is
+        voxels.  A handle without an accumulated target starts one; every cell of the blob must be absent from the target.
+        Returns targetAccumulated()."""
+        b = np.frombuffer(bytes(blob), dtype=np.uint8)
+        check(self._L.ndt_target_accumulate_import(self._h, b.ctypes.data if len(b) else None, len(b)))
+        return self.targetAccumulated()
+
+    def targetAccumulateSave(self, path, min_xyz=None, max_xyz=None):
+        """targetAccumulateExport into the file `path` (written beside it and renamed)."""
+        mn, mx = self._box(min_xyz, max_xyz)
+        check(self._L.ndt_target_accumulate_save(self._h, _f(mn) if mn is not None else None, _f(mx) if mx is not None else None,
+                                                 os.fsencode(path)))
+
+    def targetAccumulateLoad(self, path):
+        """targetAccumulateImport of the file `path`.  Returns targetAccumulated()."""
+        check(self._L.ndt_target_accumulate_load(self._h, os.fsencode(path)))
+        return self.targetAccumulated()
+
+    def targetExportDiag(self):
+        """What the last targetAccumulateExport / Save did (ndt_diag_target_export)."""
+        v, p, l = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        check(self._L.ndt_diag_target_export(self._h, C.byref(v), C.byref(p), C.byref(l)))
+        return dict(voxels=v.value, points=p.value, launches=l.value)
+
     # ---- batch (map-build) ---------------------------------------------------------
     def alignBatch(self, clouds=None, guesses=None, device_ptr=None, offsets=None, stride_bytes=16):
         """Register many sources against the one target in lock-step.
@@ -1002,6 +1048,36 @@ def crop_cell_centre(resolution, cell):
     """(cell + 0.5f) * leaf in f32: the float a cropped target carries for a corner cell of its box; it floors back to the
     cell on the lattice of pitch `resolution` for every cell of [-2^20, 2^20)."""
     return (np.asarray(cell).astype(np.float32) + np.float32(0.5)) * np.float32(resolution)
+
+
+# a row of an exported accumulated target (include/ndt_mi355.h): the absolute cell, the count, the f64 sums sx sy sz cxx cxy cxz
+# cyy cyz czz (Identity seed included), the f32 centroid sums, a zero
+ACC_ROW_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("k", "<i4"), ("count", "<i4"), ("d", "<f8", (9,)), ("f", "<f4", (3,)), ("pad", "<f4")])
+ACC_BLOB_HEADER_BYTES = 64
+
+
+def acc_blob_info(blob):
+    """Header of a blob that passes the device-free checks (ndt_host_acc_blob_info; NdtError otherwise)
+    -> dict(resolution, n_voxels, lo, hi)."""
+    b = np.frombuffer(bytes(blob), dtype=np.uint8)
+    res, n = C.c_float(0), C.c_size_t(0)
+    lo, hi = np.zeros(3, np.int32), np.zeros(3, np.int32)
+    check(_lib.lib().ndt_host_acc_blob_info(b.ctypes.data if len(b) else None, len(b), C.byref(res), C.byref(n), _i(lo), _i(hi)))
+    return dict(resolution=res.value, n_voxels=n.value, lo=lo, hi=hi)
+
+
+def acc_blob_checksum(data):
+    """The blob's hash over the 8-byte words of `data` (ndt_host_acc_blob_checksum): a blob's checksum field is this of its
+    bytes [0, 56) followed by its rows."""
+    b = np.frombuffer(bytes(data), dtype=np.uint8)
+    out = C.c_uint64(0)
+    check(_lib.lib().ndt_host_acc_blob_checksum(b.ctypes.data if len(b) else None, len(b), C.byref(out)))
+    return out.value
+
+
+def acc_blob_rows(blob):
+    """The rows of a blob as a structured array (ACC_ROW_DTYPE), a read-only view of its bytes; the header is not checked."""
+    return np.frombuffer(blob, dtype=ACC_ROW_DTYPE, offset=ACC_BLOB_HEADER_BYTES)
 
 
 def host_thread_budget():
