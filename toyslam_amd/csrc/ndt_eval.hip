@@ -494,13 +494,7 @@ ndt_status ndt_align(ndt_handle h, const float* guess, float* final_transformati
     // cloud there itself; any other path copies it over
     if (!(wrote_host_copy)) HIP_TRY(hipMemcpyAsync(h->out_pinned, h->out_cloud.p, bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    if (out_stride_bytes == sizeof(float4)) {
-      std::memcpy(out_cloud, h->out_pinned, bytes);
-    } else {
-      const unsigned char* src = static_cast<const unsigned char*>(h->out_pinned);
-      unsigned char* dst = static_cast<unsigned char*>(out_cloud);
-      for (int i = 0; i < n; i++) std::memcpy(dst + static_cast<size_t>(i) * out_stride_bytes, src + static_cast<size_t>(i) * sizeof(float4), sizeof(float4));
-    }
+    spread_records(h->out_pinned, static_cast<size_t>(n), out_cloud, out_stride_bytes);
   }
   // without a host copy nothing waits here: the cloud is complete in stream order (ndt_get_output_device
   // synchronises before handing the pointer out)

@@ -78,8 +78,9 @@ ndt_status composite_pass(ndt_handle h, const float4* block, const std::vector<B
   const size_t w_boxes = static_cast<size_t>(total_cells), w_ranges = w_boxes + 12 * nd, w_totals = w_ranges + 2 * nd, n_words = w_totals + 4;
   const size_t desc_bytes = nd * sizeof(ndt::FilterBatchCloud), seg_bytes = nd * sizeof(ndt::SegDesc);
   const size_t back_bytes = (n_words - w_boxes) * sizeof(unsigned);
-  DevBuf<unsigned> work, block_sums, leaf_start, rank;
-  DevBuf<int> key, leaf_cell, leaf_count, leaf_rec, sorted_idx;
+  DevBuf<unsigned> work, rank;
+  DevBuf<int> key;
+  ChainBufs lv;
   DevBuf<float4> big_pts;
   DevBuf<unsigned char> d_desc;
   HIP_TRY(d_desc.reserve(desc_bytes + seg_bytes));
@@ -99,27 +100,18 @@ ndt_status composite_pass(ndt_handle h, const float4* block, const std::vector<B
   const ndt::FilterBatchCloud* d_cl = reinterpret_cast<const ndt::FilterBatchCloud*>(d_desc.p);
   const ndt::SegDesc* d_seg = reinterpret_cast<const ndt::SegDesc*>(d_desc.p + desc_bytes);
   const size_t n_leaves = std::min<size_t>(members_pts, static_cast<size_t>(total_cells));  // upper bound; the count stays on the device
-  const int n_tiles = ndt::scan_tiles(total_cells);
   HIP_TRY(key.reserve(span));
   HIP_TRY(rank.reserve(span));
-  HIP_TRY(block_sums.reserve(static_cast<size_t>(n_tiles) * 3));
-  HIP_TRY(leaf_cell.reserve(n_leaves));
-  HIP_TRY(leaf_start.reserve(n_leaves));
-  HIP_TRY(leaf_count.reserve(n_leaves));
-  HIP_TRY(leaf_rec.reserve(n_leaves));
-  HIP_TRY(sorted_idx.reserve(members_pts));
+  HIP_TRY(lv.reserve(n_leaves, members_pts));
   HIP_TRY(big_pts.reserve(members_pts));  // scratch of the crowded-voxel path (k_presort_large)
   const float4* pts = block + in[s0].first;
   unsigned* totals = work.p + w_totals;
   HIP_TRY(hipMemcpyAsync(d_desc.p, h->fb_pinned, desc_bytes + seg_bytes, hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemsetAsync(work.p, 0, w_ranges * sizeof(unsigned), st));  // the counters and the box words
   HIP_TRY(ndt::launch_count_multi(pts, d_cl, static_cast<int>(nd), static_cast<int>(max_n), key.p, rank.p, work.p, st));
-  HIP_TRY(ndt::launch_scan_reduce(work.p, total_cells, 1, block_sums.p, n_tiles, st));
-  HIP_TRY(ndt::launch_scan_blocks(block_sums.p, n_tiles, totals, st));
-  HIP_TRY(ndt::launch_scan_apply(work.p, total_cells, 1, block_sums.p, n_tiles, leaf_cell.p, leaf_start.p, leaf_count.p, leaf_rec.p, st));
-  HIP_TRY(ndt::launch_scatter(key.p, rank.p, static_cast<int>(span), work.p, sorted_idx.p, st));
-  HIP_TRY(ndt::launch_voxel_centroids(pts, leaf_start.p, leaf_count.p, static_cast<int>(n_leaves), sorted_idx.p, blk->pts.p, st, totals, big_pts.p));
-  HIP_TRY(ndt::launch_leaf_ranges(leaf_cell.p, totals, d_cl, static_cast<int>(nd), work.p + w_ranges, st));
+  if ((s = chain_scan_scatter(st, work.p, total_cells, 1, key.p, rank.p, static_cast<int>(span), lv.out(), totals))) return s;
+  HIP_TRY(ndt::launch_voxel_centroids(pts, lv.leaf_start.p, lv.leaf_count.p, static_cast<int>(n_leaves), lv.sorted_idx.p, blk->pts.p, st, totals, big_pts.p));
+  HIP_TRY(ndt::launch_leaf_ranges(lv.leaf_cell.p, totals, d_cl, static_cast<int>(nd), work.p + w_ranges, st));
   HIP_TRY(ndt::launch_repack_bbox_multi(d_seg, static_cast<int>(nd), max_n, work.p + w_boxes, st));
   HIP_TRY(hipMemcpyAsync(h->fb_pinned, work.p + w_boxes, back_bytes, hipMemcpyDeviceToHost, st));
   h->fb_launches += 12;

@@ -23,6 +23,36 @@ static int fitness_chunk_blocks() {
   return v;
 }
 
+// [PCL] Registration::getFitnessScore of the dense device cloud d_src moved by T against the target of the grid g (on h's
+// stream, with h's scratch)
+ndt_status fitness_against(ndt_context* h, DeviceGrid* g, const float4* d_src, int n, const float* T_colmajor, double max_range,
+                           double* fitness) {
+  if (g->accumulated) return fail(NDT_ERR_NO_INPUT, "getFitnessScore needs the target's points: an accumulated target keeps none");
+  *fitness = std::numeric_limits<double>::max();  // nr == 0 in the reference
+  ndt_status s = grid_counts(h, g);
+  if (s) return s;
+  if (n == 0 || g->empty || g->n_sorted == 0) return NDT_OK;
+  s = ensure_cell2leaf(h, g);
+  if (s) return s;
+  s = ensure_host_rows(h, 1);
+  if (s) return s;
+  float T12[12];
+  colmajor_to_T12(T_colmajor, T12);
+  const int nblk = fitness_blocks(n);
+  HIP_TRY(h->partials.reserve(static_cast<size_t>(nblk) * ndt::kEvalStride));
+  ndt::PointIndex ix;
+  fill_point_index(g, ix);
+  HIP_TRY(ndt::launch_fitness(d_src, n, T12, ix, max_range, nblk, h->partials.p, h->stream));
+  HIP_TRY(ndt::launch_reduce(h->partials.p, nblk, 1, nullptr, h->host_result, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (h->host_result[1] > 0) *fitness = h->host_result[0] / h->host_result[1];
+  return NDT_OK;
+}
+// ... against h's own target
+ndt_status fitness_impl(ndt_context* h, const float4* d_src, int n, const float* T_colmajor, double max_range, double* fitness) {
+  return fitness_against(h, h->grid.get(), d_src, n, T_colmajor, max_range, fitness);
+}
+
 ndt_status fitness_many(ndt_context* h, const std::vector<FitnessJob>& jobs, double max_range, double* out) {
   for (size_t k = 0; k < jobs.size(); k++) out[k] = std::numeric_limits<double>::max();  // nr == 0 in the reference
   h->fit_launches = 0;
@@ -123,6 +153,13 @@ static ndt_status batch_fitness_impl(ndt_handle h, const void* pts, const size_t
 }  // namespace ndtc
 
 extern "C" {
+
+ndt_status ndt_get_fitness_score(ndt_handle h, double max_range, double* fitness) {
+  if (!h || !fitness) return fail(NDT_ERR_INVALID, "bad arguments");
+  ndt_status s = check_ready(h);
+  if (s) return s;
+  return fitness_impl(h, h->source->pts.p, static_cast<int>(h->source->n), h->final_T, max_range, fitness);
+}
 
 ndt_status ndt_pairs_fitness_scores(ndt_handle h, const float* transforms, double max_range, double* fitness) {
   if (!h) return fail(NDT_ERR_INVALID, "null handle");

@@ -1,10 +1,12 @@
 // ndt_internal.hpp -- state shared by the translation units behind the C-ABI (include/ndt_mi355.h,
 // include/gicp_mi355.h): error reporting, the caching device allocator, device clouds / grids, the handle
 // itself, and the helpers one unit offers the others.  Not installed; nothing here crosses the C-ABI.
-//   ndt_handle.hip : handle lifetime, parameters, results, profiling switches, host-only scalar exports
-//   ndt_grid.hip   : cloud upload, bounding boxes, spatial ordering, K1 target grid build (dense / sparse index),
-//                    N1 voxel filter, N2 map accumulation, getFitnessScore, calculateScore (of a cloud, of the source under
-//                    many poses), grid inspection
+//   ndt_handle.hip : handle lifetime, parameters, results, profiling switches, host-only scalar exports, ndt_warm_up
+//   ndt_clouds.hip : cloud upload and download, bounding boxes, spatial ordering, the ndt_cloud handles, the source setters
+//   ndt_grid.hip   : the cell chain and the sparse index every cell-sorting caller shares, K1 target grid build, counts and
+//                    search index of a built grid, the target setters, grid inspection
+//   ndt_filter.hip : N1 voxel filter of one cloud (ndt_filter_batch.hip: of many)      ndt_map_batch.hip : N2 map accumulation
+//   ndt_fitness.hip : getFitnessScore      ndt_score.hip : calculateScore (of a cloud, of the source under many poses)
 //   ndt_eval.hip   : one evaluation (launch path), the persistent evaluation server's host side (mailbox protocol),
 //                    ndt_align, ndt_eval*, diagnostics and self-tests
 //   ndt_batch.hip  : lock-step batches (ndt_align_batch*, ndt_align_guesses, ndt_align_multistart), the RCCL communicator
@@ -453,7 +455,7 @@ struct ndt_context {
   void* mb_pinned = nullptr;
   size_t mb_pinned_bytes = 0;
   size_t mb_transform_launches = 0, mb_filters = 0, mb_box_passes = 0;
-  // ndt_score_poses (ndt_grid.hip): the pose table of one chunk (12 row-major floats per pose) in page-locked memory and in
+  // ndt_score_poses (ndt_score.hip): the pose table of one chunk (12 row-major floats per pose) in page-locked memory and in
   // HBM, and what the last call did (ndt_diag_score_poses)
   void* sp_pinned = nullptr;
   size_t sp_pinned_bytes = 0;
@@ -545,7 +547,12 @@ ndt::SolverParams solver_params(const ndt_context* h);
 // page-locked scratch of a handle, grown on demand; `reader`: the stream whose queued copies may still read the old block
 // (waited for before it is freed).  Rewriting the block is the caller's to order: only behind a wait for what reads it
 ndt_status pinned_at_least(void*& p, size_t& have, size_t bytes, hipStream_t reader);
-// ---- ndt_grid.hip
+struct PoolStreamGuard {  // temporaries allocated (and given back) inside the scope belong to `s`'s pool
+  hipStream_t keep;
+  explicit PoolStreamGuard(hipStream_t s) : keep(tls_pool_stream) { tls_pool_stream = s; }
+  ~PoolStreamGuard() { tls_pool_stream = keep; }
+};
+// ---- ndt_clouds.hip
 ndt_status upload_cloud(ndt_context* h, const void* pts, size_t n, size_t stride, bool on_device,
                         std::shared_ptr<DeviceCloud>& out, bool by_reference = false);
 struct BBox {
@@ -557,6 +564,32 @@ ndt_status order_range(ndt_context* h, const float4* d_pts, size_t n, float pitc
                        const BBox* known_bbox = nullptr);
 ndt_status order_batch(ndt_context* h, DeviceCloud* c, const size_t* offsets, size_t n_scans);
 ndt_status order_cloud(ndt_context* h, DeviceCloud* c, const size_t* offsets, size_t n_scans);
+ndt_status download_records(ndt_context* h, const float4* d_src, size_t n, void* out, size_t out_stride);
+ndt_status out_block_at_least(ndt_context* h, size_t bytes);  // h->out_pinned, page-locked: grown behind a wait for h->stream
+void spread_records(const void* src, size_t n, void* out, size_t out_stride);  // n float4 records into records of out_stride bytes
+ndt_status cloud_use_on(ndt_handle h, DeviceCloud* c);  // an ndt_cloud made on another stream: wait for it, remember the reader
+// ---- ndt_grid.hip
+// The general cell chain sorts points by cell.  The caller counts into per-cell counters (launch_count, _count_batch or
+// _count_multi: key and rank per point); chain_scan (scan_reduce, scan_blocks, scan_apply) turns them into start offsets and
+// numbers the occupied cells (the leaves; leaf_rec: the record of those with min_pts), the totals {points, leaves,
+// candidates} staying on the device at `totals`; chain_scan_scatter also writes the points' indices in cell order.
+struct ChainOut { int* leaf_cell; unsigned* leaf_start; int *leaf_count, *leaf_rec, *sorted_idx; };
+struct ChainBufs {  // the five arrays, owned: sized for the worst case, since the leaf count stays on the device
+  DevBuf<int> leaf_cell, leaf_count, leaf_rec, sorted_idx;
+  DevBuf<unsigned> leaf_start;
+  hipError_t reserve(size_t max_leaves, size_t n_points) {
+    for (hipError_t e : {leaf_cell.reserve(max_leaves), leaf_start.reserve(max_leaves), leaf_count.reserve(max_leaves), leaf_rec.reserve(max_leaves), sorted_idx.reserve(n_points)})
+      if (e != hipSuccess) return e;
+    return hipSuccess;
+  }
+  ChainOut out() const { return ChainOut{leaf_cell.p, leaf_start.p, leaf_count.p, leaf_rec.p, sorted_idx.p}; }
+};
+ndt_status chain_scan(hipStream_t st, unsigned* counters, long long n_cells, int min_pts, const ChainOut& o, unsigned* totals);
+ndt_status chain_scan_scatter(hipStream_t st, unsigned* counters, long long n_cells, int min_pts, const int* key, const unsigned* rank,
+                              int n, const ChainOut& o, unsigned* totals);
+// the same five arrays by sorting (cell, point) pairs (ndt_sparse.hip): per-point work only, the cell space is never walked
+ndt_status sparse_index(hipStream_t st, const float4* pts, int n, int dense, const ndt::GridGeom& geo, int min_pts, const ChainOut& o,
+                        unsigned* counts);
 // What a voxel grid is built with, apart from the cloud: a handle's settings (grid_spec_of) or a caller's own (GICP's point
 // index: index_only -- cells and their point lists, no per-voxel statistics)
 struct GridSpec {
@@ -587,8 +620,8 @@ ndt_status grid_counts(ndt_context* h, DeviceGrid* g);
 ndt_status ensure_cell2leaf(ndt_context* h, DeviceGrid* g);
 ndt_status ensure_indices(ndt_context* h, const std::vector<DeviceGrid*>& grids);  // both of the above for many grids, two waits in all
 float index_slack(const DeviceGrid* g);
-ndt_status download_records(ndt_context* h, const float4* d_src, size_t n, void* out, size_t out_stride);
 void fill_point_index(const DeviceGrid* g, ndt::PointIndex& ix);
+// ---- ndt_fitness.hip
 ndt_status fitness_impl(ndt_context* h, const float4* d_src, int n, const float* T_colmajor, double max_range, double* fitness);
 // the same against a grid the caller names instead of h->grid (GICP: the target input's index)
 ndt_status fitness_against(ndt_context* h, DeviceGrid* g, const float4* d_src, int n, const float* T_colmajor, double max_range,
@@ -605,6 +638,7 @@ ndt_status fitness_many(ndt_context* h, const std::vector<FitnessJob>& jobs, dou
 // blocks of getFitnessScore over n source points (k_fitness's grid, a member's blocks of k_fitness_multi): 32 query teams per
 // block, at most 2048 blocks (the teams then stride over the queries)
 inline int fitness_blocks(int n) { return std::max(1, std::min(2048, (n + 31) / 32)); }
+// ---- ndt_filter.hip
 ndt_status filter_slots(ndt_handle h, int which, FilterPending& P);
 // The geometry and route of one N1 filter, from the cloud's box alone -- the one decision voxel_filter_enqueue and the
 // batched filter (ndt_filter_batch.hip) both take: no finite point, PCL's index overflow (copy-through), the sparse index
@@ -617,6 +651,10 @@ FilterRoute filter_route(const ndt_context* h, size_t n, const BBox& bb, float l
 ndt_status voxel_filter_enqueue(ndt_handle h, hipStream_t st, const float4* d_in, size_t n, int is_dense, float leaf, float4* d_out,
                                 const BBox& bb, FilterPending& P);
 void voxel_filter_finish(const FilterPending& P, size_t* n_out, DeviceCloud* boxes);
+// out_boxes: the result's bounding boxes as DeviceCloud keeps them ([2][3] min, [2][3] max), or null
+ndt_status voxel_filter_device(ndt_handle h, const float4* d_in, size_t n, int is_dense, float leaf, float4* d_out,
+                               size_t* n_out, bool* overflow, const BBox* known_bbox = nullptr, DeviceCloud* out_boxes = nullptr);
+// ---- ndt_map_batch.hip
 // N2 of a list of resident scans in one pass (the single ndt_map_update* are the list of one): scan k moved by its pose
 // (16 column-major floats, null = identity) behind the map, in the list's order, then one filter of the concatenation
 struct MapScan {
@@ -630,10 +668,7 @@ struct MapBatchDiag {
 ndt_status map_update_scans(ndt_handle h, const std::vector<MapScan>& scans, float leaf, int* overflowed, MapBatchDiag* diag);
 // the map's stream exists and a queued update has been waited for: map_n, the boxes and h->mb_pinned are the handle's again
 ndt_status map_settle(ndt_handle h);
-ndt_status cloud_use_on(ndt_handle h, DeviceCloud* c);  // an ndt_cloud made on another stream: wait for it, remember the reader
-// out_boxes: the result's bounding boxes as DeviceCloud keeps them ([2][3] min, [2][3] max), or null
-ndt_status voxel_filter_device(ndt_handle h, const float4* d_in, size_t n, int is_dense, float leaf, float4* d_out,
-                               size_t* n_out, bool* overflow, const BBox* known_bbox = nullptr, DeviceCloud* out_boxes = nullptr);
+ndt_status map_complete(ndt_handle h);  // ... the wait alone (ndt_warm_up: no stream is made for a handle that has no map)
 // ---- ndt_accumulate.hip
 bool acc_is_live(const ndt_context* h);  // the handle's target is an accumulated one
 void acc_drop(ndt_context* h);           // forget it (the handle is left without a target if it was live)
