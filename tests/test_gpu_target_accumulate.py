@@ -271,6 +271,23 @@ def test_table_and_slot_growth(mods, monkeypatch, voxel_index):
     assert st["voxels"] >= 200 and grown[1] and grown[2]
 
 
+def test_slots_grow_while_the_key_table_holds(mods, monkeypatch):
+    ndt, po, clouds, _ = mods
+    monkeypatch.setenv("NDT_ACC_HASH_BITS", "10")   # 1024 keys: at most half full up to 512 voxels
+    monkeypatch.setenv("NDT_ACC_SLOTS", "16")
+    rng = np.random.default_rng(6)
+    u = [slab(rng, [4 * k, 0, 0], [4 * k + 3.99, 4.99, 0.99], 400) for k in range(2)]   # 20 voxels each: 32 slots, then 64
+    src = slab(rng, [0, 0, 0], [8, 5, 1], 200)
+    g = handle(ndt)
+    g.targetAccumulate(u[0])
+    assert not g.targetAccumulateDiag()["table_grown"]           # (nothing to copy yet)
+    st = g.targetAccumulate(u[1])
+    d = g.targetAccumulateDiag()
+    assert st["voxels"] == 40 and d["new_voxels"] == 20 and d["table_grown"]
+    assert d["launches"] == 1 + 7 + 2 + int(d["relinked"])       # the slot arrays are copied; no rehash launch
+    Ref(mods, np.concatenate(u), src).check(g)
+
+
 # ---- 6: is_dense = 0 with NaN / inf rows
 def test_non_finite_rows_and_empty_clouds(mods):
     ndt, po, clouds, _ = mods

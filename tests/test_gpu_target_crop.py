@@ -275,6 +275,26 @@ def test_plan_boundaries(mods, monkeypatch, kept, small):
     Ref(mods, hist.cat(), src, min_pts=min_pts).check(g)
 
 
+def test_key_table_grows_while_the_slots_hold(mods, monkeypatch):
+    ndt, po, clouds, _ = mods
+    monkeypatch.setenv("NDT_ACC_SLOTS", "16")
+    monkeypatch.setenv("NDT_ACC_HASH_BITS", "2")
+    rng = np.random.default_rng(11)
+    cloud = lattice_cloud(rng, 5)
+    src = np.c_[rng.random(100) * 5, rng.random(100), rng.random(100)].astype(np.float32)
+    g = handle(ndt)
+    hist = History(ndt)
+    g.targetAccumulate(cloud)
+    hist.add(cloud)
+    d = crop_both(g, hist, [-INF, -INF, -INF], [0.5, INF, INF])      # one voxel stays: 16 slots again, but a key table of 4
+    assert d["kept_voxels"] == 1
+    g.targetAccumulate(cloud)                                       # 5 voxels: the slots hold them, 2 * 5 > 4
+    hist.add(cloud)
+    d = g.targetAccumulateDiag()
+    assert d["table_grown"] and d["launches"] == 1 + 7 + 2 + int(d["relinked"]) + 1   # the rehash launch; no slot copy
+    Ref(mods, hist.cat(), src).check(g)
+
+
 # ---- 7: rejected voxels, voxels under min_pts and valid ones, kept and removed
 def test_voxel_states_survive(mods):
     ndt, po, clouds, _ = mods

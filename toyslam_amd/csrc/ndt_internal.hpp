@@ -60,6 +60,7 @@ inline ndt_status fail(ndt_status s, const std::string& msg) {
     if (_e != hipSuccess)                                                                          \
       return fail(NDT_ERR_HIP, std::string(#expr) + " failed: " + hipGetErrorString(_e));          \
   } while (0)
+#define HIP_PASS(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)  // where hipError_t is returned
 
 // Caching device allocator: setInputTarget / setInputSource run once per scan in the nodes, and a
 // dozen hipMalloc/hipFree pairs per call (~100 us each) would dominate the GPU time of the grid
