@@ -702,6 +702,31 @@ ndt_status ndt_diag_stamps(ndt_handle h, const double* p, unsigned long long* st
 ndt_status ndt_diag_eval_plan(ndt_handle h, size_t n, int* ppb, int* fused_blocks, int* launch_blocks, int* server_blocks,
                               int* batch_blocks);
 
+/* The plan of a target-grid build of n_points points over a lattice of n_cells cells (ndt_host_lattice), as build_grid and
+ * the launches decide it.  Host only; the values come from the functions the build itself calls (the NDT_K1_* development
+ * switches included).  *bucket_form: the grid is within the bucket form's range (a dense voxel index then takes it; beyond, the
+ * dense chain of count / scan / scatter / k_finalize builds it); *n_buckets K and *cells_per_bucket C: the cell space dealt
+ * to K buckets of C cells (bucket = (cell >> 3) mod K); *pts_per_block and *n_blocks: the blocks of the two point passes
+ * (n_blocks is a multiple of eight, trailing blocks may be empty); *one_launch: the cloud is small enough for the one-launch
+ * form; *wmax and *lds_cap: cells one pass of the bucket form's finish may span and points it holds in LDS.  With div_b (the
+ * lattice's cells per axis; may be NULL, the following are then 0): *lut_cells the padded look-up table's size, and the record
+ * compaction's tiles over it: *compact_items table entries per thread (1, 2, 4, 8), *compact_tiles tiles, *compact_prefix
+ * whether the separate prefix pass over the tile sums runs.  *filter_buckets: the voxel filter of such a cloud (dense route)
+ * runs on the bucket front end, *filter_chunks: blocks of its bitmap prefix pass.  Any output may be NULL. */
+ndt_status ndt_host_grid_plan(long long n_cells, long long n_points, const int* div_b /*3 or NULL*/, int* bucket_form, int* n_buckets,
+                              int* cells_per_bucket, int* pts_per_block, int* n_blocks, int* one_launch, int* wmax, int* lds_cap,
+                              long long* lut_cells, int* compact_items, long long* compact_tiles, int* compact_prefix,
+                              int* filter_buckets, int* filter_chunks);
+/* Diagnostic: what built the handle's current target grid.  *form: 0 nothing (an empty grid, an accumulated target), 1 the dense
+ * chain (count / scan / scatter / k_finalize), 2 the bucket form, 3 the one-launch form of small clouds, 4 the sparse index.
+ * The plan the build stored (forms 2 and 3; pts_per_block and n_blocks: form 2) and the finish's *wmax / *lds_cap as in
+ * ndt_host_grid_plan (form 3: the one-launch kernel's own cap); *lut_cells and the compaction's tile plan for a grid with a
+ * dense table (forms 1 to 3, else 0); *compact_pending: the records still carry the build's numbering and will be compacted
+ * before the second registration.  No device work.  Any output may be NULL. */
+ndt_status ndt_diag_grid_build(ndt_handle h, int* form, size_t* n_points, long long* n_cells, int* n_buckets, int* cells_per_bucket,
+                               int* pts_per_block, int* n_blocks, int* wmax, int* lds_cap, long long* lut_cells, int* compact_items,
+                               long long* compact_tiles, int* compact_prefix, int* compact_pending);
+
 /* Diagnostic: round-trip latency of the persistent evaluation server, averaged over n_iter commands:
  * us[0] = no-op round (protocol only), us[1] = derivatives without Hessian, us[2] = with Hessian. */
 ndt_status ndt_diag_server_roundtrip(ndt_handle h, const double* p, int n_iter, double* us);

@@ -154,6 +154,10 @@ SIGNATURES = {
     "ndt_grid_dump": (C.c_int, [vp, C.POINTER(C.c_int64), ip, dp, dp, dp, dp]),
     "ndt_diag_stamps": (C.c_int, [vp, dp, C.POINTER(C.c_ulonglong), szp]),
     "ndt_diag_eval_plan": (C.c_int, [vp, C.c_size_t, ip, ip, ip, ip, ip]),
+    "ndt_host_grid_plan": (C.c_int, [C.c_longlong, C.c_longlong, ip, ip, ip, ip, ip, ip, ip, ip, ip, C.POINTER(C.c_longlong), ip,
+                                     C.POINTER(C.c_longlong), ip, ip, ip]),
+    "ndt_diag_grid_build": (C.c_int, [vp, ip, szp, C.POINTER(C.c_longlong), ip, ip, ip, ip, ip, ip, C.POINTER(C.c_longlong), ip,
+                                      C.POINTER(C.c_longlong), ip, ip]),
     "ndt_diag_server_roundtrip": (C.c_int, [vp, dp, C.c_int, dp]),
     "ndt_diag_selfdrive": (C.c_int, [vp, dp, C.c_int, dp]),
     "ndt_selftest_reduce": (C.c_int, [vp, C.c_int, dp]),

@@ -28,6 +28,16 @@ FilterRoute filter_route(const ndt_context* h, size_t n, const BBox& bb, float l
   return r;
 }
 
+bool filter_takes_buckets(long long n_cells, long long n, ndt::GridBuildPlan& plan) {
+  static const bool vf_buckets = [] { const char* v = getenv("NDT_VF"); return !(v && std::strcmp(v, "chain") == 0); }();
+  // (from 128 k points and for boxes with at most four cells per point: below / beyond, a bucket's share of the cell space --
+  // thousands of cells for a hundred points -- makes vf_finalize cost what the chain's scans cost: 60 k points 81 against 76 us,
+  // a 250 k-point map 29 us for that kernel alone; 300 k-point scan 81 against 111, 1 M 106 against 228.  NDT_VF_FROM=0: always.)
+  static const long long vf_from = [] { const char* v = getenv("NDT_VF_FROM"); return v ? static_cast<long long>(std::max(0, atoi(v))) : 131072ll; }();
+  const bool vf_dense = vf_from == 0 || (n >= vf_from && n_cells <= 4ll * n);
+  return vf_buckets && vf_dense && n <= 0x7fffffffll && ndt::filter_buckets_plan(n_cells, static_cast<int>(n), plan);
+}
+
 ndt_status voxel_filter_enqueue(ndt_handle h, hipStream_t st, const float4* d_in, size_t n, int is_dense, float leaf, float4* d_out,
                                 const BBox& bb, FilterPending& P) {
   P.n_max = n;
@@ -71,14 +81,8 @@ ndt_status voxel_filter_enqueue(ndt_handle h, hipStream_t st, const float4* d_in
   // Dense grids within the bucket plan's range: the order-preserving bucket front end of K1 + vf_finalize / vf_bitmap_prefix /
   // vf_place (ndt_grid_kernels.hip): the cell space is never walked, no point is gathered through an index.
   // NDT_VF=chain: the general chain below for every grid (the cross-check).
-  static const bool vf_buckets = [] { const char* v = getenv("NDT_VF"); return !(v && std::strcmp(v, "chain") == 0); }();
   ndt::GridBuildPlan plan{};
-  // (from 128 k points and for boxes with at most four cells per point: below / beyond, a bucket's share of the cell space --
-  // thousands of cells for a hundred points -- makes vf_finalize cost what the chain's scans cost: 60 k points 81 against 76 us,
-  // a 250 k-point map 29 us for that kernel alone; 300 k-point scan 81 against 111, 1 M 106 against 228.  NDT_VF_FROM=0: always.)
-  static const long long vf_from = [] { const char* v = getenv("NDT_VF_FROM"); return v ? static_cast<long long>(std::max(0, atoi(v))) : 131072ll; }();
-  const bool vf_dense = vf_from == 0 || (static_cast<long long>(n) >= vf_from && geo.n_cells <= 4ll * static_cast<long long>(n));
-  if (vf_buckets && vf_dense && ndt::filter_buckets_plan(geo.n_cells, ni, plan)) {
+  if (filter_takes_buckets(geo.n_cells, static_cast<long long>(n), plan)) {
     const size_t K = static_cast<size_t>(plan.n_buckets);
     const size_t bw = ndt::filter_buckets_bitmap_words(geo.n_cells);
     DevBuf<unsigned> cntmat, order, bucket_base, bitmap, wprefix;

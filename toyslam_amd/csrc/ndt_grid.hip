@@ -123,6 +123,7 @@ static ndt_status setup_bucket_form(const GridSpec& spec, const GridHead& hd, co
   HIP_TRY(g->bpts.reserve(n));
   HIP_TRY(scratch.reserve(5 * n));
   g->plan = plan;
+  g->build_form = D ? 3 : 2;
   g->leaves_pending = true;  // leaf arrays and the occupied / candidate counts: on demand (grid_counts)
   g->counts_known = false;
   g->empty = false;
@@ -224,6 +225,7 @@ ndt_status build_grid(ndt_context* h, const std::shared_ptr<DeviceCloud>& cloud,
                                  g->counts.p, big_pts.p));
     g->counts_known = false;
     g->empty = false;
+    g->build_form = 4;
     out = g;
     return NDT_OK;
   }
@@ -268,6 +270,7 @@ ndt_status build_grid(ndt_context* h, const std::shared_ptr<DeviceCloud>& cloud,
   } else {
   // every cell of the padded table starts out empty (kLutEmpty = -1 = all bits set); the finalize pass fills in the
   // voxels that reached min_points_per_voxel
+  g->build_form = 1;
   HIP_TRY(reserve_leaves(hd));
   HIP_TRY(g->lut.reserve(static_cast<size_t>(geo.lut_cells)));
   HIP_TRY(hipMemsetAsync(g->lut.p, 0xFF, static_cast<size_t>(geo.lut_cells) * sizeof(int), st));
@@ -667,6 +670,79 @@ ndt_status ndt_host_lattice(float leaf, const float* mn, const float* mx, int* m
   }
   if (n_cells) *n_cells = geo.n_cells;
   if (sparse) *sparse = ndt::wants_sparse_index(voxel_index, geo.n_cells, n_points) ? 1 : 0;
+  return NDT_OK;
+}
+
+// the host side of a build's plan: what build_grid, the bucket launches and the record compaction would decide
+ndt_status ndt_host_grid_plan(long long n_cells, long long n_points, const int* div_b, int* bucket_form, int* n_buckets, int* cells_per_bucket,
+                              int* pts_per_block, int* n_blocks, int* one_launch, int* wmax, int* lds_cap, long long* lut_cells,
+                              int* compact_items, long long* compact_tiles, int* compact_prefix, int* filter_buckets, int* filter_chunks) {
+  if (n_cells < 0 || n_points < 0 || n_points > 0x7fffffffll) return fail(NDT_ERR_INVALID, "bad arguments");
+  ndt::GridBuildPlan plan{};
+  const bool ok = ndt::grid_build_plan(n_cells, static_cast<int>(n_points), plan);
+  const ndt::K1FinishLds F = ok ? ndt::grid_build_finish_lds(plan.cells_per_bucket) : ndt::K1FinishLds{};
+  if (bucket_form) *bucket_form = ok ? 1 : 0;
+  if (n_buckets) *n_buckets = ok ? plan.n_buckets : 0;
+  if (cells_per_bucket) *cells_per_bucket = ok ? plan.cells_per_bucket : 0;
+  if (pts_per_block) *pts_per_block = ok ? plan.pts_per_block : 0;
+  if (n_blocks) *n_blocks = ok ? plan.n_blocks : 0;
+  if (one_launch) *one_launch = ok && ndt::grid_build_small_applies(static_cast<int>(n_points), plan) ? 1 : 0;
+  if (wmax) *wmax = F.wmax;
+  if (lds_cap) *lds_cap = F.lds_cap;
+  long long lc = 0;
+  if (div_b) {
+    if (div_b[0] <= 0 || div_b[1] <= 0 || div_b[2] <= 0) return fail(NDT_ERR_INVALID, "bad arguments");
+    ndt::GridGeom geo{};
+    for (int k = 0; k < 3; k++) {
+      geo.div_b[k] = div_b[k];
+      geo.leaf[k] = 1.0f;
+    }
+    ndt::set_padded_lut(geo);
+    lc = geo.lut_cells;
+  }
+  if (lut_cells) *lut_cells = lc;
+  if (compact_items) *compact_items = lc ? ndt::record_compaction_items(lc) : 0;
+  if (compact_tiles) *compact_tiles = lc ? static_cast<long long>(ndt::record_compaction_tiles(lc)) : 0;
+  if (compact_prefix) *compact_prefix = lc && ndt::record_compaction_prefix(lc) ? 1 : 0;
+  ndt::GridBuildPlan fplan{};
+  const bool fb = n_cells > 0 && filter_takes_buckets(n_cells, n_points, fplan);
+  if (filter_buckets) *filter_buckets = fb ? 1 : 0;
+  if (filter_chunks) *filter_chunks = fb ? ndt::filter_buckets_chunks(n_cells) : 0;
+  return NDT_OK;
+}
+
+ndt_status ndt_diag_grid_build(ndt_handle h, int* form, size_t* n_points, long long* n_cells, int* n_buckets, int* cells_per_bucket,
+                               int* pts_per_block, int* n_blocks, int* wmax, int* lds_cap, long long* lut_cells, int* compact_items,
+                               long long* compact_tiles, int* compact_prefix, int* compact_pending) {
+  if (!h || !h->grid) return fail(NDT_ERR_NO_INPUT, "no grid");
+  const DeviceGrid* g = h->grid.get();
+  const int f = g->empty ? 0 : g->build_form;
+  const bool bucketed = f == 2 || f == 3, table = f == 1 || bucketed;
+  ndt::K1FinishLds F{};
+  if (f == 2) F = ndt::grid_build_finish_lds(g->plan.cells_per_bucket);
+  if (f == 3) {  // the one-launch form shares the finish's LDS with its point lists: a cap of its own
+    ndt::SmallBuildDesc D{};
+    size_t lds = 0;
+    if (ndt::small_build_desc(static_cast<int>(g->target ? g->target->n : 0), g->plan, false, D, &lds)) {
+      F.wmax = D.wmax;
+      F.lds_cap = D.lds_cap;
+    }
+  }
+  const long long lc = table ? g->geom.lut_cells : 0;
+  if (form) *form = f;
+  if (n_points) *n_points = g->target ? g->target->n : 0;
+  if (n_cells) *n_cells = f ? g->geom.n_cells : 0;
+  if (n_buckets) *n_buckets = bucketed ? g->plan.n_buckets : 0;
+  if (cells_per_bucket) *cells_per_bucket = bucketed ? g->plan.cells_per_bucket : 0;
+  if (pts_per_block) *pts_per_block = f == 2 ? g->plan.pts_per_block : 0;
+  if (n_blocks) *n_blocks = f == 2 ? g->plan.n_blocks : 0;
+  if (wmax) *wmax = F.wmax;
+  if (lds_cap) *lds_cap = F.lds_cap;
+  if (lut_cells) *lut_cells = lc;
+  if (compact_items) *compact_items = lc ? ndt::record_compaction_items(lc) : 0;
+  if (compact_tiles) *compact_tiles = lc ? static_cast<long long>(ndt::record_compaction_tiles(lc)) : 0;
+  if (compact_prefix) *compact_prefix = lc && ndt::record_compaction_prefix(lc) ? 1 : 0;
+  if (compact_pending) *compact_pending = g->compact_pending ? 1 : 0;
   return NDT_OK;
 }
 

@@ -2365,6 +2365,31 @@ bool grid_build_plan(long long n_cells, int n_points, GridBuildPlan& P) {
   return true;
 }
 
+// The finish of a bucket-form build (k1_finalize, vf_finalize) for buckets of C cells: the cells one pass may span, the points
+// one pass holds in LDS, the kernel's dynamic LDS.
+// The kernel's registers allow three blocks per CU, so a pass gets what a third of the CU's LDS holds (the host does not
+// know the fullest bucket: on clustered scenes it has three times the mean, and every pass it needs beyond the first reads
+// and ranks the whole bucket again) -- or half / all of it where the per-cell state of a big C leaves less than 1024 points.
+// LDS: 3 C words of per-cell state, 3 words per point, 5 rows of wmax u16 counters (+ ~9 KB static: wave_rank's mask tables)
+K1FinishLds grid_build_finish_lds(int C) {
+  K1FinishLds F{};
+  const int wmax = std::min(C, 1024);
+  auto fin_lds = [&](int cap) { return (static_cast<size_t>(3) * C + 3 * static_cast<size_t>(cap)) * sizeof(unsigned) + 5 * static_cast<size_t>(wmax) * 2; };
+  int lds_cap = 256;
+  for (const size_t budget : {static_cast<size_t>(44 * 1024), static_cast<size_t>(70 * 1024), kK1MaxDynamicLds}) {
+    int cap = kK1LdsCap;
+    while (cap > 256 && fin_lds(cap) > budget) cap -= 256;
+    lds_cap = cap;
+    if (fin_lds(cap) <= budget && cap >= 1024) break;
+  }
+  static const int cap_env = [] { const char* v = getenv("NDT_K1_LDS_CAP"); return v ? std::max(256, atoi(v)) / 256 * 256 : 0; }();
+  if (cap_env > 0) lds_cap = std::min(lds_cap, cap_env);  // (tests: small passes, so that ordinary clouds take the multi-pass and crowded-cell paths)
+  F.wmax = wmax;
+  F.lds_cap = lds_cap;
+  F.bytes = fin_lds(lds_cap);
+  return F;
+}
+
 hipError_t launch_grid_build_buckets(const float4* pts, int n, int dense, const GridGeom& g, const GridBuildPlan& P, int min_pts,
                                      double eig_ratio, const GridBuildScratch& S, int* sorted_idx, VoxelRec* recs, VoxelSide* centroids,
                                      int* lut, unsigned* counts, hipStream_t stream) {
@@ -2386,28 +2411,16 @@ hipError_t launch_grid_build_buckets(const float4* pts, int n, int dense, const 
                      static_cast<const unsigned*>(nullptr));
   // LDS of k1_finalize: 3 C words of per-cell state + 5 words per point of a bucket that fits (at most kK1LdsCap points: eight
   // per thread, held in registers); bigger buckets (clustered data) go through their slices of the global scratch.
-  // The kernel's registers allow three blocks per CU, so a pass gets what a third of the CU's LDS holds (the host does not
-  // know the fullest bucket: on clustered scenes it has three times the mean, and every pass it needs beyond the first reads
-  // and ranks the whole bucket again) -- or half / all of it where the per-cell state of a big C leaves less than 1024 points.
-  // LDS: 3 C words of per-cell state, 3 words per point, 5 rows of wmax u16 counters (+ ~9 KB static: wave_rank's mask tables)
-  const int wmax = std::min(C, 1024);
-  auto fin_lds = [&](int cap) { return (static_cast<size_t>(3) * C + 3 * static_cast<size_t>(cap)) * sizeof(unsigned) + 5 * static_cast<size_t>(wmax) * 2; };
-  int lds_cap = 256;
-  for (const size_t budget : {static_cast<size_t>(44 * 1024), static_cast<size_t>(70 * 1024), kK1MaxDynamicLds}) {
-    int cap = kK1LdsCap;
-    while (cap > 256 && fin_lds(cap) > budget) cap -= 256;
-    lds_cap = cap;
-    if (fin_lds(cap) <= budget && cap >= 1024) break;
-  }
-  static const int cap_env = [] { const char* v = getenv("NDT_K1_LDS_CAP"); return v ? std::max(256, atoi(v)) / 256 * 256 : 0; }();
-  if (cap_env > 0) lds_cap = std::min(lds_cap, cap_env);  // (tests: small passes, so that ordinary clouds take the multi-pass and crowded-cell paths)
-  if (fin_lds(lds_cap) > kK1MaxDynamicLds) return hipErrorInvalidValue;
+  // (grid_build_finish_lds: what a pass holds)
+  const K1FinishLds F = grid_build_finish_lds(C);
+  const int wmax = F.wmax, lds_cap = F.lds_cap;
+  if (F.bytes > kK1MaxDynamicLds) return hipErrorInvalidValue;
   static bool once_f = [] {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k1_finalize), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kK1MaxDynamicLds));
     return true;
   }();
   (void)once_f;
-  hipLaunchKernelGGL(k1_finalize, dim3(K), dim3(kBlock), fin_lds(lds_cap), stream,
+  hipLaunchKernelGGL(k1_finalize, dim3(K), dim3(kBlock), F.bytes, stream,
                      S.bpts, g, P.shift, K, C, min_pts, eig_ratio, lds_cap, wmax, S.bucket_base, sorted_idx, recs, centroids, lut,
                      S.bucket_base + K + 1, S.order, static_cast<unsigned>(n), S.stamps, S.index_form ? pts : nullptr);
   return hipGetLastError();
@@ -2499,22 +2512,13 @@ hipError_t launch_filter_buckets(const float4* pts, int n, int dense, const Grid
   hipLaunchKernelGGL(k1_colscan, dim3((K + kColCols - 1) / kColCols), dim3(kK1Threads), 0, stream, S.cntmat, P.n_blocks, K, total);
   hipLaunchKernelGGL(k1_scatter, dim3(P.n_blocks), dim3(kK1Threads), lds_scatter, stream, pts, n, dense, g, P.shift, K, P.pts_per_block, S.cntmat,
                      total, S.bucket_base, S.bpts, counts, static_cast<unsigned long long*>(nullptr), 0, static_cast<const unsigned*>(nullptr));
-  const int wmax = std::min(C, 1024);
-  auto fin_lds = [&](int cap) { return (static_cast<size_t>(3) * C + 3 * static_cast<size_t>(cap)) * sizeof(unsigned) + 5 * static_cast<size_t>(wmax) * 2; };
-  int lds_cap = 256;
-  for (const size_t budget : {static_cast<size_t>(44 * 1024), static_cast<size_t>(70 * 1024), kK1MaxDynamicLds}) {
-    int cap = kK1LdsCap;
-    while (cap > 256 && fin_lds(cap) > budget) cap -= 256;
-    lds_cap = cap;
-    if (fin_lds(cap) <= budget && cap >= 1024) break;
-  }
-  static const int cap_env = [] { const char* v = getenv("NDT_K1_LDS_CAP"); return v ? std::max(256, atoi(v)) / 256 * 256 : 0; }();
-  if (cap_env > 0) lds_cap = std::min(lds_cap, cap_env);
-  if (fin_lds(lds_cap) > kK1MaxDynamicLds) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(vf_finalize, dim3(K), dim3(kBlock), fin_lds(lds_cap), stream, S.bpts, g, P.shift, K, C, lds_cap, wmax, S.bucket_base, st_cell, st_cent,
+  const K1FinishLds F = grid_build_finish_lds(C);
+  const int wmax = F.wmax, lds_cap = F.lds_cap;
+  if (F.bytes > kK1MaxDynamicLds) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(vf_finalize, dim3(K), dim3(kBlock), F.bytes, stream, S.bpts, g, P.shift, K, C, lds_cap, wmax, S.bucket_base, st_cell, st_cent,
                      reinterpret_cast<unsigned char*>(bitmap_words), S.bucket_base + K + 1, S.order, static_cast<unsigned>(n));
   const int n_words = static_cast<int>(((g.n_cells + 7) / 8 + 3) / 4);
-  const int n_chunks = (n_words + kVfChunkWords - 1) / kVfChunkWords;
+  const int n_chunks = filter_buckets_chunks(g.n_cells);
   hipLaunchKernelGGL(vf_bitmap_prefix, dim3(n_chunks), dim3(kBlock), 0, stream, bitmap_words, n_words, wprefix, counts);
   hipLaunchKernelGGL(vf_place, dim3(std::max(1, std::min(2048, (n + kBlock - 1) / kBlock))), dim3(kBlock), 0, stream, st_cell, st_cent, counts, bitmap_words,
                      wprefix, out);
@@ -2582,6 +2586,12 @@ static int rc_items(long long lut_cells) {
   int items = 1;
   while (items < 8 && lut_cells / (static_cast<long long>(kBlock) * items) >= kRcPrefixTiles) items <<= 1;
   return items;
+}
+int record_compaction_items(long long lut_cells) { return rc_items(lut_cells); }
+bool record_compaction_prefix(long long lut_cells) { return record_compaction_tiles(lut_cells) > static_cast<size_t>(kRcPrefixTiles); }
+int filter_buckets_chunks(long long n_cells) {
+  const int n_words = static_cast<int>(((n_cells + 7) / 8 + 3) / 4);
+  return (n_words + kVfChunkWords - 1) / kVfChunkWords;
 }
 size_t record_compaction_tiles(long long lut_cells) {
   const long long tile = static_cast<long long>(kBlock) * rc_items(lut_cells);

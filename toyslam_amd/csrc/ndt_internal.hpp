@@ -287,6 +287,7 @@ struct DeviceGrid {
   // bucket by bucket); maybe_compact_records makes them dense and cell-ordered once the grid is seen to be reused
   bool compact_pending = false;
   int n_registrations = 0;
+  int build_form = 0;  // what built it (ndt_diag_grid_build): 0 nothing (empty, accumulated), 1 dense chain, 2 buckets, 3 one launch, 4 sparse
   // bucket-form build (ndt_kernels.hip): kept until the leaf arrays have been written (grid_counts)
   bool leaves_pending = false;
   ndt::GridBuildPlan plan{};
@@ -649,6 +650,8 @@ struct FilterRoute {
   ndt::GridGeom geo{};
 };
 FilterRoute filter_route(const ndt_context* h, size_t n, const BBox& bb, float leaf);
+// a dense filter of n points over n_cells cells: on the bucket front end of the grid build (plan filled in), or the general chain
+bool filter_takes_buckets(long long n_cells, long long n, ndt::GridBuildPlan& plan);
 ndt_status voxel_filter_enqueue(ndt_handle h, hipStream_t st, const float4* d_in, size_t n, int is_dense, float leaf, float4* d_out,
                                 const BBox& bb, FilterPending& P);
 void voxel_filter_finish(const FilterPending& P, size_t* n_out, DeviceCloud* boxes);

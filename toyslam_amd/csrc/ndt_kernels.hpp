@@ -208,6 +208,13 @@ hipError_t launch_filter_buckets(const float4* pts, int n, int dense, const Grid
 // k1_small for one cloud, k1_small_multi for many (ndt_align_pairs: one descriptor per cloud, blockIdx.y = cloud).  The two
 // kernels are one block body with 8 and 4 scanning waves, and give a cloud the same records, table, bucketed points and counts.
 bool grid_build_small_applies(int n_points, const GridBuildPlan& plan);
+// the finish of the bucket form over buckets of C cells (k1_finalize, vf_finalize): cells one pass may span, points one pass
+// holds in LDS, dynamic LDS of the launch.  Host only: the launches call it, and so does ndt_host_grid_plan.
+struct K1FinishLds {
+  int wmax, lds_cap;
+  size_t bytes;
+};
+K1FinishLds grid_build_finish_lds(int cells_per_bucket);
 struct SmallBuildDesc {
   const float4* pts;
   int n, dense;
@@ -240,6 +247,9 @@ hipError_t launch_grid_leaves(const GridGeom& g, const GridBuildPlan& plan, int 
                               int* leaf_rec, unsigned* counts, const int* lut, hipStream_t stream, const float4* cloud = nullptr);  // cloud: the index form's points
 // records of a bucket-form build -> dense, in ascending cell order (table entries rewritten); tile_sums: record_compaction_tiles words
 size_t record_compaction_tiles(long long lut_cells);
+int record_compaction_items(long long lut_cells);    // table entries per thread of a tile (1, 2, 4, 8)
+bool record_compaction_prefix(long long lut_cells);  // more tiles than the apply pass scans itself: k_rc_scan runs
+int filter_buckets_chunks(long long n_cells);        // blocks of vf_bitmap_prefix
 hipError_t launch_compact_records(int* lut, long long lut_cells, const VoxelRec* recs_in, const VoxelSide* cent_in, VoxelRec* recs_out,
                                   VoxelSide* cent_out, unsigned* tile_sums, hipStream_t stream);
 

@@ -844,6 +844,20 @@ class NormalDistributionsTransform:
         check(self._L.ndt_diag_eval_plan(self._h, int(n), *[C.byref(x) for x in v]))
         return dict(zip(EVAL_PLAN_FIELDS, (x.value for x in v)))
 
+    def gridBuild(self):
+        """What built this handle's target grid (ndt_diag_grid_build): dict of form (a name of GRID_FORMS), n_points, n_cells,
+        the stored plan, the finish's wmax / lds_cap, lut_cells, the compaction's tile plan and compact_pending."""
+        form, nb, cpb, ppb, blk, wmax, cap, items, prefix, pending = (C.c_int(0) for _ in range(10))
+        n = C.c_size_t(0)
+        cells, lut, tiles = (C.c_longlong(0) for _ in range(3))
+        check(self._L.ndt_diag_grid_build(self._h, C.byref(form), C.byref(n), C.byref(cells), C.byref(nb), C.byref(cpb), C.byref(ppb),
+                                          C.byref(blk), C.byref(wmax), C.byref(cap), C.byref(lut), C.byref(items), C.byref(tiles),
+                                          C.byref(prefix), C.byref(pending)))
+        return dict(form=GRID_FORMS[form.value], n_points=n.value, n_cells=cells.value, n_buckets=nb.value,
+                    cells_per_bucket=cpb.value, pts_per_block=ppb.value, n_blocks=blk.value, wmax=wmax.value, lds_cap=cap.value,
+                    lut_cells=lut.value, compact_items=items.value, compact_tiles=tiles.value, compact_prefix=bool(prefix.value),
+                    compact_pending=bool(pending.value))
+
     def diag_server_roundtrip(self, p, n_iter=200):
         p = np.ascontiguousarray(p, dtype=np.float64)
         us = np.zeros(3)
@@ -978,6 +992,25 @@ def host_lattice(leaf, mn, mx, voxel_index=0, n_points=0):
     st = _lib.lib().ndt_host_lattice(float(leaf), _f(mn), _f(mx), _i(mb), _i(xb), _i(db), C.byref(cells), int(voxel_index),
                                      int(n_points), C.byref(sparse))
     return dict(status=st, min_b=mb, max_b=xb, div_b=db, n_cells=cells.value, sparse=bool(sparse.value))
+
+
+GRID_FORMS = ("empty", "chain", "buckets", "one_launch", "sparse")
+
+
+def host_grid_plan(n_cells, n_points, div_b=None):
+    """The plan of a target-grid build of n_points points over n_cells cells (ndt_host_grid_plan; no GPU): dict of bucket_form,
+    n_buckets, cells_per_bucket, pts_per_block, n_blocks, one_launch, wmax, lds_cap, and -- with div_b, the lattice's cells per
+    axis -- lut_cells, compact_items, compact_tiles, compact_prefix; filter_buckets / filter_chunks: the voxel filter's route."""
+    bf, nb, cpb, ppb, blk, one, wmax, cap, items, prefix, fb, fc = (C.c_int(0) for _ in range(12))
+    lut, tiles = C.c_longlong(0), C.c_longlong(0)
+    db = None if div_b is None else np.ascontiguousarray(div_b, dtype=np.int32).reshape(3)
+    check(_lib.lib().ndt_host_grid_plan(int(n_cells), int(n_points), None if db is None else _i(db), C.byref(bf), C.byref(nb),
+                                        C.byref(cpb), C.byref(ppb), C.byref(blk), C.byref(one), C.byref(wmax), C.byref(cap),
+                                        C.byref(lut), C.byref(items), C.byref(tiles), C.byref(prefix), C.byref(fb), C.byref(fc)))
+    return dict(bucket_form=bool(bf.value), n_buckets=nb.value, cells_per_bucket=cpb.value, pts_per_block=ppb.value,
+                n_blocks=blk.value, one_launch=bool(one.value), wmax=wmax.value, lds_cap=cap.value, lut_cells=lut.value,
+                compact_items=items.value, compact_tiles=tiles.value, compact_prefix=bool(prefix.value),
+                filter_buckets=bool(fb.value), filter_chunks=fc.value)
 
 
 def host_pose_to_matrix(p):
