@@ -13,7 +13,8 @@
 //                    (ndt_comm_*), ndt_set_allreduce
 //   ndt_accumulate.hip : the accumulating target (ndt_target_accumulate*): kernels and C-ABI
 //   ndt_io.hip     : PCD files, numbered scan sequences, PointCloud2-style repacking (host)
-//   gicp_capi.hip  : the GICP row
+//   gicp_capi.hip, gicp_inputs.hip, gicp_register.hip, gicp_batch.hip (gicp_internal.hpp, private to them) : the GICP row --
+//                    handle, parameters, results / inputs and covariances / one registration / many in one call
 #pragma once
 #include <hip/hip_runtime.h>
 
