@@ -22,7 +22,7 @@
 // after the other, 2.7 ms overlapped, 3.7 ms overlapped on CU partitions -- the steps are short host-paced sequences of
 // pageable copies and small launches, and two threads driving them get in each other's way; hence not the default.
 //
-//   map_sequence [--scan-to-map [--window <metres>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> [voxel_leaf_size (0.5 | 0.3)] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]
+//   map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> [voxel_leaf_size (0.5 | 0.3)] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]
 // ("host": the serial loop with every cloud passing through host buffers, as in rounds 1-3; the default keeps them in HBM)
 //
 // --scan-to-map (anywhere on the line; the node's loop with clouds resident in HBM): every scan after the first is registered
@@ -38,6 +38,10 @@
 // first scan is then registered against it from the identity guess -- like every later scan from the previous pose --
 // instead of being placed at the identity.  --localize (with --load-target): scans are registered against the loaded map but
 // neither accumulated into it nor is it cropped.
+// --map-fitness (with --scan-to-map): after each registration "map fitness: <value>" is printed -- getFitnessScore of the scan at
+// its registered pose against the centroid cloud of the target it was registered to (ndt_get_centroid_fitness_score), before
+// the scan is accumulated: the quality number an accumulated target, which keeps no points, can give.  Without the switch
+// every line of output is as it was.
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
@@ -123,6 +127,7 @@ struct Node {
   size_t max_voxels = 0;     // the largest voxel count the windowed target reached
   bool have_map = false;     // --load-target: the target holds a map before the first scan, which is registered like the others
   bool localize = false;     // --localize: the loaded map stays as it is
+  bool map_fitness = false;  // --map-fitness: the centroid fitness of every registration is printed
   std::vector<std::vector<float>> trajectory;                     // trajectory_
   std::vector<float> pose = std::vector<float>(kIdentity, kIdentity + 16);
   std::vector<float> pres_transform = std::vector<float>(kIdentity, kIdentity + 16);  // rosbag node :33,95
@@ -147,6 +152,14 @@ struct Node {
   // after align: -> whether the scan goes into the global map, and with which pose
   bool after_align(ndt_handle h, float* T, int converged, int iterations, std::vector<float>& map_pose, std::string& err) {
     registered++;
+    if (map_fitness) {  // against the target the scan was registered to: the scan has not been accumulated yet
+      double fitness = 0;
+      if (ndt_get_centroid_fitness_score(h, 1.7976931348623157e308, &fitness) != NDT_OK) {
+        err = ndt_last_error();
+        return false;
+      }
+      std::printf("map fitness: %.9g\n", fitness);
+    }
     if (rosbag) {  // perform_registration :119-141, then :63-68
       double fitness = 0;
       if (ndt_get_fitness_score(h, 1.7976931348623157e308, &fitness) != NDT_OK) {
@@ -553,11 +566,11 @@ static int run_pipelined(Node& node, ndt_pcd_sequence_handle seq, float voxel_le
 }
 
 int main(int argc, char** argv) {
-  bool scan_to_map = false, bad_window = false, localize = false, bad_file = false;
+  bool scan_to_map = false, bad_window = false, localize = false, bad_file = false, map_fitness = false;
   float window = 0;
   const char *save_target = nullptr, *load_target = nullptr;
   static const char kUsage[] =
-      "usage: map_sequence [--scan-to-map [--window <metres>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> "
+      "usage: map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> "
       "[voxel_leaf_size] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]\n";
   {  // the switches are taken out of the line before the positional arguments are read
     int kept = 1;
@@ -573,6 +586,8 @@ int main(int argc, char** argv) {
         bad_file = bad_file || !file;
       } else if (std::strcmp(argv[i], "--localize") == 0) {
         localize = true;
+      } else if (std::strcmp(argv[i], "--map-fitness") == 0) {
+        map_fitness = true;
       } else {
         argv[kept++] = argv[i];
       }
@@ -587,6 +602,10 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--save-target <file> and --load-target <file> go with --scan-to-map, --localize goes with --load-target\n%s", kUsage);
     return 2;
   }
+  if (map_fitness && !scan_to_map) {
+    std::fprintf(stderr, "--map-fitness goes with --scan-to-map\n%s", kUsage);
+    return 2;
+  }
   if (argc < 2) {
     std::printf("%s", kUsage);
     return 0;
@@ -599,8 +618,10 @@ int main(int argc, char** argv) {
   node.window = window;
   node.have_map = load_target != nullptr;
   node.localize = localize;
+  node.map_fitness = map_fitness;
   if (scan_to_map && (node.rosbag || !serial || host_clouds)) {
-    // (the rosbag loop prints getFitnessScore, which needs the target's points: an accumulated target keeps none)
+    // (the rosbag loop prints getFitnessScore, which needs the target's points: an accumulated target keeps none --
+    // --map-fitness prints the fitness against its voxel centroids instead)
     std::fprintf(stderr, "--scan-to-map runs the node's serial loop with resident clouds: not with rosbag, pipeline or host\n");
     return 2;
   }

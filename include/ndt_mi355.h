@@ -317,7 +317,8 @@ ndt_status ndt_promote_source_to_target(ndt_handle h, int is_dense);
  *   the next build for a cloud target.  ndt_set_resolution to a different value DROPS the accumulated target: there is no
  *   cloud to rebuild from.
  * - What needs the target's points, or shares the immutable grid with another handle, returns an error and changes
- *   nothing: ndt_get_fitness_score (and ndt_batch_fitness_scores*) NDT_ERR_NO_INPUT; ndt_clone of, and
+ *   nothing: ndt_get_fitness_score (and ndt_batch_fitness_scores*) NDT_ERR_NO_INPUT -- ndt_get_centroid_fitness_score, against
+ *   the voxel centroids the target does keep, is the fitness of such a target; ndt_clone of, and
  *   ndt_share_input_target from, such a handle NDT_ERR_INVALID (ndt_target_accumulate_export + _import, below, give another
  *   handle the same map).
  * - Refused before anything of the target changes -- NDT_ERR_INVALID: a NULL handle, NULL points or clouds with a non-zero
@@ -554,6 +555,47 @@ ndt_status ndt_batch_fitness_scores_device(ndt_handle h, const void* d_pts, cons
 /* diagnostics: the k_fitness_multi launches of the handle's last ndt_pairs_fitness_scores / ndt_batch_fitness_scores* call
  * and the blocks of the largest (its partial rows, kEvalStride doubles each, are all that call held at once) */
 ndt_status ndt_diag_fitness_launches(ndt_handle h, size_t* launches, size_t* max_blocks);
+
+/* ---- the centroid cloud of the target, and getFitnessScore against it ----------------------------------------------------
+ * The CENTROID CLOUD C of the handle's target -- built from a cloud or accumulated -- is the reference's voxel_centroids_: one
+ * point per voxel that reached min_points_per_voxel (a voxel rejected afterwards, nr_points == -1 in ndt_grid_dump, IS in it:
+ * the reference pushes the centroid before it looks at the eigenvalues; a voxel under min_points_per_voxel is not), each the
+ * voxel's f32 centroid -- the f32 coordinate sums in arrival order divided by float(count) -- in ascending linear voxel index
+ * (for an accumulated target over its current box, as ndt_grid_dump reports it).  An accumulated target keeps no points, but
+ * it keeps C: this is the fitness a scan-to-map loop reads after ndt_align.
+ * - ndt_grid_centroids: C as x, y, z, 1.0f per point and (idx != NULL) the linear indices; *n = its size in every case.
+ *   xyz1 == NULL: only *n.  capacity < *n: NDT_ERR_INVALID, neither array written.  One mark + scan + gather over the voxel
+ *   table (sparse index: the occupied hash slots sorted by key instead of the scan) and the read-back of the count.
+ * - ndt_grid_centroids_cloud: C as a resident ndt_cloud in the same order (ndt_cloud_release it), usable wherever an
+ *   ndt_cloud is: ndt_set_input_target_cloud, ndt_cloud_download, gicp_set_input_*_cloud ...  An empty C is a cloud of 0 points.
+ * - ndt_get_centroid_fitness_score: what ndt_get_fitness_score would return on a handle whose target POINTS are C -- the
+ *   handle's source moved in f32 by the last align's final transformation, every finite point's nearest point of C by f32
+ *   (dx*dx + dy*dy) + dz*dz, the f64 mean of the squared distances <= max_range; DBL_MAX when none qualifies, C is empty or
+ *   the source has no finite point.  Same readiness rule (a target and a source: NDT_ERR_NO_INPUT otherwise).  The search is
+ *   exact for every query and every centroid position: it walks shells of cells through the target's own voxel table (no
+ *   index is built, nothing is rebuilt when the map changes), and gives way by the grid's EXCURSION -- the largest per-axis
+ *   distance by which a centroid of C lies outside the box of its own cell (an f32 running sum drifts far from the origin;
+ *   0 when every centroid is inside).  The excursion takes one launch over the table and is cached per grid: computed once
+ *   for a cloud target, again by the next fitness call after every ndt_target_accumulate*, _import, _load or _crop.
+ * - ndt_batch_centroid_fitness_scores*: the same for n_scans clouds, scan k moved by transforms[16k..] (ndt_batch_fitness_scores'
+ *   layout and refusals: NDT_ERR_INVALID before any device work for a NULL handle, offsets or (with scans) transforms /
+ *   fitness, offsets that decrease, a bad stride, more than 65535 scans or INT_MAX points; NDT_ERR_NO_INPUT without a
+ *   target; n_scans == 0: NDT_OK, no device needed).  All members in one search launch plus one reduce launch; sums in a
+ *   fixed order, so results are identical run to run, and a scan's value does not depend on the scans around it.
+ * - ndt_diag_centroid_fitness, of the last fitness call above: the launches it queued (search, reduce, and the excursion
+ *   pass if it ran), the excursion passes among them (0 or 1), the excursion in metres it searched with, and the blocks of
+ *   its search launch.  Any pointer may be NULL.
+ * None of these calls changes the handle's target, source, grid, last result or statistics. */
+ndt_status ndt_grid_centroids(ndt_handle h, float* xyz1 /* capacity*4 or NULL */, int64_t* idx /* capacity or NULL */, size_t capacity,
+                              size_t* n);
+ndt_status ndt_grid_centroids_cloud(ndt_handle h, ndt_cloud* out);
+ndt_status ndt_get_centroid_fitness_score(ndt_handle h, double max_range, double* fitness);
+ndt_status ndt_batch_centroid_fitness_scores(ndt_handle h, const void* pts, const size_t* offsets /* n_scans+1 */, size_t n_scans,
+                                             size_t stride_bytes, const float* transforms /* n_scans*16 */, double max_range,
+                                             double* fitness /* n_scans */);
+ndt_status ndt_batch_centroid_fitness_scores_device(ndt_handle h, const void* d_pts, const size_t* offsets, size_t n_scans,
+                                                    size_t stride_bytes, const float* transforms, double max_range, double* fitness);
+ndt_status ndt_diag_centroid_fitness(ndt_handle h, size_t* launches, size_t* excursion_passes, float* excursion, size_t* max_blocks);
 
 /* ---- one source, many poses (re-localisation in a map, loop-closure checks, recovery after a dropped scan) ------------
  * The caller holds candidate poses of the handle's input source and wants the one that registers.

@@ -135,6 +135,12 @@ SIGNATURES = {
     "ndt_diag_fitness_launches": (C.c_int, [vp, szp, szp]),
     "ndt_batch_fitness_scores": (C.c_int, [vp, vp, szp, C.c_size_t, C.c_size_t, fp, C.c_double, dp]),
     "ndt_batch_fitness_scores_device": (C.c_int, [vp, vp, szp, C.c_size_t, C.c_size_t, fp, C.c_double, dp]),
+    "ndt_grid_centroids": (C.c_int, [vp, fp, C.POINTER(C.c_int64), C.c_size_t, szp]),
+    "ndt_grid_centroids_cloud": (C.c_int, [vp, C.POINTER(vp)]),
+    "ndt_get_centroid_fitness_score": (C.c_int, [vp, C.c_double, dp]),
+    "ndt_batch_centroid_fitness_scores": (C.c_int, [vp, vp, szp, C.c_size_t, C.c_size_t, fp, C.c_double, dp]),
+    "ndt_batch_centroid_fitness_scores_device": (C.c_int, [vp, vp, szp, C.c_size_t, C.c_size_t, fp, C.c_double, dp]),
+    "ndt_diag_centroid_fitness": (C.c_int, [vp, szp, szp, fp, szp]),
     "ndt_score_poses": (C.c_int, [vp, fp, C.c_size_t, dp]),
     "ndt_diag_score_poses": (C.c_int, [vp, szp, szp]),
     "ndt_align_guesses": (C.c_int, [vp, fp, C.c_size_t, fp, ip, ip, dp, ip]),

@@ -6,7 +6,8 @@
 //   ndt_grid.hip   : the cell chain and the sparse index every cell-sorting caller shares, K1 target grid build, counts and
 //                    search index of a built grid, the target setters, grid inspection
 //   ndt_filter.hip : N1 voxel filter of one cloud (ndt_filter_batch.hip: of many)      ndt_map_batch.hip : N2 map accumulation
-//   ndt_fitness.hip : getFitnessScore      ndt_score.hip : calculateScore (of a cloud, of the source under many poses)
+//   ndt_fitness.hip : getFitnessScore      ndt_centroid_fitness.hip : the same against the voxel centroids, the centroid cloud
+//   ndt_score.hip : calculateScore (of a cloud, of the source under many poses)
 //   ndt_eval.hip   : one evaluation (launch path), the persistent evaluation server's host side (mailbox protocol),
 //                    ndt_align, ndt_eval*, diagnostics and self-tests
 //   ndt_batch.hip  : lock-step batches (ndt_align_batch*, ndt_align_guesses, ndt_align_multistart), the RCCL communicator
@@ -298,6 +299,11 @@ struct DeviceGrid {
   // handle; no points, no leaf arrays -- what needs either (getFitnessScore, sharing) refuses it
   bool accumulated = false;
   DevBuf<unsigned> bucket_base;
+  // the centroid fitness (ndt_centroid_fitness.hip): how far any centroid of the grid lies outside its own cell's box, computed
+  // on first use (under fit_mu); an accumulated target marks it stale wherever its voxels change (commit, crop)
+  bool excursion_known = false;
+  float excursion = 0.f;
+  size_t n_centroids = 0;  // voxels of the centroid cloud, counted by the same pass
   ndt::GridView view() const {
     ndt::GridView v;
     v.lut = lut.p;
@@ -474,6 +480,10 @@ struct ndt_context {
   int crop_relinked = 0;
   // ... and the last ndt_target_accumulate_export / _save (ndt_diag_target_export)
   size_t exp_voxels = 0, exp_points = 0, exp_launches = 0;
+  // the last centroid fitness call (ndt_diag_centroid_fitness): launches queued, excursion passes among them, the excursion it
+  // searched with, the blocks of its largest launch
+  size_t cf_launches = 0, cf_passes = 0, cf_max_blocks = 0;
+  float cf_excursion = 0.f;
 
   ~ndt_context() {
     for (ndt_context* w : batch_workers) delete w;

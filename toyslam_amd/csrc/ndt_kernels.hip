@@ -724,6 +724,9 @@ hipError_t launch_fitness_multi(const FitnessMember* members, const int* starts,
                                 double* partials, double* sums, hipStream_t stream) {
   if (n_members <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_fitness_multi, dim3(n_blocks), dim3(kBlock), 0, stream, members, starts, n_members, max_range, partials);
+  return launch_fitness_reduce(partials, starts, n_members, sums, stream);
+}
+hipError_t launch_fitness_reduce(const double* partials, const int* starts, int n_members, double* sums, hipStream_t stream) {
   hipLaunchKernelGGL(k_fitness_reduce, dim3(n_members), dim3(kReduceThreads), 0, stream, partials, starts, sums);
   return hipGetLastError();
 }

@@ -408,6 +408,8 @@ hipError_t launch_fitness(const float4* src, int n, const float* T12, const Poin
 // n_blocks = starts[n_members]; partials [n_blocks][kEvalStride]; sums[m] = {sum of d^2, count} (k_reduce's order over its rows)
 hipError_t launch_fitness_multi(const FitnessMember* members, const int* starts, int n_members, int n_blocks, double max_range,
                                 double* partials, double* sums, hipStream_t stream);
+// ... its second launch alone (k_fitness_reduce), for rows another unit's kernel wrote in the same layout (ndt_centroid_fitness.hip)
+hipError_t launch_fitness_reduce(const double* partials, const int* starts, int n_members, double* sums, hipStream_t stream);
 // pts in the cell order of an index: out[q] = pts[sorted_idx[q]] for q < *d_n_sorted
 hipError_t launch_gather_points(const float4* pts, const int* sorted_idx, const unsigned* d_n_sorted, int n_max, float4* out,
                                 hipStream_t stream);

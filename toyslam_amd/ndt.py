@@ -661,6 +661,62 @@ class NormalDistributionsTransform:
                  _d(out)))
         return out[:B].copy()
 
+    # ---- the target's centroid cloud and getFitnessScore against it (any target, accumulated ones too) -------
+    def gridCentroids(self):
+        """The centroid cloud of the target (ndt_grid_centroids): ((V, 4) float32 of x, y, z, 1, (V,) int64 linear voxel indices),
+        one point per voxel that reached min_points_per_voxel, in ascending index."""
+        n = C.c_size_t(0)
+        check(self._L.ndt_grid_centroids(self._h, None, None, 0, C.byref(n)))
+        V = n.value
+        xyz1 = np.zeros((max(V, 1), 4), dtype=np.float32)
+        idx = np.zeros(max(V, 1), dtype=np.int64)
+        if V:
+            check(self._L.ndt_grid_centroids(self._h, _f(xyz1), idx.ctypes.data_as(C.POINTER(C.c_int64)), V, C.byref(n)))
+        return xyz1[:V].copy(), idx[:V].copy()
+
+    def gridCentroidsCloud(self):
+        """The same cloud as a resident DeviceCloud (ndt_grid_centroids_cloud)."""
+        c = C.c_void_p(None)
+        check(self._L.ndt_grid_centroids_cloud(self._h, C.byref(c)))
+        return DeviceCloud(self, c)
+
+    def centroidFitnessScore(self, max_range=np.finfo(np.float64).max):
+        """getFitnessScore of the source under the last align's final transformation against the target's centroid cloud
+        (ndt_get_centroid_fitness_score): works on an accumulated target, which keeps no points."""
+        out = C.c_double(0)
+        check(self._L.ndt_get_centroid_fitness_score(self._h, float(max_range), C.byref(out)))
+        return out.value
+
+    def batchCentroidFitness(self, clouds=None, transforms=None, max_range=np.finfo(np.float64).max, device_ptr=None, offsets=None,
+                             stride_bytes=16):
+        """The centroid fitness of many scans against this handle's target (ndt_batch_centroid_fitness_scores*), scan k moved
+        by transforms[k]; arguments as batchFitness takes them.  Returns (B,) float64."""
+        if clouds is not None:
+            cat = _cloud(np.concatenate(clouds, axis=0)) if len(clouds) else np.zeros((0, 4), np.float32)
+            offsets = np.zeros(len(clouds) + 1, dtype=np.uintp)
+            offsets[1:] = np.cumsum([len(c) for c in clouds])
+            ptr, stride, fn = cat.ctypes.data, cat.shape[1] * 4, self._L.ndt_batch_centroid_fitness_scores
+        else:
+            offsets = np.ascontiguousarray(offsets, dtype=np.uintp)
+            ptr, stride, fn = C.c_void_p(device_ptr), stride_bytes, self._L.ndt_batch_centroid_fitness_scores_device
+        B = len(offsets) - 1
+        if transforms is None:
+            raise ValueError("batchCentroidFitness needs one transform per scan")
+        T = np.ascontiguousarray(np.stack([_colmajor(x) for x in transforms]), dtype=np.float32) if B else np.zeros((0, 16), np.float32)
+        if T.shape[0] != B:
+            raise ValueError("one transform per scan")
+        out = np.zeros(max(B, 1), dtype=np.float64)
+        check(fn(self._h, ptr, offsets.ctypes.data_as(C.POINTER(C.c_size_t)), B, stride, _f(T) if B else None, float(max_range),
+                 _d(out)))
+        return out[:B].copy()
+
+    def centroidFitnessDiag(self):
+        """What the last centroidFitnessScore / batchCentroidFitness did (ndt_diag_centroid_fitness)."""
+        a, p, b = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        e = C.c_float(0)
+        check(self._L.ndt_diag_centroid_fitness(self._h, C.byref(a), C.byref(p), C.byref(e), C.byref(b)))
+        return dict(launches=a.value, excursion_passes=p.value, excursion=e.value, max_blocks=b.value)
+
     # ---- one source, many poses (ndt_score_poses / ndt_align_guesses / ndt_align_multistart) -------
     @staticmethod
     def _pose_table(poses):
