@@ -252,6 +252,34 @@ ndt_status ndt_cloud_size(ndt_cloud c, size_t* n);
 ndt_status ndt_cloud_data(ndt_cloud c, const void** d_pts_float4, size_t* n);               /* the records in HBM */
 ndt_status ndt_cloud_download(ndt_handle h, ndt_cloud c, void* out, size_t out_stride_bytes); /* x,y,z,1.0f per point */
 void ndt_cloud_release(ndt_cloud c);
+/* Every cloud carries two bounding boxes, computed where the cloud is made and never again: box [0] over the coordinates
+ * that are not NaN (what getMinMax3D sees for an is_dense cloud), box [1] over the points whose three coordinates are
+ * finite (the !is_dense rule).  Every lattice -- grid build, voxel filter, source ordering, the map's guessed box, GICP's
+ * extents -- is laid over one of them.  ndt_box_route names the producer that wrote a cloud's boxes. */
+typedef enum {
+  NDT_BOX_ROUTE_NONE = 0,         /* no producer ran: an empty cloud, the initial (FLT_MAX, -FLT_MAX) boxes               */
+  NDT_BOX_ROUTE_HOST_SCALAR = 1,  /* host upload, one point per step                                                      */
+  NDT_BOX_ROUTE_HOST_AVX2 = 2,    /* host upload, two points per step                                                     */
+  NDT_BOX_ROUTE_REPACK = 3,       /* device, records of any stride (k_repack_bbox): per-block rows behind a stream wait   */
+  NDT_BOX_ROUTE_REC16_COPY = 4,   /* device, aligned 16-byte records copied (k_bbox16<true>); device buffers: rows polled */
+  NDT_BOX_ROUTE_REC16_POLLED = 5, /* a cloud by reference (k_bbox16<false>): nothing copied, tagged rows polled           */
+  NDT_BOX_ROUTE_FILTER_ROWS = 6,  /* output of a voxel filter: rows of at most 64 blocks, the count read on the device    */
+  NDT_BOX_ROUTE_MULTI_WORDS = 7,  /* member of a batched call (k_repack_bbox_multi): order-encoded words, atomic max      */
+  NDT_BOX_ROUTE_STAGED = 8        /* scan of a staged PCD sequence: boxes by the reading thread                           */
+} ndt_box_route;
+/* the cloud's boxes exactly as stored: out = {min xyz, max xyz} of box [0], then of box [1]; an empty box is
+ * (FLT_MAX, -FLT_MAX).  *route (may be NULL) = the ndt_box_route that wrote them.  No device work. */
+ndt_status ndt_cloud_bounds(ndt_cloud c, float out[12], int* route);
+/* the same for a handle's inputs: which = 0 the input source, 1 the input target's cloud, 2 the map (a queued map update
+ * is waited for first; NDT_ERR_NO_INPUT when the map's boxes are not known: no update yet, or ndt_map_clear).
+ * NDT_ERR_NO_INPUT when that input is not set. */
+ndt_status ndt_diag_input_bounds(ndt_handle h, int which, float out[12], int* route);
+/* Host only, no device: the host upload's repack + bounding-box pass itself (the function upload_cloud calls for clouds of
+ * at most NDT_HOST_STAGE_MAX points), avx2 = 0 the one-point form, 1 the two-point form (NDT_ERR_INVALID where the CPU
+ * has no AVX2).  n records of stride_bytes (>= 12, a multiple of 4; x y z first) -> out_records: n records (x, y, z, 1.0f)
+ * on a 16-byte boundary; out_bounds as ndt_cloud_bounds writes them.  Records of 12 bytes: nothing behind the last
+ * record is read. */
+ndt_status ndt_host_repack_bbox(const void* pts, size_t n, size_t stride_bytes, int avx2, float* out_records, float out_bounds[12]);
 ndt_status ndt_set_input_source_cloud(ndt_handle h, ndt_cloud c);
 ndt_status ndt_set_input_target_cloud(ndt_handle h, ndt_cloud c, int is_dense);
 ndt_status ndt_map_update_cloud(ndt_handle h, ndt_cloud scan, int is_dense, const float* pose, float leaf_size, int* overflowed);

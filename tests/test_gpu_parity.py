@@ -132,11 +132,13 @@ class _DeviceCopies:
             self.hip.hipFree(p)
 
 
-@pytest.mark.parametrize("n,floats,dense", [(1, 3, 1), (777, 3, 0), (20000, 4, 1), (20000, 8, 0), (32768, 3, 0), (5000, 5, 1)])
+@pytest.mark.parametrize("n,floats,dense", [(1, 3, 1), (777, 3, 0), (20000, 4, 1), (20000, 8, 0), (20480, 3, 0), (5000, 5, 1)])
 def test_small_host_clouds_route_equals_device_route(mods, n, floats, dense):
-    """Host clouds of up to 32 768 points are repacked and bounded on the host (upload_cloud: no repack kernel, no wait);
-    the same records handed over in HBM go through k_repack_bbox.  Both must give the same boxes and the same grid, with NaN /
-    inf coordinates, any record stride and garbage behind xyz."""
+    """Host clouds of up to 20 480 points (NDT_HOST_STAGE_MAX) are repacked and bounded on the host (upload_cloud: no repack
+    kernel, no wait); the same records handed over in HBM go through k_repack_bbox, or k_bbox16 when they are 16 bytes.  Both
+    must give the same boxes -- the reference's, tests/cloud_box_cases.py -- and the same grid, with NaN / inf coordinates,
+    any record stride and garbage behind xyz.  Every case first asserts the two routes it compares."""
+    import cloud_box_cases as cb
     ndt, _, _ = mods
     rng = np.random.default_rng(1000 + n + floats)
     rec = rng.uniform(-1e3, 1e3, (n, floats)).astype(np.float32)  # (whatever follows xyz in a record must not matter)
@@ -152,6 +154,10 @@ def test_small_host_clouds_route_equals_device_route(mods, n, floats, dense):
     with _DeviceCopies() as dc:
         gh.setInputTarget(rec, is_dense=bool(dense))
         gd.setInputTargetDevice(dc.put(rec), n, floats * 4, is_dense=bool(dense))
+        (bh, rh), (bd, rd) = gh.inputBounds("target"), gd.inputBounds("target")
+        assert rh == cb.upload_route(n, floats * 4) and rd == cb.upload_route(n, floats * 4, on_device=True)
+        assert rh == cb.host_route() or cb.HOST_STAGE_MAX < n
+        assert cb.same_boxes(bh, bd) and cb.same_boxes(bh, cb.reference_boxes(rec)), cb.boxes_text(bh, cb.reference_boxes(rec))
         a, b = gh.grid(), gd.grid()
         for k in ("min_b", "max_b", "div_b", "idx", "n", "mean", "cov", "icov"):
             assert np.array_equal(a[k], b[k], equal_nan=True), k

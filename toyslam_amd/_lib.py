@@ -13,6 +13,7 @@ CSRC = os.path.join(_HERE, "csrc")
 
 NDT_OK, NDT_ERR_INVALID, NDT_ERR_NO_DEVICE, NDT_ERR_HIP, NDT_ERR_GRID_OVERFLOW, NDT_ERR_NO_INPUT, NDT_ERR_COMM = range(7)
 KDTREE, DIRECT26, DIRECT7, DIRECT1 = 0, 1, 2, 3
+BOX_ROUTES = ("none", "host_scalar", "host_avx2", "repack", "rec16_copy", "rec16_polled", "filter_rows", "multi_words", "staged")
 EVAL_STRIDE = 32
 COMM_ID_BYTES = 128
 
@@ -91,6 +92,9 @@ SIGNATURES = {
     "ndt_cloud_data": (C.c_int, [vp, C.POINTER(C.c_void_p), szp]),
     "ndt_cloud_download": (C.c_int, [vp, vp, vp, C.c_size_t]),
     "ndt_cloud_release": (None, [vp]),
+    "ndt_cloud_bounds": (C.c_int, [vp, fp, ip]),
+    "ndt_diag_input_bounds": (C.c_int, [vp, C.c_int, fp, ip]),
+    "ndt_host_repack_bbox": (C.c_int, [vp, C.c_size_t, C.c_size_t, C.c_int, vp, fp]),
     "ndt_set_input_source_cloud": (C.c_int, [vp, vp]),
     "ndt_set_input_target_cloud": (C.c_int, [vp, vp, C.c_int]),
     "ndt_map_update_cloud": (C.c_int, [vp, vp, C.c_int, fp, C.c_float, ip]),

@@ -146,6 +146,7 @@ ndt_status upload_cloud(ndt_context* h, const void* pts, size_t n, size_t stride
     static const bool avx2 = [] { const char* v = getenv("NDT_HOST_AVX2"); return (!v || atoi(v) != 0) && __builtin_cpu_supports("avx2"); }();
     if (avx2) host_repack_bbox_avx2(static_cast<const unsigned char*>(pts), n, stride, h->stage_host[slot], c->bb_min, c->bb_max);
     else host_repack_bbox(static_cast<const unsigned char*>(pts), n, stride, h->stage_host[slot], c->bb_min, c->bb_max);
+    c->box_route = avx2 ? NDT_BOX_ROUTE_HOST_AVX2 : NDT_BOX_ROUTE_HOST_SCALAR;
     HIP_TRY(ndt::launch_copy_records(reinterpret_cast<const float4*>(h->stage_host[slot]), c->pts.p, static_cast<int>(n), h->stream));
     HIP_TRY(hipEventRecord(h->stage_done[slot], h->stream));
   } else if (n) {
@@ -226,6 +227,7 @@ ndt_status upload_cloud(ndt_context* h, const void* pts, size_t n, size_t stride
           c->bb_min[v][k] = std::min(c->bb_min[v][k], mm[b * 12 + v * 6 + k]);
           c->bb_max[v][k] = std::max(c->bb_max[v][k], mm[b * 12 + v * 6 + 3 + k]);
         }
+    c->box_route = !rec16 ? NDT_BOX_ROUTE_REPACK : borrowed ? NDT_BOX_ROUTE_REC16_POLLED : NDT_BOX_ROUTE_REC16_COPY;
   }
   out = c;
   return NDT_OK;
@@ -561,6 +563,51 @@ ndt_status ndt_cloud_download(ndt_handle h, ndt_cloud c, void* out, size_t out_s
 }
 void ndt_cloud_release(ndt_cloud c) { delete c; }
 
+static void write_bounds(const float bb_min[2][3], const float bb_max[2][3], float out[12]) {
+  for (int v = 0; v < 2; v++)
+    for (int k = 0; k < 3; k++) {
+      out[6 * v + k] = bb_min[v][k];
+      out[6 * v + 3 + k] = bb_max[v][k];
+    }
+}
+static void write_bounds(const DeviceCloud& c, float out[12], int* route) {
+  write_bounds(c.bb_min, c.bb_max, out);
+  if (route) *route = c.box_route;
+}
+ndt_status ndt_cloud_bounds(ndt_cloud c, float out[12], int* route) {
+  if (!c || !out) return fail(NDT_ERR_INVALID, "bad arguments");
+  write_bounds(*c->c, out, route);
+  return NDT_OK;
+}
+ndt_status ndt_diag_input_bounds(ndt_handle h, int which, float out[12], int* route) {
+  if (!h || !out || which < 0 || which > 2) return fail(NDT_ERR_INVALID, "bad arguments");
+  if (which == 2) {
+    if (h->map_pending) {
+      ndt_status s = ensure_device(h);
+      if (!s) s = map_settle(h);
+      if (s) return s;
+    }
+    if (!h->map_boxes_known) return fail(NDT_ERR_NO_INPUT, "the map's boxes are not known");
+    write_bounds(h->map_boxes, out, route);
+    return NDT_OK;
+  }
+  const std::shared_ptr<DeviceCloud>& c = which == 0 ? h->source : h->target;
+  if (!c) return fail(NDT_ERR_NO_INPUT, which == 0 ? "no input source" : "no input target");
+  write_bounds(*c, out, route);
+  return NDT_OK;
+}
+ndt_status ndt_host_repack_bbox(const void* pts, size_t n, size_t stride, int avx2, float* out_records, float out_bounds[12]) {
+  if ((n && (!pts || !out_records)) || !out_bounds) return fail(NDT_ERR_INVALID, "bad arguments");
+  if (stride < 12 || stride % 4) return fail(NDT_ERR_INVALID, "stride_bytes must be a multiple of 4 and >= 12");
+  if (reinterpret_cast<uintptr_t>(out_records) & 15) return fail(NDT_ERR_INVALID, "out_records must be on a 16-byte boundary");
+  if (avx2 && !__builtin_cpu_supports("avx2")) return fail(NDT_ERR_INVALID, "this CPU has no AVX2");
+  float bb_min[2][3], bb_max[2][3];
+  if (avx2) ndtc::host_repack_bbox_avx2(static_cast<const unsigned char*>(pts), n, stride, out_records, bb_min, bb_max);
+  else ndtc::host_repack_bbox(static_cast<const unsigned char*>(pts), n, stride, out_records, bb_min, bb_max);
+  write_bounds(bb_min, bb_max, out_bounds);
+  return NDT_OK;
+}
+
 ndt_status ndt_set_input_source_cloud(ndt_handle h, ndt_cloud c) {
   if (!h || !c) return fail(NDT_ERR_INVALID, "bad arguments");
   ndt_status s = ensure_device(h);
@@ -573,6 +620,7 @@ ndt_status ndt_set_input_source_cloud(ndt_handle h, ndt_cloud c) {
   view->n = c->c->n;
   std::memcpy(view->bb_min, c->c->bb_min, sizeof(view->bb_min));
   std::memcpy(view->bb_max, c->c->bb_max, sizeof(view->bb_max));
+  view->box_route = c->c->box_route;
   s = order_cloud(h, view.get(), nullptr, 0);
   if (s) return s;
   if (view->n_sorted == 0) {  // (the usual case at the nodes' size: nothing to order, the cloud itself is the source)

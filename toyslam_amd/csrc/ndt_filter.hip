@@ -127,6 +127,7 @@ ndt_status voxel_filter_enqueue(ndt_handle h, hipStream_t st, const float4* d_in
 void voxel_filter_finish(const FilterPending& P, size_t* n_out, DeviceCloud* boxes) {
   *n_out = P.from_device ? P.tot[1] : P.fixed_n;
   if (!boxes) return;
+  boxes->box_route = NDT_BOX_ROUTE_FILTER_ROWS;
   for (int v = 0; v < 2; v++)
     for (int k = 0; k < 3; k++) {
       boxes->bb_min[v][k] = FLT_MAX;

@@ -37,6 +37,7 @@ void decode_boxes(const unsigned* w, DeviceCloud* c) {
       c->bb_min[v][k] = ndt::box_word_decode(w[6 * v + k], true);
       c->bb_max[v][k] = ndt::box_word_decode(w[6 * v + 3 + k], false);
     }
+  c->box_route = NDT_BOX_ROUTE_MULTI_WORDS;
 }
 
 std::shared_ptr<DeviceCloud> new_cloud(ndt_handle h) {

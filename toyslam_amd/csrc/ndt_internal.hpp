@@ -216,6 +216,7 @@ struct DeviceCloud {
   // is_dense rule of getMinMax3D), [1] over the finite points (!is_dense); min > max = no such point
   float bb_min[2][3] = {{FLT_MAX, FLT_MAX, FLT_MAX}, {FLT_MAX, FLT_MAX, FLT_MAX}};
   float bb_max[2][3] = {{-FLT_MAX, -FLT_MAX, -FLT_MAX}, {-FLT_MAX, -FLT_MAX, -FLT_MAX}};
+  int box_route = NDT_BOX_ROUTE_NONE;  // which producer wrote the boxes (ndt_box_route; set where the boxes are set)
   size_t n_sorted = 0;    // finite points only
   std::vector<size_t> scan_counts;  // batch uploads: finite points of each scan ...
   std::vector<size_t> scan_starts;  // ... and where its ordered segment starts in `sorted`

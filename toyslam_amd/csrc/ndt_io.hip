@@ -258,6 +258,7 @@ ndt_status ndt_pcd_sequence_next_cloud(ndt_pcd_sequence_handle s, ndt_cloud* clo
     c->device = s->stage_device;
     std::memcpy(c->bb_min, scan.bb_min, sizeof(c->bb_min));
     std::memcpy(c->bb_max, scan.bb_max, sizeof(c->bb_max));
+    c->box_route = NDT_BOX_ROUTE_STAGED;
     *cloud = new ndt_cloud_s{c};
   }
   return NDT_OK;

@@ -290,6 +290,7 @@ ndt_status map_batch_stage(ndt_handle h, const void* pts, const size_t* offsets,
         c->bb_min[v][i] = ndt::box_word_decode(w[12 * k + 6 * v + i], true);
         c->bb_max[v][i] = ndt::box_word_decode(w[12 * k + 6 * v + 3 + i], false);
       }
+    c->box_route = NDT_BOX_ROUTE_MULTI_WORDS;
   }
   return NDT_OK;
 }

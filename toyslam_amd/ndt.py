@@ -65,6 +65,13 @@ class DeviceCloud:
         check(self._L.ndt_cloud_download(self._owner._h, self._c, out.ctypes.data, 16))
         return out[:n, :3].copy()
 
+    def bounds(self):
+        """The cloud's two bounding boxes exactly as stored, and the producer that wrote them (ndt_cloud_bounds):
+        -> ((2, 2, 3) float32 [box][min | max][xyz], route name of _lib.BOX_ROUTES)."""
+        out, route = np.zeros(12, dtype=np.float32), C.c_int(-1)
+        check(self._L.ndt_cloud_bounds(self._c, _f(out), C.byref(route)))
+        return out.reshape(2, 2, 3), _lib.BOX_ROUTES[route.value]
+
     def release(self):
         if self._c:
             self._L.ndt_cloud_release(self._c)
@@ -435,6 +442,13 @@ class NormalDistributionsTransform:
         check(self._L.ndt_map_update_batch(self._h, C.c_void_p(dev_ptr), offsets.ctypes.data_as(C.POINTER(C.c_size_t)), n, int(stride_bytes),
                                            _i(dense), _f(P) if P is not None else None, float(leaf_size), 1, C.byref(ov)))
         return self.mapSize(), bool(ov.value)
+
+    def inputBounds(self, which):
+        """The bounding boxes of "source", "target" or "map" as stored, and their producer (ndt_diag_input_bounds):
+        -> ((2, 2, 3) float32 [box][min | max][xyz], route name)."""
+        out, route = np.zeros(12, dtype=np.float32), C.c_int(-1)
+        check(self._L.ndt_diag_input_bounds(self._h, ("source", "target", "map").index(which), _f(out), C.byref(route)))
+        return out.reshape(2, 2, 3), _lib.BOX_ROUTES[route.value]
 
     def mapBatchDiag(self):
         """What the last mapUpdateClouds / mapUpdateBatch / mapUpdateBatchDevice did (ndt_diag_map_batch)."""
@@ -1269,6 +1283,16 @@ class PcdSequence:
             return None
         return d.value, p.value, n.value, bool(dense.value), num.value
 
+    def next_cloud(self, owner):
+        """-> (DeviceCloud view of the next staged scan for the handle `owner`, (n, 4) float32 copy of its host records,
+        is_dense, file_number), or None when nothing is queued.  The view is valid until the following next* call."""
+        c, p, n, dense, num = C.c_void_p(), C.c_void_p(), C.c_size_t(0), C.c_int(1), C.c_int(-1)
+        check(self._L.ndt_pcd_sequence_next_cloud(self._h, C.byref(c), C.byref(p), C.byref(n), C.byref(dense), C.byref(num)))
+        if not c.value:
+            return None
+        rec = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), shape=(n.value, 4)).copy()
+        return DeviceCloud(owner, c), rec, bool(dense.value), num.value
+
     def next_raw(self):
         """-> (host address of n x (x, y, z, 1.0f) records, n, is_dense, file_number) or None.  The records sit in one of
         the sequence's two (page-locked) buffers and stay valid until the following call of next / next_raw."""
@@ -1287,3 +1311,18 @@ def repack_fields(data, n, point_step, off_x=0, off_y=4, off_z=8):
     dense = C.c_int(1)
     check(_lib.lib().ndt_host_repack_fields(buf.ctypes.data, n, point_step, off_x, off_y, off_z, out.ctypes.data, C.byref(dense)))
     return out, bool(dense.value)
+
+
+def host_repack_bbox(records, n, stride_bytes, avx2=False):
+    """The host upload's repack + bounding-box pass on its own (ndt_host_repack_bbox; no device).  records: a uint8 / float32
+    array whose first byte is the first record's x; nothing behind byte (n - 1) * stride_bytes + 12 is promised to exist.
+    -> ((n, 4) float32 records x, y, z, 1, (2, 2, 3) float32 boxes [box][min | max][xyz])."""
+    buf = np.asarray(records)
+    assert buf.flags.c_contiguous and (n == 0 or buf.nbytes >= (n - 1) * stride_bytes + 12)
+    raw = np.zeros(4 * max(n, 1) + 4, dtype=np.float32)
+    skip = ((-raw.ctypes.data) % 16) // 4  # (the records go to a 16-byte boundary)
+    out = raw[skip:skip + 4 * n].reshape(n, 4)
+    bounds = np.zeros(12, dtype=np.float32)
+    check(_lib.lib().ndt_host_repack_bbox(buf.ctypes.data if n else None, n, stride_bytes, int(bool(avx2)),
+                                          out.ctypes.data if n else None, _f(bounds)))
+    return out.copy(), bounds.reshape(2, 2, 3)
