@@ -328,7 +328,8 @@ ndt_status ndt_promote_source_to_target(ndt_handle h, int is_dense);
  * - Equivalence.  After any sequence of accumulate calls the handle behaves like a handle with the same parameters whose
  *   target was set from the concatenation -- in call order, and in cloud order within _clouds -- of the clouds moved by their
  *   poses: ndt_grid_size / _info / _dump return the same leaves, counts, means, covariances, inverse covariances and
- *   eigenvalues, and ndt_eval*, ndt_eval_hessian_f64, ndt_calculate_score, ndt_score_poses, ndt_align, ndt_align_guesses,
+ *   eigenvalues, and ndt_eval*, ndt_eval_hessian_f64, ndt_calculate_score, ndt_score_poses, ndt_calculate_nvtl, ndt_get_nvtl,
+ *   ndt_nvtl_poses, ndt_source_point_nvtl, ndt_align, ndt_align_guesses,
  *   ndt_align_multistart and ndt_align_batch* the same bits, for all four search methods (the evaluation kernels see an
  *   ordinary grid: the padded dense table, or the hash keyed by the reference's linear index; ndt_set_voxel_index chooses
  *   between the two as for a cloud target, by the points accumulated so far).  `pose` is a column-major 4x4, NULL =
@@ -660,6 +661,56 @@ void ndt_host_pick_top(const double* scores, size_t n, size_t keep, int* idx_out
 ndt_status ndt_align_multistart(ndt_handle h, const float* candidates /* n_candidates*16 */, size_t n_candidates, size_t keep,
                                 int* picked, size_t* n_picked, float* final_transformations, int* has_converged,
                                 int* final_num_iteration, double* transformation_probability, int* best);
+
+/* ---- nearest-voxel transformation likelihood (NVTL): is this pose right? ----------------------------------------------
+ * calculateScore averages a point's terms over ALL its neighbour voxels and divides by ALL points of the scan: its value
+ * moves with the search method's neighbour count and with how much of the scan overlaps the (possibly partly loaded) map.
+ * NVTL takes, per point, the best-fitting neighbour voxel and averages over the points that have a neighbour at all, so a
+ * fixed acceptance threshold holds across maps; per point it tells a point the map does not explain (a moving object).
+ *
+ * Definition.  Inputs: a point p (f32, used as given), the handle's target grid, its search method and (d1, d2, d3) =
+ * gauss_constants(resolution, outlier_ratio).
+ *  1. p has the neighbour set of calculateScore (ndt_calculate_score), exactly: empty for a non-finite p or a p more than a
+ *     cell outside the grid's box; DIRECT1 / DIRECT7 / DIRECT26: the valid voxels at the method's cell offsets; KDTREE: the
+ *     voxels of the centroid cloud in the 3x3x3 block whose f32 centroid is closer than the resolution.
+ *  2. Each neighbour record r gives q_r = x^T C_r^-1 x in f64, x = double(p) - mean_r, with the f64 inverse covariance and
+ *     calculateScore's association: (c00 x0 + c01 x1) + c02 x2 per row, then (x0 c0 + x1 c1) + x2 c2.
+ *  3. q_min starts at +inf and becomes q_r whenever q_r < q_min, in neighbour order: a NaN q_r never wins.
+ *  4. L(p) = -d1 exp(-d2 q_min / 2) when the set is not empty: one exp per point.  For d2 > 0 (every outlier ratio in (0, 1))
+ *     this is max_r(-d1 exp(-d2 q_r / 2)), the usual wording; the q_min form is the definition for every d2.  A point with
+ *     an empty set is NOT FOUND and adds nothing.
+ *  5. NVTL = (sum of L(p) over the found points) / n_found, in f64, summed in a fixed order (per-thread walk of the points,
+ *     block fold, fixed-order sum of the blocks): identical run to run.  n_found == 0 -- an empty grid, an empty cloud, every
+ *     point far away or non-finite -- gives 0.0: never NaN, never an error.
+ *
+ * - ndt_calculate_nvtl: of `cloud`, used as given (the sibling of ndt_calculate_score).  *n_found may be NULL.
+ * - ndt_get_nvtl: of the handle's source moved in f32 by the last align's final transformation (ndt_get_fitness_score's
+ *   transformation; the identity before any align).
+ * - ndt_nvtl_poses: of the handle's source under each of n_poses transforms (ndt_score_poses' layout, chunking --
+ *   NDT_SCORE_POSES_CHUNK and the 256 MiB bound -- and checks), one launch per chunk.  nvtl[g] has the bits of
+ *   ndt_calculate_nvtl of pcl::transformPointCloud(source, transforms + 16 g), of ndt_source_point_nvtl's reduction for that
+ *   pose, and (for the final transformation) of ndt_get_nvtl.  n_found (n_poses entries) may be NULL.
+ * - ndt_source_point_nvtl: L(p) of every source point under `transform` (NULL: the last align's final transformation), in the
+ *   caller's point order, -1.0 for a point that was not found (L itself is never negative).  out (host, n_source doubles)
+ *   and d_out (receives a device pointer to the same values, valid until the next ndt_source_point_nvtl on the handle or its
+ *   destruction) may each be NULL; *nvtl / *n_found (may be NULL) are the reduction of the same launch.
+ *   ndt_source_point_count sizes `out`: the points of the handle's input source, 0 without one (host only, no device needed).
+ * - ndt_diag_nvtl, of the last of the four calls above that reached the device: its launches (k_nvtl / k_nvtl_poses) and the
+ *   blocks of all of them together.
+ * NDT_ERR_INVALID before any device work: a NULL handle, a NULL nvtl (ndt_calculate_nvtl, ndt_get_nvtl), a NULL cloud with
+ * n > 0, a bad stride, more than INT_MAX points; for ndt_nvtl_poses what ndt_score_poses refuses, and n_poses == 0 is NDT_OK,
+ * writes nothing and needs no device.  Then NDT_ERR_NO_DEVICE without a gfx950 device, then NDT_ERR_NO_INPUT without a target
+ * (or, for the three calls that read it, a source).  No call changes the handle's target, source, grid, last result
+ * (ndt_get_result), statistics (ndt_get_stats) or the ndt_diag_score_poses counters.  Dense and sparse voxel index, cloud and
+ * accumulated targets alike. */
+ndt_status ndt_calculate_nvtl(ndt_handle h, const void* cloud, size_t n, size_t stride_bytes, double* nvtl, size_t* n_found);
+ndt_status ndt_get_nvtl(ndt_handle h, double* nvtl, size_t* n_found);
+ndt_status ndt_nvtl_poses(ndt_handle h, const float* transforms /* n_poses*16 */, size_t n_poses, double* nvtl /* n_poses */,
+                          size_t* n_found /* n_poses or NULL */);
+ndt_status ndt_source_point_count(ndt_handle h, size_t* n_source);
+ndt_status ndt_source_point_nvtl(ndt_handle h, const float* transform /* 16 or NULL */, double* out /* n_source or NULL */,
+                                 const double** d_out, double* nvtl, size_t* n_found);
+ndt_status ndt_diag_nvtl(ndt_handle h, size_t* launches, size_t* blocks);
 
 /* ---- multi-GPU (one process per GPU, RCCL over xGMI) ---------------------------
  * The reference is a single process (ndt_omp_impl.hpp:206 is its only parallel construct); this is the exchange step

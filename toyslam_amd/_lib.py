@@ -147,6 +147,12 @@ SIGNATURES = {
     "ndt_diag_centroid_fitness": (C.c_int, [vp, szp, szp, fp, szp]),
     "ndt_score_poses": (C.c_int, [vp, fp, C.c_size_t, dp]),
     "ndt_diag_score_poses": (C.c_int, [vp, szp, szp]),
+    "ndt_calculate_nvtl": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, dp, szp]),
+    "ndt_get_nvtl": (C.c_int, [vp, dp, szp]),
+    "ndt_nvtl_poses": (C.c_int, [vp, fp, C.c_size_t, dp, szp]),
+    "ndt_source_point_count": (C.c_int, [vp, szp]),
+    "ndt_source_point_nvtl": (C.c_int, [vp, fp, dp, C.POINTER(C.c_void_p), dp, szp]),
+    "ndt_diag_nvtl": (C.c_int, [vp, szp, szp]),
     "ndt_align_guesses": (C.c_int, [vp, fp, C.c_size_t, fp, ip, ip, dp, ip]),
     "ndt_host_pick_top": (None, [dp, C.c_size_t, C.c_size_t, ip, szp]),
     "ndt_align_multistart": (C.c_int, [vp, fp, C.c_size_t, C.c_size_t, ip, szp, fp, ip, ip, dp, ip]),

@@ -23,6 +23,8 @@ void ndt_context::release_buffers() {
   server_counter.release();
   server_dbg.release();
   sp_poses.release();
+  nv_poses.release();
+  nv_points.release();
 }
 
 namespace ndtc {

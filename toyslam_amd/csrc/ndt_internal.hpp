@@ -8,6 +8,7 @@
 //   ndt_filter.hip : N1 voxel filter of one cloud (ndt_filter_batch.hip: of many)      ndt_map_batch.hip : N2 map accumulation
 //   ndt_fitness.hip : getFitnessScore      ndt_centroid_fitness.hip : the same against the voxel centroids, the centroid cloud
 //   ndt_score.hip : calculateScore (of a cloud, of the source under many poses)
+//   ndt_nvtl.hip  : nearest-voxel transformation likelihood (of a cloud, of the source under one or many poses, per point)
 //   ndt_eval.hip   : one evaluation (launch path), the persistent evaluation server's host side (mailbox protocol),
 //                    ndt_align, ndt_eval*, diagnostics and self-tests
 //   ndt_batch.hip  : lock-step batches (ndt_align_batch*, ndt_align_guesses, ndt_align_multistart), the RCCL communicator
@@ -471,6 +472,13 @@ struct ndt_context {
   size_t sp_pinned_bytes = 0;
   DevBuf<float> sp_poses;
   size_t sp_launches = 0, sp_blocks = 0;
+  // the nearest-voxel likelihood calls (ndt_nvtl.hip): the pose table of one chunk as above, L of every source point of the
+  // last ndt_source_point_nvtl (what its d_out names), and what the last call that reached the device did (ndt_diag_nvtl)
+  void* nv_pinned = nullptr;
+  size_t nv_pinned_bytes = 0;
+  DevBuf<float> nv_poses;
+  DevBuf<double> nv_points;
+  size_t nv_launches = 0, nv_blocks = 0;
   // ndt_target_accumulate* (ndt_accumulate.hip): the accumulated target -- alive while `grid` is its grid -- and what the last
   // call did (ndt_diag_target_accumulate)
   std::shared_ptr<ndtc::AccTarget> acc;
@@ -518,6 +526,7 @@ struct ndt_context {
     if (fb_rows) (void)hipHostFree(fb_rows);
     if (mb_pinned) (void)hipHostFree(mb_pinned);
     if (sp_pinned) (void)hipHostFree(sp_pinned);
+    if (nv_pinned) (void)hipHostFree(nv_pinned);
     acc.reset();
     release_buffers();
     if (host_result) (void)hipHostFree(host_result);
@@ -652,6 +661,9 @@ ndt_status fitness_many(ndt_context* h, const std::vector<FitnessJob>& jobs, dou
 // blocks of getFitnessScore over n source points (k_fitness's grid, a member's blocks of k_fitness_multi): 32 query teams per
 // block, at most 2048 blocks (the teams then stride over the queries)
 inline int fitness_blocks(int n) { return std::max(1, std::min(2048, (n + 31) / 32)); }
+// ---- ndt_score.hip
+// poses per launch of ndt_score_poses and ndt_nvtl_poses: one rule, one switch (NDT_SCORE_POSES_CHUNK)
+size_t poses_chunk(size_t n_poses, size_t row_bytes);
 // ---- ndt_filter.hip
 ndt_status filter_slots(ndt_handle h, int which, FilterPending& P);
 // The geometry and route of one N1 filter, from the cloud's box alone -- the one decision voxel_filter_enqueue and the

@@ -5,7 +5,8 @@
 //  K2  per-evaluation score / gradient / Hessian (computeDerivatives, ndt_omp_impl.hpp:179-285 with updateDerivatives
 //      :484-537 fused with the f32 point transform): k_derivatives (one launch per evaluation, also over a whole lock-step
 //      batch), k_batch_step (mixed-kind batch steps), the all-f64 Hessian k_hessian64 (computeHessian :540-645), k_reduce
-//      (fixed-order sum of the per-block rows), calculateScore (:935-983; k_score_poses: of one source under many poses), getFitnessScore (k_fitness; k_fitness_multi +
+//      (fixed-order sum of the per-block rows), calculateScore (:935-983; k_score_poses: of one source under many poses), the nearest-voxel
+//      transformation likelihood over the same neighbour probe (k_nvtl, k_nvtl_poses), getFitnessScore (k_fitness; k_fitness_multi +
 //      k_fitness_reduce for many members in one launch) and the search index it walks (k_cell_ranges, k_gather_points).
 //
 // Gather work: no MFMA (there is no dense contraction).  Loads are 16 B per lane (float4 points, 3 x dwordx4 per 64-B
@@ -486,34 +487,79 @@ __global__ __launch_bounds__(kBlock) void k_transform_multi(const TransformScan*
 
 // calculateScore (ndt_omp_impl.hpp:935-983) of ONE point, used as given, f64 throughout: its score increments are added to
 // `acc`.  The one body of k_calc_score and k_score_poses: a point gets the same terms in the same order from either.
+// The neighbour probe of calculateScore and of the nearest-voxel likelihood, in three pieces both bodies are made of.
+// score_cell: the voxel of a point used as given; false = the empty neighbour set (a non-finite point has a garbage voxel
+// index in the reference; a point more than a cell outside the box has no neighbour cell inside it).
+__device__ __forceinline__ bool score_cell(const GridView& gv, float px, float py, float pz, int& vi, int& vj, int& vk, unsigned& centre) {
+  if (!finite3(px, py, pz)) return false;
+  search_ijk(gv.g, px, py, pz, vi, vj, vk);
+  if (!near_grid(gv.g, vi, vj, vk)) return false;
+  centre = lut_index(gv.g, vi, vj, vk);
+  return true;
+}
+// score_probe: record of neighbour k of the search method (DIRECT1 / 7 / 26: probe over nb_offset; 27 = KDTREE: probe_kd over
+// the 3x3x3 block within r2), negative = none
+template <int NNB>
+__device__ __forceinline__ int score_probe(const GridView& gv, int vi, int vj, int vk, unsigned centre, int k, float px, float py, float pz,
+                                           float r2) {
+  int dx, dy, dz;
+  nb_offset<NNB>(k, dx, dy, dz);
+  return (NNB == 27) ? probe_kd(gv, vi, vj, vk, centre, dx, dy, dz, px, py, pz, r2) : probe(gv, vi, vj, vk, centre, dx, dy, dz);
+}
+// score_q: x^T C^-1 x of the point against record `rec`, f64, x = double(p) - mean, the leaf's f64 icov_ (:966)
+__device__ __forceinline__ double score_q(const GridView& gv, int rec, float px, float py, float pz) {
+  const double* mu = gv.recs[rec].mean;
+  const double* ic = gv.centroids[rec].icov;
+  const double x0 = static_cast<double>(px) - mu[0], x1 = static_cast<double>(py) - mu[1], x2 = static_cast<double>(pz) - mu[2];
+  const double c00 = ic[0], c01 = ic[1], c02 = ic[2], c11 = ic[3], c12 = ic[4], c22 = ic[5];
+  const double c0 = (c00 * x0 + c01 * x1) + c02 * x2;
+  const double c1 = (c01 * x0 + c11 * x1) + c12 * x2;
+  const double c2 = (c02 * x0 + c12 * x1) + c22 * x2;
+  return (x0 * c0 + x1 * c1) + x2 * c2;
+}
+
 template <int NNB>
 __device__ __forceinline__ void calc_score_point(const GridView& gv, float px, float py, float pz, double d1, double d2, double d3,
                                                  float r2, double& acc) {
-  if (!finite3(px, py, pz)) return;  // no neighbourhood in the reference (garbage voxel index): adds nothing
   int vi, vj, vk;
-  search_ijk(gv.g, px, py, pz, vi, vj, vk);
-  if (!near_grid(gv.g, vi, vj, vk)) return;
-  const unsigned centre = lut_index(gv.g, vi, vj, vk);
+  unsigned centre;
+  if (!score_cell(gv, px, py, pz, vi, vj, vk, centre)) return;  // adds nothing
   int rec[NNB];
   int cnt = 0;
   for (int k = 0; k < NNB; k++) {
-    int dx, dy, dz;
-    nb_offset<NNB>(k, dx, dy, dz);
-    rec[k] = (NNB == 27) ? probe_kd(gv, vi, vj, vk, centre, dx, dy, dz, px, py, pz, r2) : probe(gv, vi, vj, vk, centre, dx, dy, dz);
+    rec[k] = score_probe<NNB>(gv, vi, vj, vk, centre, k, px, py, pz, r2);
     cnt += (rec[k] >= 0);
   }
   for (int k = 0; k < NNB; k++) {
     if (rec[k] < 0) continue;
-    const double* mu = gv.recs[rec[k]].mean;
-    const double* ic = gv.centroids[rec[k]].icov;  // the leaf's f64 icov_ (:966)
-    const double x0 = static_cast<double>(px) - mu[0], x1 = static_cast<double>(py) - mu[1], x2 = static_cast<double>(pz) - mu[2];
-    const double c00 = ic[0], c01 = ic[1], c02 = ic[2], c11 = ic[3], c12 = ic[4], c22 = ic[5];
-    const double c0 = (c00 * x0 + c01 * x1) + c02 * x2;
-    const double c1 = (c01 * x0 + c11 * x1) + c12 * x2;
-    const double c2 = (c02 * x0 + c12 * x1) + c22 * x2;
-    const double e = exp(-d2 * ((x0 * c0 + x1 * c1) + x2 * c2) / 2);
+    const double e = exp(-d2 * score_q(gv, rec[k], px, py, pz) / 2);
     acc += (-d1 * e - d3) / cnt;
   }
+}
+
+// Nearest-voxel transformation likelihood of ONE point, used as given: calc_score_point's neighbour set, one pass over it,
+// q_min = the smallest x^T C^-1 x in neighbour order (starts at +inf, replaced whenever q < q_min: a NaN never wins), then
+// L = -d1 exp(-d2 q_min / 2): one exp per point.  false = the empty neighbour set (L untouched).  The one body of k_nvtl
+// and k_nvtl_poses.
+template <int NNB>
+__device__ __forceinline__ bool nvtl_point(const GridView& gv, float px, float py, float pz, double d1, double d2, float r2, double& L) {
+  int vi, vj, vk;
+  unsigned centre;
+  if (!score_cell(gv, px, py, pz, vi, vj, vk, centre)) return false;
+  double q_min = INFINITY;
+  bool found = false;
+  for (int k = 0; k < NNB; k++) {
+    const int rec = score_probe<NNB>(gv, vi, vj, vk, centre, k, px, py, pz, r2);
+    if (rec < 0) continue;
+    found = true;
+    const double q = score_q(gv, rec, px, py, pz);
+    if (q < q_min) q_min = q;
+  }
+  if (found) {
+#pragma clang fp contract(off)  // (the product is rounded on its own: a caller's sum cannot fuse with it)
+    L = -d1 * exp(-d2 * q_min / 2);
+  }
+  return found;
 }
 
 // calculateScore of a cloud used as given
@@ -550,6 +596,54 @@ __global__ __launch_bounds__(kBlock) void k_score_poses(const float4* __restrict
     calc_score_point<NNB>(gv, tx, ty, tz, d1, d2, d3, r2, acc[0]);
   }
   block_reduce_store<1>(acc, partials + (static_cast<size_t>(blockIdx.y) * gridDim.x + blockIdx.x) * kEvalStride, lds);
+}
+
+// Nearest-voxel transformation likelihood of one cloud: k_calc_score's walk (same grid extent, same stride).  has_pose: every
+// point is moved by `pose` first (xform_point, k_transform's arithmetic: the record launch_transform would have written);
+// else the cloud is used as given.  out (may be null): L of point i, -1.0 where it has no neighbour.  Row: slot 0 = the sum
+// of L over the found points, slot 1 = their count (f64: exact below 2^53).
+template <int NNB>
+__global__ __launch_bounds__(kBlock) void k_nvtl(const float4* __restrict__ cloud, int n, GridView gv, Pose12 pose, int has_pose, double d1,
+                                                 double d2, float r2, double* __restrict__ out, double* __restrict__ partials) {
+  __shared__ double lds[(kBlock / kWave) * 32];
+  double acc[2] = {0.0, 0.0};
+  for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+    const float4 pt = cloud[i];
+    float tx = pt.x, ty = pt.y, tz = pt.z;
+    if (has_pose) xform_point(pose.T, pt.x, pt.y, pt.z, tx, ty, tz);
+    double L = -1.0;
+    if (nvtl_point<NNB>(gv, tx, ty, tz, d1, d2, r2, L)) {
+      acc[0] += L;
+      acc[1] += 1.0;
+    }
+    if (out) out[i] = L;
+  }
+  block_reduce_store<2>(acc, partials + static_cast<size_t>(blockIdx.x) * kEvalStride, lds);
+}
+
+// ... of ONE resident source moved by MANY transforms (ndt_nvtl_poses): k_score_poses' layout -- blockIdx.y = pose of the
+// chunk (12 row-major floats, block-uniform: scalar loads), blockIdx.x = block of k_nvtl's walk, rows
+// partials[pose][block][kEvalStride] for one launch_reduce -- so pose g's row is the one k_nvtl writes for that pose.
+template <int NNB>
+__global__ __launch_bounds__(kBlock) void k_nvtl_poses(const float4* __restrict__ src, int n, GridView gv, const float* __restrict__ poses,
+                                                       double d1, double d2, float r2, double* __restrict__ partials) {
+  __shared__ double lds[(kBlock / kWave) * 32];
+  float T[12];
+  const float* __restrict__ Tg = poses + static_cast<size_t>(blockIdx.y) * 12;
+#pragma unroll
+  for (int k = 0; k < 12; k++) T[k] = Tg[k];
+  double acc[2] = {0.0, 0.0};
+  for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+    const float4 pt = src[i];
+    float tx, ty, tz;
+    xform_point(T, pt.x, pt.y, pt.z, tx, ty, tz);
+    double L;
+    if (nvtl_point<NNB>(gv, tx, ty, tz, d1, d2, r2, L)) {
+      acc[0] += L;
+      acc[1] += 1.0;
+    }
+  }
+  block_reduce_store<2>(acc, partials + (static_cast<size_t>(blockIdx.y) * gridDim.x + blockIdx.x) * kEvalStride, lds);
 }
 
 inline int grid_for(size_t n, int max_blocks) {
@@ -702,6 +796,30 @@ hipError_t launch_score_poses(const float4* src, int n, const GridView& gv, cons
   else if (search == 1) hipLaunchKernelGGL(k_score_poses<26>, grid, block, 0, stream, src, n, gv, d_poses, d1, d2, d3, r2, partials);
   else if (search == 3) hipLaunchKernelGGL(k_score_poses<1>, grid, block, 0, stream, src, n, gv, d_poses, d1, d2, d3, r2, partials);
   else hipLaunchKernelGGL(k_score_poses<7>, grid, block, 0, stream, src, n, gv, d_poses, d1, d2, d3, r2, partials);
+  return hipGetLastError();
+}
+
+hipError_t launch_nvtl(const float4* cloud, int n, const GridView& gv, const float* T12, double d1, double d2, int search, float r2,
+                       int n_blocks, double* d_out, double* partials, hipStream_t stream) {
+  Pose12 pose = {};
+  const int has_pose = T12 != nullptr;
+  for (int i = 0; i < 12 && has_pose; i++) pose.T[i] = T12[i];
+  const dim3 grid(n_blocks), block(kBlock);
+  if (search == 0) hipLaunchKernelGGL(k_nvtl<27>, grid, block, 0, stream, cloud, n, gv, pose, has_pose, d1, d2, r2, d_out, partials);
+  else if (search == 1) hipLaunchKernelGGL(k_nvtl<26>, grid, block, 0, stream, cloud, n, gv, pose, has_pose, d1, d2, r2, d_out, partials);
+  else if (search == 3) hipLaunchKernelGGL(k_nvtl<1>, grid, block, 0, stream, cloud, n, gv, pose, has_pose, d1, d2, r2, d_out, partials);
+  else hipLaunchKernelGGL(k_nvtl<7>, grid, block, 0, stream, cloud, n, gv, pose, has_pose, d1, d2, r2, d_out, partials);
+  return hipGetLastError();
+}
+
+hipError_t launch_nvtl_poses(const float4* src, int n, const GridView& gv, const float* d_poses, int n_poses, double d1, double d2,
+                             int search, float r2, int n_blocks, double* partials, hipStream_t stream) {
+  if (n_poses <= 0) return hipSuccess;
+  const dim3 grid(n_blocks, n_poses), block(kBlock);
+  if (search == 0) hipLaunchKernelGGL(k_nvtl_poses<27>, grid, block, 0, stream, src, n, gv, d_poses, d1, d2, r2, partials);
+  else if (search == 1) hipLaunchKernelGGL(k_nvtl_poses<26>, grid, block, 0, stream, src, n, gv, d_poses, d1, d2, r2, partials);
+  else if (search == 3) hipLaunchKernelGGL(k_nvtl_poses<1>, grid, block, 0, stream, src, n, gv, d_poses, d1, d2, r2, partials);
+  else hipLaunchKernelGGL(k_nvtl_poses<7>, grid, block, 0, stream, src, n, gv, d_poses, d1, d2, r2, partials);
   return hipGetLastError();
 }
 

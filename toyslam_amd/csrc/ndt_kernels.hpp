@@ -435,6 +435,19 @@ hipError_t launch_calc_score(const float4* cloud, int n, const GridView& gv, dou
 // n_poses).  With n_blocks = launch_calc_score's, pose g's rows are the ones launch_calc_score writes for launch_transform's cloud.
 hipError_t launch_score_poses(const float4* src, int n, const GridView& gv, const float* d_poses, int n_poses, double d1, double d2,
                               double d3, int search, float r2, int n_blocks, double* partials, hipStream_t stream);
+// Nearest-voxel transformation likelihood (k_nvtl, k_nvtl_poses; the definition: include/ndt_mi355.h).  Per point p with
+// calculateScore's neighbour set: L(p) = -d1 exp(-d2 q_min / 2), q_min the smallest x^T C^-1 x over the set; a point without a
+// neighbour is not found.  Rows: slot 0 = sum of L over the found points, slot 1 = their count, for launch_reduce.
+// launch_nvtl: one cloud, moved by T12 first (row-major 3x4; null = used as given); d_out (may be null): L per point in the
+// cloud's order, -1.0 where not found.  launch_nvtl_poses: launch_score_poses' layout; with the same n_blocks pose g's rows
+// are launch_nvtl's for that pose.
+struct Pose12 {
+  float T[12];
+};
+hipError_t launch_nvtl(const float4* cloud, int n, const GridView& gv, const float* T12, double d1, double d2, int search, float r2,
+                       int n_blocks, double* d_out, double* partials, hipStream_t stream);
+hipError_t launch_nvtl_poses(const float4* src, int n, const GridView& gv, const float* d_poses, int n_poses, double d1, double d2,
+                             int search, float r2, int n_blocks, double* partials, hipStream_t stream);
 
 hipError_t launch_voxel_centroids(const float4* pts, const unsigned* leaf_start, const int* leaf_count, int n_leaves,
                                   int* sorted_idx, float4* out, hipStream_t stream, const unsigned* d_totals = nullptr,

@@ -28,14 +28,19 @@ ndt_status ndt_calculate_score(ndt_handle h, const void* cloud, size_t n, size_t
   return NDT_OK;
 }
 
-// poses per k_score_poses launch (grid.y): NDT_SCORE_POSES_CHUNK, read once, 1 .. 65535
-static size_t score_poses_chunk() {
+}  // extern "C"
+
+// poses per launch (grid.y) of a call with n_poses, a pose's partial rows taking row_bytes: NDT_SCORE_POSES_CHUNK (read once,
+// 1 .. 65535, default 4096), fewer while a chunk's rows would pass 256 MiB (4096 poses x 1024 blocks would be 1 GiB)
+size_t ndtc::poses_chunk(size_t n_poses, size_t row_bytes) {
   static const size_t v = [] {
     const char* e = getenv("NDT_SCORE_POSES_CHUNK");
     return static_cast<size_t>(std::max(1, std::min(65535, e ? atoi(e) : 4096)));
   }();
-  return v;
+  return std::min(n_poses, std::max<size_t>(1, std::min(v, (size_t(256) << 20) / row_bytes)));
 }
+
+extern "C" {
 
 ndt_status ndt_score_poses(ndt_handle h, const float* transforms, size_t n_poses, double* scores) {
   ndt_status s = many_poses_checks(h, transforms, n_poses, scores, "transforms or scores");
@@ -54,9 +59,8 @@ ndt_status ndt_score_poses(ndt_handle h, const float* transforms, size_t n_poses
   }
   const ndt::Gauss gs = ndt::gauss_constants(h->resolution, h->outlier_ratio);
   const int nblk = ndt::derivative_blocks(static_cast<int>(n), NDT_DIRECT1);  // ndt_calculate_score's grid: the same walk
-  // a chunk's partial rows stay below 256 MiB whatever the source's size (4096 poses x 1024 blocks would be 1 GiB)
   const size_t row_bytes = static_cast<size_t>(nblk) * ndt::kEvalStride * sizeof(double);
-  const size_t chunk = std::min(n_poses, std::max<size_t>(1, std::min(score_poses_chunk(), (size_t(256) << 20) / row_bytes)));
+  const size_t chunk = poses_chunk(n_poses, row_bytes);
   s = ensure_host_rows(h, chunk);
   if (s) return s;
   s = pinned_at_least(h->sp_pinned, h->sp_pinned_bytes, chunk * 12 * sizeof(float), h->stream);

@@ -757,6 +757,55 @@ class NormalDistributionsTransform:
         check(self._L.ndt_diag_score_poses(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    # ---- nearest-voxel transformation likelihood (ndt_calculate_nvtl / ndt_get_nvtl / ndt_nvtl_poses / ndt_source_point_nvtl)
+    def calculateNVTL(self, cloud):
+        """(nvtl, n_found) of `cloud`, used as given, against the target: per point the likelihood of its best-fitting
+        neighbour voxel, averaged over the points that have a neighbour at all; (0.0, 0) when none has."""
+        a = _cloud(cloud)
+        v, nf = C.c_double(0), C.c_size_t(0)
+        check(self._L.ndt_calculate_nvtl(self._h, a.ctypes.data, a.shape[0], a.shape[1] * 4, C.byref(v), C.byref(nf)))
+        return v.value, nf.value
+
+    def getNVTL(self):
+        """(nvtl, n_found) of the input source moved by the last align's final transformation (ndt_get_nvtl)."""
+        v, nf = C.c_double(0), C.c_size_t(0)
+        check(self._L.ndt_get_nvtl(self._h, C.byref(v), C.byref(nf)))
+        return v.value, nf.value
+
+    def nvtlPoses(self, transforms, counts=False):
+        """NVTL of the input source moved by each of the 4x4 transforms, all poses in one launch per chunk: (G,) float64,
+        entry g the bits of calculateNVTL(transformPointCloud(source, transforms[g])).  counts=True: (nvtl, n_found)."""
+        T = self._pose_table(transforms)
+        G = T.shape[0]
+        out = np.zeros(max(G, 1), dtype=np.float64)
+        nf = np.zeros(max(G, 1), dtype=np.uintp)
+        check(self._L.ndt_nvtl_poses(self._h, _f(T) if G else None, G, _d(out), nf.ctypes.data_as(C.POINTER(C.c_size_t))))
+        return (out[:G].copy(), nf[:G].astype(np.int64)) if counts else out[:G].copy()
+
+    def sourcePointCount(self):
+        """Points of the input source (ndt_source_point_count); 0 without one."""
+        n = C.c_size_t(0)
+        check(self._L.ndt_source_point_count(self._h, C.byref(n)))
+        return n.value
+
+    def sourcePointNVTL(self, transform=None, device=False):
+        """(per_point, nvtl, n_found): the likelihood of every source point under `transform` (None: the last align's final
+        transformation) in the caller's point order, -1.0 where a point has no neighbour voxel, and the reduction of the same
+        launch.  device=True: per_point is the device pointer (valid until the next sourcePointNVTL) instead of an array."""
+        T = None if transform is None else _colmajor(transform)
+        n = self.sourcePointCount()
+        out = None if device else np.zeros(max(n, 1), dtype=np.float64)
+        dptr, v, nf = C.c_void_p(), C.c_double(0), C.c_size_t(0)
+        check(self._L.ndt_source_point_nvtl(self._h, _f(T) if T is not None else None, _d(out) if out is not None else None,
+                                            C.byref(dptr), C.byref(v), C.byref(nf)))
+        return (dptr.value if device else out[:n].copy()), v.value, nf.value
+
+    def nvtlLaunches(self):
+        """(launches, blocks of all of them) of the last NVTL call that reached the device (ndt_diag_nvtl)."""
+        a, b = C.c_size_t(0), C.c_size_t(0)
+        check(self._L.ndt_diag_nvtl(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def alignGuesses(self, guesses):
         """Register the input source from each of the 4x4 guesses in lock-step (ndt_align_guesses).  Returns alignBatch's
         dict, one entry per guess, plus best = index of the largest transformation probability (-1 if none)."""
@@ -771,14 +820,24 @@ class NormalDistributionsTransform:
         return dict(T=np.stack([_from_colmajor(T[k]) for k in range(G)]) if G else np.zeros((0, 4, 4), np.float32),
                     converged=conv[:G].astype(bool), iterations=it[:G].copy(), trans_probability=tp[:G].copy(), best=best.value)
 
-    def alignMultistart(self, candidates, keep):
+    def alignMultistart(self, candidates, keep, metric="score"):
         """scorePoses over the candidates, the `keep` best of them (host_pick_top) as the guesses of one alignGuesses
         (ndt_align_multistart).  Returns alignGuesses' dict over the picked members, plus picked = their candidate indices;
-        best indexes the candidates."""
+        best indexes the candidates.  metric="nvtl": the candidates are ranked by nvtlPoses instead (composed here from
+        nvtlPoses, host_pick_top and alignGuesses)."""
+        if metric not in ("score", "nvtl"):
+            raise ValueError("metric must be 'score' or 'nvtl'")
         c = self._pose_table(candidates)
         n, keep = c.shape[0], int(keep)
         if keep < 0:
             raise ValueError("keep must be >= 0")
+        if metric == "nvtl":
+            cand = c.reshape(-1, 4, 4).transpose(0, 2, 1)
+            picked = host_pick_top(self.nvtlPoses(cand), keep) if n and keep else np.zeros(0, dtype=np.int32)
+            r = self.alignGuesses(cand[picked])
+            r["picked"] = picked
+            r["best"] = int(picked[r["best"]]) if r["best"] >= 0 else -1
+            return r
         room = max(min(keep, n), 1)
         picked = np.zeros(room, dtype=np.int32)
         T = np.zeros((room, 16), dtype=np.float32)
