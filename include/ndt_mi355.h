@@ -798,6 +798,21 @@ ndt_status ndt_profile_enable(ndt_handle h, int on);
  * in flight on the same device uses the launch path: the persistent kernel holds its CUs for a whole registration, so
  * concurrent callers would otherwise take turns at it; calling this with 1 insists on the persistent kernel. */
 ndt_status ndt_set_evaluation_path(ndt_handle h, int persistent);
+/* Evaluation reuse (on by default; NDT_EVAL_REUSE=0 turns the default off).  What is reused: the answer to the last request of
+ * the same kind, when the next request (kind, matrix T, pose p) equals it byte for byte -- the trials a More-Thuente line
+ * search repeats once its step is clamped to transformation_epsilon / 2.  Why it is exact: an evaluation is a function of
+ * its request (fixed-order sums, bit-identical from run to run), so the device would return the same bits.
+ * ndt_align, ndt_align_batch*, ndt_align_pairs*, ndt_align_guesses and ndt_align_multistart use it; results and ndt_get_stats
+ * (the algorithm's counts, reused steps included) do not change.  Never used under ndt_profile_enable(h, 1), with a
+ * communicator or an all-reduce hook, nor by ndt_host_run_driver: there the number of evaluations is itself observed.
+ * ndt_diag_eval_reuse: of the last align / batch call, *served evaluations the device answered (summed over members) and
+ * *reused steps the solvers fed themselves; served + reused = n_evals + n_hessian_recomputes of ndt_get_stats. */
+ndt_status ndt_set_evaluation_reuse(ndt_handle h, int on);
+ndt_status ndt_diag_eval_reuse(ndt_handle h, long long* served, long long* reused);
+/* Diagnostic: the evaluation of `kind` (0 with Hessian, 1 without, 2 f64 Hessian) at pose p, asked n_times of one running
+ * evaluation server; rows receives n_times x 43 doubles (score, g[6], H[36] row-major; H is zero for kind 1).  What evaluation
+ * reuse rests on can be read from it: the rows are equal bit for bit (ndt_eval is the launch path's counterpart). */
+ndt_status ndt_diag_eval_server(ndt_handle h, const double* p, int kind, int n_times, double* rows);
 ndt_status ndt_profile_read(ndt_handle h, int kind, long long* n_launches, double* total_ms, int reset);
 
 /* Device self-test of the wave64 fold reduction used by every kernel epilogue: n_blocks blocks
@@ -881,6 +896,13 @@ ndt_status ndt_host_run_driver(ndt_eval_cb cb, void* user, size_t n_source, cons
                                double step_size, double outlier_ratio, double trans_eps, int max_iter,
                                float* final_transformation, int* has_converged, int* final_num_iteration,
                                double* transformation_probability, int* n_evals, int* n_hessian_recomputes);
+/* The same driver with evaluation reuse on (ndt_set_evaluation_reuse): a request byte-equal to the last answered one of its
+ * kind is not passed to cb; the driver takes that answer again, which is exact for an evaluator that is a function of its
+ * request.  cb is called n_evals + n_hessian_recomputes - *n_reused times; every other output is as ndt_host_run_driver's. */
+ndt_status ndt_host_run_driver_reuse(ndt_eval_cb cb, void* user, size_t n_source, const float* guess, float resolution,
+                                     double step_size, double outlier_ratio, double trans_eps, int max_iter,
+                                     float* final_transformation, int* has_converged, int* final_num_iteration,
+                                     double* transformation_probability, int* n_evals, int* n_hessian_recomputes, int* n_reused);
 
 #ifdef __cplusplus
 }

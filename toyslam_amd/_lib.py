@@ -190,6 +190,11 @@ SIGNATURES = {
     "ndt_host_thread_plan": (None, [C.c_int, C.c_double, C.c_int, ip, ip]),
     "ndt_host_run_driver": (C.c_int, [EVAL_CB, vp, C.c_size_t, fp, C.c_float, C.c_double, C.c_double, C.c_double,
                                       C.c_int, fp, ip, ip, dp, ip, ip]),
+    "ndt_host_run_driver_reuse": (C.c_int, [EVAL_CB, vp, C.c_size_t, fp, C.c_float, C.c_double, C.c_double, C.c_double,
+                                            C.c_int, fp, ip, ip, dp, ip, ip, ip]),
+    "ndt_set_evaluation_reuse": (C.c_int, [vp, C.c_int]),
+    "ndt_diag_eval_reuse": (C.c_int, [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "ndt_diag_eval_server": (C.c_int, [vp, dp, C.c_int, C.c_int, dp]),
     "ndt_pcd_sequence_open": (C.c_int, [C.c_char_p, C.POINTER(vp)]),
     "ndt_pcd_sequence_poll": (C.c_int, [vp, C.c_size_t, szp]),
     "ndt_pcd_sequence_next": (C.c_int, [vp, C.POINTER(vp), szp, ip, ip]),

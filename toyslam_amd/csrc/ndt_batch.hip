@@ -361,8 +361,10 @@ ndt_status lock_step(ndt_context* h, const LockStepMembers& m, size_t n_local, c
   int* active = reinterpret_cast<int*>(descs + total);
   std::vector<int> live_kind(total, ndt::EVAL_NONE);  // what every scan's solver asked for this step, local or not
   size_t max_n = 0;
+  ndt::SolverParams sp = solver_params(h);
+  sp.reuse_evaluations = eval_reuse_now(h);  // a member whose line search repeats a trial at an unchanged pose asks less often
   for (size_t g = 0; g < total; g++) {
-    solvers[g].start(guesses ? guesses + 16 * g : nullptr, counts[g], solver_params(h));
+    solvers[g].start(guesses ? guesses + 16 * g : nullptr, counts[g], sp);
     descs[g].offset = 0;
     descs[g].count = 0;
     descs[g].pad = 0;
@@ -402,6 +404,11 @@ ndt_status lock_step(ndt_context* h, const LockStepMembers& m, size_t n_local, c
   std::vector<double> nn_row(total, 0.0);
   double nn_sum = 0, pts_sum = 0;
   long long evals_f32 = 0, evals_h64 = 0;
+  // ... which stay the algorithm's counts: the steps a solver fed itself (evaluation reuse) are added, by kind, with the
+  // neighbours of the served evaluation they repeat (the last one of that kind)
+  std::vector<double> nn_kind(2 * total, 0.0);
+  std::vector<int> self_fed(3 * total, 0);
+  long long n_served = 0, n_self_fed = 0;
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
   for (;;) {
@@ -521,10 +528,14 @@ ndt_status lock_step(ndt_context* h, const LockStepMembers& m, size_t n_local, c
       if (live_kind[g] == ndt::EVAL_NONE) return;
       ndt::EvalResult r;
       unpack_row(h->host_result + g * ndt::kEvalStride, live_kind[g] != ndt::EVAL_NO_HESSIAN, r, &nn_row[g]);
+      if (live_kind[g] != ndt::EVAL_HESSIAN_F64) nn_kind[2 * g + live_kind[g]] = nn_row[g];
+      for (int k = 0; k < 3; k++) self_fed[3 * g + k] = -solvers[g].reused_by_kind[k];
       solvers[g].feed(r);
+      for (int k = 0; k < 3; k++) self_fed[3 * g + k] += solvers[g].reused_by_kind[k];
     });
     for (size_t g = 0; g < total; g++) {
       if (live_kind[g] == ndt::EVAL_NONE) continue;
+      n_served++;
       if (live_kind[g] == ndt::EVAL_HESSIAN_F64) {
         evals_h64++;
       } else {
@@ -532,6 +543,18 @@ ndt_status lock_step(ndt_context* h, const LockStepMembers& m, size_t n_local, c
         nn_sum += nn_row[g];
         pts_sum += static_cast<double>(counts[g]);
       }
+      for (int k = 0; k < 2; k++) {
+        const int d = self_fed[3 * g + k];
+        evals_f32 += d;
+        nn_sum += d * nn_kind[2 * g + k];
+        pts_sum += d * static_cast<double>(counts[g]);
+      }
+      evals_h64 += self_fed[3 * g + 2];
+      n_self_fed += self_fed[3 * g] + self_fed[3 * g + 1] + self_fed[3 * g + 2];
+      if (trace_scan >= 0 && g == static_cast<size_t>(trace_scan))
+        for (int k = 0; k < 3; k++)
+          for (int i = 0; i < self_fed[3 * g + k]; i++)
+            std::fprintf(stderr, "[trace] kind %d reused: the request and the answer of the last kind %d line\n", k, k);
     }
     const auto tb3 = now();
     static const bool step_dump = [] { const char* v = getenv("NDT_TIMING"); return v && atoi(v) >= 2; }();
@@ -548,6 +571,8 @@ ndt_status lock_step(ndt_context* h, const LockStepMembers& m, size_t n_local, c
   h->n_hess = static_cast<int>(std::min<long long>(evals_h64, INT32_MAX));
   h->mean_neighbors = pts_sum > 0 ? nn_sum / pts_sum : 0.0;
   h->batch_lock_steps = n_steps;
+  h->reuse_served = n_served;
+  h->reuse_reused = n_self_fed;
   for (size_t g = 0; g < total; g++) {
     if (final_T) std::memcpy(final_T + 16 * g, solvers[g].final_T, 16 * sizeof(float));
     if (conv) conv[g] = solvers[g].converged ? 1 : 0;
@@ -640,6 +665,7 @@ ndt_status run_groups(ndt_context* h, size_t n_scans, size_t groups, const std::
     w->search = h->search;
     w->min_pts = h->min_pts;
     w->eig_ratio = h->eig_ratio;
+    w->eval_reuse = h->eval_reuse;
     w->target = h->target;
     w->target_dense = h->target_dense;
     w->grid = h->grid;
@@ -659,7 +685,7 @@ ndt_status run_groups(ndt_context* h, size_t n_scans, size_t groups, const std::
     w->target.reset();
     w->grid.reset();
   }
-  long long ne = 0, nh = 0;
+  long long ne = 0, nh = 0, served = 0, reused = 0;
   double nn_w = 0, pts_w = 0;
   int steps = 0;
   for (size_t g = 0; g < groups; g++) {
@@ -672,7 +698,11 @@ ndt_status run_groups(ndt_context* h, size_t n_scans, size_t groups, const std::
     nn_w += w->mean_neighbors * evals_pts;
     pts_w += evals_pts;
     steps = std::max(steps, w->batch_lock_steps);
+    served += w->reuse_served;
+    reused += w->reuse_reused;
   }
+  h->reuse_served = served;
+  h->reuse_reused = reused;
   h->n_evals = static_cast<int>(std::min<long long>(ne, INT32_MAX));
   h->n_hess = static_cast<int>(std::min<long long>(nh, INT32_MAX));
   h->mean_neighbors = pts_w > 0 ? nn_w / pts_w : 0.0;

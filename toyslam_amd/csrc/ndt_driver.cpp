@@ -401,6 +401,10 @@ void ScanSolver::start(const float* guess, size_t n_source, const SolverParams& 
   converged = false;
   trans_probability = 0;
   n_evals = n_hess = 0;
+  n_reused = 0;
+  reused_by_kind[0] = reused_by_kind[1] = reused_by_kind[2] = 0;
+  last_f32_kind = EVAL_WITH_HESSIAN;
+  for (Answered& a : answered_) a.valid = false;
   // pcl::Registration::align resets final_transformation_ to Identity; a
   // non-identity guess replaces it (ndt_omp_impl.hpp:95-101)
   for (int i = 0; i < 16; i++) final_T[i] = (i % 5 == 0) ? 1.0f : 0.0f;
@@ -508,7 +512,40 @@ void ScanSolver::mt_finish() {
   newton_top();
 }
 
+namespace {
+// kind, T and p as bytes (field by field: the struct has padding)
+inline bool same_request(const EvalRequest& a, const EvalRequest& b) {
+  return a.kind == b.kind && std::memcmp(a.T, b.T, sizeof(a.T)) == 0 && std::memcmp(a.p, b.p, sizeof(a.p)) == 0;
+}
+}  // namespace
+
 void ScanSolver::feed(const EvalResult& r) {
+  if (state_ == S_DONE) return;
+  if (!prm_.reuse_evaluations) {
+    step(r);
+    return;
+  }
+  {
+    Answered& a = answered_[req_.kind];
+    a.valid = true;
+    a.req = req_;
+    a.res = r;
+    step(a.res);
+  }
+  // At the noise floor of the f32 objective the More-Thuente interval collapses onto step_min_ and issue_trial() asks the
+  // same question until kMaxStepIterations runs out (mt_check's clamp): those steps are taken here, with the answer
+  // the question got before.
+  while (state_ != S_DONE) {
+    const Answered& a = answered_[req_.kind];
+    if (!a.valid || !same_request(a.req, req_)) break;
+    n_reused++;
+    reused_by_kind[req_.kind]++;
+    step(a.res);
+  }
+}
+
+void ScanSolver::step(const EvalResult& r) {
+  if (req_.kind != EVAL_HESSIAN_F64) last_f32_kind = req_.kind;
   switch (state_) {
     case S_INIT:
       n_evals++;

@@ -64,6 +64,9 @@ struct SolverParams {
   double outlier_ratio = 0.55;
   double trans_eps = 0.1;
   int max_iter = 35;
+  // Evaluation reuse: a request byte-equal (kind, T, p) to the last one of its kind that was answered is not handed out
+  // again; the solver feeds itself the remembered answer.  Exact as long as the evaluator is a function of the request.
+  bool reuse_evaluations = false;
 };
 
 class ScanSolver {
@@ -71,6 +74,8 @@ class ScanSolver {
   void start(const float* guess /*16 col-major or nullptr*/, size_t n_source, const SolverParams& prm);
   bool done() const { return state_ == S_DONE; }
   const EvalRequest& request() const { return req_; }
+  // one answer from the evaluator; with SolverParams::reuse_evaluations the solver then goes on by itself, step after
+  // step, for as long as its next request repeats an answered one (a loop, not a recursion)
   void feed(const EvalResult& r);
 
   // results (valid once done())
@@ -78,7 +83,12 @@ class ScanSolver {
   bool converged = false;
   int nr_iterations = 0;
   double trans_probability = 0;
-  int n_evals = 0, n_hess = 0;
+  int n_evals = 0, n_hess = 0;  // the algorithm's counts: self-fed steps included
+  // self-fed steps since start(), in all and by kind; the kind of the last step (served or self-fed) of an f32 kind --
+  // what a caller needs to keep per-evaluation side values (neighbour counts) of the steps it never saw
+  int n_reused = 0;
+  int reused_by_kind[3] = {0, 0, 0};
+  int last_f32_kind = EVAL_WITH_HESSIAN;
 
  private:
   enum State { S_INIT, S_MT_FIRST, S_MT_LOOP, S_MT_HESS, S_DONE };
@@ -95,6 +105,15 @@ class ScanSolver {
   bool interval_converged_, open_interval_;
   int step_iterations_;
 
+  // the last answered request of every kind and its answer (cleared by start())
+  struct Answered {
+    bool valid = false;
+    EvalRequest req;
+    EvalResult res;
+  };
+  Answered answered_[3];
+
+  void step(const EvalResult& r);
   void newton_top();
   void mt_check();
   void mt_finish();

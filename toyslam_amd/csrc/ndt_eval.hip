@@ -379,8 +379,11 @@ ndt_status ndt_align(ndt_handle h, const float* guess, float* final_transformati
     HIP_TRY(hipStreamSynchronize(h->stream));
     n_total = static_cast<size_t>(row[0]);
   }
-  solver.start(guess, n_total, solver_params(h));
-  double nn = 0;
+  ndt::SolverParams sp = solver_params(h);
+  sp.reuse_evaluations = eval_reuse_now(h);  // a trial the line search repeats at an unchanged pose is not sent again
+  solver.start(guess, n_total, sp);
+  double nn_kind[2] = {0, 0};  // neighbours of the last served evaluation of either f32 kind
+  long long n_served = 0;
   const ndt::Gauss gs_align = ndt::gauss_constants(h->resolution, h->outlier_ratio);
   struct ServerGuard {  // whatever path leaves align, the server is told to exit
     ndt_context* c;
@@ -439,17 +442,27 @@ ndt_status ndt_align(ndt_handle h, const float* guess, float* final_transformati
       s = evaluate_single(h, solver.request(), r, &nn_step);
       if (s) return s;
     }
-    if (counts_neighbors) nn = nn_step;
+    if (counts_neighbors) nn_kind[solver.request().kind] = nn_step;
+    n_served++;
     static const bool trace = [] { const char* v = getenv("NDT_ALIGN_TRACE"); return v && atoi(v) != 0; }();
     if (trace) {
       const ndt::EvalRequest& rq = solver.request();
       std::fprintf(stderr, "[trace] kind %d p %.17g %.17g %.17g %.17g %.17g %.17g -> score %.17g g0 %.17g g5 %.17g H00 %.17g nn %.17g\n", static_cast<int>(rq.kind),
                    rq.p[0], rq.p[1], rq.p[2], rq.p[3], rq.p[4], rq.p[5], r.score, r.g[0], r.g[5], r.H[0], nn_step);
     }
+    const int reused_before[3] = {solver.reused_by_kind[0], solver.reused_by_kind[1], solver.reused_by_kind[2]};
     const auto ts0 = std::chrono::steady_clock::now();
     solver.feed(r);
     h->t_solver += std::chrono::duration<double>(std::chrono::steady_clock::now() - ts0).count();
+    if (trace)
+      for (int k = 0; k < 3; k++)
+        for (int i = reused_before[k]; i < solver.reused_by_kind[k]; i++)
+          std::fprintf(stderr, "[trace] kind %d reused: the request and the answer of the last kind %d line\n", k, k);
   }
+  h->reuse_served = n_served;
+  h->reuse_reused = solver.n_reused;
+  // (a self-fed step has the neighbours of the evaluation it repeats, which is the last served one of its kind)
+  const double nn = nn_kind[solver.last_f32_kind];
   static const bool timing = [] { const char* v = getenv("NDT_TIMING"); return v && atoi(v) != 0; }();
   if (timing) {
     std::fprintf(stderr, "[ndt timing] evals=%d launch=%.1fus wait=%.1fus solver=%.1fus first-eval=%.1fus longest-poll-gap=%.1fus (per align)\n",
@@ -753,6 +766,35 @@ ndt_status ndt_selftest_server_idle(ndt_handle h, const double* p, int stall_ms,
     return s ? s : fail(NDT_ERR_HIP, "fresh server did not serve");
   }
   scores[2] = r.score;
+  return server_stop(h);
+}
+
+ndt_status ndt_diag_eval_server(ndt_handle h, const double* p, int kind, int n_times, double* rows) {
+  if (!h || !p || !rows || kind < 0 || kind > 2 || n_times <= 0) return fail(NDT_ERR_INVALID, "bad arguments");
+  ndt_status s = check_ready(h);
+  if (s) return s;
+  if (h->source->k2_n() == 0 || h->grid->empty) return fail(NDT_ERR_INVALID, "empty inputs");
+  const ndt::Gauss gs = ndt::gauss_constants(h->resolution, h->outlier_ratio);
+  ndt::EvalRequest rq;
+  rq.kind = static_cast<ndt::EvalKind>(kind);
+  std::memcpy(rq.p, p, sizeof(rq.p));
+  ndt::pose_to_matrix(p, rq.T);
+  h->server_out_host = nullptr;
+  s = server_start(h);
+  if (s) return s;
+  for (int i = 0; i < n_times; i++) {
+    ndt::EvalResult r;
+    bool served = false;
+    s = server_evaluate(h, rq, gs, r, nullptr, &served);
+    if (s || !served) {
+      (void)server_stop(h);
+      return s ? s : fail(NDT_ERR_HIP, "the server did not serve");
+    }
+    double* row = rows + static_cast<size_t>(i) * 43;
+    row[0] = r.score;
+    std::memcpy(row + 1, r.g, sizeof(r.g));
+    std::memcpy(row + 7, r.H, sizeof(r.H));
+  }
   return server_stop(h);
 }
 

@@ -133,6 +133,12 @@ ndt::SolverParams solver_params(const ndt_context* h) {
   return sp;
 }
 
+bool eval_reuse_now(const ndt_context* h) {
+  static const bool by_default = [] { const char* v = getenv("NDT_EVAL_REUSE"); return !v || atoi(v) != 0; }();
+  const bool wanted = h->eval_reuse < 0 ? by_default : h->eval_reuse != 0;
+  return wanted && !h->profiling && !h->comm && !h->allreduce;
+}
+
 }  // namespace ndtc
 
 extern "C" {
@@ -167,6 +173,7 @@ ndt_status ndt_clone(ndt_handle src, ndt_handle* out) {
   h->search = src->search;
   h->num_threads = src->num_threads;
   h->persistent = src->persistent;
+  h->eval_reuse = src->eval_reuse;
   h->cu_partition = src->cu_partition;
   h->voxel_index = src->voxel_index;
   h->min_pts = src->min_pts;
@@ -319,6 +326,13 @@ ndt_status ndt_set_neighborhood_search_method(ndt_handle h, int m) {
   return NDT_OK;
 }
 ndt_status ndt_set_evaluation_path(ndt_handle h, int persistent) { if (!h) return fail(NDT_ERR_INVALID, "null"); h->persistent = persistent ? 1 : 0; return NDT_OK; }
+ndt_status ndt_set_evaluation_reuse(ndt_handle h, int on) { if (!h) return fail(NDT_ERR_INVALID, "null"); h->eval_reuse = on ? 1 : 0; return NDT_OK; }
+ndt_status ndt_diag_eval_reuse(ndt_handle h, long long* served, long long* reused) {
+  if (!h) return fail(NDT_ERR_INVALID, "null handle");
+  if (served) *served = h->reuse_served;
+  if (reused) *reused = h->reuse_reused;
+  return NDT_OK;
+}
 ndt_status ndt_set_num_threads(ndt_handle h, int n) { if (!h) return fail(NDT_ERR_INVALID, "null"); h->num_threads = n; return NDT_OK; }
 ndt_status ndt_set_min_points_per_voxel(ndt_handle h, int n) {
   if (!h) return fail(NDT_ERR_INVALID, "null");
@@ -439,10 +453,10 @@ void ndt_host_gauss(float resolution, double outlier_ratio, double* d) {
   d[2] = g.d3;
 }
 
-ndt_status ndt_host_run_driver(ndt_eval_cb cb, void* user, size_t n_source, const float* guess, float resolution,
-                               double step_size, double outlier_ratio, double trans_eps, int max_iter,
-                               float* final_transformation, int* has_converged, int* final_num_iteration,
-                               double* transformation_probability, int* n_evals, int* n_hess) {
+static ndt_status host_run_driver(bool reuse, ndt_eval_cb cb, void* user, size_t n_source, const float* guess, float resolution,
+                                  double step_size, double outlier_ratio, double trans_eps, int max_iter,
+                                  float* final_transformation, int* has_converged, int* final_num_iteration,
+                                  double* transformation_probability, int* n_evals, int* n_hess, int* n_reused) {
   if (!cb) return fail(NDT_ERR_INVALID, "null callback");
   ndt::SolverParams sp;
   sp.resolution = resolution;
@@ -450,6 +464,7 @@ ndt_status ndt_host_run_driver(ndt_eval_cb cb, void* user, size_t n_source, cons
   sp.outlier_ratio = outlier_ratio;
   sp.trans_eps = trans_eps;
   sp.max_iter = max_iter;
+  sp.reuse_evaluations = reuse;
   ndt::ScanSolver solver;
   solver.start(guess, n_source, sp);
   while (!solver.done()) {
@@ -465,7 +480,24 @@ ndt_status ndt_host_run_driver(ndt_eval_cb cb, void* user, size_t n_source, cons
   if (transformation_probability) *transformation_probability = solver.trans_probability;
   if (n_evals) *n_evals = solver.n_evals;
   if (n_hess) *n_hess = solver.n_hess;
+  if (n_reused) *n_reused = solver.n_reused;
   return NDT_OK;
+}
+
+ndt_status ndt_host_run_driver(ndt_eval_cb cb, void* user, size_t n_source, const float* guess, float resolution,
+                               double step_size, double outlier_ratio, double trans_eps, int max_iter,
+                               float* final_transformation, int* has_converged, int* final_num_iteration,
+                               double* transformation_probability, int* n_evals, int* n_hess) {
+  return host_run_driver(false, cb, user, n_source, guess, resolution, step_size, outlier_ratio, trans_eps, max_iter, final_transformation,
+                         has_converged, final_num_iteration, transformation_probability, n_evals, n_hess, nullptr);
+}
+
+ndt_status ndt_host_run_driver_reuse(ndt_eval_cb cb, void* user, size_t n_source, const float* guess, float resolution,
+                                     double step_size, double outlier_ratio, double trans_eps, int max_iter,
+                                     float* final_transformation, int* has_converged, int* final_num_iteration,
+                                     double* transformation_probability, int* n_evals, int* n_hess, int* n_reused) {
+  return host_run_driver(true, cb, user, n_source, guess, resolution, step_size, outlier_ratio, trans_eps, max_iter, final_transformation,
+                         has_converged, final_num_iteration, transformation_probability, n_evals, n_hess, n_reused);
 }
 
 }  // extern "C"

@@ -406,6 +406,11 @@ struct ndt_context {
   std::shared_ptr<DeviceCloud> n1_in, n1_out;
   int voxel_index = 0;              // ndt_set_voxel_index: 0 automatic, 1 dense table, 2 sparse (sorted build + hash look-up)
   int persistent = -1;  // -1 = default (NDT_PERSISTENT / on), 0 = launch per evaluation, 1 = server
+  // ndt_set_evaluation_reuse: -1 = default (NDT_EVAL_REUSE / on), 0 = every evaluation is asked of the device, 1 = a solver
+  // answers a repeated request itself (ScanSolver, SolverParams::reuse_evaluations); and, for ndt_diag_eval_reuse, the
+  // evaluations the last align / batch call was served by the device and the steps its solvers fed themselves
+  int eval_reuse = -1;
+  long long reuse_served = 0, reuse_reused = 0;
   // Two command mailboxes, used by alternate server instances: a server told to finish (transform +
   // exit) is not waited for, and the next instance's first command must not overwrite the line the
   // old one may still be reading.
@@ -567,6 +572,9 @@ int side_cus();
 ndt_status ensure_device(ndt_context* h);
 ndt_status ensure_host_rows(ndt_context* h, size_t rows);
 ndt::SolverParams solver_params(const ndt_context* h);
+// may this handle's solvers reuse evaluations now?  Off where the number of evaluations is itself observed: event pairs per
+// evaluation (ndt_profile_enable(h, 1)) and the exchange modes, whose legs count a collective per evaluation.
+bool eval_reuse_now(const ndt_context* h);
 // page-locked scratch of a handle, grown on demand; `reader`: the stream whose queued copies may still read the old block
 // (waited for before it is freed).  Rewriting the block is the caller's to order: only behind a wait for what reads it
 ndt_status pinned_at_least(void*& p, size_t& have, size_t bytes, hipStream_t reader);

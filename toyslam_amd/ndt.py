@@ -1016,6 +1016,26 @@ class NormalDistributionsTransform:
         """True (default): one persistent kernel per registration; False: one launch per evaluation."""
         check(self._L.ndt_set_evaluation_path(self._h, int(bool(persistent))))
 
+    def setEvaluationReuse(self, on):
+        """True (default, NDT_EVAL_REUSE): a request that repeats the last answered one of its kind byte for byte is not
+        sent to the device again (the trials a line search repeats at an unchanged pose); same results, same stats()."""
+        check(self._L.ndt_set_evaluation_reuse(self._h, int(bool(on))))
+
+    def evalReuse(self):
+        """(served, reused) of the last align / batch / pairs call: evaluations the device answered, summed over the
+        members, and steps the solvers fed themselves; served + reused == n_evals + n_hessian_recomputes of stats()."""
+        served, reused = C.c_longlong(0), C.c_longlong(0)
+        check(self._L.ndt_diag_eval_reuse(self._h, C.byref(served), C.byref(reused)))
+        return served.value, reused.value
+
+    def evalServer(self, p, kind, n_times=2):
+        """The evaluation of `kind` (0, 1, 2 = f64 Hessian) at pose p asked n_times of one running evaluation server
+        (ndt_diag_eval_server) -> (n_times, 43) float64: score, g[6], H[36]."""
+        p = np.ascontiguousarray(p, dtype=np.float64)
+        rows = np.zeros((int(n_times), 43))
+        check(self._L.ndt_diag_eval_server(self._h, _d(p), int(kind), int(n_times), _d(rows)))
+        return rows
+
     def profile(self, on):
         check(self._L.ndt_profile_enable(self._h, int(on)))
 
@@ -1263,9 +1283,10 @@ def host_gauss(resolution, outlier_ratio):
 
 
 def host_run_driver(evaluator, n_source, guess=None, resolution=1.0, step_size=0.1, outlier_ratio=0.55,
-                    trans_eps=0.1, max_iter=35):
+                    trans_eps=0.1, max_iter=35, reuse=False):
     """Run the PRODUCT Newton/More-Thuente driver against a Python evaluator
-    evaluator(kind, T(4x4), p(6)) -> (score, g(6), H(6x6))."""
+    evaluator(kind, T(4x4), p(6)) -> (score, g(6), H(6x6)).  reuse=True: with evaluation reuse
+    (ndt_host_run_driver_reuse); the result then carries n_reused, the steps the driver fed itself."""
     def tramp(_user, kind, Tp, pp, score, g, H):
         try:
             T = _from_colmajor(np.ctypeslib.as_array(Tp, shape=(16,)))
@@ -1287,11 +1308,18 @@ def host_run_driver(evaluator, n_source, guess=None, resolution=1.0, step_size=0
     T = np.zeros(16, dtype=np.float32)
     conv, it, ne, nh = (C.c_int(0) for _ in range(4))
     tp = C.c_double(0)
-    check(_lib.lib().ndt_host_run_driver(cb, None, n_source, _f(g) if g is not None else None, resolution, step_size,
-                                         outlier_ratio, trans_eps, max_iter, _f(T), C.byref(conv), C.byref(it),
-                                         C.byref(tp), C.byref(ne), C.byref(nh)))
-    return dict(T=_from_colmajor(T), converged=bool(conv.value), iterations=it.value, trans_probability=tp.value,
-                n_evals=ne.value, n_hessian_recomputes=nh.value)
+    args = (cb, None, n_source, _f(g) if g is not None else None, resolution, step_size, outlier_ratio, trans_eps, max_iter,
+            _f(T), C.byref(conv), C.byref(it), C.byref(tp), C.byref(ne), C.byref(nh))
+    nr = C.c_int(0)
+    if reuse:
+        check(_lib.lib().ndt_host_run_driver_reuse(*args, C.byref(nr)))
+    else:
+        check(_lib.lib().ndt_host_run_driver(*args))
+    out = dict(T=_from_colmajor(T), converged=bool(conv.value), iterations=it.value, trans_probability=tp.value,
+               n_evals=ne.value, n_hessian_recomputes=nh.value)
+    if reuse:
+        out["n_reused"] = nr.value
+    return out
 
 
 def extract_file_number(stem):
