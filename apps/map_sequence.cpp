@@ -22,7 +22,7 @@
 // after the other, 2.7 ms overlapped, 3.7 ms overlapped on CU partitions -- the steps are short host-paced sequences of
 // pageable copies and small launches, and two threads driving them get in each other's way; hence not the default.
 //
-//   map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> [voxel_leaf_size (0.5 | 0.3)] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]
+//   map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> [voxel_leaf_size (0.5 | 0.3)] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]
 // ("host": the serial loop with every cloud passing through host buffers, as in rounds 1-3; the default keeps them in HBM)
 //
 // --scan-to-map (anywhere on the line; the node's loop with clouds resident in HBM): every scan after the first is registered
@@ -45,8 +45,12 @@
 // --nvtl (with --scan-to-map): after each registration "nvtl: <value> found <n_found>/<n>" is printed -- the nearest-voxel
 // transformation likelihood of the scan at its registered pose against the target it was registered to (ndt_get_nvtl), before
 // the scan is accumulated: the number a localisation stack thresholds to accept or reject the pose.
+// --covariance (with --scan-to-map): after each registration "pose sigma: sx sy sz sroll spitch syaw" is printed -- the square
+// roots of the diagonal of the sandwich covariance of the registered pose (ndt_pose_covariance) against the target the scan
+// was registered to, before the scan is accumulated; "nan" six times when the pose is not determined (NDT_COV_INDEFINITE).
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -132,6 +136,7 @@ struct Node {
   bool localize = false;     // --localize: the loaded map stays as it is
   bool map_fitness = false;  // --map-fitness: the centroid fitness of every registration is printed
   bool nvtl = false;         // --nvtl: the nearest-voxel transformation likelihood of every registration is printed
+  bool covariance = false;   // --covariance: the standard deviations of every registered pose are printed
   std::vector<std::vector<float>> trajectory;                     // trajectory_
   std::vector<float> pose = std::vector<float>(kIdentity, kIdentity + 16);
   std::vector<float> pres_transform = std::vector<float>(kIdentity, kIdentity + 16);  // rosbag node :33,95
@@ -172,6 +177,16 @@ struct Node {
         return false;
       }
       std::printf("nvtl: %.9g found %zu/%zu\n", value, found, n);
+    }
+    if (covariance) {  // likewise; the sandwich estimate has no tuning constant
+      double cov[36];
+      if (ndt_pose_covariance(h, nullptr, NDT_COV_SANDWICH, 1.0, cov, nullptr) != NDT_OK) {
+        err = ndt_last_error();
+        return false;
+      }
+      std::printf("pose sigma:");
+      for (int k = 0; k < 6; k++) std::printf(" %.9g", std::sqrt(cov[7 * k]));
+      std::printf("\n");
     }
     if (rosbag) {  // perform_registration :119-141, then :63-68
       double fitness = 0;
@@ -579,11 +594,11 @@ static int run_pipelined(Node& node, ndt_pcd_sequence_handle seq, float voxel_le
 }
 
 int main(int argc, char** argv) {
-  bool scan_to_map = false, bad_window = false, localize = false, bad_file = false, map_fitness = false, nvtl = false;
+  bool scan_to_map = false, bad_window = false, localize = false, bad_file = false, map_fitness = false, nvtl = false, covariance = false;
   float window = 0;
   const char *save_target = nullptr, *load_target = nullptr;
   static const char kUsage[] =
-      "usage: map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> "
+      "usage: map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> "
       "[voxel_leaf_size] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]\n";
   {  // the switches are taken out of the line before the positional arguments are read
     int kept = 1;
@@ -603,6 +618,8 @@ int main(int argc, char** argv) {
         map_fitness = true;
       } else if (std::strcmp(argv[i], "--nvtl") == 0) {
         nvtl = true;
+      } else if (std::strcmp(argv[i], "--covariance") == 0) {
+        covariance = true;
       } else {
         argv[kept++] = argv[i];
       }
@@ -617,8 +634,8 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--save-target <file> and --load-target <file> go with --scan-to-map, --localize goes with --load-target\n%s", kUsage);
     return 2;
   }
-  if ((map_fitness || nvtl) && !scan_to_map) {
-    std::fprintf(stderr, "--map-fitness and --nvtl go with --scan-to-map\n%s", kUsage);
+  if ((map_fitness || nvtl || covariance) && !scan_to_map) {
+    std::fprintf(stderr, "--map-fitness, --nvtl and --covariance go with --scan-to-map\n%s", kUsage);
     return 2;
   }
   if (argc < 2) {
@@ -635,6 +652,7 @@ int main(int argc, char** argv) {
   node.localize = localize;
   node.map_fitness = map_fitness;
   node.nvtl = nvtl;
+  node.covariance = covariance;
   if (scan_to_map && (node.rosbag || !serial || host_clouds)) {
     // (the rosbag loop prints getFitnessScore, which needs the target's points: an accumulated target keeps none --
     // --map-fitness prints the fitness against its voxel centroids instead)

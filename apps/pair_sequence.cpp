@@ -6,6 +6,9 @@
 // chained with ndt_host_chain_pose.  Printed per pair: "Transform k-1 to k" and "TransformSum", then one timing line.
 // --fitness: also the getFitnessScore of every pair at its final transformation, all from one ndt_pairs_fitness_scores
 // call right after the pairs call ("fitness k-1 to k: <value>", 17 significant digits), and that call's time.
+// --covariance: also the standard deviations of every pair's registered pose ("pair k sigma: sx sy sz sroll spitch syaw": the
+// square roots of the diagonal of the sandwich covariance, "nan" where the pose is not determined), all pairs from one
+// ndt_pairs_pose_covariances call right after the pairs call, and that call's time.  Not with --gicp.
 // --batch-filter: every scan is read first, then all of them are prefiltered in ONE ndt_cloud_voxel_filter_batch call; the
 // output is the plain run's, timing lines aside.
 // --gicp: the same consecutive pairs through gicp_align_pairs_clouds (pclomp::GeneralizedIterativeClosestPoint with its
@@ -16,9 +19,10 @@
 // --map <out.pcd>: after the pose chain, all filtered scans at their chained poses (scan 0 at the identity) go into the map
 // in ONE ndt_map_update_clouds call at the node's 0.5 m; "map: <n> points", and the map written as a binary PCD.
 //
-//   pair_sequence <pcd_directory> [--fitness] [--batch-filter] [--gicp [--lockstep]] [--map <out.pcd>]
+//   pair_sequence <pcd_directory> [--fitness] [--covariance] [--batch-filter] [--gicp [--lockstep]] [--map <out.pcd>]
 #include <cfloat>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -45,23 +49,28 @@ static double since(clock_type::time_point a) { return std::chrono::duration<dou
 
 int main(int argc, char** argv) {
   if (argc < 2) {
-    std::printf("usage: pair_sequence <pcd_directory> [--fitness] [--batch-filter] [--gicp [--lockstep]] [--map <out.pcd>]\n");
+    std::printf("usage: pair_sequence <pcd_directory> [--fitness] [--covariance] [--batch-filter] [--gicp [--lockstep]] [--map <out.pcd>]\n");
     return 0;
   }
-  bool want_fitness = false, batch_filter = false, use_gicp = false, lockstep = false;
+  bool want_fitness = false, want_covariance = false, batch_filter = false, use_gicp = false, lockstep = false;
   const char* map_path = nullptr;
   for (int a = 2; a < argc; a++) {
     if (std::strcmp(argv[a], "--fitness") == 0) want_fitness = true;
+    if (std::strcmp(argv[a], "--covariance") == 0) want_covariance = true;
     if (std::strcmp(argv[a], "--batch-filter") == 0) batch_filter = true;
     if (std::strcmp(argv[a], "--gicp") == 0) use_gicp = true;
     if (std::strcmp(argv[a], "--lockstep") == 0) lockstep = true;
     if (std::strcmp(argv[a], "--map") == 0) {
       if (a + 1 >= argc) {
-        std::fprintf(stderr, "--map needs a file name\nusage: pair_sequence <pcd_directory> [--fitness] [--batch-filter] [--gicp [--lockstep]] [--map <out.pcd>]\n");
+        std::fprintf(stderr, "--map needs a file name\nusage: pair_sequence <pcd_directory> [--fitness] [--covariance] [--batch-filter] [--gicp [--lockstep]] [--map <out.pcd>]\n");
         return 2;
       }
       map_path = argv[++a];
     }
+  }
+  if (want_covariance && use_gicp) {
+    std::fprintf(stderr, "--covariance is the NDT pairs call's: not with --gicp\n");
+    return 2;
   }
   const float kLeaf = 0.5f;
   ndt_handle h = nullptr;
@@ -166,6 +175,13 @@ int main(int argc, char** argv) {
     CHECK(ndt_pairs_fitness_scores(h, nullptr, DBL_MAX /* PCL's default */, fitness.data()));
     fitness_ms = since(t_fit);
   }
+  double covariance_ms = 0;
+  std::vector<double> cov(36 * n_pairs);
+  if (want_covariance && n_pairs) {  // (at the final transformations the pairs call kept, converged or not)
+    const auto t_cov = clock_type::now();
+    CHECK(ndt_pairs_pose_covariances(h, nullptr, NDT_COV_SANDWICH, 1.0, cov.data(), nullptr));
+    covariance_ms = since(t_cov);
+  }
 
   // ---- pose chain
   static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
@@ -187,10 +203,17 @@ int main(int argc, char** argv) {
   }
   if (want_fitness)
     for (size_t k = 0; k < n_pairs; k++) std::printf("fitness %zu to %zu: %.17g\n", k, k + 1, fitness[k]);
+  if (want_covariance)
+    for (size_t k = 0; k < n_pairs; k++) {
+      std::printf("pair %zu sigma:", k);
+      for (int d = 0; d < 6; d++) std::printf(" %.9g", std::sqrt(cov[36 * k + 7 * d]));
+      std::printf("\n");
+    }
   std::printf("\nclouds %zu  pairs %zu (not converged %zu)\n", clouds.size(), n_pairs, not_converged);
   std::printf("time: read + prefilter %.2f ms, pairs call %.2f ms (%.1f pairs/s)\n", load_ms, align_ms,
               align_ms > 0 ? 1e3 * static_cast<double>(n_pairs) / align_ms : 0.0);
   if (want_fitness && !use_gicp) std::printf("time: fitness call %.3f ms\n", fitness_ms);
+  if (want_covariance) std::printf("time: covariance call %.3f ms\n", covariance_ms);
   if (map_path) {  // ---- every scan at its pose into the map: one call
     const auto t_map = clock_type::now();
     std::vector<int> dense(clouds.size(), 1);

@@ -329,7 +329,7 @@ ndt_status ndt_promote_source_to_target(ndt_handle h, int is_dense);
  *   target was set from the concatenation -- in call order, and in cloud order within _clouds -- of the clouds moved by their
  *   poses: ndt_grid_size / _info / _dump return the same leaves, counts, means, covariances, inverse covariances and
  *   eigenvalues, and ndt_eval*, ndt_eval_hessian_f64, ndt_calculate_score, ndt_score_poses, ndt_calculate_nvtl, ndt_get_nvtl,
- *   ndt_nvtl_poses, ndt_source_point_nvtl, ndt_align, ndt_align_guesses,
+ *   ndt_nvtl_poses, ndt_source_point_nvtl, ndt_pose_covariance, ndt_align, ndt_align_guesses,
  *   ndt_align_multistart and ndt_align_batch* the same bits, for all four search methods (the evaluation kernels see an
  *   ordinary grid: the padded dense table, or the hash keyed by the reference's linear index; ndt_set_voxel_index chooses
  *   between the two as for a cloud target, by the points accumulated so far).  `pose` is a column-major 4x4, NULL =
@@ -711,6 +711,68 @@ ndt_status ndt_source_point_count(ndt_handle h, size_t* n_source);
 ndt_status ndt_source_point_nvtl(ndt_handle h, const float* transform /* 16 or NULL */, double* out /* n_source or NULL */,
                                  const double** d_out, double* nvtl, size_t* n_found);
 ndt_status ndt_diag_nvtl(ndt_handle h, size_t* launches, size_t* blocks);
+
+/* ---- pose covariance: how well is each of the six pose components determined? -----------------------------------------
+ * A filter that fuses the registered pose with odometry, GNSS or an IMU needs a 6x6 covariance per registration, a pose-graph
+ * back end one information matrix per edge.  Two estimates, over the pose ordered x y z roll pitch yaw:
+ *   Laplace  : cov = scale A^-1.  The NDT score is not a normalised log-likelihood, so `scale` is the caller's to tune.
+ *   sandwich : cov = A^-1 B_c A^-1 (the M-estimator covariance).  Unchanged when the objective is scaled: no tuning constant;
+ *              a direction A hardly constrains (a corridor, a plane) comes out with a large variance.
+ *
+ * Definition.  Inputs: the handle's source, target grid, search method and (d1, d2, d3) = gauss_constants(resolution,
+ * outlier_ratio); a 4x4 f32 column-major `transform` (NULL: the last align's final transformation, the identity before any
+ * align); the pose p = ndt_host_matrix_to_pose(transform).
+ *  1. Source point x_i is moved in f32 by `transform` (as ndt_eval_with_matrix moves it) to x'_i, which has the neighbour set
+ *     computeHessian gives it: empty for a non-finite x'_i or one outside the grid, else the search method's voxels.
+ *  2. J_i is computeHessian's f64 3x6 point Jacobian (identity | angle columns), built from the UNMOVED x_i and the f64
+ *     angle-derivative table at p (ndt_host_angle_derivatives' j_ang_d), each entry (a0 x + a1 y) + a2 z.
+ *  3. Neighbour record r: xt = double(x'_i) - mean_r, Cx = C_r^-1 xt with computeHessian's association ((c0 x0 + c1 x1) + c2 x2
+ *     per row), w_r = d2 exp(-d2 (xt . Cx) / 2); the neighbour is skipped when w_r > 1, w_r < 0 or w_r is NaN; else
+ *     w_r <- w_r d1.
+ *  4. g_i[k] = sum over r of w_r (Cx . J_i[:,k]), k = 0..5, all f64, in neighbour order; the dot product is
+ *     (Cx0 J0k + Cx1 J1k) + Cx2 J2k with J's structural zeros and ones not multiplied (g_i[0..2] add w_r Cx itself).  A point
+ *     with no neighbour that contributes is NOT FOUND and adds nothing.
+ *  5. g = sum_i g_i (6), B = sum_i g_i g_i^T (upper triangle, 21) and n_found, summed in the fixed order of the evaluation
+ *     kernels (per-thread walk of the points, block fold, fixed-order sum of the blocks): identical run to run.
+ *  6. H = what ndt_eval_hessian_f64 computes for the same moved cloud and p (for a transform that is ndt_host_pose_to_matrix(p)
+ *     exactly: that call's bits); A = -(H + H^T) / 2.
+ *  7. B_c = B - g g^T / n_found; n_found == 0: B_c = B, the zero matrix.
+ *  8. Host algebra in f64 on the six Jacobi eigenpairs (lambda_k, v_k) of A.  NDT_COV_INDEFINITE is set when n_found < 6 or
+ *     min lambda <= 1e-12 max lambda (that includes max lambda <= 0, and a NaN); then all 36 entries of cov are NaN.
+ *     Otherwise A^-1 = V diag(1 / lambda) V^T, Laplace cov = scale A^-1, sandwich cov = A^-1 B_c A^-1, either symmetrised as
+ *     (M + M^T) / 2.
+ *
+ * - ndt_pose_covariance: of the handle's source against its target.  cov: 36 doubles, row-major.  info (may be NULL) receives
+ *   A, the uncentred B and g, n_found, the extreme eigenvalues of A and the flags.  `scale` is ignored by the sandwich; for
+ *   Laplace it must be finite and > 0.
+ * - ndt_pairs_pose_covariances: of every pair of the last ndt_align_pairs* call, against the grid that call built for the
+ *   pair's target, at transforms + 16 k (NULL: the pair's final transformation): one launch of the gradient kernel for all
+ *   pairs.  cov: n_pairs * 36, info: n_pairs entries or NULL.  Pair k's outputs have the bits ndt_pose_covariance gives on a
+ *   handle that holds that pair (for sources below the size at which a handle re-orders its source, 65 536 points).
+ * - ndt_host_pose_covariance: steps 7 and 8 alone, host only (A, B: 36 row-major each, g: 6); eig_min, eig_max and flags may
+ *   be NULL.  The device calls' cov is this function of their info, bit for bit.
+ * - ndt_diag_pose_covariance: launches of the gradient kernel (k_grad_outer / k_grad_outer_multi) in the last of the two device
+ *   calls that reached the device, and the blocks that did work in them.
+ * NDT_ERR_INVALID before any device work: a NULL handle, a NULL cov, an unknown method, a bad Laplace scale, a handle with a
+ * communicator or an all-reduce hook.  Then NDT_ERR_NO_DEVICE, then NDT_ERR_NO_INPUT without a target or a source (pairs: when
+ * the last pairs call failed, had no pair or was never made).  An empty grid or an empty source is NDT_OK with n_found = 0,
+ * the flag set and a NaN cov.  Neither call changes the target, source, grid, last result, ndt_get_stats or the other diag
+ * counters.  Dense and sparse voxel index; cloud, accumulated and cropped targets alike. */
+typedef struct {
+  double A[36], B[36], g[6]; /* row-major; B is uncentred */
+  size_t n_found;
+  double eig_min, eig_max;   /* of A */
+  int flags;                 /* NDT_COV_INDEFINITE */
+} ndt_pose_information;
+enum { NDT_COV_LAPLACE = 0, NDT_COV_SANDWICH = 1 };
+enum { NDT_COV_INDEFINITE = 1 };
+ndt_status ndt_pose_covariance(ndt_handle h, const float* transform /* 16 or NULL */, int method, double scale, double* cov /* 36 */,
+                               ndt_pose_information* info /* or NULL */);
+ndt_status ndt_pairs_pose_covariances(ndt_handle h, const float* transforms /* n_pairs*16 or NULL */, int method, double scale,
+                                      double* cov /* n_pairs*36 */, ndt_pose_information* info /* n_pairs or NULL */);
+ndt_status ndt_host_pose_covariance(const double* A, const double* B, const double* g, size_t n_found, int method, double scale,
+                                    double* cov, double* eig_min, double* eig_max, int* flags);
+ndt_status ndt_diag_pose_covariance(ndt_handle h, size_t* launches, size_t* blocks);
 
 /* ---- multi-GPU (one process per GPU, RCCL over xGMI) ---------------------------
  * The reference is a single process (ndt_omp_impl.hpp:206 is its only parallel construct); this is the exchange step

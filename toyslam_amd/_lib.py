@@ -17,6 +17,16 @@ BOX_ROUTES = ("none", "host_scalar", "host_avx2", "repack", "rec16_copy", "rec16
 EVAL_STRIDE = 32
 COMM_ID_BYTES = 128
 
+COV_LAPLACE, COV_SANDWICH = 0, 1
+COV_INDEFINITE = 1
+
+
+class PoseInformation(C.Structure):
+    """ndt_pose_information (include/ndt_mi355.h)"""
+    _fields_ = [("A", C.c_double * 36), ("B", C.c_double * 36), ("g", C.c_double * 6), ("n_found", C.c_size_t),
+                ("eig_min", C.c_double), ("eig_max", C.c_double), ("flags", C.c_int)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
 EVAL_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_double),
                       C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double))
@@ -153,6 +163,10 @@ SIGNATURES = {
     "ndt_source_point_count": (C.c_int, [vp, szp]),
     "ndt_source_point_nvtl": (C.c_int, [vp, fp, dp, C.POINTER(C.c_void_p), dp, szp]),
     "ndt_diag_nvtl": (C.c_int, [vp, szp, szp]),
+    "ndt_pose_covariance": (C.c_int, [vp, fp, C.c_int, C.c_double, dp, vp]),
+    "ndt_pairs_pose_covariances": (C.c_int, [vp, fp, C.c_int, C.c_double, dp, vp]),
+    "ndt_host_pose_covariance": (C.c_int, [dp, dp, dp, C.c_size_t, C.c_int, C.c_double, dp, dp, dp, ip]),
+    "ndt_diag_pose_covariance": (C.c_int, [vp, szp, szp]),
     "ndt_align_guesses": (C.c_int, [vp, fp, C.c_size_t, fp, ip, ip, dp, ip]),
     "ndt_host_pick_top": (None, [dp, C.c_size_t, C.c_size_t, ip, szp]),
     "ndt_align_multistart": (C.c_int, [vp, fp, C.c_size_t, C.c_size_t, ip, szp, fp, ip, ip, dp, ip]),

@@ -738,6 +738,40 @@ __device__ __forceinline__ void finish_point64(double (&acc)[kNumAcc], const Poi
     for (int b = a; b < 3; b++) acc[idx++] += ((B[0][a] * AB[0][b] + B[1][a] * AB[1][b]) + B[2][a] * AB[2][b]) + X[a][b];
 }
 
+// One neighbour of computeHessian's loop, all f64 (:584-626), in the two straight-line pieces hessian64_body and
+// grad_outer_body are both made of (the `continue`s stay in the bodies).
+// neighbor64_probe: record of neighbour k of the search method, negative = none.
+template <int NNB>
+__device__ __forceinline__ int neighbor64_probe(const GridView& gv, int vi, int vj, int vk, unsigned centre, int k, float tx, float ty,
+                                                float tz, double r2) {
+  int dx, dy, dz;
+  nb_offset<NNB>(k, dx, dy, dz);
+  // (throughput unit: one neighbour's nine f64 words at a time -- hoisted to the top of the point, the seven
+  // neighbours' loads alone are 126 VGPRs, and the mixed batch kernel that contains this body is sized by it)
+  if (kLimitRecordLoads) asm volatile("" ::: "memory");
+  return (NNB == 27) ? probe_kd(gv, vi, vj, vk, centre, dx, dy, dz, tx, ty, tz, static_cast<float>(r2))
+                     : probe(gv, vi, vj, vk, centre, dx, dy, dz);
+}
+// neighbor64_terms: the record's inverse covariance, xc = C^-1 (double(x') - mean), and the return value
+// e = d2 exp(-d2 x.xc / 2) (:622, before the range test and the d1 factor)
+struct Neighbor64 {
+  double c00, c01, c02, c11, c12, c22;
+  double xc0, xc1, xc2;
+};
+__device__ __forceinline__ double neighbor64_terms(const GridView& gv, int rix, float tx, float ty, float tz, double d2, Neighbor64& nb) {
+  // mean from the record, the inverse covariance in f64 from the record's side sector (the leaf's icov_, :592)
+  const double* mu = gv.recs[rix].mean;
+  const double* ic = gv.centroids[rix].icov;
+  const double mx = mu[0], my = mu[1], mz = mu[2];
+  const double c00 = ic[0], c01 = ic[1], c02 = ic[2], c11 = ic[3], c12 = ic[4], c22 = ic[5];
+  const double x0 = static_cast<double>(tx) - mx, x1 = static_cast<double>(ty) - my, x2 = static_cast<double>(tz) - mz;
+  const double xc0 = (c00 * x0 + c01 * x1) + c02 * x2;
+  const double xc1 = (c01 * x0 + c11 * x1) + c12 * x2;
+  const double xc2 = (c02 * x0 + c12 * x1) + c22 * x2;
+  nb = {c00, c01, c02, c11, c12, c22, xc0, xc1, xc2};
+  return d2 * exp(-d2 * ((x0 * xc0 + x1 * xc1) + x2 * xc2) / 2);  // :622
+}
+
 // all-f64 Hessian contributions (computeHessian / updateHessian, ndt_omp_impl.hpp:584-645) of the
 // points first, first + stride, ... into acc
 // LATE_TABLES: a compiler-level memory fence in front of the per-point finish keeps the 69 f64 table
@@ -760,26 +794,14 @@ __device__ __forceinline__ void hessian64_body(const float4* __restrict__ src, i
     bool any = false;
     const unsigned centre = lut_index(gv.g, vi, vj, vk);
     for (int k = 0; k < NNB; k++) {
-      int dx, dy, dz;
-      nb_offset<NNB>(k, dx, dy, dz);
-      // (throughput unit: one neighbour's nine f64 words at a time -- hoisted to the top of the point, the seven
-      // neighbours' loads alone are 126 VGPRs, and the mixed batch kernel that contains this body is sized by it)
-      if (kLimitRecordLoads) asm volatile("" ::: "memory");
-      const int rix = (NNB == 27) ? probe_kd(gv, vi, vj, vk, centre, dx, dy, dz, tx, ty, tz, static_cast<float>(prm.r2))
-                                  : probe(gv, vi, vj, vk, centre, dx, dy, dz);
+      const int rix = neighbor64_probe<NNB>(gv, vi, vj, vk, centre, k, tx, ty, tz, prm.r2);
       if (rix < 0) continue;
-      // mean from the record, the inverse covariance in f64 from the record's side sector (the leaf's icov_, :592)
-      const double* mu = gv.recs[rix].mean;
-      const double* ic = gv.centroids[rix].icov;
-      const double mx = mu[0], my = mu[1], mz = mu[2];
-      const double c00 = ic[0], c01 = ic[1], c02 = ic[2], c11 = ic[3], c12 = ic[4], c22 = ic[5];
-      const double x0 = static_cast<double>(tx) - mx, x1 = static_cast<double>(ty) - my, x2 = static_cast<double>(tz) - mz;
-      const double xc0 = (c00 * x0 + c01 * x1) + c02 * x2;
-      const double xc1 = (c01 * x0 + c11 * x1) + c12 * x2;
-      const double xc2 = (c02 * x0 + c12 * x1) + c22 * x2;
-      double e = prm.d2 * exp(-prm.d2 * ((x0 * xc0 + x1 * xc1) + x2 * xc2) / 2);  // :622
-      if (e > 1 || e < 0 || e != e) continue;                                      // :625-626
+      Neighbor64 nb;
+      double e = neighbor64_terms(gv, rix, tx, ty, tz, prm.d2, nb);
+      if (e > 1 || e < 0 || e != e) continue;  // :625-626
       e *= prm.d1;
+      const double c00 = nb.c00, c01 = nb.c01, c02 = nb.c02, c11 = nb.c11, c12 = nb.c12, c22 = nb.c22;
+      const double xc0 = nb.xc0, xc1 = nb.xc1, xc2 = nb.xc2;
       any = true;
       pa.xe0 += e * xc0; pa.xe1 += e * xc1; pa.xe2 += e * xc2;
       const double t0 = (-prm.d2 * e) * xc0, t1 = (-prm.d2 * e) * xc1, t2 = (-prm.d2 * e) * xc2;
@@ -788,6 +810,57 @@ __device__ __forceinline__ void hessian64_body(const float4* __restrict__ src, i
     }
     if (LATE_TABLES) asm volatile("" ::: "memory");
     if (any) finish_point64(acc, pa, prm, pt.x, pt.y, pt.z);
+  }
+}
+
+// Per-point score gradients and their outer products (the pose covariance's B, include/ndt_mi355.h), all f64, of the points
+// first, first + stride, ...: computeHessian's neighbour set, point Jacobian (:805-814, from the unmoved point and prm.jd;
+// prm.hd is not read) and neighbour weights (neighbor64_terms), g_i[k] = sum_r e_r (xc_r . J[:,k]) in neighbour order.  A point
+// with a contributing neighbour adds g_i to acc[1..6], the upper triangle of g_i g_i^T (row-major) to acc[7..27] and 1 to
+// acc[28] -- the slots an evaluation row keeps its gradient, its Hessian and its neighbour count in; acc[0] stays 0.
+template <int NNB>
+__device__ __forceinline__ void grad_outer_body(const float4* __restrict__ src, int n, const GridView& gv, const Hess64Params& prm,
+                                                int first, int stride, double (&acc)[kNumAcc]) {
+  for (int i = first; i < n; i += stride) {
+    const float4 pt = src[i];
+    float tx, ty, tz;
+    xform_point(prm.T, pt.x, pt.y, pt.z, tx, ty, tz);
+    if (!finite3(tx, ty, tz)) continue;  // no neighbourhood (see hessian64_body)
+    int vi, vj, vk;
+    search_ijk(gv.g, tx, ty, tz, vi, vj, vk);
+    if (!near_grid(gv.g, vi, vj, vk)) continue;
+    const unsigned centre = lut_index(gv.g, vi, vj, vk);
+    // the eight entries of J that are neither 0 nor 1: J[1][3] J[2][3] | J[0][4] J[1][4] J[2][4] | J[0][5] J[1][5] J[2][5]
+    const double px = pt.x, py = pt.y, pz = pt.z;
+    double j[8];
+#pragma unroll
+    for (int r = 0; r < 8; r++) j[r] = (prm.jd[r][0] * px + prm.jd[r][1] * py) + prm.jd[r][2] * pz;
+    double g[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    bool any = false;
+    for (int k = 0; k < NNB; k++) {
+      const int rix = neighbor64_probe<NNB>(gv, vi, vj, vk, centre, k, tx, ty, tz, prm.r2);
+      if (rix < 0) continue;
+      Neighbor64 nb;
+      double e = neighbor64_terms(gv, rix, tx, ty, tz, prm.d2, nb);
+      if (e > 1 || e < 0 || e != e) continue;  // :625-626
+      e *= prm.d1;
+      any = true;
+      g[0] += e * nb.xc0;
+      g[1] += e * nb.xc1;
+      g[2] += e * nb.xc2;
+      g[3] += e * (nb.xc1 * j[0] + nb.xc2 * j[1]);  // (J's structural zeros and ones are not multiplied)
+      g[4] += e * ((nb.xc0 * j[2] + nb.xc1 * j[3]) + nb.xc2 * j[4]);
+      g[5] += e * ((nb.xc0 * j[5] + nb.xc1 * j[6]) + nb.xc2 * j[7]);
+    }
+    if (!any) continue;
+    int idx = 7;
+#pragma unroll
+    for (int a = 0; a < 6; a++) {
+      acc[1 + a] += g[a];
+#pragma unroll
+      for (int b = a; b < 6; b++) acc[idx++] += g[a] * g[b];
+    }
+    acc[28] += 1.0;
   }
 }
 

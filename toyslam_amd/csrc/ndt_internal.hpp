@@ -9,6 +9,7 @@
 //   ndt_fitness.hip : getFitnessScore      ndt_centroid_fitness.hip : the same against the voxel centroids, the centroid cloud
 //   ndt_score.hip : calculateScore (of a cloud, of the source under many poses)
 //   ndt_nvtl.hip  : nearest-voxel transformation likelihood (of a cloud, of the source under one or many poses, per point)
+//   ndt_pose_cov.hip: 6x6 pose covariance (Laplace / sandwich) of the handle's pair and of the pairs of a pairs call
 //   ndt_eval.hip   : one evaluation (launch path), the persistent evaluation server's host side (mailbox protocol),
 //                    ndt_align, ndt_eval*, diagnostics and self-tests
 //   ndt_batch.hip  : lock-step batches (ndt_align_batch*, ndt_align_guesses, ndt_align_multistart), the RCCL communicator
@@ -484,6 +485,9 @@ struct ndt_context {
   DevBuf<float> nv_poses;
   DevBuf<double> nv_points;
   size_t nv_launches = 0, nv_blocks = 0;
+  // the pose covariance calls (ndt_pose_cov.hip): k_grad_outer / k_grad_outer_multi launches and blocks of the last one
+  // that reached the device (ndt_diag_pose_covariance)
+  size_t pc_launches = 0, pc_blocks = 0;
   // ndt_target_accumulate* (ndt_accumulate.hip): the accumulated target -- alive while `grid` is its grid -- and what the last
   // call did (ndt_diag_target_accumulate)
   std::shared_ptr<ndtc::AccTarget> acc;

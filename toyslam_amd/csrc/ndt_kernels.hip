@@ -6,7 +6,8 @@
 //      :484-537 fused with the f32 point transform): k_derivatives (one launch per evaluation, also over a whole lock-step
 //      batch), k_batch_step (mixed-kind batch steps), the all-f64 Hessian k_hessian64 (computeHessian :540-645), k_reduce
 //      (fixed-order sum of the per-block rows), calculateScore (:935-983; k_score_poses: of one source under many poses), the nearest-voxel
-//      transformation likelihood over the same neighbour probe (k_nvtl, k_nvtl_poses), getFitnessScore (k_fitness; k_fitness_multi +
+//      transformation likelihood over the same neighbour probe (k_nvtl, k_nvtl_poses), the per-point gradient sums of the pose
+//      covariance over computeHessian's neighbour terms (k_grad_outer, k_grad_outer_multi), getFitnessScore (k_fitness; k_fitness_multi +
 //      k_fitness_reduce for many members in one launch) and the search index it walks (k_cell_ranges, k_gather_points).
 //
 // Gather work: no MFMA (there is no dense contraction).  Loads are 16 B per lane (float4 points, 3 x dwordx4 per 64-B
@@ -646,6 +647,57 @@ __global__ __launch_bounds__(kBlock) void k_nvtl_poses(const float4* __restrict_
   block_reduce_store<2>(acc, partials + (static_cast<size_t>(blockIdx.y) * gridDim.x + blockIdx.x) * kEvalStride, lds);
 }
 
+// Hess64Params into LDS without its hd table (grad_outer_body does not read it): the words in front of hd, then those behind
+__device__ __forceinline__ void stage_params_no_hd(const Hess64Params* __restrict__ from, Hess64Params& to) {
+  constexpr int kHd0 = static_cast<int>(offsetof(Hess64Params, hd) / 4), kHd1 = static_cast<int>(offsetof(Hess64Params, d1) / 4);
+  constexpr int kWords = static_cast<int>(sizeof(Hess64Params) / 4);
+  const int* sp = reinterpret_cast<const int*>(from);
+  int* dp = reinterpret_cast<int*>(&to);
+  for (int t = threadIdx.x; t < kHd0 + (kWords - kHd1); t += kBlock) {
+    const int w = t < kHd0 ? t : t - kHd0 + kHd1;
+    dp[w] = sp[w];
+  }
+}
+
+// Per-point gradient sums of the pose covariance (grad_outer_body): one f64 pass over a resident source, k_calc_score's walk
+// (same grid extent, same stride).  Row: slots 1..6 = sum of g_i, 7..27 = upper triangle of sum g_i g_i^T, 28 = n_found.
+template <int NNB>
+__global__ __launch_bounds__(kBlock) void k_grad_outer(const float4* __restrict__ src, int n, GridView gv, Hess64Params P,
+                                                       double* __restrict__ partials) {
+  __shared__ double lds[(kBlock / kWave) * 32];
+  __shared__ Hess64Params sP;  // (as kernel arguments the tables overflow the SGPR file)
+  stage_params_no_hd(&P, sP);
+  __syncthreads();
+  double acc[kNumAcc];
+#pragma unroll
+  for (int k = 0; k < kNumAcc; k++) acc[k] = 0.0;
+  grad_outer_body<NNB>(src, n, gv, sP, blockIdx.x * kBlock + threadIdx.x, static_cast<int>(gridDim.x) * kBlock, acc);
+  block_reduce_store<kNumAcc>(acc, partials + static_cast<size_t>(blockIdx.x) * kEvalStride, lds);
+}
+
+// ... of the members of a pairs call in one launch: blockIdx.y = member (its GridView and its GradOuterMember, block-uniform:
+// scalar loads), blockIdx.x = block of the member's OWN walk -- members[m].blocks of them, the grid and the stride k_grad_outer
+// has for that source, so row (m, b) is the row k_grad_outer writes; the other blocks of the member leave at once and their
+// rows keep the zeros they were cleared to.  Rows: partials[member][max_blocks][kEvalStride], for one launch_reduce.
+template <int NNB>
+__global__ __launch_bounds__(kBlock) void k_grad_outer_multi(const GridView* __restrict__ views, const GradOuterMember* __restrict__ members,
+                                                             int max_blocks, double* __restrict__ partials) {
+  __shared__ double lds[(kBlock / kWave) * 32];
+  __shared__ Hess64Params sP;
+  const GradOuterMember& M = members[blockIdx.y];
+  const int blocks = M.blocks;
+  // (block-uniform exit before any barrier: the surviving blocks reach every barrier with all their waves)
+  if (static_cast<int>(blockIdx.x) >= blocks) return;
+  stage_params_no_hd(&M.P, sP);
+  __syncthreads();
+  const GridView gv = views[blockIdx.y];
+  double acc[kNumAcc];
+#pragma unroll
+  for (int k = 0; k < kNumAcc; k++) acc[k] = 0.0;
+  grad_outer_body<NNB>(from_global(&M.src), M.n, gv, sP, blockIdx.x * kBlock + threadIdx.x, blocks * kBlock, acc);
+  block_reduce_store<kNumAcc>(acc, partials + (static_cast<size_t>(blockIdx.y) * max_blocks + blockIdx.x) * kEvalStride, lds);
+}
+
 inline int grid_for(size_t n, int max_blocks) {
   size_t b = (n + kBlock - 1) / kBlock;
   if (b < 1) b = 1;
@@ -820,6 +872,27 @@ hipError_t launch_nvtl_poses(const float4* src, int n, const GridView& gv, const
   else if (search == 1) hipLaunchKernelGGL(k_nvtl_poses<26>, grid, block, 0, stream, src, n, gv, d_poses, d1, d2, r2, partials);
   else if (search == 3) hipLaunchKernelGGL(k_nvtl_poses<1>, grid, block, 0, stream, src, n, gv, d_poses, d1, d2, r2, partials);
   else hipLaunchKernelGGL(k_nvtl_poses<7>, grid, block, 0, stream, src, n, gv, d_poses, d1, d2, r2, partials);
+  return hipGetLastError();
+}
+
+hipError_t launch_grad_outer(const float4* src, int n, const GridView& gv, const Hess64Params& P, int search, int n_blocks,
+                             double* partials, hipStream_t stream) {
+  const dim3 grid(n_blocks), block(kBlock);
+  if (search == 0) hipLaunchKernelGGL(k_grad_outer<27>, grid, block, 0, stream, src, n, gv, P, partials);
+  else if (search == 1) hipLaunchKernelGGL(k_grad_outer<26>, grid, block, 0, stream, src, n, gv, P, partials);
+  else if (search == 3) hipLaunchKernelGGL(k_grad_outer<1>, grid, block, 0, stream, src, n, gv, P, partials);
+  else hipLaunchKernelGGL(k_grad_outer<7>, grid, block, 0, stream, src, n, gv, P, partials);
+  return hipGetLastError();
+}
+
+hipError_t launch_grad_outer_multi(const GridView* d_views, const GradOuterMember* d_members, int n_members, int search, int max_blocks,
+                                   double* partials, hipStream_t stream) {
+  if (n_members <= 0 || max_blocks <= 0) return hipSuccess;
+  const dim3 grid(max_blocks, n_members), block(kBlock);
+  if (search == 0) hipLaunchKernelGGL(k_grad_outer_multi<27>, grid, block, 0, stream, d_views, d_members, max_blocks, partials);
+  else if (search == 1) hipLaunchKernelGGL(k_grad_outer_multi<26>, grid, block, 0, stream, d_views, d_members, max_blocks, partials);
+  else if (search == 3) hipLaunchKernelGGL(k_grad_outer_multi<1>, grid, block, 0, stream, d_views, d_members, max_blocks, partials);
+  else hipLaunchKernelGGL(k_grad_outer_multi<7>, grid, block, 0, stream, d_views, d_members, max_blocks, partials);
   return hipGetLastError();
 }
 

@@ -448,6 +448,23 @@ hipError_t launch_nvtl(const float4* cloud, int n, const GridView& gv, const flo
                        int n_blocks, double* d_out, double* partials, hipStream_t stream);
 hipError_t launch_nvtl_poses(const float4* src, int n, const GridView& gv, const float* d_poses, int n_poses, double d1, double d2,
                              int search, float r2, int n_blocks, double* partials, hipStream_t stream);
+// Per-point gradient sums of the pose covariance (k_grad_outer, k_grad_outer_multi; the definition: include/ndt_mi355.h).
+// Rows in an evaluation row's layout: slots 1..6 = sum of the per-point gradients g_i, 7..27 = upper triangle of
+// sum g_i g_i^T, 28 = points with a contributing neighbour; P.hd is not read.  launch_grad_outer: one source over n_blocks
+// blocks (derivative_blocks: launch_calc_score's walk).  launch_grad_outer_multi: grid (max_blocks, n_members <= 65535), member
+// m against d_views[m] over its own d_members[m].blocks <= max_blocks blocks (0: nothing of it runs); rows
+// partials[m][max_blocks][kEvalStride], cleared by the caller, for launch_reduce(partials, max_blocks, n_members): member
+// m's sums have the bits of launch_grad_outer(src, n, view, P, blocks).
+struct GradOuterMember {
+  const float4* src = nullptr;
+  int n = 0;
+  int blocks = 0;
+  Hess64Params P;
+};
+hipError_t launch_grad_outer(const float4* src, int n, const GridView& gv, const Hess64Params& P, int search, int n_blocks,
+                             double* partials, hipStream_t stream);
+hipError_t launch_grad_outer_multi(const GridView* d_views, const GradOuterMember* d_members, int n_members, int search, int max_blocks,
+                                   double* partials, hipStream_t stream);
 
 hipError_t launch_voxel_centroids(const float4* pts, const unsigned* leaf_start, const int* leaf_count, int n_leaves,
                                   int* sorted_idx, float4* out, hipStream_t stream, const unsigned* d_totals = nullptr,

@@ -806,6 +806,45 @@ class NormalDistributionsTransform:
         check(self._L.ndt_diag_nvtl(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    # ---- pose covariance (ndt_pose_covariance / ndt_pairs_pose_covariances) ----------------------------------------------
+    def poseCovariance(self, transform=None, method="sandwich", scale=1.0, info=False):
+        """6x6 covariance of the pose x y z roll pitch yaw of the input source at `transform` (None: the last align's final
+        transformation): method "sandwich" = A^-1 B_c A^-1 (no tuning constant) or "laplace" = scale A^-1.  All NaN when the
+        pose is not determined (fewer than 6 points found, or A not positive definite).  info=True: (cov, dict with A, B, g,
+        n_found, eig_min, eig_max, indefinite)."""
+        T = None if transform is None else _colmajor(transform)
+        cov = np.zeros(36)
+        I = _lib.PoseInformation()
+        check(self._L.ndt_pose_covariance(self._h, _f(T) if T is not None else None, _cov_method(method), float(scale), _d(cov),
+                                          C.byref(I)))
+        cov = cov.reshape(6, 6)
+        return (cov, _pose_information(I)) if info else cov
+
+    def pairsPoseCovariances(self, transforms=None, method="sandwich", scale=1.0, info=False):
+        """poseCovariance of every pair of the last alignPairs, all pairs in one launch of the gradient kernel: pair k's source
+        at transforms[k] (None = that call's final transformations) against pair k's target.  (P, 6, 6); info=True: also a
+        list of P dicts."""
+        T = None
+        if transforms is not None:
+            T = np.ascontiguousarray(np.stack([_colmajor(x) for x in transforms]), dtype=np.float32)
+        n = C.c_size_t(0)
+        check(self._L.ndt_pairs_count(self._h, C.byref(n)))
+        P = n.value
+        if T is not None and T.shape[0] != P:
+            raise ValueError("one transform per pair of the last alignPairs")
+        cov = np.zeros((max(P, 1), 36))
+        I = (_lib.PoseInformation * max(P, 1))()
+        check(self._L.ndt_pairs_pose_covariances(self._h, _f(T) if T is not None else None, _cov_method(method), float(scale),
+                                                 _d(cov), C.cast(I, C.c_void_p)))
+        cov = cov[:P].reshape(P, 6, 6).copy()
+        return (cov, [_pose_information(I[k]) for k in range(P)]) if info else cov
+
+    def poseCovarianceLaunches(self):
+        """(gradient-kernel launches, blocks that worked) of the last pose covariance call that reached the device."""
+        a, b = C.c_size_t(0), C.c_size_t(0)
+        check(self._L.ndt_diag_pose_covariance(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def alignGuesses(self, guesses):
         """Register the input source from each of the 4x4 guesses in lock-step (ndt_align_guesses).  Returns alignBatch's
         dict, one entry per guess, plus best = index of the largest transformation probability (-1 if none)."""
@@ -1160,6 +1199,29 @@ def host_grid_plan(n_cells, n_points, div_b=None):
                 n_blocks=blk.value, one_launch=bool(one.value), wmax=wmax.value, lds_cap=cap.value, lut_cells=lut.value,
                 compact_items=items.value, compact_tiles=tiles.value, compact_prefix=bool(prefix.value),
                 filter_buckets=bool(fb.value), filter_chunks=fc.value)
+
+
+def _cov_method(method):
+    try:
+        return {"laplace": _lib.COV_LAPLACE, "sandwich": _lib.COV_SANDWICH}[method]
+    except KeyError:
+        raise ValueError("method must be 'laplace' or 'sandwich'") from None
+
+
+def _pose_information(I):
+    return dict(A=np.array(I.A).reshape(6, 6), B=np.array(I.B).reshape(6, 6), g=np.array(I.g), n_found=int(I.n_found),
+                eig_min=float(I.eig_min), eig_max=float(I.eig_max), indefinite=bool(I.flags & _lib.COV_INDEFINITE))
+
+
+def host_pose_covariance(A, B, g, n_found, method="sandwich", scale=1.0):
+    """Steps 7 and 8 of the pose covariance's definition on the host (ndt_host_pose_covariance): (cov (6, 6), eig_min,
+    eig_max, indefinite)."""
+    A, B, g = (np.ascontiguousarray(x, dtype=np.float64) for x in (A, B, g))
+    cov = np.zeros(36)
+    lo, hi, fl = C.c_double(0), C.c_double(0), C.c_int(0)
+    check(_lib.lib().ndt_host_pose_covariance(_d(A), _d(B), _d(g), int(n_found), _cov_method(method), float(scale), _d(cov),
+                                              C.byref(lo), C.byref(hi), C.byref(fl)))
+    return cov.reshape(6, 6), lo.value, hi.value, bool(fl.value & _lib.COV_INDEFINITE)
 
 
 def host_pose_to_matrix(p):
