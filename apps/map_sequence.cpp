@@ -22,7 +22,7 @@
 // after the other, 2.7 ms overlapped, 3.7 ms overlapped on CU partitions -- the steps are short host-paced sequences of
 // pageable copies and small launches, and two threads driving them get in each other's way; hence not the default.
 //
-//   map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> [voxel_leaf_size (0.5 | 0.3)] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]
+//   map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--range <min> <max>] [--reject-unexplained <L>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> [voxel_leaf_size (0.5 | 0.3)] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]
 // ("host": the serial loop with every cloud passing through host buffers, as in rounds 1-3; the default keeps them in HBM)
 //
 // --scan-to-map (anywhere on the line; the node's loop with clouds resident in HBM): every scan after the first is registered
@@ -48,6 +48,14 @@
 // --covariance (with --scan-to-map): after each registration "pose sigma: sx sy sz sroll spitch syaw" is printed -- the square
 // roots of the diagonal of the sandwich covariance of the registered pose (ndt_pose_covariance) against the target the scan
 // was registered to, before the scan is accumulated; "nan" six times when the pose is not determined (NDT_COV_INDEFINITE).
+// --range <min> <max> (with --scan-to-map): every raw scan goes through ndt_cloud_select (RANGE | FINITE about the sensor, centre
+// 0) before its prefilter -- the ego vehicle's own returns and everything beyond the useful range are dropped on the device --
+// and "range kept: <k>/<n>" is printed per scan.
+// --reject-unexplained <L> (with --scan-to-map, not with --localize, which accumulates nothing): after each registration the
+// scan is accumulated as ndt_source_select_by_nvtl(h, NULL, L, 1, ...) -- its points whose nearest-voxel likelihood at the
+// registered pose is at least L, and those no voxel is near (new ground) -- instead of as the whole scan, so that moving objects
+// the target does not explain stay out of it; "rejected: <n - k>/<n>" is printed.  The first scan has no target and is
+// accumulated whole.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -137,6 +145,10 @@ struct Node {
   bool map_fitness = false;  // --map-fitness: the centroid fitness of every registration is printed
   bool nvtl = false;         // --nvtl: the nearest-voxel transformation likelihood of every registration is printed
   bool covariance = false;   // --covariance: the standard deviations of every registered pose are printed
+  bool range = false;        // --range: every raw scan is cropped to [range_min, range_max] about the sensor before its prefilter
+  float range_min = 0, range_max = 0;
+  bool reject = false;       // --reject-unexplained: a registered scan is accumulated without the points the target does not explain
+  double reject_below = 0;
   std::vector<std::vector<float>> trajectory;                     // trajectory_
   std::vector<float> pose = std::vector<float>(kIdentity, kIdentity + 16);
   std::vector<float> pres_transform = std::vector<float>(kIdentity, kIdentity + 16);  // rosbag node :33,95
@@ -259,6 +271,20 @@ static int run_resident(Node& node, ndt_pcd_sequence_handle seq, float voxel_lea
         return 0;
       }
       const auto t0 = clock_type::now();
+      if (node.range) {  // the crop leaves finite points only
+        ndt_select_spec spec{};
+        spec.flags = NDT_SELECT_RANGE | NDT_SELECT_FINITE;
+        spec.r_min = node.range_min;
+        spec.r_max = node.range_max;
+        ndt_cloud cropped = nullptr;
+        size_t kept = 0;
+        CHECK(ndt_cloud_select(h, r.view, &spec, nullptr, 0, &cropped, nullptr, &kept));
+        std::printf("range kept: %zu/%zu\n", kept, r.n);
+        ndt_cloud_release(r.view);
+        r.view = cropped;
+        r.n = kept;
+        r.dense = 1;
+      }
       CHECK(ndt_cloud_voxel_filter_begin(h, r.view, r.dense, voxel_leaf_size));
       node.t_filter += since(t0);
       begun = r;
@@ -329,7 +355,17 @@ static int run_resident(Node& node, ndt_pcd_sequence_handle seq, float voxel_lea
         t0 = clock_type::now();
         int ov = 0;
         CHECK(ndt_map_update_cloud(h, current, 1, map_pose.data(), 0.5f, &ov));  // :204 / map_voxel :88: leaf fixed at 0.5
-        if (node.scan_to_map && node.accumulate(h, current, map_pose.data())) return 1;
+        if (node.scan_to_map && node.reject && !node.localize) {  // the source is still `current`, the last result this registration's
+          ndt_cloud explained = nullptr;
+          size_t kept = 0;
+          CHECK(ndt_source_select_by_nvtl(h, nullptr, node.reject_below, 1, &explained, &kept, nullptr));
+          std::printf("rejected: %zu/%zu\n", m - kept, m);
+          const int failed = node.accumulate(h, explained, map_pose.data());
+          ndt_cloud_release(explained);
+          if (failed) return 1;
+        } else if (node.scan_to_map && node.accumulate(h, current, map_pose.data())) {
+          return 1;
+        }
         node.t_map += since(t0);
       }
       return 0;
@@ -595,10 +631,12 @@ static int run_pipelined(Node& node, ndt_pcd_sequence_handle seq, float voxel_le
 
 int main(int argc, char** argv) {
   bool scan_to_map = false, bad_window = false, localize = false, bad_file = false, map_fitness = false, nvtl = false, covariance = false;
-  float window = 0;
+  bool range = false, bad_range = false, reject = false, bad_reject = false;
+  float window = 0, range_min = 0, range_max = 0;
+  double reject_below = 0;
   const char *save_target = nullptr, *load_target = nullptr;
   static const char kUsage[] =
-      "usage: map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> "
+      "usage: map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--range <min> <max>] [--reject-unexplained <L>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> "
       "[voxel_leaf_size] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]\n";
   {  // the switches are taken out of the line before the positional arguments are read
     int kept = 1;
@@ -620,6 +658,21 @@ int main(int argc, char** argv) {
         nvtl = true;
       } else if (std::strcmp(argv[i], "--covariance") == 0) {
         covariance = true;
+      } else if (std::strcmp(argv[i], "--range") == 0) {
+        range = true;
+        bad_range = i + 2 >= argc;
+        if (!bad_range) {
+          range_min = static_cast<float>(std::atof(argv[++i]));
+          range_max = static_cast<float>(std::atof(argv[++i]));
+          bad_range = !(range_min >= 0 && range_min <= range_max);
+        }
+      } else if (std::strcmp(argv[i], "--reject-unexplained") == 0) {
+        reject = true;
+        bad_reject = i + 1 >= argc;
+        if (!bad_reject) {
+          reject_below = std::atof(argv[++i]);
+          bad_reject = reject_below != reject_below;
+        }
       } else {
         argv[kept++] = argv[i];
       }
@@ -638,6 +691,11 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--map-fitness, --nvtl and --covariance go with --scan-to-map\n%s", kUsage);
     return 2;
   }
+  if (bad_range || bad_reject || ((range || reject) && !scan_to_map) || (reject && localize)) {
+    std::fprintf(stderr, "--range <min> <max> (0 <= min <= max) and --reject-unexplained <L> go with --scan-to-map; --localize accumulates "
+                         "nothing, so it does not go with --reject-unexplained\n%s", kUsage);
+    return 2;
+  }
   if (argc < 2) {
     std::printf("%s", kUsage);
     return 0;
@@ -653,6 +711,11 @@ int main(int argc, char** argv) {
   node.map_fitness = map_fitness;
   node.nvtl = nvtl;
   node.covariance = covariance;
+  node.range = range;
+  node.range_min = range_min;
+  node.range_max = range_max;
+  node.reject = reject;
+  node.reject_below = reject_below;
   if (scan_to_map && (node.rosbag || !serial || host_clouds)) {
     // (the rosbag loop prints getFitnessScore, which needs the target's points: an accumulated target keeps none --
     // --map-fitness prints the fitness against its voxel centroids instead)

@@ -265,7 +265,8 @@ typedef enum {
   NDT_BOX_ROUTE_REC16_POLLED = 5, /* a cloud by reference (k_bbox16<false>): nothing copied, tagged rows polled           */
   NDT_BOX_ROUTE_FILTER_ROWS = 6,  /* output of a voxel filter: rows of at most 64 blocks, the count read on the device    */
   NDT_BOX_ROUTE_MULTI_WORDS = 7,  /* member of a batched call (k_repack_bbox_multi): order-encoded words, atomic max      */
-  NDT_BOX_ROUTE_STAGED = 8        /* scan of a staged PCD sequence: boxes by the reading thread                           */
+  NDT_BOX_ROUTE_STAGED = 8,       /* scan of a staged PCD sequence: boxes by the reading thread                           */
+  NDT_BOX_ROUTE_SELECT = 9        /* output of a selection (k_select_place): per-block rows of the kept points            */
 } ndt_box_route;
 /* the cloud's boxes exactly as stored: out = {min xyz, max xyz} of box [0], then of box [1]; an empty box is
  * (FLT_MAX, -FLT_MAX).  *route (may be NULL) = the ndt_box_route that wrote them.  No device work. */
@@ -318,6 +319,75 @@ ndt_status ndt_map_update_batch(ndt_handle h, const void* pts, const size_t* off
  * filters of the concatenation (1), exact bounding-box passes (0, or 1 when the scans' boxes under their poses did not do) */
 ndt_status ndt_diag_map_batch(ndt_handle h, size_t* transform_launches, size_t* filters, size_t* box_passes);
 ndt_status ndt_promote_source_to_target(ndt_handle h, int is_dense);
+
+/* ---- selection: dropping points from a resident cloud ---------------------------------------------------------------------
+ * pcl::removeNaNFromPointCloud (FINITE), pcl::CropBox with setNegative (BOX, BOX_NEGATE; on a cloud that is not dense:
+ * BOX | FINITE), a min / max range crop (RANGE), and pcl::PassThrough on a computed per-point value (KEY) -- of an ndt_cloud,
+ * with the result left in HBM as an ndt_cloud: a stable compaction of the kept 16-byte records (all four words as they are)
+ * and the two bounding boxes of the kept points.  A point (x, y, z as stored, f32) with key k (f64) is kept iff every
+ * enabled test passes (the definition is toyslam_amd/csrc/ndt_select.hpp, one function for host and device):
+ *   FINITE  all three coordinates finite
+ *   BOX     inside = box_min[a] <= p[a] && p[a] <= box_max[a] on all three axes (f32 compares: a NaN coordinate is never
+ *           inside); passes iff inside, with BOX_NEGATE iff not inside (a NaN point is then kept, unless FINITE is set too)
+ *   RANGE   dx = x - centre[0] ..., d2 = (dx*dx + dy*dy) + dz*dz in f32, every operation rounded on its own (no fused
+ *           multiply-add); inside = r_min*r_min <= d2 && d2 <= r_max*r_max (products in f32; r_max = +inf is allowed; a NaN
+ *           d2 is never inside); RANGE_NEGATE inverts as for the box
+ *   KEY     inside = key_lo <= k && k <= key_hi; KEY_NEGATE inverts; a NaN key fails the test in both senses
+ * flags == 0 keeps every point (the result is a copy).  A spec is invalid if it has unknown flag bits, a *_NEGATE bit without
+ * its test, with BOX a NaN bound or box_min[a] > box_max[a], with RANGE a NaN centre / r_min / r_max, r_min < 0 or
+ * r_min > r_max, with KEY a NaN bound or key_lo > key_hi. */
+enum {
+  NDT_SELECT_FINITE = 1,
+  NDT_SELECT_BOX = 2,
+  NDT_SELECT_BOX_NEGATE = 4,
+  NDT_SELECT_RANGE = 8,
+  NDT_SELECT_RANGE_NEGATE = 16,
+  NDT_SELECT_KEY = 32,
+  NDT_SELECT_KEY_NEGATE = 64
+};
+typedef struct {
+  unsigned flags;
+  float box_min[3], box_max[3]; /* BOX   */
+  float centre[3], r_min, r_max; /* RANGE */
+  double key_lo, key_hi;        /* KEY   */
+} ndt_select_spec;
+/* - ndt_cloud_select: *out is a new cloud of its own (ndt_cloud_release) holding the kept records of `in`, in in's order, with
+ *   boxes exact over the kept points (route NDT_BOX_ROUTE_SELECT) -- bit for bit what ndt_cloud_upload of the host-selected
+ *   records would be, and usable by every consumer of an ndt_cloud.  Nothing kept: an empty cloud, never NULL, with the initial
+ *   boxes and route NONE.  keys: n_in doubles, host memory or (keys_on_device != 0) device memory; may be NULL without KEY.
+ *   kept_idx (host, capacity n_in, may be NULL) receives the kept points' indices, ascending; *n_kept (may be NULL) their
+ *   number.  The call returns after its own work is done (a borrowed view of a staged sequence may be overwritten afterwards).
+ * - ndt_cloud_select_clouds: one spec for n_clouds clouds, two launches in all; out[k] and n_kept[k] are what ndt_cloud_select
+ *   gives for cloud k alone, the same bits whatever the other clouds and their order.  Every out[k] is a cloud of its own
+ *   (releasing one leaves the others valid).  KEY is refused.  n_clouds == 0 is NDT_OK, touches nothing and needs no device.
+ *   On any error every out[k] is NULL.
+ * - ndt_source_select_by_nvtl: ndt_source_point_nvtl under `transform` (NULL: the last align's final transformation), then
+ *   the selection of the handle's source with those values as device-resident keys (they never visit the host): a point is
+ *   kept iff (found and L >= min_likelihood) or (not found and keep_unfound).  *out holds the SOURCE'S OWN records, unmoved,
+ *   in the caller's point order -- what ndt_target_accumulate_cloud or ndt_map_update_cloud take at the registered pose.
+ *   *n_found (may be NULL) is the NVTL call's count, *n_kept (may be NULL) the selection's.  Refuses what ndt_source_point_nvtl
+ *   refuses, a NULL out and a NaN min_likelihood.  It is an NVTL call to ndt_diag_nvtl and overwrites the values the last
+ *   ndt_source_point_nvtl's d_out names.
+ * - ndt_diag_select, of the last of the three calls above that reached the device: kernel launches (2, whatever the number of
+ *   clouds; 0 when no cloud had a point), the blocks of each launch, the clouds.
+ * None of them changes the handle's target, source, grid, last result, statistics, map, a begun
+ * ndt_cloud_voxel_filter_begin or the pairs state.
+ * NDT_ERR_INVALID before any device work, outputs untouched apart from *out = NULL (every out[k] = NULL): a NULL handle, in,
+ * spec or out, an invalid spec, KEY without keys, a NULL entry of in, more than 65 535 clouds, a cloud of another device, more
+ * than INT_MAX points.  After those checks NDT_ERR_NO_DEVICE without a gfx950 device. */
+ndt_status ndt_cloud_select(ndt_handle h, ndt_cloud in, const ndt_select_spec* spec, const double* keys /* n_in, or NULL without KEY */,
+                            int keys_on_device, ndt_cloud* out, int32_t* kept_idx /* host, capacity n_in, or NULL */,
+                            size_t* n_kept /* or NULL */);
+ndt_status ndt_cloud_select_clouds(ndt_handle h, const ndt_cloud* in, size_t n_clouds, const ndt_select_spec* spec,
+                                   ndt_cloud* out /* n_clouds */, size_t* n_kept /* n_clouds or NULL */);
+ndt_status ndt_source_select_by_nvtl(ndt_handle h, const float* transform /* 16 or NULL: last align's */, double min_likelihood,
+                                     int keep_unfound, ndt_cloud* out, size_t* n_kept, size_t* n_found);
+ndt_status ndt_diag_select(ndt_handle h, size_t* launches, size_t* blocks, size_t* clouds);
+/* Host only, no device: the predicate itself (*keep = 0 / 1; NDT_ERR_INVALID for an invalid spec), and the launch plan of a
+ * cloud of n_points -- blocks of 256 threads, each owning one contiguous range of *points_per_block points (the last one the
+ * rest); at most 1024 blocks, beyond which points_per_block grows. */
+ndt_status ndt_host_select_point(const ndt_select_spec* spec, const float xyz[3], double key, int* keep);
+ndt_status ndt_host_select_plan(size_t n_points, int* blocks, int* points_per_block);
 
 /* ---- accumulating target: posed scans merged into the voxel grid (scan-to-MAP registration) --------------------------
  * Every other target of this library is built from ONE cloud; a mapping node that wants to register a scan against the map

@@ -13,10 +13,11 @@ CSRC = os.path.join(_HERE, "csrc")
 
 NDT_OK, NDT_ERR_INVALID, NDT_ERR_NO_DEVICE, NDT_ERR_HIP, NDT_ERR_GRID_OVERFLOW, NDT_ERR_NO_INPUT, NDT_ERR_COMM = range(7)
 KDTREE, DIRECT26, DIRECT7, DIRECT1 = 0, 1, 2, 3
-BOX_ROUTES = ("none", "host_scalar", "host_avx2", "repack", "rec16_copy", "rec16_polled", "filter_rows", "multi_words", "staged")
+BOX_ROUTES = ("none", "host_scalar", "host_avx2", "repack", "rec16_copy", "rec16_polled", "filter_rows", "multi_words", "staged", "select")
 EVAL_STRIDE = 32
 COMM_ID_BYTES = 128
 
+SELECT_FINITE, SELECT_BOX, SELECT_BOX_NEGATE, SELECT_RANGE, SELECT_RANGE_NEGATE, SELECT_KEY, SELECT_KEY_NEGATE = 1, 2, 4, 8, 16, 32, 64
 COV_LAPLACE, COV_SANDWICH = 0, 1
 COV_INDEFINITE = 1
 
@@ -25,6 +26,12 @@ class PoseInformation(C.Structure):
     """ndt_pose_information (include/ndt_mi355.h)"""
     _fields_ = [("A", C.c_double * 36), ("B", C.c_double * 36), ("g", C.c_double * 6), ("n_found", C.c_size_t),
                 ("eig_min", C.c_double), ("eig_max", C.c_double), ("flags", C.c_int)]
+
+
+class SelectSpec(C.Structure):
+    """ndt_select_spec (include/ndt_mi355.h)"""
+    _fields_ = [("flags", C.c_uint), ("box_min", C.c_float * 3), ("box_max", C.c_float * 3), ("centre", C.c_float * 3),
+                ("r_min", C.c_float), ("r_max", C.c_float), ("key_lo", C.c_double), ("key_hi", C.c_double)]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
@@ -163,6 +170,12 @@ SIGNATURES = {
     "ndt_source_point_count": (C.c_int, [vp, szp]),
     "ndt_source_point_nvtl": (C.c_int, [vp, fp, dp, C.POINTER(C.c_void_p), dp, szp]),
     "ndt_diag_nvtl": (C.c_int, [vp, szp, szp]),
+    "ndt_cloud_select": (C.c_int, [vp, vp, C.POINTER(SelectSpec), vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_int32), szp]),
+    "ndt_cloud_select_clouds": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, C.POINTER(SelectSpec), C.POINTER(vp), szp]),
+    "ndt_source_select_by_nvtl": (C.c_int, [vp, fp, C.c_double, C.c_int, C.POINTER(vp), szp, szp]),
+    "ndt_diag_select": (C.c_int, [vp, szp, szp, szp]),
+    "ndt_host_select_point": (C.c_int, [C.POINTER(SelectSpec), fp, C.c_double, ip]),
+    "ndt_host_select_plan": (C.c_int, [C.c_size_t, ip, ip]),
     "ndt_pose_covariance": (C.c_int, [vp, fp, C.c_int, C.c_double, dp, vp]),
     "ndt_pairs_pose_covariances": (C.c_int, [vp, fp, C.c_int, C.c_double, dp, vp]),
     "ndt_host_pose_covariance": (C.c_int, [dp, dp, dp, C.c_size_t, C.c_int, C.c_double, dp, dp, dp, ip]),

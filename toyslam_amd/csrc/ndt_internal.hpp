@@ -9,6 +9,7 @@
 //   ndt_fitness.hip : getFitnessScore      ndt_centroid_fitness.hip : the same against the voxel centroids, the centroid cloud
 //   ndt_score.hip : calculateScore (of a cloud, of the source under many poses)
 //   ndt_nvtl.hip  : nearest-voxel transformation likelihood (of a cloud, of the source under one or many poses, per point)
+//   ndt_select.hip : selection of the points of resident clouds (finite, box, range, per-point value): kernels and C-ABI
 //   ndt_pose_cov.hip: 6x6 pose covariance (Laplace / sandwich) of the handle's pair and of the pairs of a pairs call
 //   ndt_eval.hip   : one evaluation (launch path), the persistent evaluation server's host side (mailbox protocol),
 //                    ndt_align, ndt_eval*, diagnostics and self-tests
@@ -502,6 +503,11 @@ struct ndt_context {
   // searched with, the blocks of its largest launch
   size_t cf_launches = 0, cf_passes = 0, cf_max_blocks = 0;
   float cf_excursion = 0.f;
+  // the selections (ndt_select.hip): the page-locked block of a call -- its segment table on the way up, its totals and box
+  // rows on the way back -- and what the last call that reached the device did (ndt_diag_select)
+  void* sel_pinned = nullptr;
+  size_t sel_pinned_bytes = 0;
+  size_t sel_launches = 0, sel_blocks = 0, sel_clouds = 0;
 
   ~ndt_context() {
     for (ndt_context* w : batch_workers) delete w;
@@ -536,6 +542,7 @@ struct ndt_context {
     if (mb_pinned) (void)hipHostFree(mb_pinned);
     if (sp_pinned) (void)hipHostFree(sp_pinned);
     if (nv_pinned) (void)hipHostFree(nv_pinned);
+    if (sel_pinned) (void)hipHostFree(sel_pinned);
     acc.reset();
     release_buffers();
     if (host_result) (void)hipHostFree(host_result);
@@ -676,6 +683,13 @@ inline int fitness_blocks(int n) { return std::max(1, std::min(2048, (n + 31) / 
 // ---- ndt_score.hip
 // poses per launch of ndt_score_poses and ndt_nvtl_poses: one rule, one switch (NDT_SCORE_POSES_CHUNK)
 size_t poses_chunk(size_t n_poses, size_t row_bytes);
+// ---- ndt_nvtl.hip
+// the readiness every NVTL call shares, after its own argument checks: a device, then a target (and a source)
+ndt_status nvtl_ready(ndt_context* h, bool need_source);
+// NVTL of the n device points at d_pts, moved by the column-major T first (null: used as given).  d_out (may be null): n
+// doubles of device memory that receive L per point, -1.0 where the point has no neighbour.  Waits for the stream.
+ndt_status nvtl_launch(ndt_context* h, const float4* d_pts, size_t n, const float* T_colmajor, double* d_out, double* nvtl,
+                       size_t* n_found);
 // ---- ndt_filter.hip
 ndt_status filter_slots(ndt_handle h, int which, FilterPending& P);
 // The geometry and route of one N1 filter, from the cloud's box alone -- the one decision voxel_filter_enqueue and the

@@ -16,7 +16,7 @@ namespace ndtc {
 static double nvtl_of(const double* row) { return row[1] > 0 ? row[0] / row[1] : 0.0; }  // n_found == 0: 0.0, never NaN
 
 // the readiness every NVTL call shares, after its own argument checks: a device, then a target (and a source)
-static ndt_status nvtl_ready(ndt_context* h, bool need_source) {
+ndt_status nvtl_ready(ndt_context* h, bool need_source) {
   ndt_status s = ensure_device(h);
   if (s) return s;
   if (!h->grid || !h->target) return fail(NDT_ERR_NO_INPUT, "no input target");
@@ -28,8 +28,8 @@ static ndt_status nvtl_ready(ndt_context* h, bool need_source) {
 
 // NVTL of the n device points at d_pts, moved by the column-major T first (null: used as given).  d_out (may be null): n
 // doubles of device memory that receive L per point, -1.0 where the point has no neighbour.
-static ndt_status nvtl_launch(ndt_context* h, const float4* d_pts, size_t n, const float* T_colmajor, double* d_out, double* nvtl,
-                              size_t* n_found) {
+ndt_status nvtl_launch(ndt_context* h, const float4* d_pts, size_t n, const float* T_colmajor, double* d_out, double* nvtl,
+                       size_t* n_found) {
   if (nvtl) *nvtl = 0.0;
   if (n_found) *n_found = 0;
   if (n == 0) return NDT_OK;

@@ -806,6 +806,103 @@ class NormalDistributionsTransform:
         check(self._L.ndt_diag_nvtl(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    # ---- selection of the points of resident clouds (ndt_cloud_select / _clouds / ndt_source_select_by_nvtl) ---------------
+    @staticmethod
+    def selectSpec(finite=False, box=None, box_negate=False, range=None, centre=(0, 0, 0), range_negate=False, key_range=None,
+                   key_negate=False):
+        """The ndt_select_spec of the keyword form: box = (min_xyz, max_xyz), range = (r_min, r_max) about `centre`,
+        key_range = (key_lo, key_hi); the *_negate switches set their bit whether or not the test is given (the library
+        refuses a negation without its test)."""
+        s = _lib.SelectSpec()
+        flags = _lib.SELECT_FINITE if finite else 0
+        if box is not None:
+            flags |= _lib.SELECT_BOX
+            mn, mx = np.asarray(box[0], dtype=np.float32).reshape(3), np.asarray(box[1], dtype=np.float32).reshape(3)
+            s.box_min[:], s.box_max[:] = mn.tolist(), mx.tolist()
+        if range is not None:
+            flags |= _lib.SELECT_RANGE
+            s.centre[:] = np.asarray(centre, dtype=np.float32).reshape(3).tolist()
+            s.r_min, s.r_max = float(np.float32(range[0])), float(np.float32(range[1]))
+        if key_range is not None:
+            flags |= _lib.SELECT_KEY
+            s.key_lo, s.key_hi = float(key_range[0]), float(key_range[1])
+        flags |= (_lib.SELECT_BOX_NEGATE if box_negate else 0) | (_lib.SELECT_RANGE_NEGATE if range_negate else 0)
+        flags |= _lib.SELECT_KEY_NEGATE if key_negate else 0
+        s.flags = flags
+        return s
+
+    def selectCloud(self, dc, finite=False, box=None, box_negate=False, range=None, centre=(0, 0, 0), range_negate=False, keys=None,
+                    key_range=None, key_negate=False, indices=False, spec=None):
+        """The points of the resident cloud `dc` that pass every enabled test, in dc's order, as a new DeviceCloud with exact
+        boxes (ndt_cloud_select; the tests are defined in include/ndt_mi355.h).  keys: one float64 per point (an array), or
+        the device pointer of such values (an int, e.g. sourcePointNVTL(device=True)[0]).  spec: a ready _lib.SelectSpec
+        instead of the keywords.  indices=True: -> (DeviceCloud, (n_kept,) int32 indices of the kept points, ascending)."""
+        if spec is None:
+            spec = self.selectSpec(finite, box, box_negate, range, centre, range_negate, key_range, key_negate)
+        n = len(dc)
+        on_device, kp, keep = 0, None, None
+        if keys is not None:
+            if isinstance(keys, (int, np.integer)):
+                on_device, kp = 1, C.c_void_p(int(keys))
+            else:
+                keep = np.ascontiguousarray(keys, dtype=np.float64).reshape(-1)
+                if keep.shape[0] != n:
+                    raise ValueError("one key per point")
+                kp = C.c_void_p(keep.ctypes.data) if n else C.c_void_p(np.zeros(1).ctypes.data)
+        idx = np.zeros(max(n, 1), dtype=np.int32) if indices else None
+        c, nk = C.c_void_p(None), C.c_size_t(0)
+        check(self._L.ndt_cloud_select(self._h, dc._c, C.byref(spec), kp, on_device, C.byref(c),
+                                       idx.ctypes.data_as(C.POINTER(C.c_int32)) if indices else None, C.byref(nk)))
+        out = DeviceCloud(self, c)
+        return (out, idx[:nk.value].copy()) if indices else out
+
+    def selectClouds(self, clouds, finite=False, box=None, box_negate=False, range=None, centre=(0, 0, 0), range_negate=False,
+                     spec=None):
+        """selectCloud of every DeviceCloud of the list under one spec, two launches in all (ndt_cloud_select_clouds; no key
+        test): a list of DeviceCloud, entry k what selectCloud gives for clouds[k] alone, the same bits."""
+        if spec is None:
+            spec = self.selectSpec(finite, box, box_negate, range, centre, range_negate)
+        clouds = list(clouds)
+        n = len(clouds)
+        arr = (C.c_void_p * max(n, 1))(*[c._c for c in clouds])
+        out = (C.c_void_p * max(n, 1))()
+        nk = (C.c_size_t * max(n, 1))()
+        check(self._L.ndt_cloud_select_clouds(self._h, arr, n, C.byref(spec), out, nk))
+        return [DeviceCloud(self, C.c_void_p(p)) for p in list(out)[:n]]  # (`range` is a keyword of this method)
+
+    def sourceSelectByNVTL(self, min_likelihood, transform=None, keep_unfound=True):
+        """The input source's own points (unmoved, caller's order) that the target explains under `transform` (None: the last
+        align's final transformation): kept iff (a neighbour voxel was found and L >= min_likelihood) or (none was found and
+        keep_unfound).  The per-point values stay on the device.  -> (DeviceCloud, n_found).  Counts as an NVTL call for
+        nvtlLaunches."""
+        T = None if transform is None else _colmajor(transform)
+        c, nk, nf = C.c_void_p(None), C.c_size_t(0), C.c_size_t(0)
+        check(self._L.ndt_source_select_by_nvtl(self._h, _f(T) if T is not None else None, float(min_likelihood), int(bool(keep_unfound)),
+                                                C.byref(c), C.byref(nk), C.byref(nf)))
+        return DeviceCloud(self, c), nf.value
+
+    def selectDiag(self):
+        """What the last selection that reached the device did (ndt_diag_select)."""
+        a, b, c = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        check(self._L.ndt_diag_select(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return dict(launches=a.value, blocks=b.value, clouds=c.value)
+
+    @staticmethod
+    def selectPlan(n):
+        """(blocks, points_per_block) of the selection of a cloud of n points (ndt_host_select_plan; host only)."""
+        b, p = C.c_int(0), C.c_int(0)
+        check(_lib.lib().ndt_host_select_plan(int(n), C.byref(b), C.byref(p)))
+        return b.value, p.value
+
+    @staticmethod
+    def selectPoint(spec, xyz, key=0.0):
+        """Is the point xyz (three float32) with key `key` kept under the _lib.SelectSpec `spec`?  (ndt_host_select_point: the
+        predicate the kernels evaluate; host only.)"""
+        p = np.ascontiguousarray(xyz, dtype=np.float32).reshape(3)
+        keep = C.c_int(-1)
+        check(_lib.lib().ndt_host_select_point(C.byref(spec), _f(p), float(key), C.byref(keep)))
+        return bool(keep.value)
+
     # ---- pose covariance (ndt_pose_covariance / ndt_pairs_pose_covariances) ----------------------------------------------
     def poseCovariance(self, transform=None, method="sandwich", scale=1.0, info=False):
         """6x6 covariance of the pose x y z roll pitch yaw of the input source at `transform` (None: the last align's final
