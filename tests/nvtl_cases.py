@@ -40,7 +40,8 @@ class Grid:
         self.div_b = np.asarray(grid["div_b"], dtype=np.int64)
         self.d1, self.d2, self.d3 = (float(x) for x in gauss)
         self.method, self.leaf, self.min_pts = method, F(resolution), int(min_pts)
-        self.r2 = F(float(resolution) * float(resolution))
+        # the f32 resolution squared in f64, then rounded to f32: kd_radius2 (ndt_eval.hip) and ndt_oracle.cpp:433
+        self.r2 = F(float(F(resolution)) ** 2)
         if method == "KDTREE":
             xyz, lin = centroids
             self.c_row = np.searchsorted(self.idx, lin)          # centroid -> voxel row
