@@ -22,7 +22,7 @@
 // after the other, 2.7 ms overlapped, 3.7 ms overlapped on CU partitions -- the steps are short host-paced sequences of
 // pageable copies and small launches, and two threads driving them get in each other's way; hence not the default.
 //
-//   map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--range <min> <max>] [--reject-unexplained <L>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> [voxel_leaf_size (0.5 | 0.3)] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]
+//   map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--range <min> <max>] [--outliers-radius <r> <min_neighbors>] [--outliers-stat <mean_k> <stddev_mul>] [--reject-unexplained <L>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> [voxel_leaf_size (0.5 | 0.3)] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]
 // ("host": the serial loop with every cloud passing through host buffers, as in rounds 1-3; the default keeps them in HBM)
 //
 // --scan-to-map (anywhere on the line; the node's loop with clouds resident in HBM): every scan after the first is registered
@@ -51,6 +51,9 @@
 // --range <min> <max> (with --scan-to-map): every raw scan goes through ndt_cloud_select (RANGE | FINITE about the sensor, centre
 // 0) before its prefilter -- the ego vehicle's own returns and everything beyond the useful range are dropped on the device --
 // and "range kept: <k>/<n>" is printed per scan.
+// --outliers-radius <r> <min_neighbors> / --outliers-stat <mean_k> <stddev_mul> (with --scan-to-map): every raw scan goes through
+// ndt_cloud_remove_outliers on the device, after --range and before its prefilter -- stray returns do not become one-point
+// voxels -- and "outliers removed: <n - k>/<n>" is printed per scan (with both: the radius filter first).
 // --reject-unexplained <L> (with --scan-to-map, not with --localize, which accumulates nothing): after each registration the
 // scan is accumulated as ndt_source_select_by_nvtl(h, NULL, L, 1, ...) -- its points whose nearest-voxel likelihood at the
 // registered pose is at least L, and those no voxel is near (new ground) -- instead of as the whole scan, so that moving objects
@@ -147,6 +150,8 @@ struct Node {
   bool covariance = false;   // --covariance: the standard deviations of every registered pose are printed
   bool range = false;        // --range: every raw scan is cropped to [range_min, range_max] about the sensor before its prefilter
   float range_min = 0, range_max = 0;
+  bool outliers_radius = false, outliers_stat = false;  // --outliers-radius / --outliers-stat: every raw scan loses its outliers before its prefilter
+  ndt_outlier_spec radius_spec{}, stat_spec{};
   bool reject = false;       // --reject-unexplained: a registered scan is accumulated without the points the target does not explain
   double reject_below = 0;
   std::vector<std::vector<float>> trajectory;                     // trajectory_
@@ -282,6 +287,17 @@ static int run_resident(Node& node, ndt_pcd_sequence_handle seq, float voxel_lea
         std::printf("range kept: %zu/%zu\n", kept, r.n);
         ndt_cloud_release(r.view);
         r.view = cropped;
+        r.n = kept;
+        r.dense = 1;
+      }
+      for (const ndt_outlier_spec* spec : {node.outliers_radius ? &node.radius_spec : nullptr, node.outliers_stat ? &node.stat_spec : nullptr}) {
+        if (!spec) continue;  // what is left holds finite points only
+        ndt_cloud cleaned = nullptr;
+        size_t kept = 0;
+        CHECK(ndt_cloud_remove_outliers(h, r.view, spec, &cleaned, nullptr, &kept, nullptr));
+        std::printf("outliers removed: %zu/%zu\n", r.n - kept, r.n);
+        ndt_cloud_release(r.view);
+        r.view = cleaned;
         r.n = kept;
         r.dense = 1;
       }
@@ -632,11 +648,13 @@ static int run_pipelined(Node& node, ndt_pcd_sequence_handle seq, float voxel_le
 int main(int argc, char** argv) {
   bool scan_to_map = false, bad_window = false, localize = false, bad_file = false, map_fitness = false, nvtl = false, covariance = false;
   bool range = false, bad_range = false, reject = false, bad_reject = false;
+  bool outliers_radius = false, outliers_stat = false, bad_outliers = false;
+  ndt_outlier_spec radius_spec{}, stat_spec{};
   float window = 0, range_min = 0, range_max = 0;
   double reject_below = 0;
   const char *save_target = nullptr, *load_target = nullptr;
   static const char kUsage[] =
-      "usage: map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--range <min> <max>] [--reject-unexplained <L>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> "
+      "usage: map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--range <min> <max>] [--outliers-radius <r> <min_neighbors>] [--outliers-stat <mean_k> <stddev_mul>] [--reject-unexplained <L>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> "
       "[voxel_leaf_size] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]\n";
   {  // the switches are taken out of the line before the positional arguments are read
     int kept = 1;
@@ -666,6 +684,22 @@ int main(int argc, char** argv) {
           range_max = static_cast<float>(std::atof(argv[++i]));
           bad_range = !(range_min >= 0 && range_min <= range_max);
         }
+      } else if (std::strcmp(argv[i], "--outliers-radius") == 0 || std::strcmp(argv[i], "--outliers-stat") == 0) {
+        const bool by_radius = argv[i][11] == 'r';
+        (by_radius ? outliers_radius : outliers_stat) = true;
+        ndt_outlier_spec& spec = by_radius ? radius_spec : stat_spec;
+        if (i + 2 >= argc) {
+          bad_outliers = true;
+        } else if (by_radius) {
+          spec.method = NDT_OUTLIER_RADIUS;
+          spec.radius = static_cast<float>(std::atof(argv[++i]));
+          spec.min_neighbors = std::atoi(argv[++i]);
+        } else {
+          spec.method = NDT_OUTLIER_STATISTICAL;
+          spec.mean_k = std::atoi(argv[++i]);
+          spec.stddev_mul = std::atof(argv[++i]);
+        }
+        bad_outliers = bad_outliers || ndt_host_outlier_spec_check(&spec) != NDT_OK;
       } else if (std::strcmp(argv[i], "--reject-unexplained") == 0) {
         reject = true;
         bad_reject = i + 1 >= argc;
@@ -696,6 +730,11 @@ int main(int argc, char** argv) {
                          "nothing, so it does not go with --reject-unexplained\n%s", kUsage);
     return 2;
   }
+  if (bad_outliers || ((outliers_radius || outliers_stat) && !scan_to_map)) {
+    std::fprintf(stderr, "--outliers-radius <r> <min_neighbors> (r > 0, min_neighbors >= 0) and --outliers-stat <mean_k> <stddev_mul> (mean_k 1 ... 256) "
+                         "go with --scan-to-map\n%s", kUsage);
+    return 2;
+  }
   if (argc < 2) {
     std::printf("%s", kUsage);
     return 0;
@@ -714,6 +753,10 @@ int main(int argc, char** argv) {
   node.range = range;
   node.range_min = range_min;
   node.range_max = range_max;
+  node.outliers_radius = outliers_radius;
+  node.outliers_stat = outliers_stat;
+  node.radius_spec = radius_spec;
+  node.stat_spec = stat_spec;
   node.reject = reject;
   node.reject_below = reject_below;
   if (scan_to_map && (node.rosbag || !serial || host_clouds)) {

@@ -389,6 +389,70 @@ ndt_status ndt_diag_select(ndt_handle h, size_t* launches, size_t* blocks, size_
 ndt_status ndt_host_select_point(const ndt_select_spec* spec, const float xyz[3], double key, int* keep);
 ndt_status ndt_host_select_plan(size_t n_points, int* blocks, int* points_per_block);
 
+/* ---- outlier removal of resident clouds: the neighbourhood filters ----------------------------------------------------
+ * Modelled on pcl::RadiusOutlierRemoval and pcl::StatisticalOutlierRemoval.  Neither class is part of the reference and PCL
+ * itself was not at hand: NO bit parity with PCL is claimed, the definitions below are the contract.
+ * A cloud has n records (x, y, z as stored, f32; the fourth word is carried along).  F = the indices whose three coordinates
+ * are finite.  d2(i, j) = (dx*dx + dy*dy) + dz*dz in f32, every operation rounded on its own (no fused multiply-add).  The
+ * "other points" of i are the j in F with j != i BY INDEX: duplicates of a point are neighbours at distance 0.
+ *   RADIUS       r2 = radius*radius in f32; count_i = the other points with d2(i, j) <= r2; value_i = (double)count_i.
+ *                Kept iff i in F and count_i >= min_neighbors (negate: count_i < min_neighbors).
+ *   STATISTICAL  |F| > mean_k: value_i = (the sum, in f64 and in ascending order of d2, of sqrt((double)d2) over the mean_k
+ *                smallest d2 of i's other points) / mean_k -- a pure function of the cloud; n_valid = |F|; mean = the mean of
+ *                the values over F; stddev = sqrt(sum (v - mean)^2 / (n_valid - 1)), 0 when n_valid < 2 (per-block (count, sum,
+ *                M2) merged by Chan's rule: no cancellation); threshold = mean + stddev_mul * stddev.
+ *                |F| <= mean_k: every value is 0, n_valid = 0, mean = stddev = threshold = 0.
+ *                Kept iff i in F and value_i <= threshold (negate: value_i > threshold).  The threshold a call returns is the
+ *                one it compared with, bit for bit.
+ * A point outside F has value NaN and is never kept, in either sense.
+ * An invalid spec (NDT_ERR_INVALID before any device work): an unknown method, a radius that is not finite or <= 0,
+ * min_neighbors < 0, mean_k outside 1 ... 256, a stddev_mul that is not finite. */
+enum { NDT_OUTLIER_RADIUS = 1, NDT_OUTLIER_STATISTICAL = 2 };
+typedef struct {
+  int method, negate;
+  float radius;      /* RADIUS      */
+  int min_neighbors; /* RADIUS      */
+  int mean_k;        /* STATISTICAL */
+  double stddev_mul; /* STATISTICAL */
+} ndt_outlier_spec;
+typedef struct {
+  size_t n_finite, n_valid;
+  double mean, stddev, threshold; /* RADIUS: n_valid = n_finite, mean = stddev = 0, threshold = min_neighbors */
+} ndt_outlier_stats;
+/* - ndt_cloud_neighbor_values: value_i of every point of `in` into values (n_in doubles: host memory, or device memory with
+ *   values_on_device != 0), and the statistics (stats may be NULL).
+ * - ndt_cloud_remove_outliers: *out is a new cloud of its own holding the kept records of `in`, in in's order, all four words
+ *   as they are, with exact boxes -- bit for bit what ndt_cloud_upload of the host-selected rows gives, as ndt_cloud_select
+ *   promises.  The values are device-resident keys of that selection and never visit the host.  Nothing kept: an empty cloud,
+ *   never NULL.  kept_idx (host, capacity n_in, may be NULL), *n_kept and *stats (may be NULL) as named.
+ * - ndt_cloud_remove_outliers_clouds: one value launch over all clouds and the selection's two launches; out[k], n_kept[k]
+ *   and stats[k] are the same bits as the single call for cloud k alone, whatever the other clouds and their order (every
+ *   cloud has its own threshold).  n_clouds == 0 is NDT_OK, touches nothing and needs no device.  On any error every out[k]
+ *   is NULL.
+ * - ndt_diag_outliers, of the last of the three calls above that reached the device: point indices built, launches and
+ *   blocks of the value kernel, and the queries that left the shell walk for the scan over the whole cloud.
+ * None of them changes the handle's target, source, grid, last result, statistics, map, a begun
+ * ndt_cloud_voxel_filter_begin, the pairs state or what ndt_diag_select reports.
+ * NDT_ERR_INVALID before any device work, outputs untouched apart from *out = NULL (every out[k] = NULL): a NULL handle, in,
+ * spec, values or out, an invalid spec, a NULL entry of in, more than 65 535 clouds, a cloud of another device, more than
+ * INT_MAX points.  After those checks NDT_ERR_NO_DEVICE without a gfx950 device.
+ * Development switch NDT_OUTLIER_MAX_BLOCKS: caps the blocks a cloud gets in the value kernel (the results do not depend on it). */
+ndt_status ndt_cloud_neighbor_values(ndt_handle h, ndt_cloud in, const ndt_outlier_spec* spec,
+                                     double* values /* n_in; host, or device with values_on_device */, int values_on_device,
+                                     ndt_outlier_stats* stats /* or NULL */);
+ndt_status ndt_cloud_remove_outliers(ndt_handle h, ndt_cloud in, const ndt_outlier_spec* spec, ndt_cloud* out,
+                                     int32_t* kept_idx /* host, capacity n_in, or NULL */, size_t* n_kept /* or NULL */,
+                                     ndt_outlier_stats* stats /* or NULL */);
+ndt_status ndt_cloud_remove_outliers_clouds(ndt_handle h, const ndt_cloud* in, size_t n_clouds, const ndt_outlier_spec* spec,
+                                            ndt_cloud* out /* n_clouds */, size_t* n_kept /* n_clouds or NULL */,
+                                            ndt_outlier_stats* stats /* n_clouds or NULL */);
+ndt_status ndt_diag_outliers(ndt_handle h, size_t* index_builds, size_t* value_launches, size_t* value_blocks, size_t* scanned_queries);
+/* Host only, no device: the validity of a spec (NDT_OK / NDT_ERR_INVALID), and the value kernel's plan for a cloud of
+ * n_points -- blocks of one wave, eight queries (teams of eight lanes) per pass; one pass per block up to 4096 blocks, beyond
+ * which the blocks stride over the passes.  *queries_per_block: the most queries one block works on. */
+ndt_status ndt_host_outlier_spec_check(const ndt_outlier_spec* spec);
+ndt_status ndt_host_outlier_plan(size_t n_points, int* blocks, int* queries_per_block);
+
 /* ---- accumulating target: posed scans merged into the voxel grid (scan-to-MAP registration) --------------------------
  * Every other target of this library is built from ONE cloud; a mapping node that wants to register a scan against the map
  * would have to keep every posed point and rebuild the grid from the growing concatenation before each scan.  Here the

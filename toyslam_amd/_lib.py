@@ -18,6 +18,7 @@ EVAL_STRIDE = 32
 COMM_ID_BYTES = 128
 
 SELECT_FINITE, SELECT_BOX, SELECT_BOX_NEGATE, SELECT_RANGE, SELECT_RANGE_NEGATE, SELECT_KEY, SELECT_KEY_NEGATE = 1, 2, 4, 8, 16, 32, 64
+OUTLIER_RADIUS, OUTLIER_STATISTICAL = 1, 2
 COV_LAPLACE, COV_SANDWICH = 0, 1
 COV_INDEFINITE = 1
 
@@ -32,6 +33,18 @@ class SelectSpec(C.Structure):
     """ndt_select_spec (include/ndt_mi355.h)"""
     _fields_ = [("flags", C.c_uint), ("box_min", C.c_float * 3), ("box_max", C.c_float * 3), ("centre", C.c_float * 3),
                 ("r_min", C.c_float), ("r_max", C.c_float), ("key_lo", C.c_double), ("key_hi", C.c_double)]
+
+
+class OutlierSpec(C.Structure):
+    """ndt_outlier_spec (include/ndt_mi355.h)"""
+    _fields_ = [("method", C.c_int), ("negate", C.c_int), ("radius", C.c_float), ("min_neighbors", C.c_int), ("mean_k", C.c_int),
+                ("stddev_mul", C.c_double)]
+
+
+class OutlierStats(C.Structure):
+    """ndt_outlier_stats (include/ndt_mi355.h)"""
+    _fields_ = [("n_finite", C.c_size_t), ("n_valid", C.c_size_t), ("mean", C.c_double), ("stddev", C.c_double),
+                ("threshold", C.c_double)]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
@@ -176,6 +189,14 @@ SIGNATURES = {
     "ndt_diag_select": (C.c_int, [vp, szp, szp, szp]),
     "ndt_host_select_point": (C.c_int, [C.POINTER(SelectSpec), fp, C.c_double, ip]),
     "ndt_host_select_plan": (C.c_int, [C.c_size_t, ip, ip]),
+    "ndt_cloud_neighbor_values": (C.c_int, [vp, vp, C.POINTER(OutlierSpec), vp, C.c_int, C.POINTER(OutlierStats)]),
+    "ndt_cloud_remove_outliers": (C.c_int, [vp, vp, C.POINTER(OutlierSpec), C.POINTER(vp), C.POINTER(C.c_int32), szp,
+                                            C.POINTER(OutlierStats)]),
+    "ndt_cloud_remove_outliers_clouds": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, C.POINTER(OutlierSpec), C.POINTER(vp), szp,
+                                                   C.POINTER(OutlierStats)]),
+    "ndt_diag_outliers": (C.c_int, [vp, szp, szp, szp, szp]),
+    "ndt_host_outlier_spec_check": (C.c_int, [C.POINTER(OutlierSpec)]),
+    "ndt_host_outlier_plan": (C.c_int, [C.c_size_t, ip, ip]),
     "ndt_pose_covariance": (C.c_int, [vp, fp, C.c_int, C.c_double, dp, vp]),
     "ndt_pairs_pose_covariances": (C.c_int, [vp, fp, C.c_int, C.c_double, dp, vp]),
     "ndt_host_pose_covariance": (C.c_int, [dp, dp, dp, C.c_size_t, C.c_int, C.c_double, dp, dp, dp, ip]),

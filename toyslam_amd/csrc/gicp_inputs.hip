@@ -110,21 +110,17 @@ ndt_status gicp_set_input(gicp_context* h, int which, bool resident, bool usable
 }  // namespace
 
 namespace ndtc {
-// The voxel index of `cloud` (on the device, every point finite -- so the box the cloud carries over its finite points is
-// the box of all of them) into in.grid: leaf size from the cloud's own density (volume guess first, then corrected once
-// from the measured points per occupied cell -- scans are surfaces, so occupancy grows with the square of the leaf).
-// Built with `c`: its stream, its scratch, its pool (the caller has made `c` current); `c` holds neither the cloud nor the grid.
-ndt_status gicp_index_cloud(ndt_context* c, const std::shared_ptr<DeviceCloud>& cloud, LeafHint& hint, GicpInput& in) {
-  in.grid.reset();  // (before the new one is allocated: an input never holds two)
-  std::shared_ptr<DeviceGrid> grid;
-  const size_t n = cloud->n;
-  ndt_status s = NDT_OK;
+// The extents of a cloud's finite box and the clamp that keeps a dense cell table over it within budget
+namespace {
+struct LeafClamp {
   double ext[3], vol = 1.0;
-  for (int k = 0; k < 3; k++) {
-    ext[k] = std::max(static_cast<double>(cloud->bb_max[1][k]) - static_cast<double>(cloud->bb_min[1][k]), 1e-3);
-    vol *= ext[k];
+  explicit LeafClamp(const DeviceCloud& cloud) {
+    for (int k = 0; k < 3; k++) {
+      ext[k] = std::max(static_cast<double>(cloud.bb_max[1][k]) - static_cast<double>(cloud.bb_min[1][k]), 1e-3);
+      vol *= ext[k];
+    }
   }
-  auto clamp_leaf = [&](double leaf) {
+  float operator()(double leaf) const {
     leaf = std::max(leaf, 1e-4);
     for (int it = 0; it < 64; it++) {  // keep the dense cell table within budget
       const double cells = (ext[0] / leaf + 2) * (ext[1] / leaf + 2) * (ext[2] / leaf + 2);
@@ -132,16 +128,27 @@ ndt_status gicp_index_cloud(ndt_context* c, const std::shared_ptr<DeviceCloud>& 
       leaf *= 1.26;
     }
     return static_cast<float>(leaf);
-  };
-  float leaf = clamp_leaf(std::cbrt(vol * kGicpPointsPerCell / static_cast<double>(n)));
-  // start from the leaf the previous cloud of about this size ended up with (usually right at once; the search results do
-  // not depend on the leaf, only the time does)
-  if (hint.leaf > 0 && n >= hint.n - hint.n / 4 && n <= hint.n + hint.n / 4) leaf = clamp_leaf(hint.leaf);
+  }
+};
+}  // namespace
+
+float index_leaf_clamped(const DeviceCloud& cloud, double want) { return LeafClamp(cloud)(want); }
+
+// Leaf size from the cloud's own density (volume guess first, then corrected once from the measured points per occupied cell
+// -- scans are surfaces, so occupancy grows with the square of the leaf).  What GICP's index and the statistical outlier
+// filter's share.
+ndt_status index_cloud_by_density(ndt_context* c, const std::shared_ptr<DeviceCloud>& cloud, bool dense, float leaf0, float* leaf_out,
+                                  std::shared_ptr<DeviceGrid>& grid) {
+  const size_t n = cloud->n;
+  ndt_status s = NDT_OK;
+  const LeafClamp clamp_leaf(*cloud);
+  float leaf = leaf0 > 0 ? clamp_leaf(leaf0) : clamp_leaf(std::cbrt(clamp_leaf.vol * kGicpPointsPerCell / static_cast<double>(std::max<size_t>(n, 1))));
   for (int pass = 0; pass < 4; pass++) {
-    s = build_grid(c, cloud, GridSpec{leaf, 1, c->eig_ratio, 0, true, true}, grid);  // cells and their point lists only
+    s = build_grid(c, cloud, GridSpec{leaf, 1, c->eig_ratio, 0, dense, true}, grid);  // cells and their point lists only
     if (s) return s;
     s = grid_counts(c, grid.get());
     if (s) return s;
+    if (grid->empty) break;  // (no finite point: nothing to index)
     const double per_cell = static_cast<double>(n) / static_cast<double>(std::max<size_t>(grid->n_leaves, 1));
     if (per_cell <= 2.0 * kGicpPointsPerCell && (per_cell >= 0.4 * kGicpPointsPerCell || grid->n_leaves <= 8)) break;
     // too coarse (dense surfaces) or too fine (flat / thin clouds, where the volume guess means little)
@@ -149,6 +156,23 @@ ndt_status gicp_index_cloud(ndt_context* c, const std::shared_ptr<DeviceCloud>& 
     if (next < 0.9f * leaf || next > 1.1f * leaf) leaf = next;
     else break;
   }
+  if (leaf_out) *leaf_out = leaf;
+  return NDT_OK;
+}
+
+// The voxel index of `cloud` (on the device, every point finite -- so the box the cloud carries over its finite points is
+// the box of all of them) into in.grid: leaf size from the cloud's own density (index_cloud_by_density).
+// Built with `c`: its stream, its scratch, its pool (the caller has made `c` current); `c` holds neither the cloud nor the grid.
+ndt_status gicp_index_cloud(ndt_context* c, const std::shared_ptr<DeviceCloud>& cloud, LeafHint& hint, GicpInput& in) {
+  in.grid.reset();  // (before the new one is allocated: an input never holds two)
+  std::shared_ptr<DeviceGrid> grid;
+  const size_t n = cloud->n;
+  // start from the leaf the previous cloud of about this size ended up with (usually right at once; the search results do
+  // not depend on the leaf, only the time does)
+  const float leaf0 = hint.leaf > 0 && n >= hint.n - hint.n / 4 && n <= hint.n + hint.n / 4 ? hint.leaf : 0.f;
+  float leaf = 0.f;
+  ndt_status s = index_cloud_by_density(c, cloud, true, leaf0, &leaf, grid);
+  if (s) return s;
   if (std::getenv("NDT_GICP_DEBUG"))
     std::fprintf(stderr, "[gicp index] n=%zu leaf=%.4f cells=%lld (%d x %d x %d) occupied=%zu\n", n, static_cast<double>(leaf),
                  grid->geom.n_cells, grid->geom.div_b[0], grid->geom.div_b[1], grid->geom.div_b[2], grid->n_leaves);

@@ -508,6 +508,8 @@ struct ndt_context {
   void* sel_pinned = nullptr;
   size_t sel_pinned_bytes = 0;
   size_t sel_launches = 0, sel_blocks = 0, sel_clouds = 0;
+  // the outlier filters (ndt_outliers.hip): what the last call that reached the device did (ndt_diag_outliers)
+  size_t ol_index_builds = 0, ol_value_launches = 0, ol_value_blocks = 0, ol_scanned = 0;
 
   ~ndt_context() {
     for (ndt_context* w : batch_workers) delete w;
@@ -690,6 +692,35 @@ ndt_status nvtl_ready(ndt_context* h, bool need_source);
 // doubles of device memory that receive L per point, -1.0 where the point has no neighbour.  Waits for the stream.
 ndt_status nvtl_launch(ndt_context* h, const float4* d_pts, size_t n, const float* T_colmajor, double* d_out, double* nvtl,
                        size_t* n_found);
+// ---- ndt_select.hip
+// One cloud of a selection: n records at `in` (keys: n device doubles, or null), kept records to `out` (room for n), their
+// indices to `idx` (device, room for n; or null).  key_range (device, two doubles, or null): this cloud's own key_lo / key_hi
+// in place of the spec's.  Results: kept, and the boxes / route of the kept points in `res`.
+struct SelJob {
+  const float4* in = nullptr;
+  size_t n = 0;
+  const double* keys = nullptr;
+  const double* key_range = nullptr;
+  float4* out = nullptr;
+  int* idx = nullptr;
+  size_t kept = 0;
+  DeviceCloud* res = nullptr;  // n, bb_min / bb_max, box_route are set
+};
+// the two launches over all jobs and the call's one wait (idx_host: page-locked or null, the indices of jobs[0])
+ndt_status select_run(ndt_handle h, std::vector<SelJob>& jobs, const ndt_select_spec& spec, int* idx_host);
+// one cloud's records into a new cloud
+ndt_status select_one(ndt_handle h, const float4* d_in, size_t n, const ndt_select_spec& spec, const double* d_keys,
+                      std::shared_ptr<DeviceCloud>& out, int32_t* kept_idx, size_t* n_kept, const double* d_key_range = nullptr);
+std::shared_ptr<DeviceCloud> select_new_cloud(ndt_handle h);   // an ndt_cloud's DeviceCloud made on h's stream
+ndt_status select_cloud_checks(ndt_handle h, ndt_cloud c);     // what every selection refuses of an input cloud
+// ---- gicp_inputs.hip
+// A point index (index_only grid) over `cloud` whose leaf follows the cloud's own density: leaf0 > 0 is tried first, else a
+// volume guess, then corrected from the measured points per occupied cell.  dense: the cloud holds no NaN / inf.  *leaf_out:
+// the leaf it ended with.  Search results never depend on the leaf, only the time does.
+ndt_status index_cloud_by_density(ndt_context* c, const std::shared_ptr<DeviceCloud>& cloud, bool dense, float leaf0, float* leaf_out,
+                                  std::shared_ptr<DeviceGrid>& grid);
+// ... with a leaf of about `want` (the outlier filter's radius), clamped into the same cell budget; one build
+float index_leaf_clamped(const DeviceCloud& cloud, double want);
 // ---- ndt_filter.hip
 ndt_status filter_slots(ndt_handle h, int which, FilterPending& P);
 // The geometry and route of one N1 filter, from the cloud's box alone -- the one decision voxel_filter_enqueue and the

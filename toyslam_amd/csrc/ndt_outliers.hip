@@ -1,0 +1,711 @@
+// ndt_outliers.hip -- the neighbourhood filters of resident clouds (ndt_cloud_neighbor_values, ndt_cloud_remove_outliers,
+// ndt_cloud_remove_outliers_clouds; contract: include/ndt_mi355.h, shared host / device definitions: ndt_outliers.hpp).
+// Modelled on pcl::RadiusOutlierRemoval / pcl::StatisticalOutlierRemoval; no bit parity with PCL is claimed.
+//   index  : one PointIndex per input cloud (build_grid, index_only, not dense: rows that are not finite are simply not in
+//            it); the leaf follows the cloud's density (STATISTICAL, GICP's rule) or the radius (RADIUS).  Time only: no
+//            result depends on the leaf.
+//   values : k_outlier_values, one launch whatever the number of clouds (a member table; a block finds its member by
+//            bisection and then does what a block of a single-cloud launch does).  One wave per block, a team of eight lanes
+//            per query, the exact shell search of ndt_search.hpp.
+//            STATISTICAL keeps a per-team LDS list of the mean_k smallest DISTANCES (the value depends on the multiset of
+//            distances alone, so no positions, no tie rule); the query itself is the one zero-distance candidate dropped.
+//            RADIUS counts the candidates within r2, shells pruned by the radius; counts are integers, exact by construction.
+//            Queries the shells cannot finish within max_shells go to one scan over the whole cloud by the wave.
+//   stats  : k_outlier_stats reduces fixed chunks of the values to (count, sum, M2 about the chunk's mean), k_outlier_merge
+//            merges the rows in order by Chan's rule and writes mean, stddev, threshold and the key range of the selection --
+//            f64, no floating-point atomics, a plan that depends on n alone.
+//   select : the compaction of ndt_select.hip with the values as device-resident keys and, per cloud, the key range the merge
+//            wrote: the values never visit the host.
+#include "ndt_internal.hpp"
+#include "ndt_outliers.hpp"
+
+#include "ndt_device.hpp"
+#include "ndt_search.hpp"
+
+namespace ndtc {
+namespace {
+
+using ndt::PointIndex;
+constexpr int kTeams = ndt::kOutlierTeams;
+constexpr int kBlock = 64;  // one wave
+static_assert(kTeams * ndt::kTeam == kBlock, "a block is one wave of eight teams");
+
+struct OutMember {
+  PointIndex ix;   // mode 1: pts and n only
+  double* values;  // n
+  int first_block, n_blocks;
+  int mode;  // 0: search; 1: no search -- a finite point's value is 0 (|F| <= mean_k, or no finite point at all)
+};
+struct StatMember {
+  const double* values;
+  double* row;  // [6]: n_valid, mean, stddev, threshold, key_lo, key_hi
+  int n, chunk;
+  int first_block, n_blocks;
+  int degenerate;  // |F| <= mean_k: statistics and threshold are 0
+};
+
+__device__ __forceinline__ bool finite3(const float4& p) { return __builtin_isfinite(p.x) && __builtin_isfinite(p.y) && __builtin_isfinite(p.z); }
+
+// Block `block` of the `n_blocks` that cut cloud `ix`: eight queries per pass, strided by n_blocks.
+__device__ __forceinline__ void outlier_block(const PointIndex& ix, int mode, int method, int k, float radius, float r2, int block,
+                                              int n_blocks, double* __restrict__ values, unsigned* __restrict__ scanned) {
+#pragma clang fp contract(off)
+  using namespace ndt;
+  extern __shared__ unsigned char ol_lds[];
+  const int lane = threadIdx.x, sub = lane & (kTeam - 1), team = lane / kTeam, team_base = lane & ~(kTeam - 1);
+  float* ld = reinterpret_cast<float*>(ol_lds) + team * k;                            // [8][k] squared distances, unordered
+  double* od = reinterpret_cast<double*>(ol_lds + kTeams * k * sizeof(float)) + team * k;  // [8][k] distances, ascending
+  const bool stat = method == NDT_OUTLIER_STATISTICAL;
+  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  auto lds_fence = [] { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); };  // one wave per block: program order is enough
+  if (mode == 1) {
+    for (int i = block * kBlock + lane; i < ix.n; i += n_blocks * kBlock) values[i] = finite3(ix.pts[i]) ? 0.0 : nan;
+    return;
+  }
+  const float leaf = fminf(ix.geom.leaf[0], fminf(ix.geom.leaf[1], ix.geom.leaf[2]));
+  const int r_lim = max(ix.geom.div_b[0], max(ix.geom.div_b[1], ix.geom.div_b[2]));
+  const int r_max = max_shells(ix, r_lim);
+  // rounding: an unvisited point at true distance D may compute a d2 a few 1e-7 (relative) below D*D.  The bounds that decide
+  // what is NOT looked at keep 1e-5 clear of the values they are compared with, so what is looked at decides alone.
+  constexpr float kClear = 1.00001f;
+  // The loop is uniform across the wave (a team without a query idles): the whole-cloud scan is wave-wide.
+  for (int base = block * kTeams; base < ix.n; base += n_blocks * kTeams) {
+    const int i = base + team;  // uniform within a team
+    const bool live = i < ix.n;
+    const float4 q = live ? ix.pts[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const bool search = live && finite3(q);
+    int ci = 0, cj = 0, ck = 0;
+    float margin = 0.f;
+    if (search) query_cell(ix.geom, q.x, q.y, q.z, ci, cj, ck, margin);
+    double value = nan;
+    if (stat) {
+      int cnt = 0;  // entries in the list (team-uniform, like everything below that is not marked "lane")
+      float worst = INFINITY;
+      int worst_slot = 0;
+      bool self_dropped = false;
+      auto find_worst = [&] {  // the list's largest entry
+        float bd = -1.0f;  // lane: largest over my slots
+        int bs = -1;
+        for (int j = sub; j < cnt; j += kTeam) {
+          const float d = ld[j];
+          if (bs < 0 || d > bd) {
+            bd = d;
+            bs = j;
+          }
+        }
+#pragma unroll
+        for (int off = 1; off < kTeam; off <<= 1) {
+          const float o = __shfl_xor(bd, off, kWave);
+          const int os = __shfl_xor(bs, off, kWave);
+          if (os >= 0 && (bs < 0 || o > bd || (o == bd && os < bs))) {
+            bd = o;
+            bs = os;
+          }
+        }
+        worst = bd;
+        worst_slot = bs;
+      };
+      auto insert_one = [&](float cd) {  // team-collective: a candidate known to all eight lanes
+        if (cd == 0.0f && !self_dropped) {  // d2(i, i) is exactly 0: the query itself, or a duplicate in its place
+          self_dropped = true;
+          return;
+        }
+        if (cnt < k) {
+          if (sub == 0) ld[cnt] = cd;
+          lds_fence();
+          cnt++;
+          if (cnt == k) find_worst();
+        } else if (cd < worst) {
+          if (sub == 0) ld[worst_slot] = cd;
+          lds_fence();
+          find_worst();
+        }
+      };
+      auto offer = [&](float d, unsigned, bool ok) {  // every lane brings one candidate (or none)
+        const bool want = ok && (cnt < k || d < worst || (d == 0.0f && !self_dropped));
+        unsigned pending = static_cast<unsigned>((__ballot(want) >> team_base) & 0xffull);
+        while (pending) {
+          const int owner = __builtin_ctz(pending);
+          pending &= pending - 1;
+          insert_one(__shfl(d, team_base + owner, kWave));
+        }
+      };
+      bool done = !search;
+      for (int r = 0; r <= r_max && !done; r++) {
+        team_shell(ix, ci, cj, ck, r, sub, q.x, q.y, q.z, offer);
+        // every unvisited point is at least r cells plus the query's margin (less the index-rounding slack) away
+        const float reach = static_cast<float>(r) * leaf + margin - ix.slack;
+        if ((cnt == k && reach > 0.0f && worst * kClear < reach * reach) || r >= r_lim) done = true;
+      }
+      // Sparse neighbourhoods: the WAVE looks at every point, twice, for one unfinished query at a time.  Pass 1 keeps each
+      // lane's eight smallest distances in registers; the (k + 1)-th smallest of the wave's 512 values (the query itself is
+      // among them) bounds the k-th neighbour's distance from above.  Pass 2 hands the points inside that bound to the
+      // query's team, which fills its list afresh.
+      unsigned long long open_teams = __ballot(!done && sub == 0);
+      if (open_teams && lane == 0) atomicAdd(scanned, static_cast<unsigned>(__popcll(open_teams)));
+      while (open_teams) {
+        const int src_lane = __builtin_ctzll(open_teams);
+        open_teams &= open_teams - 1;
+        const bool mine = (team == src_lane / kTeam);
+        const float ox = __shfl(q.x, src_lane, kWave), oy = __shfl(q.y, src_lane, kWave), oz = __shfl(q.z, src_lane, kWave);
+        const int count = ix.n_sorted;
+        float m0 = INFINITY, m1 = INFINITY, m2 = INFINITY, m3 = INFINITY, m4 = INFINITY, m5 = INFINITY, m6 = INFINITY, m7 = INFINITY;
+        auto keep = [&](float d, bool ok) {
+          if (!ok || !(d < m7)) return;
+          m7 = d;  // bubble the newcomer down the sorted registers
+          float t;
+          if (m7 < m6) { t = m6; m6 = m7; m7 = t; }
+          if (m6 < m5) { t = m5; m5 = m6; m6 = t; }
+          if (m5 < m4) { t = m4; m4 = m5; m5 = t; }
+          if (m4 < m3) { t = m3; m3 = m4; m4 = t; }
+          if (m3 < m2) { t = m2; m2 = m3; m3 = t; }
+          if (m2 < m1) { t = m1; m1 = m2; m2 = t; }
+          if (m1 < m0) { t = m0; m0 = m1; m1 = t; }
+        };
+        for (int b0 = 0; b0 < count; b0 += 4 * kWave) {
+          const int p0 = b0 + lane, p1 = p0 + kWave, p2 = p1 + kWave, p3 = p2 + kWave;
+          const float4 a = ix.sorted_pts[min(p0, count - 1)], b = ix.sorted_pts[min(p1, count - 1)];
+          const float4 c = ix.sorted_pts[min(p2, count - 1)], d = ix.sorted_pts[min(p3, count - 1)];
+          keep(dist2_f32(ox, oy, oz, a.x, a.y, a.z), p0 < count);
+          keep(dist2_f32(ox, oy, oz, b.x, b.y, b.z), p1 < count);
+          keep(dist2_f32(ox, oy, oz, c.x, c.y, c.z), p2 < count);
+          keep(dist2_f32(ox, oy, oz, d.x, d.y, d.z), p3 < count);
+        }
+        float bound = INFINITY;
+        for (int j = 0; j <= k; j++) {  // pop the wave's smallest head k + 1 times (|F| > k: that many values exist)
+          float hd = m0;
+          int who = lane;
+#pragma unroll
+          for (int off = 1; off < kWave; off <<= 1) {
+            const float oh = __shfl_xor(hd, off, kWave);
+            const int ow = __shfl_xor(who, off, kWave);
+            if (oh < hd || (oh == hd && ow < who)) {
+              hd = oh;
+              who = ow;
+            }
+          }
+          bound = hd;
+          if (who == lane) { m0 = m1; m1 = m2; m2 = m3; m3 = m4; m4 = m5; m5 = m6; m6 = m7; m7 = INFINITY; }
+        }
+        if (mine) {
+          cnt = 0;
+          worst = INFINITY;
+          self_dropped = false;
+        }
+        auto hand_over = [&](float d, bool ok) {  // wave-uniform call: the hits go to the owning team one by one
+          unsigned long long hits = __ballot(ok && !(d > bound));
+          while (hits) {
+            const int from = __builtin_ctzll(hits);
+            hits &= hits - 1;
+            const float cd = __shfl(d, from, kWave);
+            if (mine) insert_one(cd);
+          }
+        };
+        for (int b0 = 0; b0 < count; b0 += 4 * kWave) {
+          const int p0 = b0 + lane, p1 = p0 + kWave, p2 = p1 + kWave, p3 = p2 + kWave;
+          const float4 a = ix.sorted_pts[min(p0, count - 1)], b = ix.sorted_pts[min(p1, count - 1)];
+          const float4 c = ix.sorted_pts[min(p2, count - 1)], d = ix.sorted_pts[min(p3, count - 1)];
+          hand_over(dist2_f32(ox, oy, oz, a.x, a.y, a.z), p0 < count);
+          hand_over(dist2_f32(ox, oy, oz, b.x, b.y, b.z), p1 < count);
+          hand_over(dist2_f32(ox, oy, oz, c.x, c.y, c.z), p2 < count);
+          hand_over(dist2_f32(ox, oy, oz, d.x, d.y, d.z), p3 < count);
+        }
+      }
+      if (search) {
+        // rank sort: entry j goes to the place given by the number of entries before it (equal distances: by slot)
+        for (int j = sub; j < cnt; j += kTeam) {
+          const float d = ld[j];
+          int rank = 0;
+          for (int t = 0; t < cnt; t++) {
+            const float o = ld[t];
+            rank += (o < d || (o == d && t < j)) ? 1 : 0;
+          }
+          od[rank] = sqrt(static_cast<double>(d));
+        }
+        lds_fence();
+        if (sub == 0) {
+          double sum = 0.0;
+          for (int j = 0; j < cnt; j++) sum += od[j];
+          value = sum / static_cast<double>(k);
+        }
+        lds_fence();
+      }
+    } else {
+      // RADIUS.  The shells out to the first whose reach clears the radius; beyond max_shells, the scan over the cloud.
+      int count_in = 0;  // lane
+      auto consider = [&](float d, unsigned, bool ok) { count_in += (ok && d <= r2) ? 1 : 0; };
+      const float far = radius * kClear;
+      int r_need = 0;
+      bool scan = false;
+      if (search) {
+        const float x = far - margin + ix.slack;
+        r_need = x > 0.0f ? static_cast<int>(fminf(x / leaf, 1.0e6f)) : 0;
+        r_need = min(r_need, r_lim);
+        while (r_need < r_lim && !(static_cast<float>(r_need) * leaf + margin - ix.slack > far)) r_need++;
+        scan = r_need > r_max;
+        if (!scan)
+          for (int r = 0; r <= r_need; r++) team_shell(ix, ci, cj, ck, r, sub, q.x, q.y, q.z, consider, r2 * (kClear * kClear));
+      }
+      int total = team_sum(count_in);
+      unsigned long long open_teams = __ballot(scan && sub == 0);
+      if (open_teams && lane == 0) atomicAdd(scanned, static_cast<unsigned>(__popcll(open_teams)));
+      while (open_teams) {
+        const int src_lane = __builtin_ctzll(open_teams);
+        open_teams &= open_teams - 1;
+        const float ox = __shfl(q.x, src_lane, kWave), oy = __shfl(q.y, src_lane, kWave), oz = __shfl(q.z, src_lane, kWave);
+        const int count = ix.n_sorted;
+        int c4 = 0;
+        for (int b0 = 0; b0 < count; b0 += 4 * kWave) {
+          const int p0 = b0 + lane, p1 = p0 + kWave, p2 = p1 + kWave, p3 = p2 + kWave;
+          const float4 a = ix.sorted_pts[min(p0, count - 1)], b = ix.sorted_pts[min(p1, count - 1)];
+          const float4 c = ix.sorted_pts[min(p2, count - 1)], d = ix.sorted_pts[min(p3, count - 1)];
+          c4 += (p0 < count && dist2_f32(ox, oy, oz, a.x, a.y, a.z) <= r2) ? 1 : 0;
+          c4 += (p1 < count && dist2_f32(ox, oy, oz, b.x, b.y, b.z) <= r2) ? 1 : 0;
+          c4 += (p2 < count && dist2_f32(ox, oy, oz, c.x, c.y, c.z) <= r2) ? 1 : 0;
+          c4 += (p3 < count && dist2_f32(ox, oy, oz, d.x, d.y, d.z) <= r2) ? 1 : 0;
+        }
+#pragma unroll
+        for (int off = 1; off < kWave; off <<= 1) c4 += __shfl_xor(c4, off, kWave);
+        if (team == src_lane / kTeam) total = c4;
+      }
+      if (search) value = static_cast<double>(total - 1);  // the query itself is within any radius of itself
+    }
+    if (live && sub == 0) values[i] = value;
+  }
+}
+
+// (a call of one cloud hands its member over as a kernel argument: no table to copy up first)
+__global__ __launch_bounds__(kBlock) void k_outlier_values(OutMember one, const OutMember* __restrict__ members, int n_members, int method,
+                                                           int k, float radius, float r2, unsigned* __restrict__ scanned) {
+  const int b = static_cast<int>(blockIdx.x);
+  if (n_members == 1) {
+    if (b < one.n_blocks) outlier_block(one.ix, one.mode, method, k, radius, r2, b, one.n_blocks, one.values, scanned);
+    return;
+  }
+  int lo = 0, hi = n_members - 1;  // the last member whose first_block <= b
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (members[mid].first_block <= b) lo = mid;
+    else hi = mid - 1;
+  }
+  const OutMember m = members[lo];
+  const int local = b - m.first_block;
+  if (local >= m.n_blocks) return;
+  outlier_block(m.ix, m.mode, method, k, radius, r2, local, m.n_blocks, m.values, scanned);
+}
+
+// tree sum over the block's threads in a fixed order; the result in every thread
+__device__ __forceinline__ double block_sum(double v, double* sh) {
+  __syncthreads();
+  sh[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = ndt::kOutlierStatBlock / 2; s > 0; s >>= 1) {
+    if (static_cast<int>(threadIdx.x) < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+    __syncthreads();
+  }
+  return sh[0];
+}
+
+// rows[block] = (count, sum, M2 about sum / count) of the block's chunk of its member's values; NaN values are no values
+__global__ __launch_bounds__(ndt::kOutlierStatBlock) void k_outlier_stats(const StatMember* __restrict__ members, int n_members,
+                                                                        double* __restrict__ rows) {
+#pragma clang fp contract(off)
+  __shared__ double sh[ndt::kOutlierStatBlock];
+  const int b = static_cast<int>(blockIdx.x);
+  int lo = 0, hi = n_members - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (members[mid].first_block <= b) lo = mid;
+    else hi = mid - 1;
+  }
+  const StatMember m = members[lo];
+  const int lb = b - m.first_block;
+  if (lb >= m.n_blocks) return;
+  const long long start = static_cast<long long>(lb) * m.chunk;
+  const int len = static_cast<int>(min(static_cast<long long>(m.chunk), m.n - start));
+  double cnt = 0.0, sum = 0.0;
+  for (int j = threadIdx.x; j < len; j += ndt::kOutlierStatBlock) {
+    const double v = m.values[start + j];
+    if (v == v) {
+      cnt += 1.0;
+      sum += v;
+    }
+  }
+  cnt = block_sum(cnt, sh);
+  sum = block_sum(sum, sh);
+  const double mean = cnt > 0.0 ? sum / cnt : 0.0;
+  double m2 = 0.0;
+  for (int j = threadIdx.x; j < len; j += ndt::kOutlierStatBlock) {
+    const double v = m.values[start + j];
+    if (v == v) m2 += (v - mean) * (v - mean);
+  }
+  m2 = block_sum(m2, sh);
+  if (threadIdx.x == 0) {
+    rows[static_cast<size_t>(b) * 3 + 0] = cnt;
+    rows[static_cast<size_t>(b) * 3 + 1] = sum;
+    rows[static_cast<size_t>(b) * 3 + 2] = m2;
+  }
+}
+
+// one thread per member: its rows merged in block order (Chan), then mean, stddev, threshold and the selection's key range
+__global__ __launch_bounds__(64) void k_outlier_merge(const StatMember* __restrict__ members, int n_members, const double* __restrict__ rows,
+                                                      double stddev_mul) {
+#pragma clang fp contract(off)
+  const int t = static_cast<int>(blockIdx.x) * 64 + static_cast<int>(threadIdx.x);
+  if (t >= n_members) return;
+  const StatMember m = members[t];
+  double na = 0.0, mean = 0.0, m2 = 0.0;
+  if (!m.degenerate)
+    for (int b = 0; b < m.n_blocks; b++) {
+      const double* r = rows + static_cast<size_t>(m.first_block + b) * 3;
+      const double nb = r[0];
+      if (nb == 0.0) continue;
+      const double mean_b = r[1] / nb, n = na + nb, delta = mean_b - mean;
+      mean = mean + delta * (nb / n);
+      m2 = (m2 + r[2]) + (delta * delta) * (na * nb / n);
+      na = n;
+    }
+  const double sd = na >= 2.0 ? sqrt(m2 / (na - 1.0)) : 0.0;
+  const double thr = mean + stddev_mul * sd;
+  m.row[0] = na;
+  m.row[1] = mean;
+  m.row[2] = sd;
+  m.row[3] = thr;
+  m.row[4] = -__longlong_as_double(0x7ff0000000000000ll);
+  m.row[5] = thr;
+}
+
+int max_blocks_switch() {
+  static const int v = [] {
+    const char* e = getenv("NDT_OUTLIER_MAX_BLOCKS");  // development switch: small values reach the strided regime with small clouds
+    const int x = e ? atoi(e) : 0;
+    return x > 0 ? std::min(x, ndt::kOutlierMaxBlocks) : ndt::kOutlierMaxBlocks;
+  }();
+  return v;
+}
+
+// What one call works on: the clouds, where each one's values go, and what comes back
+struct OutlierRun {
+  std::vector<std::shared_ptr<DeviceCloud>> clouds;
+  std::vector<double*> d_values;          // per cloud: n doubles of device memory (ignored where n == 0)
+  std::vector<ndt_outlier_stats> stats;   // per cloud, valid after the stream has been waited for (finish())
+  DevBuf<double> d_rows;                  // per cloud [6]: the merge's row (STATISTICAL); +4: the selection's key range
+  // kept until the wait
+  std::vector<std::shared_ptr<DeviceGrid>> grids;
+  std::vector<OutMember> mem;
+  std::vector<StatMember> smem;
+  std::vector<double> rows_host;
+  unsigned scanned_host = 0;
+  DevBuf<unsigned char> d_mem, d_smem;
+  DevBuf<double> d_partials;
+  DevBuf<unsigned> d_scanned;
+  std::vector<size_t> n_finite;
+  std::vector<char> degenerate;
+};
+
+// Everything up to and including the merge, queued on h's stream; the read-backs are queued too but NOT waited for.
+ndt_status outlier_queue(ndt_handle h, const ndt_outlier_spec& spec, OutlierRun& R) {
+  hipStream_t st = h->stream;
+  const size_t nc = R.clouds.size();
+  const bool stat = spec.method == NDT_OUTLIER_STATISTICAL;
+  h->ol_index_builds = h->ol_value_launches = h->ol_value_blocks = h->ol_scanned = 0;
+  R.stats.assign(nc, ndt_outlier_stats{});
+  R.grids.resize(nc);
+  R.n_finite.assign(nc, 0);
+  R.degenerate.assign(nc, 1);
+  // ---- the indices
+  for (size_t k = 0; k < nc; k++) {
+    const std::shared_ptr<DeviceCloud>& c = R.clouds[k];
+    if (c->n == 0) continue;
+    ndt_status s;
+    if (stat) {
+      s = index_cloud_by_density(h, c, false, 0.f, nullptr, R.grids[k]);
+    } else {
+      s = build_grid(h, c, GridSpec{index_leaf_clamped(*c, spec.radius), 1, h->eig_ratio, 0, false, true}, R.grids[k]);
+      if (!s) s = grid_counts(h, R.grids[k].get());
+    }
+    if (s) return s;
+    h->ol_index_builds++;
+    DeviceGrid* g = R.grids[k].get();
+    if (!g->empty && g->n_sorted) {
+      if ((s = ensure_cell2leaf(h, g))) return s;
+      R.n_finite[k] = g->n_sorted;
+    }
+    R.degenerate[k] = R.n_finite[k] == 0 || (stat && R.n_finite[k] <= static_cast<size_t>(spec.mean_k));
+  }
+  // ---- the value launch
+  long long blocks = 0, sblocks = 0;
+  for (size_t k = 0; k < nc; k++) {
+    const DeviceCloud* c = R.clouds[k].get();
+    if (c->n == 0) continue;
+    OutMember m{};
+    if (R.degenerate[k]) {
+      m.ix.pts = c->pts.p;
+      m.ix.n = static_cast<int>(c->n);
+      m.mode = 1;
+    } else {
+      fill_point_index(R.grids[k].get(), m.ix);
+    }
+    int nb = 0, qpb = 0;
+    ndt::outlier_plan(c->n, &nb, &qpb);
+    m.values = R.d_values[k];
+    m.first_block = static_cast<int>(blocks);
+    m.n_blocks = std::min(nb, max_blocks_switch());
+    blocks += m.n_blocks;
+    R.mem.push_back(m);
+    if (stat) {
+      StatMember sm{};
+      sm.values = R.d_values[k];
+      sm.n = static_cast<int>(c->n);
+      ndt::outlier_stat_plan(c->n, &sm.n_blocks, &sm.chunk);
+      sm.first_block = static_cast<int>(sblocks);
+      sm.degenerate = R.degenerate[k];
+      sblocks += sm.n_blocks;
+      R.smem.push_back(sm);  // (row: below, once the rows are allocated)
+    }
+  }
+  HIP_TRY(R.d_rows.reserve(std::max<size_t>(nc, 1) * 6));
+  if (R.mem.empty()) return NDT_OK;
+  if (blocks > std::numeric_limits<int>::max()) return fail(NDT_ERR_INVALID, "too many points");
+  const int n_mem = static_cast<int>(R.mem.size());
+  HIP_TRY(R.d_scanned.reserve(1));
+  HIP_TRY(hipMemsetAsync(R.d_scanned.p, 0, sizeof(unsigned), st));
+  if (n_mem > 1) {
+    HIP_TRY(R.d_mem.reserve(R.mem.size() * sizeof(OutMember)));
+    HIP_TRY(hipMemcpyAsync(R.d_mem.p, R.mem.data(), R.mem.size() * sizeof(OutMember), hipMemcpyHostToDevice, st));
+  }
+  const int kk = stat ? spec.mean_k : 0;
+  const size_t lds = stat ? static_cast<size_t>(kTeams) * static_cast<size_t>(kk) * (sizeof(float) + sizeof(double)) : 0;
+  hipLaunchKernelGGL(k_outlier_values, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), lds, st, R.mem[0],
+                     reinterpret_cast<const OutMember*>(R.d_mem.p), n_mem, spec.method, kk, spec.radius, spec.radius * spec.radius,
+                     R.d_scanned.p);
+  HIP_TRY(hipGetLastError());
+  h->ol_value_launches = 1;
+  h->ol_value_blocks = static_cast<size_t>(blocks);
+  HIP_TRY(hipMemcpyAsync(&R.scanned_host, R.d_scanned.p, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  // ---- the statistics
+  if (stat) {
+    size_t j = 0;
+    for (size_t k = 0; k < nc; k++)
+      if (R.clouds[k]->n) R.smem[j++].row = R.d_rows.p + 6 * k;
+    HIP_TRY(R.d_smem.reserve(R.smem.size() * sizeof(StatMember)));
+    HIP_TRY(hipMemcpyAsync(R.d_smem.p, R.smem.data(), R.smem.size() * sizeof(StatMember), hipMemcpyHostToDevice, st));
+    HIP_TRY(R.d_partials.reserve(static_cast<size_t>(sblocks) * 3));
+    const StatMember* dsm = reinterpret_cast<const StatMember*>(R.d_smem.p);
+    hipLaunchKernelGGL(k_outlier_stats, dim3(static_cast<unsigned>(sblocks)), dim3(ndt::kOutlierStatBlock), 0, st, dsm, n_mem, R.d_partials.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_outlier_merge, dim3(static_cast<unsigned>((n_mem + 63) / 64)), dim3(64), 0, st, dsm, n_mem, R.d_partials.p,
+                       spec.stddev_mul);
+    HIP_TRY(hipGetLastError());
+    R.rows_host.assign(nc * 6, 0.0);
+    for (size_t k = 0; k < nc; k++)  // (a cloud without a point has no row on the device)
+      if (R.clouds[k]->n)
+        HIP_TRY(hipMemcpyAsync(&R.rows_host[6 * k], R.d_rows.p + 6 * k, 6 * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  return NDT_OK;
+}
+
+// after the stream has been waited for: the statistics of every cloud, the diagnostics
+void outlier_finish(ndt_handle h, const ndt_outlier_spec& spec, OutlierRun& R) {
+  const bool stat = spec.method == NDT_OUTLIER_STATISTICAL;
+  for (size_t k = 0; k < R.clouds.size(); k++) {
+    ndt_outlier_stats& s = R.stats[k];
+    s.n_finite = R.n_finite[k];
+    if (!stat) {
+      s.n_valid = s.n_finite;
+      s.threshold = static_cast<double>(spec.min_neighbors);
+    } else if (!R.degenerate[k]) {
+      s.n_valid = s.n_finite;
+      s.mean = R.rows_host[6 * k + 1];
+      s.stddev = R.rows_host[6 * k + 2];
+      s.threshold = R.rows_host[6 * k + 3];
+    }
+  }
+  h->ol_scanned = R.scanned_host;
+}
+
+// the selection that goes with a spec: the values are the keys
+ndt_select_spec key_spec(const ndt_outlier_spec& spec) {
+  ndt_select_spec s{};
+  s.flags = NDT_SELECT_KEY | (spec.negate ? NDT_SELECT_KEY_NEGATE : 0);
+  if (spec.method == NDT_OUTLIER_RADIUS) {
+    s.key_lo = static_cast<double>(spec.min_neighbors);
+    s.key_hi = std::numeric_limits<double>::infinity();
+  } else {  // (the range of every cloud comes from the device: [-inf, its threshold])
+    s.key_lo = -std::numeric_limits<double>::infinity();
+    s.key_hi = std::numeric_limits<double>::infinity();
+  }
+  return s;
+}
+
+ndt_status spec_checks(const ndt_outlier_spec* spec) {
+  if (!spec) return fail(NDT_ERR_INVALID, "null spec");
+  if (const char* why = ndt::outlier_spec_error(*spec)) return fail(NDT_ERR_INVALID, why);
+  return NDT_OK;
+}
+
+// ndt_diag_select reports on the selections alone: what the compaction inside an outlier call did is taken back
+struct SelDiagKeep {
+  ndt_handle h;
+  size_t a, b, c;
+  explicit SelDiagKeep(ndt_handle hh) : h(hh), a(hh->sel_launches), b(hh->sel_blocks), c(hh->sel_clouds) {}
+  ~SelDiagKeep() {
+    h->sel_launches = a;
+    h->sel_blocks = b;
+    h->sel_clouds = c;
+  }
+};
+struct Drain {  // whatever path leaves: the queued copies have read (written) the run's host memory before it dies
+  hipStream_t s;
+  ~Drain() { (void)hipStreamSynchronize(s); }
+};
+
+}  // namespace
+}  // namespace ndtc
+
+extern "C" {
+
+ndt_status ndt_cloud_neighbor_values(ndt_handle h, ndt_cloud in, const ndt_outlier_spec* spec, double* values, int values_on_device,
+                                     ndt_outlier_stats* stats) {
+  if (!h || !values) return fail(NDT_ERR_INVALID, "bad arguments");
+  ndt_status s = select_cloud_checks(h, in);
+  if (!s) s = spec_checks(spec);
+  if (s) return s;
+  s = ensure_device(h);
+  if (!s) s = cloud_use_on(h, in->c.get());
+  if (s) return s;
+  const size_t n = in->c->n;
+  OutlierRun R;
+  DevBuf<double> d_vals;
+  if (n && !values_on_device) HIP_TRY(d_vals.reserve(n));
+  R.clouds.push_back(in->c);
+  R.d_values.push_back(values_on_device ? values : d_vals.p);
+  {
+    Drain drain{h->stream};
+    s = outlier_queue(h, *spec, R);
+    if (s) return s;
+    if (n && !values_on_device) HIP_TRY(hipMemcpyAsync(values, d_vals.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+  }
+  outlier_finish(h, *spec, R);
+  if (stats) *stats = R.stats[0];
+  return NDT_OK;
+}
+
+ndt_status ndt_cloud_remove_outliers(ndt_handle h, ndt_cloud in, const ndt_outlier_spec* spec, ndt_cloud* out, int32_t* kept_idx,
+                                     size_t* n_kept, ndt_outlier_stats* stats) {
+  if (out) *out = nullptr;
+  if (!h || !out) return fail(NDT_ERR_INVALID, "bad arguments");
+  ndt_status s = select_cloud_checks(h, in);
+  if (!s) s = spec_checks(spec);
+  if (s) return s;
+  s = ensure_device(h);
+  if (!s) s = cloud_use_on(h, in->c.get());
+  if (s) return s;
+  const size_t n = in->c->n;
+  OutlierRun R;
+  DevBuf<double> d_vals;
+  if (n) HIP_TRY(d_vals.reserve(n));
+  R.clouds.push_back(in->c);
+  R.d_values.push_back(d_vals.p);
+  std::shared_ptr<DeviceCloud> c;
+  size_t kept = 0;
+  {
+    Drain drain{h->stream};
+    SelDiagKeep keep(h);
+    s = outlier_queue(h, *spec, R);
+    if (s) return s;
+    const bool own_range = spec->method == NDT_OUTLIER_STATISTICAL && n;
+    s = select_one(h, in->c->pts.p, n, key_spec(*spec), d_vals.p, c, kept_idx, &kept, own_range ? R.d_rows.p + 4 : nullptr);
+    if (s) return s;
+  }
+  outlier_finish(h, *spec, R);
+  if (n_kept) *n_kept = kept;
+  if (stats) *stats = R.stats[0];
+  *out = new ndt_cloud_s{c};
+  return NDT_OK;
+}
+
+ndt_status ndt_cloud_remove_outliers_clouds(ndt_handle h, const ndt_cloud* in, size_t n_clouds, const ndt_outlier_spec* spec, ndt_cloud* out,
+                                            size_t* n_kept, ndt_outlier_stats* stats) {
+  if (!h || !out) return fail(NDT_ERR_INVALID, "bad arguments");
+  if (n_clouds > 65535) return fail(NDT_ERR_INVALID, "at most 65535 clouds per call");
+  for (size_t k = 0; k < n_clouds; k++) out[k] = nullptr;
+  if (n_clouds && !in) return fail(NDT_ERR_INVALID, "null clouds");
+  ndt_status s = spec_checks(spec);
+  if (s) return s;
+  size_t total = 0;
+  for (size_t k = 0; k < n_clouds; k++) {
+    if ((s = select_cloud_checks(h, in[k]))) return s;
+    total += in[k]->c->n;
+  }
+  if (total > static_cast<size_t>(std::numeric_limits<int>::max())) return fail(NDT_ERR_INVALID, "too many points");
+  if (n_clouds == 0) return NDT_OK;
+  s = ensure_device(h);
+  if (s) return s;
+  OutlierRun R;
+  DevBuf<double> d_vals;
+  HIP_TRY(d_vals.reserve(std::max<size_t>(total, 1)));
+  // the outputs are slices of one block (room for every input point), kept alive by the slices' `owner`
+  auto blk = select_new_cloud(h);
+  std::vector<std::shared_ptr<DeviceCloud>> res(n_clouds);
+  std::vector<SelJob> jobs(n_clouds);
+  HIP_TRY(blk->pts.reserve(std::max<size_t>(total, 1)));
+  blk->n = total;
+  size_t first = 0;
+  for (size_t k = 0; k < n_clouds; k++) {
+    if ((s = cloud_use_on(h, in[k]->c.get()))) return s;
+    R.clouds.push_back(in[k]->c);
+    R.d_values.push_back(d_vals.p + first);
+    first += in[k]->c->n;
+  }
+  {
+    Drain drain{h->stream};
+    SelDiagKeep keep(h);
+    s = outlier_queue(h, *spec, R);
+    if (s) return s;
+    first = 0;
+    for (size_t k = 0; k < n_clouds; k++) {
+      DeviceCloud* c = in[k]->c.get();
+      res[k] = select_new_cloud(h);
+      jobs[k].in = c->pts.p;
+      jobs[k].n = c->n;
+      jobs[k].keys = d_vals.p + first;
+      jobs[k].key_range = spec->method == NDT_OUTLIER_STATISTICAL ? R.d_rows.p + 6 * k + 4 : nullptr;
+      jobs[k].out = blk->pts.p + first;
+      jobs[k].res = res[k].get();
+      first += c->n;
+    }
+    s = select_run(h, jobs, key_spec(*spec), nullptr);
+    if (s) return s;
+  }
+  outlier_finish(h, *spec, R);
+  for (size_t k = 0; k < n_clouds; k++) {
+    res[k]->pts.borrow(jobs[k].out, jobs[k].kept);
+    res[k]->owner = blk;
+    out[k] = new ndt_cloud_s{res[k]};
+    if (n_kept) n_kept[k] = jobs[k].kept;
+    if (stats) stats[k] = R.stats[k];
+  }
+  return NDT_OK;
+}
+
+ndt_status ndt_diag_outliers(ndt_handle h, size_t* index_builds, size_t* value_launches, size_t* value_blocks, size_t* scanned_queries) {
+  if (!h || !index_builds || !value_launches || !value_blocks || !scanned_queries) return fail(NDT_ERR_INVALID, "bad arguments");
+  *index_builds = h->ol_index_builds;
+  *value_launches = h->ol_value_launches;
+  *value_blocks = h->ol_value_blocks;
+  *scanned_queries = h->ol_scanned;
+  return NDT_OK;
+}
+
+ndt_status ndt_host_outlier_spec_check(const ndt_outlier_spec* spec) { return spec_checks(spec); }
+
+ndt_status ndt_host_outlier_plan(size_t n_points, int* blocks, int* queries_per_block) {
+  if (!blocks || !queries_per_block) return fail(NDT_ERR_INVALID, "bad arguments");
+  if (n_points > static_cast<size_t>(std::numeric_limits<int>::max())) return fail(NDT_ERR_INVALID, "too many points");
+  ndt::outlier_plan(n_points, blocks, queries_per_block);
+  return NDT_OK;
+}
+
+}  // extern "C"

@@ -25,6 +25,7 @@ struct SelSeg {
   const float4* in;
   float4* out;
   const double* keys;  // null without KEY
+  const double* key_range;  // null, or two device doubles that take the place of the spec's key_lo / key_hi for this cloud
   int* idx;            // null: no indices wanted
   unsigned long long word0;  // the cloud's first ballot word
   int n, ppb, wpb;           // points, points per block, ballot words per block
@@ -48,6 +49,10 @@ __global__ __launch_bounds__(kSelBlock) void k_select_count(SelSeg one, const Se
                                                             unsigned long long* __restrict__ ballots, unsigned* __restrict__ counts) {
   __shared__ unsigned wave_count[kSelWaves];
   const SelSeg g = n_segs == 1 ? one : segs[seg_of(segs, n_segs, blockIdx.x)];
+  if (g.key_range) {  // a key range of the cloud's own, computed on the device (the outlier filters' thresholds)
+    spec.key_lo = g.key_range[0];
+    spec.key_hi = g.key_range[1];
+  }
   const int lb = static_cast<int>(blockIdx.x) - g.first_block;
   const long long start = static_cast<long long>(lb) * g.ppb;
   const int len = static_cast<int>(min(static_cast<long long>(g.ppb), g.n - start));
@@ -162,17 +167,7 @@ __global__ __launch_bounds__(kSelBlock) void k_select_place(SelSeg one, const Se
   if (lb == g.n_blocks - 1 && threadIdx.x == 0) totals[g.slot] = run;
 }
 
-// One cloud of a call: n records at `in` (keys: n device doubles, or null), kept records to `out` (room for n), their
-// indices to `idx` (device, room for n; or null).  Results: kept, and the boxes / route of the kept points in `res`.
-struct SelJob {
-  const float4* in = nullptr;
-  size_t n = 0;
-  const double* keys = nullptr;
-  float4* out = nullptr;
-  int* idx = nullptr;
-  size_t kept = 0;
-  DeviceCloud* res = nullptr;  // n, bb_min / bb_max, box_route are set
-};
+}  // namespace
 
 // The two launches over all jobs and the call's one wait.  idx_host (page-locked, may be null): the indices of jobs[0] are
 // copied there, all n of them, in front of the wait.
@@ -193,6 +188,7 @@ ndt_status select_run(ndt_handle h, std::vector<SelJob>& jobs, const ndt_select_
     g.in = j.in;
     g.out = j.out;
     g.keys = j.keys;
+    g.key_range = j.key_range;
     g.idx = j.idx;
     g.word0 = total_words;
     g.n = static_cast<int>(j.n);
@@ -257,7 +253,7 @@ ndt_status select_run(ndt_handle h, std::vector<SelJob>& jobs, const ndt_select_
   return NDT_OK;
 }
 
-std::shared_ptr<DeviceCloud> new_cloud(ndt_handle h) {
+std::shared_ptr<DeviceCloud> select_new_cloud(ndt_handle h) {
   auto c = std::make_shared<DeviceCloud>();
   c->device = h->device;
   c->made_on = h->stream;
@@ -265,12 +261,12 @@ std::shared_ptr<DeviceCloud> new_cloud(ndt_handle h) {
 }
 
 // what every selection refuses of its spec
-ndt_status spec_checks(const ndt_select_spec* spec) {
+static ndt_status spec_checks(const ndt_select_spec* spec) {
   if (!spec) return fail(NDT_ERR_INVALID, "null spec");
   if (const char* why = ndt::select_spec_error(*spec)) return fail(NDT_ERR_INVALID, why);
   return NDT_OK;
 }
-ndt_status cloud_checks(ndt_handle h, ndt_cloud c) {
+ndt_status select_cloud_checks(ndt_handle h, ndt_cloud c) {
   if (!c || !c->c) return fail(NDT_ERR_INVALID, "null cloud");
   if (c->c->device >= 0 && c->c->device != h->device) return fail(NDT_ERR_INVALID, "the cloud lives on another device");
   if (c->c->n > static_cast<size_t>(std::numeric_limits<int>::max())) return fail(NDT_ERR_INVALID, "too many points");
@@ -279,8 +275,8 @@ ndt_status cloud_checks(ndt_handle h, ndt_cloud c) {
 
 // one cloud's records (n at d_in; keys on the device or null) into a new cloud; what ndt_cloud_select and the NVTL form share
 ndt_status select_one(ndt_handle h, const float4* d_in, size_t n, const ndt_select_spec& spec, const double* d_keys,
-                      std::shared_ptr<DeviceCloud>& out, int32_t* kept_idx, size_t* n_kept) {
-  auto c = new_cloud(h);
+                      std::shared_ptr<DeviceCloud>& out, int32_t* kept_idx, size_t* n_kept, const double* d_key_range) {
+  auto c = select_new_cloud(h);
   std::vector<SelJob> jobs(1);
   DevBuf<int> d_idx;
   int* idx_host = nullptr;
@@ -295,6 +291,7 @@ ndt_status select_one(ndt_handle h, const float4* d_in, size_t n, const ndt_sele
   jobs[0].in = d_in;
   jobs[0].n = n;
   jobs[0].keys = d_keys;
+  jobs[0].key_range = d_key_range;
   jobs[0].out = c->pts.p;
   jobs[0].idx = kept_idx ? d_idx.p : nullptr;
   jobs[0].res = c.get();
@@ -309,7 +306,6 @@ ndt_status select_one(ndt_handle h, const float4* d_in, size_t n, const ndt_sele
   return NDT_OK;
 }
 
-}  // namespace
 }  // namespace ndtc
 
 extern "C" {
@@ -318,7 +314,7 @@ ndt_status ndt_cloud_select(ndt_handle h, ndt_cloud in, const ndt_select_spec* s
                             ndt_cloud* out, int32_t* kept_idx, size_t* n_kept) {
   if (out) *out = nullptr;
   if (!h || !out) return fail(NDT_ERR_INVALID, "bad arguments");
-  ndt_status s = cloud_checks(h, in);
+  ndt_status s = select_cloud_checks(h, in);
   if (!s) s = spec_checks(spec);
   if (s) return s;
   if ((spec->flags & NDT_SELECT_KEY) && !keys) return fail(NDT_ERR_INVALID, "a KEY selection needs keys");
@@ -355,7 +351,7 @@ ndt_status ndt_cloud_select_clouds(ndt_handle h, const ndt_cloud* in, size_t n_c
   if (spec->flags & NDT_SELECT_KEY) return fail(NDT_ERR_INVALID, "the many-clouds selection takes no KEY test");
   size_t total = 0;
   for (size_t k = 0; k < n_clouds; k++) {
-    if ((s = cloud_checks(h, in[k]))) return s;
+    if ((s = select_cloud_checks(h, in[k]))) return s;
     total += in[k]->c->n;
   }
   if (total > static_cast<size_t>(std::numeric_limits<int>::max())) return fail(NDT_ERR_INVALID, "too many points");
@@ -363,7 +359,7 @@ ndt_status ndt_cloud_select_clouds(ndt_handle h, const ndt_cloud* in, size_t n_c
   s = ensure_device(h);
   if (s) return s;
   // the outputs are slices of one block (room for every input point), kept alive by the slices' `owner`
-  auto blk = new_cloud(h);
+  auto blk = select_new_cloud(h);
   std::vector<std::shared_ptr<DeviceCloud>> res(n_clouds);
   std::vector<SelJob> jobs(n_clouds);
   HIP_TRY(blk->pts.reserve(std::max<size_t>(total, 1)));
@@ -372,7 +368,7 @@ ndt_status ndt_cloud_select_clouds(ndt_handle h, const ndt_cloud* in, size_t n_c
   for (size_t k = 0; k < n_clouds; k++) {
     DeviceCloud* c = in[k]->c.get();
     if ((s = cloud_use_on(h, c))) return s;
-    res[k] = new_cloud(h);
+    res[k] = select_new_cloud(h);
     jobs[k].in = c->pts.p;
     jobs[k].n = c->n;
     jobs[k].out = blk->pts.p + first;

@@ -903,6 +903,90 @@ class NormalDistributionsTransform:
         check(_lib.lib().ndt_host_select_point(C.byref(spec), _f(p), float(key), C.byref(keep)))
         return bool(keep.value)
 
+    # ---- outlier removal of resident clouds (ndt_cloud_neighbor_values / ndt_cloud_remove_outliers / _clouds) ------------
+    @staticmethod
+    def outlierSpec(radius=None, min_neighbors=None, mean_k=None, stddev_mul=None, negate=False):
+        """The ndt_outlier_spec of the keyword form: radius and min_neighbors (RADIUS), or mean_k and stddev_mul
+        (STATISTICAL); exactly one of the two pairs."""
+        if (radius is None) == (mean_k is None):
+            raise ValueError("give radius / min_neighbors or mean_k / stddev_mul")
+        s = _lib.OutlierSpec()
+        s.negate = int(bool(negate))
+        if radius is not None:
+            s.method, s.radius, s.min_neighbors = _lib.OUTLIER_RADIUS, float(np.float32(radius)), int(1 if min_neighbors is None else min_neighbors)
+        else:
+            s.method, s.mean_k, s.stddev_mul = _lib.OUTLIER_STATISTICAL, int(mean_k), float(1.0 if stddev_mul is None else stddev_mul)
+        return s
+
+    @staticmethod
+    def _outlier_stats(st):
+        return dict(n_finite=st.n_finite, n_valid=st.n_valid, mean=st.mean, stddev=st.stddev, threshold=st.threshold)
+
+    def neighborValues(self, dc, radius=None, min_neighbors=None, mean_k=None, stddev_mul=None, device=False, spec=None):
+        """The value the outlier filters judge every point of the resident cloud `dc` by (ndt_cloud_neighbor_values; defined
+        in include/ndt_mi355.h): with radius, the number of other finite points within it; with mean_k, the mean distance
+        to the mean_k nearest other finite points.  NaN for a point that is not finite.  -> ((n,) float64, stats dict).
+        device: the address (an int) of n float64 of the caller's own memory on the handle's device, which then receives
+        the values instead: -> (that address, stats dict)."""
+        if spec is None:
+            spec = self.outlierSpec(radius, min_neighbors, mean_k, stddev_mul)
+        n = len(dc)
+        st = _lib.OutlierStats()
+        if device is not False and device is not None:
+            check(self._L.ndt_cloud_neighbor_values(self._h, dc._c, C.byref(spec), C.c_void_p(int(device)), 1, C.byref(st)))
+            return int(device), self._outlier_stats(st)
+        out = np.zeros(max(n, 1), dtype=np.float64)
+        check(self._L.ndt_cloud_neighbor_values(self._h, dc._c, C.byref(spec), C.c_void_p(out.ctypes.data), 0, C.byref(st)))
+        return out[:n].copy(), self._outlier_stats(st)
+
+    def removeOutliers(self, dc, radius=None, min_neighbors=None, mean_k=None, stddev_mul=None, negate=False, indices=False,
+                       spec=None):
+        """The points of the resident cloud `dc` the radius or the statistical outlier filter keeps, in dc's order, as a new
+        DeviceCloud with exact boxes (ndt_cloud_remove_outliers); the per-point values stay on the device.
+        -> (DeviceCloud, stats dict); indices=True: (DeviceCloud, stats, (n_kept,) int32 indices of the kept points)."""
+        if spec is None:
+            spec = self.outlierSpec(radius, min_neighbors, mean_k, stddev_mul, negate)
+        n = len(dc)
+        idx = np.zeros(max(n, 1), dtype=np.int32) if indices else None
+        c, nk, st = C.c_void_p(None), C.c_size_t(0), _lib.OutlierStats()
+        check(self._L.ndt_cloud_remove_outliers(self._h, dc._c, C.byref(spec), C.byref(c),
+                                                idx.ctypes.data_as(C.POINTER(C.c_int32)) if indices else None, C.byref(nk), C.byref(st)))
+        out = DeviceCloud(self, c)
+        return (out, self._outlier_stats(st), idx[:nk.value].copy()) if indices else (out, self._outlier_stats(st))
+
+    def removeOutliersClouds(self, clouds, radius=None, min_neighbors=None, mean_k=None, stddev_mul=None, negate=False, spec=None):
+        """removeOutliers of every DeviceCloud of the list under one spec: one value launch and the selection's two
+        (ndt_cloud_remove_outliers_clouds).  -> (list of DeviceCloud, list of stats dicts), entry k what removeOutliers
+        gives for clouds[k] alone, the same bits."""
+        if spec is None:
+            spec = self.outlierSpec(radius, min_neighbors, mean_k, stddev_mul, negate)
+        clouds = list(clouds)
+        n = len(clouds)
+        arr = (C.c_void_p * max(n, 1))(*[c._c for c in clouds])
+        out = (C.c_void_p * max(n, 1))()
+        nk = (C.c_size_t * max(n, 1))()
+        st = (_lib.OutlierStats * max(n, 1))()
+        check(self._L.ndt_cloud_remove_outliers_clouds(self._h, arr, n, C.byref(spec), out, nk, st))
+        return [DeviceCloud(self, C.c_void_p(p)) for p in list(out)[:n]], [self._outlier_stats(st[k]) for k in range(n)]
+
+    def outlierDiag(self):
+        """What the last outlier call that reached the device did (ndt_diag_outliers)."""
+        a, b, c, d = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        check(self._L.ndt_diag_outliers(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return dict(index_builds=a.value, value_launches=b.value, value_blocks=c.value, scanned_queries=d.value)
+
+    @staticmethod
+    def outlierPlan(n):
+        """(blocks, queries_per_block) of the value kernel over a cloud of n points (ndt_host_outlier_plan; host only)."""
+        b, q = C.c_int(0), C.c_int(0)
+        check(_lib.lib().ndt_host_outlier_plan(int(n), C.byref(b), C.byref(q)))
+        return b.value, q.value
+
+    @staticmethod
+    def outlierSpecCheck(spec):
+        """Is the _lib.OutlierSpec valid?  (ndt_host_outlier_spec_check; host only.)"""
+        return _lib.lib().ndt_host_outlier_spec_check(C.byref(spec)) == _lib.NDT_OK
+
     # ---- pose covariance (ndt_pose_covariance / ndt_pairs_pose_covariances) ----------------------------------------------
     def poseCovariance(self, transform=None, method="sandwich", scale=1.0, info=False):
         """6x6 covariance of the pose x y z roll pitch yaw of the input source at `transform` (None: the last align's final
