@@ -42,6 +42,11 @@
 // its registered pose against the centroid cloud of the target it was registered to (ndt_get_centroid_fitness_score), before
 // the scan is accumulated: the quality number an accumulated target, which keeps no points, can give.  Without the switch
 // every line of output is as it was.
+// --gicp [--gicp-gate <m>] (with --scan-to-map): every scan after the first is registered by GICP against the accumulated target
+// (gicp_set_input_target_grid: the scan's k-NN covariances matched to the voxel distributions of the map, found through the map's
+// own voxel table -- nothing is built over the map) instead of by NDT; the guess is the previous pose as before and the same
+// per-scan lines are printed.  --gicp-gate: the correspondence distance in metres (default 5; a few leaves).  --map-fitness moves
+// the scan by the GICP result.  Not with --nvtl, --covariance or --reject-unexplained, which read the NDT registration's result.
 // --nvtl (with --scan-to-map): after each registration "nvtl: <value> found <n_found>/<n>" is printed -- the nearest-voxel
 // transformation likelihood of the scan at its registered pose against the target it was registered to (ndt_get_nvtl), before
 // the scan is accumulated: the number a localisation stack thresholds to accept or reject the pose.
@@ -72,6 +77,7 @@
 #include <thread>
 #include <vector>
 
+#include "gicp_mi355.h"
 #include "ndt_mi355.h"
 
 #define CHECK(call)                                                     \
@@ -154,6 +160,7 @@ struct Node {
   ndt_outlier_spec radius_spec{}, stat_spec{};
   bool reject = false;       // --reject-unexplained: a registered scan is accumulated without the points the target does not explain
   double reject_below = 0;
+  gicp_handle gicp = nullptr;  // --gicp: the registrations are GICP's against the accumulated target (bound to the NDT handle's grid)
   std::vector<std::vector<float>> trajectory;                     // trajectory_
   std::vector<float> pose = std::vector<float>(kIdentity, kIdentity + 16);
   std::vector<float> pres_transform = std::vector<float>(kIdentity, kIdentity + 16);  // rosbag node :33,95
@@ -176,11 +183,22 @@ struct Node {
   }
 
   // after align: -> whether the scan goes into the global map, and with which pose
-  bool after_align(ndt_handle h, float* T, int converged, int iterations, std::vector<float>& map_pose, std::string& err) {
+  bool after_align(ndt_handle h, float* T, int converged, int iterations, std::vector<float>& map_pose, std::string& err,
+                   ndt_cloud scan = nullptr) {
     registered++;
     if (map_fitness) {  // against the target the scan was registered to: the scan has not been accumulated yet
       double fitness = 0;
-      if (ndt_get_centroid_fitness_score(h, 1.7976931348623157e308, &fitness) != NDT_OK) {
+      ndt_status fs = NDT_OK;
+      if (gicp) {  // the NDT handle has no result of this registration: the scan moved by GICP's
+        const void* d_pts = nullptr;
+        size_t n = 0;
+        fs = ndt_cloud_data(scan, &d_pts, &n);
+        const size_t offsets[2] = {0, n};
+        if (fs == NDT_OK) fs = ndt_batch_centroid_fitness_scores_device(h, d_pts, offsets, 1, 16, T, 1.7976931348623157e308, &fitness);
+      } else {
+        fs = ndt_get_centroid_fitness_score(h, 1.7976931348623157e308, &fitness);
+      }
+      if (fs != NDT_OK) {
         err = ndt_last_error();
         return false;
       }
@@ -352,17 +370,22 @@ static int run_resident(Node& node, ndt_pcd_sequence_handle seq, float voxel_lea
       }
       t0 = clock_type::now();  // process_available_clouds, :70-100
       if (!node.scan_to_map) CHECK(ndt_set_input_target_cloud(h, previous, 1));
-      CHECK(ndt_set_input_source_cloud(h, current));
+      if (!node.gicp) CHECK(ndt_set_input_source_cloud(h, current));
       float T[16];
       int converged = 0, iterations = 0;
       double probability = 0;
       const float* guess = node.rosbag ? node.pres_transform.data() : nullptr;
       if (node.scan_to_map) guess = node.trajectory.empty() ? kIdentity : node.trajectory.back().data();  // the previous scan's pose
-      CHECK(ndt_align(h, guess, T, &converged, &iterations, &probability, nullptr, 0));
+      if (node.gicp) {  // against the accumulated target as it is now: the binding reads the map's grid at every call
+        CHECK(gicp_set_input_source_cloud(node.gicp, current));
+        CHECK(gicp_align(node.gicp, guess, T, &converged, &iterations, nullptr));
+      } else {
+        CHECK(ndt_align(h, guess, T, &converged, &iterations, &probability, nullptr, 0));
+      }
       node.t_align += since(t0);
       std::vector<float> map_pose;
       std::string err;
-      const bool into_map = node.after_align(h, T, converged, iterations, map_pose, err);
+      const bool into_map = node.after_align(h, T, converged, iterations, map_pose, err, current);
       if (!err.empty()) {
         std::fprintf(stderr, "%s\n", err.c_str());
         return 1;
@@ -649,12 +672,14 @@ int main(int argc, char** argv) {
   bool scan_to_map = false, bad_window = false, localize = false, bad_file = false, map_fitness = false, nvtl = false, covariance = false;
   bool range = false, bad_range = false, reject = false, bad_reject = false;
   bool outliers_radius = false, outliers_stat = false, bad_outliers = false;
+  bool use_gicp = false, have_gate = false, bad_gate = false;
+  double gicp_gate = 5.0;
   ndt_outlier_spec radius_spec{}, stat_spec{};
   float window = 0, range_min = 0, range_max = 0;
   double reject_below = 0;
   const char *save_target = nullptr, *load_target = nullptr;
   static const char kUsage[] =
-      "usage: map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--range <min> <max>] [--outliers-radius <r> <min_neighbors>] [--outliers-stat <mean_k> <stddev_mul>] [--reject-unexplained <L>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> "
+      "usage: map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--gicp [--gicp-gate <m>]] [--range <min> <max>] [--outliers-radius <r> <min_neighbors>] [--outliers-stat <mean_k> <stddev_mul>] [--reject-unexplained <L>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> "
       "[voxel_leaf_size] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]\n";
   {  // the switches are taken out of the line before the positional arguments are read
     int kept = 1;
@@ -676,6 +701,12 @@ int main(int argc, char** argv) {
         nvtl = true;
       } else if (std::strcmp(argv[i], "--covariance") == 0) {
         covariance = true;
+      } else if (std::strcmp(argv[i], "--gicp") == 0) {
+        use_gicp = true;
+      } else if (std::strcmp(argv[i], "--gicp-gate") == 0) {
+        have_gate = true;
+        gicp_gate = i + 1 < argc ? std::atof(argv[++i]) : 0.0;
+        bad_gate = !(gicp_gate > 0);
       } else if (std::strcmp(argv[i], "--range") == 0) {
         range = true;
         bad_range = i + 2 >= argc;
@@ -735,6 +766,11 @@ int main(int argc, char** argv) {
                          "go with --scan-to-map\n%s", kUsage);
     return 2;
   }
+  if (bad_gate || (have_gate && !use_gicp) || (use_gicp && (!scan_to_map || nvtl || covariance || reject))) {
+    std::fprintf(stderr, "--gicp goes with --scan-to-map and --gicp-gate <m> (m > 0) with --gicp; --nvtl, --covariance and --reject-unexplained "
+                         "read the NDT registration's result, so they do not go with --gicp\n%s", kUsage);
+    return 2;
+  }
   if (argc < 2) {
     std::printf("%s", kUsage);
     return 0;
@@ -788,6 +824,11 @@ int main(int argc, char** argv) {
   CHECK(ndt_warm_up(h, 65536));  // (a node knows its sensor: the reference's scans are lidar sweeps of some ten thousand points)
   if (map_handle) CHECK(ndt_warm_up(map_handle, 65536));
   if (load_target) CHECK(ndt_target_accumulate_load(h, load_target));  // the map is there before the first scan arrives
+  if (use_gicp) {  // (bound once: every registration reads the accumulated target as it is then)
+    CHECK(gicp_create(0, &node.gicp));
+    CHECK(gicp_set_max_correspondence_distance(node.gicp, gicp_gate));
+    CHECK(gicp_set_input_target_grid(node.gicp, h, GICP_VOXEL_COV_PLANE));
+  }
   const double warm_ms = since(t_warm);
   const auto t_begin = clock_type::now();
   const int rc = !serial ? run_pipelined(node, seq, voxel_leaf_size, h, map_handle)
@@ -822,6 +863,7 @@ int main(int argc, char** argv) {
     std::printf("global map written to %s\n", argv[3]);
   }
   ndt_pcd_sequence_close(seq);
+  if (node.gicp) gicp_destroy(node.gicp);  // (before the handle it borrows)
   ndt_destroy(h);
   if (map_handle) ndt_destroy(map_handle);
   return 0;

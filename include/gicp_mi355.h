@@ -55,6 +55,42 @@ ndt_status gicp_set_target_covariances(gicp_handle h, const double* cov, size_t 
 ndt_status gicp_set_input_target_cloud(gicp_handle h, ndt_cloud c);
 ndt_status gicp_set_input_source_cloud(gicp_handle h, ndt_cloud c);
 
+/* setInputTarget from a VOXEL GRID: the target becomes the current target grid of the NDT handle `map` -- cloud-built in any
+ * form (dense, sparse), accumulated (ndt_target_accumulate*), cropped or imported -- and GICP registers against its voxel
+ * distributions (voxelised, distribution-to-distribution GICP; scan-to-map GICP when the grid is an accumulated map).
+ * Correspondences are found through the grid's own voxel table: no index is built over the map, nothing is rebuilt when it grows.
+ *
+ * The target set D: the voxels of the grid that the DIRECT neighbour searches see -- a voxel is in D when its table entry is a
+ * record; a voxel that reached min_points_per_voxel but was rejected, and a voxel still under min_points_per_voxel, are not.
+ * D is ordered by ascending linear voxel index: a subset of the centroid cloud of ndt_grid_centroids, in its order.  A
+ * correspondence (gicp_step_correspond's corr) is an ordinal in D.  Voxel v contributes
+ *   - as target point its f32 centroid, the bits ndt_grid_centroids returns for it;
+ *   - as target covariance a 3x3 f64 matrix, by cov_mode:
+ *       GICP_VOXEL_COV_RAW   the inverse of the voxel's f64 inverse covariance (Eigen's cofactor inverse, as everywhere in the
+ *                            library): the voxel's (regularised) covariance in m^2;
+ *       GICP_VOXEL_COV_PLANE I - (1 - gicp_epsilon) n n^T, n the unit eigenvector of the largest eigenvalue of the inverse
+ *                            covariance (the f64 Jacobi routine of the k-NN covariances): GICP's (1, 1, epsilon) regularisation
+ *                            along the voxel's normal, the scale of the source's k-NN covariances.  Recommended.
+ * The GICP handle BORROWS `map`: the caller keeps it alive while it is bound and uses both handles from one thread at a time;
+ * both must be on the same device.  Every call that needs the target -- gicp_align, gicp_get_fitness_score,
+ * gicp_step_correspond, gicp_step_functor, gicp_covariances(which = 0), gicp_target_grid_voxels -- reads map's grid as it is
+ * THEN, ordered behind the work queued on map's stream by an event (the device is not synchronised).  D's arrays are made in one
+ * mark / scan / gather pass and cached; the pass runs again when the grid has changed (an update, a crop, an import, a reset)
+ * or map holds another grid (ndt_set_input_target*).  After such a change gicp_step_functor wants a new gicp_step_correspond.
+ * gicp_set_input_target* and gicp_set_input_target_grid(h, NULL, ..) drop the binding.  Everything `map` holds is left as it
+ * is (the grid's cached centroid excursion, which ndt_get_centroid_fitness_score shares, may be computed here).
+ * NDT_ERR_INVALID before any device work: NULL h, an unknown cov_mode, handles on different devices.  On a grid target also:
+ * gicp_set_target_covariances; gicp_covariances(which = 0) with neighbour lists; gicp_align_guesses (the batch forms take cloud
+ * targets).  NDT_ERR_NO_INPUT at use: map has no target, or D is empty. */
+enum { GICP_VOXEL_COV_PLANE = 0, GICP_VOXEL_COV_RAW = 1 };
+ndt_status gicp_set_input_target_grid(gicp_handle h, ndt_handle map, int cov_mode);
+/* D as the next registration would use it: *n voxels; xyz1 [n][4] f32 (x, y, z, 1), cov9 [n][9] row-major f64, idx [n] linear
+ * voxel indices (any may be NULL; all NULL: the count alone).  capacity < *n: NDT_ERR_INVALID, *n written, no array is. */
+ndt_status gicp_target_grid_voxels(gicp_handle h, float* xyz1, double* cov9, int64_t* idx, size_t capacity, size_t* n);
+/* the handle's grid target: the mark / scan / gather passes run so far, the voxels of D, the grid's centroid excursion (m) the
+ * search gives way by, and the blocks of the last k_correspond_voxel launch (gicp_diag_plan's second entry) */
+ndt_status gicp_diag_target_grid(gicp_handle h, size_t* refreshes, size_t* voxels, float* excursion, size_t* correspond_blocks);
+
 /* GICP of n_pairs (target, source) pairs of resident clouds: pairs[2k] = target, pairs[2k+1] = source of pair k.
  * Every cloud NAMED by a pair is indexed once and gets its k-NN covariances once, whatever the number of pairs that
  * name it and in whichever role -- the covariances of ALL named clouds from one launch (k_knn_covariances_multi; a further

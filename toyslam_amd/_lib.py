@@ -21,6 +21,7 @@ SELECT_FINITE, SELECT_BOX, SELECT_BOX_NEGATE, SELECT_RANGE, SELECT_RANGE_NEGATE,
 OUTLIER_RADIUS, OUTLIER_STATISTICAL = 1, 2
 COV_LAPLACE, COV_SANDWICH = 0, 1
 COV_INDEFINITE = 1
+GICP_VOXEL_COV_PLANE, GICP_VOXEL_COV_RAW = 0, 1
 
 
 class PoseInformation(C.Structure):
@@ -272,6 +273,9 @@ SIGNATURES = {
     "gicp_set_target_covariances": (C.c_int, [vp, dp, C.c_size_t]),
     "gicp_set_input_target_cloud": (C.c_int, [vp, vp]),
     "gicp_set_input_source_cloud": (C.c_int, [vp, vp]),
+    "gicp_set_input_target_grid": (C.c_int, [vp, vp, C.c_int]),
+    "gicp_target_grid_voxels": (C.c_int, [vp, fp, dp, C.POINTER(C.c_int64), C.c_size_t, szp]),
+    "gicp_diag_target_grid": (C.c_int, [vp, szp, szp, fp, szp]),
     "gicp_align_pairs_clouds": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, ip, C.c_size_t, fp, C.c_double, fp, ip, ip, ip, dp]),
     "gicp_align_pairs_lockstep": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, ip, C.c_size_t, fp, C.c_double, fp, ip, ip, ip, dp]),
     "gicp_align_guesses": (C.c_int, [vp, fp, C.c_size_t, C.c_double, fp, ip, ip, ip, dp]),

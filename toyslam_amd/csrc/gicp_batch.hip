@@ -389,6 +389,7 @@ ndt_status gicp_align_guesses(gicp_handle h, const float* guesses, size_t n_gues
   if (!h) return fail(NDT_ERR_INVALID, "null handle");
   if (n_guesses > 65535) return fail(NDT_ERR_INVALID, "at most 65535 guesses per call");
   if (n_guesses == 0) return gicp_lockstep_done(h, gicp::LockstepStats());  // (nothing to register: no inputs needed either)
+  if (h->in[0].vox) return fail(NDT_ERR_INVALID, "the batch forms take cloud targets: the handle's target is a grid target");
   ndt_status s = gicp_inputs_set(h);
   if (s) return s;
   if (!guesses) return fail(NDT_ERR_INVALID, "null guesses");

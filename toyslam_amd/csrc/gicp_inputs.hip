@@ -45,6 +45,11 @@ void cov6_from_cov9(const double* c9, size_t n, double* c6) {
 GicpInput& gicp_unset(gicp_context* h, int which) {
   GicpInput& in = h->in[which];
   in.set = in.have_cov = in.user_cov = false;
+  if (which == 0 && in.vox) {  // a voxel target (gicp_set_input_target_grid): the binding is dropped
+    in.vox = nullptr;
+    h->grid_target.map = nullptr;
+    h->grid_target.valid = false;
+  }
   h->step_ready = false;
   return in;
 }
@@ -216,7 +221,7 @@ ndt_status gicp_finite_check(gicp_context* h, const std::vector<const DeviceClou
 ndt_status gicp_read_covariances(gicp_context* h, const GicpInput& in, double* cov9) {
   const size_t n = in.n();
   std::vector<double> c6(n * 6);
-  HIP_TRY(hipMemcpyAsync(c6.data(), in.cov.p, n * 6 * sizeof(double), hipMemcpyDeviceToHost, h->tgt.stream));
+  HIP_TRY(hipMemcpyAsync(c6.data(), in.covariances(), n * 6 * sizeof(double), hipMemcpyDeviceToHost, h->tgt.stream));
   HIP_TRY(hipStreamSynchronize(h->tgt.stream));
   cov9_from_cov6(c6.data(), n, cov9);
   return NDT_OK;
@@ -270,6 +275,7 @@ static ndt_status gicp_set_covariances(gicp_handle h, int which, const double* c
   if (!h) return fail(NDT_ERR_INVALID, "null");
   GicpInput& in = h->in[which];
   if (!in.set) return fail(NDT_ERR_NO_INPUT, "set the cloud before its covariances");
+  if (in.vox) return fail(NDT_ERR_INVALID, "a grid target has its voxels' covariances: none can be set");
   if (!cov || n == 0) {  // an empty vector: computed again by the next align (:386,392)
     in.have_cov = in.user_cov = false;
     return NDT_OK;
@@ -293,6 +299,11 @@ ndt_status gicp_covariances(gicp_handle h, int which, double* cov, int* nn_idx, 
   if (!h || !cov || which < 0 || which > 1) return fail(NDT_ERR_INVALID, "bad arguments");
   GicpInput& in = h->in[which];
   if (!in.set) return fail(NDT_ERR_NO_INPUT, "cloud not set");
+  if (in.vox) {  // a voxel target: D's covariances as the next registration would use them
+    if (nn_idx || nn_d2) return fail(NDT_ERR_INVALID, "a grid target's covariances have no neighbour lists");
+    const ndt_status sg = gicp_grid_ready(h);
+    return sg ? sg : gicp_read_covariances(h, in, cov);
+  }
   ndt_status s = ensure_device(&h->tgt);
   if (s) return s;
   // inspection: the k-NN covariances for the CURRENT k (caller-supplied ones are returned as they are; neighbours cannot

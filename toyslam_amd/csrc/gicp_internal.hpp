@@ -1,5 +1,5 @@
 // gicp_internal.hpp -- private to the units of the GICP row (include/gicp_mi355.h): gicp_capi.hip, gicp_inputs.hip,
-// gicp_register.hip, gicp_batch.hip (what each holds: ndt_internal.hpp's list).  They reuse the NDT units' device pool, cloud upload and
+// gicp_register.hip, gicp_batch.hip, gicp_grid.hip (what each holds: ndt_internal.hpp's list).  They reuse the NDT units' device pool, cloud upload and
 // K1 grid build -- the voxel index K1 produces over a cloud is the search structure of GICP's nearest-neighbour queries.
 //
 // One input of a registration is a GicpInput: a cloud's search index (which holds the cloud), its packed covariances and
@@ -17,8 +17,30 @@ struct LeafHint {  // consecutive clouds have about the same density: the index 
   size_t n = 0;
 };
 
+// A VOXEL target (gicp_set_input_target_grid, gicp_grid.hip): the NDT handle whose current target grid is the target -- borrowed,
+// the caller keeps it alive -- and what is materialised from that grid's table and records in one mark / scan (or sort) /
+// gather pass: the set D of its valid voxels in ascending linear voxel index.  Refreshed when the grid's generation has moved,
+// when the handle holds another grid, or when gicp_epsilon (PLANE covariances) has changed.
+struct GridTarget {
+  ndt_context* map = nullptr;
+  int cov_mode = 0;
+  std::weak_ptr<DeviceGrid> seen;  // the grid the arrays were made from (expired: that grid is gone, whatever lies at its address)
+  unsigned long long seen_generation = 0;
+  double seen_epsilon = 0;
+  bool valid = false;
+  DevBuf<float4> pts;      // [n] the voxels' f32 centroids (x, y, z, 1)
+  DevBuf<double> cov;      // [n][6]
+  DevBuf<long long> idx;   // [n] linear voxel indices, ascending
+  DevBuf<int> ord;         // per record of the grid: its ordinal in D (read only through table entries that are records)
+  size_t n = 0;
+  size_t refreshes = 0, correspond_blocks = 0;  // gicp_diag_target_grid
+  hipEvent_t ev = nullptr;                      // the map's stream -> the main stream
+  ~GridTarget() { if (ev) (void)hipEventDestroy(ev); }
+};
+
 struct GicpInput {
   std::shared_ptr<DeviceGrid> grid;  // the search index; grid->target is the cloud
+  const GridTarget* vox = nullptr;   // the handle's target only: a voxel target instead (no index, no cloud; covariances in vox)
   DevBuf<double> cov;                // [n][6]
   bool have_cov = false;
   bool user_cov = false;  // supplied through gicp_set_*_covariances
@@ -26,7 +48,10 @@ struct GicpInput {
   bool set = false;
   LeafHint hint;
   const DeviceCloud& cloud() const { return *grid->target; }
-  size_t n() const { return grid->target->n; }
+  size_t n() const { return vox ? vox->n : grid->target->n; }
+  // what the objective kernels read of a target: its points and packed covariances
+  const float4* points() const { return vox ? vox->pts.p : grid->target->pts.p; }
+  const double* covariances() const { return vox ? vox->cov.p : cov.p; }
 };
 
 struct gicp_context;
@@ -112,6 +137,7 @@ struct gicp_context {
   ndt_context tgt, src;
   gicp::Params prm;
   GicpInput in[2];                  // target, source
+  GridTarget grid_target;           // in[0].vox points here while the target is a voxel target
   DevBuf<float4> output;            // the source moved by the guess
   DevBuf<int> corr;
   DevBuf<float> maha;
@@ -189,6 +215,15 @@ ndt_status gicp_index_cloud(ndt_context* c, const std::shared_ptr<DeviceCloud>& 
 ndt_status gicp_finite_check(gicp_context* h, const std::vector<const DeviceCloud*>& clouds, std::vector<unsigned>& bad);
 ndt_status gicp_read_covariances(gicp_context* h, const GicpInput& in, double* cov9);
 ndt_status gicp_prepare_covariances(gicp_context* h, GicpInput& tgt, GicpInput& src);
+// ---- gicp_grid.hip
+// What every call that needs a voxel target starts with (after gicp_inputs_set; a cloud target: nothing to do): the map has a
+// target, the main stream is ordered behind the map's by an event, D is materialised if stale (then step_ready is dropped) and
+// not empty.  NDT_ERR_NO_INPUT otherwise.
+ndt_status gicp_grid_ready(gicp_context* h);
+// the correspondence step against the voxel target (k_correspond_voxel), the arguments of gicp::launch_correspond otherwise
+hipError_t gicp_grid_correspond(gicp_context* h, int n, const float* T12, const gicp::Rot3d& R, const double* cov_src6, double dist_threshold);
+// getFitnessScore against D: k_fitness's shape with the voxel search -- the bits of the fitness against a cloud of D's centroids
+ndt_status gicp_grid_fitness(gicp_context* h, const float4* d_src, int n, const float* T_colmajor, double max_range, double* fitness);
 // ---- gicp_register.hip
 ndt_status gicp_scratch(gicp_context* h);
 // Waits for the n tagged rows of sequence number `seq` that a kernel queued on `st` publishes (each arrives as 64 self-validating

@@ -19,6 +19,7 @@
 // shell -- exact, and with (distance, index) ordering deterministic.
 #include "gicp_kernels.hpp"
 
+#include "gicp_device.hpp"
 #include "ndt_device.hpp"
 #include "ndt_search.hpp"
 
@@ -29,14 +30,6 @@ using namespace ndt;
 namespace {
 
 constexpr int kKnnBlock = 64;   // one wave = 8 query teams per block
-
-// [Eigen] Matrix4f * Vector4f (column by column): row r = ((T_r0 x + T_r1 y) + T_r2 z) + T_r3 * 1
-__device__ __forceinline__ void matvec_eigen(const float* T12, float x, float y, float z, float& ox, float& oy, float& oz) {
-#pragma clang fp contract(off)
-  ox = ((T12[0] * x + T12[1] * y) + T12[2] * z) + T12[3] * 1.0f;
-  oy = ((T12[4] * x + T12[5] * y) + T12[6] * z) + T12[7] * 1.0f;
-  oz = ((T12[8] * x + T12[9] * y) + T12[10] * z) + T12[11] * 1.0f;
-}
 
 // The work of ONE block of a kNN / covariance grid, shared by k_knn_covariances (one cloud per launch) and
 // k_knn_covariances_multi (many clouds per launch): block `block` of the `n_blocks` that cut cloud `ix`, eight queries per
@@ -345,12 +338,6 @@ __global__ __launch_bounds__(kFiniteBlock) void k_count_nonfinite_multi(const Fi
   if ((threadIdx.x & (kWave - 1)) == 0) atomicAdd(&counts[lo], bad);
 }
 
-__device__ __forceinline__ void load_sym(const double* __restrict__ c6, double C[3][3]) {
-  C[0][0] = c6[0]; C[0][1] = c6[1]; C[0][2] = c6[2];
-  C[1][0] = c6[1]; C[1][1] = c6[3]; C[1][2] = c6[4];
-  C[2][0] = c6[2]; C[2][1] = c6[4]; C[2][2] = c6[5];
-}
-
 // The work of ONE block of a correspondence grid, shared by k_correspond (one registration per launch) and
 // k_correspond_multi (the members of a lock-step, gicp_align_pairs_lockstep): block `block` of the `n_blocks` that cut the
 // n queries, 32 queries per pass, strided by n_blocks.  Both kernels hand it the member's arrays and the block's place
@@ -420,17 +407,7 @@ __device__ __forceinline__ void correspond_block(const float4* __restrict__ outp
     if (sub != 0) continue;
     int c_out = -1;
     if (tb_i != 0x7fffffff && static_cast<double>(tb) < dist_threshold) {  // :436
-      double C1[3][3], C2[3][3], M[3][3], tmp[3][3], inv[3][3];
-      load_sym(cov_src6 + static_cast<size_t>(i) * 6, C1);
-      load_sym(cov_tgt6 + static_cast<size_t>(tb_i) * 6, C2);
-      for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++) M[r][c] = (R.m[r * 3] * C1[0][c] + R.m[r * 3 + 1] * C1[1][c]) + R.m[r * 3 + 2] * C1[2][c];
-      for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++)
-          tmp[r][c] = ((M[r][0] * R.m[c * 3] + M[r][1] * R.m[c * 3 + 1]) + M[r][2] * R.m[c * 3 + 2]) + C2[r][c];
-      inv3_cofactor(tmp, inv);
-      for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++) maha9[static_cast<size_t>(i) * 9 + r * 3 + c] = static_cast<float>(inv[r][c]);
+      mahalanobis_store(cov_src6 + static_cast<size_t>(i) * 6, cov_tgt6 + static_cast<size_t>(tb_i) * 6, R, maha9 + static_cast<size_t>(i) * 9);
       c_out = tb_i;
     }
     corr[i] = c_out;

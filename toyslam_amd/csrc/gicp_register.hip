@@ -35,7 +35,7 @@ bool ObjectiveServer::start(gicp_context* h, const GicpInput& tgt, const GicpInp
   hipError_t e = hipMemsetAsync(counter.p, 0, 32 * gicp::kGicpServerParts * sizeof(unsigned), h->tgt.stream);
   if (e == hipSuccess) e = h->partials.reserve(static_cast<size_t>(std::max(blocks, gicp::kFunctorMaxBlocks)) * ndt::kEvalStride);
   if (e == hipSuccess)
-    e = gicp::launch_server(h->output.p, n, tgt.cloud().pts.p, h->corr.p, h->maha.p, mailbox(), blocks, h->partials.p,
+    e = gicp::launch_server(h->output.p, n, tgt.points(), h->corr.p, h->maha.p, mailbox(), blocks, h->partials.p,
                             counter.p, rows.rows(), h->seq + 1, 2000000ull /* 20 ms */, h->tgt.stream);
   if (e != hipSuccess) {
     server_mark(&h->tgt, false);
@@ -112,8 +112,9 @@ struct GicpDevice : gicp::Backend {
     h->srv.stop(h);  // the correspondences change: the next BFGS run gets a fresh server behind this kernel
     const double thr = h->prm.corr_dist_threshold * h->prm.corr_dist_threshold;  // :401
     const int n = static_cast<int>(src.n());
-    const hipError_t e = gicp::launch_correspond(h->output.p, n, transformation, rot, gicp_index_of(tgt), src.cov.p, tgt.cov.p, thr,
-                                                 gicp::correspond_blocks(n, kGicpMaxBlocks), h->corr.p, h->maha.p, h->tgt.stream);
+    const hipError_t e = tgt.vox ? gicp_grid_correspond(h, n, transformation, rot, src.cov.p, thr)  // a voxel target: through the map's table
+                                 : gicp::launch_correspond(h->output.p, n, transformation, rot, gicp_index_of(tgt), src.cov.p, tgt.cov.p, thr,
+                                                           gicp::correspond_blocks(n, kGicpMaxBlocks), h->corr.p, h->maha.p, h->tgt.stream);
     if (e != hipSuccess) {
       error = std::string("correspondence kernel: ") + hipGetErrorString(e);
       return false;
@@ -137,7 +138,7 @@ struct GicpDevice : gicp::Backend {
     if (!have_row) {
       const unsigned long long seq = ++h->seq;
       const double* pub = h->host_pub.rows();
-      const hipError_t e = gicp::launch_functor(launch_mode, h->output.p, n, tgt.cloud().pts.p, h->corr.p, h->maha.p, T,
+      const hipError_t e = gicp::launch_functor(launch_mode, h->output.p, n, tgt.points(), h->corr.p, h->maha.p, T,
                                                 gicp::functor_blocks(n, kGicpMaxBlocks), h->partials.p, h->counter.p, h->host_pub.rows(), seq, h->tgt.stream);
       if (e != hipSuccess) {
         error = std::string("functor kernel: ") + hipGetErrorString(e);
@@ -217,6 +218,7 @@ extern "C" {
 ndt_status gicp_align(gicp_handle h, const float* guess, float* final_T, int* converged, int* n_iterations, void* out_cloud) {
   if (!h) return fail(NDT_ERR_INVALID, "null");
   ndt_status s = gicp_inputs_set(h);
+  if (!s) s = gicp_grid_ready(h);
   if (s) return s;
   const GicpInput& src = h->in[1];
   const gicp::Result r = gicp_register(h, h->in[0], h->in[1], guess, &s);
@@ -242,8 +244,10 @@ ndt_status gicp_get_fitness_score(gicp_handle h, double max_range, double* fitne
   if (!h || !fitness) return fail(NDT_ERR_INVALID, "bad arguments");
   ndt_status s = gicp_inputs_set(h);
   if (!s) s = gicp_scratch(h);
+  if (!s) s = gicp_grid_ready(h);
   if (s) return s;
   const GicpInput& src = h->in[1];
+  if (h->in[0].vox) return gicp_grid_fitness(h, src.cloud().pts.p, static_cast<int>(src.n()), h->final_T, max_range, fitness);
   return fitness_against(&h->tgt, h->in[0].grid.get(), src.cloud().pts.p, static_cast<int>(src.n()), h->final_T, max_range, fitness);
 }
 
@@ -251,6 +255,7 @@ ndt_status gicp_step_correspond(gicp_handle h, const float* guess, const float* 
                                 int* n_correspondences) {
   if (!h) return fail(NDT_ERR_INVALID, "null");
   ndt_status s = gicp_inputs_set(h);
+  if (!s) s = gicp_grid_ready(h);
   if (s) return s;
   GicpInput& tgt = h->in[0];
   GicpInput& src = h->in[1];
@@ -286,7 +291,9 @@ ndt_status gicp_step_functor(gicp_handle h, int mode, const double* x, double* f
   if (!h->step_ready) return fail(NDT_ERR_NO_INPUT, "gicp_step_correspond has not run");
   ndt_status s = gicp_inputs_set(h);
   if (!s) s = gicp_scratch(h);
+  if (!s) s = gicp_grid_ready(h);  // (a voxel target that has changed since the step: its ordinals are gone)
   if (s) return s;
+  if (!h->step_ready) return fail(NDT_ERR_NO_INPUT, "the grid target has changed: gicp_step_correspond has to run again");
   GicpDevice dev(h, h->in[0], h->in[1]);
   float T[16];
   gicp::apply_state(x, T);

@@ -297,7 +297,7 @@ void acc_make_empty(AccTarget* a) {
   g->empty = true;
   g->n_leaves = g->n_cand = g->n_valid = 0;
   g->counts_known = true;
-  g->excursion_known = false;
+  g->touched();
 }
 
 // ndt_target_accumulate_crop once the bounds are cells: mark + scan, ONE read-back, then (if anything goes) the kept slots
@@ -357,7 +357,7 @@ ndt_status acc_crop(ndt_context* h, AccTarget* a, const ndt::AccCropBox& box) {
   slots.install(a);
   acc_install_table(a, lut, geo, sparse, mn, mx);
   a->n_slots = kept;
-  g->excursion_known = false;  // (the centroid fitness: voxels left, the box changed)
+  g->touched();  // (the centroid fitness and readers' caches: voxels left, the box changed)
   HIP_TRY(ndt::launch_acc_rehash(a->view(), kept, st));
   HIP_TRY(ndt::launch_acc_relink(a->view(), kept, geo, g->lut.p, st));
   h->crop_launches += 3;
@@ -427,7 +427,7 @@ ndt_status acc_commit(ndt_context* h, AccTarget* a, const std::shared_ptr<AccTar
   // ---- from here on the target changes
   if (started) acc_adopt(h, started);
   DeviceGrid* g = a->grid.get();
-  g->excursion_known = false;  // (the centroid fitness: centroids move, voxels arrive, the box may grow)
+  g->touched();  // (the centroid fitness and readers' caches: centroids move, voxels arrive, the box may grow)
   a->n_points = p.n_points;
   a->n_updates++;
   h->target->n = a->n_points;

@@ -360,6 +360,7 @@ static ndt_status compact_records_now(ndt_context* h, DeviceGrid* g) {
   HIP_TRY(ndt::launch_compact_records(g->lut.p, g->geom.lut_cells, g->recs.p, g->centroids.p, recs_new.p, cent_new.p, tile_sums.p, h->stream));
   g->recs.swap(recs_new);  // (the old arrays go back to the pool at scope exit: reused only behind these launches, stream order)
   g->centroids.swap(cent_new);
+  g->generation++;  // (the records are renumbered: whoever cached record numbers reads the table again)
   return NDT_OK;
 }
 ndt_status maybe_compact_records(ndt_context* h, bool eager) {

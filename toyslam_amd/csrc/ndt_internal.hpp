@@ -17,8 +17,9 @@
 //                    (ndt_comm_*), ndt_set_allreduce
 //   ndt_accumulate.hip : the accumulating target (ndt_target_accumulate*): kernels and C-ABI
 //   ndt_io.hip     : PCD files, numbered scan sequences, PointCloud2-style repacking (host)
-//   gicp_capi.hip, gicp_inputs.hip, gicp_register.hip, gicp_batch.hip (gicp_internal.hpp, private to them) : the GICP row --
-//                    handle, parameters, results / inputs and covariances / one registration / many in one call
+//   gicp_capi.hip, gicp_inputs.hip, gicp_register.hip, gicp_batch.hip, gicp_grid.hip (gicp_internal.hpp, private to them) : the GICP
+//                    row -- handle, parameters, results / inputs and covariances / one registration / many in one call / a voxel
+//                    target (an NDT handle's grid: its refresh pass, the correspondence kernel, the fitness)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -308,6 +309,13 @@ struct DeviceGrid {
   bool excursion_known = false;
   float excursion = 0.f;
   size_t n_centroids = 0;  // voxels of the centroid cloud, counted by the same pass
+  // what a reader that caches arrays derived from the table and the records (GICP's voxel target, gicp_grid.hip) compares:
+  // moved wherever the voxels change (touched() -- every place the excursion goes stale) or the records are renumbered
+  unsigned long long generation = 0;
+  void touched() {
+    excursion_known = false;
+    generation++;
+  }
   ndt::GridView view() const {
     ndt::GridView v;
     v.lut = lut.p;
@@ -682,6 +690,11 @@ ndt_status fitness_many(ndt_context* h, const std::vector<FitnessJob>& jobs, dou
 // blocks of getFitnessScore over n source points (k_fitness's grid, a member's blocks of k_fitness_multi): 32 query teams per
 // block, at most 2048 blocks (the teams then stride over the queries)
 inline int fitness_blocks(int n) { return std::max(1, std::min(2048, (n + 31) / 32)); }
+// ---- ndt_centroid_fitness.hip
+long long table_entries(const DeviceGrid* g);    // entries one pass over g's look-up table reads (dense cells, or hash slots)
+int centroid_shell_limit(const DeviceGrid* g);   // shells a centroid search walks before the one pass over the table
+// g's centroid excursion, computed on h's stream when unknown or stale (one launch, one read-back, waited for)
+ndt_status ensure_excursion(ndt_context* h, DeviceGrid* g);
 // ---- ndt_score.hip
 // poses per launch of ndt_score_poses and ndt_nvtl_poses: one rule, one switch (NDT_SCORE_POSES_CHUNK)
 size_t poses_chunk(size_t n_poses, size_t row_bytes);

@@ -51,6 +51,7 @@ class GeneralizedIterativeClosestPoint:
 
     def setInputTarget(self, cloud):
         c = _cloud(cloud)
+        self._map = None
         check(self._L.gicp_set_input_target(self._h, c.ctypes.data, c.shape[0], c.strides[0]))
         self._n[0] = c.shape[0]
 
@@ -63,6 +64,7 @@ class GeneralizedIterativeClosestPoint:
         """setInputTarget from a cloud resident in HBM (ndt.DeviceCloud: uploadCloud, voxelGridFilterCloud*, ...): by
         reference, no download (gicp_set_input_target_cloud)."""
         self._n[0] = 0
+        self._map = None
         check(self._L.gicp_set_input_target_cloud(self._h, dc._c))
         self._n[0] = len(dc)
 
@@ -70,6 +72,42 @@ class GeneralizedIterativeClosestPoint:
         self._n[1] = 0
         check(self._L.gicp_set_input_source_cloud(self._h, dc._c))
         self._n[1] = len(dc)
+
+    VOXEL_COV_MODES = {"plane": _lib.GICP_VOXEL_COV_PLANE, "raw": _lib.GICP_VOXEL_COV_RAW}
+
+    def setInputTargetGrid(self, ndt, cov_mode="plane"):
+        """setInputTarget from a voxel grid (gicp_set_input_target_grid): the target becomes the CURRENT target grid of the
+        NormalDistributionsTransform `ndt` -- built from a cloud, or accumulated (targetAccumulate*) -- and every later call reads
+        it as it is then; nothing is built over the map.  cov_mode: "plane" (I - (1 - epsilon) n n^T per voxel, recommended) or
+        "raw" (the voxel's covariance).  The handle borrows `ndt` (a reference is kept here); None drops the binding."""
+        self._n[0] = 0
+        if ndt is None:
+            check(self._L.gicp_set_input_target_grid(self._h, None, 0))
+            self._map = None
+            return
+        mode = self.VOXEL_COV_MODES[cov_mode] if isinstance(cov_mode, str) else int(cov_mode)
+        check(self._L.gicp_set_input_target_grid(self._h, ndt._h, mode))
+        self._map = ndt
+
+    def targetGridVoxels(self):
+        """The voxel set D the next registration against the grid target would use (gicp_target_grid_voxels): ((n, 4) float32 of
+        x, y, z, 1, (n, 3, 3) float64 covariances, (n,) int64 linear voxel indices), ascending index."""
+        n = C.c_size_t(0)
+        check(self._L.gicp_target_grid_voxels(self._h, None, None, None, 0, C.byref(n)))
+        V = n.value
+        xyz1 = np.zeros((max(V, 1), 4), dtype=np.float32)
+        cov = np.zeros((max(V, 1), 3, 3))
+        idx = np.zeros(max(V, 1), dtype=np.int64)
+        check(self._L.gicp_target_grid_voxels(self._h, _f(xyz1), _d(cov), idx.ctypes.data_as(C.POINTER(C.c_int64)), V, C.byref(n)))
+        return xyz1[:V].copy(), cov[:V].copy(), idx[:V].copy()
+
+    def diagTargetGrid(self):
+        """The grid target's bookkeeping (gicp_diag_target_grid): dict of refreshes (mark / scan / gather passes so far), voxels,
+        excursion, correspond_blocks."""
+        a = [C.c_size_t(0) for _ in range(3)]
+        e = C.c_float(0.0)
+        check(self._L.gicp_diag_target_grid(self._h, C.byref(a[0]), C.byref(a[1]), C.byref(e), C.byref(a[2])))
+        return dict(refreshes=a[0].value, voxels=a[1].value, excursion=e.value, correspond_blocks=a[2].value)
 
     def alignPairsClouds(self, clouds, pairs=None, guesses=None, max_range=None):
         """GICP of (target, source) pairs of resident clouds (gicp_align_pairs_clouds): every named cloud indexed once, the
@@ -193,6 +231,10 @@ class GeneralizedIterativeClosestPoint:
     # --- inspection (parity tests) ---
     def covariances(self, which, neighbors=False):
         n = self._n[which]
+        if which == 0 and getattr(self, "_map", None) is not None:  # a grid target: one covariance per voxel of D
+            v = C.c_size_t(0)
+            check(self._L.gicp_target_grid_voxels(self._h, None, None, None, 0, C.byref(v)))
+            n = v.value
         cov = np.zeros((n, 3, 3))
         if neighbors:
             idx = np.zeros((n, self._k), dtype=np.int32)
