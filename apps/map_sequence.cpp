@@ -22,7 +22,7 @@
 // after the other, 2.7 ms overlapped, 3.7 ms overlapped on CU partitions -- the steps are short host-paced sequences of
 // pageable copies and small launches, and two threads driving them get in each other's way; hence not the default.
 //
-//   map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--range <min> <max>] [--outliers-radius <r> <min_neighbors>] [--outliers-stat <mean_k> <stddev_mul>] [--reject-unexplained <L>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> [voxel_leaf_size (0.5 | 0.3)] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]
+//   map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--deskew <field>] [--range <min> <max>] [--outliers-radius <r> <min_neighbors>] [--outliers-stat <mean_k> <stddev_mul>] [--reject-unexplained <L>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> [voxel_leaf_size (0.5 | 0.3)] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]
 // ("host": the serial loop with every cloud passing through host buffers, as in rounds 1-3; the default keeps them in HBM)
 //
 // --scan-to-map (anywhere on the line; the node's loop with clouds resident in HBM): every scan after the first is registered
@@ -53,6 +53,12 @@
 // --covariance (with --scan-to-map): after each registration "pose sigma: sx sy sz sroll spitch syaw" is printed -- the square
 // roots of the diagonal of the sandwich covariance of the registered pose (ndt_pose_covariance) against the target the scan
 // was registered to, before the scan is accumulated; "nan" six times when the pose is not determined (NDT_COV_INDEFINITE).
+// --deskew <field> (with --scan-to-map): every raw scan is motion-compensated first of all (ndt_cloud_deskew), before --range,
+// --outliers-* and the prefilter.  The points' times are the named scalar field of the scan's file, the *_<number>.pcd of the directory
+// (ndt_pcd_read_field); t_begin / t_end are the smallest and the largest finite time of the file and t_ref = t_begin.  The motion
+// over the sweep is the increment between the two previous registered poses (constant velocity; the first scan's pose is the
+// identity), so the first two scans -- and a file whose times are all one value -- go through as they are.  "deskewed:
+// <n - untimed>/<n>" is printed per compensated scan; the points without a finite time become NaN and are dropped downstream.
 // --range <min> <max> (with --scan-to-map): every raw scan goes through ndt_cloud_select (RANGE | FINITE about the sensor, centre
 // 0) before its prefilter -- the ego vehicle's own returns and everything beyond the useful range are dropped on the device --
 // and "range kept: <k>/<n>" is printed per scan.
@@ -72,6 +78,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <dirent.h>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -99,6 +106,22 @@ static void print_matrix(const char* title, const float* T) {
 
 using clock_type = std::chrono::steady_clock;
 static double since(clock_type::time_point a) { return std::chrono::duration<double, std::milli>(clock_type::now() - a).count(); }
+
+// --deskew: the file of scan `number` in the directory -- the sequence hands out numbers, not names: the *.pcd whose stem ends
+// in _<number> as the sequence itself reads it (ndt_host_extract_file_number); empty: none
+static std::string scan_file(const std::string& directory, int number) {
+  std::string found;
+  if (DIR* d = opendir(directory.c_str())) {
+    while (const dirent* e = readdir(d)) {
+      const std::string name = e->d_name;
+      if (name.size() < 5 || name.compare(name.size() - 4, 4, ".pcd") != 0) continue;
+      if (ndt_host_extract_file_number(name.substr(0, name.size() - 4).c_str()) != number) continue;
+      if (found.empty() || name < found) found = name;  // (two files of one number: the first by name)
+    }
+    closedir(d);
+  }
+  return found.empty() ? found : directory + "/" + found;
+}
 
 static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
 
@@ -158,6 +181,8 @@ struct Node {
   float range_min = 0, range_max = 0;
   bool outliers_radius = false, outliers_stat = false;  // --outliers-radius / --outliers-stat: every raw scan loses its outliers before its prefilter
   ndt_outlier_spec radius_spec{}, stat_spec{};
+  std::string deskew_field;  // --deskew: every raw scan is motion-compensated by this field of its file, first of all
+  std::string directory;
   bool reject = false;       // --reject-unexplained: a registered scan is accumulated without the points the target does not explain
   double reject_below = 0;
   gicp_handle gicp = nullptr;  // --gicp: the registrations are GICP's against the accumulated target (bound to the NDT handle's grid)
@@ -294,6 +319,48 @@ static int run_resident(Node& node, ndt_pcd_sequence_handle seq, float voxel_lea
         return 0;
       }
       const auto t0 = clock_type::now();
+      if (!node.deskew_field.empty()) {
+        // the poses registered so far, the first scan's (the identity, unless a loaded map came first) included
+        const size_t n_poses = node.trajectory.size() + (node.have_map ? 0 : (node.loaded > 0 ? 1 : 0));
+        std::vector<double> times(r.n ? r.n : 1);
+        size_t n_times = 0;
+        const std::string path = scan_file(node.directory, r.number);
+        if (path.empty()) {
+          std::fprintf(stderr, "--deskew: no *_%d.pcd in %s\n", r.number, node.directory.c_str());
+          return 1;
+        }
+        CHECK(ndt_pcd_read_field(path.c_str(), node.deskew_field.c_str(), times.data(), r.n, &n_times));
+        if (n_times != r.n)  // (the file changed between the sequence's read and this one)
+          std::fprintf(stderr, "--deskew: %s holds %zu times for %zu points: scan %d is not compensated\n", path.c_str(), n_times, r.n, r.number);
+        double lo = INFINITY, hi = -INFINITY;
+        for (size_t i = 0; i < r.n; i++)
+          if (std::isfinite(times[i])) {
+            lo = std::min(lo, times[i]);
+            hi = std::max(hi, times[i]);
+          }
+        // (MAP_SEQUENCE_OVERLAP=1 begins this prefilter before the previous scan is registered: the increment is then one scan
+        // older, still the constant-velocity guess)
+        if (n_poses >= 2 && n_times == r.n && hi > lo) {
+          const float* B = node.trajectory.back().data();
+          const float* A = node.trajectory.size() >= 2 ? node.trajectory[node.trajectory.size() - 2].data() : kIdentity;
+          float inc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1};  // A^-1 B, column-major, in f64
+          for (int c = 0; c < 4; c++)
+            for (int rr = 0; rr < 3; rr++) {
+              double v = 0;
+              for (int k = 0; k < 3; k++) v += static_cast<double>(A[4 * rr + k]) * (static_cast<double>(B[4 * c + k]) - (c == 3 ? static_cast<double>(A[12 + k]) : 0.0));
+              inc[4 * c + rr] = static_cast<float>(v);
+            }
+          ndt_deskew_motion motion;
+          CHECK(ndt_host_deskew_motion(inc, lo, hi, lo, &motion));
+          ndt_cloud moved = nullptr;
+          size_t untimed = 0;
+          CHECK(ndt_cloud_deskew(h, r.view, &motion, times.data(), 0, &moved, &untimed));
+          std::printf("deskewed: %zu/%zu\n", r.n - untimed, r.n);
+          ndt_cloud_release(r.view);
+          r.view = moved;
+          if (untimed) r.dense = 0;
+        }
+      }
       if (node.range) {  // the crop leaves finite points only
         ndt_select_spec spec{};
         spec.flags = NDT_SELECT_RANGE | NDT_SELECT_FINITE;
@@ -677,9 +744,10 @@ int main(int argc, char** argv) {
   ndt_outlier_spec radius_spec{}, stat_spec{};
   float window = 0, range_min = 0, range_max = 0;
   double reject_below = 0;
-  const char *save_target = nullptr, *load_target = nullptr;
+  const char *save_target = nullptr, *load_target = nullptr, *deskew_field = nullptr;
+  bool bad_deskew = false;
   static const char kUsage[] =
-      "usage: map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--gicp [--gicp-gate <m>]] [--range <min> <max>] [--outliers-radius <r> <min_neighbors>] [--outliers-stat <mean_k> <stddev_mul>] [--reject-unexplained <L>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> "
+      "usage: map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--gicp [--gicp-gate <m>]] [--deskew <field>] [--range <min> <max>] [--outliers-radius <r> <min_neighbors>] [--outliers-stat <mean_k> <stddev_mul>] [--reject-unexplained <L>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> "
       "[voxel_leaf_size] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]\n";
   {  // the switches are taken out of the line before the positional arguments are read
     int kept = 1;
@@ -707,6 +775,9 @@ int main(int argc, char** argv) {
         have_gate = true;
         gicp_gate = i + 1 < argc ? std::atof(argv[++i]) : 0.0;
         bad_gate = !(gicp_gate > 0);
+      } else if (std::strcmp(argv[i], "--deskew") == 0) {
+        deskew_field = i + 1 < argc ? argv[++i] : nullptr;
+        bad_deskew = !deskew_field || !*deskew_field;
       } else if (std::strcmp(argv[i], "--range") == 0) {
         range = true;
         bad_range = i + 2 >= argc;
@@ -761,6 +832,10 @@ int main(int argc, char** argv) {
                          "nothing, so it does not go with --reject-unexplained\n%s", kUsage);
     return 2;
   }
+  if (bad_deskew || (deskew_field && !scan_to_map)) {
+    std::fprintf(stderr, "--deskew <field> names the time field of the scans' files and goes with --scan-to-map\n%s", kUsage);
+    return 2;
+  }
   if (bad_outliers || ((outliers_radius || outliers_stat) && !scan_to_map)) {
     std::fprintf(stderr, "--outliers-radius <r> <min_neighbors> (r > 0, min_neighbors >= 0) and --outliers-stat <mean_k> <stddev_mul> (mean_k 1 ... 256) "
                          "go with --scan-to-map\n%s", kUsage);
@@ -793,6 +868,8 @@ int main(int argc, char** argv) {
   node.outliers_stat = outliers_stat;
   node.radius_spec = radius_spec;
   node.stat_spec = stat_spec;
+  if (deskew_field) node.deskew_field = deskew_field;
+  node.directory = argv[1];
   node.reject = reject;
   node.reject_below = reject_below;
   if (scan_to_map && (node.rosbag || !serial || host_clouds)) {

@@ -266,7 +266,8 @@ typedef enum {
   NDT_BOX_ROUTE_FILTER_ROWS = 6,  /* output of a voxel filter: rows of at most 64 blocks, the count read on the device    */
   NDT_BOX_ROUTE_MULTI_WORDS = 7,  /* member of a batched call (k_repack_bbox_multi): order-encoded words, atomic max      */
   NDT_BOX_ROUTE_STAGED = 8,       /* scan of a staged PCD sequence: boxes by the reading thread                           */
-  NDT_BOX_ROUTE_SELECT = 9        /* output of a selection (k_select_place): per-block rows of the kept points            */
+  NDT_BOX_ROUTE_SELECT = 9,       /* output of a selection (k_select_place): per-block rows of the kept points            */
+  NDT_BOX_ROUTE_DESKEW = 10       /* output of a motion compensation (k_deskew): per-block rows of the records written    */
 } ndt_box_route;
 /* the cloud's boxes exactly as stored: out = {min xyz, max xyz} of box [0], then of box [1]; an empty box is
  * (FLT_MAX, -FLT_MAX).  *route (may be NULL) = the ndt_box_route that wrote them.  No device work. */
@@ -388,6 +389,72 @@ ndt_status ndt_diag_select(ndt_handle h, size_t* launches, size_t* blocks, size_
  * rest); at most 1024 blocks, beyond which points_per_block grows. */
 ndt_status ndt_host_select_point(const ndt_select_spec* spec, const float xyz[3], double key, int* keep);
 ndt_status ndt_host_select_plan(size_t n_points, int* blocks, int* points_per_block);
+
+/* ---- deskew: motion compensation of a resident scan by the time of every point -------------------------------------------
+ * A sweep covers [t_begin, t_end].  Over it the sensor moves by the rotation vector w = angle * axis (radians) and the
+ * translation tau (metres, in the sensor frame at t_begin): its pose at time t, relative to its pose at t_begin, is
+ * (Exp(u w), u tau) with u = (t - t_begin) / (t_end - t_begin) -- the constant-velocity model of LOAM's TransformToStart,
+ * the rotation interpolated on the geodesic, the translation linearly.  The output is the scan as seen from the sensor frame
+ * at t_ref.  All rotations share one axis k, so a point p (the stored f32 record widened to f64) with time t_i becomes
+ *   s     = (t_i - t_ref) / (t_end - t_begin)                 one subtraction, one division (the denominator computed once)
+ *   theta = s * angle
+ *   q     = p*cos(theta) + (k x p)*sin(theta) + k*(k . p)*(1 - cos(theta)) + s*tau_ref
+ * with tau_ref = Exp(-u_ref w) tau computed once on the host.  Everything is evaluated in f64, every operation rounded on its
+ * own (no fused multiply-add), and each coordinate is rounded once to f32; the fourth word of the record is carried as it is.
+ * Times outside the sweep extrapolate: there is no clamp.  The definition is ONE function for host and device
+ * (toyslam_amd/csrc/ndt_deskew.hpp); the two differ only by their libraries' sin / cos.
+ *   - a record with a non-finite coordinate is copied unchanged, all four words bit for bit, whatever its time
+ *   - a finite record with a non-finite time gets x = y = z = NaN (the quiet NaN 0x7fc00000), keeps its fourth word and is
+ *     counted in *n_untimed; the !is_dense rules downstream then drop it
+ *   - s == 0 gives q == p as f32 values (by ==, not bit for bit: a negative zero may become positive)
+ * A motion is invalid if a field is not finite, t_end <= t_begin, angle lies outside [0, pi] or |axis| differs from 1 by more
+ * than 1e-12. */
+typedef struct {
+  double t_begin, t_end, t_ref; /* finite, t_end > t_begin */
+  double axis[3], angle;        /* unit axis ((1,0,0) when angle == 0), 0 <= angle <= pi */
+  double tau_ref[3];            /* translation per unit s, already in the t_ref frame */
+} ndt_deskew_motion;
+/* - ndt_cloud_deskew: *out is a new cloud of its own (ndt_cloud_release) holding the n_in records of `in`, in in's order, moved
+ *   as above, with both boxes exact over the records it wrote (route NDT_BOX_ROUTE_DESKEW) -- bit for bit what
+ *   ndt_cloud_upload of the downloaded records would carry -- and usable by every consumer of an ndt_cloud.  An empty input
+ *   gives an empty cloud, never NULL, with the initial boxes and route NONE.  times: n_in doubles, host memory or
+ *   (times_on_device != 0) device memory; may be NULL for an empty cloud.  *n_untimed (may be NULL): the finite records whose
+ *   time is not.  One kernel launch; the call returns after its own work is done (a borrowed view of a staged sequence may be
+ *   overwritten afterwards).
+ * - ndt_cloud_deskew_clouds: cloud k under motions[k]; times holds the clouds' times packed in cloud order (all on the host or
+ *   all on the device).  One kernel launch in all.  out[k] and n_untimed[k] (n_untimed may be NULL) are the same bits as the
+ *   single call for cloud k alone, whatever the other clouds and their order.  Every out[k] is a cloud of its own.
+ *   n_clouds == 0 is NDT_OK, touches nothing and needs no device.  On any error every out[k] is NULL.
+ * - ndt_diag_deskew, of the last of the two calls that reached the device: kernel launches (1 whatever the number of clouds;
+ *   0 when no cloud had a point), its blocks, the clouds.
+ * Neither changes the handle's target, source, grid, last result, statistics, map, a begun ndt_cloud_voxel_filter_begin, the
+ * pairs state or what ndt_diag_select / ndt_diag_outliers report.
+ * NDT_ERR_INVALID before any device work, outputs untouched apart from *out = NULL (every out[k] = NULL): a NULL handle, in,
+ * motion or out, NULL times with points, an invalid motion, a NULL entry of in, more than 65 535 clouds, a cloud of another
+ * device, more than INT_MAX points.  After those checks NDT_ERR_NO_DEVICE without a gfx950 device.
+ * Development switch NDT_DESKEW_MAX_BLOCKS (read once): caps the blocks a cloud gets (the results do not depend on it). */
+ndt_status ndt_cloud_deskew(ndt_handle h, ndt_cloud in, const ndt_deskew_motion* motion, const double* times /* n_in */,
+                            int times_on_device, ndt_cloud* out, size_t* n_untimed /* or NULL */);
+ndt_status ndt_cloud_deskew_clouds(ndt_handle h, const ndt_cloud* in, size_t n_clouds, const ndt_deskew_motion* motions /* n_clouds */,
+                                   const double* times /* packed in cloud order */, int times_on_device, ndt_cloud* out /* n_clouds */,
+                                   size_t* n_untimed /* n_clouds or NULL */);
+ndt_status ndt_diag_deskew(ndt_handle h, size_t* launches, size_t* blocks, size_t* clouds);
+/* Host only, no device.
+ * - ndt_host_deskew_motion: the motion of a sweep from T (16 floats, column-major: the sensor's pose at t_end in its frame at
+ *   t_begin, e.g. the last registration increment under a constant-velocity assumption).  The rotation's logarithm is taken in
+ *   f64: angle = atan2(|v|, (trace - 1) / 2) with v the vector of the antisymmetric part; the axis is v / |v| up to a quarter
+ *   turn and beyond it comes from the symmetric part ((R + R^T)/2 - cos I) / (1 - cos) = k k^T (largest diagonal entry first,
+ *   signs from v), because the antisymmetric part vanishes towards pi; angle == 0 gives the axis (1, 0, 0).
+ *   tau_ref = Exp(-u_ref w) tau, u_ref = (t_ref - t_begin) / (t_end - t_begin).  NDT_ERR_INVALID: NULL T or out, a value that
+ *   is not finite, t_end <= t_begin.
+ * - ndt_host_deskew_point: the definition itself (the function the kernel calls) for one point; *untimed (may be NULL) = 1
+ *   where the point is finite and its time is not.  NDT_ERR_INVALID for an invalid motion.
+ * - ndt_host_deskew_plan: the launch plan of a cloud of n_points -- blocks of 256 threads, each owning one contiguous range of
+ *   *points_per_block points (the last one the rest); at most 1024 blocks (NDT_DESKEW_MAX_BLOCKS: fewer), beyond which
+ *   points_per_block grows. */
+ndt_status ndt_host_deskew_motion(const float T[16], double t_begin, double t_end, double t_ref, ndt_deskew_motion* out);
+ndt_status ndt_host_deskew_point(const ndt_deskew_motion* motion, const float xyz[3], double t, float out[3], int* untimed);
+ndt_status ndt_host_deskew_plan(size_t n_points, int* blocks, int* points_per_block);
 
 /* ---- outlier removal of resident clouds: the neighbourhood filters ----------------------------------------------------
  * Modelled on pcl::RadiusOutlierRemoval and pcl::StatisticalOutlierRemoval.  Neither class is part of the reference and PCL
@@ -610,6 +677,11 @@ ndt_status ndt_pcd_read_header(const char* path, size_t* n_points, int* n_fields
 ndt_status ndt_pcd_read_xyz(const char* path, void* out, size_t capacity_points, size_t stride_bytes, size_t* n_points,
                             int* is_dense);
 ndt_status ndt_pcd_write_xyz(const char* path, const void* pts, size_t n, size_t stride_bytes, int binary);
+/* One named scalar field of a PCD file as doubles (the per-point time of a lidar driver's records, for ndt_cloud_deskew): TYPE F
+ * of 4 / 8 bytes, I and U of 1, 2, 4 and 8 bytes, all three DATA kinds.  *n (may be NULL) = the file's points, also when
+ * capacity is too small.  NDT_ERR_INVALID: a NULL path or name, NULL out with capacity, a file that cannot be parsed, a field
+ * that is absent or has COUNT != 1, a type / size pair outside the list, more points than capacity. */
+ndt_status ndt_pcd_read_field(const char* path, const char* name, double* out, size_t capacity_points, size_t* n_points);
 
 /* A directory of numbered scans, as the mapping node consumes it (lidar_subscriber/src/ndt_omp_mapping_node.cpp):
  * process_new_clouds (:110-136) lists the *.pcd files whose number -- the integer after the last '_' of the file
@@ -647,6 +719,11 @@ int ndt_host_extract_file_number(const char* file_stem);
  * entry point takes with stride 16.  Host only.  *is_dense = every coordinate finite. */
 ndt_status ndt_host_repack_fields(const void* data, size_t n, size_t point_step, size_t off_x, size_t off_y, size_t off_z,
                                   void* out_xyz1, int* is_dense);
+/* The companion for one scalar field of such records (the time of a point): n values at byte `offset` of records of
+ * point_step bytes -- any step and offset, aligned or not -- widened to doubles.  datatype: the sensor_msgs/PointField code,
+ * 1 INT8, 2 UINT8, 3 INT16, 4 UINT16, 5 INT32, 6 UINT32, 7 FLOAT32, 8 FLOAT64 (little-endian).  Host only.  NDT_ERR_INVALID: an
+ * unknown datatype, a field that does not fit into the record, NULL data / out with n > 0. */
+ndt_status ndt_host_extract_field(const void* data, size_t n, size_t point_step, size_t offset, int datatype, double* out);
 
 /* ---- batch (map-build mode: many sources against the one target) ----------
  * Registers n_scans sources in lock-step, one fused derivative launch per

@@ -13,7 +13,8 @@ CSRC = os.path.join(_HERE, "csrc")
 
 NDT_OK, NDT_ERR_INVALID, NDT_ERR_NO_DEVICE, NDT_ERR_HIP, NDT_ERR_GRID_OVERFLOW, NDT_ERR_NO_INPUT, NDT_ERR_COMM = range(7)
 KDTREE, DIRECT26, DIRECT7, DIRECT1 = 0, 1, 2, 3
-BOX_ROUTES = ("none", "host_scalar", "host_avx2", "repack", "rec16_copy", "rec16_polled", "filter_rows", "multi_words", "staged", "select")
+BOX_ROUTES = ("none", "host_scalar", "host_avx2", "repack", "rec16_copy", "rec16_polled", "filter_rows", "multi_words", "staged", "select",
+              "deskew")
 EVAL_STRIDE = 32
 COMM_ID_BYTES = 128
 
@@ -34,6 +35,12 @@ class SelectSpec(C.Structure):
     """ndt_select_spec (include/ndt_mi355.h)"""
     _fields_ = [("flags", C.c_uint), ("box_min", C.c_float * 3), ("box_max", C.c_float * 3), ("centre", C.c_float * 3),
                 ("r_min", C.c_float), ("r_max", C.c_float), ("key_lo", C.c_double), ("key_hi", C.c_double)]
+
+
+class DeskewMotion(C.Structure):
+    """ndt_deskew_motion (include/ndt_mi355.h)"""
+    _fields_ = [("t_begin", C.c_double), ("t_end", C.c_double), ("t_ref", C.c_double), ("axis", C.c_double * 3), ("angle", C.c_double),
+                ("tau_ref", C.c_double * 3)]
 
 
 class OutlierSpec(C.Structure):
@@ -190,6 +197,14 @@ SIGNATURES = {
     "ndt_diag_select": (C.c_int, [vp, szp, szp, szp]),
     "ndt_host_select_point": (C.c_int, [C.POINTER(SelectSpec), fp, C.c_double, ip]),
     "ndt_host_select_plan": (C.c_int, [C.c_size_t, ip, ip]),
+    "ndt_cloud_deskew": (C.c_int, [vp, vp, C.POINTER(DeskewMotion), vp, C.c_int, C.POINTER(vp), szp]),
+    "ndt_cloud_deskew_clouds": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, C.POINTER(DeskewMotion), vp, C.c_int, C.POINTER(vp), szp]),
+    "ndt_diag_deskew": (C.c_int, [vp, szp, szp, szp]),
+    "ndt_host_deskew_motion": (C.c_int, [fp, C.c_double, C.c_double, C.c_double, C.POINTER(DeskewMotion)]),
+    "ndt_host_deskew_point": (C.c_int, [C.POINTER(DeskewMotion), fp, C.c_double, fp, ip]),
+    "ndt_host_deskew_plan": (C.c_int, [C.c_size_t, ip, ip]),
+    "ndt_host_extract_field": (C.c_int, [vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, dp]),
+    "ndt_pcd_read_field": (C.c_int, [C.c_char_p, C.c_char_p, dp, C.c_size_t, szp]),
     "ndt_cloud_neighbor_values": (C.c_int, [vp, vp, C.POINTER(OutlierSpec), vp, C.c_int, C.POINTER(OutlierStats)]),
     "ndt_cloud_remove_outliers": (C.c_int, [vp, vp, C.POINTER(OutlierSpec), C.POINTER(vp), C.POINTER(C.c_int32), szp,
                                             C.POINTER(OutlierStats)]),

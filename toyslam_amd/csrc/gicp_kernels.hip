@@ -369,7 +369,8 @@ __device__ __forceinline__ void correspond_block(const float4* __restrict__ outp
       int best_p = -1;        // looked up on ties and at the end of a shell only)
       auto consider = [&](float d, unsigned pos, bool ok) {
         if (!ok || d > best) return;
-        if (d < best || ix.sorted_idx[pos] < ix.sorted_idx[best_p]) {  // equal distance: the lower index
+        // equal distance: the lower index (best_p < 0 with d == best == +inf, an overflowed distance: nothing to compare with)
+        if (d < best || (best_p >= 0 && ix.sorted_idx[pos] < ix.sorted_idx[best_p])) {
           best = d;
           best_p = static_cast<int>(pos);
         }

@@ -10,6 +10,7 @@
 //   ndt_score.hip : calculateScore (of a cloud, of the source under many poses)
 //   ndt_nvtl.hip  : nearest-voxel transformation likelihood (of a cloud, of the source under one or many poses, per point)
 //   ndt_select.hip : selection of the points of resident clouds (finite, box, range, per-point value): kernels and C-ABI
+//   ndt_deskew.hip : motion compensation of resident scans by the time of every point: kernel and C-ABI
 //   ndt_pose_cov.hip: 6x6 pose covariance (Laplace / sandwich) of the handle's pair and of the pairs of a pairs call
 //   ndt_eval.hip   : one evaluation (launch path), the persistent evaluation server's host side (mailbox protocol),
 //                    ndt_align, ndt_eval*, diagnostics and self-tests
@@ -518,6 +519,11 @@ struct ndt_context {
   size_t sel_launches = 0, sel_blocks = 0, sel_clouds = 0;
   // the outlier filters (ndt_outliers.hip): what the last call that reached the device did (ndt_diag_outliers)
   size_t ol_index_builds = 0, ol_value_launches = 0, ol_value_blocks = 0, ol_scanned = 0;
+  // the motion compensation (ndt_deskew.hip): the page-locked block of a call -- its segment table on the way up, its per-block
+  // rows (boxes, untimed count) on the way back -- and what the last call that reached the device did (ndt_diag_deskew)
+  void* dsk_pinned = nullptr;
+  size_t dsk_pinned_bytes = 0;
+  size_t dsk_launches = 0, dsk_blocks = 0, dsk_clouds = 0;
 
   ~ndt_context() {
     for (ndt_context* w : batch_workers) delete w;
@@ -553,6 +559,7 @@ struct ndt_context {
     if (sp_pinned) (void)hipHostFree(sp_pinned);
     if (nv_pinned) (void)hipHostFree(nv_pinned);
     if (sel_pinned) (void)hipHostFree(sel_pinned);
+    if (dsk_pinned) (void)hipHostFree(dsk_pinned);
     acc.reset();
     release_buffers();
     if (host_result) (void)hipHostFree(host_result);

@@ -28,6 +28,16 @@ ndt_status ndt_pcd_read_xyz(const char* path, void* out, size_t capacity_points,
   }
   return NDT_OK;
 }
+ndt_status ndt_pcd_read_field(const char* path, const char* name, double* out, size_t capacity_points, size_t* n_points) {
+  if (!path || !name || (capacity_points && !out)) return fail(NDT_ERR_INVALID, "bad arguments");
+  std::string err;
+  try {
+    if (ndt::pcd_read_field(path, name, out, capacity_points, n_points, err)) return fail(NDT_ERR_INVALID, err);
+  } catch (const std::exception& e) {  // nothing C++ crosses the C boundary
+    return fail(NDT_ERR_INVALID, std::string("PCD: ") + e.what());
+  }
+  return NDT_OK;
+}
 ndt_status ndt_pcd_write_xyz(const char* path, const void* pts, size_t n, size_t stride_bytes, int binary) {
   if (!path || (n && !pts) || stride_bytes < 12) return fail(NDT_ERR_INVALID, "bad arguments");
   std::string err;
@@ -289,6 +299,34 @@ ndt_status ndt_host_repack_fields(const void* data, size_t n, size_t point_step,
     dst[4 * i + 3] = 1.0f;
   }
   if (is_dense) *is_dense = finite ? 1 : 0;
+  return NDT_OK;
+}
+
+namespace {
+// one scalar of a little-endian record as a double; false for a code outside sensor_msgs/PointField's 1 ... 8
+bool field_value(const unsigned char* p, int datatype, double* out) {
+  switch (datatype) {
+    case 1: { int8_t v; std::memcpy(&v, p, 1); *out = v; return true; }
+    case 2: { uint8_t v; std::memcpy(&v, p, 1); *out = v; return true; }
+    case 3: { int16_t v; std::memcpy(&v, p, 2); *out = v; return true; }
+    case 4: { uint16_t v; std::memcpy(&v, p, 2); *out = v; return true; }
+    case 5: { int32_t v; std::memcpy(&v, p, 4); *out = v; return true; }
+    case 6: { uint32_t v; std::memcpy(&v, p, 4); *out = v; return true; }
+    case 7: { float v; std::memcpy(&v, p, 4); *out = static_cast<double>(v); return true; }
+    case 8: { double v; std::memcpy(&v, p, 8); *out = v; return true; }
+  }
+  return false;
+}
+constexpr size_t kFieldBytes[9] = {0, 1, 1, 2, 2, 4, 4, 4, 8};
+}  // namespace
+
+ndt_status ndt_host_extract_field(const void* data, size_t n, size_t point_step, size_t offset, int datatype, double* out) {
+  if (datatype < 1 || datatype > 8) return fail(NDT_ERR_INVALID, "unknown PointField datatype");
+  if (n && (!data || !out)) return fail(NDT_ERR_INVALID, "bad arguments");
+  const size_t bytes = kFieldBytes[datatype];
+  if (point_step == 0 || offset > point_step || bytes > point_step - offset) return fail(NDT_ERR_INVALID, "field offset outside the point record");
+  const unsigned char* src = static_cast<const unsigned char*>(data);
+  for (size_t i = 0; i < n; i++) (void)field_value(src + i * point_step + offset, datatype, &out[i]);  // unaligned-safe
   return NDT_OK;
 }
 

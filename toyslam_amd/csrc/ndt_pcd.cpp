@@ -182,6 +182,21 @@ bool lzf_decompress(const unsigned char* in, size_t in_len, unsigned char* out, 
   return op == out_len;
 }
 
+// the body of a binary_compressed file (behind the header: compressed size, uncompressed size, the LZF stream) unpacked
+// into `body`; 0, or 2 with err set
+int read_compressed_body(FILE* f, const Header& h, const char* path, std::vector<unsigned char>& body, std::string& err) {
+  const size_t raw_bytes = h.points * h.record;
+  uint32_t sizes[2];
+  if (std::fread(sizes, 4, 2, f) != 2) { err = std::string(path) + ": truncated compressed header"; return 2; }
+  if (sizes[1] != raw_bytes) { err = std::string(path) + ": uncompressed size does not match the header"; return 2; }
+  if (sizes[0] > h.body_bytes) { err = std::string(path) + ": truncated compressed body"; return 2; }
+  std::vector<unsigned char> comp(sizes[0]);
+  if (sizes[0] && std::fread(comp.data(), 1, sizes[0], f) != sizes[0]) { err = std::string(path) + ": truncated compressed body"; return 2; }
+  body.resize(raw_bytes);
+  if (!lzf_decompress(comp.data(), comp.size(), body.data(), raw_bytes)) { err = std::string(path) + ": corrupt LZF stream"; return 2; }
+  return 0;
+}
+
 int find_field(const Header& h, const char* name) {
   for (size_t i = 0; i < h.fields.size(); i++)
     if (h.fields[i].name == name) return static_cast<int>(i);
@@ -322,19 +337,7 @@ int pcd_read_xyz(const char* path, void* out, size_t capacity, size_t stride, si
       if (nonfinite) dense = false;
       if (mapped) (void)munmap(const_cast<unsigned char*>(mapped), map_len);
     } else {
-      uint32_t sizes[2];
-      if (std::fread(sizes, 4, 2, f) != 2) { rc = 2; err = std::string(path) + ": truncated compressed header"; }
-      if (!rc && sizes[1] != raw_bytes) { rc = 2; err = std::string(path) + ": uncompressed size does not match the header"; }
-      if (!rc && sizes[0] > h.body_bytes) { rc = 2; err = std::string(path) + ": truncated compressed body"; }
-      std::vector<unsigned char> comp;
-      if (!rc) {
-        comp.resize(sizes[0]);
-        if (sizes[0] && std::fread(comp.data(), 1, sizes[0], f) != sizes[0]) { rc = 2; err = std::string(path) + ": truncated compressed body"; }
-      }
-      if (!rc) {
-        body.resize(raw_bytes);
-        if (!lzf_decompress(comp.data(), comp.size(), body.data(), raw_bytes)) { rc = 2; err = std::string(path) + ": corrupt LZF stream"; }
-      }
+      rc = read_compressed_body(f, h, path, body, err);
       if (!rc) {  // struct of arrays: all of field 0, then all of field 1, ...
         std::vector<size_t> base(h.fields.size());
         size_t b = 0;
@@ -348,6 +351,92 @@ int pcd_read_xyz(const char* path, void* out, size_t capacity, size_t stride, si
   }
   std::fclose(f);
   if (is_dense) *is_dense = dense ? 1 : 0;
+  return rc;
+}
+
+namespace {
+
+// one scalar of a binary record -> double; false for a type / size pair outside F4, F8 and I / U of 1, 2, 4, 8 bytes
+// (beside scalar_to_float, not under it: a 64-bit integer rounded to double and then to float is not always the float it rounds to)
+bool scalar_to_double(const unsigned char* p, const Field& fd, double* out) {
+  switch (fd.type) {
+    case 'F':
+      if (fd.size == 4) { float v; std::memcpy(&v, p, 4); *out = static_cast<double>(v); return true; }
+      if (fd.size == 8) { std::memcpy(out, p, 8); return true; }
+      break;
+    case 'U':
+      if (fd.size == 1) { *out = static_cast<double>(*p); return true; }
+      if (fd.size == 2) { uint16_t v; std::memcpy(&v, p, 2); *out = static_cast<double>(v); return true; }
+      if (fd.size == 4) { uint32_t v; std::memcpy(&v, p, 4); *out = static_cast<double>(v); return true; }
+      if (fd.size == 8) { uint64_t v; std::memcpy(&v, p, 8); *out = static_cast<double>(v); return true; }
+      break;
+    case 'I':
+      if (fd.size == 1) { int8_t v; std::memcpy(&v, p, 1); *out = static_cast<double>(v); return true; }
+      if (fd.size == 2) { int16_t v; std::memcpy(&v, p, 2); *out = static_cast<double>(v); return true; }
+      if (fd.size == 4) { int32_t v; std::memcpy(&v, p, 4); *out = static_cast<double>(v); return true; }
+      if (fd.size == 8) { int64_t v; std::memcpy(&v, p, 8); *out = static_cast<double>(v); return true; }
+      break;
+  }
+  return false;
+}
+
+}  // namespace
+
+int pcd_read_field(const char* path, const char* name, double* out, size_t capacity, size_t* n_points, std::string& err) {
+  FILE* f = std::fopen(path, "rb");
+  if (!f) { err = std::string("cannot open ") + path + ": " + std::strerror(errno); return 1; }
+  Header h;
+  err = parse_header(f, h);
+  if (!err.empty()) { std::fclose(f); err = std::string(path) + ": " + err; return 2; }
+  const int k = find_field(h, name);
+  if (k < 0) { std::fclose(f); err = std::string(path) + ": no field " + name; return 2; }
+  const Field& fd = h.fields[k];
+  double probe = 0.0;
+  const unsigned char zeros[8] = {};
+  if (fd.count != 1 || !scalar_to_double(zeros, fd, &probe)) {
+    std::fclose(f);
+    err = std::string(path) + ": field " + name + " is no scalar of a supported type (COUNT 1; F 4 8, I U 1 2 4 8)";
+    return 2;
+  }
+  if (n_points) *n_points = h.points;
+  if (h.points > capacity) { std::fclose(f); err = "output buffer too small"; return 3; }
+  int rc = 0;
+  if (h.data == 0) {  // ascii: one point per line, fields in order, COUNT values each
+    size_t col = 0, cols = 0;
+    for (size_t j = 0; j < h.fields.size(); j++) {
+      if (static_cast<int>(j) == k) col = cols;
+      cols += h.fields[j].count;
+    }
+    std::string line;
+    size_t i = 0;
+    while (i < h.points && read_line(f, line)) {
+      std::vector<std::string> tok = split(line);
+      if (tok.empty()) continue;
+      if (tok.size() < cols) { rc = 2; err = std::string(path) + ": short ascii record"; break; }
+      const char* t = tok[col].c_str();
+      if (fd.type == 'I') out[i++] = static_cast<double>(std::strtoll(t, nullptr, 10));
+      else if (fd.type == 'U') out[i++] = static_cast<double>(std::strtoull(t, nullptr, 10));
+      else out[i++] = fd.size == 4 ? static_cast<double>(std::strtof(t, nullptr)) : std::strtod(t, nullptr);
+    }
+    if (!rc && i != h.points) { rc = 2; err = std::string(path) + ": fewer ascii records than POINTS"; }
+  } else if (h.data == 1) {  // binary: records in chunks through one small buffer
+    const size_t chunk = 32768;
+    std::vector<unsigned char> body(std::min(chunk, std::max<size_t>(h.points, 1)) * h.record);
+    for (size_t i0 = 0; i0 < h.points; i0 += chunk) {
+      const size_t m = std::min(chunk, h.points - i0);
+      if (std::fread(body.data(), h.record, m, f) != m) { rc = 2; err = std::string(path) + ": truncated binary body"; break; }
+      for (size_t i = 0; i < m; i++) (void)scalar_to_double(body.data() + i * h.record + fd.offset, fd, &out[i0 + i]);
+    }
+  } else {  // binary_compressed: struct of arrays behind the two sizes
+    std::vector<unsigned char> body;
+    rc = read_compressed_body(f, h, path, body, err);
+    if (!rc) {
+      size_t base = 0;
+      for (int j = 0; j < k; j++) base += static_cast<size_t>(h.fields[j].size) * h.fields[j].count * h.points;
+      for (size_t i = 0; i < h.points; i++) (void)scalar_to_double(body.data() + base + i * static_cast<size_t>(fd.size), fd, &out[i]);
+    }
+  }
+  std::fclose(f);
   return rc;
 }
 

@@ -187,7 +187,9 @@ __device__ __forceinline__ void wave_nearest(const PointIndex& ix, float qx, flo
   int best_p = -1;
   auto take = [&](float d, int pos, bool ok) {
     if (!ok || d > best) return;
-    if (d < best || ix.sorted_idx[pos] < ix.sorted_idx[best_p]) {
+    // (best_p < 0: nothing taken yet, and d == best == +inf -- a distance that overflowed f32.  Not a neighbour, and there
+    // is no index to compare with: sorted_idx[-1] is four bytes in front of the array)
+    if (d < best || (best_p >= 0 && ix.sorted_idx[pos] < ix.sorted_idx[best_p])) {
       best = d;
       best_p = pos;
     }

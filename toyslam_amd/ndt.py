@@ -903,6 +903,51 @@ class NormalDistributionsTransform:
         check(_lib.lib().ndt_host_select_point(C.byref(spec), _f(p), float(key), C.byref(keep)))
         return bool(keep.value)
 
+    # ---- motion compensation of resident scans by point time (ndt_cloud_deskew / _clouds) --------------------------------
+    def deskewCloud(self, dc, motion, times, device=False):
+        """The resident cloud `dc` as seen from the sensor frame at motion.t_ref, every record moved by the sensor's pose at
+        its own time (ndt_cloud_deskew; the definition is in include/ndt_mi355.h): a new DeviceCloud of len(dc) records in
+        dc's order with exact boxes.  motion: a _lib.DeskewMotion (host_deskew_motion).  times: one float64 per point (an
+        array), or with device=True the device pointer of such values (an int).  -> (DeviceCloud, n_untimed)."""
+        n = len(dc)
+        keep = None
+        if device:
+            tp = C.c_void_p(int(times))
+        else:
+            keep = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
+            if keep.shape[0] != n:
+                raise ValueError("one time per point")
+            tp = C.c_void_p(keep.ctypes.data) if n else None
+        c, nu = C.c_void_p(None), C.c_size_t(0)
+        check(self._L.ndt_cloud_deskew(self._h, dc._c, C.byref(motion), tp, int(bool(device)), C.byref(c), C.byref(nu)))
+        return DeviceCloud(self, c), nu.value
+
+    def deskewClouds(self, clouds, motions, times):
+        """deskewCloud of every DeviceCloud of the list under its own motion, one launch in all (ndt_cloud_deskew_clouds).
+        times: a list of per-cloud float64 arrays, or one array packed in cloud order.  -> (list of DeviceCloud, list of
+        n_untimed), entry k what deskewCloud gives for clouds[k] alone, the same bits."""
+        clouds, motions = list(clouds), list(motions)
+        n = len(clouds)
+        if len(motions) != n:
+            raise ValueError("one motion per cloud")
+        if isinstance(times, (list, tuple)):
+            times = np.concatenate([np.asarray(t, dtype=np.float64).reshape(-1) for t in times]) if times else np.zeros(0)
+        keep = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
+        if keep.shape[0] != sum(len(c) for c in clouds):
+            raise ValueError("one time per point")
+        arr = (C.c_void_p * max(n, 1))(*[c._c for c in clouds])
+        ms = (_lib.DeskewMotion * max(n, 1))(*motions)
+        out = (C.c_void_p * max(n, 1))()
+        nu = (C.c_size_t * max(n, 1))()
+        check(self._L.ndt_cloud_deskew_clouds(self._h, arr, n, ms, C.c_void_p(keep.ctypes.data) if keep.shape[0] else None, 0, out, nu))
+        return [DeviceCloud(self, C.c_void_p(p)) for p in list(out)[:n]], list(nu)[:n]
+
+    def deskewDiag(self):
+        """What the last motion compensation that reached the device did (ndt_diag_deskew)."""
+        a, b, c = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        check(self._L.ndt_diag_deskew(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return dict(launches=a.value, blocks=b.value, clouds=c.value)
+
     # ---- outlier removal of resident clouds (ndt_cloud_neighbor_values / ndt_cloud_remove_outliers / _clouds) ------------
     @staticmethod
     def outlierSpec(radius=None, min_neighbors=None, mean_k=None, stddev_mul=None, negate=False):
@@ -1656,3 +1701,51 @@ def host_repack_bbox(records, n, stride_bytes, avx2=False):
     check(_lib.lib().ndt_host_repack_bbox(buf.ctypes.data if n else None, n, stride_bytes, int(bool(avx2)),
                                           out.ctypes.data if n else None, _f(bounds)))
     return out.copy(), bounds.reshape(2, 2, 3)
+
+
+# ---- motion compensation: the host-only pieces (no GPU needed) ------------------------------------------------------------
+def host_deskew_motion(T, t_begin, t_end, t_ref=None):
+    """The _lib.DeskewMotion of a sweep [t_begin, t_end] over which the sensor moves by the 4x4 T (its pose at t_end in its
+    frame at t_begin), output frame at t_ref (None: t_begin) -- ndt_host_deskew_motion."""
+    m = _lib.DeskewMotion()
+    check(_lib.lib().ndt_host_deskew_motion(_f(_colmajor(T)), float(t_begin), float(t_end), float(t_begin if t_ref is None else t_ref),
+                                            C.byref(m)))
+    return m
+
+
+def host_deskew_point(motion, xyz, t):
+    """ndt_host_deskew_point, the function the kernel calls: -> ((3,) float32, untimed)."""
+    p, q, u = np.ascontiguousarray(xyz, dtype=np.float32).reshape(3), np.zeros(3, dtype=np.float32), C.c_int(-1)
+    check(_lib.lib().ndt_host_deskew_point(C.byref(motion), _f(p), float(t), _f(q), C.byref(u)))
+    return q, bool(u.value)
+
+
+def host_deskew_plan(n):
+    """(blocks, points_per_block) of the motion compensation of a cloud of n points (ndt_host_deskew_plan)."""
+    b, p = C.c_int(0), C.c_int(0)
+    check(_lib.lib().ndt_host_deskew_plan(int(n), C.byref(b), C.byref(p)))
+    return b.value, p.value
+
+
+POINTFIELD_TYPES = {"int8": 1, "uint8": 2, "int16": 3, "uint16": 4, "int32": 5, "uint32": 6, "float32": 7, "float64": 8}
+
+
+def extract_field(data, n, point_step, offset, datatype):
+    """One scalar field of PointCloud2-style records (bytes-like, any step / offset) as (n,) float64 -- the companion of
+    repack_fields for the per-point time.  datatype: a sensor_msgs/PointField code 1 ... 8 or a name of POINTFIELD_TYPES."""
+    buf = np.frombuffer(data, dtype=np.uint8)
+    assert buf.size >= n * point_step
+    out = np.zeros(max(n, 1), dtype=np.float64)
+    code = POINTFIELD_TYPES.get(datatype, datatype)
+    check(_lib.lib().ndt_host_extract_field(buf.ctypes.data if buf.size else None, n, point_step, offset, int(code), _d(out)))
+    return out[:n].copy()
+
+
+def pcd_read_field(path, name):
+    """One named scalar field of a PCD file as (n,) float64 (ndt_pcd_read_field)."""
+    L = _lib.lib()
+    n, nf, kind = C.c_size_t(0), C.c_int(0), C.c_int(0)
+    check(L.ndt_pcd_read_header(os.fsencode(path), C.byref(n), C.byref(nf), C.byref(kind)))
+    out = np.zeros(max(n.value, 1), dtype=np.float64)
+    check(L.ndt_pcd_read_field(os.fsencode(path), name.encode(), _d(out), n.value, C.byref(n)))
+    return out[:n.value].copy()
