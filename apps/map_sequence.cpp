@@ -22,7 +22,7 @@
 // after the other, 2.7 ms overlapped, 3.7 ms overlapped on CU partitions -- the steps are short host-paced sequences of
 // pageable copies and small launches, and two threads driving them get in each other's way; hence not the default.
 //
-//   map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--deskew <field>] [--range <min> <max>] [--outliers-radius <r> <min_neighbors>] [--outliers-stat <mean_k> <stddev_mul>] [--reject-unexplained <L>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> [voxel_leaf_size (0.5 | 0.3)] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]
+//   map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--deskew <field>] [--range <min> <max>] [--outliers-radius <r> <min_neighbors>] [--outliers-stat <mean_k> <stddev_mul>] [--reject-unexplained <L>] [--clear-rays <min_rays> <margin>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> [voxel_leaf_size (0.5 | 0.3)] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]
 // ("host": the serial loop with every cloud passing through host buffers, as in rounds 1-3; the default keeps them in HBM)
 //
 // --scan-to-map (anywhere on the line; the node's loop with clouds resident in HBM): every scan after the first is registered
@@ -70,6 +70,10 @@
 // registered pose is at least L, and those no voxel is near (new ground) -- instead of as the whole scan, so that moving objects
 // the target does not explain stay out of it; "rejected: <n - k>/<n>" is printed.  The first scan has no target and is
 // accumulated whole.
+// --clear-rays <min_rays> <margin> (with --scan-to-map, not with --localize): every registered scan clears the map before it is
+// accumulated (ndt_target_accumulate_clear_rays at its registered pose, the sensor origin the pose's translation): a voxel that
+// at least min_rays of the scan's beams cross, up to `margin` metres before their hits, and that holds no point of the scan
+// is dropped -- a car that has left, a door that has opened.  "cleared: <removed>/<voxels before>" is printed per scan.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -185,6 +189,8 @@ struct Node {
   std::string directory;
   bool reject = false;       // --reject-unexplained: a registered scan is accumulated without the points the target does not explain
   double reject_below = 0;
+  bool clear_rays = false;   // --clear-rays: a registered scan clears the voxels it sees through before it is accumulated
+  ndt_ray_spec ray_spec{};
   gicp_handle gicp = nullptr;  // --gicp: the registrations are GICP's against the accumulated target (bound to the NDT handle's grid)
   std::vector<std::vector<float>> trajectory;                     // trajectory_
   std::vector<float> pose = std::vector<float>(kIdentity, kIdentity + 16);
@@ -193,8 +199,19 @@ struct Node {
   double t_filter = 0, t_align = 0, t_map = 0, t_wait = 0;  // t_wait: for the next file (the reader runs ahead in the background)
 
   // --scan-to-map: the scan into the accumulated target at its pose in the map (column-major), then the window around it
-  int accumulate(ndt_handle h, ndt_cloud scan, const float* map_pose) {
+  // (seen: the whole registered scan, whose beams clear the map first -- --clear-rays)
+  int accumulate(ndt_handle h, ndt_cloud scan, const float* map_pose, ndt_cloud seen = nullptr) {
     if (localize) return 0;
+    if (clear_rays && seen) {
+      size_t before = 0, removed = 0;
+      CHECK(ndt_target_accumulated(h, nullptr, &before, nullptr));
+      ndt_ray_spec spec = ray_spec;
+      spec.min_range = 0.f;
+      spec.max_range = 65536.f * ndt_get_resolution(h);  // every beam, whatever its length
+      CHECK(ndt_target_accumulate_clear_rays(h, seen, map_pose, nullptr, &spec));
+      if (before) CHECK(ndt_diag_target_clear_rays(h, nullptr, nullptr, nullptr, nullptr, &removed, nullptr, nullptr, nullptr, nullptr));
+      std::printf("cleared: %zu/%zu\n", removed, before);
+    }
     CHECK(ndt_target_accumulate_cloud(h, scan, 1, map_pose));
     if (window > 0) {
       const float lo[3] = {map_pose[12] - window, map_pose[13] - window, map_pose[14] - window};
@@ -466,10 +483,10 @@ static int run_resident(Node& node, ndt_pcd_sequence_handle seq, float voxel_lea
           size_t kept = 0;
           CHECK(ndt_source_select_by_nvtl(h, nullptr, node.reject_below, 1, &explained, &kept, nullptr));
           std::printf("rejected: %zu/%zu\n", m - kept, m);
-          const int failed = node.accumulate(h, explained, map_pose.data());
+          const int failed = node.accumulate(h, explained, map_pose.data(), current);
           ndt_cloud_release(explained);
           if (failed) return 1;
-        } else if (node.scan_to_map && node.accumulate(h, current, map_pose.data())) {
+        } else if (node.scan_to_map && node.accumulate(h, current, map_pose.data(), current)) {
           return 1;
         }
         node.t_map += since(t0);
@@ -740,6 +757,8 @@ int main(int argc, char** argv) {
   bool range = false, bad_range = false, reject = false, bad_reject = false;
   bool outliers_radius = false, outliers_stat = false, bad_outliers = false;
   bool use_gicp = false, have_gate = false, bad_gate = false;
+  bool clear_rays = false, bad_clear = false;
+  ndt_ray_spec ray_spec{};
   double gicp_gate = 5.0;
   ndt_outlier_spec radius_spec{}, stat_spec{};
   float window = 0, range_min = 0, range_max = 0;
@@ -747,7 +766,7 @@ int main(int argc, char** argv) {
   const char *save_target = nullptr, *load_target = nullptr, *deskew_field = nullptr;
   bool bad_deskew = false;
   static const char kUsage[] =
-      "usage: map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--gicp [--gicp-gate <m>]] [--deskew <field>] [--range <min> <max>] [--outliers-radius <r> <min_neighbors>] [--outliers-stat <mean_k> <stddev_mul>] [--reject-unexplained <L>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> "
+      "usage: map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--gicp [--gicp-gate <m>]] [--deskew <field>] [--range <min> <max>] [--outliers-radius <r> <min_neighbors>] [--outliers-stat <mean_k> <stddev_mul>] [--reject-unexplained <L>] [--clear-rays <min_rays> <margin>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> "
       "[voxel_leaf_size] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]\n";
   {  // the switches are taken out of the line before the positional arguments are read
     int kept = 1;
@@ -802,6 +821,14 @@ int main(int argc, char** argv) {
           spec.stddev_mul = std::atof(argv[++i]);
         }
         bad_outliers = bad_outliers || ndt_host_outlier_spec_check(&spec) != NDT_OK;
+      } else if (std::strcmp(argv[i], "--clear-rays") == 0) {
+        clear_rays = true;
+        bad_clear = i + 2 >= argc;
+        if (!bad_clear) {
+          ray_spec.min_rays = std::atoi(argv[++i]);
+          ray_spec.margin = static_cast<float>(std::atof(argv[++i]));
+          bad_clear = !(ray_spec.min_rays >= 1 && ray_spec.margin >= 0 && std::isfinite(ray_spec.margin));
+        }
       } else if (std::strcmp(argv[i], "--reject-unexplained") == 0) {
         reject = true;
         bad_reject = i + 1 >= argc;
@@ -830,6 +857,11 @@ int main(int argc, char** argv) {
   if (bad_range || bad_reject || ((range || reject) && !scan_to_map) || (reject && localize)) {
     std::fprintf(stderr, "--range <min> <max> (0 <= min <= max) and --reject-unexplained <L> go with --scan-to-map; --localize accumulates "
                          "nothing, so it does not go with --reject-unexplained\n%s", kUsage);
+    return 2;
+  }
+  if (bad_clear || (clear_rays && (!scan_to_map || localize))) {
+    std::fprintf(stderr, "--clear-rays <min_rays> <margin> (min_rays >= 1, margin >= 0) goes with --scan-to-map; --localize leaves the map as it "
+                         "is, so it does not go with --clear-rays\n%s", kUsage);
     return 2;
   }
   if (bad_deskew || (deskew_field && !scan_to_map)) {
@@ -861,6 +893,8 @@ int main(int argc, char** argv) {
   node.map_fitness = map_fitness;
   node.nvtl = nvtl;
   node.covariance = covariance;
+  node.clear_rays = clear_rays;
+  node.ray_spec = ray_spec;
   node.range = range;
   node.range_min = range_min;
   node.range_max = range_max;

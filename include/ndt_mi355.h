@@ -605,6 +605,77 @@ ndt_status ndt_diag_target_accumulate(ndt_handle h, size_t* touched_voxels, size
  * (the scan counts one). */
 ndt_status ndt_target_accumulate_crop(ndt_handle h, const float min_xyz[3], const float max_xyz[3]);
 ndt_status ndt_diag_target_crop(ndt_handle h, size_t* kept_voxels, size_t* removed_voxels, size_t* kept_points, int* relinked, size_t* launches);
+/* Clearing by rays: the accumulated target forgets what a later scan sees THROUGH.  The target keeps no points, so the
+ * occupancy-map remedy is the one available: a scan whose beams pass through a voxel's cell and hit something behind it is
+ * evidence that the cell is empty (a car that was parked and left, a pedestrian's trail, a door that has opened).
+ * A call takes one or more resident clouds, each with a pose (column-major 4x4, NULL = identity) and a sensor origin o (three
+ * f32 values in the map frame, NULL = the pose's translation), and a spec.
+ * - Posed points.  Every finite record is moved by its pose with N2's f32 transform (what ndt_target_accumulate* does): p.  A
+ *   non-finite row (or a row the pose moves to a non-finite p) gives no ray and no hit and is counted nowhere.
+ * - Hit set H: the build cell floor(p * inv_leaf) (f32, the arithmetic that bins a point) of every posed point of the call,
+ *   whatever its range.  A point whose build cell lies outside [-2^20, 2^20) on an axis gives no hit and no ray; it is not an
+ *   error (it counts as a skipped ray).
+ * - The ray of a point.  All arithmetic is f64, every operation rounded on its own.  L = (double)resolution of the running
+ *   target, d = p - o, len = sqrt(dx*dx + dy*dy + dz*dz) summed in that order.  The ray is cast exactly when len > 0,
+ *   min_range <= len <= max_range and t_end = 1 - margin / len > 0; otherwise it is skipped.  A cast ray covers o + t d for t in
+ *   [0, t_end]: the last `margin` metres before the hit are never walked.
+ * - The walk.  The start cell m has m_k L <= o_k < (m_k + 1) L on every axis (the products are exact in f64).  On an axis with
+ *   d_k != 0: s_k = sign(d_k), f_k = m_k + (s_k > 0), t_k = (f_k L - o_k) / d_k; on any other axis t_k = +inf.  Repeat: take the
+ *   axis a with the smallest t_a (the lowest axis wins a tie); stop unless t_a <= t_end; m_a += s_a, f_a += s_a; t_a is
+ *   recomputed from the formula, never accumulated.  The visited cells are the start cell and every m after a step.  The walk
+ *   also ends when m leaves [-2^20, 2^20); a start cell outside that range visits nothing.
+ * - Decision.  miss(v) = the cast rays of the whole call, over all its clouds, that visit the cell of voxel v (a ray visits a
+ *   cell at most once).  A voxel is removed exactly when miss(v) >= min_rays and its cell is not in H, whatever its state
+ *   (under min_points_per_voxel, valid, rejected).
+ * - Equivalence: the crop's, with "inside the crop range" replaced by "not removed": afterwards the handle behaves like a
+ *   handle whose target was set from the concatenation, in the original order, of every accumulated point whose voxel no later
+ *   crop or clearing removed -- the same dump, the same bits from every evaluation and registration call listed above, for all
+ *   four search methods.  Box (the tight cell box of the kept voxels), n_points (the kept counts), the dense-or-sparse choice,
+ *   the capacities, a removed cell that receives points again, ndt_warm_up: as after a crop.
+ * - Nothing removed: NDT_OK, nothing of the target is written (n_points becomes the sum of the voxels' counts, as after a
+ *   crop that removes nothing: non-finite rows accumulated earlier are forgotten).  Everything removed: the empty target of
+ *   a crop that removes everything.
+ * - Refused before anything changes and without a device -- NDT_ERR_INVALID: a NULL handle, a NULL spec, NULL clouds with a
+ *   non-zero count, a NULL entry of clouds, a non-finite pose or origin, a spec that fails ndt_host_ray_spec_check for the
+ *   target's resolution (all three lengths finite, 0 <= min_range <= max_range, max_range > 0, margin >= 0, min_rays >= 1,
+ *   max_range / resolution <= 65536: a walk is at most 3 x 65537 steps), more than INT_MAX points in one call;
+ *   NDT_ERR_NO_INPUT: no live accumulated target (checked after the NULL and finiteness checks, before the spec).
+ *   Zero clouds, or only empty clouds: NDT_OK, nothing changes, no device needed.
+ * - _clouds: all clouds go through ONE pass and the misses are summed over all of them; poses: 16 floats per cloud, origins: 3
+ *   floats per cloud, either may be NULL.
+ * - Device side: ONE ray launch over all points of all clouds (transform, hit flag, walk with a key-table probe per visited
+ *   cell, integer miss counts: independent of order), the keep-flag launch and its scan, one read-back, and -- if anything
+ *   goes and anything stays -- the crop's compaction, key-table and look-up-table rebuild: 3 launches when nothing or everything
+ *   is removed, 6 otherwise, whatever the number of clouds and points (1 for a target without voxels).
+ * - ndt_target_accumulate_ray_counts runs the same ray pass (1 launch) and removes nothing: nothing of the target is written.
+ *   One row per voxel of the target in ascending key (the export's order): its cell (3 ints), its miss count, whether its cell
+ *   is in H.  *n_voxels (may be NULL) = the rows; cells == NULL: only that.  capacity (in rows) too small: NDT_ERR_INVALID.
+ * - ndt_diag_target_clear_rays, of the last of these calls that reached the device: rays cast and skipped (together the
+ *   finite rows), the total of cells visited by cast rays, voxels with miss >= 1, voxels removed and kept and points kept
+ *   (_ray_counts: what a clearing would have done), whether the tables were rebuilt, launches (the scan counts one).
+ * Host only: ndt_host_ray_spec_check (the validity of a spec for a resolution); ndt_host_ray_cells walks ONE ray with the body
+ * the kernel uses and applies no range test (len > 0 and t_end > 0 still hold, else *n = 0): *n = the cells visited, written
+ * to cells (3 ints each) when it is not NULL; more cells than capacity: NDT_ERR_INVALID with *n set; ndt_host_ray_plan: the
+ * grid of the ray kernel for the n_points of a call -- blocks of 256 threads, a thread per point up to 1024 blocks, beyond
+ * which thread g takes the points g, g + 256 * blocks, ...; *passes = the most points one thread takes.
+ * Development switches, read per call: NDT_RAYS_MAX_BLOCKS caps the blocks of the ray kernel; NDT_RAYS_MERGE=0 adds every miss
+ * with an atomic of its own instead of merging the equal slots of a wave (the results depend on neither). */
+typedef struct ndt_ray_spec {
+  float min_range, max_range; /* metres: rays shorter or longer are skipped */
+  float margin;               /* metres before the hit that are never walked */
+  int min_rays;               /* misses a voxel needs to be removed */
+} ndt_ray_spec;
+ndt_status ndt_target_accumulate_clear_rays(ndt_handle h, ndt_cloud cloud, const float* pose, const float* origin, const ndt_ray_spec* spec);
+ndt_status ndt_target_accumulate_clear_rays_clouds(ndt_handle h, const ndt_cloud* clouds, size_t n_clouds, const float* poses /* n*16 or NULL */,
+                                                   const float* origins /* n*3 or NULL */, const ndt_ray_spec* spec);
+ndt_status ndt_target_accumulate_ray_counts(ndt_handle h, const ndt_cloud* clouds, size_t n_clouds, const float* poses, const float* origins,
+                                            const ndt_ray_spec* spec, int* cells /* 3 per row, or NULL */, unsigned* misses, unsigned char* hit,
+                                            size_t capacity, size_t* n_voxels);
+ndt_status ndt_diag_target_clear_rays(ndt_handle h, size_t* rays_cast, size_t* rays_skipped, uint64_t* cells_visited, size_t* touched_voxels,
+                                      size_t* removed_voxels, size_t* kept_voxels, size_t* kept_points, int* relinked, size_t* launches);
+ndt_status ndt_host_ray_spec_check(const ndt_ray_spec* spec, float resolution);
+ndt_status ndt_host_ray_cells(const float origin[3], const float point[3], float resolution, float margin, int* cells, size_t capacity, size_t* n);
+ndt_status ndt_host_ray_plan(size_t n_points, int* blocks, int* passes);
 /* Export and import: voxels leave an accumulated target and enter another one (or the same one later) bit for bit -- a map
  * saved to a file and loaded by a later run, a second handle with the same map (ndt_clone / ndt_share_input_target keep
  * refusing accumulated targets: export + import is the way), tiles paged out when a crop window moves on and paged back in

@@ -43,6 +43,11 @@ class DeskewMotion(C.Structure):
                 ("tau_ref", C.c_double * 3)]
 
 
+class RaySpec(C.Structure):
+    """ndt_ray_spec (include/ndt_mi355.h)"""
+    _fields_ = [("min_range", C.c_float), ("max_range", C.c_float), ("margin", C.c_float), ("min_rays", C.c_int)]
+
+
 class OutlierSpec(C.Structure):
     """ndt_outlier_spec (include/ndt_mi355.h)"""
     _fields_ = [("method", C.c_int), ("negate", C.c_int), ("radius", C.c_float), ("min_neighbors", C.c_int), ("mean_k", C.c_int),
@@ -149,6 +154,14 @@ SIGNATURES = {
     "ndt_diag_target_accumulate": (C.c_int, [vp, szp, szp, ip, ip, szp]),
     "ndt_target_accumulate_crop": (C.c_int, [vp, fp, fp]),
     "ndt_diag_target_crop": (C.c_int, [vp, szp, szp, szp, ip, szp]),
+    "ndt_target_accumulate_clear_rays": (C.c_int, [vp, vp, fp, fp, C.POINTER(RaySpec)]),
+    "ndt_target_accumulate_clear_rays_clouds": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, fp, fp, C.POINTER(RaySpec)]),
+    "ndt_target_accumulate_ray_counts": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, fp, fp, C.POINTER(RaySpec), ip, C.POINTER(C.c_uint),
+                                                   C.POINTER(C.c_ubyte), C.c_size_t, szp]),
+    "ndt_diag_target_clear_rays": (C.c_int, [vp, szp, szp, C.POINTER(C.c_uint64), szp, szp, szp, szp, ip, szp]),
+    "ndt_host_ray_spec_check": (C.c_int, [C.POINTER(RaySpec), C.c_float]),
+    "ndt_host_ray_cells": (C.c_int, [fp, fp, C.c_float, C.c_float, ip, C.c_size_t, szp]),
+    "ndt_host_ray_plan": (C.c_int, [C.c_size_t, ip, ip]),
     "ndt_target_accumulate_export": (C.c_int, [vp, fp, fp, vp, C.c_size_t, szp]),
     "ndt_target_accumulate_import": (C.c_int, [vp, vp, C.c_size_t]),
     "ndt_target_accumulate_save": (C.c_int, [vp, fp, fp, C.c_char_p]),

@@ -1,5 +1,6 @@
 // ndt_acc.hpp -- private to the units of the accumulating target: ndt_acc_kernels.hip (kernels and their launches),
-// ndt_accumulate.hip (the target's state and what changes slots), ndt_acc_persist.hip (export / import / files)
+// ndt_acc_rays.hip (the ray pass of a clearing and its launches), ndt_accumulate.hip (the target's state and what changes
+// slots), ndt_acc_persist.hip (export / import / files)
 #pragma once
 #include "ndt_acc_blob.hpp"
 #include "ndt_internal.hpp"
@@ -101,6 +102,24 @@ hipError_t launch_acc_import_check(const AccRow* rows, int n, const AccCropBox& 
 hipError_t launch_acc_finish(const int* order, int n, ndtc::AccTarget* a, VoxelRec* recs, VoxelSide* cents, int* lut, const GridGeom& geo, FinalizeDump dump,
                              int* cell_out, hipStream_t st);
 
+// ---- clearing by rays (ndt_target_accumulate_clear_rays, ndt_acc_rays.hip): a walk per point through the key table
+struct AccRayScan {  // a cloud of a call: n > 0 records, the call's points [first, first + n); its pose and its sensor origin
+  const float4* src;
+  int n, first;
+  float T[12];
+  float o[3];
+};
+constexpr int kAccRayCounters = 3;  // u64 words a ray pass adds to: rays cast, rays skipped, cells visited by cast rays
+// ONE launch over all clouds: per point the hit flag of its build cell's slot, and +1 on the miss count of every occupied cell
+// its ray visits.  box: the target's cell box (no voxel lies outside it).  miss / hit: n_slots words each, zeroed
+hipError_t launch_acc_rays(const AccRayScan& one, const AccRayScan* d_scans, int n_scans, int n_points, int blocks, float resolution,
+                           const ndt_ray_spec& spec, const AccView& v, const AccCropBox& box, unsigned* miss, unsigned* hit,
+                           unsigned long long* counters, hipStream_t st);
+// the keep flags of a clearing (miss < min_rays || hit) and their exclusive scan: launch_acc_mark's two launches and its info
+// block; info[7] = voxels with miss >= 1
+hipError_t launch_acc_rays_mark(const AccView& v, int n_slots, const unsigned* miss, const unsigned* hit, int min_rays, unsigned* keep, int* info,
+                                unsigned* number, hipStream_t st);
+
 }  // namespace ndt
 
 namespace ndtc {
@@ -129,9 +148,9 @@ struct AccTarget {
 };
 
 // the info block every call's kernels reduce into, as its kAccCropInfoWords words lie: a box (of encoded floats from k_acc_keys:
-// ndt::acc_decode; else of cells), [6] the range flag of an update / kept slots / rows / the flags of an import's rows, [8..9] points
+// ndt::acc_decode; else of cells), [6] the range flag of an update / kept slots / rows / the flags of an import's rows, [7] a clearing's voxels with a miss, [8..9] points
 struct AccInfo {
-  int lo[3], hi[3], word6, unused;
+  int lo[3], hi[3], word6, word7;
   unsigned long long points;
 };
 static_assert(sizeof(AccInfo) == ndt::kAccCropInfoWords * sizeof(int), "AccInfo is the info block");

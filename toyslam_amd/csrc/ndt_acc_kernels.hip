@@ -3,18 +3,13 @@
 #include <hipcub/hipcub.hpp>
 
 #include "ndt_acc.hpp"
-#include "ndt_device.hpp"
+#include "ndt_acc_device.hpp"
 #include "ndt_voxel_finish.hpp"
 
 namespace ndt {
 namespace {
 
-constexpr unsigned long long kAccEmptyKey = ~0ull;  // free table slot; also the key of a point that is not binned (sorts last)
 constexpr int kAccTeam = 16;
-
-__device__ __forceinline__ unsigned acc_hash(unsigned long long key, int bits) {
-  return static_cast<unsigned>((key * 0x9E3779B97F4A7C15ull) >> (64 - bits));
-}
 
 // info: [0..2] min xyz, [3..5] max xyz (encoded), [6] range flag
 __global__ __launch_bounds__(kBlock) void k_acc_keys(const float4* __restrict__ pts, int n, float inv_leaf, unsigned long long* __restrict__ keys,
@@ -69,15 +64,6 @@ __global__ __launch_bounds__(kBlock) void k_acc_heads(const unsigned long long* 
   }
 }
 
-__device__ __forceinline__ int acc_find(const AccView& v, unsigned long long key) {
-  if (!v.keys) return -1;
-  const unsigned mask = (1u << v.bits) - 1u;
-  for (unsigned h = acc_hash(key, v.bits);; h = (h + 1u) & mask) {
-    const unsigned long long seen = v.keys[h];
-    if (seen == key) return v.vals[h];
-    if (seen == kAccEmptyKey) return -1;
-  }
-}
 __device__ __forceinline__ void acc_insert(const AccView& v, unsigned long long key, int slot) {
   const unsigned mask = (1u << v.bits) - 1u;
   for (unsigned h = acc_hash(key, v.bits);; h = (h + 1u) & mask) {
@@ -257,21 +243,7 @@ __global__ __launch_bounds__(kBlock) void k_acc_crop_mark(const int4* __restrict
       pts = static_cast<double>(c.w);
     }
   }
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    mn[k] = wave_min(mn[k]);
-    mx[k] = wave_max(mx[k]);
-  }
-  pts = wave_sum(pts);  // (at most 64 x INT_MAX: exact)
-  const unsigned long long mask = __ballot(kept);
-  if ((threadIdx.x & (kWave - 1)) == 0 && mask != 0) {
-    for (int k = 0; k < 3; k++) {
-      atomicMin(info + k, static_cast<int>(mn[k]));
-      atomicMax(info + 3 + k, static_cast<int>(mx[k]));
-    }
-    atomicAdd(info + 6, __popcll(mask));
-    atomicAdd(reinterpret_cast<unsigned long long*>(info + 8), static_cast<unsigned long long>(pts));
-  }
+  acc_mark_fold(kept, mn, mx, pts, info);
 }
 
 // every kept slot to its new number (the exclusive scan of the keep flags: kept slots keep their order) in fresh arrays.

@@ -30,7 +30,14 @@
 //   ---- one read-back: kept slots, kept points, cell box; nothing removed -> return; the host derives geometry, form, capacities ----
 //   k_acc_crop_compact  kept slots into FRESH arrays (cell, sums, state, record, side sector: none depends on box or slot)
 //   k_acc_rehash / k_acc_relink   the cleared key table and the cleared look-up table from the kept slots
+//
+// One clearing by rays (ndt_target_accumulate_clear_rays*) -- one launch over the call's points, then over the slots:
+//   k_acc_rays          a thread per point of all clouds: pose, hit flag of its build cell's slot, the ray walked through the key
+//                       table, +1 on the miss count of every occupied cell it visits (ndt_acc_rays.hip, ndt_rays.hpp)
+//   k_acc_rays_mark / scan   the crop's mark with the predicate miss < min_rays || hit
+//   ---- one read-back; then the crop's tail (acc_remove_unkept): compact, rehash, relink if anything goes and anything stays
 #include "ndt_acc.hpp"
+#include "ndt_rays.hpp"
 
 namespace ndtc {
 
@@ -300,39 +307,31 @@ void acc_make_empty(AccTarget* a) {
   g->touched();
 }
 
-// ndt_target_accumulate_crop once the bounds are cells: mark + scan, ONE read-back, then (if anything goes) the kept slots
-// compacted into fresh arrays in their order, the key table and the look-up table rebuilt from them
-ndt_status acc_crop(ndt_context* h, AccTarget* a, const ndt::AccCropBox& box) {
+// What a removal of whole voxels did (a crop's and a clearing's diagnostics)
+struct AccRemoval {
+  size_t kept = 0, removed = 0, points = 0, launches = 0;
+  int relinked = 0;
+};
+
+// The shared tail of a crop and a clearing, after THE read-back of the mark pass (`seen`: kept slots, their points, their cell
+// box; keep / number: the flags and their exclusive scan): nothing removed -> nothing written; else the kept slots compacted
+// into fresh arrays in their order, the key table and the look-up table rebuilt from them (three launches)
+ndt_status acc_remove_unkept(ndt_context* h, AccTarget* a, const AccInfo& seen, const unsigned* keep, const unsigned* number, AccRemoval* r) {
   hipStream_t st = h->stream;
   DeviceGrid* g = a->grid.get();
   const int n_slots = a->n_slots;
   const size_t S = static_cast<size_t>(n_slots);
-  h->crop_kept = S;
-  h->crop_points = a->n_points;
-  h->crop_removed = h->crop_launches = 0;
-  h->crop_relinked = 0;
   auto done = [&](size_t points) {  // the points the target still holds: the non-finite rows are forgotten in any case
-    h->crop_points = a->n_points = points;
+    r->points = a->n_points = points;
     h->target->n = points;
     return NDT_OK;
   };
-  if (n_slots == 0) return done(0);  // no voxel
-  DevBuf<unsigned> w;  // keep flags, new numbers
-  DevBuf<int> info;
-  HIP_TRY(w.reserve(2 * S));
-  HIP_TRY(acc_info_reset(info, st));
-  unsigned *keep = w.p, *number = w.p + S;
-  HIP_TRY(ndt::launch_acc_mark(a->view(), n_slots, box, keep, info.p, number, nullptr, st));
-  h->crop_launches += 2;
-  // ---- the one read-back
-  AccInfo seen;
-  HIP_TRY(acc_info_read(info, st, &seen));
   const int kept = seen.word6;
   if (kept < 0 || kept > n_slots) return fail(NDT_ERR_HIP, "crop: the kept count is out of range");
   if (kept == n_slots) return done(seen.points);  // nothing removed: nothing written, no table rewritten
-  h->crop_kept = static_cast<size_t>(kept);
-  h->crop_removed = S - static_cast<size_t>(kept);
-  h->crop_points = static_cast<size_t>(seen.points);
+  r->kept = static_cast<size_t>(kept);
+  r->removed = S - static_cast<size_t>(kept);
+  r->points = static_cast<size_t>(seen.points);
   if (kept == 0) {
     acc_make_empty(a);
     return done(0);
@@ -360,12 +359,187 @@ ndt_status acc_crop(ndt_context* h, AccTarget* a, const ndt::AccCropBox& box) {
   g->touched();  // (the centroid fitness and readers' caches: voxels left, the box changed)
   HIP_TRY(ndt::launch_acc_rehash(a->view(), kept, st));
   HIP_TRY(ndt::launch_acc_relink(a->view(), kept, geo, g->lut.p, st));
-  h->crop_launches += 3;
-  h->crop_relinked = 1;
+  r->launches += 3;
+  r->relinked = 1;
   g->empty = false;
   g->n_leaves = static_cast<size_t>(kept);
   g->counts_known = false;
   return done(seen.points);
+}
+
+// ndt_target_accumulate_crop once the bounds are cells: mark + scan, ONE read-back, then (if anything goes) acc_remove_unkept
+ndt_status acc_crop_run(ndt_context* h, AccTarget* a, const ndt::AccCropBox& box, AccRemoval* r) {
+  hipStream_t st = h->stream;
+  const int n_slots = a->n_slots;
+  const size_t S = static_cast<size_t>(n_slots);
+  r->kept = S;
+  r->points = a->n_points;
+  if (n_slots == 0) {  // no voxel: the non-finite rows are forgotten
+    r->points = a->n_points = 0;
+    h->target->n = 0;
+    return NDT_OK;
+  }
+  DevBuf<unsigned> w;  // keep flags, new numbers
+  DevBuf<int> info;
+  HIP_TRY(w.reserve(2 * S));
+  HIP_TRY(acc_info_reset(info, st));
+  unsigned *keep = w.p, *number = w.p + S;
+  HIP_TRY(ndt::launch_acc_mark(a->view(), n_slots, box, keep, info.p, number, nullptr, st));
+  r->launches += 2;
+  // ---- the one read-back
+  AccInfo seen;
+  HIP_TRY(acc_info_read(info, st, &seen));
+  return acc_remove_unkept(h, a, seen, keep, number, r);
+}
+ndt_status acc_crop(ndt_context* h, AccTarget* a, const ndt::AccCropBox& box) {
+  AccRemoval r;
+  const ndt_status s = acc_crop_run(h, a, box, &r);
+  h->crop_kept = r.kept;
+  h->crop_removed = r.removed;
+  h->crop_points = r.points;
+  h->crop_launches = r.launches;
+  h->crop_relinked = r.relinked;
+  return s;
+}
+
+// ---- clearing by rays (ndt_target_accumulate_clear_rays*, _ray_counts): the ray pass over the call's points, then a removal
+int rays_max_blocks() {  // development switch, read per call: small values reach the strided regime with small clouds
+  const char* e = getenv("NDT_RAYS_MAX_BLOCKS");
+  const int x = e ? atoi(e) : 0;
+  return x > 0 ? std::min(x, ndt::kRayMaxBlocks) : ndt::kRayMaxBlocks;
+}
+
+struct RayCall {  // a checked call: its live target, its non-empty clouds as the kernel takes them, its points
+  AccTarget* a = nullptr;
+  std::vector<std::shared_ptr<DeviceCloud>> clouds;
+  std::vector<ndt::AccRayScan> scans;
+  size_t total = 0;
+};
+struct RayPass {  // what the ray pass leaves on the device: miss and hit per slot, the three totals
+  DevBuf<unsigned> w;
+  DevBuf<unsigned long long> counters;
+  DevBuf<unsigned char> d_scans;
+  unsigned *miss = nullptr, *hit = nullptr;
+};
+
+// every refusal of the three entries, in the header's order; nothing needs a device
+ndt_status rays_checks(ndt_handle h, const ndt_cloud* clouds, size_t n_clouds, const float* poses, const float* origins, const ndt_ray_spec* spec,
+                       RayCall* call) {
+  static const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  if (!h) return fail(NDT_ERR_INVALID, "null handle");
+  if (!spec) return fail(NDT_ERR_INVALID, "null ray spec");
+  if (n_clouds && !clouds) return fail(NDT_ERR_INVALID, "null clouds");
+  for (size_t k = 0; k < n_clouds; k++) {
+    for (int q = 0; poses && q < 16; q++)
+      if (!std::isfinite(poses[16 * k + q])) return fail(NDT_ERR_INVALID, "a pose of a ray call is not finite");
+    for (int q = 0; origins && q < 3; q++)
+      if (!std::isfinite(origins[3 * k + q])) return fail(NDT_ERR_INVALID, "a sensor origin of a ray call is not finite");
+  }
+  for (size_t k = 0; k < n_clouds; k++)
+    if (!clouds[k] || !clouds[k]->c) return fail(NDT_ERR_INVALID, "null cloud");
+  call->a = acc_live(h);
+  if (!call->a) return fail(NDT_ERR_NO_INPUT, "no accumulated target to cast rays through");
+  if (const char* why = ndt::ray_spec_error(*spec, call->a->resolution)) return fail(NDT_ERR_INVALID, why);
+  for (size_t k = 0; k < n_clouds; k++) {
+    const size_t m = clouds[k]->c->n;
+    if (!m) continue;
+    if (call->total + m > static_cast<size_t>(std::numeric_limits<int>::max())) return fail(NDT_ERR_INVALID, "more than INT_MAX points in one ray call");
+    ndt::AccRayScan sc{};
+    const float* pose = poses ? poses + 16 * k : I;
+    sc.n = static_cast<int>(m);
+    sc.first = static_cast<int>(call->total);
+    colmajor_to_T12(pose, sc.T);
+    for (int q = 0; q < 3; q++) sc.o[q] = origins ? origins[3 * k + q] : pose[12 + q];
+    call->scans.push_back(sc);
+    call->clouds.push_back(clouds[k]->c);
+    call->total += m;
+  }
+  return NDT_OK;
+}
+
+// the ONE launch over the call's points, queued; miss / hit / the totals are read behind the caller's wait
+ndt_status rays_pass(ndt_context* h, RayCall& call, const ndt_ray_spec& spec, RayPass& p) {
+  hipStream_t st = h->stream;
+  AccTarget* a = call.a;
+  h->ray_cast = h->ray_skipped = h->ray_touched = h->ray_removed = h->ray_points = h->ray_launches = 0;
+  h->ray_visited = 0;
+  h->ray_relinked = 0;
+  h->ray_kept = static_cast<size_t>(a->n_slots);
+  const size_t S = static_cast<size_t>(std::max(a->n_slots, 1));
+  for (size_t k = 0; k < call.scans.size(); k++) {
+    const ndt_status s = cloud_use_on(h, call.clouds[k].get());
+    if (s) return s;
+    call.scans[k].src = call.clouds[k]->pts.p;
+  }
+  HIP_TRY(p.w.reserve(2 * S));
+  HIP_TRY(p.counters.reserve(ndt::kAccRayCounters));
+  p.miss = p.w.p;
+  p.hit = p.w.p + S;
+  const int n_scans = static_cast<int>(call.scans.size());
+  if (n_scans > 1) {
+    const size_t bytes = call.scans.size() * sizeof(ndt::AccRayScan);
+    HIP_TRY(p.d_scans.reserve(bytes));
+    HIP_TRY(hipMemcpyAsync(p.d_scans.p, call.scans.data(), bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));  // (the table is pageable: the copy has read it)
+  }
+  HIP_TRY(hipMemsetAsync(p.w.p, 0, 2 * S * sizeof(unsigned), st));
+  HIP_TRY(hipMemsetAsync(p.counters.p, 0, ndt::kAccRayCounters * sizeof(unsigned long long), st));
+  ndt::AccCropBox box;
+  for (int k = 0; k < 3; k++) {  // the target's cell box: no voxel lies outside it (no voxel: the empty box)
+    box.lo[k] = a->n_slots ? a->grid->geom.min_b[k] : 1;
+    box.hi[k] = a->n_slots ? a->grid->geom.max_b[k] : 0;
+  }
+  int blocks = 0, passes = 0;
+  ndt::ray_plan(call.total, rays_max_blocks(), &blocks, &passes);
+  HIP_TRY(ndt::launch_acc_rays(call.scans[0], reinterpret_cast<const ndt::AccRayScan*>(p.d_scans.p), n_scans, static_cast<int>(call.total), blocks,
+                               a->resolution, spec, a->view(), box, p.miss, p.hit, p.counters.p, st));
+  h->ray_launches = 1;
+  return NDT_OK;
+}
+void rays_totals(ndt_context* h, const unsigned long long* c) {
+  h->ray_cast = static_cast<size_t>(c[0]);
+  h->ray_skipped = static_cast<size_t>(c[1]);
+  h->ray_visited = c[2];
+}
+
+ndt_status rays_clear(ndt_context* h, RayCall& call, const ndt_ray_spec& spec) {
+  hipStream_t st = h->stream;
+  AccTarget* a = call.a;
+  RayPass p;
+  ndt_status s = rays_pass(h, call, spec, p);
+  if (s) return s;
+  const int n_slots = a->n_slots;
+  unsigned long long totals[ndt::kAccRayCounters];
+  if (n_slots == 0) {  // no voxel: the rays are counted, nothing can go
+    HIP_TRY(hipMemcpyAsync(totals, p.counters.p, sizeof(totals), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    rays_totals(h, totals);
+    return NDT_OK;
+  }
+  const size_t S = static_cast<size_t>(n_slots);
+  DevBuf<unsigned> w;  // keep flags, new numbers
+  DevBuf<int> info;
+  HIP_TRY(w.reserve(2 * S));
+  HIP_TRY(acc_info_reset(info, st));
+  unsigned *keep = w.p, *number = w.p + S;
+  HIP_TRY(ndt::launch_acc_rays_mark(a->view(), n_slots, p.miss, p.hit, spec.min_rays, keep, info.p, number, st));
+  h->ray_launches += 2;
+  // ---- the one read-back
+  AccInfo seen;
+  HIP_TRY(hipMemcpyAsync(totals, p.counters.p, sizeof(totals), hipMemcpyDeviceToHost, st));
+  HIP_TRY(acc_info_read(info, st, &seen));
+  rays_totals(h, totals);
+  h->ray_touched = static_cast<size_t>(seen.word7);
+  AccRemoval r;
+  r.kept = S;
+  r.points = a->n_points;
+  s = acc_remove_unkept(h, a, seen, keep, number, &r);
+  h->ray_kept = r.kept;
+  h->ray_removed = r.removed;
+  h->ray_points = r.points;
+  h->ray_relinked = r.relinked;
+  h->ray_launches += r.launches;
+  return s;
 }
 
 }  // namespace
@@ -642,6 +816,124 @@ ndt_status ndt_diag_target_crop(ndt_handle h, size_t* kept_voxels, size_t* remov
   if (kept_points) *kept_points = h->crop_points;
   if (relinked) *relinked = h->crop_relinked;
   if (launches) *launches = h->crop_launches;
+  return NDT_OK;
+}
+
+ndt_status ndt_target_accumulate_clear_rays_clouds(ndt_handle h, const ndt_cloud* clouds, size_t n_clouds, const float* poses, const float* origins,
+                                                   const ndt_ray_spec* spec) {
+  RayCall call;
+  ndt_status s = rays_checks(h, clouds, n_clouds, poses, origins, spec, &call);
+  if (s || call.total == 0) return s;
+  s = ensure_device(h);
+  if (s) return s;
+  return rays_clear(h, call, *spec);
+}
+ndt_status ndt_target_accumulate_clear_rays(ndt_handle h, ndt_cloud cloud, const float* pose, const float* origin, const ndt_ray_spec* spec) {
+  if (!h) return fail(NDT_ERR_INVALID, "null handle");
+  if (!cloud) return fail(NDT_ERR_INVALID, "null cloud");
+  return ndt_target_accumulate_clear_rays_clouds(h, &cloud, 1, pose, origin, spec);
+}
+ndt_status ndt_target_accumulate_ray_counts(ndt_handle h, const ndt_cloud* clouds, size_t n_clouds, const float* poses, const float* origins,
+                                            const ndt_ray_spec* spec, int* cells, unsigned* misses, unsigned char* hit, size_t capacity,
+                                            size_t* n_voxels) {
+  RayCall call;
+  ndt_status s = rays_checks(h, clouds, n_clouds, poses, origins, spec, &call);
+  if (s) return s;
+  AccTarget* a = call.a;
+  const size_t V = static_cast<size_t>(a->n_slots);
+  if (n_voxels) *n_voxels = V;
+  if (!cells) return NDT_OK;
+  if (!misses || !hit) return fail(NDT_ERR_INVALID, "null output of the ray counts");
+  if (capacity < V) return fail(NDT_ERR_INVALID, "the ray counts need room for every voxel of the target");
+  if (V == 0) return NDT_OK;
+  s = ensure_device(h);
+  if (s) return s;
+  hipStream_t st = h->stream;
+  std::vector<int4> cell(V);
+  std::vector<unsigned> mh(2 * V, 0u);
+  if (call.total) {
+    RayPass p;
+    s = rays_pass(h, call, *spec, p);
+    if (s) return s;
+    unsigned long long totals[ndt::kAccRayCounters];
+    HIP_TRY(hipMemcpyAsync(mh.data(), p.w.p, 2 * V * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(totals, p.counters.p, sizeof(totals), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(cell.data(), a->cell.p, V * sizeof(int4), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    rays_totals(h, totals);
+  } else {
+    HIP_TRY(hipMemcpyAsync(cell.data(), a->cell.p, V * sizeof(int4), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  std::vector<size_t> perm(V);
+  for (size_t i = 0; i < V; i++) perm[i] = i;
+  std::sort(perm.begin(), perm.end(), [&](size_t x, size_t y) {
+    return ndt::acc_pack(cell[x].x, cell[x].y, cell[x].z) < ndt::acc_pack(cell[y].x, cell[y].y, cell[y].z);
+  });
+  size_t touched = 0, removed = 0, points = 0;
+  for (size_t o = 0; o < V; o++) {
+    const size_t q = perm[o];
+    cells[3 * o] = cell[q].x;
+    cells[3 * o + 1] = cell[q].y;
+    cells[3 * o + 2] = cell[q].z;
+    misses[o] = mh[q];
+    hit[o] = mh[V + q] ? 1 : 0;
+    touched += mh[q] >= 1u;
+    const bool goes = mh[q] >= static_cast<unsigned>(spec->min_rays) && !mh[V + q];
+    removed += goes;
+    if (!goes) points += static_cast<size_t>(cell[q].w);
+  }
+  if (call.total) {  // what a clearing would do
+    h->ray_touched = touched;
+    h->ray_removed = removed;
+    h->ray_kept = V - removed;
+    h->ray_points = points;
+  }
+  return NDT_OK;
+}
+ndt_status ndt_diag_target_clear_rays(ndt_handle h, size_t* rays_cast, size_t* rays_skipped, uint64_t* cells_visited, size_t* touched_voxels,
+                                      size_t* removed_voxels, size_t* kept_voxels, size_t* kept_points, int* relinked, size_t* launches) {
+  if (!h) return fail(NDT_ERR_INVALID, "null handle");
+  if (rays_cast) *rays_cast = h->ray_cast;
+  if (rays_skipped) *rays_skipped = h->ray_skipped;
+  if (cells_visited) *cells_visited = h->ray_visited;
+  if (touched_voxels) *touched_voxels = h->ray_touched;
+  if (removed_voxels) *removed_voxels = h->ray_removed;
+  if (kept_voxels) *kept_voxels = h->ray_kept;
+  if (kept_points) *kept_points = h->ray_points;
+  if (relinked) *relinked = h->ray_relinked;
+  if (launches) *launches = h->ray_launches;
+  return NDT_OK;
+}
+ndt_status ndt_host_ray_spec_check(const ndt_ray_spec* spec, float resolution) {
+  if (!spec) return fail(NDT_ERR_INVALID, "null ray spec");
+  if (const char* why = ndt::ray_spec_error(*spec, resolution)) return fail(NDT_ERR_INVALID, why);
+  return NDT_OK;
+}
+ndt_status ndt_host_ray_cells(const float* origin, const float* point, float resolution, float margin, int* cells, size_t capacity, size_t* n) {
+  if (!origin || !point || !n) return fail(NDT_ERR_INVALID, "bad arguments");
+  for (int k = 0; k < 3; k++)
+    if (!std::isfinite(origin[k]) || !std::isfinite(point[k])) return fail(NDT_ERR_INVALID, "the origin and the point of a ray must be finite");
+  if (!(std::isfinite(resolution) && resolution > 0.f)) return fail(NDT_ERR_INVALID, "the resolution must be finite and positive");
+  if (!(std::isfinite(margin) && margin >= 0.f)) return fail(NDT_ERR_INVALID, "a ray's margin must be finite and >= 0");
+  size_t seen = 0;
+  const long long c = ndt::ray_walk(origin, point, static_cast<double>(resolution), static_cast<double>(margin), 0.0,
+                                    std::numeric_limits<double>::infinity(), nullptr, [&](int i, int j, int k) {
+                                      if (cells && seen < capacity) {
+                                        cells[3 * seen] = i;
+                                        cells[3 * seen + 1] = j;
+                                        cells[3 * seen + 2] = k;
+                                      }
+                                      seen++;
+                                    });
+  *n = c < 0 ? 0 : static_cast<size_t>(c);
+  if (cells && seen > capacity) return fail(NDT_ERR_INVALID, "the ray visits more cells than the buffer holds");
+  return NDT_OK;
+}
+ndt_status ndt_host_ray_plan(size_t n_points, int* blocks, int* passes) {
+  if (!blocks || !passes) return fail(NDT_ERR_INVALID, "bad arguments");
+  if (n_points > static_cast<size_t>(std::numeric_limits<int>::max())) return fail(NDT_ERR_INVALID, "more than INT_MAX points in one ray call");
+  ndt::ray_plan(n_points, rays_max_blocks(), blocks, passes);
   return NDT_OK;
 }
 

@@ -506,6 +506,10 @@ struct ndt_context {
   // ... and the last ndt_target_accumulate_crop (ndt_diag_target_crop)
   size_t crop_kept = 0, crop_removed = 0, crop_points = 0, crop_launches = 0;
   int crop_relinked = 0;
+  // ... and the last ndt_target_accumulate_clear_rays* / _ray_counts that reached the device (ndt_diag_target_clear_rays)
+  size_t ray_cast = 0, ray_skipped = 0, ray_touched = 0, ray_removed = 0, ray_kept = 0, ray_points = 0, ray_launches = 0;
+  unsigned long long ray_visited = 0;
+  int ray_relinked = 0;
   // ... and the last ndt_target_accumulate_export / _save (ndt_diag_target_export)
   size_t exp_voxels = 0, exp_points = 0, exp_launches = 0;
   // the last centroid fitness call (ndt_diag_centroid_fitness): launches queued, excursion passes among them, the excursion it

@@ -521,6 +521,56 @@ class NormalDistributionsTransform:
         check(self._L.ndt_diag_target_crop(self._h, C.byref(k), C.byref(r), C.byref(p), C.byref(w), C.byref(l)))
         return dict(kept_voxels=k.value, removed_voxels=r.value, kept_points=p.value, relinked=bool(w.value), launches=l.value)
 
+    # ---- clearing by rays: drop the voxels a scan sees through (ndt_target_accumulate_clear_rays*) ----
+    def _ray_args(self, clouds, poses, origins, min_rays, margin, min_range, max_range):
+        clouds = [clouds] if isinstance(clouds, DeviceCloud) else list(clouds)
+        if not all(isinstance(c, DeviceCloud) for c in clouds):
+            raise ValueError("clouds must be DeviceCloud objects")
+        n = len(clouds)
+        if poses is not None and np.asarray(poses).ndim == 2:
+            poses = [poses]
+        if origins is not None and np.asarray(origins).ndim == 1:
+            origins = [origins]
+        P = self._poses(poses, n)
+        O = None
+        if origins is not None and n:
+            O = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1)
+            if len(O) != 3 * n:
+                raise ValueError("one origin (3 floats) per cloud")
+        spec = ray_spec(self.getResolution(), min_rays, margin, min_range, max_range)
+        arr = (C.c_void_p * max(n, 1))(*[c._c for c in clouds])
+        return arr, n, (_f(P) if P is not None else None), (_f(O) if O is not None else None), spec, (P, O)
+
+    def targetClearRays(self, clouds, poses=None, origins=None, min_rays=2, margin=None, min_range=0.0, max_range=None):
+        """Drop the voxels of the accumulated target that the scans see through (ndt_target_accumulate_clear_rays_clouds): every
+        DeviceCloud is moved by its pose (4x4, None = identity) and a ray is walked from its sensor origin (None = the pose's
+        translation) to every posed point, up to `margin` metres (None = the resolution) before it; a voxel goes when at least
+        min_rays rays of the call cross its cell and no point of the call lies in it.  max_range None: the largest the
+        resolution allows.  One DeviceCloud or a list; all clouds of a list go through one pass.  Returns targetAccumulated()."""
+        arr, n, P, O, spec, keep = self._ray_args(clouds, poses, origins, min_rays, margin, min_range, max_range)
+        check(self._L.ndt_target_accumulate_clear_rays_clouds(self._h, arr, n, P, O, C.byref(spec)))
+        return self.targetAccumulated()
+
+    def targetRayCounts(self, clouds, poses=None, origins=None, min_rays=2, margin=None, min_range=0.0, max_range=None):
+        """The ray pass of targetClearRays without the removal (ndt_target_accumulate_ray_counts): per voxel of the target, in
+        ascending key, -> dict(cells (V, 3) int32, miss (V,) uint32, hit (V,) bool).  The target is not changed."""
+        arr, n, P, O, spec, keep = self._ray_args(clouds, poses, origins, min_rays, margin, min_range, max_range)
+        V = self.targetAccumulated()["voxels"]
+        cells, miss, hit = np.zeros((V, 3), np.int32), np.zeros(V, np.uint32), np.zeros(V, np.uint8)
+        nv = C.c_size_t(0)
+        check(self._L.ndt_target_accumulate_ray_counts(self._h, arr, n, P, O, C.byref(spec), _i(cells), miss.ctypes.data_as(C.POINTER(C.c_uint)),
+                                                       hit.ctypes.data_as(C.POINTER(C.c_ubyte)), V, C.byref(nv)))
+        return dict(cells=cells[:nv.value], miss=miss[:nv.value], hit=hit[:nv.value].astype(bool))
+
+    def targetClearRaysDiag(self):
+        """What the last targetClearRays / targetRayCounts that reached the device did (ndt_diag_target_clear_rays)."""
+        z = [C.c_size_t(0) for _ in range(7)]
+        vis, rel = C.c_uint64(0), C.c_int(0)
+        check(self._L.ndt_diag_target_clear_rays(self._h, C.byref(z[0]), C.byref(z[1]), C.byref(vis), C.byref(z[2]), C.byref(z[3]), C.byref(z[4]),
+                                                 C.byref(z[5]), C.byref(rel), C.byref(z[6])))
+        return dict(rays_cast=z[0].value, rays_skipped=z[1].value, cells_visited=vis.value, touched_voxels=z[2].value, removed_voxels=z[3].value,
+                    kept_voxels=z[4].value, kept_points=z[5].value, relinked=bool(rel.value), launches=z[6].value)
+
     @staticmethod
     def _box(min_xyz, max_xyz):
         if (min_xyz is None) != (max_xyz is None):
@@ -1718,6 +1768,40 @@ def host_deskew_point(motion, xyz, t):
     p, q, u = np.ascontiguousarray(xyz, dtype=np.float32).reshape(3), np.zeros(3, dtype=np.float32), C.c_int(-1)
     check(_lib.lib().ndt_host_deskew_point(C.byref(motion), _f(p), float(t), _f(q), C.byref(u)))
     return q, bool(u.value)
+
+
+def ray_spec(resolution, min_rays=2, margin=None, min_range=0.0, max_range=None):
+    """An ndt_ray_spec: margin None = the resolution, max_range None = the largest the resolution allows (65536 cells)."""
+    res = np.float32(resolution)
+    return _lib.RaySpec(float(min_range), float(np.float32(65536.0) * res if max_range is None else max_range),
+                        float(res if margin is None else margin), int(min_rays))
+
+
+def ray_spec_check(resolution, min_rays=2, margin=None, min_range=0.0, max_range=None):
+    """Whether the spec is valid for a target of this resolution (ndt_host_ray_spec_check) -> (ok, message)."""
+    spec = ray_spec(resolution, min_rays, margin, min_range, max_range)
+    st = _lib.lib().ndt_host_ray_spec_check(C.byref(spec), float(resolution))
+    return st == _lib.NDT_OK, ("" if st == _lib.NDT_OK else _lib.lib().ndt_last_error().decode("utf-8", "replace"))
+
+
+def ray_cells(origin, point, resolution, margin=0.0, capacity=None):
+    """The cells one ray visits, walked by the body the kernel uses (ndt_host_ray_cells; no range test) -> (n, 3) int32; a ray
+    that is not cast gives (0, 3)."""
+    o, p = (np.ascontiguousarray(v, dtype=np.float32).reshape(3) for v in (origin, point))
+    n = C.c_size_t(0)
+    if capacity is None:
+        check(_lib.lib().ndt_host_ray_cells(_f(o), _f(p), float(resolution), float(margin), None, 0, C.byref(n)))
+        capacity = n.value
+    cells = np.zeros((max(int(capacity), 1), 3), np.int32)
+    check(_lib.lib().ndt_host_ray_cells(_f(o), _f(p), float(resolution), float(margin), _i(cells), int(capacity), C.byref(n)))
+    return cells[:n.value]
+
+
+def host_ray_plan(n):
+    """(blocks, passes) of the ray kernel over the n points of a call (ndt_host_ray_plan)."""
+    b, p = C.c_int(0), C.c_int(0)
+    check(_lib.lib().ndt_host_ray_plan(int(n), C.byref(b), C.byref(p)))
+    return b.value, p.value
 
 
 def host_deskew_plan(n):
