@@ -22,7 +22,7 @@
 // after the other, 2.7 ms overlapped, 3.7 ms overlapped on CU partitions -- the steps are short host-paced sequences of
 // pageable copies and small launches, and two threads driving them get in each other's way; hence not the default.
 //
-//   map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--deskew <field>] [--range <min> <max>] [--outliers-radius <r> <min_neighbors>] [--outliers-stat <mean_k> <stddev_mul>] [--reject-unexplained <L>] [--clear-rays <min_rays> <margin>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> [voxel_leaf_size (0.5 | 0.3)] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]
+//   map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--deskew <field>] [--range <min> <max>] [--outliers-radius <r> <min_neighbors>] [--outliers-stat <mean_k> <stddev_mul>] [--ground <threshold> <hypotheses> <eps_deg> [--ground-remove]] [--reject-unexplained <L>] [--clear-rays <min_rays> <margin>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> [voxel_leaf_size (0.5 | 0.3)] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]
 // ("host": the serial loop with every cloud passing through host buffers, as in rounds 1-3; the default keeps them in HBM)
 //
 // --scan-to-map (anywhere on the line; the node's loop with clouds resident in HBM): every scan after the first is registered
@@ -65,6 +65,11 @@
 // --outliers-radius <r> <min_neighbors> / --outliers-stat <mean_k> <stddev_mul> (with --scan-to-map): every raw scan goes through
 // ndt_cloud_remove_outliers on the device, after --range and before its prefilter -- stray returns do not become one-point
 // voxels -- and "outliers removed: <n - k>/<n>" is printed per scan (with both: the radius filter first).
+// --ground <threshold> <hypotheses> <eps_deg> [--ground-remove] (with --scan-to-map): after --deskew, --range and --outliers-* and
+// before its prefilter, the ground plane of every raw scan is found on the device (ndt_cloud_segment_plane: RANSAC over
+// <hypotheses> hypotheses with the distance threshold <threshold>, seed 0, only planes whose normal lies within <eps_deg> degrees
+// of (0, 0, 1) in the sensor frame, no refinement) and "ground: <inliers>/<n> normal <a> <b> <c> d <d>" is printed per scan; with
+// --ground-remove the scan goes on without its inliers (and without the rows that are not finite).
 // --reject-unexplained <L> (with --scan-to-map, not with --localize, which accumulates nothing): after each registration the
 // scan is accumulated as ndt_source_select_by_nvtl(h, NULL, L, 1, ...) -- its points whose nearest-voxel likelihood at the
 // registered pose is at least L, and those no voxel is near (new ground) -- instead of as the whole scan, so that moving objects
@@ -185,6 +190,8 @@ struct Node {
   float range_min = 0, range_max = 0;
   bool outliers_radius = false, outliers_stat = false;  // --outliers-radius / --outliers-stat: every raw scan loses its outliers before its prefilter
   ndt_outlier_spec radius_spec{}, stat_spec{};
+  bool ground = false, ground_remove = false;  // --ground: every raw scan's ground plane is found (and with --ground-remove dropped) before its prefilter
+  ndt_plane_spec ground_spec{};
   std::string deskew_field;  // --deskew: every raw scan is motion-compensated by this field of its file, first of all
   std::string directory;
   bool reject = false;       // --reject-unexplained: a registered scan is accumulated without the points the target does not explain
@@ -402,6 +409,19 @@ static int run_resident(Node& node, ndt_pcd_sequence_handle seq, float voxel_lea
         r.view = cleaned;
         r.n = kept;
         r.dense = 1;
+      }
+      if (node.ground) {
+        ndt_plane_result plane{};
+        ndt_cloud rest = nullptr;
+        CHECK(ndt_cloud_segment_plane(h, r.view, &node.ground_spec, nullptr, &plane, nullptr, node.ground_remove ? &rest : nullptr));
+        std::printf("ground: %zu/%zu normal %.9g %.9g %.9g d %.9g\n", plane.n_inliers, r.n, plane.coeff[0], plane.coeff[1], plane.coeff[2],
+                    plane.coeff[3]);
+        if (node.ground_remove) {  // what is left holds finite points only
+          ndt_cloud_release(r.view);
+          r.view = rest;
+          r.n = plane.n_finite - plane.n_inliers;
+          r.dense = 1;
+        }
       }
       CHECK(ndt_cloud_voxel_filter_begin(h, r.view, r.dense, voxel_leaf_size));
       node.t_filter += since(t0);
@@ -761,12 +781,14 @@ int main(int argc, char** argv) {
   ndt_ray_spec ray_spec{};
   double gicp_gate = 5.0;
   ndt_outlier_spec radius_spec{}, stat_spec{};
+  bool ground = false, ground_remove = false, bad_ground = false;
+  ndt_plane_spec ground_spec{};
   float window = 0, range_min = 0, range_max = 0;
   double reject_below = 0;
   const char *save_target = nullptr, *load_target = nullptr, *deskew_field = nullptr;
   bool bad_deskew = false;
   static const char kUsage[] =
-      "usage: map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--gicp [--gicp-gate <m>]] [--deskew <field>] [--range <min> <max>] [--outliers-radius <r> <min_neighbors>] [--outliers-stat <mean_k> <stddev_mul>] [--reject-unexplained <L>] [--clear-rays <min_rays> <margin>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> "
+      "usage: map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--gicp [--gicp-gate <m>]] [--deskew <field>] [--range <min> <max>] [--outliers-radius <r> <min_neighbors>] [--outliers-stat <mean_k> <stddev_mul>] [--ground <threshold> <hypotheses> <eps_deg> [--ground-remove]] [--reject-unexplained <L>] [--clear-rays <min_rays> <margin>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> "
       "[voxel_leaf_size] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]\n";
   {  // the switches are taken out of the line before the positional arguments are read
     int kept = 1;
@@ -821,6 +843,22 @@ int main(int argc, char** argv) {
           spec.stddev_mul = std::atof(argv[++i]);
         }
         bad_outliers = bad_outliers || ndt_host_outlier_spec_check(&spec) != NDT_OK;
+      } else if (std::strcmp(argv[i], "--ground") == 0) {
+        ground = true;
+        bad_ground = i + 3 >= argc;
+        if (!bad_ground) {
+          ground_spec.distance_threshold = static_cast<float>(std::atof(argv[++i]));
+          ground_spec.n_hypotheses = std::atoi(argv[++i]);
+          const double eps_deg = std::atof(argv[++i]);
+          ground_spec.eps_angle = static_cast<float>(eps_deg * 3.14159265358979323846 / 180.0);
+          if (eps_deg <= 90.0 && static_cast<double>(ground_spec.eps_angle) > 1.5707963267948966)  // (90 degrees round up in f32)
+            ground_spec.eps_angle = std::nextafterf(ground_spec.eps_angle, 0.0f);
+          ground_spec.use_axis = 1;
+          ground_spec.axis[2] = 1.0f;
+          bad_ground = ndt_host_plane_spec_check(&ground_spec) != NDT_OK;
+        }
+      } else if (std::strcmp(argv[i], "--ground-remove") == 0) {
+        ground_remove = true;
       } else if (std::strcmp(argv[i], "--clear-rays") == 0) {
         clear_rays = true;
         bad_clear = i + 2 >= argc;
@@ -873,6 +911,11 @@ int main(int argc, char** argv) {
                          "go with --scan-to-map\n%s", kUsage);
     return 2;
   }
+  if (bad_ground || (ground && !scan_to_map) || (ground_remove && !ground)) {
+    std::fprintf(stderr, "--ground <threshold> <hypotheses> <eps_deg> (threshold > 0, hypotheses 1 ... 65536, 0 <= eps_deg <= 90) goes with "
+                         "--scan-to-map and --ground-remove with --ground\n%s", kUsage);
+    return 2;
+  }
   if (bad_gate || (have_gate && !use_gicp) || (use_gicp && (!scan_to_map || nvtl || covariance || reject))) {
     std::fprintf(stderr, "--gicp goes with --scan-to-map and --gicp-gate <m> (m > 0) with --gicp; --nvtl, --covariance and --reject-unexplained "
                          "read the NDT registration's result, so they do not go with --gicp\n%s", kUsage);
@@ -902,6 +945,9 @@ int main(int argc, char** argv) {
   node.outliers_stat = outliers_stat;
   node.radius_spec = radius_spec;
   node.stat_spec = stat_spec;
+  node.ground = ground;
+  node.ground_remove = ground_remove;
+  node.ground_spec = ground_spec;
   if (deskew_field) node.deskew_field = deskew_field;
   node.directory = argv[1];
   node.reject = reject;

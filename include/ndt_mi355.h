@@ -520,6 +520,109 @@ ndt_status ndt_diag_outliers(ndt_handle h, size_t* index_builds, size_t* value_l
 ndt_status ndt_host_outlier_spec_check(const ndt_outlier_spec* spec);
 ndt_status ndt_host_outlier_plan(size_t n_points, int* blocks, int* queries_per_block);
 
+/* ---- the plane of a resident cloud: RANSAC segmentation (the ground of a scan) ------------------------------------------
+ * Modelled on pcl::SACSegmentation with SACMODEL_PLANE / SACMODEL_PERPENDICULAR_PLANE followed by pcl::ExtractIndices.  PCL's
+ * RNG and its probabilistic early exit are not reproducible: NO bit parity with PCL is claimed, the definitions below are the
+ * contract (ONE set of functions for host and device, toyslam_amd/csrc/ndt_plane.hpp).  All arithmetic is f64, every
+ * operation rounded on its own (no fused multiply-add); coordinates are the stored f32 values widened.
+ *   sample   the three indices of hypothesis h over a cloud of n points: idx_j = splitmix64(seed + 3 h + j) mod n, j = 0, 1, 2,
+ *            with z = x + 0x9e3779b97f4a7c15; z = (z ^ z >> 30) * 0xbf58476d1ce4e5b9; z = (z ^ z >> 27) * 0x94d049bb133111eb;
+ *            splitmix64(x) = z ^ z >> 31 (u64 arithmetic).  A caller may pass its own triples instead: 3 * n_hypotheses int32
+ *            in host memory; an index outside [0, n) makes the call NDT_ERR_INVALID.
+ *   model    of a triple (a, b, c): u = b - a, v = c - a, m = u x v, len2 = (mx*mx + my*my) + mz*mz, uu and vv summed in the
+ *            same order.  DEGENERATE (state 1, coefficients 0): two of the three indices equal, a point that is not finite,
+ *            or !(len2 > 1e-8 * (uu * vv)).  Otherwise n = m / sqrt(len2), oriented: with an axis, a^ = axis / |axis| and
+ *            cos_eps = cos((double)eps_angle) computed once on the host in f64, n is flipped so that n . a^ >= 0 and the
+ *            hypothesis is REJECTED (state 2; its coefficients are still reported) unless n . a^ >= cos_eps; without an axis n
+ *            is flipped so that its last non-zero component in the order z, y, x is positive.  d = -((nx*ax + ny*ay) + nz*az)
+ *            with the oriented n.  A cloud of fewer than 3 points has only degenerate hypotheses.
+ *   distance s = ((nx*px + ny*py) + nz*pz) + d; a point is an inlier iff -T <= s && s <= T, T = (double)distance_threshold.  A
+ *            point that is not finite gives a NaN or infinite s and is never an inlier.
+ *   choice   count(h) = the inliers of a VALID hypothesis (state 0), 0 for the others.  The best hypothesis is the valid one
+ *            with the largest count, the lowest h among equals.  There is no early exit: every hypothesis is scored, the
+ *            result is a pure function of (cloud, spec, triples).  No valid hypothesis: found = 0, best = -1, the coefficients
+ *            are 0, the inlier cloud is empty and the other cloud holds every finite point (their keys are +inf).
+ *   refine   (refine != 0 and found)  I = the inliers of the best plane, a = its first sample point, q = p - a;
+ *            S1 = sum q (3 sums), S2 = sum q q^T (6 sums) over I -- on the device per block of 256 threads over a contiguous
+ *            chunk (4096 points; beyond 64 blocks the chunk grows), a fixed tree per block, the blocks' rows added in block
+ *            order on the host: deterministic, no floating-point atomics.  Covariance S2/|I| - (S1/|I|)(S1/|I|)^T; the normal
+ *            is the eigenvector of its smallest eigenvalue (cyclic Jacobi in f64, ndt_host_plane_fit), oriented as above;
+ *            d = -n . (a + S1/|I|).  The fit is taken when |I| >= 3, every number is finite and lambda_mid > 1e-12 lambda_max;
+ *            otherwise the unrefined plane stays and refined = 0.  The angle test is not repeated.  The inliers are then
+ *            those of the refined plane.
+ * An invalid spec (NDT_ERR_INVALID before any device work): a distance_threshold that is not finite or <= 0, n_hypotheses
+ * outside 1 ... 65 536, use_axis or refine other than 0 / 1, with use_axis an axis that is not finite or all zero or an
+ * eps_angle outside 0 ... pi/2. */
+typedef struct {
+  float distance_threshold;
+  int n_hypotheses;
+  uint64_t seed;
+  int use_axis;
+  float axis[3];
+  float eps_angle; /* radians */
+  int refine;
+} ndt_plane_spec;
+typedef struct {
+  int found, refined;
+  double coeff[4];              /* nx, ny, nz, d of the plane the inliers were taken against */
+  int best;                     /* the chosen hypothesis, -1 without one */
+  size_t best_count, n_inliers; /* n_inliers == best_count without refinement */
+  size_t n_finite, n_degenerate, n_rejected;
+} ndt_plane_result;
+/* - ndt_cloud_plane_counts: per hypothesis its model (coeffs: 4 * n_hypotheses doubles, may be NULL), its state (states:
+ *   n_hypotheses int32, may be NULL) and its count (counts: n_hypotheses uint32), all host memory.  It changes nothing.
+ * - ndt_cloud_segment_plane: *result as defined; *inliers and *others (either may be NULL: that cloud is not made) are new
+ *   clouds of their own produced by the compaction of ndt_cloud_select with the signed distances as device-resident keys --
+ *   KEY over [-T, T] gives the inliers, KEY | KEY_NEGATE | FINITE the others -- with that call's promises: records in in's
+ *   order, all four words kept, exact boxes (bit for bit what ndt_cloud_upload of the host-selected rows gives), nothing kept
+ *   gives an empty cloud, never NULL.  Rows that are not finite are in neither cloud.  The keys never visit the host.
+ * - ndt_cloud_segment_plane_clouds: every cloud gets its own plane; triples always come from the sampler.  One model launch,
+ *   one count launch, one choice launch, one key launch (with refinement one sums launch more) and two selection launches per
+ *   kind of output cloud in all, whatever n_clouds.  results[k], inliers[k], others[k] are the same bits as the single call
+ *   for cloud k alone, whatever the other clouds and their order.  n_clouds == 0 is NDT_OK, touches nothing and needs no
+ *   device.  On any error every output cloud is NULL.
+ * - ndt_cloud_plane_distances: s of every point of `in` under coeff into values (n_in doubles: host memory, or device memory
+ *   with values_on_device != 0); a row that is not finite gives NaN.  The height above the ground, ready for a KEY selection
+ *   of a height band.  A coeff that is not finite or has a zero normal is NDT_ERR_INVALID.
+ * - ndt_diag_plane, of the last of the four calls above that reached the device: the plane kernels launched (counts: model,
+ *   count, choice = 3; segmentation: + keys = 4, with a refinement that was asked for + sums = 5; distances: 1; when no
+ *   cloud has a point the model and the choice launch alone = 2, distances: 0), the launches of the selections behind them
+ *   (2 per kind of output cloud asked for, 0 when no cloud has a point), the blocks of the count launch, and the clouds.
+ * None of them changes the handle's target, source, grid, last result, statistics, map, a begun
+ * ndt_cloud_voxel_filter_begin, the pairs state or what ndt_diag_select / ndt_diag_outliers report.
+ * NDT_ERR_INVALID before any device work, outputs untouched apart from the output clouds = NULL: a NULL handle, in, spec,
+ * result(s), counts, coeff or values, an invalid spec, a triple index outside the cloud, a NULL entry of in, more than 65 535
+ * clouds, a cloud of another device, more than INT_MAX points.  After those checks NDT_ERR_NO_DEVICE without a gfx950 device.
+ * Development switches: NDT_PLANE_MAX_BLOCKS caps the count blocks a cloud gets, NDT_PLANE_MERGE=rows makes the count blocks
+ * write partial rows that the choice launch sums in order instead of one integer atomic per lane (both read at every call;
+ * no result depends on either). */
+ndt_status ndt_cloud_plane_counts(ndt_handle h, ndt_cloud in, const ndt_plane_spec* spec, const int32_t* triples /* or NULL */,
+                                  double* coeffs /* 4 * n_hypotheses or NULL */, int32_t* states /* n_hypotheses or NULL */,
+                                  uint32_t* counts /* n_hypotheses */);
+ndt_status ndt_cloud_segment_plane(ndt_handle h, ndt_cloud in, const ndt_plane_spec* spec, const int32_t* triples /* or NULL */,
+                                   ndt_plane_result* result, ndt_cloud* inliers /* or NULL */, ndt_cloud* others /* or NULL */);
+ndt_status ndt_cloud_segment_plane_clouds(ndt_handle h, const ndt_cloud* in, size_t n_clouds, const ndt_plane_spec* spec,
+                                          ndt_plane_result* results /* n_clouds */, ndt_cloud* inliers /* n_clouds or NULL */,
+                                          ndt_cloud* others /* n_clouds or NULL */);
+ndt_status ndt_cloud_plane_distances(ndt_handle h, ndt_cloud in, const double coeff[4],
+                                     double* values /* n_in; host, or device with values_on_device */, int values_on_device);
+ndt_status ndt_diag_plane(ndt_handle h, size_t* launches, size_t* select_launches, size_t* count_blocks, size_t* clouds);
+/* Host only, no device: the validity of a spec; the sample (idx[3]; NDT_ERR_INVALID for n_points == 0 or h < 0); the model of
+ * three points under a spec (*state 0 / 1 / 2, coeff[4]); the signed distance; the fit of the refinement from count, S1[3],
+ * S2[6] (xx, xy, xz, yy, yz, zz) and a[3] (*taken = 0: refused, coeff untouched; lambda[3], may be NULL: the eigenvalues in
+ * ascending order); and the count kernel's grid for a cloud of n_points -- tiles of *tile_points points x blocks of
+ * *hyp_per_block hypotheses (256 threads, a lane per hypothesis), one block per pair up to 4096 blocks (NDT_PLANE_MAX_BLOCKS:
+ * fewer), beyond which *tile_blocks < *tiles and the blocks stride over the tiles; the grid is *tile_blocks * *hyp_blocks. */
+ndt_status ndt_host_plane_spec_check(const ndt_plane_spec* spec);
+ndt_status ndt_host_plane_sample(uint64_t seed, int h, size_t n_points, int32_t idx[3]);
+ndt_status ndt_host_plane_model(const ndt_plane_spec* spec, const float a[3], const float b[3], const float c[3], int same_index,
+                                double coeff[4], int* state);
+ndt_status ndt_host_plane_distance(const double coeff[4], const float xyz[3], double* s);
+ndt_status ndt_host_plane_fit(const ndt_plane_spec* spec, double count, const double S1[3], const double S2[6], const double a[3],
+                              double coeff[4], double* lambda /* 3 or NULL */, int* taken);
+ndt_status ndt_host_plane_plan(size_t n_points, int n_hypotheses, int* tile_points, int* hyp_per_block, int* tiles, int* hyp_blocks,
+                               int* tile_blocks);
+
 /* ---- accumulating target: posed scans merged into the voxel grid (scan-to-MAP registration) --------------------------
  * Every other target of this library is built from ONE cloud; a mapping node that wants to register a scan against the map
  * would have to keep every posed point and rebuild the grid from the growing concatenation before each scan.  Here the

@@ -60,6 +60,18 @@ class OutlierStats(C.Structure):
                 ("threshold", C.c_double)]
 
 
+class PlaneSpec(C.Structure):
+    """ndt_plane_spec (include/ndt_mi355.h)"""
+    _fields_ = [("distance_threshold", C.c_float), ("n_hypotheses", C.c_int), ("seed", C.c_uint64), ("use_axis", C.c_int),
+                ("axis", C.c_float * 3), ("eps_angle", C.c_float), ("refine", C.c_int)]
+
+
+class PlaneResult(C.Structure):
+    """ndt_plane_result (include/ndt_mi355.h)"""
+    _fields_ = [("found", C.c_int), ("refined", C.c_int), ("coeff", C.c_double * 4), ("best", C.c_int), ("best_count", C.c_size_t),
+                ("n_inliers", C.c_size_t), ("n_finite", C.c_size_t), ("n_degenerate", C.c_size_t), ("n_rejected", C.c_size_t)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
 EVAL_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_double),
                       C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double))
@@ -226,6 +238,20 @@ SIGNATURES = {
     "ndt_diag_outliers": (C.c_int, [vp, szp, szp, szp, szp]),
     "ndt_host_outlier_spec_check": (C.c_int, [C.POINTER(OutlierSpec)]),
     "ndt_host_outlier_plan": (C.c_int, [C.c_size_t, ip, ip]),
+    "ndt_cloud_plane_counts": (C.c_int, [vp, vp, C.POINTER(PlaneSpec), C.POINTER(C.c_int32), dp, C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_uint32)]),
+    "ndt_cloud_segment_plane": (C.c_int, [vp, vp, C.POINTER(PlaneSpec), C.POINTER(C.c_int32), C.POINTER(PlaneResult), C.POINTER(vp),
+                                          C.POINTER(vp)]),
+    "ndt_cloud_segment_plane_clouds": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, C.POINTER(PlaneSpec), C.POINTER(PlaneResult),
+                                                 C.POINTER(vp), C.POINTER(vp)]),
+    "ndt_cloud_plane_distances": (C.c_int, [vp, vp, dp, vp, C.c_int]),
+    "ndt_diag_plane": (C.c_int, [vp, szp, szp, szp, szp]),
+    "ndt_host_plane_spec_check": (C.c_int, [C.POINTER(PlaneSpec)]),
+    "ndt_host_plane_sample": (C.c_int, [C.c_uint64, C.c_int, C.c_size_t, C.POINTER(C.c_int32)]),
+    "ndt_host_plane_model": (C.c_int, [C.POINTER(PlaneSpec), fp, fp, fp, C.c_int, dp, ip]),
+    "ndt_host_plane_distance": (C.c_int, [dp, fp, dp]),
+    "ndt_host_plane_fit": (C.c_int, [C.POINTER(PlaneSpec), C.c_double, dp, dp, dp, dp, dp, ip]),
+    "ndt_host_plane_plan": (C.c_int, [C.c_size_t, C.c_int, ip, ip, ip, ip, ip]),
     "ndt_pose_covariance": (C.c_int, [vp, fp, C.c_int, C.c_double, dp, vp]),
     "ndt_pairs_pose_covariances": (C.c_int, [vp, fp, C.c_int, C.c_double, dp, vp]),
     "ndt_host_pose_covariance": (C.c_int, [dp, dp, dp, C.c_size_t, C.c_int, C.c_double, dp, dp, dp, ip]),

@@ -1082,6 +1082,76 @@ class NormalDistributionsTransform:
         """Is the _lib.OutlierSpec valid?  (ndt_host_outlier_spec_check; host only.)"""
         return _lib.lib().ndt_host_outlier_spec_check(C.byref(spec)) == _lib.NDT_OK
 
+    # ---- the plane of resident clouds (ndt_cloud_plane_counts / ndt_cloud_segment_plane / _clouds / _plane_distances) ------
+    @staticmethod
+    def _plane_result(r):
+        return dict(found=bool(r.found), refined=bool(r.refined), coeff=np.array(list(r.coeff), dtype=np.float64), best=r.best,
+                    best_count=r.best_count, n_inliers=r.n_inliers, n_finite=r.n_finite, n_degenerate=r.n_degenerate,
+                    n_rejected=r.n_rejected)
+
+    @staticmethod
+    def _plane_triples(triples, spec):
+        if triples is None:
+            return None, None
+        t = np.ascontiguousarray(triples, dtype=np.int32).reshape(-1)
+        if t.size != 3 * spec.n_hypotheses:
+            raise ValueError("triples must hold 3 * n_hypotheses indices")
+        return t, t.ctypes.data_as(C.POINTER(C.c_int32))
+
+    def planeCounts(self, dc, spec, triples=None):
+        """Every plane hypothesis of the resident cloud `dc` under the _lib.PlaneSpec (plane_spec(...)), scored against all its
+        points (ndt_cloud_plane_counts; defined in include/ndt_mi355.h).  triples: (n_hypotheses, 3) int32 of the caller's own
+        in place of the sampler's.  -> (coeffs (H, 4) float64, states (H,) int32: 0 valid, 1 degenerate, 2 rejected,
+        counts (H,) uint32)."""
+        H = spec.n_hypotheses
+        keep, tp = self._plane_triples(triples, spec)
+        co, st, cn = np.zeros((max(H, 1), 4), dtype=np.float64), np.zeros(max(H, 1), dtype=np.int32), np.zeros(max(H, 1), dtype=np.uint32)
+        check(self._L.ndt_cloud_plane_counts(self._h, dc._c, C.byref(spec), tp, _d(co), st.ctypes.data_as(C.POINTER(C.c_int32)),
+                                             cn.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return co[:H], st[:H], cn[:H]
+
+    def segmentPlane(self, dc, spec, triples=None, inliers=True, others=True):
+        """The dominant plane of the resident cloud `dc` by RANSAC over spec.n_hypotheses hypotheses, every one scored
+        (ndt_cloud_segment_plane).  -> (result dict, DeviceCloud of the inliers or None, DeviceCloud of the other finite points
+        or None), both in dc's order with exact boxes; the signed distances stay on the device."""
+        keep, tp = self._plane_triples(triples, spec)
+        r, ci, co = _lib.PlaneResult(), C.c_void_p(None), C.c_void_p(None)
+        check(self._L.ndt_cloud_segment_plane(self._h, dc._c, C.byref(spec), tp, C.byref(r), C.byref(ci) if inliers else None,
+                                              C.byref(co) if others else None))
+        return self._plane_result(r), DeviceCloud(self, ci) if inliers else None, DeviceCloud(self, co) if others else None
+
+    def segmentPlaneClouds(self, clouds, spec, inliers=True, others=True):
+        """segmentPlane of every DeviceCloud of the list under one spec, every cloud its own plane, in one model launch, one
+        count launch and the selection's launches in all (ndt_cloud_segment_plane_clouds).  -> (list of result dicts, list of
+        inlier clouds or None, list of other clouds or None), entry k what segmentPlane gives for clouds[k] alone."""
+        clouds = list(clouds)
+        n = len(clouds)
+        arr = (C.c_void_p * max(n, 1))(*[c._c for c in clouds])
+        res = (_lib.PlaneResult * max(n, 1))()
+        oi, oo = (C.c_void_p * max(n, 1))(), (C.c_void_p * max(n, 1))()
+        check(self._L.ndt_cloud_segment_plane_clouds(self._h, arr, n, C.byref(spec), res, oi if inliers else None, oo if others else None))
+        wrap = lambda out: [DeviceCloud(self, C.c_void_p(p)) for p in list(out)[:n]]
+        return [self._plane_result(res[k]) for k in range(n)], wrap(oi) if inliers else None, wrap(oo) if others else None
+
+    def planeDistances(self, dc, coeff, device=False):
+        """The signed distance of every point of the resident cloud `dc` from the plane coeff = (nx, ny, nz, d) -- the height
+        above a ground plane (ndt_cloud_plane_distances); NaN for a point that is not finite.  -> (n,) float64.  device: the
+        address (an int) of n float64 on the handle's device, which then receives the values: -> that address."""
+        c = np.ascontiguousarray(coeff, dtype=np.float64).reshape(4)
+        n = len(dc)
+        if device is not False and device is not None:
+            check(self._L.ndt_cloud_plane_distances(self._h, dc._c, _d(c), C.c_void_p(int(device)), 1))
+            return int(device)
+        out = np.zeros(max(n, 1), dtype=np.float64)
+        check(self._L.ndt_cloud_plane_distances(self._h, dc._c, _d(c), C.c_void_p(out.ctypes.data), 0))
+        return out[:n].copy()
+
+    def planeDiag(self):
+        """What the last plane call that reached the device did (ndt_diag_plane)."""
+        a, b, c, d = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        check(self._L.ndt_diag_plane(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return dict(launches=a.value, select_launches=b.value, count_blocks=c.value, clouds=d.value)
+
     # ---- pose covariance (ndt_pose_covariance / ndt_pairs_pose_covariances) ----------------------------------------------
     def poseCovariance(self, transform=None, method="sandwich", scale=1.0, info=False):
         """6x6 covariance of the pose x y z roll pitch yaw of the input source at `transform` (None: the last align's final
@@ -1802,6 +1872,62 @@ def host_ray_plan(n):
     b, p = C.c_int(0), C.c_int(0)
     check(_lib.lib().ndt_host_ray_plan(int(n), C.byref(b), C.byref(p)))
     return b.value, p.value
+
+
+def plane_spec(distance_threshold, n_hypotheses, seed=0, axis=None, eps_angle=0.0, refine=False):
+    """An ndt_plane_spec: axis None = any plane; else only planes whose normal lies within eps_angle (radians) of the axis."""
+    s = _lib.PlaneSpec()
+    s.distance_threshold, s.n_hypotheses, s.seed = float(np.float32(distance_threshold)), int(n_hypotheses), int(seed) & (2**64 - 1)
+    s.use_axis, s.refine = int(axis is not None), int(bool(refine))
+    if axis is not None:
+        s.axis[0], s.axis[1], s.axis[2] = (float(np.float32(v)) for v in axis)
+        s.eps_angle = float(np.float32(eps_angle))
+    return s
+
+
+def plane_spec_check(spec):
+    """Is the _lib.PlaneSpec valid?  (ndt_host_plane_spec_check)"""
+    return _lib.lib().ndt_host_plane_spec_check(C.byref(spec)) == _lib.NDT_OK
+
+
+def host_plane_sample(seed, h, n):
+    """The three point indices of hypothesis h over a cloud of n points (ndt_host_plane_sample) -> (3,) int32."""
+    idx = np.zeros(3, dtype=np.int32)
+    check(_lib.lib().ndt_host_plane_sample(int(seed) & (2**64 - 1), int(h), int(n), idx.ctypes.data_as(C.POINTER(C.c_int32))))
+    return idx
+
+
+def host_plane_model(spec, a, b, c, same_index=False):
+    """The model of the triple (a, b, c) under the spec (ndt_host_plane_model, the function the kernel calls)
+    -> ((4,) float64, state: 0 valid, 1 degenerate, 2 rejected)."""
+    pa, pb, pc = (np.ascontiguousarray(v, dtype=np.float32).reshape(3) for v in (a, b, c))
+    co, st = np.zeros(4, dtype=np.float64), C.c_int(-1)
+    check(_lib.lib().ndt_host_plane_model(C.byref(spec), _f(pa), _f(pb), _f(pc), int(bool(same_index)), _d(co), C.byref(st)))
+    return co, st.value
+
+
+def host_plane_distance(coeff, xyz):
+    """The signed distance of the f32 point xyz from the plane coeff (ndt_host_plane_distance)."""
+    c, p, s = np.ascontiguousarray(coeff, dtype=np.float64).reshape(4), np.ascontiguousarray(xyz, dtype=np.float32).reshape(3), C.c_double(0.0)
+    check(_lib.lib().ndt_host_plane_distance(_d(c), _f(p), C.byref(s)))
+    return s.value
+
+
+def host_plane_fit(spec, count, S1, S2, a):
+    """The fit of the refinement from the inliers' sums about a (ndt_host_plane_fit): S1 = sum q, S2 = sum q q^T as
+    (xx, xy, xz, yy, yz, zz).  -> (taken, (4,) float64 coefficients, (3,) ascending eigenvalues)."""
+    s1, s2, aa = (np.ascontiguousarray(v, dtype=np.float64).reshape(k) for v, k in ((S1, 3), (S2, 6), (a, 3)))
+    co, lam, tk = np.zeros(4, dtype=np.float64), np.zeros(3, dtype=np.float64), C.c_int(-1)
+    check(_lib.lib().ndt_host_plane_fit(C.byref(spec), float(count), _d(s1), _d(s2), _d(aa), _d(co), _d(lam), C.byref(tk)))
+    return bool(tk.value), co, lam
+
+
+def host_plane_plan(n, n_hypotheses):
+    """The count kernel's grid over a cloud of n points (ndt_host_plane_plan)
+    -> dict(tile_points, hyp_per_block, tiles, hyp_blocks, tile_blocks); the grid is tile_blocks * hyp_blocks."""
+    v = [C.c_int(0) for _ in range(5)]
+    check(_lib.lib().ndt_host_plane_plan(int(n), int(n_hypotheses), *[C.byref(x) for x in v]))
+    return dict(zip(("tile_points", "hyp_per_block", "tiles", "hyp_blocks", "tile_blocks"), (x.value for x in v)))
 
 
 def host_deskew_plan(n):
