@@ -30,6 +30,14 @@ using namespace ndt;
 namespace {
 
 constexpr int kKnnBlock = 64;   // one wave = 8 query teams per block
+static_assert(kKnnBlock == kTeamsPerWave * kTeam, "team_knn: one wave per block");
+
+// computeCovariances' neighbours (ndt_search.hpp team_knn): the k nearest in (distance, point index) order, the query --
+// a point of the cloud -- among them
+struct KnnOrdered {
+  static constexpr bool kPositions = true, kDropSelf = false, kCountScans = false;
+  static constexpr float kClear = 1.0f;
+};
 
 // The work of ONE block of a kNN / covariance grid, shared by k_knn_covariances (one cloud per launch) and
 // k_knn_covariances_multi (many clouds per launch): block `block` of the `n_blocks` that cut cloud `ix`, eight queries per
@@ -39,186 +47,24 @@ __device__ __forceinline__ void knn_covariances_block(const PointIndex& ix, int 
                                                       double* __restrict__ cov6, int* __restrict__ nn_idx,
                                                       float* __restrict__ nn_d2) {
 #pragma clang fp contract(off)
-  // One candidate list PER TEAM (k entries, unordered, its worst entry tracked), not one per lane: an eighth of the
-  // LDS (the per-lane lists capped the kernel at 3.5 waves per SIMD) and a bound every lane prunes with.  A candidate
-  // that beats the worst entry replaces it and the team finds the new worst together; order is established once, at the
-  // end, by a rank sort.  Entries are POSITIONS in the cell order; the point index behind one is looked up only when
-  // two distances are equal (the tie rule is on the index) and at the end.
-  constexpr int kTeams = kKnnBlock / kTeam;
   extern __shared__ unsigned char knn_lds[];
-  const int lane = threadIdx.x, sub = lane & (kTeam - 1), team = lane / kTeam, team_base = lane & ~(kTeam - 1);
-  float* ld = reinterpret_cast<float*>(knn_lds) + team * k;                    // [8][k] distances
-  int* lp = reinterpret_cast<int*>(knn_lds) + kTeams * k + team * k;           // [8][k] positions
-  int* ordered = reinterpret_cast<int*>(knn_lds) + 2 * kTeams * k + team * k;  // [8][k] point indices, ascending (distance, index)
-  const float leaf = fminf(ix.geom.leaf[0], fminf(ix.geom.leaf[1], ix.geom.leaf[2]));
-  const int r_lim = max(ix.geom.div_b[0], max(ix.geom.div_b[1], ix.geom.div_b[2]));
-  const int r_max = max_shells(ix, r_lim);
-  auto lds_fence = [] { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); };  // one wave per block: program order is enough
+  const int sub = threadIdx.x & (kTeam - 1), team = threadIdx.x / kTeam;
+  int* ordered = knn_row<int>(knn_lds, k, KnnOrdered::kPositions, team);  // [8][k] point indices, ascending (distance, index)
+  const ShellLimits lim = shell_limits(ix);
   // The loop is uniform across the wave (a team without a query idles): the scan of the isolated queries is wave-wide.
-  for (int base = block * kTeams; base < ix.n; base += n_blocks * kTeams) {
+  for (int base = block * kTeamsPerWave; base < ix.n; base += n_blocks * kTeamsPerWave) {
     const int i = base + team;  // uniform within a team
     const bool live = i < ix.n;
     const float4 q = live ? ix.pts[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    int cnt = 0;  // entries in the list (team-uniform, like everything below that is not marked "lane")
-    float worst = INFINITY;
-    int worst_p = 0, worst_slot = 0;
-    auto before = [&](float da, int pa, float db, int pb) {  // (distance, index) order
-      return da < db || (da == db && ix.sorted_idx[pa] < ix.sorted_idx[pb]);
-    };
-    auto find_worst = [&] {  // the list's last entry in (distance, index) order
-      float bd = -1.0f;  // lane: best so far over my slots
-      int bp = 0, bs = -1;
-      for (int j = sub; j < cnt; j += kTeam) {
-        const float d = ld[j];
-        const int p = lp[j];
-        if (bs < 0 || before(bd, bp, d, p)) {
-          bd = d;
-          bp = p;
-          bs = j;
-        }
-      }
-#pragma unroll
-      for (int off = 1; off < kTeam; off <<= 1) {
-        const float od = __shfl_xor(bd, off, kWave);
-        const int op = __shfl_xor(bp, off, kWave), os = __shfl_xor(bs, off, kWave);
-        if (os >= 0 && (bs < 0 || before(bd, bp, od, op))) {
-          bd = od;
-          bp = op;
-          bs = os;
-        }
-      }
-      worst = bd;
-      worst_p = bp;
-      worst_slot = bs;
-    };
-    auto insert_one = [&](float cd, int cp) {  // team-collective: a candidate known to all eight lanes
-      if (cnt < k) {
-        if (sub == 0) {
-          ld[cnt] = cd;
-          lp[cnt] = cp;
-        }
-        lds_fence();
-        cnt++;
-        if (cnt == k) find_worst();
-      } else if (before(cd, cp, worst, worst_p)) {
-        if (sub == 0) {
-          ld[worst_slot] = cd;
-          lp[worst_slot] = cp;
-        }
-        lds_fence();
-        find_worst();
-      }
-    };
-    // every lane brings one candidate (or none); the ones that can enter the list are taken one at a time
-    auto offer = [&](float d, unsigned upos, bool ok) {
-      const int pos = static_cast<int>(upos);
-      const bool want = ok && (cnt < k || before(d, pos, worst, worst_p));
-      unsigned pending = static_cast<unsigned>((__ballot(want) >> team_base) & 0xffull);
-      while (pending) {
-        const int owner = __builtin_ctz(pending);
-        pending &= pending - 1;
-        insert_one(__shfl(d, team_base + owner, kWave), __shfl(pos, team_base + owner, kWave));
-      }
-    };
-    int ci, cj, ck;
-    float margin;
-    query_cell(ix.geom, q.x, q.y, q.z, ci, cj, ck, margin);
-    bool done = !live;
-    for (int r = 0; r <= r_max && !done; r++) {
-      team_shell(ix, ci, cj, ck, r, sub, q.x, q.y, q.z, offer);
-      // Every unvisited point is at least r cells plus the query's margin (less the index-rounding slack) away: once the
-      // k-th best lies strictly inside that reach no unvisited point can enter the k nearest.
-      const float reach = static_cast<float>(r) * leaf + margin - ix.slack;
-      if ((cnt == k && reach > 0.0f && worst < reach * reach) || r >= r_lim) done = true;
-    }
-    // Sparse neighbourhoods: the WAVE looks at every point, twice, for one unfinished query at a time.  Pass 1 only keeps
-    // each lane's eight smallest distances, in registers; the k-th smallest of the wave's 512 values bounds the k-th
-    // neighbour's distance from above.  Pass 2 hands the points inside that bound -- about k of them -- to the query's team,
-    // which fills its list afresh.  (The few isolated queries set this kernel's time when a team walks the cloud alone,
-    // and a single pass with the list spends its time updating it: points arrive in arbitrary order.)
-    unsigned long long open_teams = __ballot(!done && sub == 0);
-    while (open_teams) {
-      const int src_lane = __builtin_ctzll(open_teams);
-      open_teams &= open_teams - 1;
-      const bool mine = (team == src_lane / kTeam);
-      const float ox = __shfl(q.x, src_lane, kWave), oy = __shfl(q.y, src_lane, kWave), oz = __shfl(q.z, src_lane, kWave);
-      const int count = ix.n_sorted;
-      float m0 = INFINITY, m1 = INFINITY, m2 = INFINITY, m3 = INFINITY, m4 = INFINITY, m5 = INFINITY, m6 = INFINITY, m7 = INFINITY;
-      auto keep = [&](float d, bool ok) {
-        if (!ok || !(d < m7)) return;
-        m7 = d;  // bubble the newcomer down the sorted registers
-        float t;
-        if (m7 < m6) { t = m6; m6 = m7; m7 = t; }
-        if (m6 < m5) { t = m5; m5 = m6; m6 = t; }
-        if (m5 < m4) { t = m4; m4 = m5; m5 = t; }
-        if (m4 < m3) { t = m3; m3 = m4; m4 = t; }
-        if (m3 < m2) { t = m2; m2 = m3; m3 = t; }
-        if (m2 < m1) { t = m1; m1 = m2; m2 = t; }
-        if (m1 < m0) { t = m0; m0 = m1; m1 = t; }
-      };
-      for (int b0 = 0; b0 < count; b0 += 4 * kWave) {
-        const int p0 = b0 + lane, p1 = p0 + kWave, p2 = p1 + kWave, p3 = p2 + kWave;
-        const float4 a = ix.sorted_pts[min(p0, count - 1)], b = ix.sorted_pts[min(p1, count - 1)];
-        const float4 c = ix.sorted_pts[min(p2, count - 1)], d = ix.sorted_pts[min(p3, count - 1)];
-        keep(dist2_f32(ox, oy, oz, a.x, a.y, a.z), p0 < count);
-        keep(dist2_f32(ox, oy, oz, b.x, b.y, b.z), p1 < count);
-        keep(dist2_f32(ox, oy, oz, c.x, c.y, c.z), p2 < count);
-        keep(dist2_f32(ox, oy, oz, d.x, d.y, d.z), p3 < count);
-      }
-      float bound = INFINITY;
-      for (int j = 0; j < k; j++) {  // pop the wave's smallest head k times (n >= k values exist)
-        float h = m0;
-        int who = lane;
-#pragma unroll
-        for (int off = 1; off < kWave; off <<= 1) {
-          const float oh = __shfl_xor(h, off, kWave);
-          const int ow = __shfl_xor(who, off, kWave);
-          if (oh < h || (oh == h && ow < who)) {
-            h = oh;
-            who = ow;
-          }
-        }
-        bound = h;
-        if (who == lane) { m0 = m1; m1 = m2; m2 = m3; m3 = m4; m4 = m5; m5 = m6; m6 = m7; m7 = INFINITY; }
-      }
-      if (mine) {
-        cnt = 0;
-        worst = INFINITY;
-      }
-      auto hand_over = [&](float d, int pos, bool ok) {  // wave-uniform call: the hits go to the owning team one by one
-        unsigned long long hits = __ballot(ok && !(d > bound));
-        while (hits) {
-          const int from = __builtin_ctzll(hits);
-          hits &= hits - 1;
-          const float cd = __shfl(d, from, kWave);
-          const int cp = __shfl(pos, from, kWave);
-          if (mine) insert_one(cd, cp);
-        }
-      };
-      for (int b0 = 0; b0 < count; b0 += 4 * kWave) {
-        const int p0 = b0 + lane, p1 = p0 + kWave, p2 = p1 + kWave, p3 = p2 + kWave;
-        const float4 a = ix.sorted_pts[min(p0, count - 1)], b = ix.sorted_pts[min(p1, count - 1)];
-        const float4 c = ix.sorted_pts[min(p2, count - 1)], d = ix.sorted_pts[min(p3, count - 1)];
-        hand_over(dist2_f32(ox, oy, oz, a.x, a.y, a.z), p0, p0 < count);
-        hand_over(dist2_f32(ox, oy, oz, b.x, b.y, b.z), p1, p1 < count);
-        hand_over(dist2_f32(ox, oy, oz, c.x, c.y, c.z), p2, p2 < count);
-        hand_over(dist2_f32(ox, oy, oz, d.x, d.y, d.z), p3, p3 < count);
-      }
-    }
-    if (!live) continue;
-    // rank sort: entry j goes to the place given by the number of entries before it
-    for (int j = sub; j < cnt; j += kTeam) {
-      const float d = ld[j];
-      const int p = lp[j];
-      int rank = 0;
-      for (int t = 0; t < cnt; t++) rank += (t != j && before(ld[t], lp[t], d, p)) ? 1 : 0;
+    const int cnt = team_knn<KnnOrdered>(ix, lim, k, knn_lds, q, live, nullptr, [&](int rank, float d, int p) {
       const int idx = ix.sorted_idx[p];
       ordered[rank] = idx;
       if (nn_idx) {
         nn_idx[static_cast<size_t>(i) * k + rank] = idx;
         nn_d2[static_cast<size_t>(i) * k + rank] = d;
       }
-    }
+    });
+    if (!live) continue;
     if (nn_idx)
       for (int j = cnt + sub; j < k; j += kTeam) {  // (only a cloud smaller than k, which the host refuses)
         nn_idx[static_cast<size_t>(i) * k + j] = -1;
@@ -297,12 +143,7 @@ __global__ __launch_bounds__(kKnnBlock) void k_knn_covariances(PointIndex ix, in
 __global__ __launch_bounds__(kKnnBlock) void k_knn_covariances_multi(const KnnMember* __restrict__ members, int n_members, int k,
                                                                      double gicp_epsilon) {
   const int b = static_cast<int>(blockIdx.x);
-  int lo = 0, hi = n_members - 1;  // the last member whose first_block <= b
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (members[mid].first_block <= b) lo = mid;
-    else hi = mid - 1;
-  }
+  const int lo = member_at(n_members, b, [&](int m) { return members[m].first_block; });
   const PointIndex ix = members[lo].ix;
   const int local = b - members[lo].first_block, n_blocks = members[lo].n_blocks;
   if (local >= n_blocks) return;  // (a grid larger than the table's blocks: nothing to do)
@@ -315,12 +156,7 @@ constexpr int kFiniteBlock = 256;
 __global__ __launch_bounds__(kFiniteBlock) void k_count_nonfinite_multi(const FiniteMember* __restrict__ members, int n_members,
                                                                         unsigned* __restrict__ counts) {
   const int b = static_cast<int>(blockIdx.x);
-  int lo = 0, hi = n_members - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (members[mid].first_block <= b) lo = mid;
-    else hi = mid - 1;
-  }
+  const int lo = member_at(n_members, b, [&](int m) { return members[m].first_block; });
   const float4* __restrict__ pts = members[lo].pts;
   const int n = members[lo].n;
   const long long first = static_cast<long long>(b - members[lo].first_block) * kFinitePointsPerBlock;
@@ -349,11 +185,8 @@ __device__ __forceinline__ void correspond_block(const float4* __restrict__ outp
 #pragma clang fp contract(off)
   constexpr int kTeams = kBlock / kTeam;
   const int sub = threadIdx.x & (kTeam - 1);
-  const float leaf = fminf(ix.geom.leaf[0], fminf(ix.geom.leaf[1], ix.geom.leaf[2]));
-  const int r_lim = max(ix.geom.div_b[0], max(ix.geom.div_b[1], ix.geom.div_b[2]));
-  const int r_max = max_shells(ix, r_lim);
+  const ShellLimits lim = shell_limits(ix);
   // The loop is uniform across the WAVE (a team without a query idles): the fallback below is a wave-wide operation.
-  constexpr int kTeamsPerWave = kWave / kTeam;
   const int wave_in_block = threadIdx.x / kWave, team_in_wave = (threadIdx.x & (kWave - 1)) / kTeam;
   for (int base = (block * (kBlock / kWave) + wave_in_block) * kTeamsPerWave; base < n; base += n_blocks * kTeams) {
     const int i = base + team_in_wave;
@@ -368,9 +201,7 @@ __device__ __forceinline__ void correspond_block(const float4* __restrict__ outp
       float best = INFINITY;  // this lane's share: distance and POSITION in the cell order (the index behind it is
       int best_p = -1;        // looked up on ties and at the end of a shell only)
       auto consider = [&](float d, unsigned pos, bool ok) {
-        if (!ok || d > best) return;
-        // equal distance: the lower index (best_p < 0 with d == best == +inf, an overflowed distance: nothing to compare with)
-        if (d < best || (best_p >= 0 && ix.sorted_idx[pos] < ix.sorted_idx[best_p])) {
+        if (ok && nearer(ix.sorted_idx, d, static_cast<int>(pos), best, best_p)) {
           best = d;
           best_p = static_cast<int>(pos);
         }
@@ -378,13 +209,13 @@ __device__ __forceinline__ void correspond_block(const float4* __restrict__ outp
       int ci, cj, ck;
       float margin;
       query_cell(ix.geom, qx, qy, qz, ci, cj, ck, margin);
-      for (int r = 0; r <= r_max && !done; r++) {
+      for (int r = 0; r <= lim.r_max && !done; r++) {
         team_shell(ix, ci, cj, ck, r, sub, qx, qy, qz, consider);
         tb = best;
         tb_i = best_p >= 0 ? ix.sorted_idx[best_p] : 0x7fffffff;
         team_min(tb, tb_i);
-        const float reach = static_cast<float>(r) * leaf + margin - ix.slack;
-        if ((tb_i != 0x7fffffff && reach > 0.0f && tb < reach * reach) || r >= r_lim) done = true;
+        const float reach = static_cast<float>(r) * lim.leaf + margin - ix.slack;
+        if ((tb_i != 0x7fffffff && reach > 0.0f && tb < reach * reach) || r >= lim.r_lim) done = true;
         // nothing closer than the gate is left once the shells reach past it: no correspondence either way
         if (reach > 0.0f && static_cast<double>(reach) * static_cast<double>(reach) >= dist_threshold &&
             !(static_cast<double>(tb) < dist_threshold))
@@ -433,12 +264,7 @@ __global__ __launch_bounds__(kBlock) void k_correspond_multi(const LockstepMembe
                                                              const LockstepCorrespond* __restrict__ steps, int n_steps,
                                                              double dist_threshold) {
   const int b = static_cast<int>(blockIdx.x);
-  int lo = 0, hi = n_steps - 1;  // the last entry whose first_block <= b
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (steps[mid].first_block <= b) lo = mid;
-    else hi = mid - 1;
-  }
+  const int lo = member_at(n_steps, b, [&](int m) { return steps[m].first_block; });
   const LockstepCorrespond* __restrict__ st = steps + lo;
   const int local = b - st->first_block, n_blocks = st->n_blocks;
   if (local >= n_blocks) return;  // (a grid larger than the table's blocks: nothing to do)
@@ -573,12 +399,7 @@ __global__ __launch_bounds__(kBlock) void k_functor_multi(const LockstepMember* 
                                                           unsigned long long seq) {
   __shared__ FunctorLds sh;
   const int b = static_cast<int>(blockIdx.x);
-  int lo = 0, hi = n_steps - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (steps[mid].first_block <= b) lo = mid;
-    else hi = mid - 1;
-  }
+  const int lo = member_at(n_steps, b, [&](int m) { return steps[m].first_block; });
   const LockstepFunctor* __restrict__ st = steps + lo;
   const int local = b - st->first_block, n_blocks = st->n_blocks, mode = st->mode;
   if (local >= n_blocks) return;
@@ -738,8 +559,7 @@ int server_blocks(int n, int max_blocks) { return grid_of(n, kBlock, 512, max_bl
 hipError_t launch_knn_covariances(const PointIndex& ix, int k, double gicp_epsilon, int blocks, double* cov6, int* nn_idx,
                                   float* nn_d2, hipStream_t stream) {
   if (k < 1 || k > kMaxK || blocks < 1) return hipErrorInvalidValue;
-  constexpr int kQueriesPerBlock = kKnnBlock / kTeam;
-  const size_t lds = static_cast<size_t>(k) * kQueriesPerBlock * 12;  // per team: k distances, k positions, k ordered indices
+  const size_t lds = knn_lds_bytes<int>(k, KnnOrdered::kPositions);  // + per team: k ordered indices
   hipLaunchKernelGGL(k_knn_covariances, dim3(blocks), dim3(kKnnBlock), lds, stream, ix, k, gicp_epsilon, cov6, nn_idx, nn_d2);
   return hipGetLastError();
 }
@@ -747,8 +567,7 @@ hipError_t launch_knn_covariances(const PointIndex& ix, int k, double gicp_epsil
 hipError_t launch_knn_covariances_multi(const KnnMember* d_members, int n_members, int n_blocks, int k, double gicp_epsilon,
                                         hipStream_t stream) {
   if (k < 1 || k > kMaxK || n_members < 1 || n_blocks < 1 || !d_members) return hipErrorInvalidValue;
-  constexpr int kQueriesPerBlock = kKnnBlock / kTeam;
-  const size_t lds = static_cast<size_t>(k) * kQueriesPerBlock * 12;  // as launch_knn_covariances: the same k for every member
+  const size_t lds = knn_lds_bytes<int>(k, KnnOrdered::kPositions);  // as launch_knn_covariances: the same k for every member
   hipLaunchKernelGGL(k_knn_covariances_multi, dim3(n_blocks), dim3(kKnnBlock), lds, stream, d_members, n_members, k, gicp_epsilon);
   return hipGetLastError();
 }

@@ -112,12 +112,7 @@ __global__ __launch_bounds__(kBlock) void k_centroid_fitness_multi(const Centroi
                                                                    double* __restrict__ partials) {
   __shared__ double lds[(kBlock / kWave) * 32];
   const int b = blockIdx.x;
-  int lo = 0, hi = n_members - 1;
-  while (lo < hi) {  // (block-uniform: scalar loads)
-    const int mid = (lo + hi + 1) >> 1;
-    if (starts[mid] <= b) lo = mid;
-    else hi = mid - 1;
-  }
+  const int lo = member_at(n_members, b, [&](int m) { return starts[m]; });
   const int first = starts[lo], nblk = starts[lo + 1] - first, blk = b - first;
   const CentroidMember& M = members[lo];
   const float4* __restrict__ src = M.src;

@@ -31,21 +31,10 @@ struct DskSeg {
   int first_block, n_blocks;
 };
 
-// the segment block b belongs to: the last one whose first block is not behind b (segments are never empty)
-__device__ __forceinline__ int seg_of(const DskSeg* __restrict__ segs, int n_segs, int b) {
-  int lo = 0, hi = n_segs - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (segs[mid].first_block <= b) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(kDskBlock) void k_deskew(DskSeg one, const DskSeg* __restrict__ segs, int n_segs, float* __restrict__ rows) {
   __shared__ float wave_box[kDskWaves][12];
   __shared__ unsigned wave_untimed[kDskWaves];
-  const DskSeg g = n_segs == 1 ? one : segs[seg_of(segs, n_segs, blockIdx.x)];
+  const DskSeg g = n_segs == 1 ? one : segs[ndt::member_at(n_segs, blockIdx.x, [&](int s) { return segs[s].first_block; })];
   const int lb = static_cast<int>(blockIdx.x) - g.first_block;
   const long long start = static_cast<long long>(lb) * g.ppb;
   const int len = static_cast<int>(min(static_cast<long long>(g.ppb), g.n - start));

@@ -193,6 +193,20 @@ __device__ __forceinline__ void block_reduce_store(double (&acc)[NV], double* __
 
 __device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
 
+// Which member of a many-member launch block b belongs to: the last of the n entries whose first block is not behind b.
+// first(m) is entry m's first block (ascending; entry 0 starts at 0, entries are never empty).  b and the table are the same
+// for the whole block, so called with blockIdx.x this is scalar loads and scalar compares: no lane searches, nothing diverges.
+template <class First>
+__device__ __forceinline__ int member_at(int n, int b, First&& first) {
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (first(mid) <= b) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
 // XCD-aware work assignment for the latency kernels.  Workgroups are dispatched round-robin over the 8
 // XCDs (block b runs on XCD b % 8), each XCD has its own L2, and the source scan is in lattice-cell
 // order: giving XCD x the x-th contiguous eighth of the scan keeps every L2 working on one compact

@@ -329,11 +329,8 @@ __device__ __forceinline__ void fitness_body(const float4* __restrict__ src, int
 #pragma unroll
   for (int k = 0; k < kNumAcc; k++) acc[k] = 0.0;
   const int sub = threadIdx.x & (kTeam - 1);
-  const float leaf = fminf(ix.geom.leaf[0], fminf(ix.geom.leaf[1], ix.geom.leaf[2]));
-  const int r_lim = max(ix.geom.div_b[0], max(ix.geom.div_b[1], ix.geom.div_b[2]));
-  const int r_max = max_shells(ix, r_lim);
+  const ShellLimits lim = shell_limits(ix);
   // The loop is uniform across the WAVE (a team without a query idles): the fallback below is a wave-wide operation.
-  constexpr int kTeamsPerWave = kWave / kTeam;
   const int wave_in_block = threadIdx.x / kWave, team_in_wave = (threadIdx.x & (kWave - 1)) / kTeam;
   // Queries are dealt to the teams in BIT-REVERSED order: the eight teams of a wave take queries an eighth of the scan apart.
   // The far queries of a scan come in runs (a wall the target does not cover), and a wave that held eight of them was the
@@ -364,15 +361,15 @@ __device__ __forceinline__ void fitness_body(const float4* __restrict__ src, int
         if (ok) best = fminf(best, d);
       };
       query_cell(ix.geom, tx, ty, tz, ci, cj, ck, margin);
-      for (int r = 0; r <= min(r_max, kTeamShells) && !done; r++) {
+      for (int r = 0; r <= min(lim.r_max, kTeamShells) && !done; r++) {
         team_shell(ix, ci, cj, ck, r, sub, tx, ty, tz, consider, tb);  // (tb: the team's best after the previous shell)
         tb = best;
 #pragma unroll
         for (int off = 1; off < kTeam; off <<= 1) tb = fminf(tb, __shfl_xor(tb, off, kWave));
         // every unvisited cell is at least r cells away (less the slack for the build-time / search-time
         // index rounding, trap 2)
-        const float reach = static_cast<float>(r) * leaf + margin - ix.slack;
-        if ((reach > 0.0f && tb <= reach * reach) || r >= r_lim) done = true;
+        const float reach = static_cast<float>(r) * lim.leaf + margin - ix.slack;
+        if ((reach > 0.0f && tb <= reach * reach) || r >= lim.r_lim) done = true;
       }
     }
     // ... the far queries (parts of the scan the target does not cover: metres to the nearest point, shells of hundreds of
@@ -392,14 +389,14 @@ __device__ __forceinline__ void fitness_body(const float4* __restrict__ src, int
         if (ok) wbest = fminf(wbest, d);
       };
       bool wdone = false;
-      for (int r = kTeamShells + 1; r <= r_max && !wdone; r++) {
+      for (int r = kTeamShells + 1; r <= lim.r_max && !wdone; r++) {
         team_shell<kWave>(ix, qi, qj, qk, r, lane, qx, qy, qz, consider_w, wb);
         float m = wbest;
 #pragma unroll
         for (int off = 1; off < kWave; off <<= 1) m = fminf(m, __shfl_xor(m, off, kWave));
         wb = fminf(wb, m);
-        const float reach = static_cast<float>(r) * leaf + q_margin - ix.slack;
-        if ((reach > 0.0f && wb <= reach * reach) || r >= r_lim) wdone = true;
+        const float reach = static_cast<float>(r) * lim.leaf + q_margin - ix.slack;
+        if ((reach > 0.0f && wb <= reach * reach) || r >= lim.r_lim) wdone = true;
       }
       if (!wdone) {  // nothing within r_max shells: one scan over all points
         float wd;
@@ -438,12 +435,7 @@ __global__ __launch_bounds__(kBlock) void k_fitness_multi(const FitnessMember* _
                                                           int n_members, double max_range, double* __restrict__ partials) {
   __shared__ double lds[(kBlock / kWave) * 32];
   const int b = blockIdx.x;
-  int lo = 0, hi = n_members - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (starts[mid] <= b) lo = mid;
-    else hi = mid - 1;
-  }
+  const int lo = member_at(n_members, b, [&](int m) { return starts[m]; });
   const int first = starts[lo], nblk = starts[lo + 1] - first;
   const FitnessMember& M = members[lo];
   PointIndex ix = M.ix;
@@ -462,12 +454,7 @@ __global__ __launch_bounds__(kBlock) void k_fitness_multi(const FitnessMember* _
 __global__ __launch_bounds__(kBlock) void k_transform_multi(const TransformScan* __restrict__ scans, const int* __restrict__ starts,
                                                             int n_scans, float4* __restrict__ dst) {
   const int b = blockIdx.x;
-  int lo = 0, hi = n_scans - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (starts[mid] <= b) lo = mid;
-    else hi = mid - 1;
-  }
+  const int lo = member_at(n_scans, b, [&](int m) { return starts[m]; });
   const int first = starts[lo];
   const unsigned step = static_cast<unsigned>(starts[lo + 1] - first) * kBlock;
   const TransformScan& S = scans[lo];

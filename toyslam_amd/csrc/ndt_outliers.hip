@@ -7,8 +7,9 @@
 //   values : k_outlier_values, one launch whatever the number of clouds (a member table; a block finds its member by
 //            bisection and then does what a block of a single-cloud launch does).  One wave per block, a team of eight lanes
 //            per query, the exact shell search of ndt_search.hpp.
-//            STATISTICAL keeps a per-team LDS list of the mean_k smallest DISTANCES (the value depends on the multiset of
-//            distances alone, so no positions, no tie rule); the query itself is the one zero-distance candidate dropped.
+//            STATISTICAL is team_knn under KnnDistances (the search GICP's covariance pass runs too): a per-team LDS list of
+//            the mean_k smallest DISTANCES (the value depends on the multiset of distances alone, so no positions, no tie
+//            rule); the query itself is the one zero-distance candidate dropped.  The mean of the distances is taken here.
 //            RADIUS counts the candidates within r2, shells pruned by the radius; counts are integers, exact by construction.
 //            Queries the shells cannot finish within max_shells go to one scan over the whole cloud by the wave.
 //   stats  : k_outlier_stats reduces fixed chunks of the values to (count, sum, M2 about the chunk's mean), k_outlier_merge
@@ -28,7 +29,18 @@ namespace {
 using ndt::PointIndex;
 constexpr int kTeams = ndt::kOutlierTeams;
 constexpr int kBlock = 64;  // one wave
-static_assert(kTeams * ndt::kTeam == kBlock, "a block is one wave of eight teams");
+static_assert(kTeams == ndt::kTeamsPerWave && kTeams * ndt::kTeam == kBlock, "a block is one wave of eight teams");
+
+// rounding: an unvisited point at true distance D may compute a d2 a few 1e-7 (relative) below D*D.  The bounds that decide
+// what is NOT looked at keep 1e-5 clear of the values they are compared with, so what is looked at decides alone.
+constexpr float kClear = 1.00001f;
+
+// STATISTICAL's neighbours (ndt_search.hpp team_knn): the mean_k smallest DISTANCES to the other points -- the value depends
+// on their multiset alone, so no positions and no tie rule; the query itself is the one zero-distance candidate dropped
+struct KnnDistances {
+  static constexpr bool kPositions = false, kDropSelf = true, kCountScans = true;
+  static constexpr float kClear = ndtc::kClear;
+};
 
 struct OutMember {
   PointIndex ix;   // mode 1: pts and n only
@@ -52,176 +64,26 @@ __device__ __forceinline__ void outlier_block(const PointIndex& ix, int mode, in
 #pragma clang fp contract(off)
   using namespace ndt;
   extern __shared__ unsigned char ol_lds[];
-  const int lane = threadIdx.x, sub = lane & (kTeam - 1), team = lane / kTeam, team_base = lane & ~(kTeam - 1);
-  float* ld = reinterpret_cast<float*>(ol_lds) + team * k;                            // [8][k] squared distances, unordered
-  double* od = reinterpret_cast<double*>(ol_lds + kTeams * k * sizeof(float)) + team * k;  // [8][k] distances, ascending
+  const int lane = threadIdx.x, sub = lane & (kTeam - 1), team = lane / kTeam;
+  double* od = knn_row<double>(ol_lds, k, KnnDistances::kPositions, team);  // [8][k] distances, ascending
   const bool stat = method == NDT_OUTLIER_STATISTICAL;
   const double nan = __longlong_as_double(0x7ff8000000000000ll);
-  auto lds_fence = [] { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); };  // one wave per block: program order is enough
   if (mode == 1) {
     for (int i = block * kBlock + lane; i < ix.n; i += n_blocks * kBlock) values[i] = finite3(ix.pts[i]) ? 0.0 : nan;
     return;
   }
-  const float leaf = fminf(ix.geom.leaf[0], fminf(ix.geom.leaf[1], ix.geom.leaf[2]));
-  const int r_lim = max(ix.geom.div_b[0], max(ix.geom.div_b[1], ix.geom.div_b[2]));
-  const int r_max = max_shells(ix, r_lim);
-  // rounding: an unvisited point at true distance D may compute a d2 a few 1e-7 (relative) below D*D.  The bounds that decide
-  // what is NOT looked at keep 1e-5 clear of the values they are compared with, so what is looked at decides alone.
-  constexpr float kClear = 1.00001f;
+  const ShellLimits lim = shell_limits(ix);
   // The loop is uniform across the wave (a team without a query idles): the whole-cloud scan is wave-wide.
   for (int base = block * kTeams; base < ix.n; base += n_blocks * kTeams) {
     const int i = base + team;  // uniform within a team
     const bool live = i < ix.n;
     const float4 q = live ? ix.pts[i] : make_float4(0.f, 0.f, 0.f, 0.f);
     const bool search = live && finite3(q);
-    int ci = 0, cj = 0, ck = 0;
-    float margin = 0.f;
-    if (search) query_cell(ix.geom, q.x, q.y, q.z, ci, cj, ck, margin);
     double value = nan;
     if (stat) {
-      int cnt = 0;  // entries in the list (team-uniform, like everything below that is not marked "lane")
-      float worst = INFINITY;
-      int worst_slot = 0;
-      bool self_dropped = false;
-      auto find_worst = [&] {  // the list's largest entry
-        float bd = -1.0f;  // lane: largest over my slots
-        int bs = -1;
-        for (int j = sub; j < cnt; j += kTeam) {
-          const float d = ld[j];
-          if (bs < 0 || d > bd) {
-            bd = d;
-            bs = j;
-          }
-        }
-#pragma unroll
-        for (int off = 1; off < kTeam; off <<= 1) {
-          const float o = __shfl_xor(bd, off, kWave);
-          const int os = __shfl_xor(bs, off, kWave);
-          if (os >= 0 && (bs < 0 || o > bd || (o == bd && os < bs))) {
-            bd = o;
-            bs = os;
-          }
-        }
-        worst = bd;
-        worst_slot = bs;
-      };
-      auto insert_one = [&](float cd) {  // team-collective: a candidate known to all eight lanes
-        if (cd == 0.0f && !self_dropped) {  // d2(i, i) is exactly 0: the query itself, or a duplicate in its place
-          self_dropped = true;
-          return;
-        }
-        if (cnt < k) {
-          if (sub == 0) ld[cnt] = cd;
-          lds_fence();
-          cnt++;
-          if (cnt == k) find_worst();
-        } else if (cd < worst) {
-          if (sub == 0) ld[worst_slot] = cd;
-          lds_fence();
-          find_worst();
-        }
-      };
-      auto offer = [&](float d, unsigned, bool ok) {  // every lane brings one candidate (or none)
-        const bool want = ok && (cnt < k || d < worst || (d == 0.0f && !self_dropped));
-        unsigned pending = static_cast<unsigned>((__ballot(want) >> team_base) & 0xffull);
-        while (pending) {
-          const int owner = __builtin_ctz(pending);
-          pending &= pending - 1;
-          insert_one(__shfl(d, team_base + owner, kWave));
-        }
-      };
-      bool done = !search;
-      for (int r = 0; r <= r_max && !done; r++) {
-        team_shell(ix, ci, cj, ck, r, sub, q.x, q.y, q.z, offer);
-        // every unvisited point is at least r cells plus the query's margin (less the index-rounding slack) away
-        const float reach = static_cast<float>(r) * leaf + margin - ix.slack;
-        if ((cnt == k && reach > 0.0f && worst * kClear < reach * reach) || r >= r_lim) done = true;
-      }
-      // Sparse neighbourhoods: the WAVE looks at every point, twice, for one unfinished query at a time.  Pass 1 keeps each
-      // lane's eight smallest distances in registers; the (k + 1)-th smallest of the wave's 512 values (the query itself is
-      // among them) bounds the k-th neighbour's distance from above.  Pass 2 hands the points inside that bound to the
-      // query's team, which fills its list afresh.
-      unsigned long long open_teams = __ballot(!done && sub == 0);
-      if (open_teams && lane == 0) atomicAdd(scanned, static_cast<unsigned>(__popcll(open_teams)));
-      while (open_teams) {
-        const int src_lane = __builtin_ctzll(open_teams);
-        open_teams &= open_teams - 1;
-        const bool mine = (team == src_lane / kTeam);
-        const float ox = __shfl(q.x, src_lane, kWave), oy = __shfl(q.y, src_lane, kWave), oz = __shfl(q.z, src_lane, kWave);
-        const int count = ix.n_sorted;
-        float m0 = INFINITY, m1 = INFINITY, m2 = INFINITY, m3 = INFINITY, m4 = INFINITY, m5 = INFINITY, m6 = INFINITY, m7 = INFINITY;
-        auto keep = [&](float d, bool ok) {
-          if (!ok || !(d < m7)) return;
-          m7 = d;  // bubble the newcomer down the sorted registers
-          float t;
-          if (m7 < m6) { t = m6; m6 = m7; m7 = t; }
-          if (m6 < m5) { t = m5; m5 = m6; m6 = t; }
-          if (m5 < m4) { t = m4; m4 = m5; m5 = t; }
-          if (m4 < m3) { t = m3; m3 = m4; m4 = t; }
-          if (m3 < m2) { t = m2; m2 = m3; m3 = t; }
-          if (m2 < m1) { t = m1; m1 = m2; m2 = t; }
-          if (m1 < m0) { t = m0; m0 = m1; m1 = t; }
-        };
-        for (int b0 = 0; b0 < count; b0 += 4 * kWave) {
-          const int p0 = b0 + lane, p1 = p0 + kWave, p2 = p1 + kWave, p3 = p2 + kWave;
-          const float4 a = ix.sorted_pts[min(p0, count - 1)], b = ix.sorted_pts[min(p1, count - 1)];
-          const float4 c = ix.sorted_pts[min(p2, count - 1)], d = ix.sorted_pts[min(p3, count - 1)];
-          keep(dist2_f32(ox, oy, oz, a.x, a.y, a.z), p0 < count);
-          keep(dist2_f32(ox, oy, oz, b.x, b.y, b.z), p1 < count);
-          keep(dist2_f32(ox, oy, oz, c.x, c.y, c.z), p2 < count);
-          keep(dist2_f32(ox, oy, oz, d.x, d.y, d.z), p3 < count);
-        }
-        float bound = INFINITY;
-        for (int j = 0; j <= k; j++) {  // pop the wave's smallest head k + 1 times (|F| > k: that many values exist)
-          float hd = m0;
-          int who = lane;
-#pragma unroll
-          for (int off = 1; off < kWave; off <<= 1) {
-            const float oh = __shfl_xor(hd, off, kWave);
-            const int ow = __shfl_xor(who, off, kWave);
-            if (oh < hd || (oh == hd && ow < who)) {
-              hd = oh;
-              who = ow;
-            }
-          }
-          bound = hd;
-          if (who == lane) { m0 = m1; m1 = m2; m2 = m3; m3 = m4; m4 = m5; m5 = m6; m6 = m7; m7 = INFINITY; }
-        }
-        if (mine) {
-          cnt = 0;
-          worst = INFINITY;
-          self_dropped = false;
-        }
-        auto hand_over = [&](float d, bool ok) {  // wave-uniform call: the hits go to the owning team one by one
-          unsigned long long hits = __ballot(ok && !(d > bound));
-          while (hits) {
-            const int from = __builtin_ctzll(hits);
-            hits &= hits - 1;
-            const float cd = __shfl(d, from, kWave);
-            if (mine) insert_one(cd);
-          }
-        };
-        for (int b0 = 0; b0 < count; b0 += 4 * kWave) {
-          const int p0 = b0 + lane, p1 = p0 + kWave, p2 = p1 + kWave, p3 = p2 + kWave;
-          const float4 a = ix.sorted_pts[min(p0, count - 1)], b = ix.sorted_pts[min(p1, count - 1)];
-          const float4 c = ix.sorted_pts[min(p2, count - 1)], d = ix.sorted_pts[min(p3, count - 1)];
-          hand_over(dist2_f32(ox, oy, oz, a.x, a.y, a.z), p0 < count);
-          hand_over(dist2_f32(ox, oy, oz, b.x, b.y, b.z), p1 < count);
-          hand_over(dist2_f32(ox, oy, oz, c.x, c.y, c.z), p2 < count);
-          hand_over(dist2_f32(ox, oy, oz, d.x, d.y, d.z), p3 < count);
-        }
-      }
+      const int cnt = team_knn<KnnDistances>(ix, lim, k, ol_lds, q, search, scanned,
+                                             [&](int rank, float d, int) { od[rank] = sqrt(static_cast<double>(d)); });
       if (search) {
-        // rank sort: entry j goes to the place given by the number of entries before it (equal distances: by slot)
-        for (int j = sub; j < cnt; j += kTeam) {
-          const float d = ld[j];
-          int rank = 0;
-          for (int t = 0; t < cnt; t++) {
-            const float o = ld[t];
-            rank += (o < d || (o == d && t < j)) ? 1 : 0;
-          }
-          od[rank] = sqrt(static_cast<double>(d));
-        }
         lds_fence();
         if (sub == 0) {
           double sum = 0.0;
@@ -232,6 +94,9 @@ __device__ __forceinline__ void outlier_block(const PointIndex& ix, int mode, in
       }
     } else {
       // RADIUS.  The shells out to the first whose reach clears the radius; beyond max_shells, the scan over the cloud.
+      int ci = 0, cj = 0, ck = 0;
+      float margin = 0.f;
+      if (search) query_cell(ix.geom, q.x, q.y, q.z, ci, cj, ck, margin);
       int count_in = 0;  // lane
       auto consider = [&](float d, unsigned, bool ok) { count_in += (ok && d <= r2) ? 1 : 0; };
       const float far = radius * kClear;
@@ -239,10 +104,10 @@ __device__ __forceinline__ void outlier_block(const PointIndex& ix, int mode, in
       bool scan = false;
       if (search) {
         const float x = far - margin + ix.slack;
-        r_need = x > 0.0f ? static_cast<int>(fminf(x / leaf, 1.0e6f)) : 0;
-        r_need = min(r_need, r_lim);
-        while (r_need < r_lim && !(static_cast<float>(r_need) * leaf + margin - ix.slack > far)) r_need++;
-        scan = r_need > r_max;
+        r_need = x > 0.0f ? static_cast<int>(fminf(x / lim.leaf, 1.0e6f)) : 0;
+        r_need = min(r_need, lim.r_lim);
+        while (r_need < lim.r_lim && !(static_cast<float>(r_need) * lim.leaf + margin - ix.slack > far)) r_need++;
+        scan = r_need > lim.r_max;
         if (!scan)
           for (int r = 0; r <= r_need; r++) team_shell(ix, ci, cj, ck, r, sub, q.x, q.y, q.z, consider, r2 * (kClear * kClear));
       }
@@ -253,17 +118,8 @@ __device__ __forceinline__ void outlier_block(const PointIndex& ix, int mode, in
         const int src_lane = __builtin_ctzll(open_teams);
         open_teams &= open_teams - 1;
         const float ox = __shfl(q.x, src_lane, kWave), oy = __shfl(q.y, src_lane, kWave), oz = __shfl(q.z, src_lane, kWave);
-        const int count = ix.n_sorted;
         int c4 = 0;
-        for (int b0 = 0; b0 < count; b0 += 4 * kWave) {
-          const int p0 = b0 + lane, p1 = p0 + kWave, p2 = p1 + kWave, p3 = p2 + kWave;
-          const float4 a = ix.sorted_pts[min(p0, count - 1)], b = ix.sorted_pts[min(p1, count - 1)];
-          const float4 c = ix.sorted_pts[min(p2, count - 1)], d = ix.sorted_pts[min(p3, count - 1)];
-          c4 += (p0 < count && dist2_f32(ox, oy, oz, a.x, a.y, a.z) <= r2) ? 1 : 0;
-          c4 += (p1 < count && dist2_f32(ox, oy, oz, b.x, b.y, b.z) <= r2) ? 1 : 0;
-          c4 += (p2 < count && dist2_f32(ox, oy, oz, c.x, c.y, c.z) <= r2) ? 1 : 0;
-          c4 += (p3 < count && dist2_f32(ox, oy, oz, d.x, d.y, d.z) <= r2) ? 1 : 0;
-        }
+        wave_scan_all(ix, ox, oy, oz, [&](float d, int, bool ok) { c4 += (ok && d <= r2) ? 1 : 0; });
 #pragma unroll
         for (int off = 1; off < kWave; off <<= 1) c4 += __shfl_xor(c4, off, kWave);
         if (team == src_lane / kTeam) total = c4;
@@ -282,12 +138,7 @@ __global__ __launch_bounds__(kBlock) void k_outlier_values(OutMember one, const 
     if (b < one.n_blocks) outlier_block(one.ix, one.mode, method, k, radius, r2, b, one.n_blocks, one.values, scanned);
     return;
   }
-  int lo = 0, hi = n_members - 1;  // the last member whose first_block <= b
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (members[mid].first_block <= b) lo = mid;
-    else hi = mid - 1;
-  }
+  const int lo = ndt::member_at(n_members, b, [&](int c) { return members[c].first_block; });
   const OutMember m = members[lo];
   const int local = b - m.first_block;
   if (local >= m.n_blocks) return;
@@ -312,12 +163,7 @@ __global__ __launch_bounds__(ndt::kOutlierStatBlock) void k_outlier_stats(const 
 #pragma clang fp contract(off)
   __shared__ double sh[ndt::kOutlierStatBlock];
   const int b = static_cast<int>(blockIdx.x);
-  int lo = 0, hi = n_members - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (members[mid].first_block <= b) lo = mid;
-    else hi = mid - 1;
-  }
+  const int lo = ndt::member_at(n_members, b, [&](int c) { return members[c].first_block; });
   const StatMember m = members[lo];
   const int lb = b - m.first_block;
   if (lb >= m.n_blocks) return;
@@ -475,7 +321,7 @@ ndt_status outlier_queue(ndt_handle h, const ndt_outlier_spec& spec, OutlierRun&
     HIP_TRY(hipMemcpyAsync(R.d_mem.p, R.mem.data(), R.mem.size() * sizeof(OutMember), hipMemcpyHostToDevice, st));
   }
   const int kk = stat ? spec.mean_k : 0;
-  const size_t lds = stat ? static_cast<size_t>(kTeams) * static_cast<size_t>(kk) * (sizeof(float) + sizeof(double)) : 0;
+  const size_t lds = stat ? ndt::knn_lds_bytes<double>(kk, KnnDistances::kPositions) : 0;
   hipLaunchKernelGGL(k_outlier_values, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), lds, st, R.mem[0],
                      reinterpret_cast<const OutMember*>(R.d_mem.p), n_mem, spec.method, kk, spec.radius, spec.radius * spec.radius,
                      R.d_scanned.p);

@@ -20,6 +20,8 @@
 #include "ndt_plane.hpp"
 #include "ndt_select.hpp"
 
+#include "ndt_device.hpp"
+
 namespace ndtc {
 namespace {
 
@@ -44,18 +46,6 @@ struct PlaneMember {
   int key_first, key_blocks, key_ppb;                         // the key launch (select_plan)
   int sum_first, sum_blocks, sum_chunk;                       // the sums launch (plane_sum_plan)
 };
-
-// the member block b belongs to: the last one whose first block (field F) is not behind b
-template <int PlaneMember::*F>
-__device__ __forceinline__ int member_of(const PlaneMember* __restrict__ members, int n_members, int b) {
-  int lo = 0, hi = n_members - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (members[mid].*F <= b) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
 
 // (a call of one cloud hands its member over as a kernel argument: no table to copy up first)
 __global__ __launch_bounds__(256) void k_plane_models(PlaneMember one, const PlaneMember* __restrict__ members, int n_members, PlaneParams P,
@@ -94,7 +84,7 @@ __global__ __launch_bounds__(kBlock) void k_plane_counts(PlaneMember one, const 
                                                          double T, int rows_form) {
   __shared__ double tx[kTile], ty[kTile], tz[kTile];
   const int b = static_cast<int>(blockIdx.x);
-  const PlaneMember m = n_members == 1 ? one : members[member_of<&PlaneMember::first_block>(members, n_members, b)];
+  const PlaneMember m = n_members == 1 ? one : members[ndt::member_at(n_members, b, [&](int c) { return members[c].first_block; })];
   const int lb = b - m.first_block;
   if (lb >= m.n_blocks) return;  // (uniform over the block)
   const int hb = lb % m.hyp_blocks, slot = lb / m.hyp_blocks;
@@ -226,7 +216,7 @@ __global__ __launch_bounds__(ndt::kPlaneSumBlock) void k_plane_sums(PlaneMember 
 #pragma clang fp contract(off)
   __shared__ double sh[ndt::kPlaneSumBlock];
   const int b = static_cast<int>(blockIdx.x);
-  const PlaneMember m = n_members == 1 ? one : members[member_of<&PlaneMember::sum_first>(members, n_members, b)];
+  const PlaneMember m = n_members == 1 ? one : members[ndt::member_at(n_members, b, [&](int c) { return members[c].sum_first; })];
   const int lb = b - m.sum_first;
   if (lb >= m.sum_blocks) return;
   const bool found = m.chosen[0] != 0.0;
@@ -262,7 +252,7 @@ __global__ __launch_bounds__(ndt::kPlaneSumBlock) void k_plane_sums(PlaneMember 
 __global__ __launch_bounds__(256) void k_plane_keys(PlaneMember one, const PlaneMember* __restrict__ members, int n_members, double T) {
   __shared__ unsigned w_in[4], w_fin[4];
   const int b = static_cast<int>(blockIdx.x);
-  const PlaneMember m = n_members == 1 ? one : members[member_of<&PlaneMember::key_first>(members, n_members, b)];
+  const PlaneMember m = n_members == 1 ? one : members[ndt::member_at(n_members, b, [&](int c) { return members[c].key_first; })];
   const int lb = b - m.key_first;
   if (lb >= m.key_blocks) return;
   const bool found = m.chosen[0] != 0.0;

@@ -15,6 +15,8 @@
 #include "ndt_internal.hpp"
 #include "ndt_select.hpp"
 
+#include "ndt_device.hpp"
+
 namespace ndtc {
 namespace {
 
@@ -33,22 +35,11 @@ struct SelSeg {
   int slot;                  // where the cloud's total goes
 };
 
-// the segment block b belongs to: the last one whose first block is not behind b (segments are never empty)
-__device__ __forceinline__ int seg_of(const SelSeg* __restrict__ segs, int n_segs, int b) {
-  int lo = 0, hi = n_segs - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (segs[mid].first_block <= b) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
 // (a call of one cloud -- the usual one -- hands its segment over as a kernel argument: no table to copy up first)
 __global__ __launch_bounds__(kSelBlock) void k_select_count(SelSeg one, const SelSeg* __restrict__ segs, int n_segs, ndt_select_spec spec,
                                                             unsigned long long* __restrict__ ballots, unsigned* __restrict__ counts) {
   __shared__ unsigned wave_count[kSelWaves];
-  const SelSeg g = n_segs == 1 ? one : segs[seg_of(segs, n_segs, blockIdx.x)];
+  const SelSeg g = n_segs == 1 ? one : segs[ndt::member_at(n_segs, blockIdx.x, [&](int s) { return segs[s].first_block; })];
   if (g.key_range) {  // a key range of the cloud's own, computed on the device (the outlier filters' thresholds)
     spec.key_lo = g.key_range[0];
     spec.key_hi = g.key_range[1];
@@ -96,7 +87,7 @@ __global__ __launch_bounds__(kSelBlock) void k_select_place(SelSeg one, const Se
                                                             unsigned* __restrict__ totals) {
   __shared__ unsigned wave_sum[kSelWaves];
   __shared__ float wave_box[kSelWaves][12];
-  const SelSeg g = n_segs == 1 ? one : segs[seg_of(segs, n_segs, blockIdx.x)];
+  const SelSeg g = n_segs == 1 ? one : segs[ndt::member_at(n_segs, blockIdx.x, [&](int s) { return segs[s].first_block; })];
   const int lb = static_cast<int>(blockIdx.x) - g.first_block;
   const long long start = static_cast<long long>(lb) * g.ppb;
   const int len = static_cast<int>(min(static_cast<long long>(g.ppb), g.n - start));
