@@ -6,13 +6,15 @@
 // see; a lut_rejected entry and a voxel under min_points_per_voxel are not in it -- in ascending linear voxel index; voxel v gives
 // its f32 centroid (the bits of ndt_grid_centroids) and a 3x3 f64 covariance (RAW: the inverse of the record's f64 icov; PLANE:
 // I - (1 - gicp_epsilon) n n^T, n the eigenvector of icov's largest eigenvalue).
-//   refresh  : one mark + scan (dense table, whose order IS the linear index order) or mark + sort by key (hash) + gather pass
+//   refresh  : table_voxels (ndt_table_voxels.hpp) over the entries that are records with VoxelEmit -- one mark + scan (dense
+//              table, whose order IS the linear index order) or mark + sort by key (hash) + gather pass, the centroid cloud's --
 //              writes D's centroids, covariances, linear indices and the record -> ordinal map; cached in the handle's GridTarget,
 //              redone when the grid's generation has moved or the map handle holds another grid (gicp_grid_ready)
 //   search   : k_correspond_voxel -- k_correspond's job and outputs.  Per query (a team of 8 lanes, wave-uniform loop) cubic
-//              shells of cells through the map's table as the centroid fitness walks them (ndt_voxel_table.hpp: cell_entry;
-//              axis_gap widened by give = index slack + the grid's excursion), the best PAIR (d2, ordinal) carried, equal d2 to
-//              the lower ordinal = the lower linear index, rejected entries passed over.  Stops: the exact-search rule (the
+//              shells of cells through the map's table, the centroid fitness's walk (ndt_voxel_table.hpp: table_shell and
+//              wave_scan_table under the policy NearestVoxel; axis_gap widened by give = index slack + the grid's excursion),
+//              the best PAIR (d2, ordinal) carried, equal d2 to the lower ordinal = the lower linear index, rejected entries
+//              passed over.  The driver (voxel_nearest) is this file's own.  Stops: the exact-search rule (the
 //              best lies strictly inside reach - give), k_correspond's gate rule (the shells reach past the gate and nothing
 //              under it has been found: -1), and after r_max shells one pass over the table by the whole wave.
 //   cost rule: shell r probes up to (2r+1)^3 - (2r-1)^3 table entries; a query with nothing near walks shells until
@@ -21,13 +23,10 @@
 //   algebra  : mahalanobis_store (gicp_device.hpp), shared with k_correspond; the objective kernels, the server and gicp::run
 //              are used as they are, their `tgt` is D's centroid array.
 //   fitness  : k_voxel_fitness -- k_fitness's loop, rows and reduction with the voxel search in it
-#include <hipcub/hipcub.hpp>
-
 #include "gicp_internal.hpp"
 
 #include "gicp_device.hpp"
-#include "ndt_search.hpp"
-#include "ndt_voxel_table.hpp"
+#include "ndt_table_voxels.hpp"
 
 namespace gicp {
 
@@ -44,93 +43,32 @@ namespace {
 
 constexpr int kNoVoxel = 0x7fffffff;
 
-// (distance, ordinal) order: the nearer, at equal distance the lower ordinal
-__device__ __forceinline__ void take_pair(float d, int o, float& best, int& best_o) {
-  if (d < best || (d == best && o < best_o)) {
-    best = d;
-    best_o = o;
-  }
-}
-
-// Shell r of cells around (cx, cy, cz): centroid_shell's walk (ndt_centroid_fitness.hip) for a team of 8 lanes, carrying the
-// ordinal.  A lane walks its rows kProbes cells at a time -- the table loads together, then the centroid and ordinal loads of
-// the entries that are records together -- and keeps its own best pair; the team combines after the shell.  Rows and cells
-// whose box, widened by ci.give, lies farther than bound2 are not looked up (at bound2 exactly they are: a tie may hide there).
-__device__ __forceinline__ void voxel_shell(const VoxelTarget& vt, int cx, int cy, int cz, int r, int sub, float qx, float qy, float qz,
-                                            float bound2, float& best, int& best_o) {
-  const CentroidIndex& ci = vt.ci;
-  const GridGeom& g = ci.gv.g;
-  const int w = 2 * r + 1, rows = w * w;
-  for (int row = sub; row < rows; row += kTeam) {
-    const int dz = row / w - r, dy = row % w - r;
-    const int z = cz + dz, y = cy + dy;
-    if (z < 0 || z >= g.div_b[2] || y < 0 || y >= g.div_b[1]) continue;
-    const float gy = axis_gap(qy, y + g.min_b[1], g.leaf[1], ci.give), gz = axis_gap(qz, z + g.min_b[2], g.leaf[2], ci.give);
-    const float row_d2 = gy * gy + gz * gz;
-    if (row_d2 > bound2) continue;
-    const bool face = (dz == -r || dz == r || dy == -r || dy == r);  // r == 0: the single row is a face row
-    const int nx = face ? w : 2;
-    for (int t = 0; t < nx; t += kProbes) {
-      int e[kProbes];
-#pragma unroll
-      for (int u = 0; u < kProbes; u++) {
-        e[u] = kLutEmpty;
-        const int tt = t + u;
-        const int x = cx + (face ? tt - r : (tt == 0 ? -r : r));
-        if (tt < nx && x >= 0 && x < g.div_b[0]) {
-          const float gx = axis_gap(qx, x + g.min_b[0], g.leaf[0], ci.give);
-          if (row_d2 + gx * gx <= bound2) e[u] = cell_entry(ci.gv, x, y, z);
-        }
-      }
-      float4 c[kProbes];
-      int o[kProbes];
-#pragma unroll
-      for (int u = 0; u < kProbes; u++)
-        if (e[u] >= 0) {  // a record: neither empty nor rejected
-          c[u] = *reinterpret_cast<const float4*>(ci.gv.centroids + e[u]);  // (cx, cy, cz, -)
-          o[u] = vt.ord[e[u]];
-        }
-#pragma unroll
-      for (int u = 0; u < kProbes; u++)
-        if (e[u] >= 0) take_pair(dist2_f32(qx, qy, qz, c[u].x, c[u].y, c[u].z), o[u], best, best_o);
+// The search policy of the voxel target (ndt_voxel_table.hpp): the entries that are records -- neither empty nor rejected --
+// are candidates, the ordinal is loaded beside the centroid, and the best PAIR (distance, ordinal) is carried: the nearer, at
+// equal distance the lower ordinal
+struct NearestVoxel {
+  struct Best {
+    float d;
+    int o;
+  };
+  using Side = int;
+  const int* ord;  // record -> ordinal in D
+  __device__ static Best none() { return Best{INFINITY, kNoVoxel}; }
+  __device__ static bool candidate(int e) { return e >= 0; }
+  __device__ static int record(int e) { return e; }
+  __device__ Side side(int rec) const { return ord[rec]; }
+  __device__ static void take(float d, int o, Best& best) {
+    if (d < best.d || (d == best.d && o < best.o)) {
+      best.d = d;
+      best.o = o;
     }
   }
-}
-
-// ONE pass over the table by the whole wave (every lane with the same query): the nearest voxel of D as (d2, ordinal), in all lanes
-__device__ __forceinline__ void wave_scan_voxels(const VoxelTarget& vt, float qx, float qy, float qz, float& out_d, int& out_o) {
-  const CentroidIndex& ci = vt.ci;
-  const int lane = threadIdx.x & (kWave - 1);
-  float best = INFINITY;
-  int best_o = kNoVoxel;
-  for (long long base = 0; base < ci.entries; base += kProbes * kWave) {
-    int e[kProbes];
-#pragma unroll
-    for (int u = 0; u < kProbes; u++) {
-      const long long t = base + lane + u * kWave;
-      e[u] = t < ci.entries ? table_entry(ci.gv, t) : kLutEmpty;
-    }
-    float4 c[kProbes];
-    int o[kProbes];
-#pragma unroll
-    for (int u = 0; u < kProbes; u++)
-      if (e[u] >= 0) {
-        c[u] = *reinterpret_cast<const float4*>(ci.gv.centroids + e[u]);
-        o[u] = vt.ord[e[u]];
-      }
-#pragma unroll
-    for (int u = 0; u < kProbes; u++)
-      if (e[u] >= 0) take_pair(dist2_f32(qx, qy, qz, c[u].x, c[u].y, c[u].z), o[u], best, best_o);
+  __device__ static void fold(Best& best, int off) {
+    const float od = __shfl_xor(best.d, off, kWave);
+    const int oo = __shfl_xor(best.o, off, kWave);
+    take(od, oo, best);
   }
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {
-    const float od = __shfl_xor(best, off, kWave);
-    const int oo = __shfl_xor(best_o, off, kWave);
-    take_pair(od, oo, best, best_o);
-  }
-  out_d = best;
-  out_o = best_o;
-}
+};
 
 // The nearest voxel of D to the query of every team of the wave: (tb, tb_o), uniform within the team; tb_o == kNoVoxel: none
 // (only with a gate: nothing lies under it).  Every lane of the WAVE must call this together (a team without a query: live =
@@ -144,19 +82,19 @@ __device__ __forceinline__ void voxel_nearest(const VoxelTarget& vt, bool live, 
   const float leaf = fminf(g.leaf[0], fminf(g.leaf[1], g.leaf[2]));
   const int r_lim = max(g.div_b[0], max(g.div_b[1], g.div_b[2]));
   const int r_max = vt.ci.r_max;
+  const NearestVoxel nearest{vt.ord};
   tb = INFINITY;
   tb_o = kNoVoxel;
   bool done = !live;
   if (live) {
-    float best = INFINITY;  // this lane's share of the candidates
-    int best_o = kNoVoxel;
+    NearestVoxel::Best best = NearestVoxel::none();  // this lane's share of the candidates
     int cx, cy, cz;
     float margin;
     query_cell(g, qx, qy, qz, cx, cy, cz, margin);
     for (int r = 0; r <= r_max && !done; r++) {
-      voxel_shell(vt, cx, cy, cz, r, sub, qx, qy, qz, tb, best, best_o);  // (tb: the team's best after the previous shell)
-      tb = best;
-      tb_o = best_o;
+      table_shell<kTeam>(vt.ci, nearest, cx, cy, cz, r, sub, qx, qy, qz, tb, best);  // (tb: the team's best after the previous shell)
+      tb = best.d;
+      tb_o = best.o;
       team_min(tb, tb_o);
       // every unvisited CELL is at least r cells away; its centroid may lie ci.give outside it.  Strictly inside the reach: a
       // voxel AT the reach could tie with a lower index
@@ -172,12 +110,11 @@ __device__ __forceinline__ void voxel_nearest(const VoxelTarget& vt, bool live, 
   while (open_teams) {
     const int src_lane = __builtin_ctzll(open_teams);
     open_teams &= open_teams - 1;
-    float wd;
-    int wo;
-    wave_scan_voxels(vt, __shfl(qx, src_lane, kWave), __shfl(qy, src_lane, kWave), __shfl(qz, src_lane, kWave), wd, wo);
+    const NearestVoxel::Best wb =
+        wave_scan_table(vt.ci, nearest, __shfl(qx, src_lane, kWave), __shfl(qy, src_lane, kWave), __shfl(qz, src_lane, kWave));
     if (lane / kTeam == src_lane / kTeam) {
-      tb = wd;
-      tb_o = wo;
+      tb = wb.d;
+      tb_o = wb.o;
     }
   }
 }
@@ -253,10 +190,22 @@ __global__ __launch_bounds__(kBlock) void k_voxel_fitness(const float4* __restri
 }
 
 // ---- the refresh pass
-// One voxel of D to position p: centroid, linear index, covariance, and the record's ordinal.  One thread's work.
-__device__ __forceinline__ void voxel_emit(const VoxelSide* __restrict__ sides, int rec, unsigned p, long long linear, double epsilon,
-                                           int cov_mode, float4* __restrict__ pts, double* __restrict__ cov6, long long* __restrict__ idx,
-                                           int* __restrict__ ord) {
+// D's enumeration (ndt_table_voxels.hpp): the entries that are records ...
+struct IsRecord {
+  __device__ static bool pick(int e) { return e >= 0; }
+};
+// ... and one voxel of D to position p: centroid, linear index, covariance, and the record's ordinal.  One thread's work.
+struct VoxelEmit {
+  const VoxelSide* sides;
+  double epsilon;
+  int cov_mode;
+  float4* pts;
+  double* cov6;
+  long long* idx;
+  int* ord;
+  __device__ void operator()(int rec, unsigned p, long long linear) const;
+};
+__device__ __forceinline__ void VoxelEmit::operator()(int rec, unsigned p, long long linear) const {
 #pragma clang fp contract(off)
   const VoxelSide s = sides[rec];
   pts[p] = make_float4(s.cx, s.cy, s.cz, 1.0f);
@@ -282,53 +231,6 @@ __device__ __forceinline__ void voxel_emit(const VoxelSide* __restrict__ sides, 
   for (int t = 0; t < 6; t++) cov6[static_cast<size_t>(p) * 6 + t] = out[t];
 }
 
-// dense table: flag[t] = 1 where entry t is a record (flag has entries + 1 words, the last 0: its scan ends in the total)
-__global__ __launch_bounds__(kBlock) void k_voxel_mark(GridView gv, long long entries, unsigned* __restrict__ flag) {
-  for (long long t = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; t <= entries; t += static_cast<long long>(gridDim.x) * kBlock)
-    flag[t] = (t < entries && gv.lut[t] >= 0) ? 1u : 0u;
-}
-// ... and, the flags scanned in place: the padded table's order is the linear index's order (x fastest, then y, then z in both)
-__global__ __launch_bounds__(kBlock) void k_voxel_gather(GridView gv, long long entries, const unsigned* __restrict__ pos, double epsilon,
-                                                         int cov_mode, float4* __restrict__ pts, double* __restrict__ cov6,
-                                                         long long* __restrict__ idx, int* __restrict__ ord) {
-  for (long long t = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; t < entries; t += static_cast<long long>(gridDim.x) * kBlock) {
-    const int e = gv.lut[t];
-    if (e < 0) continue;
-    int x, y, z;
-    table_cell(gv, t, x, y, z);
-    const long long linear = static_cast<long long>(x) * gv.g.mul[0] + static_cast<long long>(y) * gv.g.mul[1] + static_cast<long long>(z) * gv.g.mul[2];
-    voxel_emit(gv.centroids, e, pos[t], linear, epsilon, cov_mode, pts, cov6, idx, ord);
-  }
-}
-// hash: every slot's (key, entry) for the sort -- a slot that is free, or holds no record, gets the key 0xffffffff, which sorts
-// behind every linear index -- and the count of the others
-__global__ __launch_bounds__(kBlock) void k_voxel_mark_hash(GridView gv, long long entries, unsigned* __restrict__ keys, int* __restrict__ vals,
-                                                            unsigned* __restrict__ count) {
-  int n = 0;
-  for (long long t = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; t < entries; t += static_cast<long long>(gridDim.x) * kBlock) {
-    const int2 s = reinterpret_cast<const int2*>(gv.lut)[t];
-    const bool in_d = s.x != -1 && s.y >= 0;
-    keys[t] = in_d ? static_cast<unsigned>(s.x) : 0xffffffffu;
-    vals[t] = s.y;
-    n += in_d ? 1 : 0;
-  }
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) n += __shfl_xor(n, off, kWave);
-  if ((threadIdx.x & (kWave - 1)) == 0 && n) atomicAdd(count, static_cast<unsigned>(n));
-}
-__global__ __launch_bounds__(kBlock) void k_voxel_gather_sorted(const VoxelSide* __restrict__ sides, const unsigned* __restrict__ keys,
-                                                                const int* __restrict__ vals, int n, double epsilon, int cov_mode,
-                                                                float4* __restrict__ pts, double* __restrict__ cov6,
-                                                                long long* __restrict__ idx, int* __restrict__ ord) {
-  const int p = blockIdx.x * kBlock + threadIdx.x;
-  if (p >= n) return;
-  voxel_emit(sides, vals[p], static_cast<unsigned>(p), static_cast<long long>(keys[p]), epsilon, cov_mode, pts, cov6, idx, ord);
-}
-
-dim3 voxel_table_grid(long long entries) {
-  return dim3(static_cast<unsigned>(std::max<long long>(1, std::min<long long>(4096, (entries + kBlock - 1) / kBlock))));
-}
-
 }  // namespace
 }  // namespace gicp
 
@@ -338,79 +240,34 @@ gicp::VoxelTarget voxel_view(const gicp_context* h) {
   const GridTarget& gt = h->grid_target;
   const DeviceGrid* g = gt.map->grid.get();
   gicp::VoxelTarget vt;
-  vt.ci.gv = g->view();
-  vt.ci.entries = table_entries(g);
-  vt.ci.give = index_slack(g) + g->excursion;
-  vt.ci.r_max = centroid_shell_limit(g);
+  vt.ci = centroid_index(g);
   vt.ord = gt.ord.p;
   vt.cov6 = gt.cov.p;
   return vt;
 }
 
-// D of `grid` into gt's arrays, on the main stream: one mark + scan (or sort) + gather, the count read back between them
+// D of `grid` into gt's arrays, on the main stream: one enumeration of the table's records (table_voxels).  Nothing waits for
+// the gather: what reads D next is queued on the same stream.
 ndt_status voxel_refresh(gicp_context* h, const std::shared_ptr<DeviceGrid>& grid) {
   GridTarget& gt = h->grid_target;
   DeviceGrid* g = grid.get();
-  hipStream_t st = h->tgt.stream;
   gt.valid = false;
   gt.n = 0;
   h->step_ready = false;  // (the ordinals a correspondence step wrote mean nothing in the new D)
-  const long long entries = table_entries(g);
-  const ndt::GridView gv = g->view();
-  const dim3 grid_dim = gicp::voxel_table_grid(entries);
   const double eps = h->prm.gicp_epsilon;
   HIP_TRY(gt.ord.reserve(std::max<size_t>(g->centroids.cap, 1)));
-  DevBuf<unsigned char> temp;
-  size_t tb = 0;
-  unsigned cnt = 0;
-  auto reserve_d = [&]() -> hipError_t {
-    for (hipError_t e : {gt.pts.reserve(cnt), gt.cov.reserve(static_cast<size_t>(cnt) * 6), gt.idx.reserve(cnt)})
-      if (e != hipSuccess) return e;
-    return hipSuccess;
-  };
-  if (g->geom.hash_bits) {
-    if (entries > std::numeric_limits<int>::max()) return fail(NDT_ERR_INVALID, "the voxel hash is too large to sort");
-    const int slots = static_cast<int>(entries);
-    DevBuf<unsigned> keys_a, keys_b, count;
-    DevBuf<int> vals_a, vals_b;
-    HIP_TRY(keys_a.reserve(slots));
-    HIP_TRY(vals_a.reserve(slots));
-    HIP_TRY(keys_b.reserve(slots));
-    HIP_TRY(vals_b.reserve(slots));
-    HIP_TRY(count.reserve(1));
-    HIP_TRY(hipMemsetAsync(count.p, 0, sizeof(unsigned), st));
-    hipLaunchKernelGGL(gicp::k_voxel_mark_hash, grid_dim, dim3(ndt::kBlock), 0, st, gv, entries, keys_a.p, vals_a.p, count.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys_a.p, keys_b.p, vals_a.p, vals_b.p, slots, 0, 32, st));
-    HIP_TRY(temp.reserve(tb + 256));
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(temp.p, tb, keys_a.p, keys_b.p, vals_a.p, vals_b.p, slots, 0, 32, st));
-    HIP_TRY(hipMemcpyAsync(&cnt, count.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (cnt) {
-      HIP_TRY(reserve_d());
-      hipLaunchKernelGGL(gicp::k_voxel_gather_sorted, dim3((cnt + ndt::kBlock - 1) / ndt::kBlock), dim3(ndt::kBlock), 0, st, gv.centroids, keys_b.p,
-                         vals_b.p, static_cast<int>(cnt), eps, gt.cov_mode, gt.pts.p, gt.cov.p, gt.idx.p, gt.ord.p);
-      HIP_TRY(hipGetLastError());
-    }
-  } else {
-    if (entries + 1 > std::numeric_limits<int>::max()) return fail(NDT_ERR_INVALID, "the voxel table is too large to scan");
-    DevBuf<unsigned> pos;
-    HIP_TRY(pos.reserve(static_cast<size_t>(entries) + 1));
-    hipLaunchKernelGGL(gicp::k_voxel_mark, grid_dim, dim3(ndt::kBlock), 0, st, gv, entries, pos.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, pos.p, pos.p, static_cast<int>(entries + 1), st));
-    HIP_TRY(temp.reserve(tb + 256));
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(temp.p, tb, pos.p, pos.p, static_cast<int>(entries + 1), st));
-    HIP_TRY(hipMemcpyAsync(&cnt, pos.p + entries, sizeof(cnt), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (cnt) {
-      HIP_TRY(reserve_d());
-      hipLaunchKernelGGL(gicp::k_voxel_gather, grid_dim, dim3(ndt::kBlock), 0, st, gv, entries, pos.p, eps, gt.cov_mode, gt.pts.p, gt.cov.p,
-                         gt.idx.p, gt.ord.p);
-      HIP_TRY(hipGetLastError());
-    }
-  }
-  // (the scratch goes back to the pool behind the gather, in stream order)
+  size_t cnt = 0;
+  const ndt_status s = table_voxels<gicp::IsRecord, gicp::VoxelEmit>(
+      h->tgt.stream, g, true,
+      [&](unsigned n, gicp::VoxelEmit& emit) -> hipError_t {
+        HIP_PASS(gt.pts.reserve(n));
+        HIP_PASS(gt.cov.reserve(static_cast<size_t>(n) * 6));
+        HIP_PASS(gt.idx.reserve(n));
+        emit = {g->view().centroids, eps, gt.cov_mode, gt.pts.p, gt.cov.p, gt.idx.p, gt.ord.p};
+        return hipSuccess;
+      },
+      &cnt);
+  if (s) return s;
   gt.n = cnt;
   gt.seen = grid;
   gt.seen_generation = g->generation;

@@ -1,9 +1,8 @@
-// ndt_acc_kernels.hip -- HIP kernels of the accumulating target and the launch functions over them (hipCUB's radix sort and
-// scan included).  What each call queues, and in which order, is told where the host decides: ndt_accumulate.hip, ndt_acc_persist.hip
-#include <hipcub/hipcub.hpp>
-
+// ndt_acc_kernels.hip -- HIP kernels of the accumulating target and the launch functions over them (the radix sort and
+// scan of ndt_prims.hpp included).  What each call queues, and in which order, is told where the host decides: ndt_accumulate.hip, ndt_acc_persist.hip
 #include "ndt_acc.hpp"
 #include "ndt_acc_device.hpp"
+#include "ndt_prims.hpp"
 #include "ndt_voxel_finish.hpp"
 
 namespace ndt {
@@ -384,19 +383,16 @@ hipError_t launch_acc_bin(const float4* posed, int n, float inv_leaf, const AccV
   unsigned *flags = b.w.p, *ord = b.w.p + N, *is_new = b.w.p + 3 * N;
   b.run_start = b.w.p + 2 * N;
   b.new_rank = b.w.p + 4 * N;
-  size_t tb_sort = 0, tb_scan = 0;
-  HIP_PASS(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, keys_a.p, b.keys.p, vals_a.p, b.sorted_idx.p, n, 0, 64, st));
-  HIP_PASS(hipcub::DeviceScan::ExclusiveSum(nullptr, tb_scan, flags, ord, n, st));
-  size_t tb = std::max(tb_sort, tb_scan) + 256;  // (in and out for hipCUB, written only by the size queries above)
+  const size_t tb = std::max(sort_pairs_temp_bytes(n, sizeof(unsigned long long)), exclusive_sum_temp_bytes(n));
   HIP_PASS(temp.reserve(tb));
   HIP_PASS(hipMemsetAsync(b.counts.p, 0, 4 * sizeof(unsigned), st));
   HIP_PASS(hipMemsetAsync(is_new, 0, N * sizeof(unsigned), st));
   hipLaunchKernelGGL(k_acc_keys, dim3(acc_grid_for(N, 2048)), dim3(kBlock), 0, st, posed, n, inv_leaf, keys_a.p, vals_a.p, info);
-  HIP_PASS(hipcub::DeviceRadixSort::SortPairs(temp.p, tb, keys_a.p, b.keys.p, vals_a.p, b.sorted_idx.p, n, 0, 64, st));
+  HIP_PASS(sort_pairs(keys_a.p, b.keys.p, vals_a.p, b.sorted_idx.p, n, 64, temp.p, tb, st));
   hipLaunchKernelGGL(k_acc_heads, dim3(acc_grid_for(N, 2048)), dim3(kBlock), 0, st, b.keys.p, n, flags, b.counts.p);
-  HIP_PASS(hipcub::DeviceScan::ExclusiveSum(temp.p, tb, flags, ord, n, st));
+  HIP_PASS(exclusive_sum(flags, ord, n, temp.p, tb, st));
   hipLaunchKernelGGL(k_acc_runs, dim3(acc_grid_for(N, 2048)), dim3(kBlock), 0, st, b.keys.p, flags, ord, n, v, b.run_start, b.run_slot.p, is_new, b.counts.p);
-  HIP_PASS(hipcub::DeviceScan::ExclusiveSum(temp.p, tb, is_new, b.new_rank, n, st));
+  HIP_PASS(exclusive_sum(is_new, b.new_rank, n, temp.p, tb, st));
   hipLaunchKernelGGL(k_acc_new_total, dim3(1), dim3(1), 0, st, is_new, b.new_rank, b.counts.p);
   return hipGetLastError();
 }
@@ -412,19 +408,18 @@ hipError_t launch_acc_mark(const AccView& v, int n_slots, const AccCropBox& box,
     HIP_PASS(keys_b.reserve(S));
     HIP_PASS(vals_a.reserve(S));
     HIP_PASS(vals_b.reserve(S));
-    HIP_PASS(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys_a.p, keys_b.p, vals_a.p, vals_b.p, n_slots, 0, 64, st));
+    tb = sort_pairs_temp_bytes(n_slots, sizeof(unsigned long long));
   } else if (number) {
-    HIP_PASS(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, keep, number, n_slots, st));
+    tb = exclusive_sum_temp_bytes(n_slots);
   }
-  tb += 256;
   if (rows || number) HIP_PASS(temp.reserve(tb));
   hipLaunchKernelGGL(k_acc_crop_mark, acc_blocks(S), dim3(kBlock), 0, st, v.cell, n_slots, box, keep, info, keys_a.p, vals_a.p);
   HIP_PASS(hipGetLastError());
   if (rows) {
-    HIP_PASS(hipcub::DeviceRadixSort::SortPairs(temp.p, tb, keys_a.p, keys_b.p, vals_a.p, vals_b.p, n_slots, 0, 64, st));
+    HIP_PASS(sort_pairs(keys_a.p, keys_b.p, vals_a.p, vals_b.p, n_slots, 64, temp.p, tb, st));
     hipLaunchKernelGGL(k_acc_export_gather, acc_blocks(S), dim3(kBlock), 0, st, v, vals_b.p, info, n_slots, rows);
   } else if (number) {
-    HIP_PASS(hipcub::DeviceScan::ExclusiveSum(temp.p, tb, keep, number, n_slots, st));
+    HIP_PASS(exclusive_sum(keep, number, n_slots, temp.p, tb, st));
   }
   return hipGetLastError();
 }

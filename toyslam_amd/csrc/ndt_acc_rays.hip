@@ -10,10 +10,9 @@
 //                    not depend on the order.  No barrier: lanes leave the walk at different steps; the three totals (cast,
 //                    skipped, visited) are folded in the wave after the loop, one 64-bit atomic per wave and word.
 //   k_acc_rays_mark  k_acc_crop_mark with the predicate miss < min_rays || hit: the same fold into the info block
-#include <hipcub/hipcub.hpp>
-
 #include "ndt_acc.hpp"
 #include "ndt_acc_device.hpp"
+#include "ndt_prims.hpp"
 #include "ndt_rays.hpp"
 
 namespace ndt {
@@ -143,14 +142,12 @@ hipError_t launch_acc_rays(const AccRayScan& one, const AccRayScan* d_scans, int
 hipError_t launch_acc_rays_mark(const AccView& v, int n_slots, const unsigned* miss, const unsigned* hit, int min_rays, unsigned* keep, int* info,
                                 unsigned* number, hipStream_t st) {
   ndtc::DevBuf<unsigned char> temp;
-  size_t tb = 0;
-  HIP_PASS(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, keep, number, n_slots, st));
-  tb += 256;
+  const size_t tb = exclusive_sum_temp_bytes(n_slots);
   HIP_PASS(temp.reserve(tb));
   const int blocks = std::max(1, (n_slots + kBlock - 1) / kBlock);
   hipLaunchKernelGGL(k_acc_rays_mark, dim3(blocks), dim3(kBlock), 0, st, v.cell, n_slots, miss, hit, static_cast<unsigned>(min_rays), keep, info);
   HIP_PASS(hipGetLastError());
-  HIP_PASS(hipcub::DeviceScan::ExclusiveSum(temp.p, tb, keep, number, n_slots, st));
+  HIP_PASS(exclusive_sum(keep, number, n_slots, temp.p, tb, st));
   return hipGetLastError();
 }
 

@@ -11,7 +11,9 @@
 // compacted have none either.  No per-map index is built; nothing is rebuilt when the map changes.
 //   search   : k_centroid_fitness_multi -- per query cubic shells of cells through the table, a candidate per occupied entry
 //              (centroids[r]); a team of 8 lanes for shells 0..2, the whole wave for the far queries, queries dealt in
-//              bit-reversed order, a row per block (block_reduce_store), then k_fitness_reduce: k_fitness's shape
+//              bit-reversed order, a row per block (block_reduce_store), then k_fitness_reduce: k_fitness's shape.  The walk
+//              of a shell and the pass over the table are ndt_voxel_table.hpp's (table_shell, wave_scan_table) under the policy
+//              NearestCentroid; which shells the team walks, when the wave takes over and the stopping rule are this kernel's
 //   excursion: the table is keyed by the cell the POINTS fell into; the centroid is an f32 running sum over the count and, far
 //              from the origin, drifts out of that cell (by cells, not ulps).  The stopping rule and the pruning of rows and
 //              cells give way by the grid's excursion -- the largest per-axis distance by which a centroid lies outside its
@@ -20,14 +22,12 @@
 //   cost rule: shells 0..r probe up to (2r+1)^3 entries one scattered load each; one pass over the table reads `entries`
 //              words coalesced.  Shells are walked while (2r+1)^3 <= entries / 4 (but at least kKnnMinRing shells, at most
 //              the grid's extent); a query still open then takes ONE scan of the table by its whole wave (centroid_shell_limit)
-//   gather   : ndt_grid_centroids* -- dense: mark + exclusive scan + gather over the padded table, whose order IS the linear
-//              index order; sparse: the occupied hash slots sorted by key (hipCUB), then gathered; one read-back of the count
+//   gather   : ndt_grid_centroids* -- table_voxels (ndt_table_voxels.hpp) over the occupied entries with CentroidEmit; dense:
+//              mark + exclusive scan + gather over the padded table, whose order IS the linear index order; sparse: the
+//              occupied hash slots sorted by key, then gathered; one read-back of the count
 // None of these calls touches the handle's target, source, grid, last result or statistics.
-#include <hipcub/hipcub.hpp>
-
 #include "ndt_acc.hpp"
-#include "ndt_search.hpp"
-#include "ndt_voxel_table.hpp"
+#include "ndt_table_voxels.hpp"
 
 namespace ndt {
 
@@ -39,70 +39,18 @@ struct CentroidMember {
 
 namespace {
 
-// Shell r of cells around (cx, cy, cz): its (2r+1)^2 rows dealt to the TEAM lanes; a lane walks its row (a face row: every x;
-// an interior row: x = -r and +r) kProbes cells at a time -- the table loads together, then the centroid loads of the occupied
-// ones together -- and keeps its own best.  No lane needs another inside the walk: the team combines after it.  Rows and cells
-// whose box, widened by ci.give, lies farther than bound2 are not looked up.
-template <int TEAM>
-__device__ __forceinline__ void centroid_shell(const CentroidIndex& ci, int cx, int cy, int cz, int r, int sub, float qx, float qy,
-                                               float qz, float bound2, float& best) {
-  const GridGeom& g = ci.gv.g;
-  const int w = 2 * r + 1, rows = w * w;
-  for (int row = sub; row < rows; row += TEAM) {
-    const int dz = row / w - r, dy = row % w - r;
-    const int z = cz + dz, y = cy + dy;
-    if (z < 0 || z >= g.div_b[2] || y < 0 || y >= g.div_b[1]) continue;
-    const float gy = axis_gap(qy, y + g.min_b[1], g.leaf[1], ci.give), gz = axis_gap(qz, z + g.min_b[2], g.leaf[2], ci.give);
-    const float row_d2 = gy * gy + gz * gz;
-    if (row_d2 > bound2) continue;
-    const bool face = (dz == -r || dz == r || dy == -r || dy == r);  // r == 0: the single row is a face row
-    const int nx = face ? w : 2;
-    for (int t = 0; t < nx; t += kProbes) {
-      int e[kProbes];
-#pragma unroll
-      for (int u = 0; u < kProbes; u++) {
-        e[u] = kLutEmpty;
-        const int tt = t + u;
-        const int x = cx + (face ? tt - r : (tt == 0 ? -r : r));
-        if (tt < nx && x >= 0 && x < g.div_b[0]) {
-          const float gx = axis_gap(qx, x + g.min_b[0], g.leaf[0], ci.give);
-          if (row_d2 + gx * gx <= bound2) e[u] = cell_entry(ci.gv, x, y, z);
-        }
-      }
-      float4 c[kProbes];
-#pragma unroll
-      for (int u = 0; u < kProbes; u++)
-        if (e[u] != kLutEmpty) c[u] = *reinterpret_cast<const float4*>(ci.gv.centroids + entry_record(e[u]));  // (cx, cy, cz, -)
-#pragma unroll
-      for (int u = 0; u < kProbes; u++)
-        if (e[u] != kLutEmpty) best = fminf(best, dist2_f32(qx, qy, qz, c[u].x, c[u].y, c[u].z));
-    }
-  }
-}
-
-// ONE pass over the table by the whole wave (every lane with the same query): the nearest centroid's squared distance, in all lanes
-__device__ __forceinline__ float wave_scan_table(const CentroidIndex& ci, float qx, float qy, float qz) {
-  const int lane = threadIdx.x & (kWave - 1);
-  float best = INFINITY;
-  for (long long base = 0; base < ci.entries; base += kProbes * kWave) {
-    int e[kProbes];
-#pragma unroll
-    for (int u = 0; u < kProbes; u++) {
-      const long long t = base + lane + u * kWave;
-      e[u] = t < ci.entries ? table_entry(ci.gv, t) : kLutEmpty;
-    }
-    float4 c[kProbes];
-#pragma unroll
-    for (int u = 0; u < kProbes; u++)
-      if (e[u] != kLutEmpty) c[u] = *reinterpret_cast<const float4*>(ci.gv.centroids + entry_record(e[u]));
-#pragma unroll
-    for (int u = 0; u < kProbes; u++)
-      if (e[u] != kLutEmpty) best = fminf(best, dist2_f32(qx, qy, qz, c[u].x, c[u].y, c[u].z));
-  }
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) best = fminf(best, __shfl_xor(best, off, kWave));
-  return best;
-}
+// The search policy of the centroid fitness (ndt_voxel_table.hpp): every occupied entry is a candidate -- a rejected voxel's
+// centroid is in C -- and the squared distance alone is carried, by fminf (a NaN centroid never wins)
+struct NearestCentroid {
+  using Best = float;
+  struct Side {};
+  __device__ static Best none() { return INFINITY; }
+  __device__ static bool candidate(int e) { return e != kLutEmpty; }
+  __device__ static int record(int e) { return entry_record(e); }
+  __device__ Side side(int) const { return Side{}; }
+  __device__ static void take(float d, Side, Best& best) { best = fminf(best, d); }
+  __device__ static void fold(Best& best, int off) { best = fminf(best, __shfl_xor(best, off, kWave)); }
+};
 
 // Many members against ONE centroid index in one launch: member m owns blocks [starts[m], starts[m + 1]) and block b's row is
 // partials[b] (k_fitness_multi's layout: k_fitness_reduce sums it).  acc[0] = sum of the accepted squared distances, acc[1] =
@@ -130,6 +78,7 @@ __global__ __launch_bounds__(kBlock) void k_centroid_fitness_multi(const Centroi
   const float leaf = fminf(g.leaf[0], fminf(g.leaf[1], g.leaf[2]));
   const int r_lim = max(g.div_b[0], max(g.div_b[1], g.div_b[2]));
   const int r_max = ci.r_max;
+  const NearestCentroid nearest;
   const int wave_in_block = threadIdx.x / kWave, team_in_wave = (threadIdx.x & (kWave - 1)) / kTeam;
   const int lane = threadIdx.x & (kWave - 1);
   // queries dealt to the teams in BIT-REVERSED order: the far queries of a scan come in runs (see k_fitness)
@@ -154,7 +103,7 @@ __global__ __launch_bounds__(kBlock) void k_centroid_fitness_multi(const Centroi
       float best = INFINITY;  // this lane's share of the candidates
       query_cell(g, tx, ty, tz, cx, cy, cz, margin);
       for (int r = 0; r <= min(r_max, kTeamShells) && !done; r++) {
-        centroid_shell<kTeam>(ci, cx, cy, cz, r, sub, tx, ty, tz, tb, best);  // (tb: the team's best after the previous shell)
+        table_shell<kTeam>(ci, nearest, cx, cy, cz, r, sub, tx, ty, tz, tb, best);  // (tb: the team's best after the previous shell)
         tb = best;
 #pragma unroll
         for (int off = 1; off < kTeam; off <<= 1) tb = fminf(tb, __shfl_xor(tb, off, kWave));
@@ -174,7 +123,7 @@ __global__ __launch_bounds__(kBlock) void k_centroid_fitness_multi(const Centroi
       float wbest = INFINITY;
       bool wdone = false;
       for (int r = kTeamShells + 1; r <= r_max && !wdone; r++) {
-        centroid_shell<kWave>(ci, qi, qj, qk, r, lane, qx, qy, qz, wb, wbest);
+        table_shell<kWave>(ci, nearest, qi, qj, qk, r, lane, qx, qy, qz, wb, wbest);
         float m = wbest;
 #pragma unroll
         for (int off = 1; off < kWave; off <<= 1) m = fminf(m, __shfl_xor(m, off, kWave));
@@ -182,7 +131,7 @@ __global__ __launch_bounds__(kBlock) void k_centroid_fitness_multi(const Centroi
         const float reach = static_cast<float>(r) * leaf + q_margin - ci.give;
         if ((reach > 0.0f && wb <= reach * reach) || r >= r_lim) wdone = true;
       }
-      if (!wdone) wb = wave_scan_table(ci, qx, qy, qz);  // the shells got dearer than the table itself: one pass over it
+      if (!wdone) wb = wave_scan_table(ci, nearest, qx, qy, qz);  // the shells got dearer than the table itself: one pass over it
       if (lane / kTeam == src_lane / kTeam) tb = wb;
     }
     if (live && sub == 0 && static_cast<double>(tb) <= max_range) {  // the squared distance against max_range, as PCL does
@@ -224,53 +173,21 @@ __global__ __launch_bounds__(kBlock) void k_centroid_excursion(GridView gv, long
   }
 }
 
-// ---- the centroid cloud
-// dense table: flag[t] = 1 where entry t is occupied (flag has entries + 1 words, the last 0: its scan ends in the total)
-__global__ __launch_bounds__(kBlock) void k_centroid_mark(GridView gv, long long entries, unsigned* __restrict__ flag) {
-  for (long long t = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; t <= entries; t += static_cast<long long>(gridDim.x) * kBlock)
-    flag[t] = (t < entries && gv.lut[t] != kLutEmpty) ? 1u : 0u;
-}
-// ... and, the flags scanned in place: entry t's centroid and linear index to position pos[t].  The padded table's order is the
-// linear index's order (x fastest, then y, then z in both)
-__global__ __launch_bounds__(kBlock) void k_centroid_gather(GridView gv, long long entries, const unsigned* __restrict__ pos,
-                                                            float4* __restrict__ out, long long* __restrict__ idx) {
-  for (long long t = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; t < entries; t += static_cast<long long>(gridDim.x) * kBlock) {
-    const int e = gv.lut[t];
-    if (e == kLutEmpty) continue;
-    int x, y, z;
-    table_cell(gv, t, x, y, z);
-    const float4 c = *reinterpret_cast<const float4*>(gv.centroids + entry_record(e));
-    const unsigned p = pos[t];
+// ---- the centroid cloud (ndt_table_voxels.hpp): every occupied entry, its centroid and / or linear index to its position
+struct Occupied {
+  __device__ static bool pick(int e) { return e != kLutEmpty; }
+};
+struct CentroidEmit {
+  const VoxelSide* centroids;
+  float4* out;     // or null
+  long long* idx;  // or null
+  __device__ void operator()(int rec, unsigned p, long long linear) const {
+    const float4 c = *reinterpret_cast<const float4*>(centroids + rec);
     if (out) out[p] = make_float4(c.x, c.y, c.z, 1.0f);
-    if (idx) idx[p] = static_cast<long long>(x) * gv.g.mul[0] + static_cast<long long>(y) * gv.g.mul[1] + static_cast<long long>(z) * gv.g.mul[2];
+    if (idx) idx[p] = linear;
   }
-}
-// hash: every slot's (key, entry) for the sort -- a free slot's key 0xffffffff sorts behind every linear index -- and the count
-__global__ __launch_bounds__(kBlock) void k_centroid_mark_hash(GridView gv, long long entries, unsigned* __restrict__ keys,
-                                                               int* __restrict__ vals, unsigned* __restrict__ count) {
-  int n = 0;
-  for (long long t = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; t < entries; t += static_cast<long long>(gridDim.x) * kBlock) {
-    const int2 s = reinterpret_cast<const int2*>(gv.lut)[t];
-    const bool occupied = s.x != -1 && s.y != kLutEmpty;
-    keys[t] = occupied ? static_cast<unsigned>(s.x) : 0xffffffffu;
-    vals[t] = s.y;
-    n += occupied ? 1 : 0;
-  }
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) n += __shfl_xor(n, off, kWave);
-  if ((threadIdx.x & (kWave - 1)) == 0 && n) atomicAdd(count, static_cast<unsigned>(n));
-}
-__global__ __launch_bounds__(kBlock) void k_centroid_gather_sorted(const VoxelSide* __restrict__ centroids, const unsigned* __restrict__ keys,
-                                                                   const int* __restrict__ vals, int n, float4* __restrict__ out,
-                                                                   long long* __restrict__ idx) {
-  const int p = blockIdx.x * kBlock + threadIdx.x;
-  if (p >= n) return;
-  const float4 c = *reinterpret_cast<const float4*>(centroids + entry_record(vals[p]));
-  if (out) out[p] = make_float4(c.x, c.y, c.z, 1.0f);
-  if (idx) idx[p] = static_cast<long long>(keys[p]);
-}
+};
 
-dim3 table_grid(long long entries) { return dim3(static_cast<unsigned>(std::max<long long>(1, std::min<long long>(4096, (entries + kBlock - 1) / kBlock)))); }
 
 }  // namespace
 }  // namespace ndt
@@ -287,6 +204,16 @@ int centroid_shell_limit(const DeviceGrid* g) {
   int r = 0;
   while (r < r_lim && static_cast<long long>(2 * r + 3) * (2 * r + 3) * (2 * r + 3) <= budget) r++;
   return std::min(r_lim, std::max(ndt::kKnnMinRing, r));
+}
+
+// g's table as the centroid searches walk it (its excursion known: ensure_excursion)
+ndt::CentroidIndex centroid_index(const DeviceGrid* g) {
+  ndt::CentroidIndex ci;
+  ci.gv = g->view();
+  ci.entries = table_entries(g);
+  ci.give = index_slack(g) + g->excursion;
+  ci.r_max = centroid_shell_limit(g);
+  return ci;
 }
 
 // the grid's excursion, computed when unknown or stale: one launch and one read-back
@@ -349,11 +276,7 @@ ndt_status centroid_fitness_many(ndt_context* h, DeviceGrid* g, const std::vecto
   const size_t n_mem = mem.size();
   s = ensure_host_rows(h, (2 * n_mem + ndt::kEvalStride - 1) / ndt::kEvalStride);
   if (s) return s;
-  ndt::CentroidIndex ci;
-  ci.gv = g->view();
-  ci.entries = table_entries(g);
-  ci.give = index_slack(g) + g->excursion;
-  ci.r_max = centroid_shell_limit(g);
+  const ndt::CentroidIndex ci = centroid_index(g);
   DevBuf<ndt::CentroidMember> d_mem;
   DevBuf<int> d_starts;
   HIP_TRY(d_mem.reserve(n_mem));
@@ -403,65 +326,21 @@ ndt_status batch_centroid_fitness_impl(ndt_handle h, const void* pts, const size
 }
 
 // C on the device: its points (x, y, z, 1) and / or linear indices, *n of them.  want == false: the count alone.
-// One mark + scan (or sort) + gather, and the read-back of the count between them.
+// One enumeration of the occupied entries (table_voxels), then the wait for the gather: the caller copies next.
 ndt_status centroids_device(ndt_context* h, DeviceGrid* g, bool want, DevBuf<float4>& xyz1, DevBuf<long long>* idx, size_t* n) {
   *n = 0;
   if (g->empty) return NDT_OK;
-  hipStream_t st = h->stream;
-  const long long entries = table_entries(g);
-  const ndt::GridView gv = g->view();
-  const dim3 grid = ndt::table_grid(entries);
-  DevBuf<unsigned char> temp;
-  size_t tb = 0;
-  if (g->geom.hash_bits) {
-    if (entries > std::numeric_limits<int>::max()) return fail(NDT_ERR_INVALID, "the voxel hash is too large to sort");
-    const int slots = static_cast<int>(entries);
-    DevBuf<unsigned> keys_a, keys_b, count;
-    DevBuf<int> vals_a, vals_b;
-    HIP_TRY(keys_a.reserve(slots));
-    HIP_TRY(vals_a.reserve(slots));
-    HIP_TRY(count.reserve(1));
-    HIP_TRY(hipMemsetAsync(count.p, 0, sizeof(unsigned), st));
-    hipLaunchKernelGGL(ndt::k_centroid_mark_hash, grid, dim3(ndt::kBlock), 0, st, gv, entries, keys_a.p, vals_a.p, count.p);
-    HIP_TRY(hipGetLastError());
-    if (want) {
-      HIP_TRY(keys_b.reserve(slots));
-      HIP_TRY(vals_b.reserve(slots));
-      HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys_a.p, keys_b.p, vals_a.p, vals_b.p, slots, 0, 32, st));
-      HIP_TRY(temp.reserve(tb + 256));
-      HIP_TRY(hipcub::DeviceRadixSort::SortPairs(temp.p, tb, keys_a.p, keys_b.p, vals_a.p, vals_b.p, slots, 0, 32, st));
-    }
-    unsigned cnt = 0;
-    HIP_TRY(hipMemcpyAsync(&cnt, count.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *n = cnt;
-    if (!want || cnt == 0) return NDT_OK;
-    HIP_TRY(xyz1.reserve(cnt));
-    if (idx) HIP_TRY(idx->reserve(cnt));
-    hipLaunchKernelGGL(ndt::k_centroid_gather_sorted, dim3((cnt + ndt::kBlock - 1) / ndt::kBlock), dim3(ndt::kBlock), 0, st, gv.centroids, keys_b.p,
-                       vals_b.p, static_cast<int>(cnt), xyz1.p, idx ? idx->p : nullptr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));  // (the sorted pairs go back to the pool behind the gather in any case; the caller copies next)
-    return NDT_OK;
-  }
-  if (entries + 1 > std::numeric_limits<int>::max()) return fail(NDT_ERR_INVALID, "the voxel table is too large to scan");
-  DevBuf<unsigned> pos;
-  HIP_TRY(pos.reserve(static_cast<size_t>(entries) + 1));
-  hipLaunchKernelGGL(ndt::k_centroid_mark, grid, dim3(ndt::kBlock), 0, st, gv, entries, pos.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, pos.p, pos.p, static_cast<int>(entries + 1), st));
-  HIP_TRY(temp.reserve(tb + 256));
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(temp.p, tb, pos.p, pos.p, static_cast<int>(entries + 1), st));
-  unsigned cnt = 0;
-  HIP_TRY(hipMemcpyAsync(&cnt, pos.p + entries, sizeof(cnt), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  *n = cnt;
-  if (!want || cnt == 0) return NDT_OK;
-  HIP_TRY(xyz1.reserve(cnt));
-  if (idx) HIP_TRY(idx->reserve(cnt));
-  hipLaunchKernelGGL(ndt::k_centroid_gather, grid, dim3(ndt::kBlock), 0, st, gv, entries, pos.p, xyz1.p, idx ? idx->p : nullptr);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(st));
+  const ndt_status s = table_voxels<ndt::Occupied, ndt::CentroidEmit>(
+      h->stream, g, want,
+      [&](unsigned cnt, ndt::CentroidEmit& emit) -> hipError_t {
+        HIP_PASS(xyz1.reserve(cnt));
+        if (idx) HIP_PASS(idx->reserve(cnt));
+        emit = {g->view().centroids, xyz1.p, idx ? idx->p : nullptr};
+        return hipSuccess;
+      },
+      n);
+  if (s) return s;
+  if (want && *n) HIP_TRY(hipStreamSynchronize(h->stream));
   return NDT_OK;
 }
 

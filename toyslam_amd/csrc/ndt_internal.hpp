@@ -599,6 +599,8 @@ struct ndt_context {
   void release_buffers();
 };
 
+namespace ndt { struct CentroidIndex; }  // ndt_voxel_table.hpp
+
 namespace ndtc {
 // ---- ndt_handle.hip
 int usable_devices();
@@ -708,6 +710,8 @@ long long table_entries(const DeviceGrid* g);    // entries one pass over g's lo
 int centroid_shell_limit(const DeviceGrid* g);   // shells a centroid search walks before the one pass over the table
 // g's centroid excursion, computed on h's stream when unknown or stale (one launch, one read-back, waited for)
 ndt_status ensure_excursion(ndt_context* h, DeviceGrid* g);
+// g's table as the centroid searches walk it: view, table_entries, index_slack + excursion (ensure_excursion first), shell limit
+ndt::CentroidIndex centroid_index(const DeviceGrid* g);
 // ---- ndt_score.hip
 // poses per launch of ndt_score_poses and ndt_nvtl_poses: one rule, one switch (NDT_SCORE_POSES_CHUNK)
 size_t poses_chunk(size_t n_poses, size_t row_bytes);

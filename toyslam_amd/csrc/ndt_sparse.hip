@@ -4,15 +4,14 @@
 //
 // The dense forms of K1 keep per-CELL arrays (counters, the look-up table); here everything is per POINT:
 //   keys      linear voxel index of every point (the build's index math, trap 2), invalid points last
-//   sort      stable LSD radix sort of (key, point index) pairs -- rocPRIM's device-wide sort through hipCUB, the one
-//             library primitive of this repository's kernels: a plain sort, nothing NDT-specific to fuse into it.
+//   sort      stable LSD radix sort of (key, point index) pairs -- rocPRIM's device-wide sort through hipCUB (ndt_prims.hpp), the
+//             one library primitive of this repository's kernels: a plain sort, nothing NDT-specific to fuse into it.
 //             Stable, so the points of a voxel come out in ascending point order: the order the reference adds them in
 //   segments  heads of equal-key runs -> leaf arrays (cell, start, count, record slot) in ascending voxel order
 // and the derivative kernels find a voxel through an open-addressing hash table keyed by the same linear index
 // (GridView::hash, filled by the finalize pass) instead of the padded dense table.
-#include <hipcub/hipcub.hpp>
-
 #include "ndt_device.hpp"
+#include "ndt_prims.hpp"
 
 namespace ndt {
 
@@ -90,13 +89,7 @@ inline int grid_for_n(size_t n, int cap) {
 
 }  // namespace
 
-size_t sparse_index_temp_bytes(int n) {
-  size_t a = 0, b = 0;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, a, static_cast<const unsigned*>(nullptr), static_cast<unsigned*>(nullptr),
-                                           static_cast<const int*>(nullptr), static_cast<int*>(nullptr), n, 0, 31);
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, static_cast<const unsigned*>(nullptr), static_cast<unsigned*>(nullptr), n);
-  return std::max(a, b) + 256;
-}
+size_t sparse_index_temp_bytes(int n) { return std::max(sort_pairs_temp_bytes(n, sizeof(unsigned)), exclusive_sum_temp_bytes(n)); }
 
 hipError_t launch_sparse_index(const float4* pts, int n, int dense, const GridGeom& g, int min_pts, void* temp, size_t temp_bytes,
                                unsigned* keys_a, unsigned* keys_b, int* vals_a, unsigned* flags, unsigned* ord, int* leaf_cell,
@@ -109,12 +102,10 @@ hipError_t launch_sparse_index(const float4* pts, int n, int dense, const GridGe
   int bits = 1;
   while (bits < 31 && (1ll << bits) < g.n_cells) bits++;
   bits = 31;  // the invalid key (0x7fffffff) must sort last: all 31 bits take part
-  size_t tb = temp_bytes;
-  e = hipcub::DeviceRadixSort::SortPairs(temp, tb, keys_a, keys_b, vals_a, sorted_idx, n, 0, bits, stream);
+  e = sort_pairs(keys_a, keys_b, vals_a, sorted_idx, n, bits, temp, temp_bytes, stream);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_sp_heads, dim3(grid_for_n(n, 2048)), dim3(kBlock), 0, stream, keys_b, n, flags, counts);
-  tb = temp_bytes;
-  e = hipcub::DeviceScan::ExclusiveSum(temp, tb, flags, ord, n, stream);
+  e = exclusive_sum(flags, ord, n, temp, temp_bytes, stream);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_sp_leaves, dim3(grid_for_n(n, 2048)), dim3(kBlock), 0, stream, keys_b, flags, ord, n, leaf_cell, leaf_start, counts);
   hipLaunchKernelGGL(k_sp_counts, dim3(grid_for_n(n, 1024)), dim3(kBlock), 0, stream, leaf_start, counts, min_pts, leaf_count, leaf_rec, counts);
