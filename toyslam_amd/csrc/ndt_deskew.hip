@@ -10,7 +10,8 @@
 //   block  : wave folds, then one row of 12 floats and the untimed count, written straight into page-locked memory and read
 //            behind the call's one wait; the host folds the rows.  No global atomics, no second pass.
 // The rest of the file is host only: the motion of a sweep from a registration increment (ndt_host_deskew_motion), the body for
-// one point and the plan.  The entries that fetch the per-point times are in ndt_io.hip.
+// one point and the plan.  The entries that fetch the per-point times are in ndt_io.hip.  The member table, the box fold
+// (device and host), the output slices and the entry preambles are ndt_cloud_ops.hpp / .hip's.
 #include "ndt_internal.hpp"
 #include "ndt_deskew.hpp"
 #include "ndt_device.hpp"
@@ -34,18 +35,15 @@ struct DskSeg {
 __global__ __launch_bounds__(kDskBlock) void k_deskew(DskSeg one, const DskSeg* __restrict__ segs, int n_segs, float* __restrict__ rows) {
   __shared__ float wave_box[kDskWaves][12];
   __shared__ unsigned wave_untimed[kDskWaves];
-  const DskSeg g = n_segs == 1 ? one : segs[ndt::member_at(n_segs, blockIdx.x, [&](int s) { return segs[s].first_block; })];
-  const int lb = static_cast<int>(blockIdx.x) - g.first_block;
-  const long long start = static_cast<long long>(lb) * g.ppb;
-  const int len = static_cast<int>(min(static_cast<long long>(g.ppb), g.n - start));
+  const DskSeg g = ndt::block_member(one, segs, n_segs, blockIdx.x, &DskSeg::first_block);
+  long long start;
+  const int len = ndt::block_range(static_cast<int>(blockIdx.x) - g.first_block, g.ppb, g.n, &start);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const double dt = g.m.t_end - g.m.t_begin;
   const float4* __restrict__ in = g.in + start;
   float4* __restrict__ out = g.out + start;
   const double* __restrict__ times = g.times + start;
-  // box [0]: per coordinate over the values that are not NaN (fminf / fmaxf drop a NaN operand); box [1]: finite points
-  float mn0[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx0[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-  float mn1[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx1[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+  ndt::TwoBox<kDskWaves> box;  // of the f32 values that were stored
   unsigned untimed = 0;
   for (int i = threadIdx.x; i < len; i += kDskBlock) {
     float4 p = in[i];
@@ -59,39 +57,16 @@ __global__ __launch_bounds__(kDskBlock) void k_deskew(DskSeg one, const DskSeg* 
     }
     untimed += kind == 2 ? 1u : 0u;
     out[i] = p;
-    const float v[3] = {p.x, p.y, p.z};
-    const bool fin = __builtin_isfinite(p.x) && __builtin_isfinite(p.y) && __builtin_isfinite(p.z);
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-      mn0[a] = fminf(mn0[a], v[a]);
-      mx0[a] = fmaxf(mx0[a], v[a]);
-      if (fin) {
-        mn1[a] = fminf(mn1[a], v[a]);
-        mx1[a] = fmaxf(mx1[a], v[a]);
-      }
-    }
+    box.add(p);
   }
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-    const float r0v = ndt::wave_min(mn0[a]), r1v = ndt::wave_max(mx0[a]), r2v = ndt::wave_min(mn1[a]), r3v = ndt::wave_max(mx1[a]);
-    if (lane == 0) {
-      wave_box[wave][a] = r0v;
-      wave_box[wave][3 + a] = r1v;
-      wave_box[wave][6 + a] = r2v;
-      wave_box[wave][9 + a] = r3v;
-    }
-  }
+  box.to_lds(wave_box);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) untimed += __shfl_xor(untimed, o);
   if (lane == 0) wave_untimed[wave] = untimed;
   __syncthreads();
   float* row = rows + static_cast<size_t>(blockIdx.x) * kDskRow;
   if (threadIdx.x < 12) {
-    const int t = threadIdx.x;
-    const bool is_min = (t % 6) < 3;
-    float v = wave_box[0][t];
-    for (int w = 1; w < kDskWaves; w++) v = is_min ? fminf(v, wave_box[w][t]) : fmaxf(v, wave_box[w][t]);
-    row[t] = v;
+    row[threadIdx.x] = box.block_value(wave_box, threadIdx.x);
   } else if (threadIdx.x == 12) {
     unsigned u = 0;
     for (int w = 0; w < kDskWaves; w++) u += wave_untimed[w];
@@ -99,12 +74,8 @@ __global__ __launch_bounds__(kDskBlock) void k_deskew(DskSeg one, const DskSeg* 
   }
 }
 
-int max_blocks_switch() {
-  static const int v = [] {
-    const char* e = getenv("NDT_DESKEW_MAX_BLOCKS");  // development switch: small values reach the strided regime with small clouds
-    const int x = e ? atoi(e) : 0;
-    return x > 0 ? std::min(x, ndt::kDeskewMaxBlocks) : ndt::kDeskewMaxBlocks;
-  }();
+int max_blocks_switch() {  // development switch, read once: small values reach the strided regime with small clouds
+  static const int v = env_block_cap("NDT_DESKEW_MAX_BLOCKS", ndt::kDeskewMaxBlocks);
   return v;
 }
 
@@ -125,7 +96,7 @@ ndt_status deskew_run(ndt_handle h, std::vector<DskJob>& jobs) {
   hipStream_t st = h->stream;
   h->dsk_launches = h->dsk_blocks = 0;
   h->dsk_clouds = jobs.size();
-  std::vector<DskSeg> segs;
+  MemberTable<DskSeg> segs;
   std::vector<size_t> slot;
   long long total_blocks = 0;
   for (size_t k = 0; k < jobs.size(); k++) {
@@ -144,57 +115,41 @@ ndt_status deskew_run(ndt_handle h, std::vector<DskJob>& jobs) {
     g.ppb = ppb;
     g.first_block = static_cast<int>(total_blocks);
     g.n_blocks = blocks;
-    segs.push_back(g);
+    segs.host.push_back(g);
     slot.push_back(k);
     total_blocks += blocks;
   }
-  if (segs.empty()) return NDT_OK;
+  if (segs.host.empty()) return NDT_OK;
   if (total_blocks > std::numeric_limits<int>::max()) return fail(NDT_ERR_INVALID, "too many points");
   const size_t nb = static_cast<size_t>(total_blocks);
   // page-locked: [segment table | rows, one per block]
-  const size_t seg_bytes = (segs.size() * sizeof(DskSeg) + 15) / 16 * 16;
+  const size_t seg_bytes = (segs.bytes() + 15) / 16 * 16;
   const size_t row_bytes = nb * kDskRow * sizeof(float);
   ndt_status s = pinned_at_least(h->dsk_pinned, h->dsk_pinned_bytes, seg_bytes + row_bytes, st);
   if (s) return s;
   unsigned char* pin = static_cast<unsigned char*>(h->dsk_pinned);
   float* rows = reinterpret_cast<float*>(pin + seg_bytes);
-  std::memcpy(pin, segs.data(), segs.size() * sizeof(DskSeg));
-  DevBuf<unsigned char> d_segs;
-  const int n_segs = static_cast<int>(segs.size());
-  if (n_segs > 1) {
-    HIP_TRY(d_segs.reserve(seg_bytes));
-    HIP_TRY(hipMemcpyAsync(d_segs.p, pin, seg_bytes, hipMemcpyHostToDevice, st));
-  }
-  hipLaunchKernelGGL(k_deskew, dim3(static_cast<unsigned>(nb)), dim3(kDskBlock), 0, st, segs[0], reinterpret_cast<const DskSeg*>(d_segs.p), n_segs, rows);
+  std::memcpy(pin, segs.host.data(), segs.bytes());
+  if ((s = segs.upload(st, pin))) return s;
+  hipLaunchKernelGGL(k_deskew, dim3(static_cast<unsigned>(nb)), dim3(kDskBlock), 0, st, segs.one(), segs.table(), segs.n(), rows);
   HIP_TRY(hipGetLastError());
   h->dsk_launches = 1;
   h->dsk_blocks = nb;
   HIP_TRY(hipStreamSynchronize(st));
-  for (size_t q = 0; q < segs.size(); q++) {
-    const DskSeg& g = segs[q];
+  for (size_t q = 0; q < segs.host.size(); q++) {
+    const DskSeg& g = segs.host[q];
     DskJob& j = jobs[slot[q]];
     for (int b = g.first_block; b < g.first_block + g.n_blocks; b++) {
-      const float* row = rows + static_cast<size_t>(b) * kDskRow;
       unsigned u;
-      std::memcpy(&u, row + 12, sizeof u);
+      std::memcpy(&u, rows + static_cast<size_t>(b) * kDskRow + 12, sizeof u);
       j.untimed += u;
-      if (!j.res) continue;
-      for (int v = 0; v < 2; v++)
-        for (int a = 0; a < 3; a++) {
-          j.res->bb_min[v][a] = std::min(j.res->bb_min[v][a], row[v * 6 + a]);
-          j.res->bb_max[v][a] = std::max(j.res->bb_max[v][a], row[v * 6 + 3 + a]);
-        }
     }
-    if (j.res) j.res->box_route = NDT_BOX_ROUTE_DESKEW;
+    if (j.res) fold_box_rows(j.res, rows, kDskRow, g.first_block, g.n_blocks, NDT_BOX_ROUTE_DESKEW);
   }
   return NDT_OK;
 }
 
-ndt_status motion_checks(const ndt_deskew_motion* m) {
-  if (!m) return fail(NDT_ERR_INVALID, "null motion");
-  if (const char* why = ndt::deskew_motion_error(*m)) return fail(NDT_ERR_INVALID, why);
-  return NDT_OK;
-}
+ndt_status motion_checks(const ndt_deskew_motion* m) { return spec_checks(m, ndt::deskew_motion_error, "null motion"); }
 
 // Rodrigues' formula: Exp(angle * k) v, in f64
 void rotate_about(const double k[3], double angle, const double v[3], double out[3]) {
@@ -213,25 +168,19 @@ ndt_status ndt_cloud_deskew(ndt_handle h, ndt_cloud in, const ndt_deskew_motion*
                             ndt_cloud* out, size_t* n_untimed) {
   if (out) *out = nullptr;
   if (!h || !out) return fail(NDT_ERR_INVALID, "bad arguments");
-  ndt_status s = select_cloud_checks(h, in);
-  if (!s) s = motion_checks(motion);
+  ndt_status s = cloud_entry(h, in, [&]() -> ndt_status {
+    if (ndt_status e = motion_checks(motion)) return e;
+    if (in->c->n && !times) return fail(NDT_ERR_INVALID, "a deskew needs the points' times");
+    return NDT_OK;
+  });
   if (s) return s;
   const size_t n = in->c->n;
-  if (n && !times) return fail(NDT_ERR_INVALID, "a deskew needs the points' times");
-  s = ensure_device(h);
-  if (!s) s = cloud_use_on(h, in->c.get());
-  if (s) return s;
   DevBuf<double> d_times;
   const double* tp = times;
-  auto c = select_new_cloud(h);
-  if (n) {  // (every buffer first: nothing is queued yet when a reservation fails and the others go back to the pool)
-    HIP_TRY(c->pts.reserve(n));
-    if (!times_on_device) {
-      HIP_TRY(d_times.reserve(n));
-      HIP_TRY(hipMemcpyAsync(d_times.p, times, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      tp = d_times.p;
-    }
-  }
+  auto c = new_cloud(h);
+  if (n) HIP_TRY(c->pts.reserve(n));  // (before anything is queued: a failure gives back what was reserved, and nothing uses it)
+  Drain drain{h->stream};             // (from here on nothing queued may still read or write what goes back to the pool)
+  if ((s = doubles_in(h->stream, times, n, times_on_device, d_times, &tp))) return s;
   std::vector<DskJob> jobs(1);
   jobs[0].in = in->c->pts.p;
   jobs[0].n = n;
@@ -239,11 +188,8 @@ ndt_status ndt_cloud_deskew(ndt_handle h, ndt_cloud in, const ndt_deskew_motion*
   jobs[0].m = motion;
   jobs[0].out = c->pts.p;
   jobs[0].res = c.get();
-  s = deskew_run(h, jobs);
-  if (s) {
-    (void)hipStreamSynchronize(h->stream);  // (nothing queued may still write into what goes back to the pool)
-    return s;
-  }
+  if ((s = deskew_run(h, jobs))) return s;
+  drain.done = true;  // (the run has waited)
   if (n_untimed) *n_untimed = jobs[0].untimed;
   *out = new ndt_cloud_s{c};
   return NDT_OK;
@@ -252,58 +198,38 @@ ndt_status ndt_cloud_deskew(ndt_handle h, ndt_cloud in, const ndt_deskew_motion*
 ndt_status ndt_cloud_deskew_clouds(ndt_handle h, const ndt_cloud* in, size_t n_clouds, const ndt_deskew_motion* motions, const double* times,
                                    int times_on_device, ndt_cloud* out, size_t* n_untimed) {
   if (!h || !out) return fail(NDT_ERR_INVALID, "bad arguments");
-  if (n_clouds > 65535) return fail(NDT_ERR_INVALID, "at most 65535 clouds per call");
-  for (size_t k = 0; k < n_clouds; k++) out[k] = nullptr;
+  ndt_status s = clouds_begin(n_clouds, out);
+  if (s) return s;
   if (n_clouds && !in) return fail(NDT_ERR_INVALID, "null clouds");
   if (n_clouds && !motions) return fail(NDT_ERR_INVALID, "null motion");
-  ndt_status s = NDT_OK;
-  size_t total = 0;
-  for (size_t k = 0; k < n_clouds; k++) {
-    if ((s = select_cloud_checks(h, in[k]))) return s;
-    if ((s = motion_checks(&motions[k]))) return s;
-    total += in[k]->c->n;
-  }
-  if (total > static_cast<size_t>(std::numeric_limits<int>::max())) return fail(NDT_ERR_INVALID, "too many points");
+  std::vector<size_t> first;
+  if ((s = clouds_total(h, in, n_clouds, first, [&](size_t k) { return motion_checks(&motions[k]); }))) return s;
+  const size_t total = first[n_clouds];
   if (total && !times) return fail(NDT_ERR_INVALID, "a deskew needs the points' times");
   if (n_clouds == 0) return NDT_OK;
   s = ensure_device(h);
   if (s) return s;
-  // the outputs are slices of one block, kept alive by the slices' `owner`
-  auto blk = select_new_cloud(h);
-  std::vector<std::shared_ptr<DeviceCloud>> res(n_clouds);
+  OutSlices outs;
   std::vector<DskJob> jobs(n_clouds);
   DevBuf<double> d_times;
   const double* tp = times;
-  // (every buffer first: nothing is queued yet when a reservation fails and the others go back to the pool)
-  HIP_TRY(blk->pts.reserve(std::max<size_t>(total, 1)));
-  blk->n = total;
-  if (total && !times_on_device) {
-    HIP_TRY(d_times.reserve(total));
-    HIP_TRY(hipMemcpyAsync(d_times.p, times, total * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    tp = d_times.p;
-  }
-  size_t first = 0;
+  if ((s = outs.reserve(h, first))) return s;  // (before anything is queued)
+  Drain drain{h->stream};  // (from here on nothing queued may still read or write what goes back to the pool)
+  if ((s = doubles_in(h->stream, times, total, times_on_device, d_times, &tp))) return s;
   for (size_t k = 0; k < n_clouds; k++) {
     DeviceCloud* c = in[k]->c.get();
-    if ((s = cloud_use_on(h, c))) break;
-    res[k] = select_new_cloud(h);
+    if ((s = cloud_use_on(h, c))) return s;
     jobs[k].in = c->pts.p;
     jobs[k].n = c->n;
-    jobs[k].times = tp ? tp + first : nullptr;
+    jobs[k].times = tp ? tp + first[k] : nullptr;
     jobs[k].m = &motions[k];
-    jobs[k].out = blk->pts.p + first;
-    jobs[k].res = res[k].get();
-    first += c->n;
+    jobs[k].out = outs.at(k);
+    jobs[k].res = outs.cloud(k);
   }
-  if (!s) s = deskew_run(h, jobs);
-  if (s) {
-    (void)hipStreamSynchronize(h->stream);  // (nothing queued may still read or write what goes back to the pool)
-    return s;
-  }
+  if ((s = deskew_run(h, jobs))) return s;
+  drain.done = true;  // (the run has waited)
   for (size_t k = 0; k < n_clouds; k++) {
-    res[k]->pts.borrow(jobs[k].out, jobs[k].n);
-    res[k]->owner = blk;
-    out[k] = new ndt_cloud_s{res[k]};
+    out[k] = outs.publish(k, jobs[k].n);
     if (n_untimed) n_untimed[k] = jobs[k].untimed;
   }
   return NDT_OK;

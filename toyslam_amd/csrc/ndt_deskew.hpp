@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstddef>
 
+#include "ndt_cloud_ops.hpp"
 #include "ndt_mi355.h"
 
 #if defined(__HIPCC__)
@@ -71,15 +72,8 @@ inline const char* deskew_motion_error(const ndt_deskew_motion& m) {
   return nullptr;
 }
 
-// The launch plan of one cloud: blocks of kDeskewBlock threads, block b owns points [b * ppb, min(n, (b + 1) * ppb)).
-// ppb is one pass of the block's threads until that would take more than max_blocks blocks, then n / max_blocks rounded up:
-// monotone in n, and the blocks tile [0, n).  n == 0: no block.
-inline void deskew_plan(size_t n, int max_blocks, int* blocks, int* ppb) {
-  const size_t cap = static_cast<size_t>(max_blocks);
-  const size_t per = (n + cap - 1) / cap;
-  const size_t p = per > static_cast<size_t>(kDeskewBlock) ? per : static_cast<size_t>(kDeskewBlock);
-  *ppb = static_cast<int>(p);
-  *blocks = static_cast<int>((n + p - 1) / p);
-}
+// The launch plan of one cloud (range_plan): blocks of kDeskewBlock threads, block b owns points [b * ppb, min(n, (b + 1) * ppb));
+// ppb is one pass of the block's threads until that would take more than max_blocks blocks.
+inline void deskew_plan(size_t n, int max_blocks, int* blocks, int* ppb) { range_plan(n, kDeskewBlock, max_blocks, blocks, ppb); }
 
 }  // namespace ndt

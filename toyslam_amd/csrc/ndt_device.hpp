@@ -192,6 +192,7 @@ __device__ __forceinline__ void block_reduce_store(double (&acc)[NV], double* __
 }
 
 __device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
+__device__ __forceinline__ bool finite3(const float4& p) { return __builtin_isfinite(p.x) && __builtin_isfinite(p.y) && __builtin_isfinite(p.z); }
 
 // Which member of a many-member launch block b belongs to: the last of the n entries whose first block is not behind b.
 // first(m) is entry m's first block (ascending; entry 0 starts at 0, entries are never empty).  b and the table are the same

@@ -40,13 +40,6 @@ void decode_boxes(const unsigned* w, DeviceCloud* c) {
   c->box_route = NDT_BOX_ROUTE_MULTI_WORDS;
 }
 
-std::shared_ptr<DeviceCloud> new_cloud(ndt_handle h) {
-  auto c = std::make_shared<DeviceCloud>();
-  c->device = h->device;
-  c->made_on = h->stream;
-  return c;
-}
-
 // One composite pass over clouds [s0, s1] of `in`: the members (is_member) are filtered, the others in that span only get
 // keys of -1.  Every member's result is a slice of the pass's output block.  Waits for the stream.
 ndt_status composite_pass(ndt_handle h, const float4* block, const std::vector<BatchIn>& in, const std::vector<FilterRoute>& route,

@@ -11,6 +11,8 @@
 //   ndt_nvtl.hip  : nearest-voxel transformation likelihood (of a cloud, of the source under one or many poses, per point)
 //   ndt_select.hip : selection of the points of resident clouds (finite, box, range, per-point value): kernels and C-ABI
 //   ndt_deskew.hip : motion compensation of resident scans by the time of every point: kernel and C-ABI
+//   ndt_cloud_ops.hip : what ndt_select / _deskew / _outliers / _plane.hip share on the host: the checks of an input cloud and
+//                    the parts of the entry preambles, the member table, output slices, the box-row fold, per-point doubles
 //   ndt_pose_cov.hip: 6x6 pose covariance (Laplace / sandwich) of the handle's pair and of the pairs of a pairs call
 //   ndt_eval.hip   : one evaluation (launch path), the persistent evaluation server's host side (mailbox protocol),
 //                    ndt_align, ndt_eval*, diagnostics and self-tests
@@ -741,8 +743,112 @@ ndt_status select_run(ndt_handle h, std::vector<SelJob>& jobs, const ndt_select_
 // one cloud's records into a new cloud
 ndt_status select_one(ndt_handle h, const float4* d_in, size_t n, const ndt_select_spec& spec, const double* d_keys,
                       std::shared_ptr<DeviceCloud>& out, int32_t* kept_idx, size_t* n_kept, const double* d_key_range = nullptr);
-std::shared_ptr<DeviceCloud> select_new_cloud(ndt_handle h);   // an ndt_cloud's DeviceCloud made on h's stream
-ndt_status select_cloud_checks(ndt_handle h, ndt_cloud c);     // what every selection refuses of an input cloud
+// ---- ndt_cloud_ops.hip: what the operations on resident clouds share (ndt_select / _deskew / _outliers / _plane.hip)
+std::shared_ptr<DeviceCloud> new_cloud(ndt_handle h);  // an ndt_cloud's DeviceCloud made on h's stream
+ndt_status cloud_checks(ndt_handle h, ndt_cloud c);    // what every operation refuses of an input cloud
+// a spec (a motion) the caller hands over: there, and valid by its own rule (error_of: null = valid, else what is wrong)
+template <class Spec>
+ndt_status spec_checks(const Spec* spec, const char* (*error_of)(const Spec&), const char* if_null = "null spec") {
+  if (!spec) return fail(NDT_ERR_INVALID, if_null);
+  if (const char* why = error_of(*spec)) return fail(NDT_ERR_INVALID, why);
+  return NDT_OK;
+}
+// The preamble of an entry over ONE cloud, behind the entry's own argument checks: the cloud; own() -- the entry's checks of
+// its spec and what goes with it, run only for a cloud that passed; the device; the cloud's stream.
+template <class Own>
+ndt_status cloud_entry(ndt_handle h, ndt_cloud in, Own&& own) {
+  ndt_status s = cloud_checks(h, in);
+  if (!s) s = own();
+  if (!s) s = ensure_device(h);
+  if (!s) s = cloud_use_on(h, in->c.get());
+  return s;
+}
+// The preamble of an entry over a LIST of clouds, in two steps with the entry's own refusals (a missing list, the spec)
+// between them.  clouds_begin: at most 65535 clouds, then every output nulled (out_b: the plane's second kind).
+// clouds_total: per cloud k cloud_checks and each(k); first[k] = the points before cloud k, first[n_clouds] = the total,
+// refused beyond INT_MAX.
+ndt_status clouds_begin(size_t n_clouds, ndt_cloud* out_a, ndt_cloud* out_b = nullptr);
+template <class Each>
+ndt_status clouds_total(ndt_handle h, const ndt_cloud* in, size_t n_clouds, std::vector<size_t>& first, Each&& each) {
+  first.assign(n_clouds + 1, 0);
+  for (size_t k = 0; k < n_clouds; k++) {
+    ndt_status s = cloud_checks(h, in[k]);
+    if (!s) s = each(k);
+    if (s) return s;
+    first[k + 1] = first[k] + in[k]->c->n;
+  }
+  if (first[n_clouds] > static_cast<size_t>(std::numeric_limits<int>::max())) return fail(NDT_ERR_INVALID, "too many points");
+  return NDT_OK;
+}
+inline ndt_status clouds_total(ndt_handle h, const ndt_cloud* in, size_t n_clouds, std::vector<size_t>& first) {
+  return clouds_total(h, in, n_clouds, first, [](size_t) { return NDT_OK; });
+}
+// whatever path leaves the scope: nothing queued may still read or write what the scope's buffers give back to the pool, and
+// the queued copies have read (written) the call's host memory before it dies.  done: set by a path that has waited itself
+struct Drain {
+  hipStream_t s;
+  bool done = false;
+  ~Drain() {
+    if (!done) (void)hipStreamSynchronize(s);
+  }
+};
+// ndt_diag_select reports on the selections alone: what the compaction inside an outlier or a plane call did is taken back
+struct SelDiagKeep {
+  ndt_handle h;
+  size_t a, b, c;
+  explicit SelDiagKeep(ndt_handle hh) : h(hh), a(hh->sel_launches), b(hh->sel_blocks), c(hh->sel_clouds) {}
+  ~SelDiagKeep() {
+    h->sel_launches = a;
+    h->sel_blocks = b;
+    h->sel_clouds = c;
+  }
+};
+// The member table of a launch: the host's entries and a device copy made only when there are several -- a call of one
+// member hands entry 0 over as a kernel argument.  upload(st, src): src = a page-locked copy of the entries, else theirs.
+template <class M>
+struct MemberTable {
+  std::vector<M> host;
+  DevBuf<unsigned char> dev;
+  int n() const { return static_cast<int>(host.size()); }
+  size_t bytes() const { return host.size() * sizeof(M); }
+  const M& one() const { return host[0]; }
+  const M* table() const { return reinterpret_cast<const M*>(dev.p); }
+  ndt_status upload(hipStream_t st, const void* src = nullptr) {
+    if (host.size() < 2) return NDT_OK;
+    HIP_TRY(dev.reserve(bytes()));
+    HIP_TRY(hipMemcpyAsync(dev.p, src ? src : host.data(), bytes(), hipMemcpyHostToDevice, st));
+    return NDT_OK;
+  }
+};
+// per-block box rows (12 floats at the head of every `stride` floats) of blocks [b0, b0 + nb) folded into c's boxes; the route set
+void fold_box_rows(DeviceCloud* c, const float* rows, size_t stride, int b0, int nb, int route);
+// The outputs of a call over a list of clouds: slices of ONE block with room for every input point, kept alive by the slices'
+// `owner`.  reserve (first: clouds_total's) before anything is queued; publish(k, count) once nothing can fail any more.
+struct OutSlices {
+  std::shared_ptr<DeviceCloud> blk;
+  std::vector<std::shared_ptr<DeviceCloud>> res;
+  std::vector<size_t> first;
+  ndt_status reserve(ndt_handle h, const std::vector<size_t>& first_points);
+  float4* at(size_t k) const { return blk->pts.p + first[k]; }
+  DeviceCloud* cloud(size_t k) const { return res[k].get(); }  // what the job of cloud k writes n, the boxes and the route to
+  ndt_cloud publish(size_t k, size_t count);
+};
+// n per-point doubles on their way in (keys, times): *d = the caller's device pointer as it is, or a copy of the host's
+// queued on st and held by buf
+ndt_status doubles_in(hipStream_t st, const double* src, size_t n, int on_device, DevBuf<double>& buf, const double** d);
+// ... and on their way out (neighbour values, plane distances): at() is where the kernels write -- the caller's device
+// memory, or a buffer reserve() made that fetch() queues the copy of to the caller's host memory
+struct DoublesOut {
+  DevBuf<double> buf;
+  double* dst = nullptr;
+  size_t n = 0;
+  bool on_device = false;
+  ndt_status reserve(double* dst_, size_t n_, int on_device_);
+  double* at() const { return on_device ? dst : buf.p; }
+  ndt_status fetch(hipStream_t st);
+};
+// a development switch that lowers a plan's block cap: the environment variable's value where it is > 0, at most cap
+int env_block_cap(const char* name, int cap);
 // ---- gicp_inputs.hip
 // A point index (index_only grid) over `cloud` whose leaf follows the cloud's own density: leaf0 > 0 is tried first, else a
 // volume guess, then corrected from the measured points per occupied cell.  dense: the cloud holds no NaN / inf.  *leaf_out:

@@ -56,8 +56,6 @@ struct StatMember {
   int degenerate;  // |F| <= mean_k: statistics and threshold are 0
 };
 
-__device__ __forceinline__ bool finite3(const float4& p) { return __builtin_isfinite(p.x) && __builtin_isfinite(p.y) && __builtin_isfinite(p.z); }
-
 // Block `block` of the `n_blocks` that cut cloud `ix`: eight queries per pass, strided by n_blocks.
 __device__ __forceinline__ void outlier_block(const PointIndex& ix, int mode, int method, int k, float radius, float r2, int block,
                                               int n_blocks, double* __restrict__ values, unsigned* __restrict__ scanned) {
@@ -133,6 +131,8 @@ __device__ __forceinline__ void outlier_block(const PointIndex& ix, int mode, in
 // (a call of one cloud hands its member over as a kernel argument: no table to copy up first)
 __global__ __launch_bounds__(kBlock) void k_outlier_values(OutMember one, const OutMember* __restrict__ members, int n_members, int method,
                                                            int k, float radius, float r2, unsigned* __restrict__ scanned) {
+  // (not ndt::block_member: one body fed by a select between the argument and a table entry -- an OutMember carries a whole
+  // PointIndex -- took the kernel from 75 to 124 VGPRs and from 6 to 4 waves per SIMD; two calls keep each path's own registers)
   const int b = static_cast<int>(blockIdx.x);
   if (n_members == 1) {
     if (b < one.n_blocks) outlier_block(one.ix, one.mode, method, k, radius, r2, b, one.n_blocks, one.values, scanned);
@@ -145,18 +145,6 @@ __global__ __launch_bounds__(kBlock) void k_outlier_values(OutMember one, const 
   outlier_block(m.ix, m.mode, method, k, radius, r2, local, m.n_blocks, m.values, scanned);
 }
 
-// tree sum over the block's threads in a fixed order; the result in every thread
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-  __syncthreads();
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = ndt::kOutlierStatBlock / 2; s > 0; s >>= 1) {
-    if (static_cast<int>(threadIdx.x) < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-    __syncthreads();
-  }
-  return sh[0];
-}
-
 // rows[block] = (count, sum, M2 about sum / count) of the block's chunk of its member's values; NaN values are no values
 __global__ __launch_bounds__(ndt::kOutlierStatBlock) void k_outlier_stats(const StatMember* __restrict__ members, int n_members,
                                                                         double* __restrict__ rows) {
@@ -167,8 +155,8 @@ __global__ __launch_bounds__(ndt::kOutlierStatBlock) void k_outlier_stats(const 
   const StatMember m = members[lo];
   const int lb = b - m.first_block;
   if (lb >= m.n_blocks) return;
-  const long long start = static_cast<long long>(lb) * m.chunk;
-  const int len = static_cast<int>(min(static_cast<long long>(m.chunk), m.n - start));
+  long long start;
+  const int len = ndt::block_range(lb, m.chunk, m.n, &start);
   double cnt = 0.0, sum = 0.0;
   for (int j = threadIdx.x; j < len; j += ndt::kOutlierStatBlock) {
     const double v = m.values[start + j];
@@ -177,15 +165,15 @@ __global__ __launch_bounds__(ndt::kOutlierStatBlock) void k_outlier_stats(const 
       sum += v;
     }
   }
-  cnt = block_sum(cnt, sh);
-  sum = block_sum(sum, sh);
+  cnt = ndt::block_sum<ndt::kOutlierStatBlock>(cnt, sh);
+  sum = ndt::block_sum<ndt::kOutlierStatBlock>(sum, sh);
   const double mean = cnt > 0.0 ? sum / cnt : 0.0;
   double m2 = 0.0;
   for (int j = threadIdx.x; j < len; j += ndt::kOutlierStatBlock) {
     const double v = m.values[start + j];
     if (v == v) m2 += (v - mean) * (v - mean);
   }
-  m2 = block_sum(m2, sh);
+  m2 = ndt::block_sum<ndt::kOutlierStatBlock>(m2, sh);
   if (threadIdx.x == 0) {
     rows[static_cast<size_t>(b) * 3 + 0] = cnt;
     rows[static_cast<size_t>(b) * 3 + 1] = sum;
@@ -221,12 +209,8 @@ __global__ __launch_bounds__(64) void k_outlier_merge(const StatMember* __restri
   m.row[5] = thr;
 }
 
-int max_blocks_switch() {
-  static const int v = [] {
-    const char* e = getenv("NDT_OUTLIER_MAX_BLOCKS");  // development switch: small values reach the strided regime with small clouds
-    const int x = e ? atoi(e) : 0;
-    return x > 0 ? std::min(x, ndt::kOutlierMaxBlocks) : ndt::kOutlierMaxBlocks;
-  }();
+int max_blocks_switch() {  // development switch, read once: small values reach the strided regime with small clouds
+  static const int v = env_block_cap("NDT_OUTLIER_MAX_BLOCKS", ndt::kOutlierMaxBlocks);
   return v;
 }
 
@@ -238,11 +222,11 @@ struct OutlierRun {
   DevBuf<double> d_rows;                  // per cloud [6]: the merge's row (STATISTICAL); +4: the selection's key range
   // kept until the wait
   std::vector<std::shared_ptr<DeviceGrid>> grids;
-  std::vector<OutMember> mem;
+  MemberTable<OutMember> mem;
   std::vector<StatMember> smem;
   std::vector<double> rows_host;
   unsigned scanned_host = 0;
-  DevBuf<unsigned char> d_mem, d_smem;
+  DevBuf<unsigned char> d_smem;
   DevBuf<double> d_partials;
   DevBuf<unsigned> d_scanned;
   std::vector<size_t> n_finite;
@@ -298,7 +282,7 @@ ndt_status outlier_queue(ndt_handle h, const ndt_outlier_spec& spec, OutlierRun&
     m.first_block = static_cast<int>(blocks);
     m.n_blocks = std::min(nb, max_blocks_switch());
     blocks += m.n_blocks;
-    R.mem.push_back(m);
+    R.mem.host.push_back(m);
     if (stat) {
       StatMember sm{};
       sm.values = R.d_values[k];
@@ -311,19 +295,16 @@ ndt_status outlier_queue(ndt_handle h, const ndt_outlier_spec& spec, OutlierRun&
     }
   }
   HIP_TRY(R.d_rows.reserve(std::max<size_t>(nc, 1) * 6));
-  if (R.mem.empty()) return NDT_OK;
+  if (R.mem.host.empty()) return NDT_OK;
   if (blocks > std::numeric_limits<int>::max()) return fail(NDT_ERR_INVALID, "too many points");
-  const int n_mem = static_cast<int>(R.mem.size());
+  const int n_mem = R.mem.n();
   HIP_TRY(R.d_scanned.reserve(1));
   HIP_TRY(hipMemsetAsync(R.d_scanned.p, 0, sizeof(unsigned), st));
-  if (n_mem > 1) {
-    HIP_TRY(R.d_mem.reserve(R.mem.size() * sizeof(OutMember)));
-    HIP_TRY(hipMemcpyAsync(R.d_mem.p, R.mem.data(), R.mem.size() * sizeof(OutMember), hipMemcpyHostToDevice, st));
-  }
+  if (ndt_status s = R.mem.upload(st)) return s;
   const int kk = stat ? spec.mean_k : 0;
   const size_t lds = stat ? ndt::knn_lds_bytes<double>(kk, KnnDistances::kPositions) : 0;
-  hipLaunchKernelGGL(k_outlier_values, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), lds, st, R.mem[0],
-                     reinterpret_cast<const OutMember*>(R.d_mem.p), n_mem, spec.method, kk, spec.radius, spec.radius * spec.radius,
+  hipLaunchKernelGGL(k_outlier_values, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), lds, st, R.mem.one(),
+                     R.mem.table(), n_mem, spec.method, kk, spec.radius, spec.radius * spec.radius,
                      R.d_scanned.p);
   HIP_TRY(hipGetLastError());
   h->ol_value_launches = 1;
@@ -384,27 +365,7 @@ ndt_select_spec key_spec(const ndt_outlier_spec& spec) {
   return s;
 }
 
-ndt_status spec_checks(const ndt_outlier_spec* spec) {
-  if (!spec) return fail(NDT_ERR_INVALID, "null spec");
-  if (const char* why = ndt::outlier_spec_error(*spec)) return fail(NDT_ERR_INVALID, why);
-  return NDT_OK;
-}
-
-// ndt_diag_select reports on the selections alone: what the compaction inside an outlier call did is taken back
-struct SelDiagKeep {
-  ndt_handle h;
-  size_t a, b, c;
-  explicit SelDiagKeep(ndt_handle hh) : h(hh), a(hh->sel_launches), b(hh->sel_blocks), c(hh->sel_clouds) {}
-  ~SelDiagKeep() {
-    h->sel_launches = a;
-    h->sel_blocks = b;
-    h->sel_clouds = c;
-  }
-};
-struct Drain {  // whatever path leaves: the queued copies have read (written) the run's host memory before it dies
-  hipStream_t s;
-  ~Drain() { (void)hipStreamSynchronize(s); }
-};
+ndt_status spec_checks(const ndt_outlier_spec* spec) { return ndtc::spec_checks(spec, ndt::outlier_spec_error); }
 
 }  // namespace
 }  // namespace ndtc
@@ -414,23 +375,18 @@ extern "C" {
 ndt_status ndt_cloud_neighbor_values(ndt_handle h, ndt_cloud in, const ndt_outlier_spec* spec, double* values, int values_on_device,
                                      ndt_outlier_stats* stats) {
   if (!h || !values) return fail(NDT_ERR_INVALID, "bad arguments");
-  ndt_status s = select_cloud_checks(h, in);
-  if (!s) s = spec_checks(spec);
+  ndt_status s = cloud_entry(h, in, [&] { return spec_checks(spec); });
   if (s) return s;
-  s = ensure_device(h);
-  if (!s) s = cloud_use_on(h, in->c.get());
-  if (s) return s;
-  const size_t n = in->c->n;
   OutlierRun R;
-  DevBuf<double> d_vals;
-  if (n && !values_on_device) HIP_TRY(d_vals.reserve(n));
+  DoublesOut vals;
+  if ((s = vals.reserve(values, in->c->n, values_on_device))) return s;
   R.clouds.push_back(in->c);
-  R.d_values.push_back(values_on_device ? values : d_vals.p);
+  R.d_values.push_back(vals.at());
   {
     Drain drain{h->stream};
     s = outlier_queue(h, *spec, R);
+    if (!s) s = vals.fetch(h->stream);
     if (s) return s;
-    if (n && !values_on_device) HIP_TRY(hipMemcpyAsync(values, d_vals.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
   }
   outlier_finish(h, *spec, R);
@@ -442,11 +398,7 @@ ndt_status ndt_cloud_remove_outliers(ndt_handle h, ndt_cloud in, const ndt_outli
                                      size_t* n_kept, ndt_outlier_stats* stats) {
   if (out) *out = nullptr;
   if (!h || !out) return fail(NDT_ERR_INVALID, "bad arguments");
-  ndt_status s = select_cloud_checks(h, in);
-  if (!s) s = spec_checks(spec);
-  if (s) return s;
-  s = ensure_device(h);
-  if (!s) s = cloud_use_on(h, in->c.get());
+  ndt_status s = cloud_entry(h, in, [&] { return spec_checks(spec); });
   if (s) return s;
   const size_t n = in->c->n;
   OutlierRun R;
@@ -475,61 +427,46 @@ ndt_status ndt_cloud_remove_outliers(ndt_handle h, ndt_cloud in, const ndt_outli
 ndt_status ndt_cloud_remove_outliers_clouds(ndt_handle h, const ndt_cloud* in, size_t n_clouds, const ndt_outlier_spec* spec, ndt_cloud* out,
                                             size_t* n_kept, ndt_outlier_stats* stats) {
   if (!h || !out) return fail(NDT_ERR_INVALID, "bad arguments");
-  if (n_clouds > 65535) return fail(NDT_ERR_INVALID, "at most 65535 clouds per call");
-  for (size_t k = 0; k < n_clouds; k++) out[k] = nullptr;
-  if (n_clouds && !in) return fail(NDT_ERR_INVALID, "null clouds");
-  ndt_status s = spec_checks(spec);
+  ndt_status s = clouds_begin(n_clouds, out);
   if (s) return s;
-  size_t total = 0;
-  for (size_t k = 0; k < n_clouds; k++) {
-    if ((s = select_cloud_checks(h, in[k]))) return s;
-    total += in[k]->c->n;
-  }
-  if (total > static_cast<size_t>(std::numeric_limits<int>::max())) return fail(NDT_ERR_INVALID, "too many points");
+  if (n_clouds && !in) return fail(NDT_ERR_INVALID, "null clouds");
+  if ((s = spec_checks(spec))) return s;
+  std::vector<size_t> first;
+  if ((s = clouds_total(h, in, n_clouds, first))) return s;
   if (n_clouds == 0) return NDT_OK;
   s = ensure_device(h);
   if (s) return s;
   OutlierRun R;
   DevBuf<double> d_vals;
-  HIP_TRY(d_vals.reserve(std::max<size_t>(total, 1)));
-  // the outputs are slices of one block (room for every input point), kept alive by the slices' `owner`
-  auto blk = select_new_cloud(h);
-  std::vector<std::shared_ptr<DeviceCloud>> res(n_clouds);
+  HIP_TRY(d_vals.reserve(std::max<size_t>(first[n_clouds], 1)));
+  OutSlices outs;
   std::vector<SelJob> jobs(n_clouds);
-  HIP_TRY(blk->pts.reserve(std::max<size_t>(total, 1)));
-  blk->n = total;
-  size_t first = 0;
+  if ((s = outs.reserve(h, first))) return s;
   for (size_t k = 0; k < n_clouds; k++) {
     if ((s = cloud_use_on(h, in[k]->c.get()))) return s;
     R.clouds.push_back(in[k]->c);
-    R.d_values.push_back(d_vals.p + first);
-    first += in[k]->c->n;
+    R.d_values.push_back(d_vals.p + first[k]);
   }
   {
     Drain drain{h->stream};
     SelDiagKeep keep(h);
     s = outlier_queue(h, *spec, R);
     if (s) return s;
-    first = 0;
     for (size_t k = 0; k < n_clouds; k++) {
       DeviceCloud* c = in[k]->c.get();
-      res[k] = select_new_cloud(h);
       jobs[k].in = c->pts.p;
       jobs[k].n = c->n;
-      jobs[k].keys = d_vals.p + first;
+      jobs[k].keys = d_vals.p + first[k];
       jobs[k].key_range = spec->method == NDT_OUTLIER_STATISTICAL ? R.d_rows.p + 6 * k + 4 : nullptr;
-      jobs[k].out = blk->pts.p + first;
-      jobs[k].res = res[k].get();
-      first += c->n;
+      jobs[k].out = outs.at(k);
+      jobs[k].res = outs.cloud(k);
     }
     s = select_run(h, jobs, key_spec(*spec), nullptr);
     if (s) return s;
   }
   outlier_finish(h, *spec, R);
   for (size_t k = 0; k < n_clouds; k++) {
-    res[k]->pts.borrow(jobs[k].out, jobs[k].kept);
-    res[k]->owner = blk;
-    out[k] = new ndt_cloud_s{res[k]};
+    out[k] = outs.publish(k, jobs[k].kept);
     if (n_kept) n_kept[k] = jobs[k].kept;
     if (stats) stats[k] = R.stats[k];
   }

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstddef>
 
+#include "ndt_cloud_ops.hpp"
 #include "ndt_mi355.h"
 
 namespace ndt {
@@ -42,14 +43,8 @@ inline void outlier_plan(size_t n, int* blocks, int* qpb) {
   *qpb = b ? static_cast<int>((passes + b - 1) / b) * kOutlierTeams : 0;
 }
 
-// The statistics' plan, a function of n alone: block b reduces the values [b * chunk, min(n, (b + 1) * chunk)) to
+// The statistics' plan (range_plan), a function of n alone: block b reduces the values [b * chunk, min(n, (b + 1) * chunk)) to
 // (count, sum, M2 about its own mean); the rows are merged in block order by Chan's rule.
-inline void outlier_stat_plan(size_t n, int* blocks, int* chunk) {
-  size_t c = kOutlierStatChunk;
-  const size_t per = (n + kOutlierStatMaxBlocks - 1) / kOutlierStatMaxBlocks;
-  if (per > c) c = per;
-  *chunk = static_cast<int>(c);
-  *blocks = static_cast<int>((n + c - 1) / c);
-}
+inline void outlier_stat_plan(size_t n, int* blocks, int* chunk) { range_plan(n, kOutlierStatChunk, kOutlierStatMaxBlocks, blocks, chunk); }
 
 }  // namespace ndt

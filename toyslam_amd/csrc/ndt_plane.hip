@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void k_plane_models(PlaneMember one, const Pla
   const int H = P.n_hypotheses;
   if (g >= static_cast<long long>(n_members) * H) return;
   const int c = static_cast<int>(g / H), h = static_cast<int>(g % H);
-  const PlaneMember m = n_members == 1 ? one : members[c];
+  const PlaneMember m = ndt::member_of(one, members, n_members, c);
   double coeff[4] = {0.0, 0.0, 0.0, 0.0};
   int state = ndt::kPlaneDegenerateState;
   if (m.n >= 3) {
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(kBlock) void k_plane_counts(PlaneMember one, const 
                                                          double T, int rows_form) {
   __shared__ double tx[kTile], ty[kTile], tz[kTile];
   const int b = static_cast<int>(blockIdx.x);
-  const PlaneMember m = n_members == 1 ? one : members[ndt::member_at(n_members, b, [&](int c) { return members[c].first_block; })];
+  const PlaneMember m = ndt::block_member(one, members, n_members, b, &PlaneMember::first_block);
   const int lb = b - m.first_block;
   if (lb >= m.n_blocks) return;  // (uniform over the block)
   const int hb = lb % m.hyp_blocks, slot = lb / m.hyp_blocks;
@@ -102,8 +102,8 @@ __global__ __launch_bounds__(kBlock) void k_plane_counts(PlaneMember one, const 
   }
   unsigned cnt = 0;
   for (int t = slot; t < m.tiles; t += m.tile_blocks) {
-    const long long start = static_cast<long long>(t) * kTile;
-    const int len = static_cast<int>(min(static_cast<long long>(kTile), m.n - start));
+    long long start;
+    const int len = ndt::block_range(t, kTile, m.n, &start);
     __syncthreads();  // the tile before this one has been walked by every wave
     for (int i = threadIdx.x; i < len; i += kBlock) {
       const float4 p = m.pts[start + i];
@@ -129,7 +129,7 @@ __global__ __launch_bounds__(kBlock) void k_plane_best(PlaneMember one, const Pl
   __shared__ long long s_cnt[kBlock];
   __shared__ int s_h[kBlock];
   __shared__ unsigned s_deg[kBlock], s_rej[kBlock];
-  const PlaneMember m = n_members == 1 ? one : members[blockIdx.x];
+  const PlaneMember m = ndt::member_of(one, members, n_members, blockIdx.x);
   const int H = P.n_hypotheses, tid = threadIdx.x;
   long long bc = -1;  // the best count so far; -1: no valid hypothesis seen
   int bh = H;
@@ -198,32 +198,19 @@ __global__ __launch_bounds__(kBlock) void k_plane_best(PlaneMember one, const Pl
   }
 }
 
-// tree sum over the block's threads in a fixed order; the result in every thread
-__device__ __forceinline__ double plane_block_sum(double v, double* sh) {
-#pragma clang fp contract(off)
-  __syncthreads();
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = ndt::kPlaneSumBlock / 2; s > 0; s >>= 1) {
-    if (static_cast<int>(threadIdx.x) < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-    __syncthreads();
-  }
-  return sh[0];
-}
-
 __global__ __launch_bounds__(ndt::kPlaneSumBlock) void k_plane_sums(PlaneMember one, const PlaneMember* __restrict__ members, int n_members,
                                                                     double T) {
 #pragma clang fp contract(off)
   __shared__ double sh[ndt::kPlaneSumBlock];
   const int b = static_cast<int>(blockIdx.x);
-  const PlaneMember m = n_members == 1 ? one : members[ndt::member_at(n_members, b, [&](int c) { return members[c].sum_first; })];
+  const PlaneMember m = ndt::block_member(one, members, n_members, b, &PlaneMember::sum_first);
   const int lb = b - m.sum_first;
   if (lb >= m.sum_blocks) return;
   const bool found = m.chosen[0] != 0.0;
   const double nx = m.chosen[5], ny = m.chosen[6], nz = m.chosen[7], d = m.chosen[8];
   const double ax = m.chosen[9], ay = m.chosen[10], az = m.chosen[11];
-  const long long start = static_cast<long long>(lb) * m.sum_chunk;
-  const int len = found ? static_cast<int>(min(static_cast<long long>(m.sum_chunk), m.n - start)) : 0;
+  long long start;
+  const int len = found ? ndt::block_range(lb, m.sum_chunk, m.n, &start) : 0;
   double acc[kSumRow] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   for (int j = threadIdx.x; j < len; j += ndt::kPlaneSumBlock) {
     const float4 p = m.pts[start + j];
@@ -244,7 +231,7 @@ __global__ __launch_bounds__(ndt::kPlaneSumBlock) void k_plane_sums(PlaneMember 
   double* row = m.sum_rows + static_cast<size_t>(lb) * kSumRow;
 #pragma unroll
   for (int k = 0; k < kSumRow; k++) {
-    const double v = plane_block_sum(acc[k], sh);
+    const double v = ndt::block_sum<ndt::kPlaneSumBlock>(acc[k], sh);
     if (threadIdx.x == 0) row[k] = v;
   }
 }
@@ -252,14 +239,14 @@ __global__ __launch_bounds__(ndt::kPlaneSumBlock) void k_plane_sums(PlaneMember 
 __global__ __launch_bounds__(256) void k_plane_keys(PlaneMember one, const PlaneMember* __restrict__ members, int n_members, double T) {
   __shared__ unsigned w_in[4], w_fin[4];
   const int b = static_cast<int>(blockIdx.x);
-  const PlaneMember m = n_members == 1 ? one : members[ndt::member_at(n_members, b, [&](int c) { return members[c].key_first; })];
+  const PlaneMember m = ndt::block_member(one, members, n_members, b, &PlaneMember::key_first);
   const int lb = b - m.key_first;
   if (lb >= m.key_blocks) return;
   const bool found = m.chosen[0] != 0.0;
   const double nx = m.chosen[5], ny = m.chosen[6], nz = m.chosen[7], d = m.chosen[8];
   const double nan = __longlong_as_double(0x7ff8000000000000ll), inf = __longlong_as_double(0x7ff0000000000000ll);
-  const long long start = static_cast<long long>(lb) * m.key_ppb;
-  const int len = static_cast<int>(min(static_cast<long long>(m.key_ppb), m.n - start));
+  long long start;
+  const int len = ndt::block_range(lb, m.key_ppb, m.n, &start);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   unsigned n_in = 0, n_fin = 0;
   for (int r0 = 0; r0 < len; r0 += 256) {
@@ -267,7 +254,7 @@ __global__ __launch_bounds__(256) void k_plane_keys(PlaneMember one, const Plane
     bool fin = false, in = false;
     if (i < len) {
       const float4 p = m.pts[start + i];
-      fin = __builtin_isfinite(p.x) && __builtin_isfinite(p.y) && __builtin_isfinite(p.z);
+      fin = ndt::finite3(p);
       double s = nan;
       if (fin) {
         s = found ? ndt::plane_distance(nx, ny, nz, d, static_cast<double>(p.x), static_cast<double>(p.y), static_cast<double>(p.z)) : inf;
@@ -292,11 +279,7 @@ __global__ __launch_bounds__(256) void k_plane_keys(PlaneMember one, const Plane
 }
 
 // development switches, read at every call (tools alternate the two merge forms in one process)
-int max_blocks_switch() {
-  const char* e = getenv("NDT_PLANE_MAX_BLOCKS");
-  const int x = e ? atoi(e) : 0;
-  return x > 0 ? std::min(x, ndt::kPlaneMaxBlocks) : ndt::kPlaneMaxBlocks;
-}
+int max_blocks_switch() { return env_block_cap("NDT_PLANE_MAX_BLOCKS", ndt::kPlaneMaxBlocks); }
 bool rows_switch() {
   const char* e = getenv("NDT_PLANE_MERGE");
   return e && std::strcmp(e, "rows") == 0;
@@ -310,18 +293,15 @@ struct PlaneRun {
   const int* d_triples = nullptr;
   double* keys_override = nullptr;  // the distances call: where the one cloud's keys go instead of d_keys
   bool rows = false;
-  std::vector<PlaneMember> mem;
-  DevBuf<unsigned char> d_mem;
+  MemberTable<PlaneMember> mem;
   DevBuf<double> d_models, d_chosen, d_keys, d_sum_rows;
   DevBuf<int> d_states;
   DevBuf<unsigned> d_counts, d_partials, d_tally;
   long long count_blocks = 0, key_blocks = 0, sum_blocks = 0;
   std::vector<double> chosen_host, sums_host;
   std::vector<unsigned> tally_host;
-  std::vector<size_t> key_first_pt;
+  std::vector<size_t> key_first_pt;  // [clouds + 1]: the points before each cloud, the total
   std::vector<ndt_plane_result> results;
-  const PlaneMember* table() const { return reinterpret_cast<const PlaneMember*>(d_mem.p); }
-  int n_mem() const { return static_cast<int>(mem.size()); }
 };
 
 // the buffers and the member table of a call (want_keys: the key launch follows)
@@ -331,11 +311,11 @@ ndt_status plane_plan_run(ndt_handle h, PlaneRun& R, bool want_keys) {
   const size_t H = static_cast<size_t>(R.P.n_hypotheses);
   const int cap = max_blocks_switch();
   R.rows = rows_switch();
-  R.mem.assign(nc, PlaneMember{});
-  R.key_first_pt.assign(nc, 0);
+  R.mem.host.assign(nc, PlaneMember{});
+  R.key_first_pt.assign(nc + 1, 0);
   size_t total_pts = 0, partial_rows = 0;
   for (size_t k = 0; k < nc; k++) {
-    PlaneMember& m = R.mem[k];
+    PlaneMember& m = R.mem.host[k];
     const size_t n = R.clouds[k]->n;
     m.pts = R.clouds[k]->pts.p;
     m.n = static_cast<int>(n);
@@ -359,6 +339,7 @@ ndt_status plane_plan_run(ndt_handle h, PlaneRun& R, bool want_keys) {
     total_pts += n;
     partial_rows += static_cast<size_t>(m.tile_blocks);
   }
+  R.key_first_pt[nc] = total_pts;
   if (R.count_blocks > std::numeric_limits<int>::max()) return fail(NDT_ERR_INVALID, "too many points");
   HIP_TRY(R.d_models.reserve(nc * H * 4));
   HIP_TRY(R.d_states.reserve(nc * H));
@@ -370,7 +351,7 @@ ndt_status plane_plan_run(ndt_handle h, PlaneRun& R, bool want_keys) {
   if (R.refine) HIP_TRY(R.d_sum_rows.reserve(std::max<size_t>(static_cast<size_t>(R.sum_blocks) * kSumRow, 1)));
   size_t rows_before = 0;
   for (size_t k = 0; k < nc; k++) {
-    PlaneMember& m = R.mem[k];
+    PlaneMember& m = R.mem.host[k];
     m.models = R.d_models.p + k * H * 4;
     m.states = R.d_states.p + k * H;
     m.counts = R.d_counts.p + k * H;
@@ -381,11 +362,7 @@ ndt_status plane_plan_run(ndt_handle h, PlaneRun& R, bool want_keys) {
     m.sum_rows = R.refine ? R.d_sum_rows.p + static_cast<size_t>(m.sum_first) * kSumRow : nullptr;
     rows_before += static_cast<size_t>(m.tile_blocks);
   }
-  if (nc > 1) {
-    HIP_TRY(R.d_mem.reserve(nc * sizeof(PlaneMember)));
-    HIP_TRY(hipMemcpyAsync(R.d_mem.p, R.mem.data(), nc * sizeof(PlaneMember), hipMemcpyHostToDevice, st));
-  }
-  return NDT_OK;
+  return R.mem.upload(st);
 }
 
 // models, counts, choice: queued on h's stream, nothing waited for
@@ -394,44 +371,25 @@ ndt_status plane_front(ndt_handle h, PlaneRun& R) {
   const size_t nc = R.clouds.size();
   const size_t H = static_cast<size_t>(R.P.n_hypotheses);
   const unsigned model_blocks = static_cast<unsigned>((nc * H + 255) / 256);
-  hipLaunchKernelGGL(k_plane_models, dim3(model_blocks), dim3(256), 0, st, R.mem[0], R.table(), R.n_mem(), R.P, R.d_triples);
+  hipLaunchKernelGGL(k_plane_models, dim3(model_blocks), dim3(256), 0, st, R.mem.one(), R.mem.table(), R.mem.n(), R.P, R.d_triples);
   HIP_TRY(hipGetLastError());
   h->pl_launches++;
   if (!R.rows) HIP_TRY(hipMemsetAsync(R.d_counts.p, 0, nc * H * sizeof(unsigned), st));
   if (R.count_blocks) {
-    hipLaunchKernelGGL(k_plane_counts, dim3(static_cast<unsigned>(R.count_blocks)), dim3(kBlock), 0, st, R.mem[0], R.table(), R.n_mem(),
+    hipLaunchKernelGGL(k_plane_counts, dim3(static_cast<unsigned>(R.count_blocks)), dim3(kBlock), 0, st, R.mem.one(), R.mem.table(), R.mem.n(),
                        R.P.n_hypotheses, R.P.T, R.rows ? 1 : 0);
     HIP_TRY(hipGetLastError());
     h->pl_launches++;
   }
   h->pl_count_blocks = static_cast<size_t>(R.count_blocks);
-  hipLaunchKernelGGL(k_plane_best, dim3(static_cast<unsigned>(nc)), dim3(kBlock), 0, st, R.mem[0], R.table(), R.n_mem(), R.P, R.d_triples,
+  hipLaunchKernelGGL(k_plane_best, dim3(static_cast<unsigned>(nc)), dim3(kBlock), 0, st, R.mem.one(), R.mem.table(), R.mem.n(), R.P, R.d_triples,
                      R.rows ? 1 : 0);
   HIP_TRY(hipGetLastError());
   h->pl_launches++;
   return NDT_OK;
 }
 
-struct SelDiagKeep {  // ndt_diag_select reports on the selections alone: what the compaction inside a plane call did is taken back
-  ndt_handle h;
-  size_t a, b, c;
-  explicit SelDiagKeep(ndt_handle hh) : h(hh), a(hh->sel_launches), b(hh->sel_blocks), c(hh->sel_clouds) {}
-  ~SelDiagKeep() {
-    h->sel_launches = a;
-    h->sel_blocks = b;
-    h->sel_clouds = c;
-  }
-};
-struct Drain {  // whatever path leaves: the queued copies have read (written) the run's host memory before it dies
-  hipStream_t s;
-  ~Drain() { (void)hipStreamSynchronize(s); }
-};
-
-ndt_status spec_checks(const ndt_plane_spec* spec) {
-  if (!spec) return fail(NDT_ERR_INVALID, "null spec");
-  if (const char* why = ndt::plane_spec_error(*spec)) return fail(NDT_ERR_INVALID, why);
-  return NDT_OK;
-}
+ndt_status spec_checks(const ndt_plane_spec* spec) { return ndtc::spec_checks(spec, ndt::plane_spec_error); }
 
 void diag_reset(ndt_handle h, size_t clouds) {
   h->pl_launches = h->pl_select_launches = h->pl_count_blocks = 0;
@@ -452,8 +410,6 @@ ndt_status segment_run(ndt_handle h, PlaneRun& R, ndt_cloud* inliers, ndt_cloud*
   const size_t nc = R.clouds.size();
   diag_reset(h, nc);
   R.results.assign(nc, ndt_plane_result{});
-  size_t total = 0;
-  for (size_t k = 0; k < nc; k++) total += R.clouds[k]->n;
   Drain drain{st};
   SelDiagKeep keep(h);
   ndt_status s = plane_plan_run(h, R, true);
@@ -463,7 +419,7 @@ ndt_status segment_run(ndt_handle h, PlaneRun& R, ndt_cloud* inliers, ndt_cloud*
   std::vector<char> refined(nc, 0);
   const bool sums_ran = R.refine && R.sum_blocks;
   if (sums_ran) {
-    hipLaunchKernelGGL(k_plane_sums, dim3(static_cast<unsigned>(R.sum_blocks)), dim3(ndt::kPlaneSumBlock), 0, st, R.mem[0], R.table(), R.n_mem(),
+    hipLaunchKernelGGL(k_plane_sums, dim3(static_cast<unsigned>(R.sum_blocks)), dim3(ndt::kPlaneSumBlock), 0, st, R.mem.one(), R.mem.table(), R.mem.n(),
                        R.P.T);
     HIP_TRY(hipGetLastError());
     h->pl_launches++;
@@ -475,7 +431,7 @@ ndt_status segment_run(ndt_handle h, PlaneRun& R, ndt_cloud* inliers, ndt_cloud*
       double* row = &R.chosen_host[k * kChosen];
       if (row[0] == 0.0) continue;
       double S[kSumRow] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-      const PlaneMember& m = R.mem[k];
+      const PlaneMember& m = R.mem.host[k];
       for (int b = 0; b < m.sum_blocks; b++)
         for (int j = 0; j < kSumRow; j++) S[j] += R.sums_host[static_cast<size_t>(m.sum_first + b) * kSumRow + j];
       double coeff[4];
@@ -488,36 +444,31 @@ ndt_status segment_run(ndt_handle h, PlaneRun& R, ndt_cloud* inliers, ndt_cloud*
   R.tally_host.assign(nc * 2, 0u);
   HIP_TRY(hipMemsetAsync(R.d_tally.p, 0, nc * 2 * sizeof(unsigned), st));
   if (R.key_blocks) {
-    hipLaunchKernelGGL(k_plane_keys, dim3(static_cast<unsigned>(R.key_blocks)), dim3(256), 0, st, R.mem[0], R.table(), R.n_mem(), R.P.T);
+    hipLaunchKernelGGL(k_plane_keys, dim3(static_cast<unsigned>(R.key_blocks)), dim3(256), 0, st, R.mem.one(), R.mem.table(), R.mem.n(), R.P.T);
     HIP_TRY(hipGetLastError());
     h->pl_launches++;
   }
   // (without a refinement nothing has come back so far: the rows are read behind the last plane kernel, in one wait)
   if (!sums_ran) HIP_TRY(hipMemcpyAsync(R.chosen_host.data(), R.d_chosen.p, nc * kChosen * sizeof(double), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(R.tally_host.data(), R.d_tally.p, nc * 2 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-  // ---- the selections: the outputs of one kind are slices of one block (room for every input point), kept alive by `owner`
+  // ---- the selections: the outputs of one kind are slices of one block
   ndt_cloud* outs[2] = {inliers, others};
-  std::vector<std::shared_ptr<DeviceCloud>> res[2];
+  OutSlices slices[2];
   std::vector<SelJob> jobs[2];
-  std::shared_ptr<DeviceCloud> blk[2];
   for (int v = 0; v < 2; v++) {
     if (!outs[v]) continue;
     ndt_select_spec sel{};
     sel.flags = v == 0 ? NDT_SELECT_KEY : (NDT_SELECT_KEY | NDT_SELECT_KEY_NEGATE | NDT_SELECT_FINITE);
     sel.key_lo = -R.P.T;
     sel.key_hi = R.P.T;
-    blk[v] = select_new_cloud(h);
-    HIP_TRY(blk[v]->pts.reserve(std::max<size_t>(total, 1)));
-    blk[v]->n = total;
-    res[v].resize(nc);
+    if ((s = slices[v].reserve(h, R.key_first_pt))) return s;
     jobs[v].resize(nc);
     for (size_t k = 0; k < nc; k++) {
-      res[v][k] = select_new_cloud(h);
       jobs[v][k].in = R.clouds[k]->pts.p;
       jobs[v][k].n = R.clouds[k]->n;
       jobs[v][k].keys = R.d_keys.p + R.key_first_pt[k];
-      jobs[v][k].out = blk[v]->pts.p + R.key_first_pt[k];
-      jobs[v][k].res = res[v][k].get();
+      jobs[v][k].out = slices[v].at(k);
+      jobs[v][k].res = slices[v].cloud(k);
     }
     s = select_run(h, jobs[v], sel, nullptr);
     if (s) return s;
@@ -539,11 +490,7 @@ ndt_status segment_run(ndt_handle h, PlaneRun& R, ndt_cloud* inliers, ndt_cloud*
   }
   for (int v = 0; v < 2; v++) {
     if (!outs[v]) continue;
-    for (size_t k = 0; k < nc; k++) {
-      res[v][k]->pts.borrow(jobs[v][k].out, jobs[v][k].kept);
-      res[v][k]->owner = blk[v];
-      outs[v][k] = new ndt_cloud_s{res[v][k]};
-    }
+    for (size_t k = 0; k < nc; k++) outs[v][k] = slices[v].publish(k, jobs[v][k].kept);
   }
   return NDT_OK;
 }
@@ -556,12 +503,10 @@ extern "C" {
 ndt_status ndt_cloud_plane_counts(ndt_handle h, ndt_cloud in, const ndt_plane_spec* spec, const int32_t* triples, double* coeffs,
                                   int32_t* states, uint32_t* counts) {
   if (!h || !counts) return fail(NDT_ERR_INVALID, "bad arguments");
-  ndt_status s = select_cloud_checks(h, in);
-  if (!s) s = spec_checks(spec);
-  if (!s) s = triples_checks(triples, spec->n_hypotheses, in->c->n);
-  if (s) return s;
-  s = ensure_device(h);
-  if (!s) s = cloud_use_on(h, in->c.get());
+  ndt_status s = cloud_entry(h, in, [&] {
+    const ndt_status e = spec_checks(spec);
+    return e ? e : triples_checks(triples, spec->n_hypotheses, in->c->n);
+  });
   if (s) return s;
   hipStream_t st = h->stream;
   const size_t H = static_cast<size_t>(spec->n_hypotheses);
@@ -591,12 +536,10 @@ ndt_status ndt_cloud_segment_plane(ndt_handle h, ndt_cloud in, const ndt_plane_s
   if (inliers) *inliers = nullptr;
   if (others) *others = nullptr;
   if (!h || !result) return fail(NDT_ERR_INVALID, "bad arguments");
-  ndt_status s = select_cloud_checks(h, in);
-  if (!s) s = spec_checks(spec);
-  if (!s) s = triples_checks(triples, spec->n_hypotheses, in->c->n);
-  if (s) return s;
-  s = ensure_device(h);
-  if (!s) s = cloud_use_on(h, in->c.get());
+  ndt_status s = cloud_entry(h, in, [&] {
+    const ndt_status e = spec_checks(spec);
+    return e ? e : triples_checks(triples, spec->n_hypotheses, in->c->n);
+  });
   if (s) return s;
   PlaneRun R;
   R.clouds.push_back(in->c);
@@ -622,20 +565,12 @@ ndt_status ndt_cloud_segment_plane(ndt_handle h, ndt_cloud in, const ndt_plane_s
 ndt_status ndt_cloud_segment_plane_clouds(ndt_handle h, const ndt_cloud* in, size_t n_clouds, const ndt_plane_spec* spec,
                                           ndt_plane_result* results, ndt_cloud* inliers, ndt_cloud* others) {
   if (!h) return fail(NDT_ERR_INVALID, "bad arguments");
-  if (n_clouds > 65535) return fail(NDT_ERR_INVALID, "at most 65535 clouds per call");
-  for (size_t k = 0; k < n_clouds; k++) {
-    if (inliers) inliers[k] = nullptr;
-    if (others) others[k] = nullptr;
-  }
-  if (n_clouds && (!in || !results)) return fail(NDT_ERR_INVALID, "null clouds or results");
-  ndt_status s = spec_checks(spec);
+  ndt_status s = clouds_begin(n_clouds, inliers, others);
   if (s) return s;
-  size_t total = 0;
-  for (size_t k = 0; k < n_clouds; k++) {
-    if ((s = select_cloud_checks(h, in[k]))) return s;
-    total += in[k]->c->n;
-  }
-  if (total > static_cast<size_t>(std::numeric_limits<int>::max())) return fail(NDT_ERR_INVALID, "too many points");
+  if (n_clouds && (!in || !results)) return fail(NDT_ERR_INVALID, "null clouds or results");
+  if ((s = spec_checks(spec))) return s;
+  std::vector<size_t> first;
+  if ((s = clouds_total(h, in, n_clouds, first))) return s;
   if (n_clouds == 0) return NDT_OK;
   s = ensure_device(h);
   if (s) return s;
@@ -659,27 +594,27 @@ ndt_status ndt_cloud_segment_plane_clouds(ndt_handle h, const ndt_cloud* in, siz
 
 ndt_status ndt_cloud_plane_distances(ndt_handle h, ndt_cloud in, const double coeff[4], double* values, int values_on_device) {
   if (!h || !coeff || !values) return fail(NDT_ERR_INVALID, "bad arguments");
-  ndt_status s = select_cloud_checks(h, in);
-  if (s) return s;
-  for (int k = 0; k < 4; k++)
-    if (!std::isfinite(coeff[k])) return fail(NDT_ERR_INVALID, "the plane must be finite");
-  if (coeff[0] == 0.0 && coeff[1] == 0.0 && coeff[2] == 0.0) return fail(NDT_ERR_INVALID, "the plane's normal must not be zero");
-  s = ensure_device(h);
-  if (!s) s = cloud_use_on(h, in->c.get());
+  ndt_status s = cloud_entry(h, in, [&]() -> ndt_status {
+    for (int k = 0; k < 4; k++)
+      if (!std::isfinite(coeff[k])) return fail(NDT_ERR_INVALID, "the plane must be finite");
+    if (coeff[0] == 0.0 && coeff[1] == 0.0 && coeff[2] == 0.0) return fail(NDT_ERR_INVALID, "the plane's normal must not be zero");
+    return NDT_OK;
+  });
   if (s) return s;
   hipStream_t st = h->stream;
   const size_t n = in->c->n;
   diag_reset(h, 1);
   if (n == 0) return NDT_OK;
-  DevBuf<double> d_vals, d_row;
-  if (!values_on_device) HIP_TRY(d_vals.reserve(n));
+  DoublesOut vals;
+  DevBuf<double> d_row;
+  if ((s = vals.reserve(values, n, values_on_device))) return s;
   HIP_TRY(d_row.reserve(kChosen));
   double row[kChosen] = {1.0, 0.0, 0.0, 0.0, 0.0, coeff[0], coeff[1], coeff[2], coeff[3]};
   PlaneMember m{};
   m.pts = in->c->pts.p;
   m.n = static_cast<int>(n);
   m.chosen = d_row.p;
-  m.keys = values_on_device ? values : d_vals.p;
+  m.keys = vals.at();
   ndt::select_plan(n, &m.key_blocks, &m.key_ppb);
   Drain drain{st};
   HIP_TRY(hipMemcpyAsync(d_row.p, row, sizeof(row), hipMemcpyHostToDevice, st));
@@ -687,7 +622,7 @@ ndt_status ndt_cloud_plane_distances(ndt_handle h, ndt_cloud in, const double co
                      0.0);
   HIP_TRY(hipGetLastError());
   h->pl_launches = 1;
-  if (!values_on_device) HIP_TRY(hipMemcpyAsync(values, d_vals.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
+  if ((s = vals.fetch(st))) return s;
   HIP_TRY(hipStreamSynchronize(st));
   return NDT_OK;
 }

@@ -10,6 +10,7 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "ndt_cloud_ops.hpp"
 #include "ndt_mi355.h"
 
 #if defined(__HIPCC__)
@@ -166,15 +167,9 @@ inline void plane_plan(size_t n, int n_hypotheses, int max_blocks, int* tiles, i
   *tile_blocks = static_cast<int>(tb);
 }
 
-// The plan of the refinement's sums, a function of n alone: block b sums the points [b * chunk, min(n, (b + 1) * chunk)); the
-// rows are added in block order.
-inline void plane_sum_plan(size_t n, int* blocks, int* chunk) {
-  size_t c = kPlaneSumChunk;
-  const size_t per = (n + kPlaneSumMaxBlocks - 1) / kPlaneSumMaxBlocks;
-  if (per > c) c = per;
-  *chunk = static_cast<int>(c);
-  *blocks = static_cast<int>((n + c - 1) / c);
-}
+// The plan of the refinement's sums (range_plan), a function of n alone: block b sums the points [b * chunk, min(n, (b + 1) * chunk));
+// the rows are added in block order.
+inline void plane_sum_plan(size_t n, int* blocks, int* chunk) { range_plan(n, kPlaneSumChunk, kPlaneSumMaxBlocks, blocks, chunk); }
 
 // The fit of the refinement: count inliers, S1 = sum q (x, y, z), S2 = sum q q^T (xx, xy, xz, yy, yz, zz), q = p - a.
 // The covariance S2/count - (S1/count)(S1/count)^T is solved by cyclic Jacobi rotations in f64; the normal is the eigenvector

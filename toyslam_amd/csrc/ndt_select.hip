@@ -12,6 +12,7 @@
 //            block of a cloud writes the cloud's total.
 // No block waits for another: the two launches are ordered by the stream and nothing else.  Totals and box rows are
 // written straight into page-locked memory and read behind the call's one wait; the host folds the rows.
+// The member table, the box fold (device and host), the output slices and the entry preambles are ndt_cloud_ops.hpp / .hip's.
 #include "ndt_internal.hpp"
 #include "ndt_select.hpp"
 
@@ -35,18 +36,17 @@ struct SelSeg {
   int slot;                  // where the cloud's total goes
 };
 
-// (a call of one cloud -- the usual one -- hands its segment over as a kernel argument: no table to copy up first)
 __global__ __launch_bounds__(kSelBlock) void k_select_count(SelSeg one, const SelSeg* __restrict__ segs, int n_segs, ndt_select_spec spec,
                                                             unsigned long long* __restrict__ ballots, unsigned* __restrict__ counts) {
   __shared__ unsigned wave_count[kSelWaves];
-  const SelSeg g = n_segs == 1 ? one : segs[ndt::member_at(n_segs, blockIdx.x, [&](int s) { return segs[s].first_block; })];
+  const SelSeg g = ndt::block_member(one, segs, n_segs, blockIdx.x, &SelSeg::first_block);
   if (g.key_range) {  // a key range of the cloud's own, computed on the device (the outlier filters' thresholds)
     spec.key_lo = g.key_range[0];
     spec.key_hi = g.key_range[1];
   }
   const int lb = static_cast<int>(blockIdx.x) - g.first_block;
-  const long long start = static_cast<long long>(lb) * g.ppb;
-  const int len = static_cast<int>(min(static_cast<long long>(g.ppb), g.n - start));
+  long long start;
+  const int len = ndt::block_range(lb, g.ppb, g.n, &start);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   unsigned long long* bw = ballots + g.word0 + static_cast<size_t>(lb) * g.wpb;
   const bool keyed = (spec.flags & NDT_SELECT_KEY) != 0;
@@ -72,25 +72,16 @@ __global__ __launch_bounds__(kSelBlock) void k_select_count(SelSeg one, const Se
   }
 }
 
-__device__ __forceinline__ float wave_min(float v) {
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-
 __global__ __launch_bounds__(kSelBlock) void k_select_place(SelSeg one, const SelSeg* __restrict__ segs, int n_segs,
                                                             const unsigned long long* __restrict__ ballots,
                                                             const unsigned* __restrict__ counts, float* __restrict__ rows,
                                                             unsigned* __restrict__ totals) {
   __shared__ unsigned wave_sum[kSelWaves];
   __shared__ float wave_box[kSelWaves][12];
-  const SelSeg g = n_segs == 1 ? one : segs[ndt::member_at(n_segs, blockIdx.x, [&](int s) { return segs[s].first_block; })];
+  const SelSeg g = ndt::block_member(one, segs, n_segs, blockIdx.x, &SelSeg::first_block);
   const int lb = static_cast<int>(blockIdx.x) - g.first_block;
-  const long long start = static_cast<long long>(lb) * g.ppb;
-  const int len = static_cast<int>(min(static_cast<long long>(g.ppb), g.n - start));
+  long long start;
+  const int len = ndt::block_range(lb, g.ppb, g.n, &start);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   // the base: what the blocks before this one, in this cloud, kept
   unsigned part = 0;
@@ -100,9 +91,7 @@ __global__ __launch_bounds__(kSelBlock) void k_select_place(SelSeg one, const Se
   __syncthreads();
   unsigned run = 0;
   for (int w = 0; w < kSelWaves; w++) run += wave_sum[w];
-  // box [0]: per coordinate over the values that are not NaN (fminf / fmaxf drop a NaN operand); box [1]: finite points
-  float mn0[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx0[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-  float mn1[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx1[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+  ndt::TwoBox<kSelWaves> box;  // of the kept records
   const unsigned long long* bw = ballots + g.word0 + static_cast<size_t>(lb) * g.wpb;
   for (int r0 = 0; r0 < len; r0 += kSelBlock) {
     const int w0 = r0 >> 6;
@@ -123,38 +112,13 @@ __global__ __launch_bounds__(kSelBlock) void k_select_place(SelSeg one, const Se
       const float4 p = g.in[i];
       g.out[dst] = p;
       if (g.idx) g.idx[dst] = static_cast<int>(i);
-      const float v[3] = {p.x, p.y, p.z};
-      const bool fin = __builtin_isfinite(p.x) && __builtin_isfinite(p.y) && __builtin_isfinite(p.z);
-#pragma unroll
-      for (int a = 0; a < 3; a++) {
-        mn0[a] = fminf(mn0[a], v[a]);
-        mx0[a] = fmaxf(mx0[a], v[a]);
-        if (fin) {
-          mn1[a] = fminf(mn1[a], v[a]);
-          mx1[a] = fmaxf(mx1[a], v[a]);
-        }
-      }
+      box.add(p);
     }
     run += total;
   }
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-    const float r0v = wave_min(mn0[a]), r1v = wave_max(mx0[a]), r2v = wave_min(mn1[a]), r3v = wave_max(mx1[a]);
-    if (lane == 0) {
-      wave_box[wave][a] = r0v;
-      wave_box[wave][3 + a] = r1v;
-      wave_box[wave][6 + a] = r2v;
-      wave_box[wave][9 + a] = r3v;
-    }
-  }
+  box.to_lds(wave_box);
   __syncthreads();
-  if (threadIdx.x < 12) {
-    const int t = threadIdx.x;
-    const bool is_min = (t % 6) < 3;
-    float v = wave_box[0][t];
-    for (int w = 1; w < kSelWaves; w++) v = is_min ? fminf(v, wave_box[w][t]) : fmaxf(v, wave_box[w][t]);
-    rows[static_cast<size_t>(blockIdx.x) * 12 + t] = v;
-  }
+  if (threadIdx.x < 12) rows[static_cast<size_t>(blockIdx.x) * 12 + threadIdx.x] = box.block_value(wave_box, threadIdx.x);
   if (lb == g.n_blocks - 1 && threadIdx.x == 0) totals[g.slot] = run;
 }
 
@@ -166,7 +130,7 @@ ndt_status select_run(ndt_handle h, std::vector<SelJob>& jobs, const ndt_select_
   hipStream_t st = h->stream;
   h->sel_launches = h->sel_blocks = 0;
   h->sel_clouds = jobs.size();
-  std::vector<SelSeg> segs;
+  MemberTable<SelSeg> segs;
   long long total_blocks = 0;
   unsigned long long total_words = 0;
   for (size_t k = 0; k < jobs.size(); k++) {
@@ -188,15 +152,15 @@ ndt_status select_run(ndt_handle h, std::vector<SelJob>& jobs, const ndt_select_
     g.first_block = static_cast<int>(total_blocks);
     g.n_blocks = blocks;
     g.slot = static_cast<int>(k);
-    segs.push_back(g);
+    segs.host.push_back(g);
     total_blocks += blocks;
     total_words += static_cast<unsigned long long>(blocks) * g.wpb;
   }
-  if (!segs.empty()) {
+  if (!segs.host.empty()) {
     if (total_blocks > std::numeric_limits<int>::max()) return fail(NDT_ERR_INVALID, "too many points");
     const size_t nb = static_cast<size_t>(total_blocks);
     // page-locked: [segment table | totals, one per job | box rows, one per block]
-    const size_t seg_bytes = (segs.size() * sizeof(SelSeg) + 15) / 16 * 16;
+    const size_t seg_bytes = (segs.bytes() + 15) / 16 * 16;
     const size_t tot_bytes = (jobs.size() * sizeof(unsigned) + 15) / 16 * 16;
     const size_t row_bytes = nb * 12 * sizeof(float);
     ndt_status s = pinned_at_least(h->sel_pinned, h->sel_pinned_bytes, seg_bytes + tot_bytes + row_bytes, st);
@@ -204,39 +168,26 @@ ndt_status select_run(ndt_handle h, std::vector<SelJob>& jobs, const ndt_select_
     unsigned char* pin = static_cast<unsigned char*>(h->sel_pinned);
     unsigned* totals = reinterpret_cast<unsigned*>(pin + seg_bytes);
     float* rows = reinterpret_cast<float*>(pin + seg_bytes + tot_bytes);
-    std::memcpy(pin, segs.data(), segs.size() * sizeof(SelSeg));
+    std::memcpy(pin, segs.host.data(), segs.bytes());
     std::memset(totals, 0, tot_bytes);
-    DevBuf<unsigned char> d_segs;
     DevBuf<unsigned long long> ballots;
     DevBuf<unsigned> counts;
-    const int n_segs = static_cast<int>(segs.size());
-    if (n_segs > 1) {
-      HIP_TRY(d_segs.reserve(seg_bytes));
-      HIP_TRY(hipMemcpyAsync(d_segs.p, pin, seg_bytes, hipMemcpyHostToDevice, st));
-    }
+    if ((s = segs.upload(st, pin))) return s;
     HIP_TRY(ballots.reserve(static_cast<size_t>(total_words)));
     HIP_TRY(counts.reserve(nb));
-    const SelSeg* ds = reinterpret_cast<const SelSeg*>(d_segs.p);
-    hipLaunchKernelGGL(k_select_count, dim3(static_cast<unsigned>(nb)), dim3(kSelBlock), 0, st, segs[0], ds, n_segs, spec, ballots.p, counts.p);
+    hipLaunchKernelGGL(k_select_count, dim3(static_cast<unsigned>(nb)), dim3(kSelBlock), 0, st, segs.one(), segs.table(), segs.n(), spec, ballots.p, counts.p);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_select_place, dim3(static_cast<unsigned>(nb)), dim3(kSelBlock), 0, st, segs[0], ds, n_segs, ballots.p, counts.p, rows, totals);
+    hipLaunchKernelGGL(k_select_place, dim3(static_cast<unsigned>(nb)), dim3(kSelBlock), 0, st, segs.one(), segs.table(), segs.n(), ballots.p, counts.p, rows, totals);
     HIP_TRY(hipGetLastError());
     if (idx_host && jobs[0].idx && jobs[0].n)
       HIP_TRY(hipMemcpyAsync(idx_host, jobs[0].idx, jobs[0].n * sizeof(int), hipMemcpyDeviceToHost, st));
     h->sel_launches = 2;
     h->sel_blocks = nb;
     HIP_TRY(hipStreamSynchronize(st));
-    for (const SelSeg& g : segs) {
+    for (const SelSeg& g : segs.host) {
       SelJob& j = jobs[static_cast<size_t>(g.slot)];
       j.kept = totals[g.slot];
-      if (!j.res || j.kept == 0) continue;
-      for (int b = g.first_block; b < g.first_block + g.n_blocks; b++)
-        for (int v = 0; v < 2; v++)
-          for (int a = 0; a < 3; a++) {
-            j.res->bb_min[v][a] = std::min(j.res->bb_min[v][a], rows[static_cast<size_t>(b) * 12 + v * 6 + a]);
-            j.res->bb_max[v][a] = std::max(j.res->bb_max[v][a], rows[static_cast<size_t>(b) * 12 + v * 6 + 3 + a]);
-          }
-      j.res->box_route = NDT_BOX_ROUTE_SELECT;
+      if (j.res && j.kept) fold_box_rows(j.res, rows, 12, g.first_block, g.n_blocks, NDT_BOX_ROUTE_SELECT);
     }
   }
   for (SelJob& j : jobs)
@@ -244,30 +195,10 @@ ndt_status select_run(ndt_handle h, std::vector<SelJob>& jobs, const ndt_select_
   return NDT_OK;
 }
 
-std::shared_ptr<DeviceCloud> select_new_cloud(ndt_handle h) {
-  auto c = std::make_shared<DeviceCloud>();
-  c->device = h->device;
-  c->made_on = h->stream;
-  return c;
-}
-
-// what every selection refuses of its spec
-static ndt_status spec_checks(const ndt_select_spec* spec) {
-  if (!spec) return fail(NDT_ERR_INVALID, "null spec");
-  if (const char* why = ndt::select_spec_error(*spec)) return fail(NDT_ERR_INVALID, why);
-  return NDT_OK;
-}
-ndt_status select_cloud_checks(ndt_handle h, ndt_cloud c) {
-  if (!c || !c->c) return fail(NDT_ERR_INVALID, "null cloud");
-  if (c->c->device >= 0 && c->c->device != h->device) return fail(NDT_ERR_INVALID, "the cloud lives on another device");
-  if (c->c->n > static_cast<size_t>(std::numeric_limits<int>::max())) return fail(NDT_ERR_INVALID, "too many points");
-  return NDT_OK;
-}
-
 // one cloud's records (n at d_in; keys on the device or null) into a new cloud; what ndt_cloud_select and the NVTL form share
 ndt_status select_one(ndt_handle h, const float4* d_in, size_t n, const ndt_select_spec& spec, const double* d_keys,
                       std::shared_ptr<DeviceCloud>& out, int32_t* kept_idx, size_t* n_kept, const double* d_key_range) {
-  auto c = select_new_cloud(h);
+  auto c = new_cloud(h);
   std::vector<SelJob> jobs(1);
   DevBuf<int> d_idx;
   int* idx_host = nullptr;
@@ -286,11 +217,9 @@ ndt_status select_one(ndt_handle h, const float4* d_in, size_t n, const ndt_sele
   jobs[0].out = c->pts.p;
   jobs[0].idx = kept_idx ? d_idx.p : nullptr;
   jobs[0].res = c.get();
-  ndt_status s = select_run(h, jobs, spec, idx_host);
-  if (s) {
-    (void)hipStreamSynchronize(h->stream);  // (nothing queued may still write into what goes back to the pool)
-    return s;
-  }
+  Drain drain{h->stream};  // (on a failure nothing queued may still write into what goes back to the pool)
+  if (ndt_status s = select_run(h, jobs, spec, idx_host)) return s;
+  drain.done = true;  // (the run has waited)
   if (kept_idx && jobs[0].kept) std::memcpy(kept_idx, idx_host, jobs[0].kept * sizeof(int32_t));
   if (n_kept) *n_kept = jobs[0].kept;
   out = c;
@@ -305,25 +234,16 @@ ndt_status ndt_cloud_select(ndt_handle h, ndt_cloud in, const ndt_select_spec* s
                             ndt_cloud* out, int32_t* kept_idx, size_t* n_kept) {
   if (out) *out = nullptr;
   if (!h || !out) return fail(NDT_ERR_INVALID, "bad arguments");
-  ndt_status s = select_cloud_checks(h, in);
-  if (!s) s = spec_checks(spec);
-  if (s) return s;
-  if ((spec->flags & NDT_SELECT_KEY) && !keys) return fail(NDT_ERR_INVALID, "a KEY selection needs keys");
-  s = ensure_device(h);
-  if (!s) s = cloud_use_on(h, in->c.get());
+  ndt_status s = cloud_entry(h, in, [&]() -> ndt_status {
+    if (ndt_status e = spec_checks(spec, ndt::select_spec_error)) return e;
+    if ((spec->flags & NDT_SELECT_KEY) && !keys) return fail(NDT_ERR_INVALID, "a KEY selection needs keys");
+    return NDT_OK;
+  });
   if (s) return s;
   const size_t n = in->c->n;
   DevBuf<double> d_keys;
   const double* kp = nullptr;
-  if ((spec->flags & NDT_SELECT_KEY) && n) {
-    if (keys_on_device) {
-      kp = keys;
-    } else {
-      HIP_TRY(d_keys.reserve(n));
-      HIP_TRY(hipMemcpyAsync(d_keys.p, keys, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      kp = d_keys.p;
-    }
-  }
+  if ((spec->flags & NDT_SELECT_KEY) && n && (s = doubles_in(h->stream, keys, n, keys_on_device, d_keys, &kp))) return s;
   std::shared_ptr<DeviceCloud> c;
   s = select_one(h, in->c->pts.p, n, *spec, kp, c, kept_idx, n_kept);
   if (s) return s;
@@ -334,47 +254,32 @@ ndt_status ndt_cloud_select(ndt_handle h, ndt_cloud in, const ndt_select_spec* s
 ndt_status ndt_cloud_select_clouds(ndt_handle h, const ndt_cloud* in, size_t n_clouds, const ndt_select_spec* spec, ndt_cloud* out,
                                    size_t* n_kept) {
   if (!h || !out) return fail(NDT_ERR_INVALID, "bad arguments");
-  if (n_clouds > 65535) return fail(NDT_ERR_INVALID, "at most 65535 clouds per call");
-  for (size_t k = 0; k < n_clouds; k++) out[k] = nullptr;
-  if (n_clouds && !in) return fail(NDT_ERR_INVALID, "null clouds");
-  ndt_status s = spec_checks(spec);
+  ndt_status s = clouds_begin(n_clouds, out);
   if (s) return s;
+  if (n_clouds && !in) return fail(NDT_ERR_INVALID, "null clouds");
+  if ((s = spec_checks(spec, ndt::select_spec_error))) return s;
   if (spec->flags & NDT_SELECT_KEY) return fail(NDT_ERR_INVALID, "the many-clouds selection takes no KEY test");
-  size_t total = 0;
-  for (size_t k = 0; k < n_clouds; k++) {
-    if ((s = select_cloud_checks(h, in[k]))) return s;
-    total += in[k]->c->n;
-  }
-  if (total > static_cast<size_t>(std::numeric_limits<int>::max())) return fail(NDT_ERR_INVALID, "too many points");
+  std::vector<size_t> first;
+  if ((s = clouds_total(h, in, n_clouds, first))) return s;
   if (n_clouds == 0) return NDT_OK;
   s = ensure_device(h);
   if (s) return s;
-  // the outputs are slices of one block (room for every input point), kept alive by the slices' `owner`
-  auto blk = select_new_cloud(h);
-  std::vector<std::shared_ptr<DeviceCloud>> res(n_clouds);
+  OutSlices outs;
   std::vector<SelJob> jobs(n_clouds);
-  HIP_TRY(blk->pts.reserve(std::max<size_t>(total, 1)));
-  blk->n = total;
-  size_t first = 0;
+  if ((s = outs.reserve(h, first))) return s;
   for (size_t k = 0; k < n_clouds; k++) {
     DeviceCloud* c = in[k]->c.get();
     if ((s = cloud_use_on(h, c))) return s;
-    res[k] = select_new_cloud(h);
     jobs[k].in = c->pts.p;
     jobs[k].n = c->n;
-    jobs[k].out = blk->pts.p + first;
-    jobs[k].res = res[k].get();
-    first += c->n;
+    jobs[k].out = outs.at(k);
+    jobs[k].res = outs.cloud(k);
   }
-  s = select_run(h, jobs, *spec, nullptr);
-  if (s) {
-    (void)hipStreamSynchronize(h->stream);  // (nothing queued may still write into what goes back to the pool)
-    return s;
-  }
+  Drain drain{h->stream};  // (on a failure nothing queued may still write into what goes back to the pool)
+  if ((s = select_run(h, jobs, *spec, nullptr))) return s;
+  drain.done = true;  // (the run has waited)
   for (size_t k = 0; k < n_clouds; k++) {
-    res[k]->pts.borrow(jobs[k].out, jobs[k].kept);
-    res[k]->owner = blk;
-    out[k] = new ndt_cloud_s{res[k]};
+    out[k] = outs.publish(k, jobs[k].kept);
     if (n_kept) n_kept[k] = jobs[k].kept;
   }
   return NDT_OK;
@@ -423,7 +328,7 @@ ndt_status ndt_diag_select(ndt_handle h, size_t* launches, size_t* blocks, size_
 
 ndt_status ndt_host_select_point(const ndt_select_spec* spec, const float xyz[3], double key, int* keep) {
   if (!xyz || !keep) return fail(NDT_ERR_INVALID, "bad arguments");
-  if (ndt_status s = spec_checks(spec)) return s;
+  if (ndt_status s = spec_checks(spec, ndt::select_spec_error)) return s;
   *keep = ndt::select_keep(*spec, xyz[0], xyz[1], xyz[2], key) ? 1 : 0;
   return NDT_OK;
 }

@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstddef>
 
+#include "ndt_cloud_ops.hpp"
 #include "ndt_mi355.h"
 
 #if defined(__HIPCC__)
@@ -78,14 +79,8 @@ inline const char* select_spec_error(const ndt_select_spec& s) {
   return nullptr;
 }
 
-// The launch plan of one cloud: blocks of kSelectBlock threads, block b owns points [b * ppb, min(n, (b + 1) * ppb)).
-// ppb is one pass of the block's threads until that would take more than kSelectMaxBlocks blocks, then n / kSelectMaxBlocks
-// rounded up: monotone in n, and the blocks tile [0, n).
-inline void select_plan(size_t n, int* blocks, int* ppb) {
-  const size_t per = (n + kSelectMaxBlocks - 1) / kSelectMaxBlocks;
-  const size_t p = per > static_cast<size_t>(kSelectBlock) ? per : static_cast<size_t>(kSelectBlock);
-  *ppb = static_cast<int>(p);
-  *blocks = static_cast<int>((n + p - 1) / p);
-}
+// The launch plan of one cloud (range_plan): blocks of kSelectBlock threads, block b owns points [b * ppb, min(n, (b + 1) * ppb));
+// ppb is one pass of the block's threads until that would take more than kSelectMaxBlocks blocks.
+inline void select_plan(size_t n, int* blocks, int* ppb) { range_plan(n, kSelectBlock, kSelectMaxBlocks, blocks, ppb); }
 
 }  // namespace ndt

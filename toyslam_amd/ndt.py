@@ -94,6 +94,17 @@ def _dense_flags(is_dense, n):
     return np.ascontiguousarray(f, dtype=np.int32) if n else np.zeros(1, dtype=np.int32)
 
 
+def _handle_array(clouds):
+    """A list of DeviceCloud as the array of ndt_cloud a *_clouds entry takes -> (the list, its length, the array)."""
+    clouds = list(clouds)
+    return clouds, len(clouds), (C.c_void_p * max(len(clouds), 1))(*[c._c for c in clouds])
+
+
+def _out_array(n):
+    """The array of ndt_cloud a *_clouds entry fills."""
+    return (C.c_void_p * max(n, 1))()
+
+
 def pairs_array(n_clouds, pairs=None):
     """(P, 2) int32 C-contiguous (target, source) cloud indices; None = the consecutive pairs (k-1, k) of n_clouds clouds."""
     if pairs is None:
@@ -327,7 +338,7 @@ class NormalDistributionsTransform:
             raise ValueError("clouds must be all DeviceCloud or all host arrays, not a mix")
         n = len(clouds)
         dense = _dense_flags(is_dense, n)
-        out = (C.c_void_p * max(n, 1))()
+        out = _out_array(n)
         ov = np.zeros(max(n, 1), dtype=np.int32)
         if n and all(resident):
             arr = (C.c_void_p * n)(*[c._c for c in clouds])
@@ -341,24 +352,34 @@ class NormalDistributionsTransform:
             offsets[1:] = np.cumsum([len(c) for c in clouds])
             check(self._L.ndt_cloud_voxel_filter_batch(self._h, cat.ctypes.data, offsets.ctypes.data_as(C.POINTER(C.c_size_t)), n,
                                                        cat.shape[1] * 4, _i(dense), float(leaf_size), 0, out, _i(ov)))
-        return [DeviceCloud(self, C.c_void_p(out[k])) for k in range(n)], ov[:n].astype(bool)
+        return self._wrap(out, n), ov[:n].astype(bool)
 
     def voxelGridFilterBatchDevice(self, dev_ptr, offsets, stride_bytes, leaf_size, is_dense=True):
         """The buffer form over records already in HBM: cloud k = records [offsets[k], offsets[k+1]) at dev_ptr."""
         offsets = np.ascontiguousarray(offsets, dtype=np.uintp)
         n = len(offsets) - 1
         dense = _dense_flags(is_dense, n)
-        out = (C.c_void_p * max(n, 1))()
+        out = _out_array(n)
         ov = np.zeros(max(n, 1), dtype=np.int32)
         check(self._L.ndt_cloud_voxel_filter_batch(self._h, C.c_void_p(dev_ptr), offsets.ctypes.data_as(C.POINTER(C.c_size_t)), n,
                                                    int(stride_bytes), _i(dense), float(leaf_size), 1, out, _i(ov)))
-        return [DeviceCloud(self, C.c_void_p(out[k])) for k in range(n)], ov[:n].astype(bool)
+        return self._wrap(out, n), ov[:n].astype(bool)
+
+    def _wrap(self, out, n):
+        """The first n ndt_cloud of an output array as DeviceCloud of this handle."""
+        return [DeviceCloud(self, C.c_void_p(p)) for p in list(out)[:n]]
+
+    def _diag(self, fn, *fields):
+        """The diagnostics entry fn(handle, out...) as a dict in the order of its arguments.  A field is a name (a size_t) or
+        (name, ctypes type, conversion)."""
+        fields = [(f, C.c_size_t, int) if isinstance(f, str) else f for f in fields]
+        vals = [t(0) for _, t, _ in fields]
+        check(fn(self._h, *[C.byref(v) for v in vals]))
+        return {name: conv(v.value) for (name, _, conv), v in zip(fields, vals)}
 
     def filterBatchDiag(self):
         """What the last voxelGridFilterClouds / voxelGridFilterBatchDevice did (ndt_diag_filter_batch)."""
-        p, s, l = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
-        check(self._L.ndt_diag_filter_batch(self._h, C.byref(p), C.byref(s), C.byref(l)))
-        return dict(passes=p.value, single_route=s.value, launches=l.value)
+        return self._diag(self._L.ndt_diag_filter_batch, "passes", "single_route", "launches")
 
     def warmUp(self, expected_scan_points=0):
         check(self._L.ndt_warm_up(self._h, int(expected_scan_points)))
@@ -408,7 +429,7 @@ class NormalDistributionsTransform:
         n = len(clouds)
         P = self._poses(poses, n)
         dense = _dense_flags(is_dense, n)
-        arr = (C.c_void_p * max(n, 1))(*[c._c for c in clouds])
+        arr = _handle_array(clouds)[2]
         ov = C.c_int(0)
         check(self._L.ndt_map_update_clouds(self._h, arr, n, _i(dense), _f(P) if P is not None else None, float(leaf_size), C.byref(ov)))
         return self.mapSize(), bool(ov.value)
@@ -452,9 +473,7 @@ class NormalDistributionsTransform:
 
     def mapBatchDiag(self):
         """What the last mapUpdateClouds / mapUpdateBatch / mapUpdateBatchDevice did (ndt_diag_map_batch)."""
-        t, f, b = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
-        check(self._L.ndt_diag_map_batch(self._h, C.byref(t), C.byref(f), C.byref(b)))
-        return dict(transform_launches=t.value, filters=f.value, box_passes=b.value)
+        return self._diag(self._L.ndt_diag_map_batch, "transform_launches", "filters", "box_passes")
 
     # ---- accumulating target: posed scans merged into the voxel grid (ndt_target_accumulate*) ----
     def targetAccumulate(self, scan, pose=None, is_dense=True):
@@ -486,7 +505,7 @@ class NormalDistributionsTransform:
             raise ValueError("clouds must be DeviceCloud objects")
         n = len(clouds)
         P = self._poses(poses, n)
-        arr = (C.c_void_p * max(n, 1))(*[c._c for c in clouds])
+        arr = _handle_array(clouds)[2]
         check(self._L.ndt_target_accumulate_clouds(self._h, arr, n, int(is_dense), _f(P) if P is not None else None))
         return self.targetAccumulated()
 
@@ -501,10 +520,8 @@ class NormalDistributionsTransform:
 
     def targetAccumulateDiag(self):
         """What the last targetAccumulate* call did (ndt_diag_target_accumulate)."""
-        t, n, l = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
-        r, g = C.c_int(0), C.c_int(0)
-        check(self._L.ndt_diag_target_accumulate(self._h, C.byref(t), C.byref(n), C.byref(r), C.byref(g), C.byref(l)))
-        return dict(touched_voxels=t.value, new_voxels=n.value, relinked=bool(r.value), table_grown=bool(g.value), launches=l.value)
+        return self._diag(self._L.ndt_diag_target_accumulate, "touched_voxels", "new_voxels", ("relinked", C.c_int, bool),
+                          ("table_grown", C.c_int, bool), "launches")
 
     def targetAccumulateCrop(self, min_xyz, max_xyz):
         """Crop the accumulated target to the box [min_xyz, max_xyz] (ndt_target_accumulate_crop): a voxel stays exactly when
@@ -516,10 +533,7 @@ class NormalDistributionsTransform:
 
     def targetCropDiag(self):
         """What the last targetAccumulateCrop did (ndt_diag_target_crop)."""
-        k, r, p, l = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
-        w = C.c_int(0)
-        check(self._L.ndt_diag_target_crop(self._h, C.byref(k), C.byref(r), C.byref(p), C.byref(w), C.byref(l)))
-        return dict(kept_voxels=k.value, removed_voxels=r.value, kept_points=p.value, relinked=bool(w.value), launches=l.value)
+        return self._diag(self._L.ndt_diag_target_crop, "kept_voxels", "removed_voxels", "kept_points", ("relinked", C.c_int, bool), "launches")
 
     # ---- clearing by rays: drop the voxels a scan sees through (ndt_target_accumulate_clear_rays*) ----
     def _ray_args(self, clouds, poses, origins, min_rays, margin, min_range, max_range):
@@ -538,7 +552,7 @@ class NormalDistributionsTransform:
             if len(O) != 3 * n:
                 raise ValueError("one origin (3 floats) per cloud")
         spec = ray_spec(self.getResolution(), min_rays, margin, min_range, max_range)
-        arr = (C.c_void_p * max(n, 1))(*[c._c for c in clouds])
+        arr = _handle_array(clouds)[2]
         return arr, n, (_f(P) if P is not None else None), (_f(O) if O is not None else None), spec, (P, O)
 
     def targetClearRays(self, clouds, poses=None, origins=None, min_rays=2, margin=None, min_range=0.0, max_range=None):
@@ -564,12 +578,8 @@ class NormalDistributionsTransform:
 
     def targetClearRaysDiag(self):
         """What the last targetClearRays / targetRayCounts that reached the device did (ndt_diag_target_clear_rays)."""
-        z = [C.c_size_t(0) for _ in range(7)]
-        vis, rel = C.c_uint64(0), C.c_int(0)
-        check(self._L.ndt_diag_target_clear_rays(self._h, C.byref(z[0]), C.byref(z[1]), C.byref(vis), C.byref(z[2]), C.byref(z[3]), C.byref(z[4]),
-                                                 C.byref(z[5]), C.byref(rel), C.byref(z[6])))
-        return dict(rays_cast=z[0].value, rays_skipped=z[1].value, cells_visited=vis.value, touched_voxels=z[2].value, removed_voxels=z[3].value,
-                    kept_voxels=z[4].value, kept_points=z[5].value, relinked=bool(rel.value), launches=z[6].value)
+        return self._diag(self._L.ndt_diag_target_clear_rays, "rays_cast", "rays_skipped", ("cells_visited", C.c_uint64, int), "touched_voxels",
+                          "removed_voxels", "kept_voxels", "kept_points", ("relinked", C.c_int, bool), "launches")
 
     @staticmethod
     def _box(min_xyz, max_xyz):
@@ -613,9 +623,7 @@ class NormalDistributionsTransform:
 
     def targetExportDiag(self):
         """What the last targetAccumulateExport / Save did (ndt_diag_target_export)."""
-        v, p, l = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
-        check(self._L.ndt_diag_target_export(self._h, C.byref(v), C.byref(p), C.byref(l)))
-        return dict(voxels=v.value, points=p.value, launches=l.value)
+        return self._diag(self._L.ndt_diag_target_export, "voxels", "points", "launches")
 
     # ---- batch (map-build) ---------------------------------------------------------
     def alignBatch(self, clouds=None, guesses=None, device_ptr=None, offsets=None, stride_bytes=16):
@@ -698,9 +706,7 @@ class NormalDistributionsTransform:
 
     def fitnessLaunches(self):
         """(launches, blocks of the largest) of the last pairsFitness / batchFitness (ndt_diag_fitness_launches)."""
-        a, b = C.c_size_t(0), C.c_size_t(0)
-        check(self._L.ndt_diag_fitness_launches(self._h, C.byref(a), C.byref(b)))
-        return a.value, b.value
+        return tuple(self._diag(self._L.ndt_diag_fitness_launches, "launches", "blocks").values())
 
     def batchFitness(self, clouds=None, transforms=None, max_range=np.finfo(np.float64).max, device_ptr=None, offsets=None,
                      stride_bytes=16):
@@ -776,10 +782,7 @@ class NormalDistributionsTransform:
 
     def centroidFitnessDiag(self):
         """What the last centroidFitnessScore / batchCentroidFitness did (ndt_diag_centroid_fitness)."""
-        a, p, b = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
-        e = C.c_float(0)
-        check(self._L.ndt_diag_centroid_fitness(self._h, C.byref(a), C.byref(p), C.byref(e), C.byref(b)))
-        return dict(launches=a.value, excursion_passes=p.value, excursion=e.value, max_blocks=b.value)
+        return self._diag(self._L.ndt_diag_centroid_fitness, "launches", "excursion_passes", ("excursion", C.c_float, float), "max_blocks")
 
     # ---- one source, many poses (ndt_score_poses / ndt_align_guesses / ndt_align_multistart) -------
     @staticmethod
@@ -803,9 +806,7 @@ class NormalDistributionsTransform:
 
     def scorePosesLaunches(self):
         """(launches, blocks of all of them) of the last scorePoses (ndt_diag_score_poses)."""
-        a, b = C.c_size_t(0), C.c_size_t(0)
-        check(self._L.ndt_diag_score_poses(self._h, C.byref(a), C.byref(b)))
-        return a.value, b.value
+        return tuple(self._diag(self._L.ndt_diag_score_poses, "launches", "blocks").values())
 
     # ---- nearest-voxel transformation likelihood (ndt_calculate_nvtl / ndt_get_nvtl / ndt_nvtl_poses / ndt_source_point_nvtl)
     def calculateNVTL(self, cloud):
@@ -852,9 +853,7 @@ class NormalDistributionsTransform:
 
     def nvtlLaunches(self):
         """(launches, blocks of all of them) of the last NVTL call that reached the device (ndt_diag_nvtl)."""
-        a, b = C.c_size_t(0), C.c_size_t(0)
-        check(self._L.ndt_diag_nvtl(self._h, C.byref(a), C.byref(b)))
-        return a.value, b.value
+        return tuple(self._diag(self._L.ndt_diag_nvtl, "launches", "blocks").values())
 
     # ---- selection of the points of resident clouds (ndt_cloud_select / _clouds / ndt_source_select_by_nvtl) ---------------
     @staticmethod
@@ -912,13 +911,10 @@ class NormalDistributionsTransform:
         test): a list of DeviceCloud, entry k what selectCloud gives for clouds[k] alone, the same bits."""
         if spec is None:
             spec = self.selectSpec(finite, box, box_negate, range, centre, range_negate)
-        clouds = list(clouds)
-        n = len(clouds)
-        arr = (C.c_void_p * max(n, 1))(*[c._c for c in clouds])
-        out = (C.c_void_p * max(n, 1))()
-        nk = (C.c_size_t * max(n, 1))()
+        clouds, n, arr = _handle_array(clouds)
+        out, nk = _out_array(n), (C.c_size_t * max(n, 1))()
         check(self._L.ndt_cloud_select_clouds(self._h, arr, n, C.byref(spec), out, nk))
-        return [DeviceCloud(self, C.c_void_p(p)) for p in list(out)[:n]]  # (`range` is a keyword of this method)
+        return self._wrap(out, n)
 
     def sourceSelectByNVTL(self, min_likelihood, transform=None, keep_unfound=True):
         """The input source's own points (unmoved, caller's order) that the target explains under `transform` (None: the last
@@ -933,9 +929,7 @@ class NormalDistributionsTransform:
 
     def selectDiag(self):
         """What the last selection that reached the device did (ndt_diag_select)."""
-        a, b, c = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
-        check(self._L.ndt_diag_select(self._h, C.byref(a), C.byref(b), C.byref(c)))
-        return dict(launches=a.value, blocks=b.value, clouds=c.value)
+        return self._diag(self._L.ndt_diag_select, "launches", "blocks", "clouds")
 
     @staticmethod
     def selectPlan(n):
@@ -976,8 +970,7 @@ class NormalDistributionsTransform:
         """deskewCloud of every DeviceCloud of the list under its own motion, one launch in all (ndt_cloud_deskew_clouds).
         times: a list of per-cloud float64 arrays, or one array packed in cloud order.  -> (list of DeviceCloud, list of
         n_untimed), entry k what deskewCloud gives for clouds[k] alone, the same bits."""
-        clouds, motions = list(clouds), list(motions)
-        n = len(clouds)
+        (clouds, n, arr), motions = _handle_array(clouds), list(motions)
         if len(motions) != n:
             raise ValueError("one motion per cloud")
         if isinstance(times, (list, tuple)):
@@ -985,18 +978,14 @@ class NormalDistributionsTransform:
         keep = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
         if keep.shape[0] != sum(len(c) for c in clouds):
             raise ValueError("one time per point")
-        arr = (C.c_void_p * max(n, 1))(*[c._c for c in clouds])
         ms = (_lib.DeskewMotion * max(n, 1))(*motions)
-        out = (C.c_void_p * max(n, 1))()
-        nu = (C.c_size_t * max(n, 1))()
+        out, nu = _out_array(n), (C.c_size_t * max(n, 1))()
         check(self._L.ndt_cloud_deskew_clouds(self._h, arr, n, ms, C.c_void_p(keep.ctypes.data) if keep.shape[0] else None, 0, out, nu))
-        return [DeviceCloud(self, C.c_void_p(p)) for p in list(out)[:n]], list(nu)[:n]
+        return self._wrap(out, n), list(nu)[:n]
 
     def deskewDiag(self):
         """What the last motion compensation that reached the device did (ndt_diag_deskew)."""
-        a, b, c = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
-        check(self._L.ndt_diag_deskew(self._h, C.byref(a), C.byref(b), C.byref(c)))
-        return dict(launches=a.value, blocks=b.value, clouds=c.value)
+        return self._diag(self._L.ndt_diag_deskew, "launches", "blocks", "clouds")
 
     # ---- outlier removal of resident clouds (ndt_cloud_neighbor_values / ndt_cloud_remove_outliers / _clouds) ------------
     @staticmethod
@@ -1055,20 +1044,14 @@ class NormalDistributionsTransform:
         gives for clouds[k] alone, the same bits."""
         if spec is None:
             spec = self.outlierSpec(radius, min_neighbors, mean_k, stddev_mul, negate)
-        clouds = list(clouds)
-        n = len(clouds)
-        arr = (C.c_void_p * max(n, 1))(*[c._c for c in clouds])
-        out = (C.c_void_p * max(n, 1))()
-        nk = (C.c_size_t * max(n, 1))()
-        st = (_lib.OutlierStats * max(n, 1))()
+        clouds, n, arr = _handle_array(clouds)
+        out, nk, st = _out_array(n), (C.c_size_t * max(n, 1))(), (_lib.OutlierStats * max(n, 1))()
         check(self._L.ndt_cloud_remove_outliers_clouds(self._h, arr, n, C.byref(spec), out, nk, st))
-        return [DeviceCloud(self, C.c_void_p(p)) for p in list(out)[:n]], [self._outlier_stats(st[k]) for k in range(n)]
+        return self._wrap(out, n), [self._outlier_stats(st[k]) for k in range(n)]
 
     def outlierDiag(self):
         """What the last outlier call that reached the device did (ndt_diag_outliers)."""
-        a, b, c, d = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
-        check(self._L.ndt_diag_outliers(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
-        return dict(index_builds=a.value, value_launches=b.value, value_blocks=c.value, scanned_queries=d.value)
+        return self._diag(self._L.ndt_diag_outliers, "index_builds", "value_launches", "value_blocks", "scanned_queries")
 
     @staticmethod
     def outlierPlan(n):
@@ -1124,14 +1107,11 @@ class NormalDistributionsTransform:
         """segmentPlane of every DeviceCloud of the list under one spec, every cloud its own plane, in one model launch, one
         count launch and the selection's launches in all (ndt_cloud_segment_plane_clouds).  -> (list of result dicts, list of
         inlier clouds or None, list of other clouds or None), entry k what segmentPlane gives for clouds[k] alone."""
-        clouds = list(clouds)
-        n = len(clouds)
-        arr = (C.c_void_p * max(n, 1))(*[c._c for c in clouds])
+        clouds, n, arr = _handle_array(clouds)
         res = (_lib.PlaneResult * max(n, 1))()
-        oi, oo = (C.c_void_p * max(n, 1))(), (C.c_void_p * max(n, 1))()
+        oi, oo = _out_array(n), _out_array(n)
         check(self._L.ndt_cloud_segment_plane_clouds(self._h, arr, n, C.byref(spec), res, oi if inliers else None, oo if others else None))
-        wrap = lambda out: [DeviceCloud(self, C.c_void_p(p)) for p in list(out)[:n]]
-        return [self._plane_result(res[k]) for k in range(n)], wrap(oi) if inliers else None, wrap(oo) if others else None
+        return [self._plane_result(res[k]) for k in range(n)], self._wrap(oi, n) if inliers else None, self._wrap(oo, n) if others else None
 
     def planeDistances(self, dc, coeff, device=False):
         """The signed distance of every point of the resident cloud `dc` from the plane coeff = (nx, ny, nz, d) -- the height
@@ -1148,9 +1128,7 @@ class NormalDistributionsTransform:
 
     def planeDiag(self):
         """What the last plane call that reached the device did (ndt_diag_plane)."""
-        a, b, c, d = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
-        check(self._L.ndt_diag_plane(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
-        return dict(launches=a.value, select_launches=b.value, count_blocks=c.value, clouds=d.value)
+        return self._diag(self._L.ndt_diag_plane, "launches", "select_launches", "count_blocks", "clouds")
 
     # ---- pose covariance (ndt_pose_covariance / ndt_pairs_pose_covariances) ----------------------------------------------
     def poseCovariance(self, transform=None, method="sandwich", scale=1.0, info=False):
@@ -1187,9 +1165,7 @@ class NormalDistributionsTransform:
 
     def poseCovarianceLaunches(self):
         """(gradient-kernel launches, blocks that worked) of the last pose covariance call that reached the device."""
-        a, b = C.c_size_t(0), C.c_size_t(0)
-        check(self._L.ndt_diag_pose_covariance(self._h, C.byref(a), C.byref(b)))
-        return a.value, b.value
+        return tuple(self._diag(self._L.ndt_diag_pose_covariance, "launches", "blocks").values())
 
     def alignGuesses(self, guesses):
         """Register the input source from each of the 4x4 guesses in lock-step (ndt_align_guesses).  Returns alignBatch's
