@@ -22,7 +22,7 @@
 // after the other, 2.7 ms overlapped, 3.7 ms overlapped on CU partitions -- the steps are short host-paced sequences of
 // pageable copies and small launches, and two threads driving them get in each other's way; hence not the default.
 //
-//   map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--deskew <field>] [--range <min> <max>] [--outliers-radius <r> <min_neighbors>] [--outliers-stat <mean_k> <stddev_mul>] [--ground <threshold> <hypotheses> <eps_deg> [--ground-remove]] [--reject-unexplained <L>] [--clear-rays <min_rays> <margin>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> [voxel_leaf_size (0.5 | 0.3)] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]
+//   map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--deskew <field>] [--range <min> <max>] [--outliers-radius <r> <min_neighbors>] [--outliers-stat <mean_k> <stddev_mul>] [--ground <threshold> <hypotheses> <eps_deg> [--ground-remove]] [--clusters <tolerance> <min_size> [<max_size>]] [--reject-unexplained <L>] [--clear-rays <min_rays> <margin>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> [voxel_leaf_size (0.5 | 0.3)] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]
 // ("host": the serial loop with every cloud passing through host buffers, as in rounds 1-3; the default keeps them in HBM)
 //
 // --scan-to-map (anywhere on the line; the node's loop with clouds resident in HBM): every scan after the first is registered
@@ -70,6 +70,11 @@
 // <hypotheses> hypotheses with the distance threshold <threshold>, seed 0, only planes whose normal lies within <eps_deg> degrees
 // of (0, 0, 1) in the sensor frame, no refinement) and "ground: <inliers>/<n> normal <a> <b> <c> d <d>" is printed per scan; with
 // --ground-remove the scan goes on without its inliers (and without the rows that are not finite).
+// --clusters <tolerance> <min_size> [<max_size>] (with --scan-to-map): after --ground and before its prefilter, every raw scan
+// goes through ndt_cloud_extract_clusters on the device -- what stands on the ground split into objects, Euclidean clusters of
+// points nearer than <tolerance>, and only the objects of min_size ... max_size points (no upper limit without <max_size>) go
+// on: rain, noise and pedestrians smaller than min_size stay out of the map -- and "clusters: <C> kept <k>/<n>" is printed per
+// scan.
 // --reject-unexplained <L> (with --scan-to-map, not with --localize, which accumulates nothing): after each registration the
 // scan is accumulated as ndt_source_select_by_nvtl(h, NULL, L, 1, ...) -- its points whose nearest-voxel likelihood at the
 // registered pose is at least L, and those no voxel is near (new ground) -- instead of as the whole scan, so that moving objects
@@ -87,6 +92,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <limits>
 #include <dirent.h>
 #include <mutex>
 #include <string>
@@ -192,6 +198,8 @@ struct Node {
   ndt_outlier_spec radius_spec{}, stat_spec{};
   bool ground = false, ground_remove = false;  // --ground: every raw scan's ground plane is found (and with --ground-remove dropped) before its prefilter
   ndt_plane_spec ground_spec{};
+  bool clusters = false;  // --clusters: every raw scan goes on with its clustered points only
+  ndt_cluster_spec cluster_spec{};
   std::string deskew_field;  // --deskew: every raw scan is motion-compensated by this field of its file, first of all
   std::string directory;
   bool reject = false;       // --reject-unexplained: a registered scan is accumulated without the points the target does not explain
@@ -422,6 +430,17 @@ static int run_resident(Node& node, ndt_pcd_sequence_handle seq, float voxel_lea
           r.n = plane.n_finite - plane.n_inliers;
           r.dense = 1;
         }
+      }
+      if (node.clusters) {  // what is left holds finite points only
+        ndt_cloud objects = nullptr;
+        size_t kept = 0;
+        ndt_cluster_summary sum{};
+        CHECK(ndt_cloud_extract_clusters(h, r.view, &node.cluster_spec, 0, &objects, nullptr, &kept, &sum));
+        std::printf("clusters: %zu kept %zu/%zu\n", sum.n_clusters, kept, r.n);
+        ndt_cloud_release(r.view);
+        r.view = objects;
+        r.n = kept;
+        r.dense = 1;
       }
       CHECK(ndt_cloud_voxel_filter_begin(h, r.view, r.dense, voxel_leaf_size));
       node.t_filter += since(t0);
@@ -783,12 +802,14 @@ int main(int argc, char** argv) {
   ndt_outlier_spec radius_spec{}, stat_spec{};
   bool ground = false, ground_remove = false, bad_ground = false;
   ndt_plane_spec ground_spec{};
+  bool clusters = false, bad_clusters = false;
+  ndt_cluster_spec cluster_spec{};
   float window = 0, range_min = 0, range_max = 0;
   double reject_below = 0;
   const char *save_target = nullptr, *load_target = nullptr, *deskew_field = nullptr;
   bool bad_deskew = false;
   static const char kUsage[] =
-      "usage: map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--gicp [--gicp-gate <m>]] [--deskew <field>] [--range <min> <max>] [--outliers-radius <r> <min_neighbors>] [--outliers-stat <mean_k> <stddev_mul>] [--ground <threshold> <hypotheses> <eps_deg> [--ground-remove]] [--reject-unexplained <L>] [--clear-rays <min_rays> <margin>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> "
+      "usage: map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--gicp [--gicp-gate <m>]] [--deskew <field>] [--range <min> <max>] [--outliers-radius <r> <min_neighbors>] [--outliers-stat <mean_k> <stddev_mul>] [--ground <threshold> <hypotheses> <eps_deg> [--ground-remove]] [--clusters <tolerance> <min_size> [<max_size>]] [--reject-unexplained <L>] [--clear-rays <min_rays> <margin>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> "
       "[voxel_leaf_size] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]\n";
   {  // the switches are taken out of the line before the positional arguments are read
     int kept = 1;
@@ -859,6 +880,18 @@ int main(int argc, char** argv) {
         }
       } else if (std::strcmp(argv[i], "--ground-remove") == 0) {
         ground_remove = true;
+      } else if (std::strcmp(argv[i], "--clusters") == 0) {
+        clusters = true;
+        bad_clusters = i + 2 >= argc;
+        if (!bad_clusters) {
+          cluster_spec.tolerance = static_cast<float>(std::atof(argv[++i]));
+          cluster_spec.min_size = std::atoi(argv[++i]);
+          cluster_spec.max_size = std::numeric_limits<int>::max();
+          // (the optional <max_size> is a number; the directory that follows the switches is not)
+          if (i + 1 < argc && argv[i + 1][0] != '\0' && std::strspn(argv[i + 1], "0123456789") == std::strlen(argv[i + 1]))
+            cluster_spec.max_size = std::atoi(argv[++i]);
+          bad_clusters = ndt_host_cluster_spec_check(&cluster_spec) != NDT_OK;
+        }
       } else if (std::strcmp(argv[i], "--clear-rays") == 0) {
         clear_rays = true;
         bad_clear = i + 2 >= argc;
@@ -916,6 +949,11 @@ int main(int argc, char** argv) {
                          "--scan-to-map and --ground-remove with --ground\n%s", kUsage);
     return 2;
   }
+  if (bad_clusters || (clusters && !scan_to_map)) {
+    std::fprintf(stderr, "--clusters <tolerance> <min_size> [<max_size>] (tolerance > 0, 1 <= min_size <= max_size) goes with --scan-to-map\n%s",
+                 kUsage);
+    return 2;
+  }
   if (bad_gate || (have_gate && !use_gicp) || (use_gicp && (!scan_to_map || nvtl || covariance || reject))) {
     std::fprintf(stderr, "--gicp goes with --scan-to-map and --gicp-gate <m> (m > 0) with --gicp; --nvtl, --covariance and --reject-unexplained "
                          "read the NDT registration's result, so they do not go with --gicp\n%s", kUsage);
@@ -948,6 +986,8 @@ int main(int argc, char** argv) {
   node.ground = ground;
   node.ground_remove = ground_remove;
   node.ground_spec = ground_spec;
+  node.clusters = clusters;
+  node.cluster_spec = cluster_spec;
   if (deskew_field) node.deskew_field = deskew_field;
   node.directory = argv[1];
   node.reject = reject;

@@ -623,6 +623,88 @@ ndt_status ndt_host_plane_fit(const ndt_plane_spec* spec, double count, const do
 ndt_status ndt_host_plane_plan(size_t n_points, int n_hypotheses, int* tile_points, int* hyp_per_block, int* tiles, int* hyp_blocks,
                                int* tile_blocks);
 
+/* ---- Euclidean cluster extraction of resident clouds: what stands on the ground, split into objects -------------------
+ * Modelled on pcl::EuclideanClusterExtraction.  The class is not part of the reference and PCL itself was not at hand: NO bit
+ * parity with PCL is claimed, the definitions below are the contract.
+ * F, d2(i, j) and the "other points" of i are those of the outlier section above: d2 = (dx*dx + dy*dy) + dz*dz in f32, every
+ * operation rounded on its own (no fused multiply-add), and j != i BY INDEX.  d2(i, j) == d2(j, i) bit for bit, so the
+ * relation below is symmetric by construction.
+ *   tol2       = tolerance*tolerance in f32.
+ *   i ~ j      iff both are in F, i != j and d2(i, j) <= tol2 (duplicates of a point are joined: their distance is 0).
+ *   component  a connected component of the graph (F, ~).  Its ROOT is its smallest point index, its SIZE its number of points.
+ *   cluster    a component with min_size <= size <= max_size.  The clusters are numbered 0 ... C-1 by descending size, equal
+ *              sizes by ascending root.
+ *   label_i    the number of i's cluster; -1 when i's component is no cluster, and when i is not in F.
+ *   root_i     the root of i's component; -1 when i is not in F.
+ * An invalid spec (NDT_ERR_INVALID before any device work): a tolerance that is not finite or <= 0, or min_size, max_size for
+ * which 1 <= min_size <= max_size does not hold. */
+typedef struct {
+  float tolerance;
+  int min_size, max_size;
+} ndt_cluster_spec;
+/* One row of the cluster table: `first` is the offset of the cluster's run in `indices` (row c covers indices[first .. first +
+ * size)); the box is the f32 min / max of the cluster's stored coordinates, exact; the centroid is the f64 sum of the widened
+ * coordinates over the cluster's points divided by the size -- thread t of a block of 256 adds the run's entries t, t + 256,
+ * ... in that order and the threads are added in a fixed tree, a shape that depends on the size alone: the same bits on every
+ * run and whatever else is in the call.  No floating-point atomics anywhere. */
+typedef struct {
+  int32_t root, size;
+  uint32_t first;
+  float box_min[3], box_max[3];
+  double centroid[3];
+} ndt_cluster_info;
+typedef struct {
+  size_t n_finite, n_components, n_clusters; /* |F|, the components, C */
+  size_t n_clustered, largest;               /* the points with label >= 0; the largest component, a cluster or not */
+} ndt_cluster_summary;
+/* - ndt_cloud_cluster: label_i into labels and (roots != NULL) root_i into roots, n_in int32 each, both in host memory or
+ *   (labels_on_device != 0) both in device memory.  The first min(C, cluster_capacity) rows of the table into clusters (host;
+ *   may be NULL with cluster_capacity == 0): the largest clusters, so "the 32 largest" is one call; summary->n_clusters always
+ *   reports C.  indices (host, capacity n_in, may be NULL) receives the n_clustered clustered points grouped by cluster number,
+ *   ascending inside a cluster -- PCL's vector<PointIndices>, flattened.  *summary may be NULL.
+ * - ndt_cloud_extract_clusters: *out is a new cloud of its own holding the points with label >= 0 -- with negate != 0 the points
+ *   of F with label < 0; a point outside F is never kept -- in in's order, all four words as they are, with exact boxes: bit
+ *   for bit what ndt_cloud_upload of the host-selected rows gives, as ndt_cloud_select promises.  The per-point keys (1: in a
+ *   cluster, 0: in none, NaN: not finite) are device-resident keys of that selection (KEY over [1, 1], or KEY | KEY_NEGATE) and
+ *   never visit the host.  Nothing kept: an empty cloud, never NULL.  It needs the sizes alone: no ordering sort, no table.
+ *   kept_idx (host, capacity n_in, may be NULL), *n_kept and *summary (may be NULL) as named.
+ * - ndt_cloud_extract_clusters_clouds: one spec for many clouds; every kernel of the extraction is launched once whatever
+ *   n_clouds, and the selection adds its two launches.  out[k], n_kept[k] and summaries[k] are the same bits as the single call
+ *   for cloud k alone, whatever the other clouds and their order.  n_clouds == 0 is NDT_OK, touches nothing and needs no
+ *   device.  On any error every out[k] is NULL.
+ * - ndt_diag_clusters, of the last of the three calls above that reached the device: point indices built; launches of the
+ *   extraction's own kernels (parents, link, flatten, keys = 4; 3 when no cloud has a finite point, 0 when none has a point;
+ *   ndt_cloud_cluster adds the label pass, with C > 0 the two numbering passes, and the table pass when rows are written: up
+ *   to 8 -- the sorts, the scans and the selection are not counted); the blocks of the link launch; the queries that left the
+ *   shell walk for the scan over the whole cloud; and the compare-and-swaps of the union-find that failed and were retried
+ *   (it varies from run to run; no result depends on it).
+ * None of them changes the handle's target, source, grid, last result, statistics, map, a begun
+ * ndt_cloud_voxel_filter_begin, the pairs state or what ndt_diag_select / ndt_diag_outliers / ndt_diag_plane report.
+ * NDT_ERR_INVALID before any device work, outputs untouched apart from *out = NULL (every out[k] = NULL): a NULL handle, in,
+ * spec, labels or out, NULL clusters with cluster_capacity > 0, an invalid spec, a NULL entry of in, more than 65 535 clouds,
+ * a cloud of another device, more than INT_MAX points.  After those checks NDT_ERR_NO_DEVICE without a gfx950 device.
+ * Development switch NDT_CLUSTER_MAX_BLOCKS (read at every call): caps the blocks a cloud gets in the link kernel (no result
+ * depends on it). */
+ndt_status ndt_cloud_cluster(ndt_handle h, ndt_cloud in, const ndt_cluster_spec* spec,
+                             int32_t* labels /* n_in; host, or device with labels_on_device */, int labels_on_device,
+                             int32_t* roots /* n_in, placed like labels, or NULL */, ndt_cluster_info* clusters /* cluster_capacity */,
+                             size_t cluster_capacity, int32_t* indices /* host, capacity n_in, or NULL */,
+                             ndt_cluster_summary* summary /* or NULL */);
+ndt_status ndt_cloud_extract_clusters(ndt_handle h, ndt_cloud in, const ndt_cluster_spec* spec, int negate, ndt_cloud* out,
+                                      int32_t* kept_idx /* host, capacity n_in, or NULL */, size_t* n_kept /* or NULL */,
+                                      ndt_cluster_summary* summary /* or NULL */);
+ndt_status ndt_cloud_extract_clusters_clouds(ndt_handle h, const ndt_cloud* in, size_t n_clouds, const ndt_cluster_spec* spec, int negate,
+                                             ndt_cloud* out /* n_clouds */, size_t* n_kept /* n_clouds or NULL */,
+                                             ndt_cluster_summary* summaries /* n_clouds or NULL */);
+ndt_status ndt_diag_clusters(ndt_handle h, size_t* index_builds, size_t* launches, size_t* link_blocks, size_t* scanned_queries,
+                             size_t* cas_retries);
+/* Host only, no device: the validity of a spec (NDT_OK / NDT_ERR_INVALID), and the link kernel's plan for a cloud of n_points
+ * -- blocks of one wave, eight queries (teams of eight lanes) per pass; one pass per block up to 4096 blocks
+ * (NDT_CLUSTER_MAX_BLOCKS: fewer), beyond which the blocks stride over the passes.  *queries_per_block: the most queries one
+ * block works on. */
+ndt_status ndt_host_cluster_spec_check(const ndt_cluster_spec* spec);
+ndt_status ndt_host_cluster_plan(size_t n_points, int* blocks, int* queries_per_block);
+
 /* ---- accumulating target: posed scans merged into the voxel grid (scan-to-MAP registration) --------------------------
  * Every other target of this library is built from ONE cloud; a mapping node that wants to register a scan against the map
  * would have to keep every posed point and rebuild the grid from the growing concatenation before each scan.  Here the

@@ -72,6 +72,23 @@ class PlaneResult(C.Structure):
                 ("n_inliers", C.c_size_t), ("n_finite", C.c_size_t), ("n_degenerate", C.c_size_t), ("n_rejected", C.c_size_t)]
 
 
+class ClusterSpec(C.Structure):
+    """ndt_cluster_spec (include/ndt_mi355.h)"""
+    _fields_ = [("tolerance", C.c_float), ("min_size", C.c_int), ("max_size", C.c_int)]
+
+
+class ClusterInfo(C.Structure):
+    """ndt_cluster_info (include/ndt_mi355.h)"""
+    _fields_ = [("root", C.c_int32), ("size", C.c_int32), ("first", C.c_uint32), ("box_min", C.c_float * 3), ("box_max", C.c_float * 3),
+                ("centroid", C.c_double * 3)]
+
+
+class ClusterSummary(C.Structure):
+    """ndt_cluster_summary (include/ndt_mi355.h)"""
+    _fields_ = [("n_finite", C.c_size_t), ("n_components", C.c_size_t), ("n_clusters", C.c_size_t), ("n_clustered", C.c_size_t),
+                ("largest", C.c_size_t)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
 EVAL_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_double),
                       C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double))
@@ -252,6 +269,15 @@ SIGNATURES = {
     "ndt_host_plane_distance": (C.c_int, [dp, fp, dp]),
     "ndt_host_plane_fit": (C.c_int, [C.POINTER(PlaneSpec), C.c_double, dp, dp, dp, dp, dp, ip]),
     "ndt_host_plane_plan": (C.c_int, [C.c_size_t, C.c_int, ip, ip, ip, ip, ip]),
+    "ndt_cloud_cluster": (C.c_int, [vp, vp, C.POINTER(ClusterSpec), vp, C.c_int, vp, C.POINTER(ClusterInfo), C.c_size_t, C.POINTER(C.c_int32),
+                                    C.POINTER(ClusterSummary)]),
+    "ndt_cloud_extract_clusters": (C.c_int, [vp, vp, C.POINTER(ClusterSpec), C.c_int, C.POINTER(vp), C.POINTER(C.c_int32), szp,
+                                             C.POINTER(ClusterSummary)]),
+    "ndt_cloud_extract_clusters_clouds": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, C.POINTER(ClusterSpec), C.c_int, C.POINTER(vp), szp,
+                                                    C.POINTER(ClusterSummary)]),
+    "ndt_diag_clusters": (C.c_int, [vp, szp, szp, szp, szp, szp]),
+    "ndt_host_cluster_spec_check": (C.c_int, [C.POINTER(ClusterSpec)]),
+    "ndt_host_cluster_plan": (C.c_int, [C.c_size_t, ip, ip]),
     "ndt_pose_covariance": (C.c_int, [vp, fp, C.c_int, C.c_double, dp, vp]),
     "ndt_pairs_pose_covariances": (C.c_int, [vp, fp, C.c_int, C.c_double, dp, vp]),
     "ndt_host_pose_covariance": (C.c_int, [dp, dp, dp, C.c_size_t, C.c_int, C.c_double, dp, dp, dp, ip]),

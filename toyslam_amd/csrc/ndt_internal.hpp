@@ -527,6 +527,8 @@ struct ndt_context {
   size_t ol_index_builds = 0, ol_value_launches = 0, ol_value_blocks = 0, ol_scanned = 0;
   // the plane of a cloud (ndt_plane.hip): what the last call that reached the device did (ndt_diag_plane)
   size_t pl_launches = 0, pl_select_launches = 0, pl_count_blocks = 0, pl_clouds = 0;
+  // the cluster extraction (ndt_clusters.hip): what the last call that reached the device did (ndt_diag_clusters)
+  size_t cl_index_builds = 0, cl_launches = 0, cl_link_blocks = 0, cl_scanned = 0, cl_cas_retries = 0;
   // the motion compensation (ndt_deskew.hip): the page-locked block of a call -- its segment table on the way up, its per-block
   // rows (boxes, untimed count) on the way back -- and what the last call that reached the device did (ndt_diag_deskew)
   void* dsk_pinned = nullptr;

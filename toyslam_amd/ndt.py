@@ -1130,6 +1130,105 @@ class NormalDistributionsTransform:
         """What the last plane call that reached the device did (ndt_diag_plane)."""
         return self._diag(self._L.ndt_diag_plane, "launches", "select_launches", "count_blocks", "clouds")
 
+    # ---- Euclidean cluster extraction of resident clouds (ndt_cloud_cluster / ndt_cloud_extract_clusters / _clouds) ----------
+    CLUSTER_DTYPE = np.dtype([("root", np.int32), ("size", np.int32), ("first", np.uint32), ("box_min", np.float32, 3),
+                              ("box_max", np.float32, 3), ("centroid", np.float64, 3)], align=True)
+
+    @staticmethod
+    def clusterSpec(tolerance, min_size=1, max_size=None):
+        """The ndt_cluster_spec of the keyword form: points nearer than `tolerance` belong together; a component of
+        min_size ... max_size points (max_size None: no upper limit) is a cluster."""
+        s = _lib.ClusterSpec()
+        s.tolerance, s.min_size, s.max_size = float(np.float32(tolerance)), int(min_size), int(2 ** 31 - 1 if max_size is None else max_size)
+        return s
+
+    @staticmethod
+    def _cluster_summary(st):
+        return dict(n_finite=st.n_finite, n_components=st.n_components, n_clusters=st.n_clusters, n_clustered=st.n_clustered,
+                    largest=st.largest)
+
+    def clusterCloud(self, dc, tolerance=None, min_size=1, max_size=None, capacity=None, indices=True, roots=False, device=False,
+                     spec=None):
+        """The Euclidean clusters of the resident cloud `dc` (ndt_cloud_cluster; defined in include/ndt_mi355.h): the connected
+        components of "nearer than tolerance" over the finite points whose size lies in min_size ... max_size, numbered by
+        descending size (equal sizes: by their smallest point index).
+        -> (labels (n,) int32: the cluster number, -1 in no cluster or not finite; table: a structured array (CLUSTER_DTYPE:
+        root, size, first, box_min, box_max, centroid) of the min(C, capacity) largest clusters -- capacity None: all of them;
+        indices (n_clustered,) int32: the clustered points grouped by cluster, ascending inside one, row c of the table
+        covering indices[first : first + size], or None with indices=False; summary dict).  roots=True adds the (n,) int32
+        roots -- the smallest index of every point's component, -1 for a point that is not finite -- as a fifth entry.
+        device: the address (an int) of n int32 on the handle's device (with roots=True of 2 n: labels, then roots), which
+        then receives the labels instead; the first entry is that address.
+        One cluster's cloud is selectCloud(dc, keys=labels, key_range=(c, c)).  spec: a ready _lib.ClusterSpec."""
+        if spec is None:
+            spec = self.clusterSpec(tolerance, min_size, max_size)
+        n = len(dc)
+        st = _lib.ClusterSummary()
+        on_device = device is not False and device is not None
+        idx = np.zeros(max(n, 1), dtype=np.int32) if indices else None
+        ip32 = C.POINTER(C.c_int32)
+        if on_device:
+            lp, rp = C.c_void_p(int(device)), C.c_void_p(int(device) + 4 * n) if roots else None
+        else:
+            lab = np.full(max(n, 1), -1, dtype=np.int32)
+            rts = np.full(max(n, 1), -1, dtype=np.int32) if roots else None
+            lp, rp = C.c_void_p(lab.ctypes.data), C.c_void_p(rts.ctypes.data) if roots else None
+
+        if capacity is None:  # as many rows as there are clusters: at most one per min_size points
+            capacity = n // max(spec.min_size, 1)
+        capacity = int(capacity)
+        rows = np.zeros(max(capacity, 1) * self.CLUSTER_DTYPE.itemsize, dtype=np.uint8)  # (bytes: a copy keeps a row's padding too)
+        check(self._L.ndt_cloud_cluster(self._h, dc._c, C.byref(spec), lp, int(on_device), rp,
+                                        rows.ctypes.data_as(C.POINTER(_lib.ClusterInfo)) if capacity else None, capacity,
+                                        idx.ctypes.data_as(ip32) if indices else None, C.byref(st)))
+        table = rows[:min(capacity, st.n_clusters) * self.CLUSTER_DTYPE.itemsize].copy().view(self.CLUSTER_DTYPE)
+        out = [int(device) if on_device else lab[:n].copy(), table, idx[:st.n_clustered].copy() if indices else None, self._cluster_summary(st)]
+        if roots:
+            out.append(int(device) + 4 * n if on_device else rts[:n].copy())
+        return tuple(out)
+
+    def extractClusters(self, dc, tolerance=None, min_size=1, max_size=None, negate=False, indices=False, spec=None):
+        """The points of the resident cloud `dc` that belong to a cluster (clusterCloud's label >= 0; negate: the finite points
+        that belong to none), in dc's order, as a new DeviceCloud with exact boxes (ndt_cloud_extract_clusters); the per-point
+        keys stay on the device, and no cluster is numbered.
+        -> (DeviceCloud, summary dict); indices=True: (DeviceCloud, summary, (n_kept,) int32 indices of the kept points)."""
+        if spec is None:
+            spec = self.clusterSpec(tolerance, min_size, max_size)
+        n = len(dc)
+        idx = np.zeros(max(n, 1), dtype=np.int32) if indices else None
+        c, nk, st = C.c_void_p(None), C.c_size_t(0), _lib.ClusterSummary()
+        check(self._L.ndt_cloud_extract_clusters(self._h, dc._c, C.byref(spec), int(bool(negate)), C.byref(c),
+                                                 idx.ctypes.data_as(C.POINTER(C.c_int32)) if indices else None, C.byref(nk), C.byref(st)))
+        out = DeviceCloud(self, c)
+        return (out, self._cluster_summary(st), idx[:nk.value].copy()) if indices else (out, self._cluster_summary(st))
+
+    def extractClustersClouds(self, clouds, tolerance=None, min_size=1, max_size=None, negate=False, spec=None):
+        """extractClusters of every DeviceCloud of the list under one spec: every kernel of the extraction launched once, and
+        the selection's two (ndt_cloud_extract_clusters_clouds).  -> (list of DeviceCloud, list of summary dicts), entry k
+        what extractClusters gives for clouds[k] alone, the same bits."""
+        if spec is None:
+            spec = self.clusterSpec(tolerance, min_size, max_size)
+        clouds, n, arr = _handle_array(clouds)
+        out, nk, st = _out_array(n), (C.c_size_t * max(n, 1))(), (_lib.ClusterSummary * max(n, 1))()
+        check(self._L.ndt_cloud_extract_clusters_clouds(self._h, arr, n, C.byref(spec), int(bool(negate)), out, nk, st))
+        return self._wrap(out, n), [self._cluster_summary(st[k]) for k in range(n)]
+
+    def diagClusters(self):
+        """What the last cluster call that reached the device did (ndt_diag_clusters)."""
+        return self._diag(self._L.ndt_diag_clusters, "index_builds", "launches", "link_blocks", "scanned_queries", "cas_retries")
+
+    @staticmethod
+    def clusterPlan(n):
+        """(blocks, queries_per_block) of the link kernel over a cloud of n points (ndt_host_cluster_plan; host only)."""
+        b, q = C.c_int(0), C.c_int(0)
+        check(_lib.lib().ndt_host_cluster_plan(int(n), C.byref(b), C.byref(q)))
+        return b.value, q.value
+
+    @staticmethod
+    def clusterSpecCheck(spec):
+        """Is the _lib.ClusterSpec valid?  (ndt_host_cluster_spec_check; host only.)"""
+        return _lib.lib().ndt_host_cluster_spec_check(C.byref(spec)) == _lib.NDT_OK
+
     # ---- pose covariance (ndt_pose_covariance / ndt_pairs_pose_covariances) ----------------------------------------------
     def poseCovariance(self, transform=None, method="sandwich", scale=1.0, info=False):
         """6x6 covariance of the pose x y z roll pitch yaw of the input source at `transform` (None: the last align's final
