@@ -22,7 +22,7 @@
 // after the other, 2.7 ms overlapped, 3.7 ms overlapped on CU partitions -- the steps are short host-paced sequences of
 // pageable copies and small launches, and two threads driving them get in each other's way; hence not the default.
 //
-//   map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--deskew <field>] [--range <min> <max>] [--outliers-radius <r> <min_neighbors>] [--outliers-stat <mean_k> <stddev_mul>] [--ground <threshold> <hypotheses> <eps_deg> [--ground-remove]] [--clusters <tolerance> <min_size> [<max_size>]] [--reject-unexplained <L>] [--clear-rays <min_rays> <margin>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> [voxel_leaf_size (0.5 | 0.3)] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]
+//   map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--deskew <field>] [--range <min> <max>] [--outliers-radius <r> <min_neighbors>] [--outliers-stat <mean_k> <stddev_mul>] [--ground <threshold> <hypotheses> <eps_deg> [--ground-remove]] [--clusters <tolerance> <min_size> [<max_size>]] [--flat <k> <curvature_max>] [--reject-unexplained <L>] [--clear-rays <min_rays> <margin>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> [voxel_leaf_size (0.5 | 0.3)] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]
 // ("host": the serial loop with every cloud passing through host buffers, as in rounds 1-3; the default keeps them in HBM)
 //
 // --scan-to-map (anywhere on the line; the node's loop with clouds resident in HBM): every scan after the first is registered
@@ -70,6 +70,9 @@
 // <hypotheses> hypotheses with the distance threshold <threshold>, seed 0, only planes whose normal lies within <eps_deg> degrees
 // of (0, 0, 1) in the sensor frame, no refinement) and "ground: <inliers>/<n> normal <a> <b> <c> d <d>" is printed per scan; with
 // --ground-remove the scan goes on without its inliers (and without the rows that are not finite).
+// --flat <k> <curvature_max> (with --scan-to-map): last before its prefilter, every raw scan goes through
+// ndt_cloud_select_by_normals on the device -- normals over the k nearest neighbours, the viewpoint the origin, and only the
+// points of curvature <= curvature_max go on -- and "flat kept: <kept>/<n>" is printed per scan.
 // --clusters <tolerance> <min_size> [<max_size>] (with --scan-to-map): after --ground and before its prefilter, every raw scan
 // goes through ndt_cloud_extract_clusters on the device -- what stands on the ground split into objects, Euclidean clusters of
 // points nearer than <tolerance>, and only the objects of min_size ... max_size points (no upper limit without <max_size>) go
@@ -199,6 +202,9 @@ struct Node {
   bool ground = false, ground_remove = false;  // --ground: every raw scan's ground plane is found (and with --ground-remove dropped) before its prefilter
   ndt_plane_spec ground_spec{};
   bool clusters = false;  // --clusters: every raw scan goes on with its clustered points only
+  bool flat = false;      // --flat: every raw scan goes on with its points of low curvature only
+  ndt_normal_spec flat_spec{};
+  ndt_normal_filter flat_filter{};
   ndt_cluster_spec cluster_spec{};
   std::string deskew_field;  // --deskew: every raw scan is motion-compensated by this field of its file, first of all
   std::string directory;
@@ -439,6 +445,16 @@ static int run_resident(Node& node, ndt_pcd_sequence_handle seq, float voxel_lea
         std::printf("clusters: %zu kept %zu/%zu\n", sum.n_clusters, kept, r.n);
         ndt_cloud_release(r.view);
         r.view = objects;
+        r.n = kept;
+        r.dense = 1;
+      }
+      if (node.flat) {  // what is left holds finite points only
+        ndt_cloud smooth = nullptr;
+        size_t kept = 0;
+        CHECK(ndt_cloud_select_by_normals(h, r.view, &node.flat_spec, &node.flat_filter, &smooth, nullptr, &kept, nullptr));
+        std::printf("flat kept: %zu/%zu\n", kept, r.n);
+        ndt_cloud_release(r.view);
+        r.view = smooth;
         r.n = kept;
         r.dense = 1;
       }
@@ -804,12 +820,15 @@ int main(int argc, char** argv) {
   ndt_plane_spec ground_spec{};
   bool clusters = false, bad_clusters = false;
   ndt_cluster_spec cluster_spec{};
+  bool flat = false, bad_flat = false;
+  ndt_normal_spec flat_spec{};
+  ndt_normal_filter flat_filter{};
   float window = 0, range_min = 0, range_max = 0;
   double reject_below = 0;
   const char *save_target = nullptr, *load_target = nullptr, *deskew_field = nullptr;
   bool bad_deskew = false;
   static const char kUsage[] =
-      "usage: map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--gicp [--gicp-gate <m>]] [--deskew <field>] [--range <min> <max>] [--outliers-radius <r> <min_neighbors>] [--outliers-stat <mean_k> <stddev_mul>] [--ground <threshold> <hypotheses> <eps_deg> [--ground-remove]] [--clusters <tolerance> <min_size> [<max_size>]] [--reject-unexplained <L>] [--clear-rays <min_rays> <margin>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> "
+      "usage: map_sequence [--scan-to-map [--window <metres>] [--map-fitness] [--nvtl] [--covariance] [--gicp [--gicp-gate <m>]] [--deskew <field>] [--range <min> <max>] [--outliers-radius <r> <min_neighbors>] [--outliers-stat <mean_k> <stddev_mul>] [--ground <threshold> <hypotheses> <eps_deg> [--ground-remove]] [--clusters <tolerance> <min_size> [<max_size>]] [--flat <k> <curvature_max>] [--reject-unexplained <L>] [--clear-rays <min_rays> <margin>] [--save-target <file>] [--load-target <file> [--localize]]] <pcd_directory> "
       "[voxel_leaf_size] [global_map_out.pcd | -] [rosbag | node] [serial | pipeline] [host]\n";
   {  // the switches are taken out of the line before the positional arguments are read
     int kept = 1;
@@ -892,6 +911,18 @@ int main(int argc, char** argv) {
             cluster_spec.max_size = std::atoi(argv[++i]);
           bad_clusters = ndt_host_cluster_spec_check(&cluster_spec) != NDT_OK;
         }
+      } else if (std::strcmp(argv[i], "--flat") == 0) {
+        flat = true;
+        bad_flat = i + 2 >= argc;
+        if (!bad_flat) {
+          flat_spec.method = NDT_NORMAL_KNN;
+          flat_spec.k = std::atoi(argv[++i]);
+          flat_spec.min_neighbors = 3;  // (the viewpoint stays the origin: the sensor of a raw scan)
+          flat_filter.flags = NDT_NORMAL_KEEP_CURVATURE;
+          flat_filter.curvature_lo = 0.f;
+          flat_filter.curvature_hi = static_cast<float>(std::atof(argv[++i]));
+          bad_flat = ndt_host_normal_spec_check(&flat_spec) != NDT_OK || ndt_host_normal_filter_check(&flat_filter) != NDT_OK;
+        }
       } else if (std::strcmp(argv[i], "--clear-rays") == 0) {
         clear_rays = true;
         bad_clear = i + 2 >= argc;
@@ -954,6 +985,10 @@ int main(int argc, char** argv) {
                  kUsage);
     return 2;
   }
+  if (bad_flat || (flat && !scan_to_map)) {
+    std::fprintf(stderr, "--flat <k> <curvature_max> (k 3 ... 256, curvature_max >= 0) goes with --scan-to-map\n%s", kUsage);
+    return 2;
+  }
   if (bad_gate || (have_gate && !use_gicp) || (use_gicp && (!scan_to_map || nvtl || covariance || reject))) {
     std::fprintf(stderr, "--gicp goes with --scan-to-map and --gicp-gate <m> (m > 0) with --gicp; --nvtl, --covariance and --reject-unexplained "
                          "read the NDT registration's result, so they do not go with --gicp\n%s", kUsage);
@@ -988,6 +1023,9 @@ int main(int argc, char** argv) {
   node.ground_spec = ground_spec;
   node.clusters = clusters;
   node.cluster_spec = cluster_spec;
+  node.flat = flat;
+  node.flat_spec = flat_spec;
+  node.flat_filter = flat_filter;
   if (deskew_field) node.deskew_field = deskew_field;
   node.directory = argv[1];
   node.reject = reject;

@@ -705,6 +705,108 @@ ndt_status ndt_diag_clusters(ndt_handle h, size_t* index_builds, size_t* launche
 ndt_status ndt_host_cluster_spec_check(const ndt_cluster_spec* spec);
 ndt_status ndt_host_cluster_plan(size_t n_points, int* blocks, int* queries_per_block);
 
+/* ---- surface normals and curvature of resident clouds: the flat points, the walls, the edges ---------------------------
+ * Modelled on pcl::NormalEstimation (setKSearch / setRadiusSearch, setViewPoint).  The class is not part of the reference and
+ * PCL itself was not at hand: NO bit parity with PCL is claimed, the definitions below are the contract (the step from a
+ * neighbourhood's sums to the record is ONE function for host and device, toyslam_amd/csrc/ndt_normals.hpp).
+ * A cloud has n records (x, y, z as stored, f32; the fourth word is ignored).  F and d2(i, j) are those of the outlier section
+ * above: F the indices whose three coordinates are finite, d2 = (dx*dx + dy*dy) + dz*dz in f32, every operation rounded on its
+ * own (no fused multiply-add).
+ *   N_i        the neighbourhood of i in F; the point itself is always a member, at distance 0 (as with PCL).
+ *              NDT_NORMAL_KNN: the first min(k, |F|) indices of F in ascending (d2(i, j), j) order.
+ *              NDT_NORMAL_RADIUS: the j in F with d2(i, j) <= r2, r2 = radius*radius in f32.   m_i = |N_i|.
+ *   sums       about the query, in f64: e_j = (double)p_j - (double)p_i per coordinate, S1 = sum e_j (3 numbers), S2 = sum
+ *              e_j e_j^T (6 numbers: xx xy xz yy yz zz), every product and addition rounded on its own.  The ORDER of the sums
+ *              is the implementation's, a function of the cloud and the spec alone: KNN adds the neighbours of rank s, s + 8,
+ *              ... (s = 0 ... 7) in that order and the eight partial sums in a fixed tree; RADIUS adds them in the order of a
+ *              point index built from the cloud and the radius, every cell's points in ascending index.  No floating-point
+ *              atomics anywhere.
+ *   record     from (p_i, m, S1, S2):  mu = S1 / m, C = S2 / m - mu mu^T (symmetric); C solved by cyclic Jacobi in f64, the
+ *              eigenvalues ascending l0 <= l1 <= l2, t = l0 + l1 + l2.  The point is VALID iff m >= min_neighbors, every entry
+ *              of C is finite and t > 0.  n = the eigenvector of l0, renormalised in f64; s = n . ((double)viewpoint -
+ *              (double)p_i): s < 0 flips n, s == 0 makes the component of largest magnitude (the first on ties) positive.
+ *              curvature = max(l0, 0) / t.  The record is (float)n.x, (float)n.y, (float)n.z, (float)curvature, each rounded
+ *              once: pcl::Normal's layout, 16 bytes per point.  An invalid point and a point outside F get four quiet NaNs
+ *              (0x7fc00000); a point outside F has count 0, an invalid point of F its m_i.
+ *   collinear  l1 <= 1e-12 * l2: the neighbourhood is a line.  The record is still valid -- whatever unit vector orthogonal to
+ *              the line the solver returns -- and such points are counted in n_collinear.
+ * An invalid spec (NDT_ERR_INVALID before any device work): an unknown method, k outside 3 ... 256 under KNN, a radius that is
+ * not finite or <= 0 under RADIUS, min_neighbors < 3, a viewpoint that is not finite. */
+enum { NDT_NORMAL_KNN = 1, NDT_NORMAL_RADIUS = 2 };
+typedef struct {
+  int method;
+  int k;               /* KNN: 3 ... 256, the point itself included */
+  float radius;        /* RADIUS: finite, > 0 */
+  int min_neighbors;   /* >= 3; fewer members: no normal */
+  double viewpoint[3]; /* finite; (0,0,0) = the sensor of a raw scan */
+} ndt_normal_spec;
+typedef struct {
+  size_t n_finite, n_valid, n_collinear, max_neighbors; /* |F|, the valid records, the collinear ones among them, max m_i */
+} ndt_normal_stats;
+/* The filter of ndt_cloud_select_by_normals.  A point is kept iff its record is valid and every enabled test passes; NEGATE
+ * inverts the outcome for valid records only; an invalid record is never kept; flags == 0 keeps every point that has a normal.
+ *   CURVATURE  curvature_lo <= c && c <= curvature_hi on the stored f32.
+ *   ANGLE      a = |(nx*ax + ny*ay) + nz*az| in f64 on the stored f32 record widened; cos_lo <= a && a <= cos_hi.
+ * An invalid filter (NDT_ERR_INVALID): unknown bits; of an enabled test NaN bounds or lo > hi; with ANGLE an axis whose length
+ * differs from 1 by more than 1e-12 (the deskew rule), or cosine bounds outside [0, 1]. */
+enum { NDT_NORMAL_KEEP_CURVATURE = 1, NDT_NORMAL_KEEP_ANGLE = 2, NDT_NORMAL_KEEP_NEGATE = 4 };
+typedef struct {
+  unsigned flags;
+  float curvature_lo, curvature_hi;
+  double axis[3], cos_lo, cos_hi;
+} ndt_normal_filter;
+/* - ndt_cloud_estimate_normals: the record of every point into normals (4 * n_in floats) and m_i into counts (n_in int32, may
+ *   be NULL), both in host memory or (on_device != 0) both in device memory.  *stats may be NULL.
+ * - ndt_cloud_estimate_normals_clouds: one spec for many clouds, the outputs packed in cloud order (cloud k's records behind
+ *   those of the clouds before it).  ONE normals launch whatever n_clouds.  Every cloud's records, counts and stats are the same
+ *   bits as the single call for it alone, whatever the other clouds and their order.  n_clouds == 0 is NDT_OK, touches nothing
+ *   and needs no device.
+ * - ndt_cloud_select_by_normals: *out is a new cloud of its own holding the points the filter keeps, in in's order, all four
+ *   words as they are, with exact boxes: bit for bit what ndt_cloud_upload of the host-selected rows gives, as ndt_cloud_select
+ *   promises.  The keep decision is written on the device by the normals launch itself as the key of that selection (1: kept,
+ *   0: not kept, NaN: not finite; KEY over [1, 1]); normals and keys never visit the host.  Nothing kept: an empty cloud, never
+ *   NULL.  kept_idx (host, capacity n_in, may be NULL), *n_kept and *stats (may be NULL) as named.
+ * - ndt_cloud_select_by_normals_clouds: the same for many clouds: one normals launch and the selection's two.  out[k],
+ *   n_kept[k] and stats[k] are the same bits as the single call for cloud k alone.  On any error every out[k] is NULL.
+ * - ndt_diag_normals, of the last of the four calls above that reached the device: point indices built (one per cloud with a
+ *   point), normals launches (1; 0 when no cloud has a point), its blocks, and the queries that left the shell walk for the
+ *   scan over the whole cloud.
+ * The same bits: a cloud's records, counts and stats are bit-identical across the single and the list call, host and device
+ * outputs, and every value of NDT_NORMAL_MAX_BLOCKS.
+ * None of them changes the handle's target, source, grid, last result, statistics, map, a begun
+ * ndt_cloud_voxel_filter_begin, the pairs state or what ndt_diag_select / ndt_diag_outliers / ndt_diag_plane /
+ * ndt_diag_clusters report.
+ * NDT_ERR_INVALID before any device work, outputs untouched apart from *out = NULL (every out[k] = NULL): a NULL handle, in,
+ * spec, filter, normals or out, an invalid spec or filter, a NULL entry of in, more than 65 535 clouds, a cloud of another
+ * device, more than INT_MAX points.  After those checks NDT_ERR_NO_DEVICE without a gfx950 device.
+ * Development switch NDT_NORMAL_MAX_BLOCKS (read at every call; default and maximum 4096): caps the blocks a cloud gets in the
+ * normals kernel (no result depends on it). */
+ndt_status ndt_cloud_estimate_normals(ndt_handle h, ndt_cloud in, const ndt_normal_spec* spec,
+                                      float* normals /* 4 * n_in; host, or device with on_device */,
+                                      int32_t* counts /* n_in, placed like normals, or NULL */, int on_device,
+                                      ndt_normal_stats* stats /* or NULL */);
+ndt_status ndt_cloud_estimate_normals_clouds(ndt_handle h, const ndt_cloud* in, size_t n_clouds, const ndt_normal_spec* spec,
+                                             float* normals /* 4 * total points */, int32_t* counts /* total points or NULL */,
+                                             int on_device, ndt_normal_stats* stats /* n_clouds or NULL */);
+ndt_status ndt_cloud_select_by_normals(ndt_handle h, ndt_cloud in, const ndt_normal_spec* spec, const ndt_normal_filter* filter,
+                                       ndt_cloud* out, int32_t* kept_idx /* host, capacity n_in, or NULL */,
+                                       size_t* n_kept /* or NULL */, ndt_normal_stats* stats /* or NULL */);
+ndt_status ndt_cloud_select_by_normals_clouds(ndt_handle h, const ndt_cloud* in, size_t n_clouds, const ndt_normal_spec* spec,
+                                              const ndt_normal_filter* filter, ndt_cloud* out /* n_clouds */,
+                                              size_t* n_kept /* n_clouds or NULL */, ndt_normal_stats* stats /* n_clouds or NULL */);
+ndt_status ndt_diag_normals(ndt_handle h, size_t* index_builds, size_t* launches, size_t* blocks, size_t* scanned_queries);
+/* Host only, no device: the validity of a spec and of a filter (NDT_OK / NDT_ERR_INVALID); the kernel's plan for a cloud of
+ * n_points -- blocks of one wave, eight queries (teams of eight lanes) per pass; one pass per block up to 4096 blocks
+ * (NDT_NORMAL_MAX_BLOCKS: fewer), beyond which the blocks stride over the passes; *queries_per_block: the most queries one
+ * block works on; the record of a point from its sums, the definition itself (out[4]; *collinear, may be NULL: 1 for a valid
+ * record of a line); and the filter's decision on a record (*keep 0 / 1). */
+ndt_status ndt_host_normal_spec_check(const ndt_normal_spec* spec);
+ndt_status ndt_host_normal_filter_check(const ndt_normal_filter* filter);
+ndt_status ndt_host_normal_plan(size_t n_points, int* blocks, int* queries_per_block);
+ndt_status ndt_host_normal_from_sums(const ndt_normal_spec* spec, const float xyz[3], int m, const double S1[3], const double S2[6],
+                                     float out[4], int* collinear /* or NULL */);
+ndt_status ndt_host_normal_keep(const ndt_normal_filter* filter, const float record[4], int* keep);
+
 /* ---- accumulating target: posed scans merged into the voxel grid (scan-to-MAP registration) --------------------------
  * Every other target of this library is built from ONE cloud; a mapping node that wants to register a scan against the map
  * would have to keep every posed point and rebuild the grid from the growing concatenation before each scan.  Here the

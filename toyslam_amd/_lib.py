@@ -20,6 +20,8 @@ COMM_ID_BYTES = 128
 
 SELECT_FINITE, SELECT_BOX, SELECT_BOX_NEGATE, SELECT_RANGE, SELECT_RANGE_NEGATE, SELECT_KEY, SELECT_KEY_NEGATE = 1, 2, 4, 8, 16, 32, 64
 OUTLIER_RADIUS, OUTLIER_STATISTICAL = 1, 2
+NORMAL_KNN, NORMAL_RADIUS = 1, 2
+NORMAL_KEEP_CURVATURE, NORMAL_KEEP_ANGLE, NORMAL_KEEP_NEGATE = 1, 2, 4
 COV_LAPLACE, COV_SANDWICH = 0, 1
 COV_INDEFINITE = 1
 GICP_VOXEL_COV_PLANE, GICP_VOXEL_COV_RAW = 0, 1
@@ -75,6 +77,22 @@ class PlaneResult(C.Structure):
 class ClusterSpec(C.Structure):
     """ndt_cluster_spec (include/ndt_mi355.h)"""
     _fields_ = [("tolerance", C.c_float), ("min_size", C.c_int), ("max_size", C.c_int)]
+
+
+class NormalSpec(C.Structure):
+    """ndt_normal_spec (include/ndt_mi355.h)"""
+    _fields_ = [("method", C.c_int), ("k", C.c_int), ("radius", C.c_float), ("min_neighbors", C.c_int), ("viewpoint", C.c_double * 3)]
+
+
+class NormalStats(C.Structure):
+    """ndt_normal_stats (include/ndt_mi355.h)"""
+    _fields_ = [("n_finite", C.c_size_t), ("n_valid", C.c_size_t), ("n_collinear", C.c_size_t), ("max_neighbors", C.c_size_t)]
+
+
+class NormalFilter(C.Structure):
+    """ndt_normal_filter (include/ndt_mi355.h)"""
+    _fields_ = [("flags", C.c_uint), ("curvature_lo", C.c_float), ("curvature_hi", C.c_float), ("axis", C.c_double * 3),
+                ("cos_lo", C.c_double), ("cos_hi", C.c_double)]
 
 
 class ClusterInfo(C.Structure):
@@ -278,6 +296,19 @@ SIGNATURES = {
     "ndt_diag_clusters": (C.c_int, [vp, szp, szp, szp, szp, szp]),
     "ndt_host_cluster_spec_check": (C.c_int, [C.POINTER(ClusterSpec)]),
     "ndt_host_cluster_plan": (C.c_int, [C.c_size_t, ip, ip]),
+    "ndt_cloud_estimate_normals": (C.c_int, [vp, vp, C.POINTER(NormalSpec), vp, vp, C.c_int, C.POINTER(NormalStats)]),
+    "ndt_cloud_estimate_normals_clouds": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, C.POINTER(NormalSpec), vp, vp, C.c_int,
+                                                    C.POINTER(NormalStats)]),
+    "ndt_cloud_select_by_normals": (C.c_int, [vp, vp, C.POINTER(NormalSpec), C.POINTER(NormalFilter), C.POINTER(vp), C.POINTER(C.c_int32), szp,
+                                              C.POINTER(NormalStats)]),
+    "ndt_cloud_select_by_normals_clouds": (C.c_int, [vp, C.POINTER(vp), C.c_size_t, C.POINTER(NormalSpec), C.POINTER(NormalFilter),
+                                                     C.POINTER(vp), szp, C.POINTER(NormalStats)]),
+    "ndt_diag_normals": (C.c_int, [vp, szp, szp, szp, szp]),
+    "ndt_host_normal_spec_check": (C.c_int, [C.POINTER(NormalSpec)]),
+    "ndt_host_normal_filter_check": (C.c_int, [C.POINTER(NormalFilter)]),
+    "ndt_host_normal_plan": (C.c_int, [C.c_size_t, ip, ip]),
+    "ndt_host_normal_from_sums": (C.c_int, [C.POINTER(NormalSpec), fp, C.c_int, dp, dp, fp, ip]),
+    "ndt_host_normal_keep": (C.c_int, [C.POINTER(NormalFilter), fp, ip]),
     "ndt_pose_covariance": (C.c_int, [vp, fp, C.c_int, C.c_double, dp, vp]),
     "ndt_pairs_pose_covariances": (C.c_int, [vp, fp, C.c_int, C.c_double, dp, vp]),
     "ndt_host_pose_covariance": (C.c_int, [dp, dp, dp, C.c_size_t, C.c_int, C.c_double, dp, dp, dp, ip]),

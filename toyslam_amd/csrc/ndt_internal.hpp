@@ -11,6 +11,7 @@
 //   ndt_nvtl.hip  : nearest-voxel transformation likelihood (of a cloud, of the source under one or many poses, per point)
 //   ndt_select.hip : selection of the points of resident clouds (finite, box, range, per-point value): kernels and C-ABI
 //   ndt_deskew.hip : motion compensation of resident scans by the time of every point: kernel and C-ABI
+//   ndt_normals.hip: surface normals and curvature of resident clouds (k-nearest / radius neighbourhoods): kernels and C-ABI
 //   ndt_cloud_ops.hip : what ndt_select / _deskew / _outliers / _plane.hip share on the host: the checks of an input cloud and
 //                    the parts of the entry preambles, the member table, output slices, the box-row fold, per-point doubles
 //   ndt_pose_cov.hip: 6x6 pose covariance (Laplace / sandwich) of the handle's pair and of the pairs of a pairs call
@@ -529,6 +530,8 @@ struct ndt_context {
   size_t pl_launches = 0, pl_select_launches = 0, pl_count_blocks = 0, pl_clouds = 0;
   // the cluster extraction (ndt_clusters.hip): what the last call that reached the device did (ndt_diag_clusters)
   size_t cl_index_builds = 0, cl_launches = 0, cl_link_blocks = 0, cl_scanned = 0, cl_cas_retries = 0;
+  // the normals (ndt_normals.hip): what the last call that reached the device did (ndt_diag_normals)
+  size_t nr_index_builds = 0, nr_launches = 0, nr_blocks = 0, nr_scanned = 0;
   // the motion compensation (ndt_deskew.hip): the page-locked block of a call -- its segment table on the way up, its per-block
   // rows (boxes, untimed count) on the way back -- and what the last call that reached the device did (ndt_diag_deskew)
   void* dsk_pinned = nullptr;

@@ -11,7 +11,8 @@
 //
 // Users: getFitnessScore (ndt_kernels.hip fitness_body: shells, wave_nearest); GICP (gicp_kernels.hip: team_knn for the
 // covariances, shells + nearer + wave_nearest for the correspondences); the outlier filters (ndt_outliers.hip: team_knn for
-// STATISTICAL, shells + wave_scan_all for RADIUS); the searches over voxel centroids (ndt_centroid_fitness.hip,
+// STATISTICAL, shells + wave_scan_all for RADIUS); the normals (ndt_normals.hip: team_knn, and the shells and the scan in
+// the forms that hand the visitor the record); the searches over voxel centroids (ndt_centroid_fitness.hip,
 // gicp_grid.hip: query_cell, axis_gap, team_min over their own tables).
 #pragma once
 #include "ndt_device.hpp"
@@ -68,6 +69,20 @@ __device__ __forceinline__ void scan_run(const float4* __restrict__ sp, unsigned
     visit(db, first + p1, v1);
   }
 }
+// the sibling whose visitor is also handed the record just loaded: visit(d, position, valid, record) -- for a visitor that
+// sums over the neighbours themselves (ndt_normals.hip); same loads, same order
+template <int TEAM = kTeam, class F>
+__device__ __forceinline__ void scan_run_pts(const float4* __restrict__ sp, unsigned first, int count, int sub, float qx, float qy,
+                                             float qz, F&& visit) {
+  for (int base = 0; base < count; base += 2 * TEAM) {
+    const int p0 = base + sub, p1 = p0 + TEAM;
+    const bool v0 = p0 < count, v1 = p1 < count;
+    const float4 a = sp[first + min(p0, count - 1)], b = sp[first + min(p1, count - 1)];
+    const float da = dist2_f32(qx, qy, qz, a.x, a.y, a.z), db = dist2_f32(qx, qy, qz, b.x, b.y, b.z);
+    visit(da, first + p0, v0, a);
+    visit(db, first + p1, v1, b);
+  }
+}
 
 // lexicographic minimum of (d, idx) over the 8 lanes of a team
 __device__ __forceinline__ void team_min(float& d, int& idx) {
@@ -99,7 +114,8 @@ __device__ __forceinline__ float axis_gap(float q, int cell_abs, float leaf, flo
   const float lo = static_cast<float>(cell_abs) * leaf, hi = lo + leaf;
   return fmaxf(fmaxf(lo - q, q - hi) - slack, 0.0f);
 }
-template <int TEAM = kTeam, class F>
+// PTS: consider(d, position, valid, record) -- scan_run_pts instead of scan_run
+template <int TEAM = kTeam, bool PTS = false, class F>
 __device__ __forceinline__ void team_shell(const PointIndex& ix, int ci, int cj, int ck, int r, int sub, float qx, float qy,
                                            float qz, F&& consider, float bound2 = INFINITY) {
   // (TEAM = 8: the team search; TEAM = 64: a whole wave on one query -- the far queries of getFitnessScore, whose shells
@@ -152,7 +168,8 @@ __device__ __forceinline__ void team_shell(const PointIndex& ix, int ci, int cj,
           found &= found - 1;
           const unsigned fs = __shfl(first, team_base + owner, kWave);
           const int fc = __shfl(count, team_base + owner, kWave);
-          scan_run<TEAM>(ix.sorted_pts, fs, fc, sub, qx, qy, qz, consider);
+          if constexpr (PTS) scan_run_pts<TEAM>(ix.sorted_pts, fs, fc, sub, qx, qy, qz, consider);
+          else scan_run<TEAM>(ix.sorted_pts, fs, fc, sub, qx, qy, qz, consider);
         }
       }
     }
@@ -195,6 +212,20 @@ __device__ __forceinline__ void wave_scan_all(const PointIndex& ix, float qx, fl
     visit(dist2_f32(qx, qy, qz, b.x, b.y, b.z), p1, p1 < count);
     visit(dist2_f32(qx, qy, qz, c.x, c.y, c.z), p2, p2 < count);
     visit(dist2_f32(qx, qy, qz, d.x, d.y, d.z), p3, p3 < count);
+  }
+}
+// the sibling whose visitor is also handed the record just loaded (see scan_run_pts)
+template <class F>
+__device__ __forceinline__ void wave_scan_all_pts(const PointIndex& ix, float qx, float qy, float qz, F&& visit) {
+  const int lane = threadIdx.x & (kWave - 1), count = ix.n_sorted;
+  for (int base = 0; base < count; base += 4 * kWave) {
+    const int p0 = base + lane, p1 = p0 + kWave, p2 = p1 + kWave, p3 = p2 + kWave;
+    const float4 a = ix.sorted_pts[min(p0, count - 1)], b = ix.sorted_pts[min(p1, count - 1)];
+    const float4 c = ix.sorted_pts[min(p2, count - 1)], d = ix.sorted_pts[min(p3, count - 1)];
+    visit(dist2_f32(qx, qy, qz, a.x, a.y, a.z), p0, p0 < count, a);
+    visit(dist2_f32(qx, qy, qz, b.x, b.y, b.z), p1, p1 < count, b);
+    visit(dist2_f32(qx, qy, qz, c.x, c.y, c.z), p2, p2 < count, c);
+    visit(dist2_f32(qx, qy, qz, d.x, d.y, d.z), p3, p3 < count, d);
   }
 }
 

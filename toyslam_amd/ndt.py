@@ -1229,6 +1229,125 @@ class NormalDistributionsTransform:
         """Is the _lib.ClusterSpec valid?  (ndt_host_cluster_spec_check; host only.)"""
         return _lib.lib().ndt_host_cluster_spec_check(C.byref(spec)) == _lib.NDT_OK
 
+    # ---- surface normals and curvature of resident clouds (ndt_cloud_estimate_normals / ndt_cloud_select_by_normals) ------
+    @staticmethod
+    def normalSpec(k=None, radius=None, min_neighbors=3, viewpoint=(0.0, 0.0, 0.0)):
+        """The ndt_normal_spec of the keyword form: the k nearest neighbours (the point itself included), or every point within
+        `radius`; fewer than min_neighbors members: no normal; normals point towards `viewpoint`."""
+        if (k is None) == (radius is None):
+            raise ValueError("give either k or radius")
+        s = _lib.NormalSpec()
+        s.method = _lib.NORMAL_KNN if k is not None else _lib.NORMAL_RADIUS
+        s.k, s.radius, s.min_neighbors = int(k or 0), float(np.float32(radius or 0.0)), int(min_neighbors)
+        s.viewpoint[:] = [float(v) for v in viewpoint]
+        return s
+
+    @staticmethod
+    def normalFilter(curvature=None, axis=None, cos=None, negate=False):
+        """The ndt_normal_filter of the keyword form: curvature = (lo, hi) keeps lo <= curvature <= hi; axis (a unit vector)
+        with cos = (lo, hi) keeps lo <= |n . axis| <= hi; negate inverts the outcome for the points that have a normal."""
+        f = _lib.NormalFilter()
+        if curvature is not None:
+            f.flags |= _lib.NORMAL_KEEP_CURVATURE
+            f.curvature_lo, f.curvature_hi = float(np.float32(curvature[0])), float(np.float32(curvature[1]))
+        if axis is not None:
+            f.flags |= _lib.NORMAL_KEEP_ANGLE
+            f.axis[:] = [float(v) for v in axis]
+            f.cos_lo, f.cos_hi = (0.0, 1.0) if cos is None else (float(cos[0]), float(cos[1]))
+        if negate:
+            f.flags |= _lib.NORMAL_KEEP_NEGATE
+        return f
+
+    @staticmethod
+    def _normal_stats(st):
+        return dict(n_finite=st.n_finite, n_valid=st.n_valid, n_collinear=st.n_collinear, max_neighbors=st.max_neighbors)
+
+    def estimateNormals(self, dc, k=None, radius=None, min_neighbors=3, viewpoint=(0.0, 0.0, 0.0), counts=True, device=False, spec=None):
+        """Unit normal and surface variation of every point of the resident cloud `dc` (ndt_cloud_estimate_normals; defined in
+        include/ndt_mi355.h).  -> (normals (n, 4) float32: nx, ny, nz, curvature -- four NaNs where there is no normal;
+        counts (n,) int32: the neighbours of every point, or None with counts=False; stats dict).
+        device: the address (an int) of 4 n float32 on the handle's device (with counts=True followed by n int32), which then
+        receives the outputs; the first entry is that address, the second the address of the counts or None."""
+        if spec is None:
+            spec = self.normalSpec(k, radius, min_neighbors, viewpoint)
+        n = len(dc)
+        st = _lib.NormalStats()
+        if device is not False and device is not None:
+            np_, cp = int(device), int(device) + 16 * n if counts else None
+            check(self._L.ndt_cloud_estimate_normals(self._h, dc._c, C.byref(spec), C.c_void_p(np_), C.c_void_p(cp) if counts else None, 1,
+                                                     C.byref(st)))
+            return np_, cp, self._normal_stats(st)
+        nr = np.zeros((max(n, 1), 4), dtype=np.float32)
+        ct = np.zeros(max(n, 1), dtype=np.int32) if counts else None
+        check(self._L.ndt_cloud_estimate_normals(self._h, dc._c, C.byref(spec), C.c_void_p(nr.ctypes.data),
+                                                 C.c_void_p(ct.ctypes.data) if counts else None, 0, C.byref(st)))
+        return nr[:n].copy(), ct[:n].copy() if counts else None, self._normal_stats(st)
+
+    def estimateNormalsClouds(self, clouds, k=None, radius=None, min_neighbors=3, viewpoint=(0.0, 0.0, 0.0), counts=True, spec=None):
+        """estimateNormals of every DeviceCloud of the list under one spec in ONE normals launch
+        (ndt_cloud_estimate_normals_clouds).  -> (list of (n_k, 4) float32, list of (n_k,) int32 or None, list of stats dicts),
+        entry k what estimateNormals gives for clouds[k] alone, the same bits."""
+        if spec is None:
+            spec = self.normalSpec(k, radius, min_neighbors, viewpoint)
+        clouds, n, arr = _handle_array(clouds)
+        sizes = [len(c) for c in clouds]
+        first = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        total = int(first[-1])
+        nr = np.zeros((max(total, 1), 4), dtype=np.float32)
+        ct = np.zeros(max(total, 1), dtype=np.int32) if counts else None
+        st = (_lib.NormalStats * max(n, 1))()
+        check(self._L.ndt_cloud_estimate_normals_clouds(self._h, arr, n, C.byref(spec), C.c_void_p(nr.ctypes.data),
+                                                        C.c_void_p(ct.ctypes.data) if counts else None, 0, st))
+        return ([nr[first[j]:first[j + 1]].copy() for j in range(n)],
+                [ct[first[j]:first[j + 1]].copy() for j in range(n)] if counts else None, [self._normal_stats(st[j]) for j in range(n)])
+
+    def selectByNormals(self, dc, spec, filter=None, indices=False):
+        """The points of the resident cloud `dc` whose normal record passes the _lib.NormalFilter (normalFilter(...); None: every
+        point that has a normal), in dc's order, as a new DeviceCloud with exact boxes (ndt_cloud_select_by_normals); normals
+        and keys stay on the device.
+        -> (DeviceCloud, stats dict); indices=True: (DeviceCloud, stats, (n_kept,) int32 indices of the kept points)."""
+        if filter is None:
+            filter = _lib.NormalFilter()
+        n = len(dc)
+        idx = np.zeros(max(n, 1), dtype=np.int32) if indices else None
+        c, nk, st = C.c_void_p(None), C.c_size_t(0), _lib.NormalStats()
+        check(self._L.ndt_cloud_select_by_normals(self._h, dc._c, C.byref(spec), C.byref(filter), C.byref(c),
+                                                  idx.ctypes.data_as(C.POINTER(C.c_int32)) if indices else None, C.byref(nk), C.byref(st)))
+        out = DeviceCloud(self, c)
+        return (out, self._normal_stats(st), idx[:nk.value].copy()) if indices else (out, self._normal_stats(st))
+
+    def selectByNormalsClouds(self, clouds, spec, filter=None):
+        """selectByNormals of every DeviceCloud of the list under one spec and filter: one normals launch and the selection's
+        two (ndt_cloud_select_by_normals_clouds).  -> (list of DeviceCloud, list of stats dicts), entry k what selectByNormals
+        gives for clouds[k] alone, the same bits."""
+        if filter is None:
+            filter = _lib.NormalFilter()
+        clouds, n, arr = _handle_array(clouds)
+        out, nk, st = _out_array(n), (C.c_size_t * max(n, 1))(), (_lib.NormalStats * max(n, 1))()
+        check(self._L.ndt_cloud_select_by_normals_clouds(self._h, arr, n, C.byref(spec), C.byref(filter), out, nk, st))
+        return self._wrap(out, n), [self._normal_stats(st[j]) for j in range(n)]
+
+    def normalDiag(self):
+        """What the last normals call that reached the device did (ndt_diag_normals)."""
+        return self._diag(self._L.ndt_diag_normals, "index_builds", "launches", "blocks", "scanned_queries")
+
+    @staticmethod
+    def normalPlan(n):
+        """(blocks, queries_per_block) of the normals kernel over a cloud of n points (ndt_host_normal_plan; host only)."""
+        b, q = C.c_int(0), C.c_int(0)
+        check(_lib.lib().ndt_host_normal_plan(int(n), C.byref(b), C.byref(q)))
+        return b.value, q.value
+
+    @staticmethod
+    def normalSpecCheck(spec):
+        """Is the _lib.NormalSpec valid?  (ndt_host_normal_spec_check; host only.)"""
+        return _lib.lib().ndt_host_normal_spec_check(C.byref(spec)) == _lib.NDT_OK
+
+    @staticmethod
+    def normalFilterCheck(filter):
+        """Is the _lib.NormalFilter valid?  (ndt_host_normal_filter_check; host only.)"""
+        return _lib.lib().ndt_host_normal_filter_check(C.byref(filter)) == _lib.NDT_OK
+
     # ---- pose covariance (ndt_pose_covariance / ndt_pairs_pose_covariances) ----------------------------------------------
     def poseCovariance(self, transform=None, method="sandwich", scale=1.0, info=False):
         """6x6 covariance of the pose x y z roll pitch yaw of the input source at `transform` (None: the last align's final
